@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — tracked frames/sec of the HIP hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: the headline and what follows
+from it without further GPU work. Every other leg described below (device_only, the synchronous latency,
+the roofline and per-kernel times, the secondary ingest legs, the one-tracker leg, byte_kernels and
+cpu_baseline) runs only with --full, after the timed steps; the --no-* options then leave single legs out.
+
+--dump-outputs DIR: right after the timed steps, rank 0 writes what the last timed step returned to its
+callers, one row per stream in stream order: DIR/bbox.npy (float64 [B, 4]: x, y, width, height),
+DIR/score.npy (float32 [B]) and DIR/success.npy (float32 [B], 1 or 0). Weights and clip are seeded, so
+the same arguments give the same inputs on every run and two builds can be compared output for output.
 
 N > 1 with no RANK in the environment: this process starts the N rank processes itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`), relays
@@ -18,12 +28,12 @@ the host maps the buffer, then tracks): the frames live in ordinary HOST memory 
 product's own ingest, vt_group_enqueue_host / vt_group_wait_next - each stream's search window is
 packed into a pinned arena and crosses PCIe on a copy stream while the previous pass runs.
 `device_only` (frames already resident in HBM, vt_group_enqueue_device) and `full_frame` (every
-3.1 MB frame copied whole) are measured beside it in the same run. value = tracked frames of ALL
+3.1 MB frame copied whole) are measured beside it in a --full run. value = tracked frames of ALL
 ranks / max-over-ranks wall time. Streams are independent (one frame chain each); ranks exchange
 nothing per frame - the only collective is the start-up weight broadcast (RCCL), outside the timed
 region, recorded under `collective`.
 
-Also on the JSON line: "roofline" for the dominant kernel (HIP events on the library's own stream,
+Also on the --full JSON line: "roofline" for the dominant kernel (HIP events on the library's own stream,
 algorithmic FLOPs / measured time against the 2.5 PFLOP/s dense bf16 MFMA peak), "byte_kernels"
 (HBM-bound kernels against 8 TB/s) and "cpu_baseline" (float32 torch-CPU forward on all host cores,
 oracle/cpu_fp32.py, rank 0, N = 1 only).
@@ -111,7 +121,34 @@ def parse_args(argv=None):
                     help="no GPU work: ranks rendezvous over gloo on the CPU, broadcast the weight blob, plan "
                          "their streams and aggregate synthetic timings (exercises the launcher, the collective "
                          "record and the aggregation; the JSON line says dry_run)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg too (device_only, latency, roofline, ingest legs, "
+                         "single stream, byte_kernels, cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's results (rank 0's streams) to DIR as .npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(path: str, results) -> None:
+    """what the callers of the timed path received in its last step (one TrackResult per stream, stream
+    order) as float arrays: DIR/bbox.npy float64 [B, 4], DIR/score.npy and DIR/success.npy float32 [B]"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "bbox.npy"), np.array([r.bbox for r in results], np.float64).reshape(-1, 4))
+    np.save(os.path.join(path, "score.npy"), np.array([r.score for r in results], np.float32))
+    np.save(os.path.join(path, "success.npy"), np.array([r.success for r in results], np.float32))
+
+
+def emit(out: dict, rank: int, world: int) -> None:
+    """rank 0 prints the one JSON line; every rank leaves the process group"""
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
 
 # ---- N > 1 without a launcher: start the ranks ourselves (no torch, no HIP in this process) ----------
@@ -237,15 +274,16 @@ def run_rank(args):
                                amp=3.8 * R / (2 * np.pi))
     host_t = torch.from_numpy(np.stack([sc.frame_nv12(t) for t in range(R)])).pin_memory()
     host = host_t.numpy()
-    clip = host_t.to(dev)
     fbytes = host.shape[1]
-    base = clip.data_ptr()
     phase = plan["phase"]
     frames_at = []
-    for t in range(R):
-        frames_at.append([vt.frame_nv12(base + ((t + phase[i]) % R) * fbytes,
-                                        base + ((t + phase[i]) % R) * fbytes + fw * fh, fw, fh)
-                          for i in range(B)])
+    if args.full or args.ingest == "device":    # the HBM copy: only the device-ingest headline and --full legs read it
+        clip = host_t.to(dev)
+        base = clip.data_ptr()
+        for t in range(R):
+            frames_at.append([vt.frame_nv12(base + ((t + phase[i]) % R) * fbytes,
+                                            base + ((t + phase[i]) % R) * fbytes + fw * fh, fw, fh)
+                              for i in range(B)])
     hclip = [vt.NV12Frame(host[t], fw, fh) for t in range(R)]      # the same frames as host buffers
 
     def host_frames_for(gi, t):
@@ -304,7 +342,7 @@ def run_rank(args):
         barrier()
         dt = time.perf_counter() - t0
         ok, miou = check_tracking(res, W_ + K_, W_ + K_)
-        return dt, ok, miou, enqueue_all, wait_all
+        return dt, ok, miou, res, enqueue_all, wait_all
 
     def timed_host(K_, W_, pipelined=True):
         """frames in host memory through the product's ingest; one host thread per engine (as a host
@@ -371,16 +409,16 @@ def run_rank(args):
         [x.join() for x in th]
         res = [r for g in range(G) for r in results[g]]
         ok, miou = check_tracking(res, W_ + K_, W_ + K_)
-        return dt, bool(ok and all(oks)), miou
+        return dt, bool(ok and all(oks)), miou, res
 
     # ---- headline ------------------------------------------------------------------------------------
     if args.ingest == "host":
-        dt_local, tracked_ok, miou = timed_host(K, W)
+        dt_local, tracked_ok, miou, last = timed_host(K, W)
         ingest_text = ("host memory -> vt_group_enqueue_host / vt_group_wait_next: every stream's search window "
                        "(speculative: 1.75x the crop side) packed into one of two pinned arenas, one H2D copy per "
                        "engine and step on a copy stream, overlapping the previous pass (H2D-inclusive)")
     else:
-        dt_local, tracked_ok, miou, _, _ = timed_device(K, W)
+        dt_local, tracked_ok, miou, last, _, _ = timed_device(K, W)
         ingest_text = "frames resident in HBM (vt_group_enqueue_device)"
     agg = vd.aggregate_throughput(B * K, dt_local, device=dev if world > 1 else "cpu")
     dt, total_frames, fps = agg["seconds"], agg["frames"], agg["frames_per_s"]
@@ -409,10 +447,14 @@ def run_rank(args):
         "encoder_gflop_per_frame": mi.encoder_flops_per_frame / 1e9,
         "whole_frame_mfma_frac": fps / world * mi.flops_per_frame / 1e12 / PEAK_BF16_TFLOPS,
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    if not args.full:       # a plain run: the headline and nothing that needs more GPU work
+        return emit(out, rank, world)
 
     # ---- device_only: the same engines on frames already resident in HBM (today's `value` until round 3) ----
     if args.ingest == "host":
-        ddt, dok, dmiou, enqueue_all, wait_all = timed_device(K, W)
+        ddt, dok, dmiou, _, enqueue_all, wait_all = timed_device(K, W)
         dagg = vd.aggregate_throughput(B * K, ddt, device=dev if world > 1 else "cpu")
         out["device_only"] = {
             "value": dagg["frames_per_s"], "unit": "frames/s", "ms_per_step": dagg["seconds"] / K * 1e3,
@@ -421,7 +463,7 @@ def run_rank(args):
             "whole_frame_mfma_frac": dagg["frames_per_s"] / world * mi.flops_per_frame / 1e12 / PEAK_BF16_TFLOPS,
             "headline_vs_device_only": fps / dagg["frames_per_s"]}
     else:
-        _, _, _, enqueue_all, wait_all = timed_device(0, 2)
+        _, _, _, _, enqueue_all, wait_all = timed_device(0, 2)
 
     # ---- synchronous single-call latency (the literal drop-in call pattern), device-resident frames ------
     lat = []
@@ -509,11 +551,11 @@ def run_rank(args):
     if not args.no_host_leg and rank == 0 and world == 1:
         hs = args.host_steps
         # (a) the synchronous form of the headline ingest (vt_group_update_host): no overlap
-        sdt, sok, _ = timed_host(hs, 3, pipelined=False)
+        sdt, sok, _, _ = timed_host(hs, 3, pipelined=False)
         out["host_synchronous"] = {"value": B * hs / sdt, "unit": "frames/s", "tracked_ok": sok,
                                    "ingest": "vt_group_update_host: pack + H2D + pass, one call per step"}
         if args.ingest != "host":
-            hdt, hok, _ = timed_host(hs, 3, pipelined=True)
+            hdt, hok, _, _ = timed_host(hs, 3, pipelined=True)
             out["pcie_inclusive"] = {"value": B * hs / hdt, "unit": "frames/s", "tracked_ok": hok}
         # (b) full frames: every stream's WHOLE NV12 frame crosses PCIe every step, what a host that maps
         # the whole buffer pays (/root/reference/src/pipeline.rs:95-106). The streams of an engine sit at
@@ -595,7 +637,7 @@ def run_rank(args):
         hm = vt.HostMapping(np.array(host))          # a pageable copy: torch's pinned tensor is registered already
         zframes = [[vt.frame_nv12(hm.d_ptr + ((t + phase[i]) % R) * fbytes, hm.d_ptr + ((t + phase[i]) % R) * fbytes + fw * fh,
                                   fw, fh) for i in range(B)] for t in range(R)]
-        zdt, zok, zmiou, _, _ = timed_device(hs, 5, fa=zframes)
+        zdt, zok, zmiou, _, _, _ = timed_device(hs, 5, fa=zframes)
         out["zero_copy"] = {
             "value": B * hs / zdt, "unit": "frames/s", "ms_per_step": zdt / hs * 1e3, "tracked_ok": zok,
             "min_iou_vs_truth": zmiou, "vs_headline": (B * hs / zdt) / (fps / world),
@@ -746,10 +788,7 @@ def run_rank(args):
             "nv12_full_frame_convert_ms_by_threads": conv,
         }
 
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+    emit(out, rank, world)
 
 
 def dry_run(args, vt, vd, world, rank, cfg_name, wl_text, affinity):

@@ -1,12 +1,14 @@
 """bench.py's driver-facing contract, end to end on the GPU (a short run): ONE JSON line on stdout with
 the fields the task statement names - metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config.workload - plus the `roofline` and
-`cpu_baseline` objects, and the consistency relations between them."""
+higher_is_better / scaling / vs_baseline / dtype / data / config.workload - plus, with --full, the `roofline`
+and `cpu_baseline` objects, and the consistency relations between them; a plain run's line and the outputs
+--dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +25,7 @@ def _run(*args):
 
 
 def test_bench_line_has_the_contract_fields_and_is_self_consistent():
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--host-steps", "10")
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--host-steps", "10", "--full")
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"] and d["unit"] == "frames/s"
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5
@@ -74,9 +76,35 @@ def test_bench_gpus_2_on_one_gpu_fails_from_inside_the_ranks():
 
 
 def test_bench_single_stream_and_planned_engines():
-    d = _run("--streams", "1", "--groups", "1", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-host-leg",
-             "--no-profile")
-    assert d["config"]["engine_sizes"] == [1] and d["tracked_ok"] and "roofline" not in d and "cpu_baseline" not in d
-    d = _run("--streams", "33", "--engines", "auto", "--steps", "10", "--warmup", "3", "--no-cpu-baseline",
+    d = _run("--streams", "1", "--groups", "1", "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline",
              "--no-host-leg", "--no-profile")
+    assert d["config"]["engine_sizes"] == [1] and d["tracked_ok"] and "roofline" not in d and "cpu_baseline" not in d
+    d = _run("--streams", "33", "--engines", "auto", "--steps", "10", "--warmup", "3", "--full",
+             "--no-cpu-baseline", "--no-host-leg", "--no-profile")
     assert d["config"]["engine_sizes"] == [30, 3] and d["tracked_ok"]
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """the plain run: the headline fields, none of the --full legs, exactly --steps timed steps after --warmup
+    (tracked_ok checks that every stream did warmup + steps updates), and the last step's results as .npy -
+    identical on a second run with the same arguments"""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _run("--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(out))
+        assert d["steps"] == 7 and d["warmup"] == 3 and d["unit"] == "frames/s" and d["dtype"] == "bf16"
+        assert d["higher_is_better"] is True and d["tracked_ok"] is True
+        B = d["config"]["streams_per_gpu"]
+        assert abs(d["value"] - B * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        for k in ("device_only", "sync_update_latency_ms", "sync_update_latency_p99_ms", "reference_style", "roofline",
+                  "kernels", "eager_event_ms_per_step", "host_synchronous", "pcie_inclusive", "full_frame", "zero_copy",
+                  "single_stream", "byte_kernels", "cpu_baseline"):
+            assert k not in d, k
+        z = {n: np.load(out / f"{n}.npy") for n in ("bbox", "score", "success")}
+        assert z["bbox"].shape == (B, 4) and z["bbox"].dtype == np.float64
+        assert z["score"].shape == (B,) and z["score"].dtype == np.float32
+        assert z["success"].dtype == np.float32 and (z["success"] == 1).all()
+        assert (z["bbox"][:, 2:] > 0).all() and (z["score"] > 0).all()
+        dumps.append(z)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

@@ -8,9 +8,9 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 O=gpurun_out/r06
 mkdir -p $O
 if [ "${PART:-1}" = "1" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_30x1 -- python3 bench.py --steps 60 --warmup 10 --streams 30 --groups 1 --no-cpu-baseline --no-host-leg --no-single-leg > $O/trace_30x1.json 2> $O/trace_30x1.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_30x1 -- python3 bench.py --steps 60 --warmup 10 --streams 30 --groups 1 --full --no-cpu-baseline --no-host-leg --no-single-leg > $O/trace_30x1.json 2> $O/trace_30x1.err
 echo "trace 30x1 done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_60x2 -- python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-host-leg --no-single-leg > $O/trace_60x2.json 2> $O/trace_60x2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_60x2 -- python3 bench.py --steps 60 --warmup 10 --full --no-cpu-baseline --no-host-leg --no-single-leg > $O/trace_60x2.json 2> $O/trace_60x2.err
 echo "trace 60x2 done"
 fi
 if [ "${PART:-1}" = "1" ] || [ "${PART:-1}" = "4" ]; then     # PMC passes of the dominant kernel (PART=4: these alone)
@@ -35,16 +35,16 @@ echo "pmc done ($SHA)"
 find $O -name "*kernel_stats.csv" | head
 fi
 if [ "${PART:-1}" = "2" ]; then
-python3 bench.py > $O/bench_cfg3_60x2.json 2> $O/bench_cfg3_60x2.err
+python3 bench.py --full > $O/bench_cfg3_60x2.json 2> $O/bench_cfg3_60x2.err
 echo "bench default done"
-python3 bench.py --streams 30 --groups 1 --no-cpu-baseline --no-host-leg --no-single-leg > $O/bench_cfg3_30x1.json 2>> $O/bench.err
-python3 bench.py --workload cfg2 --no-cpu-baseline --no-single-leg > $O/bench_cfg2.json 2>> $O/bench.err
-python3 bench.py --workload cfg5 --steps 100 --no-cpu-baseline --no-single-leg > $O/bench_cfg5.json 2>> $O/bench.err
-python3 bench.py --streams 1 --groups 1 --steps 1000 --warmup 100 --no-cpu-baseline --no-host-leg --no-single-leg > $O/bench_cfg4_literal_n1.json 2>> $O/bench.err
+python3 bench.py --streams 30 --groups 1 --full --no-cpu-baseline --no-host-leg --no-single-leg > $O/bench_cfg3_30x1.json 2>> $O/bench.err
+python3 bench.py --workload cfg2 --full --no-cpu-baseline --no-single-leg > $O/bench_cfg2.json 2>> $O/bench.err
+python3 bench.py --workload cfg5 --steps 100 --full --no-cpu-baseline --no-single-leg > $O/bench_cfg5.json 2>> $O/bench.err
+python3 bench.py --streams 1 --groups 1 --steps 1000 --warmup 100 --full --no-cpu-baseline --no-host-leg --no-single-leg > $O/bench_cfg4_literal_n1.json 2>> $O/bench.err
 echo "benches done"
 fi
-if [ "${PART:-1}" = "3" ]; then     # the driver's exact command, three times
-for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd_$i.json 2>> $O/driver_cmd.err; done
+if [ "${PART:-1}" = "3" ]; then     # the driver's command three times, with --full for the roofline read below
+for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_cmd_$i.json 2>> $O/driver_cmd.err; done
 python3 - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r06/driver_cmd_*.json")):
