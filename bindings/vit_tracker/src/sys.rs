@@ -181,6 +181,11 @@ extern "C" {
     pub fn vt_group_update_host(g: *mut vt_group, host_frames: *const VtFrame, n: c_int, out: *mut VtResult) -> c_int;
     pub fn vt_group_enqueue_host(g: *mut vt_group, host_frames: *const VtFrame, n: c_int) -> c_int;
     pub fn vt_group_wait_next(g: *mut vt_group, out: *mut VtResult, n: c_int) -> c_int;
+    pub fn vt_group_enqueue_device_streams(g: *mut vt_group, streams: *const i32, frames: *const VtFrame, n: c_int) -> c_int;
+    pub fn vt_group_update_device_streams(g: *mut vt_group, streams: *const i32, frames: *const VtFrame, n: c_int,
+                                          out: *mut VtResult) -> c_int;
+    pub fn vt_group_update_host_streams(g: *mut vt_group, streams: *const i32, host_frames: *const VtFrame, n: c_int,
+                                        out: *mut VtResult) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

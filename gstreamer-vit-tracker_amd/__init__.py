@@ -92,7 +92,7 @@ EXPORTS = [
     "vt_group_host_redos", "vt_group_graph_captures", "vt_nv12_to_rgb8", "vt_nv12_to_rgb8_device", "vt_nv12_to_rgb8_batch_device", "vt_overlay_nv12", "vt_overlay_nv12_device", "vt_overlay_rgb8",
     "vt_overlay_rgb8_device",
     "vt_group_profile_device", "vt_group_enable_taps", "vt_group_set_tuning", "vt_group_set_state_box", "vt_tracker_as_group",
-    "vt_group_read_tensor",
+    "vt_group_read_tensor", "vt_group_enqueue_device_streams", "vt_group_update_device_streams", "vt_group_update_host_streams",
     "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob",
 ]
 # every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
@@ -164,6 +164,9 @@ def lib():
     L.vt_group_update_host.argtypes = [c_void_p, POINTER(CFrame), c_int, POINTER(CResult)]
     L.vt_group_enqueue_host.argtypes = [c_void_p, POINTER(CFrame), c_int]
     L.vt_group_wait_next.argtypes = [c_void_p, POINTER(CResult), c_int]
+    L.vt_group_enqueue_device_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int]
+    L.vt_group_update_device_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int, POINTER(CResult)]
+    L.vt_group_update_host_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int, POINTER(CResult)]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -577,20 +580,40 @@ class Group:
         arr = (CFrame * len(frames))(*frames)
         return arr
 
-    def enqueue_device(self, frames):
+    @staticmethod
+    def _streams(streams, n):
+        """int32 array of a subset pass's stream indices (the library checks them)"""
+        s = [int(i) for i in streams]
+        if len(s) != n:
+            raise VtError(-1, f"{len(s)} stream indices for {n} frames")
+        return (c_int32 * max(n, 1))(*s)
+
+    def enqueue_device(self, frames, streams=None):
+        """one pass; streams=None: all streams (frames[i] feeds stream i), else frames[i] feeds streams[i]
+        and no other stream is touched (vt_group_enqueue_device_streams)"""
         arr = self._arr(frames)
-        _check(lib().vt_group_enqueue_device(self._h, arr, len(frames)))
+        if streams is None:
+            _check(lib().vt_group_enqueue_device(self._h, arr, len(frames)))
+        else:
+            _check(lib().vt_group_enqueue_device_streams(self._h, self._streams(streams, len(frames)), arr, len(frames)))
+        self._last_n = len(frames)
 
     def wait(self):
-        n = self.streams
+        """results of the last pass, as many as it had streams, in its order"""
+        n = getattr(self, "_last_n", None) or self.streams
         out = (CResult * n)()
         _check(lib().vt_group_wait(self._h, out, n))
         return [TrackResult(r) for r in out]
 
-    def update_device(self, frames):
+    def update_device(self, frames, streams=None):
         arr = self._arr(frames)
         out = (CResult * len(frames))()
-        _check(lib().vt_group_update_device(self._h, arr, len(frames), out))
+        if streams is None:
+            _check(lib().vt_group_update_device(self._h, arr, len(frames), out))
+        else:
+            _check(lib().vt_group_update_device_streams(self._h, self._streams(streams, len(frames)), arr, len(frames),
+                                                        out))
+        self._last_n = len(frames)
         return [TrackResult(r) for r in out]
 
     @staticmethod
@@ -612,13 +635,17 @@ class Group:
         f, keep = self._host_frame(frame)
         _check(lib().vt_group_init_host(self._h, stream, byref(f), bbox._c()))
 
-    def update_host(self, frames):
-        """one pass on HOST frames (RGB arrays / NV12Frame / YUY2Frame, one per stream): only the
-        search windows cross PCIe, in one copy"""
+    def update_host(self, frames, streams=None):
+        """one pass on HOST frames (RGB arrays / NV12Frame / YUY2Frame, one per stream - or one per
+        listed stream with `streams`): only the search windows cross PCIe, in one copy"""
         pairs = [self._host_frame(fr) for fr in frames]
         arr = (CFrame * len(pairs))(*[p[0] for p in pairs])
         out = (CResult * len(pairs))()
-        _check(lib().vt_group_update_host(self._h, arr, len(pairs), out))
+        if streams is None:
+            _check(lib().vt_group_update_host(self._h, arr, len(pairs), out))
+        else:
+            _check(lib().vt_group_update_host_streams(self._h, self._streams(streams, len(pairs)), arr, len(pairs), out))
+        self._last_n = len(pairs)
         return [TrackResult(r) for r in out]
 
     def enqueue_host(self, frames):
@@ -628,6 +655,7 @@ class Group:
         pairs = [self._host_frame(fr) for fr in frames]
         arr = (CFrame * len(pairs))(*[p[0] for p in pairs])
         _check(lib().vt_group_enqueue_host(self._h, arr, len(pairs)))
+        self._last_n = None       # pipelined passes cover every stream
         if not hasattr(self, "_keep") or self._keep is None:
             self._keep = {}
         self._keep[self._keep.get("seq", 0)] = pairs

@@ -61,9 +61,10 @@ __device__ __forceinline__ bool hc_better(float ra, int ia, float rb, int ib) { 
 // terms in vto_decode's order (dy, dx ascending: bit-identical to the serial form) and writes the result. s_win:
 // 9 x 5 floats + 1 (the argmax cell's score logit) of LDS; every thread of the block calls this (one barrier).
 // pre / pre_po (thread 0 only, may be null): the stream's state and the pass's output addresses as fetched earlier
-// (nothing else writes them during the launch).
+// (nothing else writes them during the launch). b: the slot (logits, results); sb: the stream it works for (state),
+// = a.slot_stream[b] in a subset pass, b otherwise - read by thread 0 only.
 template <bool SC1, bool PRE = false>
-__device__ __forceinline__ void decode_box(const DecodeArgs& a, int b, int idx, int tid, float* s_win,
+__device__ __forceinline__ void decode_box(const DecodeArgs& a, int b, int sb, int idx, int tid, float* s_win,
                                            const StreamState& pre = StreamState{}, const PassOut& pre_po = PassOut{}) {
     const int grid = a.grid, ns = a.ns;
     const int bx = idx % grid, by = idx / grid;
@@ -91,7 +92,7 @@ __device__ __forceinline__ void decode_box(const DecodeArgs& a, int b, int idx, 
     __syncthreads();
     if (tid != 0) return;
     StreamState s;
-    if constexpr (PRE) s = pre; else s = a.states[b];
+    if constexpr (PRE) s = pre; else s = a.states[sb];
     const float score = hc_sigmoid(s_win[45]);
     float sw = 0.0f, scx = 0.0f, scy = 0.0f, sbw = 0.0f, sbh = 0.0f;
     for (int j = 0; j < 9; ++j) {
@@ -143,8 +144,8 @@ __device__ __forceinline__ void decode_box(const DecodeArgs& a, int b, int idx, 
     PassOut po;
     if constexpr (PRE) po = pre_po; else po = *a.out;
     if (po.host_results) po.host_results[b] = r;
-    if (po.host_states) po.host_states[b] = s;
-    a.states[b] = s;
+    if (po.host_states) po.host_states[sb] = s;
+    a.states[sb] = s;
     __threadfence_system();
 }
 
@@ -176,7 +177,7 @@ __device__ __forceinline__ void decode_stream(const DecodeArgs& a, int b, int ti
     }
     const int idx = s_idx[0];
     __syncthreads();
-    decode_box<SC1>(a, b, idx, tid, s_win);
+    decode_box<SC1>(a, b, a.slot_stream ? a.slot_stream[b] : b, idx, tid, s_win);
 }
 
 // one block per stream: the decode as a launch of its own (head_out written by an earlier launch)
@@ -579,11 +580,15 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
     // last: fetched here by thread 0 with inline-asm loads (hipcc would sink plain loads to their use - a dependent round
     // trip at the very end of the pass - or, hoisted above the main loop, spill them around it), consumed behind the
     // ticket; nothing else writes them during this launch.
+    // The stream of a subset pass's slot comes from the pass's map through an ORDINARY load: the compiler waits for it
+    // itself before the address it feeds; it is not one of the hand-counted asm loads.
     uint2 pre_s[11], pre_o[2];                     // 8-B loads: both structs are 8-B aligned in their arrays
     static_assert(sizeof(StreamState) == 88 && sizeof(PassOut) == 16, "prefetch layout");
+    int sb = b;                                    // thread 0: the stream this slot works for
     if constexpr (TAIL) {
         if (tid == 0) {
-            const char* sp = reinterpret_cast<const char*>(dec.states + b);
+            if (dec.slot_stream) sb = dec.slot_stream[b];
+            const char* sp = reinterpret_cast<const char*>(dec.states + sb);
             const char* op = reinterpret_cast<const char*>(dec.out);
 #pragma unroll
             for (int i = 0; i < 11; ++i) asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(pre_s[i]) : "v"(sp + 8 * i) : "memory");
@@ -722,7 +727,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
             const uint32_t q[4] = {pre_o[0].x, pre_o[0].y, pre_o[1].x, pre_o[1].y};
             __builtin_memcpy(&pre_po, q, 16);
         }
-        decode_box<true, true>(dec, b, idx, tid, reinterpret_cast<float*>(smem + 64), pre_state, pre_po);
+        decode_box<true, true>(dec, b, sb, idx, tid, reinterpret_cast<float*>(smem + 64), pre_state, pre_po);
     }
 }
 

@@ -306,10 +306,11 @@ __global__ __launch_bounds__(256) void preproc_kernel(const FrameDesc* __restric
                                                       int size, int patch, int kpad, int ntok,
                                                       int row_off, float factor, float na0,
                                                       float na1, float na2, float nb0, float nb1,
-                                                      float nb2, int is_template) {
-    const int b = b0 + blockIdx.y;
+                                                      float nb2, int is_template,
+                                                      const int32_t* __restrict__ slot_stream) {
+    const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
-    StreamState& s = states[b];
+    StreamState& s = states[slot_stream ? slot_stream[b] : b];     // the stream it works for (null map: the slot)
     // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
     const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
     const float area = bw * bh;
@@ -368,10 +369,11 @@ __global__ __launch_bounds__(256) void preproc_wide_kernel(const FrameDesc* __re
                                                            int size, int patch, int kpad, int ntok,
                                                            int row_off, float factor, float na0,
                                                            float na1, float na2, float nb0, float nb1,
-                                                           float nb2, int is_template) {
-    const int b = b0 + blockIdx.y;
+                                                           float nb2, int is_template,
+                                                           const int32_t* __restrict__ slot_stream) {
+    const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
-    StreamState& s = states[b];
+    StreamState& s = states[slot_stream ? slot_stream[b] : b];     // the stream it works for (null map: the slot)
     // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
     const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
     const float area = bw * bh;
@@ -475,12 +477,13 @@ __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __re
                                                            int size, int patch, int kpad, int ntok,
                                                            int row_off, float factor, float na0,
                                                            float na1, float na2, float nb0, float nb1,
-                                                           float nb2, int is_template) {
+                                                           float nb2, int is_template,
+                                                           const int32_t* __restrict__ slot_stream) {
     __shared__ uint32_t src[LDSPX];
     constexpr int PX = 8;
-    const int b = b0 + blockIdx.y;
+    const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
-    StreamState& s = states[b];
+    StreamState& s = states[slot_stream ? slot_stream[b] : b];     // the stream it works for (null map: the slot)
     // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
     const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
     const float area = bw * bh;
@@ -648,12 +651,13 @@ int preproc_tier_for_box(const ModelDims& d, float w, float h, bool is_template)
 }
 
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
-                          const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier) {
+                          const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
+                          const int32_t* slot_stream) {
     const int size = is_template ? d.T : d.S;
     const int row_off = is_template ? 0 : d.nt;
     const float factor = is_template ? 2.0f : 4.0f;
 #define PRE_ARGS frames, states, patches, b0, size, d.patch, d.kpad, d.ntok, row_off, factor, d.norm_a[0], \
-                 d.norm_a[1], d.norm_a[2], d.norm_b[0], d.norm_b[1], d.norm_b[2], is_template ? 1 : 0
+                 d.norm_a[1], d.norm_a[2], d.norm_b[0], d.norm_b[1], d.norm_b[2], is_template ? 1 : 0, slot_stream
     // store alignment: a run starts at element c*p*p + py*p + px0 of a row of kpad elements
     if (d.patch % 8 == 0 && d.kpad % 8 == 0 && size % PRE_TILE_W == 0 && size % PRE_TILE_H == 0) {
         dim3 grid((size / PRE_TILE_W) * (size / PRE_TILE_H), nb);   // 64 x 32 output tiles, source staged in LDS
@@ -671,5 +675,31 @@ hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* 
         vt_launch(preproc_kernel, grid, dim3(256), 0, st, PRE_ARGS);
     }
 #undef PRE_ARGS
+    return hipGetLastError();
+}
+
+// ---- template rows of a subset pass -----------------------------------------------------------------------------
+// A pass over a chosen subset of the streams runs on n compacted slots: slot i's template rows (the first nt rows of
+// segment i of the patch matrix, which the patch embedding re-embeds every pass) must be those of stream
+// slot_stream[i]. init writes every stream's rows to a store of their own (tpl[B][nt][kpad]); this copies them in,
+// 16 B per lane (kpad % 64 == 0: every row is a whole number of 16-B pieces, both sides 16-B aligned).
+// grid: (ceil(nt * kpad / 8 / 256), n).
+__global__ __launch_bounds__(256) void gather_template_rows_kernel(const bf16_t* __restrict__ tpl, bf16_t* __restrict__ patches,
+                                                                   const int32_t* __restrict__ slot_stream, int pieces,
+                                                                   int seg_elems, int tpl_elems) {
+    const int i = blockIdx.y;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pieces) return;
+    const u32x4_t* src = reinterpret_cast<const u32x4_t*>(tpl + (size_t)slot_stream[i] * tpl_elems);
+    u32x4_t* dst = reinterpret_cast<u32x4_t*>(patches + (size_t)i * seg_elems);
+    dst[p] = src[p];
+}
+
+hipError_t launch_gather_template_rows(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream, int n,
+                                       const ModelDims& d, hipStream_t st) {
+    if (n < 1 || !tpl || !patches || !slot_stream || d.kpad % 8) return hipErrorInvalidValue;
+    const int pieces = d.nt * d.kpad / 8;
+    vt_launch(gather_template_rows_kernel, dim3((pieces + 255) / 256, n), dim3(256), 0, st, tpl, patches, slot_stream,
+              pieces, d.ntok * d.kpad, d.nt * d.kpad);
     return hipGetLastError();
 }

@@ -287,6 +287,18 @@ int vt_group_update_device(vt_group* g, const vt_frame* frames, int n, vt_result
     if (int rc = g->e->enqueue(frames, n)) return rc;
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
+int vt_group_enqueue_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (int rc = refuse_while_pipelined(g->e, "enqueue_device_streams")) return rc;
+    return g->e->enqueue_streams(streams, frames, n);
+} VT_NOTHROW_INT
+int vt_group_update_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n,
+                                   vt_result* out) try {
+    if (!g || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    if (int rc = refuse_while_pipelined(g->e, "update_device_streams")) return rc;
+    if (int rc = g->e->enqueue_streams(streams, frames, n)) return rc;
+    return g->e->wait(out, n);
+} VT_NOTHROW_INT
 void* vt_group_hip_stream(vt_group* g) { return g ? (void*)g->e->stream : nullptr; }
 
 int vt_group_enable_taps(vt_group* g, int enable) try {
@@ -353,9 +365,12 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
     *(PassOut*)(hf + e->B) = PassOut{e->h_results, e->h_states_all};
     HIPCHK(hipMemcpyAsync(e->d_frames, hf, e->frames_block_bytes(), hipMemcpyHostToDevice, e->stream));
     Profiler prof;
+    if (int rc = e->restore_segments()) return rc;      // a full pass: every stream's template rows in its own segment
+    e->pass_n = e->B;
+    e->pass_streams.clear();
     e->crop_tier = e->pick_crop_tier();
     for (int it = 0; it < iters; ++it)
-        if (int rc = e->run_pass(&prof)) return rc;
+        if (int rc = e->run_pass(&prof, e->B, nullptr)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     for (auto& r : prof.recs) {
         float ms = 0;
@@ -429,10 +444,16 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         return set_err(VT_ERR_HIP, "read_tensor: sync failed");
     const ModelDims& d = e->d;
     const std::string n(name);
-    const size_t b = (size_t)stream;
+    // every tensor but the stream's state and the replay counters belongs to the last pass: the stream's slot in it
+    size_t b = (size_t)stream;
+    if (n != "state" && n != "graph_replays") {
+        const int slot = e->slot_of(stream);
+        if (slot < 0) return set_err(VT_ERR_INVALID_ARG, "read_tensor: stream %d was not in the last pass", stream);
+        b = (size_t)slot;
+    }
     if (n == "patches") return copy_out_bf16(e->d_patches + b * d.ntok * d.kpad, (int64_t)d.ntok * d.kpad, out, capacity);
     if (n == "feat" && e->feat_in_head) {       // the pass normalised the rows inside the head's first kernel: same arithmetic, now
-        HIPCHK(e->final_layernorm());        // as a launch (the residual stream of the last pass is still in place)
+        HIPCHK(e->final_layernorm(e->pass_n));        // as a launch (the residual stream of the last pass is still in place)
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     if (n == "feat") return copy_out_bf16(e->d_feat + b * d.ns * d.D, (int64_t)d.ns * d.D, out, capacity);
@@ -456,7 +477,7 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
     else if (n.rfind("layer", 0) == 0) slot = 1 + atoi(n.c_str() + 5);
     if (slot >= 0 && slot <= d.L) {
         if (!e->d_taps) return set_err(VT_ERR_INVALID_ARG, "taps not enabled (vt_group_enable_taps)");
-        const size_t M = (size_t)e->B * d.ntok;
+        const size_t M = (size_t)e->pass_n * d.ntok;      // the taps of the last pass: [hi | lo8] of its n slots
         const uint8_t* base = e->d_taps + (size_t)slot * e->tap_slot_bytes();
         const bf16_t* hi = reinterpret_cast<const bf16_t*>(base) + b * d.ntok * d.D;
         const uint8_t* lo = base + sizeof(bf16_t) * M * d.D + b * d.ntok * d.D;

@@ -179,10 +179,16 @@ hipError_t attention_prepare();   // once per device, before the first launch / 
 hipError_t launch_attention_mode(const bf16_t* qk, const bf16_t* vt, bf16_t* out, int B, int tokens,
                                  int H, int npad, int mode, hipStream_t st);
 
-// crop + bilinear + normalise -> patch rows; one launch covers streams [b0, b0+nb)
+// crop + bilinear + normalise -> patch rows; one launch covers slots [b0, b0+nb)
 // tier: the tile kernel's LDS buffer (0: 16 KiB, 1: 32 KiB, 2 or more: 64 KiB), a choice of speed only
+// slot_stream (device, [nb + b0] or null = identity): the stream a slot works for. Frame descriptor and patch rows are
+// the slot's; the StreamState read (and its geo / frame_w / frame_h / window_miss written) is the stream's.
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
-                          const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier = 0);
+                          const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier = 0,
+                          const int32_t* slot_stream = nullptr);
+// subset passes: slot i's template rows [nt][kpad] of the patch matrix <- the template store tpl[slot_stream[i]]
+hipError_t launch_gather_template_rows(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream, int n,
+                                       const ModelDims& d, hipStream_t st);
 int preproc_tier_for_box(const ModelDims& d, float w, float h, bool is_template);
 
 hipError_t launch_nv12_to_rgb8(const uint8_t* nv12, int w, int h, uint8_t* rgb, hipStream_t st);
@@ -203,8 +209,8 @@ hipError_t launch_overlay_rgb(uint8_t* rgb, int width, int height, int stride, c
 // stores to directly (no device-to-host copy on the stream). Uploaded with the frame descriptors of
 // the pass, right behind them in the same buffer.
 struct PassOut {
-    vt_result* host_results;    // [B] or null
-    StreamState* host_states;   // [B] or null
+    vt_result* host_results;    // [slots of the pass] or null
+    StreamState* host_states;   // [B] (by stream) or null
 };
 
 struct DecodeArgs {
@@ -216,7 +222,10 @@ struct DecodeArgs {
     StreamState* states;    // [B]
     vt_result* results;     // [B] (device)
     const PassOut* out;     // device copy of this pass's PassOut
-    int B, ns, grid, C;
+    // [B] slot -> stream of a subset pass (null: the identity, every full pass). head_out, results and
+    // out->host_results are indexed by slot; states and out->host_states by stream.
+    const int32_t* slot_stream;
+    int B, ns, grid, C;     // B: slots of the pass
     float success_threshold;
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t st);     // head_out_kernel + decode_kernel (two launches)

@@ -34,7 +34,7 @@ void Engine::destroy() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     drop_graphs();
-    void* devp[] = {d_blob, d_patches, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
+    void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
                     d_results, d_stage};
     for (void* p : devp)
@@ -72,12 +72,23 @@ void Engine::drop_graphs() {
 // The crop kernel's buffer tier for the pass about to be enqueued: the largest any stream's last known box needs (the
 // boxes of a pipelined pass are one pass old: targets change by a few per cent per frame, the tier has headroom, and a
 // tile that does not fit its buffer after all takes the per-pixel path - slower, never wrong).
-int Engine::pick_crop_tier() const {
+// A subset pass considers the boxes of its own streams only.
+int Engine::pick_crop_tier(const int32_t* streams, int n) const {
     if (crop_tier_forced >= 0) return std::min(crop_tier_forced, TIERS - 1);
     int t = 0;
-    for (int b = 0; b < B && t < TIERS - 1; ++b)
-        t = std::max(t, std::min(preproc_tier_for_box(d, known[b].box[2], known[b].box[3], false), TIERS - 1));
+    const int cnt = streams ? n : B;
+    for (int i = 0; i < cnt && t < TIERS - 1; ++i) {
+        const StreamState& k = known[streams ? streams[i] : i];
+        t = std::max(t, std::min(preproc_tier_for_box(d, k.box[2], k.box[3], false), TIERS - 1));
+    }
     return t;
+}
+
+int Engine::slot_of(int stream) const {
+    if (pass_streams.empty()) return stream < pass_n ? stream : -1;
+    for (size_t i = 0; i < pass_streams.size(); ++i)
+        if (pass_streams[i] == stream) return (int)i;
+    return -1;
 }
 
 int Engine::index_blob(const uint8_t* hc, size_t bytes) {
@@ -216,7 +227,8 @@ size_t Engine::activation_bytes() const {
     return 2 * (M * d.kpad + M * d.D + M * 2 * d.D + (size_t)B * d.H * 64 * d.npad + M * d.D + M * d.mlp +
                 Ms * d.D + 2 * Ms * d.C + fold_rows * d.D) + M * d.D /* lo8 plane */ +
            8 * (M * (d.D / VT_STAT_CHUNK) + M) + 4 * (Ms * 8 + 2 * fold_rows) +
-           (size_t)B * (sizeof(StreamState) + sizeof(FrameDesc) + sizeof(vt_result));
+           (size_t)B * (sizeof(StreamState) + sizeof(FrameDesc) + sizeof(vt_result) + 4 /* slot map */) +
+           2 * (size_t)B * d.nt * d.kpad /* template store */;
 }
 
 int Engine::alloc_buffers() {
@@ -233,6 +245,7 @@ int Engine::alloc_buffers() {
                            "are free on device %d", B, need / 1048576.0, free_b / 1048576.0, device);
     }
     HIPCHK(dalloc0(&d_patches, M * d.kpad, stream));
+    HIPCHK(dalloc0(&d_tpl, (size_t)B * d.nt * d.kpad, stream));
     HIPCHK(dalloc0(&d_xh, M * d.D, stream));
     HIPCHK(dalloc0(&d_xl, M * d.D, stream));       // bytes
     HIPCHK(dalloc0(&d_cstat, M * (d.D / VT_STAT_CHUNK), stream));
@@ -266,7 +279,7 @@ int Engine::alloc_buffers() {
     HIPCHK(dalloc0(&d_states, (size_t)B, stream));
     HIPCHK(dalloc0(&d_band_cnt, (size_t)B + 1, stream));
     HIPCHK(dalloc0(&d_band_best, (size_t)B * d.gs * 2, stream));
-    {   // B frame descriptors + the pass's PassOut behind them (one upload per pass)
+    {   // B frame descriptors + the pass's PassOut + the slot map behind them (one upload per pass)
         void* p = nullptr;
         HIPCHK(hipMalloc(&p, frames_block_bytes()));
         HIPCHK(hipMemsetAsync(p, 0, frames_block_bytes(), stream));
@@ -281,6 +294,8 @@ int Engine::alloc_buffers() {
     memset(h_results, 0, sizeof(vt_result) * B);
     for (int i = 0; i < RING; ++i) HIPCHK(hipEventCreateWithFlags(&ring_ev[i], hipEventDisableTiming));
     h_initialized.assign(B, 0);
+    pass_n = B;
+    pass_streams.clear();
     known.assign((size_t)B, StreamState{});
     HIPCHK(hipStreamSynchronize(stream));       // every fill has landed before the handle is handed out
     return VT_OK;
@@ -296,10 +311,11 @@ double Engine::flops_head() const {
     return 2.0 * d.ns * (d.D * C + 27 * C * C + 8 * C);
 }
 
-// One hot-path pass over all B streams. With prof != nullptr every launch is bracketed by HIP
-// events on this engine's stream.
-int Engine::run_pass(Profiler* prof) {
-    const int M = B * d.ntok, Ms = B * d.ns, D = d.D;
+// One hot-path pass over n slots: all B streams (slot_stream null: slot b is stream b), or a subset pass, whose slot i
+// works for stream slot_stream[i] (device map). Between the crop and the decode every kernel is slot-indexed and
+// sized by M = n * ntok. With prof != nullptr every launch is bracketed by HIP events on this engine's stream.
+int Engine::run_pass(Profiler* prof, int n, const int32_t* slot_stream) {
+    const int M = n * d.ntok, Ms = n * d.ns, D = d.D;
     hipError_t lerr = hipSuccess;
     auto L = [&](const char* name, double flops, double bytes, auto&& fn) {
         if (lerr != hipSuccess) return;
@@ -379,8 +395,11 @@ int Engine::run_pass(Profiler* prof) {
     GemmArgs qkv = qkv_args(0);             // LayerNorm 1 is folded into the QKV GEMM
 
     // K1: crop + resize + normalise the search window of every stream -> patch rows
-    L("preproc_search", 0, (double)B * (d.S * d.S * 3 * 2 + 1.5 * d.S * d.S),
-      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, B, false, stream, crop_tier); });
+    if (slot_stream)        // the slots' template rows from the store (a full pass finds them in place)
+        L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
+          [&] { return launch_gather_template_rows(d_tpl, d_patches, slot_stream, n, d, stream); });
+    L("preproc_search", 0, (double)n * (d.S * d.S * 3 * 2 + 1.5 * d.S * d.S),
+      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, n, false, stream, crop_tier, slot_stream); });
     // K2: patch embedding (+bias +pos) -> residual stream (3-byte pair + chunk statistics)
     {
         GemmArgs a{};
@@ -395,8 +414,8 @@ int Engine::run_pass(Profiler* prof) {
     for (int l = 0; l < d.L; ++l) {
         const LayerW& w = layers[l];
         gemm(EPI_QKV, qkv);
-        L("attention", 4.0 * B * (double)d.ntok * d.ntok * D, (double)M * D * 8, [&] {
-            return launch_attention(d_qk, d_vt, d_attn, B, d.ntok, d.H, d.npad, stream);
+        L("attention", 4.0 * n * (double)d.ntok * d.ntok * D, (double)M * D * 8, [&] {
+            return launch_attention(d_qk, d_vt, d_attn, n, d.ntok, d.H, d.npad, stream);
         });
         {
             GemmArgs a{};
@@ -427,7 +446,7 @@ int Engine::run_pass(Profiler* prof) {
     const bool ln_fused = band && head_band_kernel >= 2 && headconv_ln_supported(d.gs, d.C, D);
     feat_in_head = ln_fused;
     if (!ln_fused)
-        L("layernorm", 0, (double)Ms * D * 6, [&] { return final_layernorm(); });
+        L("layernorm", 0, (double)Ms * D * 6, [&] { return final_layernorm(n); });
     // centre head: 1x1 conv, three 3x3 convs, then the f32 5-logit layer + decode. On the band kernel of
     // k_head.hip (the A image of a band resident in LDS, logits + decode fused behind the last layer: 4 launches)
     // where the shape allows it, else as implicit GEMMs on the 4-wave kernel + head_out + decode (6 launches).
@@ -436,8 +455,9 @@ int Engine::run_pass(Profiler* prof) {
     dec.b4 = (const float*)find("head.b4")->ptr;
     dec.hann = (const float*)find("hann")->ptr;
     dec.head_out = d_headout; dec.states = d_states; dec.results = d_results;
-    dec.out = (const PassOut*)(d_frames + B);
-    dec.B = B; dec.ns = d.ns; dec.grid = d.gs; dec.C = d.C;
+    dec.out = (const PassOut*)(d_frames + B);      // behind the B descriptors whatever the pass's slot count
+    dec.slot_stream = slot_stream;
+    dec.B = n; dec.ns = d.ns; dec.grid = d.gs; dec.C = d.C;
     dec.success_threshold = success_threshold;
     bf16_t* cur = d_ta;
     bf16_t* nxt = d_tb;
@@ -445,7 +465,7 @@ int Engine::run_pass(Profiler* prof) {
         HeadConvArgs h{};
         h.in = d_feat; h.ldin = D; h.W = (const bf16_t*)find("head.w0")->ptr; h.ldw = D;
         h.bias = (const float*)find("head.b0")->ptr; h.out = d_ta; h.ldout = d.C; h.zeros = d_zeros;
-        h.B = B; h.grid = d.gs; h.C = d.C; h.N = d.C; h.K = D; h.conv3x3 = 0;
+        h.B = n; h.grid = d.gs; h.C = d.C; h.N = d.C; h.K = D; h.conv3x3 = 0;
         if (ln_fused) {
             h.in = nullptr;
             h.xh = d_xh; h.xl = d_xl; h.ln_g = (const float*)find("norm_g")->ptr; h.ln_b = (const float*)find("norm_b")->ptr;
@@ -459,7 +479,7 @@ int Engine::run_pass(Profiler* prof) {
             HeadConvArgs c{};
             c.in = cur; c.ldin = d.C; c.W = (const bf16_t*)find(wn)->ptr; c.ldw = 9 * d.C;
             c.bias = (const float*)find(bn)->ptr; c.out = nxt; c.ldout = d.C; c.zeros = d_zeros;
-            c.B = B; c.grid = d.gs; c.C = d.C; c.N = d.C; c.K = 9 * d.C; c.conv3x3 = 1;
+            c.B = n; c.grid = d.gs; c.C = d.C; c.N = d.C; c.K = 9 * d.C; c.conv3x3 = 1;
             c.band_cnt = d_band_cnt; c.band_best = d_band_best;
             const bool tail = k == 3;
             const double fl = 2.0 * Ms * d.C * 9.0 * d.C + (tail ? 2.0 * Ms * d.C * 5 : 0.0);
@@ -494,15 +514,15 @@ int Engine::run_pass(Profiler* prof) {
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
 }
 
-hipError_t Engine::final_layernorm() {
+hipError_t Engine::final_layernorm(int n) {
     return launch_layernorm_split(d_xh, d_xl, (const float*)find("norm_g")->ptr, (const float*)find("norm_b")->ptr, d_feat,
-                                  (int)((size_t)B * d.ns), d.D, d.ns, d.ntok, d.nt, d.ln_eps, stream);
+                                  (int)((size_t)n * d.ns), d.D, d.ns, d.ntok, d.nt, d.ln_eps, stream);
 }
 
 int Engine::capture_graph(int tier) {
     crop_tier = tier;
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    int rc = run_pass(nullptr);
+    int rc = run_pass(nullptr, B, nullptr);
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(stream, &g);
     if (rc != VT_OK) {
@@ -605,10 +625,24 @@ int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
     HIPCHK(hipMemcpyAsync(d_frames + b, slot, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
     HIPCHK(launch_preproc(d_frames, d_states, d_patches, d, b, 1, true, stream,
                           preproc_tier_for_box(d, (float)box.width, (float)box.height, true)));
+    // the stream's template rows, kept for the subset passes that run it in another slot
+    HIPCHK(hipMemcpyAsync(d_tpl + (size_t)b * d.nt * d.kpad, d_patches + (size_t)b * d.ntok * d.kpad,
+                          sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     h_states_all[b] = *h_state;
     known[b] = *h_state;
     h_initialized[b] = 1;
+    return VT_OK;
+}
+
+// After a subset pass the segments of d_patches hold other streams' template rows: one strided copy puts every stream's
+// rows back into its own segment before a full pass (its captured graph expects them in place).
+int Engine::restore_segments() {
+    if (!segments_moved) return VT_OK;
+    const size_t row = sizeof(bf16_t) * d.nt * d.kpad;
+    HIPCHK(hipMemcpy2DAsync(d_patches, sizeof(bf16_t) * (size_t)d.ntok * d.kpad, d_tpl, row, row, (size_t)B,
+                            hipMemcpyDeviceToDevice, stream));
+    segments_moved = false;
     return VT_OK;
 }
 
@@ -627,6 +661,9 @@ int Engine::enqueue(const vt_frame* frames, int n, vt_result* host_res, StreamSt
     *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all};
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipEventRecord(ring_ev[slot], stream));
+    if (int rc = restore_segments()) return rc;
+    pass_n = B;
+    pass_streams.clear();
     const int tier = pick_crop_tier();
     if (use_graph && !taps) {
         if (!graph_exec[tier])      // not reached after a successful creation (capture_all_graphs); kept as the safe path
@@ -636,11 +673,55 @@ int Engine::enqueue(const vt_frame* frames, int n, vt_result* host_res, StreamSt
         return VT_OK;
     }
     crop_tier = tier;
-    return run_pass(nullptr);
+    return run_pass(nullptr, B, nullptr);
+}
+
+int Engine::check_streams(const int32_t* streams, int n) const {
+    if (!streams) return set_err(VT_ERR_INVALID_ARG, "null stream list");
+    if (n < 1 || n > B) return set_err(VT_ERR_INVALID_ARG, "pass over %d streams: need 1..%d", n, B);
+    std::vector<char> seen((size_t)B, 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = streams[i];
+        if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "streams[%d] = %d out of range (0..%d)", i, s, B - 1);
+        if (seen[(size_t)s]) return set_err(VT_ERR_INVALID_ARG, "stream %d listed twice", s);
+        seen[(size_t)s] = 1;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!h_initialized[streams[i]]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d: update before init", streams[i]);
+    return VT_OK;
+}
+
+// A pass over the streams streams[0..n) on n compacted slots: slot i takes frames[i] and works for stream streams[i];
+// no other stream's state is touched. The full identity list is the full pass (captured graph); any other list runs
+// eagerly - never a capture inside an update - behind the gather of its template rows.
+int Engine::enqueue_streams(const int32_t* streams, const vt_frame* frames, int n) {
+    if (int rc = check_streams(streams, n)) return rc;
+    if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
+    for (int i = 0; i < n; ++i)
+        if (int rc = check_frame(frames[i])) return rc;
+    bool identity = n == B;
+    for (int i = 0; i < n && identity; ++i) identity = streams[i] == i;
+    if (identity) return enqueue(frames, n);
+    DEVICE_SCOPE(device);
+    const int slot = ring_pos;
+    ring_pos = (ring_pos + 1) % RING;
+    HIPCHK(hipEventSynchronize(ring_ev[slot]));
+    FrameDesc* hf = h_block(slot);
+    for (int i = 0; i < n; ++i) to_desc(frames[i], hf + i);
+    *(PassOut*)(hf + B) = PassOut{h_results, h_states_all};
+    int32_t* map = (int32_t*)((char*)hf + map_offset());
+    for (int i = 0; i < n; ++i) map[i] = streams[i];
+    HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ring_ev[slot], stream));
+    pass_n = n;
+    pass_streams.assign(streams, streams + n);
+    segments_moved = true;
+    crop_tier = pick_crop_tier(streams, n);
+    return run_pass(nullptr, n, d_map());
 }
 
 int Engine::wait(vt_result* out, int n) {
-    if (n > B) n = B;
+    if (n > pass_n) n = pass_n;         // the results of the last pass, in its slot order
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     if (out)

@@ -138,12 +138,22 @@ struct Engine {
     unsigned* d_panel_cnt = nullptr;   // arrival counters of the 256-row panels (X-epilogues of the 256x256 kernel)
     float *d_foldv = nullptr, *d_headout = nullptr;
     StreamState* d_states = nullptr;
-    FrameDesc* d_frames = nullptr;
+    FrameDesc* d_frames = nullptr;      // per-pass block: [B] frame descriptors (by slot) | PassOut | [B] slot -> stream
+    // template rows of every stream as init wrote them, [B][nt][kpad]: a subset pass gathers its streams' rows into its
+    // slots' segments of d_patches, and the next full pass puts every segment back from here
+    bf16_t* d_tpl = nullptr;
+    bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
     vt_result* d_results = nullptr;
     // pinned host
     static const int RING = 8;
-    FrameDesc* h_frames = nullptr;  // [RING] blocks of B descriptors + PassOut
-    size_t frames_block_bytes() const { return sizeof(FrameDesc) * (size_t)B + sizeof(PassOut); }
+    FrameDesc* h_frames = nullptr;  // [RING] blocks of B descriptors + PassOut + the slot map (16-B multiples)
+    size_t frames_block_bytes() const { return (sizeof(FrameDesc) * (size_t)B + sizeof(PassOut) + 4 * (size_t)B + 15) & ~(size_t)15; }
+    size_t map_offset() const { return sizeof(FrameDesc) * (size_t)B + sizeof(PassOut); }
+    const int32_t* d_map() const { return (const int32_t*)((const char*)d_frames + map_offset()); }
+    // the last pass: its slot count and, for a subset pass, the stream of every slot (empty: all B streams in order)
+    int pass_n = 1;
+    std::vector<int32_t> pass_streams;
+    int slot_of(int stream) const;      // slot of `stream` in the last pass, -1 if it was not in it
     FrameDesc* h_block(int slot) const { return (FrameDesc*)((char*)h_frames + (size_t)slot * frames_block_bytes()); }
     hipEvent_t ring_ev[RING]{};
     int ring_pos = 0;
@@ -188,7 +198,7 @@ struct Engine {
                                                   // 1: band kernels behind the LayerNorm kernel; 2: + the final LayerNorm
                                                   // inside the 1x1 layer's kernel where the shape allows it (default)
     bool feat_in_head = false;                    // the passes do not write d_feat (recomputed when read)
-    hipError_t final_layernorm();
+    hipError_t final_layernorm(int n);
     int host_zero_copy = 0;                       // vt_config.host_zero_copy: 0 auto (single-stream engines), 1 always, -1 never
     float success_threshold = 0.2f;
     std::vector<int> h_initialized;
@@ -200,14 +210,20 @@ struct Engine {
     int index_blob(const uint8_t* host_copy, size_t bytes);
     size_t activation_bytes() const;
     int alloc_buffers();
-    int run_pass(Profiler* prof);
+    // n slots (M = n * ntok); slot_stream: the device map of a subset pass, null for a full pass (n == B)
+    int run_pass(Profiler* prof, int n, const int32_t* slot_stream);
+    int restore_segments();             // every stream's template rows back into its own segment (after a subset pass)
     int capture_graph(int tier);
     int capture_all_graphs();
-    int pick_crop_tier() const;
+    int pick_crop_tier(const int32_t* streams = nullptr, int n = 0) const;   // streams == null: all B
     void drop_graphs();
     // host_res / host_st: pinned buffers the pass's results and states are stored to (null: the
     // engine's own h_results / h_states_all)
     int enqueue(const vt_frame* frames, int n, vt_result* host_res = nullptr, StreamState* host_st = nullptr);
+    // one pass over streams[0..n): VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input; a
+    // full identity list is the full pass
+    int check_streams(const int32_t* streams, int n) const;
+    int enqueue_streams(const int32_t* streams, const vt_frame* frames, int n);
     int wait(vt_result* out, int n);
     int init_stream(int b, const vt_frame* f, vt_bbox box);
     const TensorRef* find(const std::string& n) const {

@@ -251,6 +251,24 @@ int vt_group_update_host(vt_group* g, const vt_frame* host_frames, int n, vt_res
     return e->wait(out, n);
 } VT_NOTHROW_INT
 
+// the same window logic on the n streams of a subset pass: stream streams[i]'s window is cut around its own last box
+int vt_group_update_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n,
+                                 vt_result* out) try {
+    if (!g || !host_frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    Engine* e = g->e;
+    if (int rc = refuse_while_pipelined(e, "update_host_streams")) return rc;
+    if (int rc = e->check_streams(streams, n)) return rc;
+    DEVICE_SCOPE(e->device);
+    if (int rc = e->wait(nullptr, 0)) return rc;   // last pass done: its boxes are in `known`
+    std::vector<vt_frame> dev((size_t)n);
+    std::vector<float> boxes((size_t)n * 4);
+    for (int i = 0; i < n; ++i) memcpy(&boxes[(size_t)i * 4], e->known[streams[i]].box, 4 * sizeof(float));
+    if (int rc = stage_host_frames(e, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
+        return rc;
+    if (int rc = e->enqueue_streams(streams, dev.data(), n)) return rc;
+    return e->wait(out, n);
+} VT_NOTHROW_INT
+
 int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n) try {
     if (!g || !host_frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
     Engine* e = g->e;

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures; the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
+#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
 
 typedef enum vt_status {
     VT_OK = 0,
@@ -222,7 +222,8 @@ int vt_group_init_device(vt_group* g, int stream, const vt_frame* frame, vt_bbox
 /* One hot-path pass: frames[i] feeds stream i (n == vt_group_streams). Asynchronous: the pass is
  * enqueued on the group's HIP stream; results land in the group's pinned result ring. */
 int vt_group_enqueue_device(vt_group* g, const vt_frame* frames, int n);
-/* Wait for every enqueued pass and copy the results of the LAST pass (n entries). */
+/* Wait for every enqueued pass and copy the results of the LAST pass (n entries, in that pass's order; n may not
+ * exceed that pass's size - entries beyond it are not written). */
 int vt_group_wait(vt_group* g, vt_result* out, int n);
 /* enqueue + wait */
 int vt_group_update_device(vt_group* g, const vt_frame* frames, int n, vt_result* out);
@@ -250,7 +251,7 @@ int vt_group_update_host(vt_group* g, const vt_frame* host_frames, int n, vt_res
  * the states the previous pass left (collected by the wait_next before it) and redoes that pass (and
  * the one queued behind it) with exact windows, so the results are always those of the full frames.
  * While a pass is outstanding it owns the stream states: every entry point that would advance or
- * overwrite them (vt_group_init_*, vt_group_enqueue_device, vt_group_update_device / _host,
+ * overwrite them (vt_group_init_*, vt_group_enqueue_device, vt_group_update_device / _host, the *_streams passes,
  * vt_group_wait, vt_group_set_state_box, vt_group_profile_device) returns VT_ERR_INVALID_ARG until
  * vt_group_wait_next has collected it. (host -> tracker: src/pipeline.rs:95-101 maps the buffer on the CPU) */
 int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n);
@@ -262,6 +263,27 @@ int vt_group_host_redos(const vt_group* g);
  * vt_group_set_tuning), never inside an enqueue: a live 60-fps stream (src/pipeline.rs:26-37) whose target grows
  * across a tier boundary takes no capture stall mid-track. Constant after creation unless the tuning is changed. */
 int vt_group_graph_captures(const vt_group* g);
+/* One pass over the n streams streams[0..n): distinct, each initialised, 1 <= n <= vt_group_streams.
+ * frames[i] feeds streams[i]; out[i] / vt_group_wait's i-th entry is its result. Streams not listed are
+ * not touched (their state, template and results stay as they were) and need not be initialised.
+ * ≙ a multi-camera host that calls tracker.update only for the cameras that are tracking, or confirm a selection
+ * this frame (src/tracker_context.rs:88-90,120); cameras that are selecting or lost sit the frame out.
+ * The pass runs the full pass's kernels on n compacted slots (M = n x the tokens of one frame): a stream's results are
+ * bit-identical to those of an n-stream group given the same inputs, and the encoder's work is linear in n.
+ * The full identity list (0, 1, ..., B-1) is the full pass and replays its captured graph; any other list is
+ * launched eagerly (no graph is ever captured inside an update: vt_group_graph_captures stays constant).
+ * Bad input - a duplicate or out-of-range index, n < 1 or n > vt_group_streams, a null pointer, an invalid frame -
+ * returns VT_ERR_INVALID_ARG; a listed stream that was never initialised, VT_ERR_NOT_INITIALIZED. In both cases
+ * nothing is enqueued and no state changes. Refused (VT_ERR_INVALID_ARG) while a pipelined host pass is outstanding.
+ * Per-pass tensors of vt_group_read_tensor ("x", "feat", "head_out", ...) then exist only for the listed streams. */
+int vt_group_enqueue_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n);
+/* enqueue + wait */
+int vt_group_update_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n,
+                                   vt_result* out);
+/* The same with HOST frames: stream streams[i]'s search window is cut from host_frames[i] around its own last box
+ * and uploaded as by vt_group_update_host. Synchronous. */
+int vt_group_update_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n,
+                                 vt_result* out);
 
 /* ---- dma-buf ingest ------------------------------------------------------------------------
  * The reference's capture side can hand out dma-bufs (v4l2src io-mode=dmabuf, src/pipeline_ir.rs:24)
@@ -401,7 +423,9 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * as: bf16 + a signed byte in units of 2^-12), "rowstat" [N,2] (row terms of the last folded LayerNorm), "attn" [N,D] (last block's attention output),
  * "feat" [Ns,D], "head_t3" [Ns,C], "head_out" [Ns,8] (score,ox,oy,w,h logits),
  * "state" (the stream's device state record as raw 32-bit words), "graph_replays" [3] (passes replayed so far
- * per crop-buffer tier: which of the captured graphs ran).
+ * per crop-buffer tier: which of the captured graphs ran). After a subset pass (vt_group_*_streams) every
+ * tensor but "state" and "graph_replays" is that of the stream's slot in it; a stream that was not in the pass
+ * returns VT_ERR_INVALID_ARG.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);
