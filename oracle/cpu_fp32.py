@@ -53,6 +53,8 @@ class VitTrackFp32(vit_ref.VitTrackRef):
         success = bool(score >= self.thr)
         if success:
             self.box = ib.astype(np.float32).copy()
+        if taps:    # as VitTrackRef.last (tests/golden/make_traj.py reads the margin from head_out)
+            self.last = {"head_out": ho, "patches": patches, "geo": geo}
         return vit_ref.Result(success, score, tuple(int(v) for v in ib), dec[1:5].copy(), int(dec[5]))
 
 

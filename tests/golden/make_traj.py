@@ -9,6 +9,17 @@ from /root/reference (it holds no vectors for this path, SURVEY.md §8c: PARITY 
       (per frame: box, score, success, argmax cell, top-1/top-2 response margin, state box)
   python tests/golden/make_traj.py traj cfg3 --frames 300 --seed 9 --square 80 --tag _b
       a second clip (other background, phase and target size) -> traj_cfg3_300_b.npz
+  python tests/golden/make_traj.py fp32 cfg3 --frames 300 --seed 1
+      the float32 yardstick (tests/test_fp32_yardstick.py, tests/test_gpu_fp32_yardstick.py): closed loop of the
+      float32 tracker (oracle/cpu_fp32.py, no bf16 rounding) on the clip of traj_<cfg>_<frames><tag>.npz (same seed,
+      --square, --hide, --tag) -> tests/golden/fp32_traj_<cfg>_<frames><tag>.npz with the fields of `traj` (margin and
+      idx2 from the float32 head logits) + generator / torch_version / threads, and on every recorded state ONE
+      teacher-forced update of the bf16 oracle: oracle_fbox / oracle_idx / oracle_score, the specification's own distance
+      from float32 on exactly the inputs the GPU test replays. Cost on 2 torch threads per process (four processes side
+      by side on 8 cores): cfg2 300 frames 7.5 min, cfg3 300 frames 20 min (the oracle pass is 80 % of it), cfg5 100
+      frames 30 min - so fp32_traj_cfg5_100.npz holds 100 frames (its twin is the first 100 of traj_cfg5_300.npz).
+      The committed files: cfg3 and cfg2 seed 1, cfg3 `--seed 9 --square 80 --tag _b`, cfg5 `--frames 100`. They are
+      regenerated only when the weights or the clip change, never together with a kernel or specification change.
   python tests/golden/make_traj.py gen1head cfg3
       the FIRST-GENERATION head: fitted on ~128 CPU-oracle samples only (noisy, 1-2 px
       of frame-to-frame jitter) -> tests/golden/head_gen1_<cfg>.npz
@@ -108,6 +119,62 @@ def run(cfg: str, weights: str, frames: int, seed: int, out: str, verbose=True, 
     print(f"wrote {out} ({os.path.getsize(out)} bytes)", flush=True)
 
 
+def run_fp32(cfg: str, frames: int, seed: int, out: str, square: int = 0, hide=None, threads: int = 0):
+    """closed loop of the float32 tracker (oracle/cpu_fp32.py) on the clip of a `traj_*` fixture, and on every
+    recorded state one teacher-forced update of the bf16 oracle (oracle_fbox / oracle_idx / oracle_score): the
+    specification's own per-frame distance from float32 on exactly the inputs the GPU test replays"""
+    import torch
+    from oracle import cpu_fp32
+    weights = vt.weights.ensure_weights(cfg)
+    w, h, sq = CLIPS[cfg]
+    sq = square or sq
+    sc = vt.synth.MovingSquare(w, h, sq, seed=seed, hide=hide)
+    trk = cpu_fp32.VitTrackFp32(weights, threads=threads or None)
+    ref = R.VitTrackRef(weights)
+    hann = trk.m.t["hann"].reshape(-1)
+    keys = ("state", "bbox", "score", "success", "idx", "idx2", "margin", "gt", "fbox",
+            "oracle_fbox", "oracle_idx", "oracle_score")
+    rec = {k: [] for k in keys}
+    t0 = time.time()
+    for t in range(frames):
+        fr = R.Frame.nv12(sc.frame_nv12(t), w, h)
+        if t == 0:
+            trk.init(fr, sc.gt_box(0))
+            ref.init(fr, sc.gt_box(0))
+        rec["state"].append(trk.box.copy())
+        ref.box = trk.box.copy()
+        r = trk.update(fr, taps=True)
+        o = ref.update(fr)
+        resp = (1.0 / (1.0 + np.exp(-trk.last["head_out"][:, 0].astype(np.float64)))) * hann
+        order = np.argsort(-resp, kind="stable")
+        rec["bbox"].append(r.bbox)
+        rec["fbox"].append(r.fbox)
+        rec["score"].append(r.score)
+        rec["success"].append(int(r.success))
+        rec["idx"].append(r.idx)
+        rec["idx2"].append(int(order[1]))
+        rec["margin"].append(float(resp[order[0]] - resp[order[1]]))
+        rec["gt"].append(sc.gt_box(t))
+        rec["oracle_fbox"].append(o.fbox)
+        rec["oracle_idx"].append(o.idx)
+        rec["oracle_score"].append(o.score)
+        if t % 20 == 0 or t == frames - 1:
+            print(f"[fp32 {cfg}] frame {t}: {r} idx {r.idx} margin {rec['margin'][-1]:.4f} | oracle idx {o.idx} "
+                  f"|dfbox| {np.abs(np.asarray(o.fbox) - np.asarray(r.fbox)).max():.4f} ({time.time() - t0:.0f}s)",
+                  flush=True)
+    np.savez_compressed(
+        out, config=cfg, frame_w=w, frame_h=h, square=sq, seed=seed, frames=frames,
+        weights_sha256=sha256_file(weights), hide=np.array(hide if hide else (0, 0), np.int32),
+        generator="fp32", torch_version=torch.__version__, threads=trk.threads,
+        state=np.array(rec["state"], np.float32), bbox=np.array(rec["bbox"], np.int32),
+        score=np.array(rec["score"], np.float32), success=np.array(rec["success"], np.int8),
+        idx=np.array(rec["idx"], np.int32), idx2=np.array(rec["idx2"], np.int32),
+        margin=np.array(rec["margin"], np.float32), gt=np.array(rec["gt"], np.int32),
+        fbox=np.array(rec["fbox"], np.float32), oracle_fbox=np.array(rec["oracle_fbox"], np.float32),
+        oracle_idx=np.array(rec["oracle_idx"], np.int32), oracle_score=np.array(rec["oracle_score"], np.float32))
+    print(f"wrote {out} ({os.path.getsize(out)} bytes, {time.time() - t0:.0f}s)", flush=True)
+
+
 def add_fbox(name: str):
     """re-evaluate every frame of an existing fixture from its recorded state; verify; append `fbox`"""
     path = os.path.join(HERE, name)
@@ -143,7 +210,7 @@ if __name__ == "__main__":
         add_fbox(sys.argv[2])
         sys.exit(0)
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["traj", "gen1head", "forced"])
+    ap.add_argument("what", choices=["traj", "fp32", "gen1head", "forced"])
     ap.add_argument("cfg", choices=sorted(CLIPS))
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--seed", type=int, default=1)
@@ -151,10 +218,14 @@ if __name__ == "__main__":
     ap.add_argument("--tag", default="", help="suffix of the output file, e.g. _b for a second clip")
     ap.add_argument("--hide", type=int, nargs=2, default=None, metavar=("T0", "T1"),
                     help="occlusion: the target is absent from frames T0 <= t < T1")
+    ap.add_argument("--threads", type=int, default=0, help="fp32: torch-CPU threads (default: torch's own)")
     a = ap.parse_args()
     if a.what == "traj":
         run(a.cfg, vt.weights.ensure_weights(a.cfg), a.frames, a.seed,
             os.path.join(HERE, f"traj_{a.cfg}_{a.frames}{a.tag}.npz"), square=a.square, hide=a.hide)
+    elif a.what == "fp32":
+        run_fp32(a.cfg, a.frames, a.seed, os.path.join(HERE, f"fp32_traj_{a.cfg}_{a.frames}{a.tag}.npz"),
+                 square=a.square, hide=a.hide, threads=a.threads)
     elif a.what == "gen1head":
         import importlib.util
         spec = importlib.util.spec_from_file_location("fit_head", os.path.join(HERE, "fit_head.py"))

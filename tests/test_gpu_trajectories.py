@@ -11,7 +11,7 @@ run does not pay seconds of CPU oracle per frame.
   * teacher-forced tests assert the FLOAT box (StreamState.last_fbox vs the fixture's `fbox`) to 0.15 px,
     closed-loop tests the score to 0.01 on every frame whose input was bit-identical, and the number of
     frames below IoU 0.99 may not exceed round 3's count by more than the stated headroom; the gen-1 head also runs CLOSED loop,
-    bounded as ASSERTED there: max <= 5 px, at most 8 % of the frames beyond 2 px, mean IoU >= 0.975 (bars set from the
+    bounded as ASSERTED there: max <= 6 px, at most 8 % of the frames beyond 2 px, mean IoU >= 0.975 (bars set from the
     round-4 measurement - max 4 px, 5 % beyond 2 px, mean 0.982-0.985 - so this gate catches a regression of an
     ill-conditioned head's closed loop, it does not bound the divergence a priori).
   * teacher-forced (open loop) on the FIRST-GENERATION noisy head (fitted on 128 CPU samples only,
@@ -266,7 +266,7 @@ def _teacher_forced(gpu, fx, weights, engine_streams):
     return np.array(idx), np.array(boxes), np.array(scores), np.array(fboxes)
 
 
-def _check_teacher_forced(fx, tag, idx, boxes, scores, fboxes, capsys):
+def _check_teacher_forced(fx, tag, idx, boxes, scores, fboxes, capsys, fbox_bar=FBOX_BAR_PX, score_bar=SCORE_BAR_SAME_INPUT):
     assert "fbox" in fx, "fixture has no float boxes: python tests/golden/make_traj.py fbox <fixture>"
     n = len(idx)
     d = np.abs(boxes - fx["bbox"])
@@ -287,10 +287,10 @@ def _check_teacher_forced(fx, tag, idx, boxes, scores, fboxes, capsys):
     # the integer box hides up to a pixel of float error: on identical inputs the FLOAT boxes must agree to a
     # fraction of a pixel wherever both decode around the same cell (a near-tie taken the other way moves the
     # 3x3 decode window by a cell: second-order, bounded by the +-1 px above)
-    assert df[~differ].max() <= FBOX_BAR_PX, \
+    assert df[~differ].max() <= fbox_bar, \
         f"float box differs by {df[~differ].max():.3f} px at frame {int(np.argmax(np.where(~differ, df, 0)))}"
     assert df.max() <= 1.0
-    assert ds[~differ].max() < SCORE_BAR_SAME_INPUT and ds.max() < 0.10
+    assert ds[~differ].max() < score_bar and ds.max() < 0.10
 
 
 @pytest.mark.parametrize("name", FIXTURES)

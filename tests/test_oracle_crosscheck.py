@@ -53,21 +53,39 @@ def test_unrounded_oracle_equals_torch_functional(vt, oracle, cfg, w, h, sq):
     assert max(worst.values()) <= 5e-6, worst
 
 
-def test_bf16_oracle_stays_within_bf16_noise_of_the_unquantised_answer(vt, oracle):
+# cfg3 (the model bench.py times), relative to the tensor's maximum: block 0 / every block / feat / head logits of max(1, max
+# |logit|), measured 4.9e-4 / 1.6e-3 (blocks 9-11; the error grows block by block) / 3.1e-3 / 5.1e-3; with a plain bf16 residual
+# stream (the pair's low byte zero) every block is several times worse and these bars fail
+CFG3_BARS = dict(block0=1e-3, blocks=4e-3, feat=8e-3, head=1.2e-2)
+
+
+@pytest.mark.parametrize("cfg", ["cfg2", "cfg3"])
+def test_bf16_oracle_stays_within_bf16_noise_of_the_unquantised_answer(vt, oracle, cfg, capsys):
     from oracle import torch_ref
-    weights, trk, patches = _patches(vt, oracle, "cfg2", 1920, 1080, 64)
+    weights, trk, patches = _patches(vt, oracle, cfg, 1920, 1080, 64)
     truth = torch_ref.TorchModel(weights).forward(patches)
     got = oracle.Model(weights).forward(patches, taps=True)
     L = trk.m.L
+    e = [_rel(got[f"layer{l}"], truth[f"layer{l}"]) for l in range(L)]
+    e_head = float(np.abs(got["head_out"][:, :5] - truth["head_out"][:, :5]).max() / max(1.0, np.abs(truth["head_out"][:, :5]).max()))
+    with capsys.disabled():
+        print(f"\n[bf16 oracle vs float64, {cfg}] tokens0 {np.abs(got['tokens0'] - truth['tokens0']).max():.2e} abs; blocks "
+              f"{' '.join(f'{v:.1e}' for v in e)}; feat {_rel(got['feat'], truth['feat']):.2e}; head {e_head:.2e}")
     # only the 3-byte pair's half quantum, 2^-13 absolute (numerical specification v3; with the bf16 low half of rounds 3-5: 2^-18 relative)
     assert np.abs(got["tokens0"] - truth["tokens0"]).max() <= 2.0 ** -13 * 1.01
     assert _rel(got[f"layer{L - 1}"], truth[f"layer{L - 1}"]) <= 4e-3      # measured 1.5e-3
     assert _rel(got["feat"], truth["feat"]) <= 8e-3                  # feat itself is rounded to bf16 (measured 3.1e-3)
+    if cfg == "cfg3":
+        assert e[0] <= CFG3_BARS["block0"] and max(e) <= CFG3_BARS["blocks"], e
+        assert e_head <= CFG3_BARS["head"], e_head
     # the decision the tracker takes from the map is the same
     hann = trk.m.t["hann"].reshape(-1)
     r_o = 1 / (1 + np.exp(-got["head_out"][:, 0])) * hann
     r_t = 1 / (1 + np.exp(-truth["head_out"][:, 0])) * hann
-    assert int(np.argmax(r_o)) == int(np.argmax(r_t))
+    top = np.sort(r_t)[::-1]
+    # cfg3's crop holds no clear peak (responses ~1e-10, top-1/top-2 margin ~0): its cell is asserted only at a clear margin
+    if cfg == "cfg2" or top[0] - top[1] >= 0.01:
+        assert int(np.argmax(r_o)) == int(np.argmax(r_t))
     assert abs(r_o.max() - r_t.max()) < 0.02
 
 
