@@ -24,6 +24,11 @@ pub const VT_ERR_OOM: c_int = -8;
 pub const VT_PIX_RGB8: i32 = 0;
 pub const VT_PIX_NV12: i32 = 1;
 pub const VT_PIX_YUY2: i32 = 2;
+pub const VT_PIX_BGR8: i32 = 3;
+pub const VT_PIX_RGBX: i32 = 4;
+pub const VT_PIX_BGRX: i32 = 5;
+pub const VT_PIX_NV21: i32 = 6;
+pub const VT_PIX_UYVY: i32 = 7;
 
 /// ≙ vt_bbox ≙ vit_tracker::BBox (src/selection_state.rs:44, src/tracker_context.rs:85)
 #[repr(C)]
@@ -166,6 +171,9 @@ extern "C" {
     pub fn vt_rccl_unique_id(id_out: *mut u8) -> c_int;
     pub fn vt_broadcast_weights_rccl(id: *const u8, world: c_int, rank: c_int, device_id: c_int, weights_path: *const c_char, d_blob_out: *mut *mut c_void, bytes_out: *mut usize) -> c_int;
     pub fn vt_free_device_blob(device_id: c_int, d_blob: *mut c_void);
+
+    pub fn vt_init_frame(t: *mut vt_tracker, frame: *const VtFrame, on_device: c_int, bbox: BBox) -> c_int;
+    pub fn vt_update_frame(t: *mut vt_tracker, frame: *const VtFrame, on_device: c_int, out: *mut VtResult) -> c_int;
 
     pub fn vt_group_create(weights_path: *const c_char, device_id: c_int, cfg: *const VtConfig, out: *mut *mut vt_group) -> c_int;
     pub fn vt_group_create_from_device_blob(d_blob: *const c_void, bytes: usize, device_id: c_int, cfg: *const VtConfig, out: *mut *mut vt_group) -> c_int;

@@ -26,6 +26,8 @@ OPS_LIB_PATH = os.environ.get("VITTRACK_HIP_OPS_LIB") or os.environ.get("VITTRAC
     os.path.join(PKG_DIR, "libvittrack_hip_ops.so")
 
 PIX_RGB8, PIX_NV12, PIX_YUY2 = 0, 1, 2
+# byte permutations / paddings of the three above (include/vittrack_hip.h: vt_pixfmt)
+PIX_BGR8, PIX_RGBX, PIX_BGRX, PIX_NV21, PIX_UYVY = 3, 4, 5, 6, 7
 
 
 class VtError(RuntimeError):
@@ -93,7 +95,7 @@ EXPORTS = [
     "vt_overlay_rgb8_device",
     "vt_group_profile_device", "vt_group_enable_taps", "vt_group_set_tuning", "vt_group_set_state_box", "vt_tracker_as_group",
     "vt_group_read_tensor", "vt_group_enqueue_device_streams", "vt_group_update_device_streams", "vt_group_update_host_streams",
-    "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob",
+    "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob", "vt_init_frame", "vt_update_frame",
 ]
 # every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
 OPS_EXPORTS = [
@@ -135,6 +137,8 @@ def lib():
     L.vt_update_yuy2.argtypes = [c_void_p, u8p, c_int, c_int, c_int, POINTER(CResult)]
     L.vt_init_nv12.argtypes = [c_void_p, u8p, u8p, c_int, c_int, c_int, c_int, CBBox]
     L.vt_update_nv12.argtypes = [c_void_p, u8p, u8p, c_int, c_int, c_int, c_int, POINTER(CResult)]
+    L.vt_init_frame.argtypes = [c_void_p, POINTER(CFrame), c_int, CBBox]
+    L.vt_update_frame.argtypes = [c_void_p, POINTER(CFrame), c_int, POINTER(CResult)]
     L.vt_init_rgb8_device.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, CBBox]
     L.vt_update_rgb8_device.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(CResult)]
     L.vt_init_nv12_device.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -431,6 +435,80 @@ class YUY2Frame:
         assert self.buf.size >= 2 * width * height and width % 2 == 0
 
 
+class _PackedFrame:
+    """(H,W,C) uint8 host array of a packed pixel format. An array whose rows lie a constant number of bytes apart with
+    the pixels of a row contiguous (e.g. buf[:, :W] of a wider buffer) is used in place, its row pitch as the stride;
+    any other array is copied to C order. `stride` (bytes, >= C*W) asks for rows that far apart: the pixels are copied
+    into such a buffer unless the array already has that pitch."""
+    C = 3
+    FMT = PIX_RGB8
+
+    def __init__(self, a: np.ndarray, stride: int | None = None):
+        a = np.asarray(a)
+        if a.ndim != 3 or a.shape[2] != self.C:
+            raise VtError(-1, f"{type(self).__name__}: need an (H,W,{self.C}) array, got {a.shape}")
+        self.h, self.w = a.shape[0], a.shape[1]
+        row = self.C * self.w
+        if not (a.dtype == np.uint8 and a.strides[1:] == (self.C, 1) and a.strides[0] >= row):
+            a = np.ascontiguousarray(a, np.uint8)
+        if stride is not None and stride != a.strides[0]:
+            if stride < row:
+                raise VtError(-1, f"{type(self).__name__}: stride {stride} < {row}")
+            buf = np.zeros((self.h, stride), np.uint8)
+            buf[:, :row] = a.reshape(self.h, row)
+            a = buf[:, :row].reshape(self.h, self.w, self.C)
+        self.arr = a
+        self.stride = int(a.strides[0])
+
+    def cframe(self) -> "CFrame":
+        return CFrame(self.arr.ctypes.data, None, self.w, self.h, self.stride, 0, self.FMT, 0, 0, 0, 0, 0)
+
+
+class BGR8Frame(_PackedFrame):
+    """(H,W,3) host array, channel order B,G,R (OpenCV's cv2.imread / VideoCapture)"""
+    C, FMT = 3, PIX_BGR8
+
+
+class RGBXFrame(_PackedFrame):
+    """(H,W,4) host array R,G,B,x (RGBA: alpha ignored)"""
+    C, FMT = 4, PIX_RGBX
+
+
+class BGRXFrame(_PackedFrame):
+    """(H,W,4) host array B,G,R,x (BGRA: alpha ignored; GStreamer BGRx / BGRA)"""
+    C, FMT = 4, PIX_BGRX
+
+
+class NV21Frame:
+    """packed NV21 host buffer: Y plane then interleaved V,U, stride == width (Android / V4L2 sensors)"""
+
+    def __init__(self, buf: np.ndarray, width: int, height: int):
+        self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+        self.w, self.h = width, height
+        assert self.buf.size >= width * height + ((width + 1) & ~1) * ((height + 1) // 2)
+
+    def cframe(self) -> "CFrame":
+        vu = self.buf[self.w * self.h:]
+        return CFrame(self.buf.ctypes.data, vu.ctypes.data, self.w, self.h, self.w, (self.w + 1) & ~1, PIX_NV21,
+                      0, 0, 0, 0, 0)
+
+
+class UYVYFrame:
+    """packed 4:2:2 host frame (U Y0 V Y1), rows of 2*width bytes (V4L2 / SDI capture)"""
+
+    def __init__(self, buf: np.ndarray, width: int, height: int):
+        self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+        self.w, self.h = width, height
+        assert self.buf.size >= 2 * width * height and width % 2 == 0
+
+    def cframe(self) -> "CFrame":
+        return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
+
+
+# host frame classes that go through vt_init_frame / vt_update_frame (each has .cframe())
+_ANY_FRAMES = (_PackedFrame, NV21Frame, UYVYFrame)
+
+
 class VitTrack:
     """≙ vit_tracker::VitTrack (src/tracker_context.rs:21,88,90,120)."""
 
@@ -463,9 +541,12 @@ class VitTrack:
         return Group._view(lib().vt_tracker_as_group(self._h), self)
 
     def init(self, frame, bbox: BBox) -> None:
-        """frame: (H,W,3) uint8 RGB array (≙ ArrayView3<u8>) or NV12Frame. Like the reference's
-        call site (src/tracker_context.rs:88) the caller gets nothing back; errors raise."""
-        if isinstance(frame, YUY2Frame):
+        """frame: (H,W,3) uint8 RGB array (≙ ArrayView3<u8>), NV12Frame, YUY2Frame, or one of BGR8Frame, RGBXFrame,
+        BGRXFrame, NV21Frame, UYVYFrame. Like the reference's call site (src/tracker_context.rs:88) the caller gets
+        nothing back; errors raise."""
+        if isinstance(frame, _ANY_FRAMES):
+            _check(lib().vt_init_frame(self._h, byref(frame.cframe()), 0, bbox._c()))
+        elif isinstance(frame, YUY2Frame):
             _check(lib().vt_init_yuy2(self._h, _u8(frame.buf), frame.w, frame.h, 2 * frame.w,
                                       bbox._c()))
         elif isinstance(frame, NV12Frame):
@@ -480,7 +561,9 @@ class VitTrack:
 
     def update(self, frame) -> TrackResult:
         r = CResult()
-        if isinstance(frame, YUY2Frame):
+        if isinstance(frame, _ANY_FRAMES):
+            _check(lib().vt_update_frame(self._h, byref(frame.cframe()), 0, byref(r)))
+        elif isinstance(frame, YUY2Frame):
             _check(lib().vt_update_yuy2(self._h, _u8(frame.buf), frame.w, frame.h, 2 * frame.w,
                                         byref(r)))
         elif isinstance(frame, NV12Frame):
@@ -504,6 +587,15 @@ class VitTrack:
                                            byref(r)))
         return TrackResult(r)
 
+    def init_device(self, frame: "CFrame", bbox: BBox):
+        """any vt_pixfmt resident in this GPU's HBM (frame_nv12, frame_bgrx, ...): vt_init_frame(on_device=1)"""
+        _check(lib().vt_init_frame(self._h, byref(frame), 1, bbox._c()))
+
+    def update_device(self, frame: "CFrame") -> TrackResult:
+        r = CResult()
+        _check(lib().vt_update_frame(self._h, byref(frame), 1, byref(r)))
+        return TrackResult(r)
+
     def init_rgb8_device(self, d_rgb, w, h, stride, bbox: BBox):
         _check(lib().vt_init_rgb8_device(self._h, d_rgb, w, h, stride, bbox._c()))
 
@@ -519,6 +611,26 @@ def frame_nv12(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
 
 def frame_rgb8(d_rgb, w, h, stride=None) -> CFrame:
     return CFrame(d_rgb, None, w, h, stride or 3 * w, 0, PIX_RGB8, 0, 0, 0, 0, 0)
+
+
+def frame_bgr8(d_bgr, w, h, stride=None) -> CFrame:
+    return CFrame(d_bgr, None, w, h, stride or 3 * w, 0, PIX_BGR8, 0, 0, 0, 0, 0)
+
+
+def frame_rgbx(d_rgbx, w, h, stride=None) -> CFrame:
+    return CFrame(d_rgbx, None, w, h, stride or 4 * w, 0, PIX_RGBX, 0, 0, 0, 0, 0)
+
+
+def frame_bgrx(d_bgrx, w, h, stride=None) -> CFrame:
+    return CFrame(d_bgrx, None, w, h, stride or 4 * w, 0, PIX_BGRX, 0, 0, 0, 0, 0)
+
+
+def frame_nv21(d_y, d_vu, w, h, y_stride=None, vu_stride=None) -> CFrame:
+    return CFrame(d_y, d_vu, w, h, y_stride or w, vu_stride or ((w + 1) & ~1), PIX_NV21, 0, 0, 0, 0, 0)
+
+
+def frame_uyvy(d_uyvy, w, h, stride=None) -> CFrame:
+    return CFrame(d_uyvy, None, w, h, stride or 2 * w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
 
 
 class Group:
@@ -618,8 +730,10 @@ class Group:
 
     @staticmethod
     def _host_frame(frame):
-        """(CFrame with HOST pointers, keep-alive object) for an (H,W,3) RGB array, NV12Frame or
-        YUY2Frame"""
+        """(CFrame with HOST pointers, keep-alive object) for an (H,W,3) RGB array, NV12Frame, YUY2Frame or one of
+        the frame classes of the other formats"""
+        if isinstance(frame, _ANY_FRAMES):
+            return frame.cframe(), frame
         if isinstance(frame, NV12Frame):
             uv = frame.buf[frame.w * frame.h:]
             return CFrame(frame.buf.ctypes.data, uv.ctypes.data, frame.w, frame.h, frame.w,
@@ -672,7 +786,8 @@ class Group:
         return [TrackResult(r) for r in out]
 
     def graph_captures(self) -> int:
-        """hipGraph captures since creation: all crop tiers are captured when the engine is created, none inside a pass"""
+        """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
+        other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""
         return lib().vt_group_graph_captures(self._h)
 
     def host_redos(self) -> int:

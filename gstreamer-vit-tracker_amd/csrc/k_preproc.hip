@@ -270,7 +270,12 @@ hipError_t launch_nv12_to_rgb8(const uint8_t* nv12, int w, int h, uint8_t* rgb, 
     return hipGetLastError();
 }
 
-// frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding)
+// frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding).
+// ANY = false: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
+// constants); ANY = true: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_common.hpp). The
+// engine launches the ANY kernels only for passes that carry one of the other formats: reading the offsets at run time
+// costs the crop kernels 3-19 SGPRs (kernel-resource-usage), and those of the three original formats keep their budget.
+template <bool ANY>
 __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, float* rgb, int& miss) {
     if (px < 0 || py < 0 || px >= f.w || py >= f.h) {
         rgb[0] = rgb[1] = rgb[2] = 0.0f;
@@ -285,7 +290,23 @@ __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, fl
         miss = 1;
         return;
     }
-    if (f.fmt == VT_PIX_RGB8) {
+    if constexpr (ANY) {    // the masks keep every offset inside its pixel / pair
+        const int lay = f.lay;
+        if (f.fmt == PIXF_RGB) {            // RGB8, BGR8, RGBX, BGRX: colour bytes 0-2, permuted by the offsets
+            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * (unsigned)(lay >> 24);
+            const uint32_t c = __builtin_amdgcn_perm(0u, (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16),
+                                                     ((uint32_t)lay & 0x00ffffffu) | 0x0c000000u);
+            r = c & 255; g = (c >> 8) & 255; b = c >> 16;
+        } else if (f.fmt == PIXF_420SP) {   // NV12, NV21
+            const int y = f.p0[(size_t)sy * f.s0 + sx];
+            const uint8_t* uv = f.p1 + (size_t)(sy >> 1) * f.s1 + (sx & ~1);   // x0, y0 even
+            const uint32_t c = __builtin_amdgcn_perm(0u, (uint32_t)uv[0] | ((uint32_t)uv[1] << 8), ((uint32_t)lay & 0xffffu) | 0x0c0c0000u);
+            yuv_to_rgb(y, c & 255, c >> 8, r, g, b);
+        } else {                            // YUY2 (Y0 U Y1 V), UYVY (U Y0 V Y1) per pixel pair
+            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
+            yuv_to_rgb(p[(sx & 1) ? (lay >> 16) & 3 : lay & 3], p[(lay >> 8) & 3], p[(lay >> 24) & 3], r, g, b);
+        }
+    } else if (f.fmt == VT_PIX_RGB8) {
         const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * 3;
         r = p[0]; g = p[1]; b = p[2];
     } else if (f.fmt == VT_PIX_NV12) {
@@ -300,6 +321,7 @@ __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, fl
 }
 
 // grid: (ceil(size*size/256), nb); one lane per output pixel, 3 channels each.
+template <bool ANY>
 __global__ __launch_bounds__(256) void preproc_kernel(const FrameDesc* __restrict__ frames,
                                                       StreamState* __restrict__ states,
                                                       bf16_t* __restrict__ patches, int b0,
@@ -335,10 +357,10 @@ __global__ __launch_bounds__(256) void preproc_kernel(const FrameDesc* __restric
     const int iy = (int)fy0, ix = (int)fx0;
     float p00[3], p01[3], p10[3], p11[3];
     int miss = 0;
-    fetch_rgb(f, ix, iy, p00, miss);
-    fetch_rgb(f, ix + 1, iy, p01, miss);
-    fetch_rgb(f, ix, iy + 1, p10, miss);
-    fetch_rgb(f, ix + 1, iy + 1, p11, miss);
+    fetch_rgb<ANY>(f, ix, iy, p00, miss);
+    fetch_rgb<ANY>(f, ix + 1, iy, p01, miss);
+    fetch_rgb<ANY>(f, ix, iy + 1, p10, miss);
+    fetch_rgb<ANY>(f, ix + 1, iy + 1, p11, miss);
     if (miss && !is_template) s.window_miss = s.frames_done + 1;   // every writer stores the same value
     const int grid = size / patch;
     const int token = (oy / patch) * grid + (ox / patch);
@@ -362,7 +384,7 @@ __global__ __launch_bounds__(256) void preproc_kernel(const FrameDesc* __restric
 // the stores were 2-B scatters, 48 per 32-B segment. Same per-pixel arithmetic and tap order as
 // preproc_kernel (bit-exact with oracle/vt_oracle.c); neighbouring pixels re-fetch shared taps from
 // L1. grid: (ceil(size*size/PX/256), nb).
-template <int PX>
+template <int PX, bool ANY>
 __global__ __launch_bounds__(256) void preproc_wide_kernel(const FrameDesc* __restrict__ frames,
                                                            StreamState* __restrict__ states,
                                                            bf16_t* __restrict__ patches, int b0,
@@ -406,10 +428,10 @@ __global__ __launch_bounds__(256) void preproc_wide_kernel(const FrameDesc* __re
         const float wx = fx - fx0;
         const int ix = (int)fx0;
         float p00[3], p01[3], p10[3], p11[3];
-        fetch_rgb(f, ix, iy, p00, miss);
-        fetch_rgb(f, ix + 1, iy, p01, miss);
-        fetch_rgb(f, ix, iy + 1, p10, miss);
-        fetch_rgb(f, ix + 1, iy + 1, p11, miss);
+        fetch_rgb<ANY>(f, ix, iy, p00, miss);
+        fetch_rgb<ANY>(f, ix + 1, iy, p01, miss);
+        fetch_rgb<ANY>(f, ix, iy + 1, p10, miss);
+        fetch_rgb<ANY>(f, ix + 1, iy + 1, p11, miss);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float top = p00[c] + wx * (p01[c] - p00[c]);
@@ -470,7 +492,7 @@ __global__ __launch_bounds__(256) void preproc_wide_kernel(const FrameDesc* __re
 // (64 KiB, two blocks per CU: scales up to ~2.75, ~260 / ~175 px). A tile that still does not fit takes the per-pixel
 // path below - correct at any size, a 3-4x cliff in time (profiles/r05_preproc_by_target.txt) that tier 0 alone hit
 // from ~130-px targets. The tier changes which path a tile takes, never a value: every path is bit-exact.
-template <int LDSPX>
+template <int LDSPX, bool ANY>
 __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __restrict__ frames,
                                                            StreamState* __restrict__ states,
                                                            bf16_t* __restrict__ patches, int b0,
@@ -528,8 +550,14 @@ __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __re
         // loads - and converted with the same integer formulas. A group that is not entirely inside the
         // frame and the stored window goes through fetch_rgb pixel by pixel (frame border: black; outside the
         // window: black + miss), so every entry of the LDS image is what the per-pixel loop writes.
-        const bool fast = f.fmt == VT_PIX_NV12 && (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 7) == 0;
+        // NV21 takes the same path (ANY kernels): the descriptor says which byte of a pair is U
+        const bool fast = f.fmt == PIXF_420SP && (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 7) == 0;
+        // ANY kernels, 4-byte RGB formats (RGBX, BGRX) whose rows start on 16-byte boundaries (the library's packed
+        // windows; whole frames with such strides): ONE 16-byte load per 4 pixels, where the per-pixel path issues 12
+        // byte loads; the same edge rule as the NV12 groups
+        const bool fast4 = ANY && f.fmt == PIXF_RGB && (f.lay >> 24) == 4 && (((uintptr_t)f.p0 | (uintptr_t)f.s0) & 15) == 0;
         if (fast) {
+            const int us = ANY ? (f.lay & 1) * 8 : 0, vs = ANY ? ((f.lay >> 8) & 1) * 8 : 8;   // bit offsets of U, V in a pair
             const int g_lo = (sx_lo - f.x0) >> 3, g_hi = (sx_hi - f.x0) >> 3;     // arithmetic shift: floor for negatives
             const int gpr = g_hi - g_lo + 1, ng = gpr * (int)sh;
             for (int i = threadIdx.x; i < ng; i += 256) {
@@ -548,7 +576,7 @@ __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __re
                         if (col < 0 || col >= w_) continue;
                         const uint32_t pair = uw[k >> 2] >> (((k >> 1) & 1) * 16);   // U, V of the pixel pair
                         int r, g, b;
-                        yuv_to_rgb((int)((yw[k >> 2] >> ((k & 3) * 8)) & 255u), (int)(pair & 255u), (int)((pair >> 8) & 255u), r, g, b);
+                        yuv_to_rgb((int)((yw[k >> 2] >> ((k & 3) * 8)) & 255u), (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
                         dst[k] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
                     }
                 } else {
@@ -557,7 +585,36 @@ __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __re
                         if (col < 0 || col >= w_) continue;
                         float p[3];
                         int miss = 0;
-                        fetch_rgb(f, px0 + k, py, p, miss);
+                        fetch_rgb<ANY>(f, px0 + k, py, p, miss);
+                        dst[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
+                    }
+                }
+            }
+        } else if (fast4) {
+            const uint32_t sel = ((uint32_t)f.lay & 0x00ffffffu) | 0x0c000000u;   // bytes R, G, B, zero of a pixel
+            const int g_lo = (sx_lo - f.x0) >> 2, g_hi = (sx_hi - f.x0) >> 2;     // arithmetic shift: floor for negatives
+            const int gpr = g_hi - g_lo + 1, ng = gpr * (int)sh;
+            for (int i = threadIdx.x; i < ng; i += 256) {
+                const int ry = i / gpr, wx0 = (g_lo + i % gpr) << 2;                // window column of the group
+                const int py = sy_lo + ry, wy_ = py - f.y0, px0 = wx0 + f.x0;
+                const bool inside = (unsigned)wy_ < (unsigned)f.wh && (unsigned)py < (unsigned)f.h && wx0 >= 0 &&
+                                    wx0 + 3 < f.ww && px0 >= 0 && px0 + 3 < f.w;
+                uint32_t* dst = src + ry * w_ + (px0 - sx_lo);
+                if (inside) {
+                    const u32x4_t q = *reinterpret_cast<const u32x4_t*>(f.p0 + (size_t)wy_ * f.s0 + (size_t)wx0 * 4);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int col = px0 - sx_lo + k;
+                        if (col < 0 || col >= w_) continue;
+                        dst[k] = __builtin_amdgcn_perm(0u, q[k], sel);              // r | g << 8 | b << 16
+                    }
+                } else {
+                    for (int k = 0; k < 4; ++k) {
+                        const int col = px0 - sx_lo + k;
+                        if (col < 0 || col >= w_) continue;
+                        float p[3];
+                        int miss = 0;
+                        fetch_rgb<ANY>(f, px0 + k, py, p, miss);
                         dst[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
                     }
                 }
@@ -566,7 +623,7 @@ __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __re
             for (int i = threadIdx.x; i < n; i += 256) {
                 float p[3];
                 int miss = 0;
-                fetch_rgb(f, sx_lo + i % w_, sy_lo + i / w_, p, miss);
+                fetch_rgb<ANY>(f, sx_lo + i % w_, sy_lo + i / w_, p, miss);
                 src[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
             }
         }
@@ -594,10 +651,10 @@ __global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __re
             const float wx = fx - fx0;
             const int ix = (int)fx0;
             float p00[3], p01[3], p10[3], p11[3];
-            fetch_rgb(f, ix, iy, p00, miss);
-            fetch_rgb(f, ix + 1, iy, p01, miss);
-            fetch_rgb(f, ix, iy + 1, p10, miss);
-            fetch_rgb(f, ix + 1, iy + 1, p11, miss);
+            fetch_rgb<ANY>(f, ix, iy, p00, miss);
+            fetch_rgb<ANY>(f, ix + 1, iy, p01, miss);
+            fetch_rgb<ANY>(f, ix, iy + 1, p10, miss);
+            fetch_rgb<ANY>(f, ix + 1, iy + 1, p11, miss);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float top = p00[c] + wx * (p01[c] - p00[c]);
@@ -650,9 +707,10 @@ int preproc_tier_for_box(const ModelDims& d, float w, float h, bool is_template)
     return px <= PRE_TILE_LDS ? 0 : (px <= 2 * PRE_TILE_LDS ? 1 : (px <= 4 * PRE_TILE_LDS ? 2 : 3));
 }
 
-hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
-                          const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
-                          const int32_t* slot_stream) {
+template <bool ANY>
+static void launch_preproc_t(const FrameDesc* frames, StreamState* states, bf16_t* patches,
+                             const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
+                             const int32_t* slot_stream) {
     const int size = is_template ? d.T : d.S;
     const int row_off = is_template ? 0 : d.nt;
     const float factor = is_template ? 2.0f : 4.0f;
@@ -661,20 +719,27 @@ hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* 
     // store alignment: a run starts at element c*p*p + py*p + px0 of a row of kpad elements
     if (d.patch % 8 == 0 && d.kpad % 8 == 0 && size % PRE_TILE_W == 0 && size % PRE_TILE_H == 0) {
         dim3 grid((size / PRE_TILE_W) * (size / PRE_TILE_H), nb);   // 64 x 32 output tiles, source staged in LDS
-        if (tier <= 0) vt_launch(preproc_tile_kernel<PRE_TILE_LDS>, grid, dim3(256), 0, st, PRE_ARGS);
-        else if (tier == 1) vt_launch(preproc_tile_kernel<2 * PRE_TILE_LDS>, grid, dim3(256), 0, st, PRE_ARGS);
-        else vt_launch(preproc_tile_kernel<4 * PRE_TILE_LDS>, grid, dim3(256), 0, st, PRE_ARGS);
+        if (tier <= 0) vt_launch(preproc_tile_kernel<PRE_TILE_LDS, ANY>, grid, dim3(256), 0, st, PRE_ARGS);
+        else if (tier == 1) vt_launch(preproc_tile_kernel<2 * PRE_TILE_LDS, ANY>, grid, dim3(256), 0, st, PRE_ARGS);
+        else vt_launch(preproc_tile_kernel<4 * PRE_TILE_LDS, ANY>, grid, dim3(256), 0, st, PRE_ARGS);
     } else if (d.patch % 8 == 0 && d.kpad % 8 == 0) {          // 16-B stores
         dim3 grid((size * size / 8 + 255) / 256, nb);
-        vt_launch(preproc_wide_kernel<8>, grid, dim3(256), 0, st, PRE_ARGS);
+        vt_launch(preproc_wide_kernel<8, ANY>, grid, dim3(256), 0, st, PRE_ARGS);
     } else if (d.patch % 2 == 0 && d.kpad % 2 == 0) {          // 4-B stores (patch 14)
         dim3 grid((size * size / 2 + 255) / 256, nb);
-        vt_launch(preproc_wide_kernel<2>, grid, dim3(256), 0, st, PRE_ARGS);
+        vt_launch(preproc_wide_kernel<2, ANY>, grid, dim3(256), 0, st, PRE_ARGS);
     } else {
         dim3 grid((size * size + 255) / 256, nb);
-        vt_launch(preproc_kernel, grid, dim3(256), 0, st, PRE_ARGS);
+        vt_launch(preproc_kernel<ANY>, grid, dim3(256), 0, st, PRE_ARGS);
     }
 #undef PRE_ARGS
+}
+
+hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
+                          const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
+                          const int32_t* slot_stream, bool any_layout) {
+    if (any_layout) launch_preproc_t<true>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
+    else launch_preproc_t<false>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
     return hipGetLastError();
 }
 

@@ -358,9 +358,11 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
     FrameDesc* hf = e->h_block(0);
+    e->any_layout = false;
     for (int b = 0; b < e->B; ++b) {
         if (int rc = check_frame(frames[b])) return rc;
         to_desc(frames[b], hf + b);
+        e->any_layout = e->any_layout || pix_any_layout(frames[b].format);
     }
     *(PassOut*)(hf + e->B) = PassOut{e->h_results, e->h_states_all};
     HIPCHK(hipMemcpyAsync(e->d_frames, hf, e->frames_block_bytes(), hipMemcpyHostToDevice, e->stream));
@@ -601,6 +603,28 @@ int vt_update_nv12_device(vt_tracker* t, const void* d_y, const void* d_uv, int 
                           int uv_stride, vt_result* out) try {
     if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
     vt_frame f = dev_frame(VT_PIX_NV12, d_y, d_uv, w, h, y_stride, uv_stride);
+    return do_update(t, &f, out);
+} VT_NOTHROW_INT
+
+// any vt_pixfmt: host planes are staged like vt_init_rgb8's buffer (the search window only), device planes go to the
+// kernels as they are (like the *_device calls)
+int vt_init_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_bbox box) try {
+    if (!t || !frame) return set_err(VT_ERR_INVALID_ARG, "null tracker or frame");
+    if (on_device != 0 && on_device != 1) return set_err(VT_ERR_INVALID_ARG, "on_device must be 0 or 1");
+    if (on_device) return do_init(t, frame, box);
+    vt_frame f;
+    const float fb[1][4] = {{(float)box.x, (float)box.y, (float)box.width, (float)box.height}};
+    if (int rc = stage_host_frames(t->e, frame, 1, fb, &f)) return rc;
+    return do_init(t, &f, box);
+} VT_NOTHROW_INT
+int vt_update_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_result* out) try {
+    if (!t || !frame) return set_err(VT_ERR_INVALID_ARG, "null tracker or frame");
+    if (on_device != 0 && on_device != 1) return set_err(VT_ERR_INVALID_ARG, "on_device must be 0 or 1");
+    if (on_device) return do_update(t, frame, out);
+    if (!t->e->h_initialized[0]) return set_err(VT_ERR_NOT_INITIALIZED, "update before init");
+    vt_frame f;
+    const float(*kb)[4] = (const float(*)[4])t->e->known[0].box;
+    if (int rc = stage_host_frames(t->e, frame, 1, kb, &f)) return rc;
     return do_update(t, &f, out);
 } VT_NOTHROW_INT
 

@@ -14,14 +14,58 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 
+// Pixel layout families: every vt_pixfmt is one family plus the byte offsets of its components (FrameDesc.lay). The
+// family codes are the vt_pixfmt values of the formats that defined them, so those formats' descriptors are unchanged.
+enum PixFamily {
+    PIXF_RGB = VT_PIX_RGB8,       // packed R,G,B(,x): lay = R | G << 8 | B << 16 (byte offsets) | bytes per pixel << 24
+    PIXF_420SP = VT_PIX_NV12,     // Y plane + interleaved chroma pairs: lay = U offset in the pair | V offset << 8
+    PIXF_422 = VT_PIX_YUY2        // packed pixel pairs: lay = Y0 | U << 8 | Y1 << 16 | V << 24 (byte offsets)
+};
+
+// family of a vt_pixfmt (-1: unknown) and its layout word
+inline int pix_family(int fmt) {
+    switch (fmt) {
+    case VT_PIX_RGB8: case VT_PIX_BGR8: case VT_PIX_RGBX: case VT_PIX_BGRX: return PIXF_RGB;
+    case VT_PIX_NV12: case VT_PIX_NV21: return PIXF_420SP;
+    case VT_PIX_YUY2: case VT_PIX_UYVY: return PIXF_422;
+    default: return -1;
+    }
+}
+inline int32_t pix_layout(int fmt) {
+    switch (fmt) {
+    case VT_PIX_RGB8: return 0 | 1 << 8 | 2 << 16 | 3 << 24;
+    case VT_PIX_BGR8: return 2 | 1 << 8 | 0 << 16 | 3 << 24;
+    case VT_PIX_RGBX: return 0 | 1 << 8 | 2 << 16 | 4 << 24;
+    case VT_PIX_BGRX: return 2 | 1 << 8 | 0 << 16 | 4 << 24;
+    case VT_PIX_NV12: return 0 | 1 << 8;
+    case VT_PIX_NV21: return 1 | 0 << 8;
+    case VT_PIX_YUY2: return 0 | 1 << 8 | 2 << 16 | 3 << 24;
+    case VT_PIX_UYVY: return 1 | 0 << 8 | 3 << 16 | 2 << 24;
+    default: return 0;
+    }
+}
+// name of a vt_pixfmt for error texts
+inline const char* pix_name(int fmt) {
+    static const char* const names[] = {"rgb8", "nv12", "yuy2", "bgr8", "rgbx", "bgrx", "nv21", "uyvy"};
+    return fmt >= 0 && fmt < 8 ? names[fmt] : "?";
+}
+// the crop kernels that read f.lay (k_preproc.hip) are needed for this format
+inline bool pix_any_layout(int fmt) { return fmt != VT_PIX_RGB8 && fmt != VT_PIX_NV12 && fmt != VT_PIX_YUY2; }
+// bytes per pixel of plane 0's rows (4:2:0 semi-planar: the Y plane)
+inline int pix_row_bpp(int fmt) {
+    const int fam = pix_family(fmt);
+    return fam == PIXF_RGB ? pix_layout(fmt) >> 24 : fam == PIXF_422 ? 2 : 1;
+}
+
 // one device-resident input frame (mirrors vt_frame, 64-bit pointers)
 struct FrameDesc {
-    const uint8_t* p0;  // RGB8 packed pixels or NV12 Y plane
-    const uint8_t* p1;  // NV12 interleaved UV plane
-    int32_t w, h, s0, s1, fmt;
+    const uint8_t* p0;  // packed pixels, or the Y plane of 4:2:0 semi-planar
+    const uint8_t* p1;  // 4:2:0 semi-planar: the interleaved chroma plane
+    int32_t w, h, s0, s1;
+    int32_t fmt;        // PixFamily
     int32_t x0, y0;     // frame coordinates of the first stored pixel (window upload)
     int32_t ww, wh;     // extent of the stored window in pixels: samples outside it read as black
-    int32_t pad;
+    int32_t lay;        // byte layout within the family (PixFamily)
 };
 static_assert(sizeof(FrameDesc) == 56, "FrameDesc layout");
 
@@ -183,9 +227,10 @@ hipError_t launch_attention_mode(const bf16_t* qk, const bf16_t* vt, bf16_t* out
 // tier: the tile kernel's LDS buffer (0: 16 KiB, 1: 32 KiB, 2 or more: 64 KiB), a choice of speed only
 // slot_stream (device, [nb + b0] or null = identity): the stream a slot works for. Frame descriptor and patch rows are
 // the slot's; the StreamState read (and its geo / frame_w / frame_h / window_miss written) is the stream's.
+// any_layout: some slot's frame is not RGB8, NV12 or YUY2 (its layout is read from FrameDesc.lay: k_preproc.hip, fetch_rgb)
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
                           const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier = 0,
-                          const int32_t* slot_stream = nullptr);
+                          const int32_t* slot_stream = nullptr, bool any_layout = false);
 // subset passes: slot i's template rows [nt][kpad] of the patch matrix <- the template store tpl[slot_stream[i]]
 hipError_t launch_gather_template_rows(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream, int n,
                                        const ModelDims& d, hipStream_t st);

@@ -66,6 +66,9 @@ void Engine::drop_graphs() {
         if (graph_exec[t]) (void)hipGraphExecDestroy(graph_exec[t]);
         if (graph[t]) (void)hipGraphDestroy(graph[t]);
         graph_exec[t] = nullptr; graph[t] = nullptr;
+        if (graph_exec_any[t]) (void)hipGraphExecDestroy(graph_exec_any[t]);
+        if (graph_any[t]) (void)hipGraphDestroy(graph_any[t]);
+        graph_exec_any[t] = nullptr; graph_any[t] = nullptr;
     }
 }
 
@@ -399,7 +402,7 @@ int Engine::run_pass(Profiler* prof, int n, const int32_t* slot_stream) {
         L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
           [&] { return launch_gather_template_rows(d_tpl, d_patches, slot_stream, n, d, stream); });
     L("preproc_search", 0, (double)n * (d.S * d.S * 3 * 2 + 1.5 * d.S * d.S),
-      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, n, false, stream, crop_tier, slot_stream); });
+      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, n, false, stream, crop_tier, slot_stream, any_layout); });
     // K2: patch embedding (+bias +pos) -> residual stream (3-byte pair + chunk statistics)
     {
         GemmArgs a{};
@@ -536,8 +539,8 @@ int Engine::capture_graph(int tier) {
         (void)hipGraphDestroy(g);
         return set_err(e == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     }
-    graph[tier] = g;
-    graph_exec[tier] = x;
+    (any_layout ? graph_any : graph)[tier] = g;
+    (any_layout ? graph_exec_any : graph_exec)[tier] = x;
     graph_captures += 1;
     return VT_OK;
 }
@@ -545,25 +548,35 @@ int Engine::capture_graph(int tier) {
 // Every crop-buffer tier's pass, captured and instantiated NOW (engine creation, vt_group_set_tuning): the hot path only
 // replays. A live stream whose target grows across a tier boundary (~130 / ~200 px at search 384) must not pay a
 // capture + instantiate inside an update (60 fps: /root/reference/src/pipeline.rs:26-37).
+// With want_any_graphs, the passes of the crop kernels that read any vt_pixfmt too (Engine::init_stream sets it).
 int Engine::capture_all_graphs() {
     if (!use_graph) return VT_OK;
     const int keep = crop_tier;
-    for (int t = 0; t < TIERS; ++t)
-        if (!graph_exec[t])
-            if (int rc = capture_graph(t)) { crop_tier = keep; return rc; }
+    const bool keep_any = any_layout;
+    int rc = VT_OK;
+    for (int v = 0; v < (want_any_graphs ? 2 : 1) && rc == VT_OK; ++v) {
+        any_layout = v == 1;
+        const hipGraphExec_t* ex = any_layout ? graph_exec_any : graph_exec;
+        for (int t = 0; t < TIERS && rc == VT_OK; ++t)
+            if (!ex[t]) rc = capture_graph(t);
+    }
     crop_tier = keep;
-    return VT_OK;
+    any_layout = keep_any;
+    return rc;
 }
 
+// every format is checked by its family (vt_common.hpp: PixFamily): 4:2:0 semi-planar by the rules of NV12, packed
+// 4:2:2 by those of YUY2, packed RGB by its bytes per pixel
 int check_frame(const vt_frame& f) {
     if (!f.plane0 || f.width < 16 || f.height < 16 || f.width > 16384 || f.height > 16384)
         return set_err(VT_ERR_INVALID_ARG, "frame: null plane or size out of range");
-    if (f.format != VT_PIX_RGB8 && f.format != VT_PIX_NV12 && f.format != VT_PIX_YUY2)
+    const int fam = pix_family(f.format);
+    if (fam < 0)
         return set_err(VT_ERR_INVALID_ARG, "unknown pixel format %d", f.format);
     const bool window = f.origin_x != 0 || f.origin_y != 0 || f.windowed == 1;
     if (f.origin_x < 0 || f.origin_y < 0 || f.origin_x >= f.width || f.origin_y >= f.height ||
-        (f.format == VT_PIX_NV12 && ((f.origin_x | f.origin_y) & 1)) ||
-        (f.format == VT_PIX_YUY2 && (f.origin_x & 1)))
+        (fam == PIXF_420SP && ((f.origin_x | f.origin_y) & 1)) ||
+        (fam == PIXF_422 && (f.origin_x & 1)))
         return set_err(VT_ERR_INVALID_ARG, "frame window origin %d,%d invalid", f.origin_x, f.origin_y);
     // extent of what the planes hold: the kernels never read outside it (fetch_rgb, k_preproc.hip)
     int ww = f.width, wh = f.height;
@@ -575,21 +588,23 @@ int check_frame(const vt_frame& f) {
                            "(got %dx%d at %d,%d of %dx%d)", f.window_w, f.window_h, f.origin_x, f.origin_y,
                            f.width, f.height);
         ww = f.window_w; wh = f.window_h;
-        if (f.format == VT_PIX_NV12 && (((ww & 1) && f.origin_x + ww != f.width) ||
-                                        ((wh & 1) && f.origin_y + wh != f.height)))
-            return set_err(VT_ERR_INVALID_ARG, "nv12 window extent must be even unless it ends at the frame edge");
+        if (fam == PIXF_420SP && (((ww & 1) && f.origin_x + ww != f.width) ||
+                                  ((wh & 1) && f.origin_y + wh != f.height)))
+            return set_err(VT_ERR_INVALID_ARG, "%s window extent must be even unless it ends at the frame edge",
+                           pix_name(f.format));
     } else if (f.window_w != 0 || f.window_h != 0) {
         if (f.window_w != f.width || f.window_h != f.height)
             return set_err(VT_ERR_INVALID_ARG, "window_w/window_h set on a frame that is not windowed");
     }
-    if (f.format == VT_PIX_RGB8) {
-        if (f.stride0 < ww * 3) return set_err(VT_ERR_INVALID_ARG, "rgb8 stride < 3*width");
-    } else if (f.format == VT_PIX_NV12) {
+    if (fam == PIXF_RGB) {
+        const int bpp = pix_row_bpp(f.format);
+        if (f.stride0 < ww * bpp) return set_err(VT_ERR_INVALID_ARG, "%s stride < %d*width", pix_name(f.format), bpp);
+    } else if (fam == PIXF_420SP) {
         if (!f.plane1 || f.stride0 < ww || f.stride1 < ((ww + 1) & ~1))
-            return set_err(VT_ERR_INVALID_ARG, "nv12: null UV plane or stride too small");
+            return set_err(VT_ERR_INVALID_ARG, "%s: null UV plane or stride too small", pix_name(f.format));
     } else {
         if ((f.width & 1) || f.stride0 < ((ww + 1) & ~1) * 2)
-            return set_err(VT_ERR_INVALID_ARG, "yuy2: odd width or stride < 2*width");
+            return set_err(VT_ERR_INVALID_ARG, "%s: odd width or stride < 2*width", pix_name(f.format));
     }
     return VT_OK;
 }
@@ -598,11 +613,12 @@ void to_desc(const vt_frame& f, FrameDesc* o) {
     const bool window = f.origin_x != 0 || f.origin_y != 0 || f.windowed == 1;
     o->p0 = (const uint8_t*)f.plane0;
     o->p1 = (const uint8_t*)f.plane1;
-    o->w = f.width; o->h = f.height; o->s0 = f.stride0; o->s1 = f.stride1; o->fmt = f.format;
+    o->w = f.width; o->h = f.height; o->s0 = f.stride0; o->s1 = f.stride1;
+    o->fmt = pix_family(f.format);      // RGB8, NV12, YUY2: their own value
     o->x0 = f.origin_x; o->y0 = f.origin_y;
     o->ww = window ? f.window_w : f.width;
     o->wh = window ? f.window_h : f.height;
-    o->pad = 0;
+    o->lay = pix_layout(f.format);
 }
 
 int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
@@ -614,6 +630,13 @@ int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
                        box.width, box.height);
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
+    // the first stream on a format other than RGB8 / NV12 / YUY2: every tier's pass with the crop kernels that read the
+    // layout is captured here, before anything changes, so that no update of such a stream captures (a failure leaves
+    // the engine as it was, apart from the tiers already captured, which stay valid)
+    if (use_graph && !want_any_graphs && pix_any_layout(f->format)) {
+        want_any_graphs = true;
+        if (int rc = capture_all_graphs()) { want_any_graphs = false; return rc; }
+    }
     memset(h_state, 0, sizeof(StreamState));
     h_state->box[0] = (float)box.x; h_state->box[1] = (float)box.y;
     h_state->box[2] = (float)box.width; h_state->box[3] = (float)box.height;
@@ -624,7 +647,8 @@ int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
     to_desc(*f, slot);
     HIPCHK(hipMemcpyAsync(d_frames + b, slot, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
     HIPCHK(launch_preproc(d_frames, d_states, d_patches, d, b, 1, true, stream,
-                          preproc_tier_for_box(d, (float)box.width, (float)box.height, true)));
+                          preproc_tier_for_box(d, (float)box.width, (float)box.height, true), nullptr,
+                          pix_any_layout(f->format)));
     // the stream's template rows, kept for the subset passes that run it in another slot
     HIPCHK(hipMemcpyAsync(d_tpl + (size_t)b * d.nt * d.kpad, d_patches + (size_t)b * d.ntok * d.kpad,
                           sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
@@ -657,7 +681,11 @@ int Engine::enqueue(const vt_frame* frames, int n, vt_result* host_res, StreamSt
     ring_pos = (ring_pos + 1) % RING;
     HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copy that last used this slot is done
     FrameDesc* hf = h_block(slot);
-    for (int b = 0; b < B; ++b) to_desc(frames[b], hf + b);
+    any_layout = false;
+    for (int b = 0; b < B; ++b) {
+        to_desc(frames[b], hf + b);
+        any_layout = any_layout || pix_any_layout(frames[b].format);
+    }
     *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all};
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipEventRecord(ring_ev[slot], stream));
@@ -666,11 +694,16 @@ int Engine::enqueue(const vt_frame* frames, int n, vt_result* host_res, StreamSt
     pass_streams.clear();
     const int tier = pick_crop_tier();
     if (use_graph && !taps) {
-        if (!graph_exec[tier])      // not reached after a successful creation (capture_all_graphs); kept as the safe path
+        if (!any_layout && !graph_exec[tier])   // not reached after a successful creation (capture_all_graphs); kept as the safe path
             if (int rc = capture_graph(tier)) return rc;
-        HIPCHK(hipGraphLaunch(graph_exec[tier], stream));
-        graph_replays[tier] += 1;
-        return VT_OK;
+        // passes with another format replay the graphs captured when a stream was initialised on one; without them
+        // (every stream was initialised on RGB8 / NV12 / YUY2) the pass launches eagerly: no capture inside an update
+        hipGraphExec_t x = any_layout ? graph_exec_any[tier] : graph_exec[tier];
+        if (x) {
+            HIPCHK(hipGraphLaunch(x, stream));
+            graph_replays[tier] += 1;
+            return VT_OK;
+        }
     }
     crop_tier = tier;
     return run_pass(nullptr, B, nullptr);
@@ -707,7 +740,11 @@ int Engine::enqueue_streams(const int32_t* streams, const vt_frame* frames, int 
     ring_pos = (ring_pos + 1) % RING;
     HIPCHK(hipEventSynchronize(ring_ev[slot]));
     FrameDesc* hf = h_block(slot);
-    for (int i = 0; i < n; ++i) to_desc(frames[i], hf + i);
+    any_layout = false;
+    for (int i = 0; i < n; ++i) {
+        to_desc(frames[i], hf + i);
+        any_layout = any_layout || pix_any_layout(frames[i].format);
+    }
     *(PassOut*)(hf + B) = PassOut{h_results, h_states_all};
     int32_t* map = (int32_t*)((char*)hf + map_offset());
     for (int i = 0; i < n; ++i) map[i] = streams[i];

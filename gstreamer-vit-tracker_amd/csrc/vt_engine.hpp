@@ -164,6 +164,13 @@ struct Engine {
     static constexpr int TIERS = 3;
     hipGraph_t graph[TIERS] = {nullptr, nullptr, nullptr};
     hipGraphExec_t graph_exec[TIERS] = {nullptr, nullptr, nullptr};
+    // the same passes with the crop kernels that read any vt_pixfmt (k_preproc.hip: fetch_rgb<true>), for passes that
+    // carry a format other than RGB8 / NV12 / YUY2: all tiers captured together (capture_all_graphs) when the first
+    // stream is initialised on such a format - never inside an update
+    hipGraph_t graph_any[TIERS] = {nullptr, nullptr, nullptr};
+    hipGraphExec_t graph_exec_any[TIERS] = {nullptr, nullptr, nullptr};
+    bool want_any_graphs = false;                 // a stream was initialised on such a format: capture_all_graphs takes them too
+    bool any_layout = false;                      // the pass being enqueued carries such a format
     int crop_tier = 0;                            // tier of the pass being enqueued (from the boxes the host knows)
     int crop_tier_forced = -1;                    // >= 0: tests / A-B runs (vt_group_set_tuning "crop_tier")
     int graph_captures = 0;                       // hipGraph captures since creation (vt_group_graph_captures)
@@ -213,7 +220,7 @@ struct Engine {
     // n slots (M = n * ntok); slot_stream: the device map of a subset pass, null for a full pass (n == B)
     int run_pass(Profiler* prof, int n, const int32_t* slot_stream);
     int restore_segments();             // every stream's template rows back into its own segment (after a subset pass)
-    int capture_graph(int tier);
+    int capture_graph(int tier);                  // into graph_exec_any when any_layout
     int capture_all_graphs();
     int pick_crop_tier(const int32_t* streams = nullptr, int n = 0) const;   // streams == null: all B
     void drop_graphs();

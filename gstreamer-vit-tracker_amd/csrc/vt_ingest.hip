@@ -21,17 +21,26 @@ struct HostWin {
 
 // `grow`: enlargement of the crop side for a SPECULATIVE window (the box of the pass that is still
 // running is not known): 0 = the exact crop
+// row pitch of a packed format's window in the arena: 4-byte pixels on 16-byte boundaries (the crop kernel then fetches
+// 4 pixels per load), the others back to back
+static size_t packed_row_bytes(int fmt, int ww) {
+    const size_t rb = (size_t)ww * pix_row_bpp(fmt);
+    return pix_row_bpp(fmt) == 4 ? (rb + 15) & ~(size_t)15 : rb;
+}
+
 static int plan_window(const Engine* e, int fmt, const uint8_t* p0, const uint8_t* p1, int w, int h,
                        int s0, int s1, const float* box, float grow, HostWin* win) {
     if (!p0 || w < 16 || h < 16) return set_err(VT_ERR_INVALID_ARG, "null frame or size < 16");
     if (w > e->max_w || h > e->max_h)
         return set_err(VT_ERR_INVALID_ARG, "frame %dx%d exceeds configured max %dx%d", w, h, e->max_w, e->max_h);
-    if (fmt == VT_PIX_RGB8) {
-        if (s0 < 3 * w) return set_err(VT_ERR_INVALID_ARG, "rgb8 stride < 3*width");
-    } else if (fmt == VT_PIX_YUY2) {
-        if ((w & 1) || s0 < 2 * w) return set_err(VT_ERR_INVALID_ARG, "yuy2: odd width or stride < 2*width");
-    } else if (fmt == VT_PIX_NV12) {
-        if (!p1 || s0 < w || s1 < ((w + 1) & ~1)) return set_err(VT_ERR_INVALID_ARG, "nv12: bad plane or stride");
+    // by family (vt_common.hpp: PixFamily); the messages name the format
+    const int fam = pix_family(fmt), bpp = pix_row_bpp(fmt);
+    if (fam == PIXF_RGB) {
+        if (s0 < bpp * w) return set_err(VT_ERR_INVALID_ARG, "%s stride < %d*width", pix_name(fmt), bpp);
+    } else if (fam == PIXF_422) {
+        if ((w & 1) || s0 < 2 * w) return set_err(VT_ERR_INVALID_ARG, "%s: odd width or stride < 2*width", pix_name(fmt));
+    } else if (fam == PIXF_420SP) {
+        if (!p1 || s0 < w || s1 < ((w + 1) & ~1)) return set_err(VT_ERR_INVALID_ARG, "%s: bad plane or stride", pix_name(fmt));
     } else {
         return set_err(VT_ERR_INVALID_ARG, "unknown pixel format %d", fmt);
     }
@@ -50,7 +59,7 @@ static int plan_window(const Engine* e, int fmt, const uint8_t* p0, const uint8_
     win->fmt = fmt; win->w = w; win->h = h; win->s0 = s0; win->s1 = s1; win->p0 = p0; win->p1 = p1;
     win->x_lo = (int)x_lo; win->y_lo = (int)y_lo;
     win->ww = (int)(x_hi - x_lo); win->wh = (int)(y_hi - y_lo);
-    if (fmt == VT_PIX_NV12) {
+    if (fam == PIXF_420SP) {
         // rows of the packed window start on 16-byte boundaries: the pixel kernel then fetches 8 pixels per load
         const int uvh = (win->wh + 1) / 2;
         const size_t ys = ((size_t)win->ww + 15) & ~(size_t)15, uvs = ((size_t)((win->ww + 1) & ~1) + 15) & ~(size_t)15;
@@ -58,7 +67,7 @@ static int plan_window(const Engine* e, int fmt, const uint8_t* p0, const uint8_
         win->bytes = win->uv_off + uvs * uvh;
     } else {
         win->uv_off = 0;
-        win->bytes = (size_t)win->ww * win->wh * (fmt == VT_PIX_RGB8 ? 3 : 2);
+        win->bytes = packed_row_bytes(fmt, win->ww) * win->wh;
     }
     win->bytes = (win->bytes + 255) & ~(size_t)255;
     return VT_OK;
@@ -96,12 +105,12 @@ static void pack_window(const Arena& a, const HostWin& wn, size_t off, vt_frame*
     f->origin_x = wn.x_lo; f->origin_y = wn.y_lo;
     f->windowed = 1;   // strides describe the packed window
     f->window_w = wn.ww; f->window_h = wn.wh;
-    if (wn.fmt == VT_PIX_RGB8 || wn.fmt == VT_PIX_YUY2) {
-        const size_t bpp = wn.fmt == VT_PIX_RGB8 ? 3 : 2;
-        const size_t rb = (size_t)wn.ww * bpp;
+    if (pix_family(wn.fmt) != PIXF_420SP) {
+        const size_t bpp = (size_t)pix_row_bpp(wn.fmt);
+        const size_t rb = (size_t)wn.ww * bpp, rs = packed_row_bytes(wn.fmt, wn.ww);   // as plan_window
         for (int r = 0; r < wn.wh; ++r)
-            memcpy(dst + r * rb, wn.p0 + (size_t)(wn.y_lo + r) * wn.s0 + (size_t)wn.x_lo * bpp, rb);
-        f->plane0 = *a.d + off; f->stride0 = (int)rb;
+            memcpy(dst + r * rs, wn.p0 + (size_t)(wn.y_lo + r) * wn.s0 + (size_t)wn.x_lo * bpp, rb);
+        f->plane0 = *a.d + off; f->stride0 = (int)rs;
     } else {
         const int uvw = (wn.ww + 1) & ~1, uvh = (wn.wh + 1) / 2;
         const size_t ys = ((size_t)wn.ww + 15) & ~(size_t)15, uvs = ((size_t)uvw + 15) & ~(size_t)15;   // as plan_window
@@ -135,12 +144,13 @@ static int stage_host_frames_to(Engine* e, const Arena& a, const vt_frame* host,
         const bool zc = e->host_zero_copy > 0 || (e->host_zero_copy == 0 && e->B == 1);
         if (!zc) { total += wins[i].bytes; continue; }
         // bytes the kernels may touch: every row of the frame, the last one only as far as it is wide
-        const size_t rowb = hf.format == VT_PIX_NV12 ? (size_t)hf.width : hf.format == VT_PIX_RGB8 ? (size_t)hf.width * 3 : (size_t)hf.width * 2;
+        const bool sp = pix_family(hf.format) == PIXF_420SP;
+        const size_t rowb = (size_t)hf.width * pix_row_bpp(hf.format);
         const size_t ext0 = (size_t)(hf.height - 1) * (size_t)hf.stride0 + rowb;
-        const size_t ext1 = hf.format == VT_PIX_NV12 ? (size_t)((hf.height + 1) / 2 - 1) * (size_t)hf.stride1 + (size_t)((hf.width + 1) & ~1) : 0;
+        const size_t ext1 = sp ? (size_t)((hf.height + 1) / 2 - 1) * (size_t)hf.stride1 + (size_t)((hf.width + 1) & ~1) : 0;
         const uint8_t* d0 = mapped_device_ptr(e->device, (const uint8_t*)hf.plane0, ext0);
-        const uint8_t* d1 = hf.format == VT_PIX_NV12 ? mapped_device_ptr(e->device, (const uint8_t*)hf.plane1, ext1) : nullptr;
-        if (d0 && (hf.format != VT_PIX_NV12 || d1)) {
+        const uint8_t* d1 = sp ? mapped_device_ptr(e->device, (const uint8_t*)hf.plane1, ext1) : nullptr;
+        if (d0 && (!sp || d1)) {
             mapped[(size_t)i] = 1;
             memset(&dev[i], 0, sizeof(vt_frame));
             dev[i].plane0 = d0; dev[i].plane1 = d1; dev[i].width = hf.width; dev[i].height = hf.height;

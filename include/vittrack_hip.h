@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
+#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); VT_PIX_BGR8 .. VT_PIX_UYVY, vt_init_frame / vt_update_frame (added later still, additions only for the same reason); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
 
 typedef enum vt_status {
     VT_OK = 0,
@@ -188,28 +188,45 @@ void vt_free_device_blob(int device_id, void* d_blob);
 
 /* VT_PIX_YUY2: packed 4:2:2, bytes Y0 U Y1 V per pixel pair (the format the reference's IR
  * pipeline captures, src/pipeline_ir.rs:27-41, before GStreamer's videoconvert turns it into RGB);
- * converted per sampled pixel with the same BT.601 integer formulas as NV12. */
-typedef enum vt_pixfmt { VT_PIX_RGB8 = 0, VT_PIX_NV12 = 1, VT_PIX_YUY2 = 2 } vt_pixfmt;
+ * converted per sampled pixel with the same BT.601 integer formulas as NV12.
+ * Formats 3-7 are byte permutations or paddings of the first three and sample exactly as they do. */
+typedef enum vt_pixfmt {
+    VT_PIX_RGB8 = 0,
+    VT_PIX_NV12 = 1,
+    VT_PIX_YUY2 = 2,
+    VT_PIX_BGR8 = 3,   /* packed B,G,R, stride >= 3*w (OpenCV's order): RGB8 with the channels reversed */
+    VT_PIX_RGBX = 4,   /* packed R,G,B,x, stride >= 4*w (RGBA: alpha ignored): RGB8 */
+    VT_PIX_BGRX = 5,   /* packed B,G,R,x, stride >= 4*w (BGRA: alpha ignored): RGB8 with the channels reversed */
+    VT_PIX_NV21 = 6,   /* Y plane + interleaved V,U plane: NV12 with U and V swapped, window rules of NV12 */
+    VT_PIX_UYVY = 7    /* packed U Y0 V Y1, w even: YUY2 with the bytes reordered, window rules of YUY2 */
+} vt_pixfmt;
 
 typedef struct vt_frame {        /* one device-resident frame (or a window of it) */
-    const void* plane0;          /* RGB8: packed pixels; NV12: Y plane */
-    const void* plane1;          /* NV12: interleaved UV plane; RGB8: NULL */
+    const void* plane0;          /* packed formats: the pixels; NV12 / NV21: Y plane */
+    const void* plane1;          /* NV12 / NV21: interleaved UV / VU plane; packed formats: NULL */
     int32_t width, height;       /* size of the FULL frame in pixels */
     int32_t stride0, stride1;    /* bytes */
     int32_t format;              /* vt_pixfmt */
     /* The planes may hold only a window of the frame: plane0 points at frame pixel
-     * (origin_x, origin_y) (NV12: both even; plane1 at the matching UV pair). Pixels of the frame
+     * (origin_x, origin_y) (NV12 / NV21: both even, plane1 at the matching chroma pair; YUY2 /
+     * UYVY: origin_x even). Pixels of the frame
      * outside the stored window must not be needed by the call (the tracker reads the search
      * window, side 4*sqrt(w*h) around the last box, plus one pixel). 0,0 = the whole frame. */
     int32_t origin_x, origin_y;
     int32_t windowed;            /* 1: the planes hold only window_w x window_h pixels (strides
                                   * describe that window); 0 with origin 0,0: the whole frame */
     /* Extent of the stored window in pixels (required when windowed == 1 or an origin is set; both
-     * even for NV12, window_w even for YUY2, unless the window ends at the frame's edge). A sample
+     * even for NV12 / NV21, window_w even for YUY2 / UYVY, unless the window ends at the frame's edge). A sample
      * that falls inside the frame but outside the stored window reads as black - never out of
      * bounds. 0,0 with no origin: width x height. */
     int32_t window_w, window_h;
 } vt_frame;
+
+/* The single tracker on a frame of any vt_pixfmt. on_device == 0: the planes are host addresses, read
+ * like vt_init_rgb8 reads its buffer (only the search window crosses PCIe; origin fields ignored);
+ * on_device == 1: they are device addresses, used like the *_device calls' (windows honoured). */
+int vt_init_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_bbox box);
+int vt_update_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_result* out);
 
 int vt_group_create(const char* weights_path, int device_id, const vt_config* cfg, vt_group** out);
 int vt_group_create_from_device_blob(const void* d_blob, size_t bytes, int device_id,
@@ -261,7 +278,11 @@ int vt_group_host_redos(const vt_group* g);
 /* hipGraph captures this engine has made since creation. The pass is replayed as a captured graph, one per
  * crop-buffer tier; all of them are captured and instantiated when the engine is created (and again by
  * vt_group_set_tuning), never inside an enqueue: a live 60-fps stream (src/pipeline.rs:26-37) whose target grows
- * across a tier boundary takes no capture stall mid-track. Constant after creation unless the tuning is changed. */
+ * across a tier boundary takes no capture stall mid-track. Passes that carry a format other than RGB8, NV12 and YUY2
+ * replay a second set of graphs (crop kernels that read the byte layout): all its tiers are captured inside the init
+ * call (vt_group_init_*, vt_init_*) that first initialises a stream on such a format, again never inside an enqueue.
+ * A pass with such a format on an engine none of whose streams was initialised on one launches eagerly. Constant
+ * after creation unless the tuning is changed or that first init happens. */
 int vt_group_graph_captures(const vt_group* g);
 /* One pass over the n streams streams[0..n): distinct, each initialised, 1 <= n <= vt_group_streams.
  * frames[i] feeds streams[i]; out[i] / vt_group_wait's i-th entry is its result. Streams not listed are
