@@ -224,3 +224,33 @@ pub fn nv12_full_to_rgb(nv12: &[u8], w: usize, h: usize, device: i32) -> Result<
     }
     Ok(out)
 }
+
+/// The pipelined subset pass of a group (vt_group_enqueue_host_streams): `host_frames[i]` feeds `streams[i]`; collect
+/// with `sys::vt_group_wait_next`. A multi-camera host calls this for the cameras that are tracking this frame
+/// (src/tracker_context.rs:90,120) while the previous frame's pass is still running.
+///
+/// # Safety
+/// `g` is a live group handle; the planes of `host_frames` stay valid and unchanged until the pass is collected.
+pub unsafe fn group_enqueue_host_streams(g: *mut sys::vt_group, streams: &[i32], host_frames: &[sys::VtFrame]) -> Result<(), TrackError> {
+    if streams.len() != host_frames.len() || streams.len() > c_int::MAX as usize {
+        return Err(TrackError { code: sys::VT_ERR_INVALID_ARG, text: "one frame per listed stream expected".into() });
+    }
+    let rc = sys::vt_group_enqueue_host_streams(g, streams.as_ptr(), host_frames.as_ptr(), streams.len() as c_int);
+    if rc != sys::VT_OK {
+        return Err(last(rc));
+    }
+    Ok(())
+}
+
+/// ≙ tracker.init (src/tracker_context.rs:88) on one camera of a group while the others keep tracking
+/// (vt_group_enqueue_init_host): queued behind the outstanding pipelined passes, no wait for them.
+///
+/// # Safety
+/// `g` is a live group handle; `host_frame`'s planes are readable for the duration of the call.
+pub unsafe fn group_enqueue_init_host(g: *mut sys::vt_group, stream: i32, host_frame: &sys::VtFrame, bbox: BBox) -> Result<(), TrackError> {
+    let rc = sys::vt_group_enqueue_init_host(g, stream, host_frame, bbox);
+    if rc != sys::VT_OK {
+        return Err(last(rc));
+    }
+    Ok(())
+}

@@ -194,6 +194,8 @@ extern "C" {
                                           out: *mut VtResult) -> c_int;
     pub fn vt_group_update_host_streams(g: *mut vt_group, streams: *const i32, host_frames: *const VtFrame, n: c_int,
                                         out: *mut VtResult) -> c_int;
+    pub fn vt_group_enqueue_host_streams(g: *mut vt_group, streams: *const i32, host_frames: *const VtFrame, n: c_int) -> c_int;
+    pub fn vt_group_enqueue_init_host(g: *mut vt_group, stream: c_int, host_frame: *const VtFrame, bbox: BBox) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

@@ -95,6 +95,7 @@ EXPORTS = [
     "vt_overlay_rgb8_device",
     "vt_group_profile_device", "vt_group_enable_taps", "vt_group_set_tuning", "vt_group_set_state_box", "vt_tracker_as_group",
     "vt_group_read_tensor", "vt_group_enqueue_device_streams", "vt_group_update_device_streams", "vt_group_update_host_streams",
+    "vt_group_enqueue_host_streams", "vt_group_enqueue_init_host",
     "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob", "vt_init_frame", "vt_update_frame",
 ]
 # every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
@@ -171,6 +172,8 @@ def lib():
     L.vt_group_enqueue_device_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int]
     L.vt_group_update_device_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int, POINTER(CResult)]
     L.vt_group_update_host_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int, POINTER(CResult)]
+    L.vt_group_enqueue_host_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int]
+    L.vt_group_enqueue_init_host.argtypes = [c_void_p, c_int, POINTER(CFrame), CBBox]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -762,27 +765,41 @@ class Group:
         self._last_n = len(pairs)
         return [TrackResult(r) for r in out]
 
-    def enqueue_host(self, frames):
+    def enqueue_init_host(self, stream: int, frame, bbox: BBox):
+        """(re)initialise `stream` behind the outstanding pipelined passes without waiting for them
+        (vt_group_enqueue_init_host); the stream must be in none of them. The frame is consumed before this returns."""
+        f, keep = self._host_frame(frame)
+        _check(lib().vt_group_enqueue_init_host(self._h, stream, byref(f), bbox._c()))
+
+    def enqueue_host(self, frames, streams=None):
         """pipelined host pass: returns once the windows are packed and the upload + pass are
-        enqueued; collect with wait_next(). The frames must stay alive and unchanged until then
-        (this wrapper keeps references)."""
+        enqueued; collect with wait_next(). streams=None: all streams (frames[i] feeds stream i), else
+        frames[i] feeds streams[i] and no other stream is touched (vt_group_enqueue_host_streams). The frames
+        must stay alive and unchanged until then (this wrapper keeps references)."""
         pairs = [self._host_frame(fr) for fr in frames]
-        arr = (CFrame * len(pairs))(*[p[0] for p in pairs])
-        _check(lib().vt_group_enqueue_host(self._h, arr, len(pairs)))
-        self._last_n = None       # pipelined passes cover every stream
+        arr = (CFrame * max(len(pairs), 1))(*[p[0] for p in pairs])
+        if streams is None:
+            _check(lib().vt_group_enqueue_host(self._h, arr, len(pairs)))
+        else:
+            _check(lib().vt_group_enqueue_host_streams(self._h, self._streams(streams, len(pairs)), arr, len(pairs)))
+        self._last_n = None       # the results of a pipelined pass come from wait_next()
         if not hasattr(self, "_keep") or self._keep is None:
             self._keep = {}
+        # the frames and the size of every outstanding pass, oldest first
         self._keep[self._keep.get("seq", 0)] = pairs
         self._keep["seq"] = self._keep.get("seq", 0) + 1
 
     def wait_next(self):
-        n = self.streams
+        """results of the oldest uncollected pipelined pass, as many as it had streams, in its order"""
+        keep = getattr(self, "_keep", None) or {}
+        pairs = keep.get(keep.get("done", 0))
+        n = len(pairs) if pairs else self.streams
         out = (CResult * n)()
         _check(lib().vt_group_wait_next(self._h, out, n))
-        if getattr(self, "_keep", None):
-            done = self._keep.get("done", 0)
-            self._keep.pop(done, None)
-            self._keep["done"] = done + 1
+        if keep:
+            done = keep.get("done", 0)
+            keep.pop(done, None)
+            keep["done"] = done + 1
         return [TrackResult(r) for r in out]
 
     def graph_captures(self) -> int:

@@ -53,6 +53,17 @@ void Engine::destroy() {
         if (sl.done_ev) (void)hipEventDestroy(sl.done_ev);
         sl = HostSlot();
     }
+    for (QueuedInit* q : qinits) {
+        if (!q) continue;
+        if (q->d_arena) (void)hipFree(q->d_arena);
+        if (q->h_arena) (void)hipHostFree(q->h_arena);
+        if (q->h_state) (void)hipHostFree(q->h_state);
+        if (q->h_desc) (void)hipHostFree(q->h_desc);
+        if (q->up_ev) (void)hipEventDestroy(q->up_ev);
+        if (q->done_ev) (void)hipEventDestroy(q->done_ev);
+        delete q;
+    }
+    qinits.clear();
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
     for (int i = 0; i < RING; ++i)
         if (ring_ev[i]) (void)hipEventDestroy(ring_ev[i]);
@@ -621,13 +632,38 @@ void to_desc(const vt_frame& f, FrameDesc* o) {
     o->lay = pix_layout(f.format);
 }
 
-int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
-    if (b < 0 || b >= B || !f) return set_err(VT_ERR_INVALID_ARG, "init: bad stream index");
-    if (int rc = check_frame(*f)) return rc;
+int Engine::check_init_box(vt_bbox box) const {
     if (box.width < 1 || box.height < 1 || box.width > 32768 || box.height > 32768 ||
         box.x < -32768 || box.y < -32768 || box.x > 32768 || box.y > 32768)
         return set_err(VT_ERR_INVALID_ARG, "init: bbox %d,%d %dx%d out of range", box.x, box.y,
                        box.width, box.height);
+    return VT_OK;
+}
+
+int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st, FrameDesc* h_desc) {
+    memset(h_st, 0, sizeof(StreamState));
+    h_st->box[0] = (float)box.x; h_st->box[1] = (float)box.y;
+    h_st->box[2] = (float)box.width; h_st->box[3] = (float)box.height;
+    h_st->frame_w = f->width; h_st->frame_h = f->height;
+    h_st->initialized = 1;
+    HIPCHK(hipMemcpyAsync(d_states + b, h_st, sizeof(StreamState), hipMemcpyHostToDevice, stream));
+    to_desc(*f, h_desc);
+    // entry b of the per-pass block: every pass uploads its own block ahead of its kernels, in stream order
+    HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
+    HIPCHK(launch_preproc(d_frames, d_states, d_patches, d, b, 1, true, stream,
+                          preproc_tier_for_box(d, (float)box.width, (float)box.height, true), nullptr,
+                          pix_any_layout(f->format)));
+    // the stream's template rows, kept for the subset passes that run it in another slot (and for the full pass that
+    // follows one: restore_segments puts every stream's rows back from here, these included)
+    HIPCHK(hipMemcpyAsync(d_tpl + (size_t)b * d.nt * d.kpad, d_patches + (size_t)b * d.ntok * d.kpad,
+                          sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
+    return VT_OK;
+}
+
+int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
+    if (b < 0 || b >= B || !f) return set_err(VT_ERR_INVALID_ARG, "init: bad stream index");
+    if (int rc = check_frame(*f)) return rc;
+    if (int rc = check_init_box(box)) return rc;
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     // the first stream on a format other than RGB8 / NV12 / YUY2: every tier's pass with the crop kernels that read the
@@ -637,21 +673,8 @@ int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
         want_any_graphs = true;
         if (int rc = capture_all_graphs()) { want_any_graphs = false; return rc; }
     }
-    memset(h_state, 0, sizeof(StreamState));
-    h_state->box[0] = (float)box.x; h_state->box[1] = (float)box.y;
-    h_state->box[2] = (float)box.width; h_state->box[3] = (float)box.height;
-    h_state->frame_w = f->width; h_state->frame_h = f->height;
-    h_state->initialized = 1;
-    HIPCHK(hipMemcpyAsync(d_states + b, h_state, sizeof(StreamState), hipMemcpyHostToDevice, stream));
-    FrameDesc* slot = h_frames;  // stream is idle: ring slot 0 is free
-    to_desc(*f, slot);
-    HIPCHK(hipMemcpyAsync(d_frames + b, slot, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
-    HIPCHK(launch_preproc(d_frames, d_states, d_patches, d, b, 1, true, stream,
-                          preproc_tier_for_box(d, (float)box.width, (float)box.height, true), nullptr,
-                          pix_any_layout(f->format)));
-    // the stream's template rows, kept for the subset passes that run it in another slot
-    HIPCHK(hipMemcpyAsync(d_tpl + (size_t)b * d.nt * d.kpad, d_patches + (size_t)b * d.ntok * d.kpad,
-                          sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
+    // stream is idle: h_state and ring slot 0 are free
+    if (int rc = launch_init(b, f, box, h_state, h_frames)) return rc;
     HIPCHK(hipStreamSynchronize(stream));
     h_states_all[b] = *h_state;
     known[b] = *h_state;
@@ -727,14 +750,15 @@ int Engine::check_streams(const int32_t* streams, int n) const {
 // A pass over the streams streams[0..n) on n compacted slots: slot i takes frames[i] and works for stream streams[i];
 // no other stream's state is touched. The full identity list is the full pass (captured graph); any other list runs
 // eagerly - never a capture inside an update - behind the gather of its template rows.
-int Engine::enqueue_streams(const int32_t* streams, const vt_frame* frames, int n) {
+int Engine::enqueue_streams(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res,
+                            StreamState* host_st) {
     if (int rc = check_streams(streams, n)) return rc;
     if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
     for (int i = 0; i < n; ++i)
         if (int rc = check_frame(frames[i])) return rc;
     bool identity = n == B;
     for (int i = 0; i < n && identity; ++i) identity = streams[i] == i;
-    if (identity) return enqueue(frames, n);
+    if (identity) return enqueue(frames, n, host_res, host_st);
     DEVICE_SCOPE(device);
     const int slot = ring_pos;
     ring_pos = (ring_pos + 1) % RING;
@@ -745,7 +769,7 @@ int Engine::enqueue_streams(const int32_t* streams, const vt_frame* frames, int 
         to_desc(frames[i], hf + i);
         any_layout = any_layout || pix_any_layout(frames[i].format);
     }
-    *(PassOut*)(hf + B) = PassOut{h_results, h_states_all};
+    *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all};
     int32_t* map = (int32_t*)((char*)hf + map_offset());
     for (int i = 0; i < n; ++i) map[i] = streams[i];
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));

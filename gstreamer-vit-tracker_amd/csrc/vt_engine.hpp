@@ -186,17 +186,34 @@ struct Engine {
     // host-side copy of the stream states after the last pass the HOST has collected (window planning
     // reads this, never a pinned buffer a running pass may still write)
     std::vector<StreamState> known;
-    // pipelined host passes (vt_group_enqueue_host / vt_group_wait_next): two slots, each with its own
+    // pipelined host passes (vt_group_enqueue_host[_streams] / vt_group_wait_next): two slots, each with its own
     // pinned + device arena, result buffers, state snapshot and events; uploads go on copy_stream
     struct HostSlot {
         uint8_t *d_arena = nullptr, *h_arena = nullptr;
         size_t bytes = 0;
-        vt_result* h_res = nullptr;
-        StreamState* h_st = nullptr;
+        vt_result* h_res = nullptr;     // the pass's results, by SLOT (list order)
+        StreamState* h_st = nullptr;    // [B] by STREAM: valid at the listed streams' indices only
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
         std::vector<vt_frame> host;     // the caller's frames, valid until the pass is collected
-        bool pending = false, speculative = false, redone = false;
+        std::vector<int32_t> list;      // the pass's streams (the identity list: the full pass)
+        std::vector<char> spec;         // per listed stream: its window was speculative (it was in the pass then outstanding)
+        bool pending = false, redone = false;
+        bool lists(int stream) const { return std::find(list.begin(), list.end(), stream) != list.end(); }
     } hs[2];
+    // staging of the queued inits (vt_group_enqueue_init_host): each owns its pinned state + descriptor, its window
+    // arena and the event behind its work on the group's stream; one is reused once that event has passed
+    struct QueuedInit {
+        uint8_t *d_arena = nullptr, *h_arena = nullptr;
+        size_t bytes = 0;
+        StreamState* h_state = nullptr;
+        FrameDesc* h_desc = nullptr;
+        hipEvent_t up_ev = nullptr, done_ev = nullptr;
+    };
+    std::vector<QueuedInit*> qinits;
+    int check_init_box(vt_bbox box) const;
+    // the state write, the template crop and its copy to d_tpl, on the group's stream; h_st / h_desc: pinned staging
+    // that stays untouched until that work is done
+    int launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st, FrameDesc* h_desc);
     hipStream_t copy_stream = nullptr;
     unsigned host_seq = 0, host_collected = 0;   // pipelined passes enqueued / collected
     unsigned host_redos = 0;                      // passes redone because a speculative window missed
@@ -230,7 +247,8 @@ struct Engine {
     // one pass over streams[0..n): VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input; a
     // full identity list is the full pass
     int check_streams(const int32_t* streams, int n) const;
-    int enqueue_streams(const int32_t* streams, const vt_frame* frames, int n);
+    int enqueue_streams(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
+                        StreamState* host_st = nullptr);
     int wait(vt_result* out, int n);
     int init_stream(int b, const vt_frame* f, vt_bbox box);
     const TensorRef* find(const std::string& n) const {

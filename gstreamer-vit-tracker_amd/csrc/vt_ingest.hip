@@ -127,21 +127,23 @@ static void pack_window(const Arena& a, const HostWin& wn, size_t off, vt_frame*
 }
 
 // n host frames -> n device frame descriptors (windows packed, ONE H2D copy enqueued on a.copy_on).
-// boxes[i]: the box that decides stream i's window (the new box at init, the last state at update).
+// boxes[i]: the box that decides frame i's window (the new box at init, the last state at update);
+// grow[i]: its enlargement (plan_window), null: every window exact. pack_all: no zero-copy route, whatever the
+// configuration says (the kernels must not read the caller's memory after the call has returned).
 static int stage_host_frames_to(Engine* e, const Arena& a, const vt_frame* host, int n, const float (*boxes)[4],
-                                float grow, vt_frame* dev, size_t* bytes_out) {
+                                const float* grow, vt_frame* dev, size_t* bytes_out, bool pack_all = false) {
     std::vector<HostWin> wins((size_t)n);
     std::vector<char> mapped((size_t)n, 0);
     size_t total = 0;
     for (int i = 0; i < n; ++i) {
         const vt_frame& hf = host[i];
         if (int rc = plan_window(e, hf.format, (const uint8_t*)hf.plane0, (const uint8_t*)hf.plane1, hf.width,
-                                 hf.height, hf.stride0, hf.stride1, boxes[i], grow, &wins[i]))
+                                 hf.height, hf.stride0, hf.stride1, boxes[i], grow ? grow[i] : 0.0f, &wins[i]))
             return rc;
         // a frame inside a range mapped by vt_host_register goes to the kernels as it lies (zero copy) - on
         // single-stream engines, or where the caller asked for it: for a batched engine the packed upload beside
         // the previous pass is faster than PCIe reads inside the pass (vt_config.host_zero_copy, vittrack_hip.h)
-        const bool zc = e->host_zero_copy > 0 || (e->host_zero_copy == 0 && e->B == 1);
+        const bool zc = !pack_all && (e->host_zero_copy > 0 || (e->host_zero_copy == 0 && e->B == 1));
         if (!zc) { total += wins[i].bytes; continue; }
         // bytes the kernels may touch: every row of the frame, the last one only as far as it is wide
         const bool sp = pix_family(hf.format) == PIXF_420SP;
@@ -178,7 +180,7 @@ static int stage_host_frames_to(Engine* e, const Arena& a, const vt_frame* host,
 // for its pass before returning, so the arena is free again at the next call)
 int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev) {
     const Arena a{&e->d_stage, &e->h_pack, &e->stage_bytes, e->stream};
-    return stage_host_frames_to(e, a, host, n, boxes, 0.0f, dev, nullptr);
+    return stage_host_frames_to(e, a, host, n, boxes, nullptr, dev, nullptr);
 }
 
 int stage_host_frame(Engine* e, int fmt, const uint8_t* p0, const uint8_t* p1, int w, int h,
@@ -209,21 +211,95 @@ static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
     return VT_OK;
 }
 
-// exact (non-speculative) synchronous pass over `host` with the states the device holds now; results
-// and states land in the slot's buffers
-static int host_pass_exact_sync(Engine* e, Engine::HostSlot& sl) {
-    const int n = e->B;
-    std::vector<vt_frame> dev((size_t)n);
+// the boxes the windows of a pass over streams[0..n) are planned around: the last the host knows
+static std::vector<float> known_boxes(const Engine* e, const int32_t* streams, int n) {
     std::vector<float> boxes((size_t)n * 4);
-    for (int b = 0; b < n; ++b) memcpy(&boxes[(size_t)b * 4], e->known[b].box, 4 * sizeof(float));
+    for (int i = 0; i < n; ++i) memcpy(&boxes[(size_t)i * 4], e->known[streams[i]].box, 4 * sizeof(float));
+    return boxes;
+}
+
+// a collected (or redone) pass becomes what the host knows: the entries of ITS streams move, no others. The
+// decode kernel stores a slot's results by slot and its states by stream (k_head.hip: decode_box).
+static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
+    for (size_t i = 0; i < sl.list.size(); ++i) {
+        const int s = sl.list[i];
+        e->known[s] = sl.h_st[s];
+        e->h_states_all[s] = sl.h_st[s];        // the engine's own mirrors follow
+        e->h_results[i] = sl.h_res[i];
+    }
+}
+
+// exact (non-speculative) synchronous pass over the slot's frames and list with the states the device holds
+// now; results and states land in the slot's buffers
+static int host_pass_exact_sync(Engine* e, Engine::HostSlot& sl) {
+    const int n = (int)sl.list.size();
+    std::vector<vt_frame> dev((size_t)n);
+    const std::vector<float> boxes = known_boxes(e, sl.list.data(), n);
     if (int rc = stage_host_frames(e, sl.host.data(), n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
         return rc;
-    if (int rc = e->enqueue(dev.data(), n)) return rc;
+    if (int rc = e->enqueue_streams(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
-    memcpy(sl.h_res, e->h_results, sizeof(vt_result) * n);
-    memcpy(sl.h_st, e->h_states_all, sizeof(StreamState) * n);
-    for (int b = 0; b < n; ++b) e->known[b] = e->h_states_all[b];
+    adopt_slot(e, sl);
     sl.redone = true;
+    return VT_OK;
+}
+
+// One pipelined pass over streams[0..n) (checked by the caller): windows packed into the free slot's arena and
+// uploaded on the copy stream, the pass enqueued behind that upload. vt_group_enqueue_host is the identity list.
+static int enqueue_host_pass(Engine* e, const int32_t* streams, const vt_frame* host_frames, int n, const char* what) {
+    const unsigned outstanding = e->host_seq - e->host_collected;
+    if (outstanding >= 2)
+        return set_err(VT_ERR_INVALID_ARG, "%s: two passes outstanding, call vt_group_wait_next first", what);
+    DEVICE_SCOPE(e->device);
+    Engine::HostSlot& sl = e->hs[e->host_seq & 1];
+    if (int rc = host_slot_prepare(e, sl)) return rc;
+    if (outstanding == 0) {
+        // nothing of ours is running: make sure nothing else is either, then the boxes are exact
+        if (int rc = e->wait(nullptr, 0)) return rc;
+    }
+    // a stream that is in the pass still outstanding has a box nobody knows yet: its window is cut around the last
+    // known one, enlarged; every other stream's known box is exact, and so is its window - it cannot cause a redo
+    const Engine::HostSlot& older = e->hs[(e->host_seq + 1) & 1];
+    std::vector<char> spec((size_t)n, 0);
+    std::vector<float> grow((size_t)n, 0.0f);
+    for (int i = 0; i < n; ++i)
+        if (outstanding == 1 && older.lists(streams[i])) { spec[(size_t)i] = 1; grow[(size_t)i] = e->margin; }
+    std::vector<vt_frame> dev((size_t)n);
+    const std::vector<float> boxes = known_boxes(e, streams, n);
+    const Arena a{&sl.d_arena, &sl.h_arena, &sl.bytes, e->copy_stream};
+    if (int rc = stage_host_frames_to(e, a, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()),
+                                      grow.data(), dev.data(), nullptr))
+        return rc;
+    HIPCHK(hipEventRecord(sl.up_ev, e->copy_stream));
+    HIPCHK(hipStreamWaitEvent(e->stream, sl.up_ev, 0));          // the pass starts behind ITS upload only
+    if (int rc = e->enqueue_streams(streams, dev.data(), n, sl.h_res, sl.h_st)) return rc;   // results land in THIS slot's buffers
+    HIPCHK(hipEventRecord(sl.done_ev, e->stream));
+    sl.host.assign(host_frames, host_frames + n);
+    sl.list.assign(streams, streams + n);
+    sl.spec.swap(spec);
+    sl.redone = false;
+    sl.pending = true;
+    e->host_seq += 1;
+    return VT_OK;
+}
+
+// staging for one queued init with an arena of `need` bytes: one whose work on the group's stream is done, else a
+// new one. Never grown in place: freeing device memory waits for the device, and a queued init waits for nothing.
+static int queued_init_staging(Engine* e, size_t need, Engine::QueuedInit** out) {
+    for (Engine::QueuedInit* q : e->qinits)
+        if (q && q->bytes >= need && q->done_ev && hipEventQuery(q->done_ev) == hipSuccess) { *out = q; return VT_OK; }
+    (void)hipGetLastError();                 // hipErrorNotReady of the queries above is no error
+    e->qinits.push_back(nullptr);
+    Engine::QueuedInit* q = e->qinits.back() = new Engine::QueuedInit();   // the engine's from here on, whatever fails below
+    HIPCHK(hipHostMalloc((void**)&q->h_state, sizeof(StreamState)));
+    HIPCHK(hipHostMalloc((void**)&q->h_desc, sizeof(FrameDesc)));
+    HIPCHK(hipEventCreateWithFlags(&q->up_ev, hipEventDisableTiming));
+    const size_t cap = need + need / 2 + 4096;
+    HIPCHK(hipMalloc((void**)&q->d_arena, cap));
+    HIPCHK(hipHostMalloc((void**)&q->h_arena, cap));
+    q->bytes = cap;
+    HIPCHK(hipEventCreateWithFlags(&q->done_ev, hipEventDisableTiming));   // last: a half-built one is never picked
+    *out = q;
     return VT_OK;
 }
 
@@ -285,32 +361,67 @@ int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n) try {
     if (n != e->B) return set_err(VT_ERR_INVALID_ARG, "enqueue_host: need exactly %d frames", e->B);
     for (int b = 0; b < n; ++b)
         if (!e->h_initialized[b]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d not initialised", b);
-    const unsigned outstanding = e->host_seq - e->host_collected;
-    if (outstanding >= 2)
-        return set_err(VT_ERR_INVALID_ARG, "enqueue_host: two passes outstanding, call vt_group_wait_next first");
-    DEVICE_SCOPE(e->device);
-    Engine::HostSlot& sl = e->hs[e->host_seq & 1];
-    if (int rc = host_slot_prepare(e, sl)) return rc;
-    if (outstanding == 0) {
-        // nothing of ours is running: make sure nothing else is either, then the boxes are exact
-        if (int rc = e->wait(nullptr, 0)) return rc;
-    }
-    sl.host.assign(host_frames, host_frames + n);
-    sl.speculative = outstanding == 1;
-    sl.redone = false;
-    std::vector<vt_frame> dev((size_t)n);
-    std::vector<float> boxes((size_t)n * 4);
-    for (int b = 0; b < n; ++b) memcpy(&boxes[(size_t)b * 4], e->known[b].box, 4 * sizeof(float));
-    const Arena a{&sl.d_arena, &sl.h_arena, &sl.bytes, e->copy_stream};
-    if (int rc = stage_host_frames_to(e, a, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()),
-                                      sl.speculative ? e->margin : 0.0f, dev.data(), nullptr))
+    std::vector<int32_t> all((size_t)n);
+    for (int b = 0; b < n; ++b) all[(size_t)b] = b;
+    return enqueue_host_pass(e, all.data(), host_frames, n, "enqueue_host");
+} VT_NOTHROW_INT
+
+int vt_group_enqueue_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n) try {
+    if (!g || !host_frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    Engine* e = g->e;
+    if (int rc = e->check_streams(streams, n)) return rc;
+    return enqueue_host_pass(e, streams, host_frames, n, "enqueue_host_streams");
+} VT_NOTHROW_INT
+
+int vt_group_enqueue_init_host(vt_group* g, int stream, const vt_frame* host_frame, vt_bbox box) try {
+    if (!g || !host_frame) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    Engine* e = g->e;
+    if (stream < 0 || stream >= e->B) return set_err(VT_ERR_INVALID_ARG, "bad stream index");
+    if (e->host_seq == e->host_collected) return vt_group_init_host(g, stream, host_frame, box);
+    for (const Engine::HostSlot& sl : e->hs)
+        if (sl.pending && sl.lists(stream))
+            return set_err(VT_ERR_INVALID_ARG, "enqueue_init_host: stream %d is in an outstanding pass, collect it "
+                           "first (vt_group_wait_next)", stream);
+    if (int rc = e->check_init_box(box)) return rc;
+    // the frame's own checks, before anything is allocated or changed
+    const float fb[1][4] = {{(float)box.x, (float)box.y, (float)box.width, (float)box.height}};
+    HostWin probe;
+    if (int rc = plan_window(e, host_frame->format, (const uint8_t*)host_frame->plane0, (const uint8_t*)host_frame->plane1,
+                             host_frame->width, host_frame->height, host_frame->stride0, host_frame->stride1, fb[0], 0.0f,
+                             &probe))
         return rc;
-    HIPCHK(hipEventRecord(sl.up_ev, e->copy_stream));
-    HIPCHK(hipStreamWaitEvent(e->stream, sl.up_ev, 0));          // the pass starts behind ITS upload only
-    if (int rc = e->enqueue(dev.data(), n, sl.h_res, sl.h_st)) return rc;   // results land in THIS slot's buffers
-    HIPCHK(hipEventRecord(sl.done_ev, e->stream));
-    sl.pending = true;
-    e->host_seq += 1;
+    DEVICE_SCOPE(e->device);
+    // the first stream on a format other than RGB8 / NV12 / YUY2 has the second graph set captured (Engine::init_stream);
+    // a capture needs the group's stream idle, so this one call waits for the outstanding passes (they stay
+    // uncollected): never a capture beside a running pass
+    if (e->use_graph && !e->want_any_graphs && pix_any_layout(host_frame->format)) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->want_any_graphs = true;
+        if (int rc = e->capture_all_graphs()) { e->want_any_graphs = false; return rc; }
+    }
+    Engine::QueuedInit* q = nullptr;
+    if (int rc = queued_init_staging(e, probe.bytes, &q)) return rc;
+    // window packed into the init's own pinned arena now (the caller's buffer is free on return), uploaded on the
+    // copy stream; the state write and the template crop go on the group's stream behind the passes already queued
+    // and behind that upload. Nothing here waits for the group's stream.
+    vt_frame f;
+    size_t up_bytes = 0;
+    const Arena a{&q->d_arena, &q->h_arena, &q->bytes, e->copy_stream};
+    // packed also from registered memory: the crop runs after this call has returned
+    if (int rc = stage_host_frames_to(e, a, host_frame, 1, fb, nullptr, &f, &up_bytes, true)) return rc;
+    if (int rc = check_frame(f)) return rc;
+    if (up_bytes) {
+        HIPCHK(hipEventRecord(q->up_ev, e->copy_stream));
+        HIPCHK(hipStreamWaitEvent(e->stream, q->up_ev, 0));
+    }
+    const int rc = e->launch_init(stream, &f, box, q->h_state, q->h_desc);
+    HIPCHK(hipEventRecord(q->done_ev, e->stream));   // also after a failed launch: the staging is busy until then
+    if (rc) return rc;
+    // what the host knows of this stream is its init state from now on: the next window is cut around the init box,
+    // exact, and a rewind behind this init restores the initialised state (the template rows are not rewound)
+    e->known[stream] = *q->h_state;
+    e->h_states_all[stream] = *q->h_state;
+    e->h_initialized[stream] = 1;
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -322,34 +433,39 @@ int vt_group_wait_next(vt_group* g, vt_result* out, int n) try {
     Engine::HostSlot& sl = e->hs[e->host_collected & 1];
     Engine::HostSlot& younger = e->hs[(e->host_collected + 1) & 1];
     const bool has_younger = e->host_seq - e->host_collected == 2;
+    const int pass_n = (int)sl.list.size();
     if (!sl.redone) {
         HIPCHK(hipEventSynchronize(sl.done_ev));
         bool miss = false;
-        if (sl.speculative)
-            for (int b = 0; b < e->B; ++b)
-                miss = miss || (sl.h_st[b].window_miss != 0 && sl.h_st[b].window_miss == sl.h_st[b].frames_done);
+        for (int i = 0; i < pass_n; ++i) {
+            const StreamState& st = sl.h_st[sl.list[(size_t)i]];
+            miss = miss || (sl.spec[(size_t)i] && st.window_miss != 0 && st.window_miss == st.frames_done);
+        }
         if (miss) {
-            // a stream moved out of its speculative window: rewind to the states this pass started
-            // from - `known`, the host's copy of the states the previous pass left (collected by the
-            // wait_next before this one) - and redo it, and the pass queued behind it, which consumed
-            // its wrong states, with exact windows
+            // a stream moved out of its speculative window: rewind the streams of this pass and of the one queued
+            // behind it to the states they started from - `known`, the host's copy of the states the last collected
+            // pass (or a queued init) left each of them - and redo this pass over its list, then the younger one,
+            // which may have consumed its wrong states, over its own, with exact windows. The same lists: a stream's
+            // bits depend on the pass size. Streams in neither pass are not touched.
             e->host_redos += 1;
             HIPCHK(hipStreamSynchronize(e->stream));
-            HIPCHK(hipMemcpy(e->d_states, e->known.data(), sizeof(StreamState) * e->B, hipMemcpyHostToDevice));
+            std::vector<char> rewind((size_t)e->B, 0);
+            for (int s : sl.list) rewind[(size_t)s] = 1;
+            if (has_younger)
+                for (int s : younger.list) rewind[(size_t)s] = 1;
+            for (int b = 0; b < e->B; ++b)
+                if (rewind[(size_t)b])
+                    HIPCHK(hipMemcpy(e->d_states + b, &e->known[(size_t)b], sizeof(StreamState), hipMemcpyHostToDevice));
             if (int rc = host_pass_exact_sync(e, sl)) return rc;
             if (has_younger)
                 if (int rc = host_pass_exact_sync(e, younger)) return rc;
         }
     }
     if (out)
-        for (int b = 0; b < std::min(n, e->B); ++b) out[b] = sl.h_res[b];
+        for (int i = 0; i < std::min(n, pass_n); ++i) out[i] = sl.h_res[i];
     // boxes the next window is planned around: this pass's - unless a younger pass was redone just
-    // now, whose states are newer (host_pass_exact_sync set `known` already)
-    if (!(has_younger && younger.redone)) {
-        for (int b = 0; b < e->B; ++b) e->known[b] = sl.h_st[b];
-        memcpy(e->h_states_all, sl.h_st, sizeof(StreamState) * e->B);   // the engine's own mirrors follow
-        memcpy(e->h_results, sl.h_res, sizeof(vt_result) * e->B);
-    }
+    // now, whose states are newer (host_pass_exact_sync adopted both already, in order)
+    if (!(has_younger && younger.redone)) adopt_slot(e, sl);
     sl.pending = false;
     e->host_collected += 1;
     return VT_OK;

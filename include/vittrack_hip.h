@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); VT_PIX_BGR8 .. VT_PIX_UYVY, vt_init_frame / vt_update_frame (added later still, additions only for the same reason); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
+#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); VT_PIX_BGR8 .. VT_PIX_UYVY, vt_init_frame / vt_update_frame, then vt_group_enqueue_host_streams / vt_group_enqueue_init_host (added later still, additions only for the same reason); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
 
 typedef enum vt_status {
     VT_OK = 0,
@@ -268,9 +268,10 @@ int vt_group_update_host(vt_group* g, const vt_frame* host_frames, int n, vt_res
  * the states the previous pass left (collected by the wait_next before it) and redoes that pass (and
  * the one queued behind it) with exact windows, so the results are always those of the full frames.
  * While a pass is outstanding it owns the stream states: every entry point that would advance or
- * overwrite them (vt_group_init_*, vt_group_enqueue_device, vt_group_update_device / _host, the *_streams passes,
- * vt_group_wait, vt_group_set_state_box, vt_group_profile_device) returns VT_ERR_INVALID_ARG until
- * vt_group_wait_next has collected it. (host -> tracker: src/pipeline.rs:95-101 maps the buffer on the CPU) */
+ * overwrite them (vt_group_init_*, vt_group_enqueue_device, vt_group_update_device / _host, the *_streams passes
+ * other than vt_group_enqueue_host_streams, vt_group_wait, vt_group_set_state_box, vt_group_profile_device) returns
+ * VT_ERR_INVALID_ARG until vt_group_wait_next has collected it; vt_group_enqueue_init_host takes a stream that is in
+ * no outstanding pass. (host -> tracker: src/pipeline.rs:95-101 maps the buffer on the CPU) */
 int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n);
 int vt_group_wait_next(vt_group* g, vt_result* out, int n);
 /* passes vt_group_wait_next had to redo because a speculative window missed (since creation) */
@@ -305,6 +306,40 @@ int vt_group_update_device_streams(vt_group* g, const int32_t* streams, const vt
  * and uploaded as by vt_group_update_host. Synchronous. */
 int vt_group_update_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n,
                                  vt_result* out);
+/* The pipelined form of a subset pass, collected by vt_group_wait_next: vt_group_enqueue_host over the streams
+ * streams[0..n). The list is checked as vt_group_enqueue_device_streams checks it (same status codes, nothing enqueued
+ * and nothing changed on failure); host_frames[i] feeds streams[i] (any vt_pixfmt, strides honoured, origin fields
+ * ignored) and must stay valid and unchanged until the pass is collected.
+ * At most two passes outstanding, as for vt_group_enqueue_host. The two may have different lists, overlapping or
+ * disjoint, and full and subset passes may alternate freely: the identity list (0, 1, ..., B-1) IS the full pass and
+ * replays its captured graph, any other list launches eagerly (vt_group_graph_captures stays constant).
+ * vt_group_wait_next returns the oldest uncollected pass's results in THAT pass's list order; n larger than that
+ * pass's size writes only the pass's entries (the rule of vt_group_wait).
+ * Windows: a stream that is in the pass still outstanding has a box nobody knows yet, so its window is speculative
+ * (cut around the last known box, enlarged by vt_config.host_window_margin_pct); a stream that is NOT in the
+ * outstanding pass has an exact known box: its window is exact and it can never cause a redo. vt_group_wait_next
+ * looks at the window misses of the speculative streams of the pass it collects; on a miss it rewinds the streams of
+ * that pass and of the younger one to the states they started from, redoes the pass with exact windows over the SAME
+ * list, then the younger pass over ITS list (a stream's bits depend on the pass size, so only the same lists keep the
+ * results those of vt_group_update_host_streams, bit for bit). Streams in neither pass are not touched.
+ * vt_group_host_redos counts as before. After a collect only the listed streams' known states and results move;
+ * vt_group_read_tensor behaves as after the synchronous subset pass. Frames inside a vt_host_register range take the
+ * zero-copy route under the same vt_config.host_zero_copy rule. Everything refused while a pipelined pass is
+ * outstanding stays refused, whichever kind of pass it is. */
+int vt_group_enqueue_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n);
+/* (Re)initialise `stream` BEHIND the outstanding pipelined passes, without waiting for them: ≙ tracker.init
+ * (src/tracker_context.rs:88) on one camera while the others keep tracking. Allowed only if `stream` is in no
+ * outstanding pass (VT_ERR_INVALID_ARG otherwise: collect it with vt_group_wait_next first; nothing changed); with
+ * nothing outstanding it is vt_group_init_host. Arguments are checked as by vt_group_init_host.
+ * The window is packed into pinned memory of the call's own before it returns (the caller's buffer may be reused; a
+ * frame in a vt_host_register range is packed too, since the crop runs after the call has returned), its
+ * upload goes on the copy stream, the state write and the template crop on the group's stream behind the passes
+ * already queued; the call does not wait for that stream. The stream may be listed from the very next
+ * vt_group_enqueue_host_streams on; its first window is exact (its box is the init box). A redo behind the init
+ * restores the initialised state. One exception to "does not wait": the first stream initialised on a format other
+ * than RGB8 / NV12 / YUY2 has the second set of graphs captured inside this call (vt_group_graph_captures), a capture
+ * needs an idle stream, so that one call waits for the outstanding passes (they stay uncollected). */
+int vt_group_enqueue_init_host(vt_group* g, int stream, const vt_frame* host_frame, vt_bbox box);
 
 /* ---- dma-buf ingest ------------------------------------------------------------------------
  * The reference's capture side can hand out dma-bufs (v4l2src io-mode=dmabuf, src/pipeline_ir.rs:24)
