@@ -428,6 +428,11 @@ class NV12Frame:
         self.w, self.h = width, height
         assert self.buf.size >= width * height + ((width + 1) & ~1) * ((height + 1) // 2)
 
+    def cframe(self) -> "CFrame":
+        uv = self.buf[self.w * self.h:]
+        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, self.w, (self.w + 1) & ~1, PIX_NV12,
+                      0, 0, 0, 0, 0)
+
 
 class YUY2Frame:
     """packed 4:2:2 host frame (Y0 U Y1 V), rows of 2*width bytes (src/pipeline_ir.rs:27-41)"""
@@ -436,6 +441,9 @@ class YUY2Frame:
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= 2 * width * height and width % 2 == 0
+
+    def cframe(self) -> "CFrame":
+        return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, PIX_YUY2, 0, 0, 0, 0, 0)
 
 
 class _PackedFrame:
@@ -508,10 +516,6 @@ class UYVYFrame:
         return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
 
 
-# host frame classes that go through vt_init_frame / vt_update_frame (each has .cframe())
-_ANY_FRAMES = (_PackedFrame, NV21Frame, UYVYFrame)
-
-
 class VitTrack:
     """≙ vit_tracker::VitTrack (src/tracker_context.rs:21,88,90,120)."""
 
@@ -543,41 +547,29 @@ class VitTrack:
     def as_group(self) -> "Group":
         return Group._view(lib().vt_tracker_as_group(self._h), self)
 
+    def _call(self, op, frame, last):
+        """vt_<op>_rgb8 / _nv12 / _yuy2 for a frame of those formats (the reference's call sites), vt_<op>_frame for
+        every other format; `last`: the call's last argument (the box / the result)"""
+        c, keep = Group._host_frame(frame)
+        p0, p1 = ctypes.cast(c.plane0, POINTER(c_uint8)), ctypes.cast(c.plane1, POINTER(c_uint8))
+        if c.format == PIX_NV12:
+            rc = getattr(lib(), f"vt_{op}_nv12")(self._h, p0, p1, c.width, c.height, c.stride0, c.stride1, last)
+        elif c.format in (PIX_RGB8, PIX_YUY2):
+            fn = getattr(lib(), f"vt_{op}_{'rgb8' if c.format == PIX_RGB8 else 'yuy2'}")
+            rc = fn(self._h, p0, c.width, c.height, c.stride0, last)
+        else:
+            rc = getattr(lib(), f"vt_{op}_frame")(self._h, byref(c), 0, last)
+        _check(rc)
+
     def init(self, frame, bbox: BBox) -> None:
         """frame: (H,W,3) uint8 RGB array (≙ ArrayView3<u8>), NV12Frame, YUY2Frame, or one of BGR8Frame, RGBXFrame,
         BGRXFrame, NV21Frame, UYVYFrame. Like the reference's call site (src/tracker_context.rs:88) the caller gets
         nothing back; errors raise."""
-        if isinstance(frame, _ANY_FRAMES):
-            _check(lib().vt_init_frame(self._h, byref(frame.cframe()), 0, bbox._c()))
-        elif isinstance(frame, YUY2Frame):
-            _check(lib().vt_init_yuy2(self._h, _u8(frame.buf), frame.w, frame.h, 2 * frame.w,
-                                      bbox._c()))
-        elif isinstance(frame, NV12Frame):
-            y = frame.buf
-            uv = frame.buf[frame.w * frame.h:]
-            _check(lib().vt_init_nv12(self._h, _u8(y), _u8(uv), frame.w, frame.h, frame.w,
-                                      (frame.w + 1) & ~1, bbox._c()))
-        else:
-            a = np.ascontiguousarray(frame, np.uint8)
-            h, w, _ = a.shape
-            _check(lib().vt_init_rgb8(self._h, _u8(a), w, h, w * 3, bbox._c()))
+        self._call("init", frame, bbox._c())
 
     def update(self, frame) -> TrackResult:
         r = CResult()
-        if isinstance(frame, _ANY_FRAMES):
-            _check(lib().vt_update_frame(self._h, byref(frame.cframe()), 0, byref(r)))
-        elif isinstance(frame, YUY2Frame):
-            _check(lib().vt_update_yuy2(self._h, _u8(frame.buf), frame.w, frame.h, 2 * frame.w,
-                                        byref(r)))
-        elif isinstance(frame, NV12Frame):
-            y = frame.buf
-            uv = frame.buf[frame.w * frame.h:]
-            _check(lib().vt_update_nv12(self._h, _u8(y), _u8(uv), frame.w, frame.h, frame.w,
-                                        (frame.w + 1) & ~1, byref(r)))
-        else:
-            a = np.ascontiguousarray(frame, np.uint8)
-            h, w, _ = a.shape
-            _check(lib().vt_update_rgb8(self._h, _u8(a), w, h, w * 3, byref(r)))
+        self._call("update", frame, byref(r))
         return TrackResult(r)
 
     # device-resident frames (pointers into this GPU's HBM, e.g. torch tensors' data_ptr())
@@ -733,17 +725,10 @@ class Group:
 
     @staticmethod
     def _host_frame(frame):
-        """(CFrame with HOST pointers, keep-alive object) for an (H,W,3) RGB array, NV12Frame, YUY2Frame or one of
-        the frame classes of the other formats"""
-        if isinstance(frame, _ANY_FRAMES):
+        """(CFrame with HOST pointers, keep-alive object): a frame object (NV12Frame, YUY2Frame, BGR8Frame, ...) says
+        what it is through cframe(); a bare (H,W,3) array is RGB8"""
+        if hasattr(frame, "cframe"):
             return frame.cframe(), frame
-        if isinstance(frame, NV12Frame):
-            uv = frame.buf[frame.w * frame.h:]
-            return CFrame(frame.buf.ctypes.data, uv.ctypes.data, frame.w, frame.h, frame.w,
-                          (frame.w + 1) & ~1, PIX_NV12, 0, 0, 0, 0, 0), frame
-        if isinstance(frame, YUY2Frame):
-            return CFrame(frame.buf.ctypes.data, None, frame.w, frame.h, 2 * frame.w, 0, PIX_YUY2,
-                          0, 0, 0, 0, 0), frame
         a = np.ascontiguousarray(frame, np.uint8)
         h, w, _ = a.shape
         return CFrame(a.ctypes.data, None, w, h, 3 * w, 0, PIX_RGB8, 0, 0, 0, 0, 0), a

@@ -134,6 +134,22 @@ const uint8_t* mapped_device_ptr(int device, const uint8_t* p, size_t bytes) {
     return nullptr;
 }
 
+// make an engine of B streams from a weights file or a device blob and wrap it in a handle; nothing stays behind on failure
+template <typename Handle>
+static int create_handle(const char* path, const void* d_blob, size_t bytes, int device_id, const vt_config* cfg, int B,
+                         Handle** out) {
+    if ((!path && !d_blob) || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    Engine* e = nullptr;
+    if (int rc = make_engine(path, d_blob, bytes, device_id, cfg, B, &e)) return rc;
+    Handle* h = new (std::nothrow) Handle{e};
+    if (!h) { delete e; return set_err(VT_ERR_OOM, "out of host memory"); }
+    *out = h;
+    return VT_OK;
+}
+static int config_streams(const vt_config* cfg) {
+    return (cfg && cfg->struct_size >= sizeof(vt_config) && cfg->n_streams > 0) ? cfg->n_streams : 1;
+}
+
 extern "C" {
 
 int vt_host_register(int device_id, void* host_ptr, size_t bytes, void** d_ptr) try {
@@ -223,25 +239,11 @@ int vt_plan_engines(const vt_model_info* info, int n_streams, int* sizes, int ca
 } VT_NOTHROW_INT
 
 int vt_group_create(const char* weights_path, int device_id, const vt_config* cfg, vt_group** out) try {
-    if (!weights_path || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
-    Engine* e = nullptr;
-    const int B = (cfg && cfg->struct_size >= sizeof(vt_config) && cfg->n_streams > 0) ? cfg->n_streams : 1;
-    if (int rc = make_engine(weights_path, nullptr, 0, device_id, cfg, B, &e)) return rc;
-    vt_group* g = new (std::nothrow) vt_group{e};
-    if (!g) { delete e; return set_err(VT_ERR_OOM, "out of host memory"); }
-    *out = g;
-    return VT_OK;
+    return create_handle(weights_path, nullptr, 0, device_id, cfg, config_streams(cfg), out);
 } VT_NOTHROW_INT
 int vt_group_create_from_device_blob(const void* d_blob, size_t bytes, int device_id,
                                      const vt_config* cfg, vt_group** out) try {
-    if (!d_blob || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
-    Engine* e = nullptr;
-    const int B = (cfg && cfg->struct_size >= sizeof(vt_config) && cfg->n_streams > 0) ? cfg->n_streams : 1;
-    if (int rc = make_engine(nullptr, d_blob, bytes, device_id, cfg, B, &e)) return rc;
-    vt_group* g = new (std::nothrow) vt_group{e};
-    if (!g) { delete e; return set_err(VT_ERR_OOM, "out of host memory"); }
-    *out = g;
-    return VT_OK;
+    return create_handle(nullptr, d_blob, bytes, device_id, cfg, config_streams(cfg), out);
 } VT_NOTHROW_INT
 void vt_group_destroy(vt_group* g) try {
     if (!g) return;
@@ -272,9 +274,9 @@ int vt_group_init_device(vt_group* g, int stream, const vt_frame* frame, vt_bbox
     return g->e->init_stream(stream, frame, box);
 } VT_NOTHROW_INT
 int vt_group_enqueue_device(vt_group* g, const vt_frame* frames, int n) try {
-    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (!g || !frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "enqueue_device")) return rc;
-    return g->e->enqueue(frames, n);
+    return g->e->enqueue(nullptr, frames, n);
 } VT_NOTHROW_INT
 int vt_group_wait(vt_group* g, vt_result* out, int n) try {
     if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
@@ -282,21 +284,21 @@ int vt_group_wait(vt_group* g, vt_result* out, int n) try {
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
 int vt_group_update_device(vt_group* g, const vt_frame* frames, int n, vt_result* out) try {
-    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (!g || !frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "update_device")) return rc;
-    if (int rc = g->e->enqueue(frames, n)) return rc;
+    if (int rc = g->e->enqueue(nullptr, frames, n)) return rc;
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
 int vt_group_enqueue_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n) try {
-    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (!g || !streams) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "enqueue_device_streams")) return rc;
-    return g->e->enqueue_streams(streams, frames, n);
+    return g->e->enqueue(streams, frames, n);
 } VT_NOTHROW_INT
 int vt_group_update_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n,
                                    vt_result* out) try {
-    if (!g || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    if (!g || !streams || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "update_device_streams")) return rc;
-    if (int rc = g->e->enqueue_streams(streams, frames, n)) return rc;
+    if (int rc = g->e->enqueue(streams, frames, n)) return rc;
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
 void* vt_group_hip_stream(vt_group* g) { return g ? (void*)g->e->stream : nullptr; }
@@ -353,26 +355,13 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
     Engine* e = g->e;
     if (n != e->B) return set_err(VT_ERR_INVALID_ARG, "profile: need exactly %d frames", e->B);
     if (int rc = refuse_while_pipelined(e, "profile")) return rc;
-    for (int b = 0; b < e->B; ++b)
-        if (!e->h_initialized[b]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d not initialised", b);
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
-    FrameDesc* hf = e->h_block(0);
-    e->any_layout = false;
-    for (int b = 0; b < e->B; ++b) {
-        if (int rc = check_frame(frames[b])) return rc;
-        to_desc(frames[b], hf + b);
-        e->any_layout = e->any_layout || pix_any_layout(frames[b].format);
-    }
-    *(PassOut*)(hf + e->B) = PassOut{e->h_results, e->h_states_all};
-    HIPCHK(hipMemcpyAsync(e->d_frames, hf, e->frames_block_bytes(), hipMemcpyHostToDevice, e->stream));
+    PassShape ps;       // the full pass, built as Engine::enqueue builds it, launched eagerly under the profiler
+    if (int rc = e->prepare_pass(nullptr, frames, n, nullptr, nullptr, &ps)) return rc;
     Profiler prof;
-    if (int rc = e->restore_segments()) return rc;      // a full pass: every stream's template rows in its own segment
-    e->pass_n = e->B;
-    e->pass_streams.clear();
-    e->crop_tier = e->pick_crop_tier();
     for (int it = 0; it < iters; ++it)
-        if (int rc = e->run_pass(&prof, e->B, nullptr)) return rc;
+        if (int rc = e->run_pass(&prof, ps)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     for (auto& r : prof.recs) {
         float ms = 0;
@@ -491,23 +480,11 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
 // ---- single-stream drop-in --------------------------------------------------------------------------
 
 int vt_create(const char* weights_path, int device_id, const vt_config* cfg, vt_tracker** out) try {
-    if (!weights_path || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
-    Engine* e = nullptr;
-    if (int rc = make_engine(weights_path, nullptr, 0, device_id, cfg, 1, &e)) return rc;
-    vt_tracker* t = new (std::nothrow) vt_tracker{e, {e}};
-    if (!t) { delete e; return set_err(VT_ERR_OOM, "out of host memory"); }
-    *out = t;
-    return VT_OK;
+    return create_handle(weights_path, nullptr, 0, device_id, cfg, 1, out);
 } VT_NOTHROW_INT
 int vt_create_from_device_blob(const void* d_blob, size_t bytes, int device_id, const vt_config* cfg,
                                vt_tracker** out) try {
-    if (!d_blob || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
-    Engine* e = nullptr;
-    if (int rc = make_engine(nullptr, d_blob, bytes, device_id, cfg, 1, &e)) return rc;
-    vt_tracker* t = new (std::nothrow) vt_tracker{e, {e}};
-    if (!t) { delete e; return set_err(VT_ERR_OOM, "out of host memory"); }
-    *out = t;
-    return VT_OK;
+    return create_handle(nullptr, d_blob, bytes, device_id, cfg, 1, out);
 } VT_NOTHROW_INT
 void vt_destroy(vt_tracker* t) try {
     if (!t) return;
@@ -523,109 +500,82 @@ int vt_get_model_info(const vt_tracker* t, vt_model_info* out) try {
 int vt_group_host_redos(const vt_group* g) { return g ? (int)g->e->host_redos : 0; }
 int vt_group_graph_captures(const vt_group* g) { return g ? g->e->graph_captures : 0; }
 
-static int do_init(vt_tracker* t, const vt_frame* f, vt_bbox box) { return t->e->init_stream(0, f, box); }
-static int do_update(vt_tracker* t, const vt_frame* f, vt_result* out) {
+// The single tracker's init and update, once for every format entry point below: each of those builds a vt_frame and
+// calls one of these. Host planes (on_device 0) are staged, the search window only, around the box that decides it -
+// the new box at init, the last known one at update; device planes go to the kernels as they are.
+static int tracker_init(vt_tracker* t, const vt_frame& frame, int on_device, vt_bbox box) {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    if (on_device != 0 && on_device != 1) return set_err(VT_ERR_INVALID_ARG, "on_device must be 0 or 1");
+    vt_frame f = frame;
+    const float fb[1][4] = {{(float)box.x, (float)box.y, (float)box.width, (float)box.height}};
+    if (!on_device)
+        if (int rc = stage_host_frames(t->e, &frame, 1, fb, &f)) return rc;
+    return t->e->init_stream(0, &f, box);
+}
+static int tracker_update(vt_tracker* t, const vt_frame& frame, int on_device, vt_result* out) {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    if (on_device != 0 && on_device != 1) return set_err(VT_ERR_INVALID_ARG, "on_device must be 0 or 1");
+    Engine* e = t->e;
+    vt_frame f = frame;
+    if (!on_device) {
+        if (!e->h_initialized[0]) return set_err(VT_ERR_NOT_INITIALIZED, "update before init");
+        if (int rc = stage_host_frames(e, &frame, 1, (const float(*)[4])e->known[0].box, &f)) return rc;
+    }
     if (!out) return set_err(VT_ERR_INVALID_ARG, "null result pointer");
     memset(out, 0, sizeof(*out));
-    if (int rc = t->e->enqueue(f, 1)) return rc;
-    return t->e->wait(out, 1);
+    if (int rc = e->enqueue(nullptr, &f, 1)) return rc;
+    return e->wait(out, 1);
 }
-
-int vt_init_rgb8(vt_tracker* t, const uint8_t* rgb, int w, int h, int stride_bytes, vt_bbox box) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f;
-    const float fb[4] = {(float)box.x, (float)box.y, (float)box.width, (float)box.height};
-    if (int rc = stage_host_frame(t->e, VT_PIX_RGB8, rgb, nullptr, w, h, stride_bytes, 0, fb, &f)) return rc;
-    return do_init(t, &f, box);
-} VT_NOTHROW_INT
-int vt_update_rgb8(vt_tracker* t, const uint8_t* rgb, int w, int h, int stride_bytes, vt_result* out) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    if (!t->e->h_initialized[0]) return set_err(VT_ERR_NOT_INITIALIZED, "update before init");
-    vt_frame f;
-    if (int rc = stage_host_frame(t->e, VT_PIX_RGB8, rgb, nullptr, w, h, stride_bytes, 0, t->e->known[0].box, &f)) return rc;
-    return do_update(t, &f, out);
-} VT_NOTHROW_INT
-int vt_init_yuy2(vt_tracker* t, const uint8_t* yuy2, int w, int h, int stride_bytes, vt_bbox box) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f;
-    const float fb[4] = {(float)box.x, (float)box.y, (float)box.width, (float)box.height};
-    if (int rc = stage_host_frame(t->e, VT_PIX_YUY2, yuy2, nullptr, w, h, stride_bytes, 0, fb, &f)) return rc;
-    return do_init(t, &f, box);
-} VT_NOTHROW_INT
-int vt_update_yuy2(vt_tracker* t, const uint8_t* yuy2, int w, int h, int stride_bytes, vt_result* out) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    if (!t->e->h_initialized[0]) return set_err(VT_ERR_NOT_INITIALIZED, "update before init");
-    vt_frame f;
-    if (int rc = stage_host_frame(t->e, VT_PIX_YUY2, yuy2, nullptr, w, h, stride_bytes, 0, t->e->known[0].box, &f)) return rc;
-    return do_update(t, &f, out);
-} VT_NOTHROW_INT
-int vt_init_nv12(vt_tracker* t, const uint8_t* y, const uint8_t* uv, int w, int h, int y_stride,
-                 int uv_stride, vt_bbox box) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f;
-    const float fb[4] = {(float)box.x, (float)box.y, (float)box.width, (float)box.height};
-    if (int rc = stage_host_frame(t->e, VT_PIX_NV12, y, uv, w, h, y_stride, uv_stride, fb, &f)) return rc;
-    return do_init(t, &f, box);
-} VT_NOTHROW_INT
-int vt_update_nv12(vt_tracker* t, const uint8_t* y, const uint8_t* uv, int w, int h, int y_stride,
-                   int uv_stride, vt_result* out) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    if (!t->e->h_initialized[0]) return set_err(VT_ERR_NOT_INITIALIZED, "update before init");
-    vt_frame f;
-    if (int rc = stage_host_frame(t->e, VT_PIX_NV12, y, uv, w, h, y_stride, uv_stride, t->e->known[0].box, &f)) return rc;
-    return do_update(t, &f, out);
-} VT_NOTHROW_INT
-
-static vt_frame dev_frame(int fmt, const void* p0, const void* p1, int w, int h, int s0, int s1) {
+static vt_frame plain_frame(int fmt, const void* p0, const void* p1, int w, int h, int s0, int s1) {
     vt_frame f;
     memset(&f, 0, sizeof(f));
     f.plane0 = p0; f.plane1 = p1; f.width = w; f.height = h; f.stride0 = s0; f.stride1 = s1;
     f.format = fmt;
     return f;
 }
+
+int vt_init_rgb8(vt_tracker* t, const uint8_t* rgb, int w, int h, int stride_bytes, vt_bbox box) try {
+    return tracker_init(t, plain_frame(VT_PIX_RGB8, rgb, nullptr, w, h, stride_bytes, 0), 0, box);
+} VT_NOTHROW_INT
+int vt_update_rgb8(vt_tracker* t, const uint8_t* rgb, int w, int h, int stride_bytes, vt_result* out) try {
+    return tracker_update(t, plain_frame(VT_PIX_RGB8, rgb, nullptr, w, h, stride_bytes, 0), 0, out);
+} VT_NOTHROW_INT
+int vt_init_yuy2(vt_tracker* t, const uint8_t* yuy2, int w, int h, int stride_bytes, vt_bbox box) try {
+    return tracker_init(t, plain_frame(VT_PIX_YUY2, yuy2, nullptr, w, h, stride_bytes, 0), 0, box);
+} VT_NOTHROW_INT
+int vt_update_yuy2(vt_tracker* t, const uint8_t* yuy2, int w, int h, int stride_bytes, vt_result* out) try {
+    return tracker_update(t, plain_frame(VT_PIX_YUY2, yuy2, nullptr, w, h, stride_bytes, 0), 0, out);
+} VT_NOTHROW_INT
+int vt_init_nv12(vt_tracker* t, const uint8_t* y, const uint8_t* uv, int w, int h, int y_stride,
+                 int uv_stride, vt_bbox box) try {
+    return tracker_init(t, plain_frame(VT_PIX_NV12, y, uv, w, h, y_stride, uv_stride), 0, box);
+} VT_NOTHROW_INT
+int vt_update_nv12(vt_tracker* t, const uint8_t* y, const uint8_t* uv, int w, int h, int y_stride,
+                   int uv_stride, vt_result* out) try {
+    return tracker_update(t, plain_frame(VT_PIX_NV12, y, uv, w, h, y_stride, uv_stride), 0, out);
+} VT_NOTHROW_INT
 int vt_init_rgb8_device(vt_tracker* t, const void* d_rgb, int w, int h, int stride_bytes, vt_bbox box) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f = dev_frame(VT_PIX_RGB8, d_rgb, nullptr, w, h, stride_bytes, 0);
-    return do_init(t, &f, box);
+    return tracker_init(t, plain_frame(VT_PIX_RGB8, d_rgb, nullptr, w, h, stride_bytes, 0), 1, box);
 } VT_NOTHROW_INT
 int vt_update_rgb8_device(vt_tracker* t, const void* d_rgb, int w, int h, int stride_bytes, vt_result* out) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f = dev_frame(VT_PIX_RGB8, d_rgb, nullptr, w, h, stride_bytes, 0);
-    return do_update(t, &f, out);
+    return tracker_update(t, plain_frame(VT_PIX_RGB8, d_rgb, nullptr, w, h, stride_bytes, 0), 1, out);
 } VT_NOTHROW_INT
 int vt_init_nv12_device(vt_tracker* t, const void* d_y, const void* d_uv, int w, int h, int y_stride,
                         int uv_stride, vt_bbox box) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f = dev_frame(VT_PIX_NV12, d_y, d_uv, w, h, y_stride, uv_stride);
-    return do_init(t, &f, box);
+    return tracker_init(t, plain_frame(VT_PIX_NV12, d_y, d_uv, w, h, y_stride, uv_stride), 1, box);
 } VT_NOTHROW_INT
 int vt_update_nv12_device(vt_tracker* t, const void* d_y, const void* d_uv, int w, int h, int y_stride,
                           int uv_stride, vt_result* out) try {
-    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
-    vt_frame f = dev_frame(VT_PIX_NV12, d_y, d_uv, w, h, y_stride, uv_stride);
-    return do_update(t, &f, out);
+    return tracker_update(t, plain_frame(VT_PIX_NV12, d_y, d_uv, w, h, y_stride, uv_stride), 1, out);
 } VT_NOTHROW_INT
-
-// any vt_pixfmt: host planes are staged like vt_init_rgb8's buffer (the search window only), device planes go to the
-// kernels as they are (like the *_device calls)
+// any vt_pixfmt, on the host or on the device
 int vt_init_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_bbox box) try {
-    if (!t || !frame) return set_err(VT_ERR_INVALID_ARG, "null tracker or frame");
-    if (on_device != 0 && on_device != 1) return set_err(VT_ERR_INVALID_ARG, "on_device must be 0 or 1");
-    if (on_device) return do_init(t, frame, box);
-    vt_frame f;
-    const float fb[1][4] = {{(float)box.x, (float)box.y, (float)box.width, (float)box.height}};
-    if (int rc = stage_host_frames(t->e, frame, 1, fb, &f)) return rc;
-    return do_init(t, &f, box);
+    if (!frame) return set_err(VT_ERR_INVALID_ARG, "null tracker or frame");
+    return tracker_init(t, *frame, on_device, box);
 } VT_NOTHROW_INT
 int vt_update_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_result* out) try {
-    if (!t || !frame) return set_err(VT_ERR_INVALID_ARG, "null tracker or frame");
-    if (on_device != 0 && on_device != 1) return set_err(VT_ERR_INVALID_ARG, "on_device must be 0 or 1");
-    if (on_device) return do_update(t, frame, out);
-    if (!t->e->h_initialized[0]) return set_err(VT_ERR_NOT_INITIALIZED, "update before init");
-    vt_frame f;
-    const float(*kb)[4] = (const float(*)[4])t->e->known[0].box;
-    if (int rc = stage_host_frames(t->e, frame, 1, kb, &f)) return rc;
-    return do_update(t, &f, out);
+    if (!frame) return set_err(VT_ERR_INVALID_ARG, "null tracker or frame");
+    return tracker_update(t, *frame, on_device, out);
 } VT_NOTHROW_INT
 
 // a single tracker viewed as a group of one (taps, profiling, stream handle)

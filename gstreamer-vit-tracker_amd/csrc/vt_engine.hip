@@ -1,5 +1,6 @@
 // vt_engine.hip — host side of libvittrack_hip.so: weight blob, per-GPU buffers, the per-frame
-// launch plan (eager or one hipGraph replay), and the extern "C" ABI of include/vittrack_hip.h.
+// launch plan (eager or one hipGraph replay) and the one path that builds and submits a pass. The
+// extern "C" ABI of include/vittrack_hip.h is in vt_abi.hip and vt_ingest.hip.
 //
 // One Engine = B independent tracked streams on one GPU. Everything a frame needs stays in HBM:
 // the decode kernel of frame t writes the box that the preprocessing kernel of frame t+1 reads, so
@@ -36,17 +37,16 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_stage};
+                    d_results};
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_frames) (void)hipHostFree(h_frames);
     if (h_results) (void)hipHostFree(h_results);
     if (h_state) (void)hipHostFree(h_state);
-    if (h_pack) (void)hipHostFree(h_pack);
+    stage.release();
     if (h_states_all) (void)hipHostFree(h_states_all);
     for (HostSlot& sl : hs) {
-        if (sl.d_arena) (void)hipFree(sl.d_arena);
-        if (sl.h_arena) (void)hipHostFree(sl.h_arena);
+        sl.arena.release();
         if (sl.h_res) (void)hipHostFree(sl.h_res);
         if (sl.h_st) (void)hipHostFree(sl.h_st);
         if (sl.up_ev) (void)hipEventDestroy(sl.up_ev);
@@ -55,8 +55,7 @@ void Engine::destroy() {
     }
     for (QueuedInit* q : qinits) {
         if (!q) continue;
-        if (q->d_arena) (void)hipFree(q->d_arena);
-        if (q->h_arena) (void)hipHostFree(q->h_arena);
+        q->arena.release();
         if (q->h_state) (void)hipHostFree(q->h_state);
         if (q->h_desc) (void)hipHostFree(q->h_desc);
         if (q->up_ev) (void)hipEventDestroy(q->up_ev);
@@ -73,14 +72,12 @@ void Engine::destroy() {
 }
 
 void Engine::drop_graphs() {
-    for (int t = 0; t < TIERS; ++t) {
-        if (graph_exec[t]) (void)hipGraphExecDestroy(graph_exec[t]);
-        if (graph[t]) (void)hipGraphDestroy(graph[t]);
-        graph_exec[t] = nullptr; graph[t] = nullptr;
-        if (graph_exec_any[t]) (void)hipGraphExecDestroy(graph_exec_any[t]);
-        if (graph_any[t]) (void)hipGraphDestroy(graph_any[t]);
-        graph_exec_any[t] = nullptr; graph_any[t] = nullptr;
-    }
+    for (auto& set : graphs)
+        for (PassGraph& g : set) {
+            if (g.exec) (void)hipGraphExecDestroy(g.exec);
+            if (g.graph) (void)hipGraphDestroy(g.graph);
+            g = PassGraph();
+        }
 }
 
 // The crop kernel's buffer tier for the pass about to be enqueued: the largest any stream's last known box needs (the
@@ -308,8 +305,7 @@ int Engine::alloc_buffers() {
     memset(h_results, 0, sizeof(vt_result) * B);
     for (int i = 0; i < RING; ++i) HIPCHK(hipEventCreateWithFlags(&ring_ev[i], hipEventDisableTiming));
     h_initialized.assign(B, 0);
-    pass_n = B;
-    pass_streams.clear();
+    pass_n = B;                     // no pass yet: reads as a full pass (pass_streams is empty)
     known.assign((size_t)B, StreamState{});
     HIPCHK(hipStreamSynchronize(stream));       // every fill has landed before the handle is handed out
     return VT_OK;
@@ -325,10 +321,12 @@ double Engine::flops_head() const {
     return 2.0 * d.ns * (d.D * C + 27 * C * C + 8 * C);
 }
 
-// One hot-path pass over n slots: all B streams (slot_stream null: slot b is stream b), or a subset pass, whose slot i
+// One hot-path pass over ps.n slots: all B streams (slot_stream null: slot b is stream b), or a subset pass, whose slot i
 // works for stream slot_stream[i] (device map). Between the crop and the decode every kernel is slot-indexed and
 // sized by M = n * ntok. With prof != nullptr every launch is bracketed by HIP events on this engine's stream.
-int Engine::run_pass(Profiler* prof, int n, const int32_t* slot_stream) {
+int Engine::run_pass(Profiler* prof, const PassShape& ps) {
+    const int n = ps.n;
+    const int32_t* slot_stream = ps.slot_stream;
     const int M = n * d.ntok, Ms = n * d.ns, D = d.D;
     hipError_t lerr = hipSuccess;
     auto L = [&](const char* name, double flops, double bytes, auto&& fn) {
@@ -413,7 +411,7 @@ int Engine::run_pass(Profiler* prof, int n, const int32_t* slot_stream) {
         L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
           [&] { return launch_gather_template_rows(d_tpl, d_patches, slot_stream, n, d, stream); });
     L("preproc_search", 0, (double)n * (d.S * d.S * 3 * 2 + 1.5 * d.S * d.S),
-      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, n, false, stream, crop_tier, slot_stream, any_layout); });
+      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, n, false, stream, ps.tier, slot_stream, ps.any_layout); });
     // K2: patch embedding (+bias +pos) -> residual stream (3-byte pair + chunk statistics)
     {
         GemmArgs a{};
@@ -456,9 +454,7 @@ int Engine::run_pass(Profiler* prof, int n, const int32_t* slot_stream) {
     }
     // final LayerNorm on the search tokens only, compacted to [B*ns][D] - as a launch of its own unless the head's
     // first layer normalises its rows itself (k_head.hip, LNC)
-    const bool band = head_band_kernel && head_band_ok;
-    const bool ln_fused = band && head_band_kernel >= 2 && headconv_ln_supported(d.gs, d.C, D);
-    feat_in_head = ln_fused;
+    const bool band = head_band(), ln_fused = head_ln_fused();
     if (!ln_fused)
         L("layernorm", 0, (double)Ms * D * 6, [&] { return final_layernorm(n); });
     // centre head: 1x1 conv, three 3x3 convs, then the f32 5-logit layer + decode. On the band kernel of
@@ -533,10 +529,9 @@ hipError_t Engine::final_layernorm(int n) {
                                   (int)((size_t)n * d.ns), d.D, d.ns, d.ntok, d.nt, d.ln_eps, stream);
 }
 
-int Engine::capture_graph(int tier) {
-    crop_tier = tier;
+int Engine::capture_graph(int tier, bool any_layout) {
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    int rc = run_pass(nullptr, B, nullptr);
+    int rc = run_pass(nullptr, PassShape{B, nullptr, tier, any_layout});
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(stream, &g);
     if (rc != VT_OK) {
@@ -550,8 +545,7 @@ int Engine::capture_graph(int tier) {
         (void)hipGraphDestroy(g);
         return set_err(e == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     }
-    (any_layout ? graph_any : graph)[tier] = g;
-    (any_layout ? graph_exec_any : graph_exec)[tier] = x;
+    graphs[any_layout][tier] = PassGraph{g, x};
     graph_captures += 1;
     return VT_OK;
 }
@@ -562,18 +556,22 @@ int Engine::capture_graph(int tier) {
 // With want_any_graphs, the passes of the crop kernels that read any vt_pixfmt too (Engine::init_stream sets it).
 int Engine::capture_all_graphs() {
     if (!use_graph) return VT_OK;
-    const int keep = crop_tier;
-    const bool keep_any = any_layout;
-    int rc = VT_OK;
-    for (int v = 0; v < (want_any_graphs ? 2 : 1) && rc == VT_OK; ++v) {
-        any_layout = v == 1;
-        const hipGraphExec_t* ex = any_layout ? graph_exec_any : graph_exec;
-        for (int t = 0; t < TIERS && rc == VT_OK; ++t)
-            if (!ex[t]) rc = capture_graph(t);
-    }
-    crop_tier = keep;
-    any_layout = keep_any;
-    return rc;
+    for (int any = 0; any < (want_any_graphs ? 2 : 1); ++any)
+        for (int t = 0; t < TIERS; ++t)
+            if (!graphs[any][t].exec)
+                if (int rc = capture_graph(t, any == 1)) return rc;
+    return VT_OK;
+}
+
+// The first stream on a format other than RGB8 / NV12 / YUY2: every tier's pass with the crop kernels that read the
+// layout is captured at its init, on the idle stream, so that no update of such a stream captures (a failure leaves the
+// engine as it was, apart from the tiers already captured, which stay valid).
+int Engine::capture_graphs_for(int format) {
+    if (!use_graph || want_any_graphs || !pix_any_layout(format)) return VT_OK;
+    HIPCHK(hipStreamSynchronize(stream));
+    want_any_graphs = true;
+    if (int rc = capture_all_graphs()) { want_any_graphs = false; return rc; }
+    return VT_OK;
 }
 
 // every format is checked by its family (vt_common.hpp: PixFamily): 4:2:0 semi-planar by the rules of NV12, packed
@@ -666,13 +664,7 @@ int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
     if (int rc = check_init_box(box)) return rc;
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
-    // the first stream on a format other than RGB8 / NV12 / YUY2: every tier's pass with the crop kernels that read the
-    // layout is captured here, before anything changes, so that no update of such a stream captures (a failure leaves
-    // the engine as it was, apart from the tiers already captured, which stay valid)
-    if (use_graph && !want_any_graphs && pix_any_layout(f->format)) {
-        want_any_graphs = true;
-        if (int rc = capture_all_graphs()) { want_any_graphs = false; return rc; }
-    }
+    if (int rc = capture_graphs_for(f->format)) return rc;      // before anything changes
     // stream is idle: h_state and ring slot 0 are free
     if (int rc = launch_init(b, f, box, h_state, h_frames)) return rc;
     HIPCHK(hipStreamSynchronize(stream));
@@ -693,92 +685,86 @@ int Engine::restore_segments() {
     return VT_OK;
 }
 
-int Engine::enqueue(const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st) {
-    if (!frames || n != B) return set_err(VT_ERR_INVALID_ARG, "enqueue: need exactly %d frames", B);
-    for (int b = 0; b < B; ++b) {
-        if (!h_initialized[b]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d: update before init", b);
-        if (int rc = check_frame(frames[b])) return rc;
-    }
-    DEVICE_SCOPE(device);
-    const int slot = ring_pos;
-    ring_pos = (ring_pos + 1) % RING;
-    HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copy that last used this slot is done
-    FrameDesc* hf = h_block(slot);
-    any_layout = false;
-    for (int b = 0; b < B; ++b) {
-        to_desc(frames[b], hf + b);
-        any_layout = any_layout || pix_any_layout(frames[b].format);
-    }
-    *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all};
-    HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ring_ev[slot], stream));
-    if (int rc = restore_segments()) return rc;
-    pass_n = B;
-    pass_streams.clear();
-    const int tier = pick_crop_tier();
-    if (use_graph && !taps) {
-        if (!any_layout && !graph_exec[tier])   // not reached after a successful creation (capture_all_graphs); kept as the safe path
-            if (int rc = capture_graph(tier)) return rc;
-        // passes with another format replay the graphs captured when a stream was initialised on one; without them
-        // (every stream was initialised on RGB8 / NV12 / YUY2) the pass launches eagerly: no capture inside an update
-        hipGraphExec_t x = any_layout ? graph_exec_any[tier] : graph_exec[tier];
-        if (x) {
-            HIPCHK(hipGraphLaunch(x, stream));
-            graph_replays[tier] += 1;
-            return VT_OK;
+int Engine::check_streams(const int32_t* streams, int n) const {
+    if (!streams) {
+        if (n != B) return set_err(VT_ERR_INVALID_ARG, "pass over all streams: need exactly %d frames", B);
+    } else {
+        if (n < 1 || n > B) return set_err(VT_ERR_INVALID_ARG, "pass over %d streams: need 1..%d", n, B);
+        std::vector<char> seen((size_t)B, 0);
+        for (int i = 0; i < n; ++i) {
+            const int s = streams[i];
+            if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "streams[%d] = %d out of range (0..%d)", i, s, B - 1);
+            if (seen[(size_t)s]) return set_err(VT_ERR_INVALID_ARG, "stream %d listed twice", s);
+            seen[(size_t)s] = 1;
         }
     }
-    crop_tier = tier;
-    return run_pass(nullptr, B, nullptr);
-}
-
-int Engine::check_streams(const int32_t* streams, int n) const {
-    if (!streams) return set_err(VT_ERR_INVALID_ARG, "null stream list");
-    if (n < 1 || n > B) return set_err(VT_ERR_INVALID_ARG, "pass over %d streams: need 1..%d", n, B);
-    std::vector<char> seen((size_t)B, 0);
     for (int i = 0; i < n; ++i) {
-        const int s = streams[i];
-        if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "streams[%d] = %d out of range (0..%d)", i, s, B - 1);
-        if (seen[(size_t)s]) return set_err(VT_ERR_INVALID_ARG, "stream %d listed twice", s);
-        seen[(size_t)s] = 1;
+        const int s = streams ? streams[i] : i;
+        if (!h_initialized[s]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d: update before init", s);
     }
-    for (int i = 0; i < n; ++i)
-        if (!h_initialized[streams[i]]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d: update before init", streams[i]);
     return VT_OK;
 }
 
-// A pass over the streams streams[0..n) on n compacted slots: slot i takes frames[i] and works for stream streams[i];
-// no other stream's state is touched. The full identity list is the full pass (captured graph); any other list runs
-// eagerly - never a capture inside an update - behind the gather of its template rows.
-int Engine::enqueue_streams(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res,
-                            StreamState* host_st) {
+// The one place a pass is built. A pass over the streams streams[0..n) on n compacted slots: slot i takes frames[i]
+// and works for stream streams[i]; no other stream's state is touched. A null list or the full identity list is the
+// full pass: every stream's template rows in its own segment, no slot map. The pass's block (descriptors, PassOut,
+// slot map) goes up from a block of the pinned ring, behind whatever the stream is doing.
+int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
+                         PassShape* ps) {
     if (int rc = check_streams(streams, n)) return rc;
     if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
     for (int i = 0; i < n; ++i)
         if (int rc = check_frame(frames[i])) return rc;
-    bool identity = n == B;
-    for (int i = 0; i < n && identity; ++i) identity = streams[i] == i;
-    if (identity) return enqueue(frames, n, host_res, host_st);
-    DEVICE_SCOPE(device);
+    bool full = n == B;
+    for (int i = 0; streams && i < n && full; ++i) full = streams[i] == i;
     const int slot = ring_pos;
     ring_pos = (ring_pos + 1) % RING;
-    HIPCHK(hipEventSynchronize(ring_ev[slot]));
+    HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copy that last used this block is done
     FrameDesc* hf = h_block(slot);
-    any_layout = false;
+    *ps = PassShape{n, full ? nullptr : d_map(), 0, false};
     for (int i = 0; i < n; ++i) {
         to_desc(frames[i], hf + i);
-        any_layout = any_layout || pix_any_layout(frames[i].format);
+        ps->any_layout = ps->any_layout || pix_any_layout(frames[i].format);
     }
     *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all};
-    int32_t* map = (int32_t*)((char*)hf + map_offset());
-    for (int i = 0; i < n; ++i) map[i] = streams[i];
+    if (!full) {
+        int32_t* map = (int32_t*)((char*)hf + map_offset());
+        for (int i = 0; i < n; ++i) map[i] = streams[i];
+    }
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipEventRecord(ring_ev[slot], stream));
+    if (full) {
+        if (int rc = restore_segments()) return rc;
+        pass_streams.clear();
+    } else {
+        segments_moved = true;
+        pass_streams.assign(streams, streams + n);
+    }
     pass_n = n;
-    pass_streams.assign(streams, streams + n);
-    segments_moved = true;
-    crop_tier = pick_crop_tier(streams, n);
-    return run_pass(nullptr, n, d_map());
+    feat_in_head = head_ln_fused();
+    ps->tier = pick_crop_tier(full ? nullptr : streams, n);     // a subset pass: from the boxes of its own streams
+    return VT_OK;
+}
+
+// The one entry every pass takes. The full pass replays its captured graph; a subset pass runs eagerly - never a
+// capture inside an update - behind the gather of its template rows.
+int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st) {
+    DEVICE_SCOPE(device);
+    PassShape ps;
+    if (int rc = prepare_pass(streams, frames, n, host_res, host_st, &ps)) return rc;
+    if (!ps.slot_stream && use_graph && !taps) {
+        const PassGraph& g = graphs[ps.any_layout][ps.tier];
+        if (!ps.any_layout && !g.exec)   // not reached after a successful creation (capture_all_graphs); kept as the safe path
+            if (int rc = capture_graph(ps.tier, false)) return rc;
+        // passes with another format replay the graphs captured when a stream was initialised on one; without them
+        // (every stream was initialised on RGB8 / NV12 / YUY2) the pass launches eagerly: no capture inside an update
+        if (g.exec) {
+            HIPCHK(hipGraphLaunch(g.exec, stream));
+            graph_replays[ps.tier] += 1;
+            return VT_OK;
+        }
+    }
+    return run_pass(nullptr, ps);
 }
 
 int Engine::wait(vt_result* out, int n) {

@@ -1,9 +1,11 @@
 // vt_engine.hpp — what the host-side translation units of libvittrack_hip.so share: error plumbing, the device
 // scope, the Engine (one GPU's batch of tracked streams) and the handles of the C ABI.
-//   vt_engine.hip   the Engine: weight blob, buffers, the per-frame launch plan, graphs, enqueue / wait
-//   vt_abi.hip      the extern "C" boundary of include/vittrack_hip.h (create / init / update, groups, diagnostics,
-//                   colour converter, overlays, dma-buf and host-mapping ingest)
-//   vt_ingest.hip   host-frame ingest: window planning and packing, the pipelined enqueue_host / wait_next
+//   vt_engine.hip   the Engine: weight blob, buffers, the per-frame launch plan (run_pass), graphs, and the one way a
+//                   pass is built and submitted (prepare_pass / enqueue), wait
+//   vt_abi.hip      the extern "C" boundary of include/vittrack_hip.h (create / init / update, device-frame passes of a
+//                   group, diagnostics, colour converter, overlays, dma-buf and host-mapping ingest)
+//   vt_ingest.hip   host-frame ingest: the staging arena, window planning and packing, the host-frame passes of a group
+//                   (synchronous, pipelined enqueue_host / wait_next, queued init)
 //   vt_rccl.hip     the start-up weight broadcast over a lazily loaded librccl
 //   vt_ops.hip      operator-level entry points of include/vittrack_hip_ops.h - linked into
 //                   libvittrack_hip_ops.so (tests, tuning tools) only, NOT into the product library
@@ -112,6 +114,24 @@ struct Profiler {
     }
 };
 
+// One pass as run_pass launches it and capture_graph captures it. Engine::prepare_pass builds it for a pass that is
+// about to run; nothing of it is engine state.
+struct PassShape {
+    int n = 0;                              // slots (M = n * ntok)
+    const int32_t* slot_stream = nullptr;   // device map slot -> stream of a subset pass; null: the full pass (n == B, slot b is stream b)
+    int tier = 0;                           // crop-buffer tier (Engine::pick_crop_tier)
+    bool any_layout = false;                // some slot's frame is not RGB8 / NV12 / YUY2 (k_preproc.hip: fetch_rgb<true>)
+};
+
+// Where the packed windows of host frames go: a pinned host arena and its device twin of the same capacity
+// (vt_ingest.hip). The synchronous path, each pipelined slot and each queued init own one.
+struct StageArena {
+    uint8_t *d = nullptr, *h = nullptr;
+    size_t cap = 0;
+    int ensure(size_t need);    // at least `need` bytes; a larger pair replaces the old one, which nothing may be using
+    void release();
+};
+
 struct Engine {
     int device = 0, B = 1;
     bool use_graph = true, taps = false;
@@ -150,9 +170,11 @@ struct Engine {
     size_t frames_block_bytes() const { return (sizeof(FrameDesc) * (size_t)B + sizeof(PassOut) + 4 * (size_t)B + 15) & ~(size_t)15; }
     size_t map_offset() const { return sizeof(FrameDesc) * (size_t)B + sizeof(PassOut); }
     const int32_t* d_map() const { return (const int32_t*)((const char*)d_frames + map_offset()); }
-    // the last pass: its slot count and, for a subset pass, the stream of every slot (empty: all B streams in order)
+    // the last pass (written by prepare_pass only): its slot count and, for a subset pass, the stream of every slot
+    // (empty: all B streams in order); feat_in_head: it did not write d_feat (recomputed when read)
     int pass_n = 1;
     std::vector<int32_t> pass_streams;
+    bool feat_in_head = false;
     int slot_of(int stream) const;      // slot of `stream` in the last pass, -1 if it was not in it
     FrameDesc* h_block(int slot) const { return (FrameDesc*)((char*)h_frames + (size_t)slot * frames_block_bytes()); }
     hipEvent_t ring_ev[RING]{};
@@ -162,24 +184,17 @@ struct Engine {
     // graph
     // one captured pass per crop-buffer tier (k_preproc.hip: 16 / 32 / 64 KiB of LDS per tile), all captured at creation
     static constexpr int TIERS = 3;
-    hipGraph_t graph[TIERS] = {nullptr, nullptr, nullptr};
-    hipGraphExec_t graph_exec[TIERS] = {nullptr, nullptr, nullptr};
-    // the same passes with the crop kernels that read any vt_pixfmt (k_preproc.hip: fetch_rgb<true>), for passes that
-    // carry a format other than RGB8 / NV12 / YUY2: all tiers captured together (capture_all_graphs) when the first
-    // stream is initialised on such a format - never inside an update
-    hipGraph_t graph_any[TIERS] = {nullptr, nullptr, nullptr};
-    hipGraphExec_t graph_exec_any[TIERS] = {nullptr, nullptr, nullptr};
+    // graphs[1]: the same passes with the crop kernels that read any vt_pixfmt (k_preproc.hip: fetch_rgb<true>), for
+    // passes that carry a format other than RGB8 / NV12 / YUY2: all tiers captured together (capture_all_graphs) when
+    // the first stream is initialised on such a format - never inside an update
+    struct PassGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
+    PassGraph graphs[2][TIERS];                   // [any_layout][tier]
     bool want_any_graphs = false;                 // a stream was initialised on such a format: capture_all_graphs takes them too
-    bool any_layout = false;                      // the pass being enqueued carries such a format
-    int crop_tier = 0;                            // tier of the pass being enqueued (from the boxes the host knows)
     int crop_tier_forced = -1;                    // >= 0: tests / A-B runs (vt_group_set_tuning "crop_tier")
     int graph_captures = 0;                       // hipGraph captures since creation (vt_group_graph_captures)
     long graph_replays[TIERS] = {0, 0, 0};        // passes replayed per tier (vt_group_read_tensor "graph_replays")
     bool head_band_ok = false;                    // the head's band kernel takes this model's shapes (planner consulted at creation)
-    // host-pointer staging (single-stream API)
-    uint8_t* d_stage = nullptr;
-    uint8_t* h_pack = nullptr;      // pinned: the window of a host frame, packed
-    size_t stage_bytes = 0;
+    StageArena stage;               // host-frame staging of the synchronous entry points
     StreamState* h_states_all = nullptr;  // pinned mirror of d_states after the last pass
     int max_w = 3840, max_h = 2160;
     size_t max_device_bytes = 0;    // vt_config.max_device_mib (0: no limit but free memory)
@@ -189,8 +204,7 @@ struct Engine {
     // pipelined host passes (vt_group_enqueue_host[_streams] / vt_group_wait_next): two slots, each with its own
     // pinned + device arena, result buffers, state snapshot and events; uploads go on copy_stream
     struct HostSlot {
-        uint8_t *d_arena = nullptr, *h_arena = nullptr;
-        size_t bytes = 0;
+        StageArena arena;
         vt_result* h_res = nullptr;     // the pass's results, by SLOT (list order)
         StreamState* h_st = nullptr;    // [B] by STREAM: valid at the listed streams' indices only
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
@@ -203,8 +217,7 @@ struct Engine {
     // staging of the queued inits (vt_group_enqueue_init_host): each owns its pinned state + descriptor, its window
     // arena and the event behind its work on the group's stream; one is reused once that event has passed
     struct QueuedInit {
-        uint8_t *d_arena = nullptr, *h_arena = nullptr;
-        size_t bytes = 0;
+        StageArena arena;
         StreamState* h_state = nullptr;
         FrameDesc* h_desc = nullptr;
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
@@ -221,7 +234,9 @@ struct Engine {
     int head_band_kernel = 2;                     // 0: the head as implicit GEMMs + head_out + decode (A/B, tests);
                                                   // 1: band kernels behind the LayerNorm kernel; 2: + the final LayerNorm
                                                   // inside the 1x1 layer's kernel where the shape allows it (default)
-    bool feat_in_head = false;                    // the passes do not write d_feat (recomputed when read)
+    bool head_band() const { return head_band_kernel && head_band_ok; }
+    // the head's first kernel normalises its rows itself: the passes run no final LayerNorm and write no d_feat
+    bool head_ln_fused() const { return head_band() && head_band_kernel >= 2 && headconv_ln_supported(d.gs, d.C, d.D); }
     hipError_t final_layernorm(int n);
     int host_zero_copy = 0;                       // vt_config.host_zero_copy: 0 auto (single-stream engines), 1 always, -1 never
     float success_threshold = 0.2f;
@@ -234,21 +249,23 @@ struct Engine {
     int index_blob(const uint8_t* host_copy, size_t bytes);
     size_t activation_bytes() const;
     int alloc_buffers();
-    // n slots (M = n * ntok); slot_stream: the device map of a subset pass, null for a full pass (n == B)
-    int run_pass(Profiler* prof, int n, const int32_t* slot_stream);
+    int run_pass(Profiler* prof, const PassShape& ps);
     int restore_segments();             // every stream's template rows back into its own segment (after a subset pass)
-    int capture_graph(int tier);                  // into graph_exec_any when any_layout
+    int capture_graph(int tier, bool any_layout);     // the full pass of that shape into graphs[any_layout][tier]
     int capture_all_graphs();
+    int capture_graphs_for(int format);           // the graphs[1] set, once, when a stream starts on a format that needs it
     int pick_crop_tier(const int32_t* streams = nullptr, int n = 0) const;   // streams == null: all B
     void drop_graphs();
-    // host_res / host_st: pinned buffers the pass's results and states are stored to (null: the
-    // engine's own h_results / h_states_all)
-    int enqueue(const vt_frame* frames, int n, vt_result* host_res = nullptr, StreamState* host_st = nullptr);
-    // one pass over streams[0..n): VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input; a
-    // full identity list is the full pass
+    // One pass over streams[0..n), frames[i] for streams[i]; streams == null: all B streams in order (n == B), and no
+    // list is built for it. VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input (checked in
+    // the order list, initialisation, frames). host_res / host_st: pinned buffers the pass's results and states are
+    // stored to (null: the engine's own h_results / h_states_all).
     int check_streams(const int32_t* streams, int n) const;
-    int enqueue_streams(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
-                        StreamState* host_st = nullptr);
+    // checks + the pass's block uploaded behind the stream's work + the last-pass record; the engine's device is current
+    int prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
+                     PassShape* ps);
+    int enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
+                StreamState* host_st = nullptr);
     int wait(vt_result* out, int n);
     int init_stream(int b, const vt_frame* f, vt_bbox box);
     const TensorRef* find(const std::string& n) const {
@@ -279,15 +296,17 @@ void to_desc(const vt_frame& f, FrameDesc* o);
 
 // ---- handles of the C ABI --------------------------------------------------------------------------
 struct vt_group { Engine* e; };
-struct vt_tracker { Engine* e; vt_group view; };   // view: the tracker as a group of one
+struct vt_tracker {                 // view: the tracker as a group of one
+    Engine* e;
+    vt_group view;
+    explicit vt_tracker(Engine* en) : e(en), view{en} {}
+};
 
 // A pipelined host pass (vt_group_enqueue_host) that has not been collected owns the stream states
 int refuse_while_pipelined(const Engine* e, const char* what);
 
 // ---- host-frame ingest (vt_ingest.hip) ---------------------------------------------------------------
 int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev);
-int stage_host_frame(Engine* e, int fmt, const uint8_t* p0, const uint8_t* p1, int w, int h, int s0, int s1,
-                     const float* box, vt_frame* f);
 const uint8_t* mapped_device_ptr(int device, const uint8_t* p, size_t bytes);
 
 struct DevBuf {

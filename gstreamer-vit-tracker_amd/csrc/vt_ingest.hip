@@ -2,16 +2,13 @@
 // PCIe; the pipelined form uploads frame t+1 on a copy stream while pass t runs.
 #include "vt_engine.hpp"
 
-// Host-pointer ingest: only the window of the frame that the call can sample is uploaded. The
-// reference hands over the whole frame (6.2 MB of RGB8 at 1080p, src/pipeline.rs:105-112) although
-// the tracker reads a window of side 4*sqrt(w*h) around the last box; that window is packed into a
-// pinned buffer on the host (a few hundred KB) and copied asynchronously ahead of the kernels.
-// The caller's buffer is no longer referenced when this returns (src/pipeline.rs:125 draws into it).
 // ---- host-frame ingest: only the windows that the pass can sample cross PCIe ----------------------
 // The reference hands over whole frames (6.2 MB of RGB8 at 1080p, src/pipeline.rs:105-112) although
 // the tracker reads a window of side 4*sqrt(w*h) around the last box. The windows of all the frames
 // of a call are packed back to back into one pinned arena and moved with ONE async H2D copy; the
 // frame descriptors handed to the kernels point into the device copy and carry the window origin.
+// The caller's buffer of a synchronous call is no longer referenced when the call returns (src/pipeline.rs:125
+// draws into it).
 struct HostWin {
     int fmt, w, h, s0, s1;
     const uint8_t *p0, *p1;
@@ -19,8 +16,6 @@ struct HostWin {
     size_t bytes, uv_off;
 };
 
-// `grow`: enlargement of the crop side for a SPECULATIVE window (the box of the pass that is still
-// running is not known): 0 = the exact crop
 // row pitch of a packed format's window in the arena: 4-byte pixels on 16-byte boundaries (the crop kernel then fetches
 // 4 pixels per load), the others back to back
 static size_t packed_row_bytes(int fmt, int ww) {
@@ -28,8 +23,11 @@ static size_t packed_row_bytes(int fmt, int ww) {
     return pix_row_bpp(fmt) == 4 ? (rb + 15) & ~(size_t)15 : rb;
 }
 
-static int plan_window(const Engine* e, int fmt, const uint8_t* p0, const uint8_t* p1, int w, int h,
-                       int s0, int s1, const float* box, float grow, HostWin* win) {
+// `grow`: enlargement of the crop side for a SPECULATIVE window (the box of the pass that is still
+// running is not known): 0 = the exact crop
+static int plan_window(const Engine* e, const vt_frame& hf, const float* box, float grow, HostWin* win) {
+    const int fmt = hf.format, w = hf.width, h = hf.height, s0 = hf.stride0, s1 = hf.stride1;
+    const uint8_t *p0 = (const uint8_t*)hf.plane0, *p1 = (const uint8_t*)hf.plane1;
     if (!p0 || w < 16 || h < 16) return set_err(VT_ERR_INVALID_ARG, "null frame or size < 16");
     if (w > e->max_w || h > e->max_h)
         return set_err(VT_ERR_INVALID_ARG, "frame %dx%d exceeds configured max %dx%d", w, h, e->max_w, e->max_h);
@@ -73,33 +71,25 @@ static int plan_window(const Engine* e, int fmt, const uint8_t* p0, const uint8_
     return VT_OK;
 }
 
-// where the packed windows of one call go: a pinned host arena, its device twin, and the stream the
-// single H2D copy is enqueued on
-struct Arena {
-    uint8_t** d;
-    uint8_t** h;
-    size_t* cap;
-    hipStream_t copy_on;
-};
-
-// pinned + device arena of at least `need` bytes (grown only while nothing uses it)
-static int ensure_arena(Engine* e, const Arena& a, size_t need) {
-    if (need <= *a.cap) return VT_OK;
-    DEVICE_SCOPE(e->device);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (a.copy_on != e->stream) HIPCHK(hipStreamSynchronize(a.copy_on));
-    if (*a.d) { (void)hipFree(*a.d); *a.d = nullptr; }
-    if (*a.h) { (void)hipHostFree(*a.h); *a.h = nullptr; }
-    *a.cap = 0;
-    const size_t cap = need + need / 2 + 4096;
-    HIPCHK(hipMalloc((void**)a.d, cap));
-    HIPCHK(hipHostMalloc((void**)a.h, cap));
-    *a.cap = cap;
+// The one growth rule of a staging arena: half as much again as asked for. The old pair is freed here - hipFree waits
+// for the device - so a caller that must not wait (queued_init_staging) only ever calls this on a fresh arena.
+int StageArena::ensure(size_t need) {
+    if (need <= cap) return VT_OK;
+    release();
+    const size_t want = need + need / 2 + 4096;
+    HIPCHK(hipMalloc((void**)&d, want));
+    HIPCHK(hipHostMalloc((void**)&h, want));
+    cap = want;
     return VT_OK;
 }
+void StageArena::release() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    *this = StageArena();
+}
 
-static void pack_window(const Arena& a, const HostWin& wn, size_t off, vt_frame* f) {
-    uint8_t* dst = *a.h + off;
+static void pack_window(const StageArena& a, const HostWin& wn, size_t off, vt_frame* f) {
+    uint8_t* dst = a.h + off;
     memset(f, 0, sizeof(*f));
     f->width = wn.w; f->height = wn.h; f->format = wn.fmt;
     f->origin_x = wn.x_lo; f->origin_y = wn.y_lo;
@@ -110,7 +100,7 @@ static void pack_window(const Arena& a, const HostWin& wn, size_t off, vt_frame*
         const size_t rb = (size_t)wn.ww * bpp, rs = packed_row_bytes(wn.fmt, wn.ww);   // as plan_window
         for (int r = 0; r < wn.wh; ++r)
             memcpy(dst + r * rs, wn.p0 + (size_t)(wn.y_lo + r) * wn.s0 + (size_t)wn.x_lo * bpp, rb);
-        f->plane0 = *a.d + off; f->stride0 = (int)rs;
+        f->plane0 = a.d + off; f->stride0 = (int)rs;
     } else {
         const int uvw = (wn.ww + 1) & ~1, uvh = (wn.wh + 1) / 2;
         const size_t ys = ((size_t)wn.ww + 15) & ~(size_t)15, uvs = ((size_t)uvw + 15) & ~(size_t)15;   // as plan_window
@@ -121,25 +111,24 @@ static void pack_window(const Arena& a, const HostWin& wn, size_t off, vt_frame*
         for (int r = 0; r < uvh; ++r)
             memcpy(dst + wn.uv_off + (size_t)r * uvs, wn.p1 + (size_t)(wn.y_lo / 2 + r) * wn.s1 + wn.x_lo,
                    (size_t)uv_avail);
-        f->plane0 = *a.d + off; f->plane1 = *a.d + off + wn.uv_off;
+        f->plane0 = a.d + off; f->plane1 = a.d + off + wn.uv_off;
         f->stride0 = (int)ys; f->stride1 = (int)uvs;
     }
 }
 
-// n host frames -> n device frame descriptors (windows packed, ONE H2D copy enqueued on a.copy_on).
+// n host frames -> n device frame descriptors (windows packed into `a`, ONE H2D copy enqueued on copy_on).
 // boxes[i]: the box that decides frame i's window (the new box at init, the last state at update);
 // grow[i]: its enlargement (plan_window), null: every window exact. pack_all: no zero-copy route, whatever the
 // configuration says (the kernels must not read the caller's memory after the call has returned).
-static int stage_host_frames_to(Engine* e, const Arena& a, const vt_frame* host, int n, const float (*boxes)[4],
-                                const float* grow, vt_frame* dev, size_t* bytes_out, bool pack_all = false) {
+static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, const vt_frame* host, int n,
+                                const float (*boxes)[4], const float* grow, vt_frame* dev, size_t* bytes_out,
+                                bool pack_all = false) {
     std::vector<HostWin> wins((size_t)n);
     std::vector<char> mapped((size_t)n, 0);
     size_t total = 0;
     for (int i = 0; i < n; ++i) {
         const vt_frame& hf = host[i];
-        if (int rc = plan_window(e, hf.format, (const uint8_t*)hf.plane0, (const uint8_t*)hf.plane1, hf.width,
-                                 hf.height, hf.stride0, hf.stride1, boxes[i], grow ? grow[i] : 0.0f, &wins[i]))
-            return rc;
+        if (int rc = plan_window(e, hf, boxes[i], grow ? grow[i] : 0.0f, &wins[i])) return rc;
         // a frame inside a range mapped by vt_host_register goes to the kernels as it lies (zero copy) - on
         // single-stream engines, or where the caller asked for it: for a batched engine the packed upload beside
         // the previous pass is faster than PCIe reads inside the pass (vt_config.host_zero_copy, vittrack_hip.h)
@@ -163,33 +152,26 @@ static int stage_host_frames_to(Engine* e, const Arena& a, const vt_frame* host,
     }
     if (bytes_out) *bytes_out = total;
     if (total == 0) return VT_OK;            // every frame mapped: nothing to pack, nothing to copy
-    if (int rc = ensure_arena(e, a, total)) return rc;
     DEVICE_SCOPE(e->device);
+    if (total > a.cap) {        // grown only while nothing uses it
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (copy_on != e->stream) HIPCHK(hipStreamSynchronize(copy_on));
+        if (int rc = a.ensure(total)) return rc;
+    }
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         if (mapped[(size_t)i]) continue;
         pack_window(a, wins[i], off, &dev[i]);
         off += wins[i].bytes;
     }
-    HIPCHK(hipMemcpyAsync(*a.d, *a.h, total, hipMemcpyHostToDevice, a.copy_on));
-    if (bytes_out) *bytes_out = total;
+    HIPCHK(hipMemcpyAsync(a.d, a.h, total, hipMemcpyHostToDevice, copy_on));
     return VT_OK;
 }
 
 // the synchronous entry points: one arena, copy on the engine's own stream (every such call waits
 // for its pass before returning, so the arena is free again at the next call)
 int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev) {
-    const Arena a{&e->d_stage, &e->h_pack, &e->stage_bytes, e->stream};
-    return stage_host_frames_to(e, a, host, n, boxes, nullptr, dev, nullptr);
-}
-
-int stage_host_frame(Engine* e, int fmt, const uint8_t* p0, const uint8_t* p1, int w, int h,
-                            int s0, int s1, const float* box, vt_frame* f) {
-    vt_frame hf;
-    memset(&hf, 0, sizeof(hf));
-    hf.plane0 = p0; hf.plane1 = p1; hf.width = w; hf.height = h; hf.stride0 = s0; hf.stride1 = s1; hf.format = fmt;
-    float b4[1][4] = {{box[0], box[1], box[2], box[3]}};
-    return stage_host_frames(e, &hf, 1, b4, f);
+    return stage_host_frames_to(e, e->stage, e->stream, host, n, boxes, nullptr, dev, nullptr);
 }
 
 // ---- pipelined host passes -------------------------------------------------------------------------
@@ -211,11 +193,28 @@ static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
     return VT_OK;
 }
 
-// the boxes the windows of a pass over streams[0..n) are planned around: the last the host knows
+// the boxes the windows of a pass over streams[0..n) (null: all streams in order) are planned around: the last the
+// host knows
 static std::vector<float> known_boxes(const Engine* e, const int32_t* streams, int n) {
     std::vector<float> boxes((size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(&boxes[(size_t)i * 4], e->known[streams[i]].box, 4 * sizeof(float));
+    for (int i = 0; i < n; ++i) memcpy(&boxes[(size_t)i * 4], e->known[streams ? streams[i] : i].box, 4 * sizeof(float));
     return boxes;
+}
+
+// One synchronous host pass over streams[0..n) (null: all streams in order): every window cut around its stream's own
+// last box, the pass enqueued and waited for. vt_group_update_host is the null list.
+static int update_host_pass(Engine* e, const int32_t* streams, const vt_frame* host_frames, int n, vt_result* out,
+                            const char* what) {
+    if (int rc = refuse_while_pipelined(e, what)) return rc;
+    if (int rc = e->check_streams(streams, n)) return rc;
+    DEVICE_SCOPE(e->device);
+    if (int rc = e->wait(nullptr, 0)) return rc;   // last pass done: its boxes are in `known`
+    std::vector<vt_frame> dev((size_t)n);
+    const std::vector<float> boxes = known_boxes(e, streams, n);
+    if (int rc = stage_host_frames(e, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
+        return rc;
+    if (int rc = e->enqueue(streams, dev.data(), n)) return rc;
+    return e->wait(out, n);
 }
 
 // a collected (or redone) pass becomes what the host knows: the entries of ITS streams move, no others. The
@@ -237,7 +236,7 @@ static int host_pass_exact_sync(Engine* e, Engine::HostSlot& sl) {
     const std::vector<float> boxes = known_boxes(e, sl.list.data(), n);
     if (int rc = stage_host_frames(e, sl.host.data(), n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
         return rc;
-    if (int rc = e->enqueue_streams(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st)) return rc;
+    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     adopt_slot(e, sl);
     sl.redone = true;
@@ -266,13 +265,12 @@ static int enqueue_host_pass(Engine* e, const int32_t* streams, const vt_frame* 
         if (outstanding == 1 && older.lists(streams[i])) { spec[(size_t)i] = 1; grow[(size_t)i] = e->margin; }
     std::vector<vt_frame> dev((size_t)n);
     const std::vector<float> boxes = known_boxes(e, streams, n);
-    const Arena a{&sl.d_arena, &sl.h_arena, &sl.bytes, e->copy_stream};
-    if (int rc = stage_host_frames_to(e, a, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()),
-                                      grow.data(), dev.data(), nullptr))
+    if (int rc = stage_host_frames_to(e, sl.arena, e->copy_stream, host_frames, n,
+                                      reinterpret_cast<const float(*)[4]>(boxes.data()), grow.data(), dev.data(), nullptr))
         return rc;
     HIPCHK(hipEventRecord(sl.up_ev, e->copy_stream));
     HIPCHK(hipStreamWaitEvent(e->stream, sl.up_ev, 0));          // the pass starts behind ITS upload only
-    if (int rc = e->enqueue_streams(streams, dev.data(), n, sl.h_res, sl.h_st)) return rc;   // results land in THIS slot's buffers
+    if (int rc = e->enqueue(streams, dev.data(), n, sl.h_res, sl.h_st)) return rc;   // results land in THIS slot's buffers
     HIPCHK(hipEventRecord(sl.done_ev, e->stream));
     sl.host.assign(host_frames, host_frames + n);
     sl.list.assign(streams, streams + n);
@@ -287,17 +285,14 @@ static int enqueue_host_pass(Engine* e, const int32_t* streams, const vt_frame* 
 // new one. Never grown in place: freeing device memory waits for the device, and a queued init waits for nothing.
 static int queued_init_staging(Engine* e, size_t need, Engine::QueuedInit** out) {
     for (Engine::QueuedInit* q : e->qinits)
-        if (q && q->bytes >= need && q->done_ev && hipEventQuery(q->done_ev) == hipSuccess) { *out = q; return VT_OK; }
+        if (q && q->arena.cap >= need && q->done_ev && hipEventQuery(q->done_ev) == hipSuccess) { *out = q; return VT_OK; }
     (void)hipGetLastError();                 // hipErrorNotReady of the queries above is no error
     e->qinits.push_back(nullptr);
     Engine::QueuedInit* q = e->qinits.back() = new Engine::QueuedInit();   // the engine's from here on, whatever fails below
     HIPCHK(hipHostMalloc((void**)&q->h_state, sizeof(StreamState)));
     HIPCHK(hipHostMalloc((void**)&q->h_desc, sizeof(FrameDesc)));
     HIPCHK(hipEventCreateWithFlags(&q->up_ev, hipEventDisableTiming));
-    const size_t cap = need + need / 2 + 4096;
-    HIPCHK(hipMalloc((void**)&q->d_arena, cap));
-    HIPCHK(hipHostMalloc((void**)&q->h_arena, cap));
-    q->bytes = cap;
+    if (int rc = q->arena.ensure(need)) return rc;        // fresh: nothing is freed, nothing waits
     HIPCHK(hipEventCreateWithFlags(&q->done_ev, hipEventDisableTiming));   // last: a half-built one is never picked
     *out = q;
     return VT_OK;
@@ -324,35 +319,14 @@ int vt_group_update_host(vt_group* g, const vt_frame* host_frames, int n, vt_res
     if (n != e->B) return set_err(VT_ERR_INVALID_ARG, "update_host: need exactly %d frames", e->B);
     for (int b = 0; b < n; ++b)
         if (!e->h_initialized[b]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d not initialised", b);
-    if (e->host_seq != e->host_collected)
-        return set_err(VT_ERR_INVALID_ARG, "update_host: collect the pipelined passes first (vt_group_wait_next)");
-    DEVICE_SCOPE(e->device);
-    if (int rc = e->wait(nullptr, 0)) return rc;   // last pass done: its boxes are in `known`
-    std::vector<vt_frame> dev((size_t)n);
-    std::vector<float> boxes((size_t)n * 4);
-    for (int b = 0; b < n; ++b) memcpy(&boxes[(size_t)b * 4], e->known[b].box, 4 * sizeof(float));
-    if (int rc = stage_host_frames(e, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
-        return rc;
-    if (int rc = e->enqueue(dev.data(), n)) return rc;
-    return e->wait(out, n);
+    return update_host_pass(e, nullptr, host_frames, n, out, "update_host");
 } VT_NOTHROW_INT
 
 // the same window logic on the n streams of a subset pass: stream streams[i]'s window is cut around its own last box
 int vt_group_update_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n,
                                  vt_result* out) try {
-    if (!g || !host_frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
-    Engine* e = g->e;
-    if (int rc = refuse_while_pipelined(e, "update_host_streams")) return rc;
-    if (int rc = e->check_streams(streams, n)) return rc;
-    DEVICE_SCOPE(e->device);
-    if (int rc = e->wait(nullptr, 0)) return rc;   // last pass done: its boxes are in `known`
-    std::vector<vt_frame> dev((size_t)n);
-    std::vector<float> boxes((size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(&boxes[(size_t)i * 4], e->known[streams[i]].box, 4 * sizeof(float));
-    if (int rc = stage_host_frames(e, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
-        return rc;
-    if (int rc = e->enqueue_streams(streams, dev.data(), n)) return rc;
-    return e->wait(out, n);
+    if (!g || !streams || !host_frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    return update_host_pass(g->e, streams, host_frames, n, out, "update_host_streams");
 } VT_NOTHROW_INT
 
 int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n) try {
@@ -367,7 +341,7 @@ int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n) try {
 } VT_NOTHROW_INT
 
 int vt_group_enqueue_host_streams(vt_group* g, const int32_t* streams, const vt_frame* host_frames, int n) try {
-    if (!g || !host_frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    if (!g || !streams || !host_frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
     Engine* e = g->e;
     if (int rc = e->check_streams(streams, n)) return rc;
     return enqueue_host_pass(e, streams, host_frames, n, "enqueue_host_streams");
@@ -386,19 +360,12 @@ int vt_group_enqueue_init_host(vt_group* g, int stream, const vt_frame* host_fra
     // the frame's own checks, before anything is allocated or changed
     const float fb[1][4] = {{(float)box.x, (float)box.y, (float)box.width, (float)box.height}};
     HostWin probe;
-    if (int rc = plan_window(e, host_frame->format, (const uint8_t*)host_frame->plane0, (const uint8_t*)host_frame->plane1,
-                             host_frame->width, host_frame->height, host_frame->stride0, host_frame->stride1, fb[0], 0.0f,
-                             &probe))
-        return rc;
+    if (int rc = plan_window(e, *host_frame, fb[0], 0.0f, &probe)) return rc;
     DEVICE_SCOPE(e->device);
-    // the first stream on a format other than RGB8 / NV12 / YUY2 has the second graph set captured (Engine::init_stream);
-    // a capture needs the group's stream idle, so this one call waits for the outstanding passes (they stay
-    // uncollected): never a capture beside a running pass
-    if (e->use_graph && !e->want_any_graphs && pix_any_layout(host_frame->format)) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->want_any_graphs = true;
-        if (int rc = e->capture_all_graphs()) { e->want_any_graphs = false; return rc; }
-    }
+    // the first stream on a format other than RGB8 / NV12 / YUY2 has the second graph set captured; a capture needs
+    // the group's stream idle, so this one call waits for the outstanding passes (they stay uncollected): never a
+    // capture beside a running pass
+    if (int rc = e->capture_graphs_for(host_frame->format)) return rc;
     Engine::QueuedInit* q = nullptr;
     if (int rc = queued_init_staging(e, probe.bytes, &q)) return rc;
     // window packed into the init's own pinned arena now (the caller's buffer is free on return), uploaded on the
@@ -406,9 +373,8 @@ int vt_group_enqueue_init_host(vt_group* g, int stream, const vt_frame* host_fra
     // and behind that upload. Nothing here waits for the group's stream.
     vt_frame f;
     size_t up_bytes = 0;
-    const Arena a{&q->d_arena, &q->h_arena, &q->bytes, e->copy_stream};
     // packed also from registered memory: the crop runs after this call has returned
-    if (int rc = stage_host_frames_to(e, a, host_frame, 1, fb, nullptr, &f, &up_bytes, true)) return rc;
+    if (int rc = stage_host_frames_to(e, q->arena, e->copy_stream, host_frame, 1, fb, nullptr, &f, &up_bytes, true)) return rc;
     if (int rc = check_frame(f)) return rc;
     if (up_bytes) {
         HIPCHK(hipEventRecord(q->up_ev, e->copy_stream));
