@@ -254,3 +254,58 @@ pub unsafe fn group_enqueue_init_host(g: *mut sys::vt_group, stream: i32, host_f
     }
     Ok(())
 }
+
+/// The candidate state boxes whose search windows tile a `w` x `h` frame (vt_scan_windows), row by row; needs no GPU.
+/// Empty on arguments the library refuses.
+pub fn scan_windows(w: i32, h: i32, box_w: f32, box_h: f32, overlap_pct: i32) -> Vec<[f32; 4]> {
+    let n = unsafe { sys::vt_scan_windows(w, h, box_w, box_h, overlap_pct, std::ptr::null_mut(), 0) };
+    if n <= 0 {
+        return Vec::new();
+    }
+    let mut out = vec![[0f32; 4]; n as usize];
+    let got = unsafe { sys::vt_scan_windows(w, h, box_w, box_h, overlap_pct, out.as_mut_ptr() as *mut f32, n) };
+    out.truncate(got.clamp(0, n) as usize);
+    out
+}
+
+/// Look for a lost camera's target over the whole frame instead of sitting the frame out (≙ the `Lost` branch of
+/// src/tracker_context.rs:142-153): the windows of `scan_windows` for a `box_w` x `box_h` target, in grid order, in
+/// candidate passes (vt_group_update_host_candidates) of as many slots as the group has streams. Stops at the first
+/// pass whose winner succeeds and returns it, else the last pass's winner. Each pass is one update of `stream`; a
+/// failed scan leaves the stream's box where it was.
+///
+/// # Safety
+/// `g` is a live group handle with no pipelined pass outstanding; `host_frame`'s planes are readable for the
+/// duration of the call.
+pub unsafe fn group_reacquire_host(g: *mut sys::vt_group, stream: i32, host_frame: &sys::VtFrame, box_w: f32, box_h: f32,
+                                   overlap_pct: i32) -> Result<TrackResult, TrackError> {
+    let bad = |text: &str| TrackError { code: sys::VT_ERR_INVALID_ARG, text: text.into() };
+    let slots = sys::vt_group_streams(g);
+    if slots < 1 {
+        return Err(bad("null group"));
+    }
+    let boxes = scan_windows(host_frame.width, host_frame.height, box_w, box_h, overlap_pct);
+    if boxes.is_empty() {
+        return Err(bad("scan_windows refused the frame or box size"));
+    }
+    let mut best: Option<TrackResult> = None;
+    for chunk in boxes.chunks(slots as usize) {
+        let cands: Vec<sys::VtCandidate> = chunk.iter().map(|b| sys::VtCandidate { stream, has_box: 1, r#box: *b }).collect();
+        let frames: Vec<sys::VtFrame> = chunk.iter().map(|_| *host_frame).collect();
+        let mut out = vec![sys::VtResult::default(); chunk.len()];
+        let mut winner = vec![0i32; chunk.len()];
+        let rc = sys::vt_group_update_host_candidates(g, cands.as_ptr(), frames.as_ptr(), chunk.len() as c_int, out.as_mut_ptr(),
+                                                      winner.as_mut_ptr());
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        // every slot works for `stream`: winner[0] is the pass's winning slot
+        let w = winner.first().copied().unwrap_or(0).max(0) as usize;
+        let r: TrackResult = out.get(w).copied().ok_or_else(|| bad("winner out of range"))?.into();
+        best = Some(r);
+        if r.success {
+            break;
+        }
+    }
+    best.ok_or_else(|| bad("no scan window"))
+}

@@ -104,6 +104,15 @@ pub struct VtFrame {
     pub window_h: i32,
 }
 
+/// ≙ vt_candidate: one slot of a candidate pass
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct VtCandidate {
+    pub stream: i32,
+    pub has_box: i32,
+    pub r#box: [f32; 4],
+}
+
 /// ≙ vt_draw_cmd
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -196,6 +205,12 @@ extern "C" {
                                         out: *mut VtResult) -> c_int;
     pub fn vt_group_enqueue_host_streams(g: *mut vt_group, streams: *const i32, host_frames: *const VtFrame, n: c_int) -> c_int;
     pub fn vt_group_enqueue_init_host(g: *mut vt_group, stream: c_int, host_frame: *const VtFrame, bbox: BBox) -> c_int;
+    pub fn vt_group_update_device_candidates(g: *mut vt_group, cands: *const VtCandidate, frames: *const VtFrame, n: c_int,
+                                             out: *mut VtResult, winner: *mut i32) -> c_int;
+    pub fn vt_group_update_host_candidates(g: *mut vt_group, cands: *const VtCandidate, host_frames: *const VtFrame, n: c_int,
+                                           out: *mut VtResult, winner: *mut i32) -> c_int;
+    pub fn vt_scan_windows(frame_w: c_int, frame_h: c_int, box_w: f32, box_h: f32, overlap_pct: c_int, boxes4: *mut f32,
+                           cap: c_int) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

@@ -67,6 +67,12 @@ class CFrame(Structure):
                 ("windowed", c_int32), ("window_w", c_int32), ("window_h", c_int32)]
 
 
+class CCandidate(Structure):
+    """one slot of a candidate pass (vt_candidate): the stream it works for and, with has_box, the box its search
+    window is cut around instead of the stream's own state box"""
+    _fields_ = [("stream", c_int32), ("has_box", c_int32), ("box", c_float * 4)]
+
+
 class CDrawCmd(Structure):
     _fields_ = [("type", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
                 ("p", c_int32), ("value", c_int32), ("text", c_char * 36)]
@@ -96,6 +102,7 @@ EXPORTS = [
     "vt_group_profile_device", "vt_group_enable_taps", "vt_group_set_tuning", "vt_group_set_state_box", "vt_tracker_as_group",
     "vt_group_read_tensor", "vt_group_enqueue_device_streams", "vt_group_update_device_streams", "vt_group_update_host_streams",
     "vt_group_enqueue_host_streams", "vt_group_enqueue_init_host",
+    "vt_group_update_device_candidates", "vt_group_update_host_candidates", "vt_scan_windows",
     "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob", "vt_init_frame", "vt_update_frame",
 ]
 # every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
@@ -174,6 +181,10 @@ def lib():
     L.vt_group_update_host_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int, POINTER(CResult)]
     L.vt_group_enqueue_host_streams.argtypes = [c_void_p, POINTER(c_int32), POINTER(CFrame), c_int]
     L.vt_group_enqueue_init_host.argtypes = [c_void_p, c_int, POINTER(CFrame), CBBox]
+    L.vt_group_update_device_candidates.argtypes = [c_void_p, POINTER(CCandidate), POINTER(CFrame), c_int, POINTER(CResult),
+                                                    POINTER(c_int32)]
+    L.vt_group_update_host_candidates.argtypes = L.vt_group_update_device_candidates.argtypes
+    L.vt_scan_windows.argtypes = [c_int, c_int, c_float, c_float, c_int, POINTER(c_float), c_int]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -274,6 +285,17 @@ def plan_engines(info: "CModelInfo", n_streams: int) -> list:
     if k <= 0:
         raise ValueError(f"vt_plan_engines({n_streams}) failed")
     return [int(sizes[i]) for i in range(k)]
+
+
+def scan_windows(w: int, h: int, box_w: float, box_h: float, overlap_pct: int = 50) -> np.ndarray:
+    """vt_scan_windows: the candidate state boxes [n, 4] (x, y, w, h) whose search windows tile a w x h frame, row by
+    row; needs no GPU. Raises ValueError on arguments the library refuses."""
+    n = lib().vt_scan_windows(w, h, box_w, box_h, overlap_pct, None, 0)
+    if n <= 0:
+        raise ValueError(f"vt_scan_windows({w}, {h}, {box_w}, {box_h}, {overlap_pct}) refused its arguments")
+    out = np.empty((n, 4), np.float32)
+    lib().vt_scan_windows(w, h, box_w, box_h, overlap_pct, _f32(out), n)
+    return out
 
 
 class DmaBuf:
@@ -749,6 +771,69 @@ class Group:
             _check(lib().vt_group_update_host_streams(self._h, self._streams(streams, len(pairs)), arr, len(pairs), out))
         self._last_n = len(pairs)
         return [TrackResult(r) for r in out]
+
+    @staticmethod
+    def _cands(cands):
+        """CCandidate array of a candidate pass: items are CCandidate, a stream index, or (stream, box or None)"""
+        arr = (CCandidate * max(len(cands), 1))()
+        for i, c in enumerate(cands):
+            if isinstance(c, CCandidate):
+                arr[i] = c
+                continue
+            s, box = c if isinstance(c, (tuple, list)) else (c, None)
+            arr[i].stream = int(s)
+            if box is not None:
+                arr[i].has_box = 1
+                arr[i].box = (c_float * 4)(*[float(v) for v in box])
+        return arr
+
+    def update_device_candidates(self, cands, frames):
+        """one candidate pass (vt_group_update_device_candidates): slot i is cands[i] - a stream index, or (stream, box) -
+        on frames[i]; a stream may fill several slots, each an independent update around its own box, and only the
+        stream's best slot is committed. Returns (results by slot, winners: the winning slot of slot i's stream)."""
+        n = len(frames)
+        if len(cands) != n:
+            raise VtError(-1, f"{len(cands)} candidates for {n} frames")
+        out, win = (CResult * max(n, 1))(), (c_int32 * max(n, 1))()
+        _check(lib().vt_group_update_device_candidates(self._h, self._cands(cands), self._arr(frames), n, out, win))
+        self._last_n = n
+        return [TrackResult(out[i]) for i in range(n)], [int(win[i]) for i in range(n)]
+
+    def update_host_candidates(self, cands, frames):
+        """the same on HOST frames (vt_group_update_host_candidates): slots that are given the same frame object's
+        buffer are staged once, as the bounding rectangle of their windows"""
+        n = len(frames)
+        if len(cands) != n:
+            raise VtError(-1, f"{len(cands)} candidates for {n} frames")
+        pairs = [self._host_frame(fr) for fr in frames]
+        arr = (CFrame * max(n, 1))(*[p[0] for p in pairs])
+        out, win = (CResult * max(n, 1))(), (c_int32 * max(n, 1))()
+        _check(lib().vt_group_update_host_candidates(self._h, self._cands(cands), arr, n, out, win))
+        self._last_n = n
+        return [TrackResult(out[i]) for i in range(n)], [int(win[i]) for i in range(n)]
+
+    def reacquire(self, stream: int, frame, box_wh=None, overlap_pct: int = 50, host: bool = False):
+        """Look for a lost stream's target over the whole frame: the windows of scan_windows, in grid order, in candidate
+        passes of `streams` slots each; stops at the first chunk whose winner succeeds and returns that result, or the
+        last chunk's winner if none does. box_wh: the (w, h) of the candidate boxes, default the size of the stream's
+        state box. Each chunk is one update of the stream. frame: a CFrame of device memory, or with host=True a host
+        frame object. `last_scan` keeps every chunk's (results, winners) for inspection."""
+        if box_wh is None:
+            box_wh = self.read_state(stream)["box"][2:4]
+        cf = self._host_frame(frame)[0] if host else frame
+        boxes = scan_windows(cf.width, cf.height, float(box_wh[0]), float(box_wh[1]), overlap_pct)
+        step, best = self.streams, None
+        self.last_scan = []
+        for c0 in range(0, len(boxes), step):
+            chunk = boxes[c0:c0 + step]
+            cands = [(stream, b) for b in chunk]
+            fn = self.update_host_candidates if host else self.update_device_candidates
+            res, win = fn(cands, [frame] * len(chunk))
+            self.last_scan.append((res, win))
+            best = res[win[0]]
+            if best.success:
+                break
+        return best
 
     def enqueue_init_host(self, stream: int, frame, bbox: BBox):
         """(re)initialise `stream` behind the outstanding pipelined passes without waiting for them

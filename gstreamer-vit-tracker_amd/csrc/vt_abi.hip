@@ -301,7 +301,44 @@ int vt_group_update_device_streams(vt_group* g, const int32_t* streams, const vt
     if (int rc = g->e->enqueue(streams, frames, n)) return rc;
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
+int vt_group_update_device_candidates(vt_group* g, const vt_candidate* cands, const vt_frame* frames, int n,
+                                      vt_result* out, int32_t* winner) try {
+    if (!g || !cands || !frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    if (int rc = refuse_while_pipelined(g->e, "update_device_candidates")) return rc;
+    if (int rc = g->e->enqueue_candidates(cands, frames, n)) return rc;
+    return g->e->wait_candidates(out, winner, n);
+} VT_NOTHROW_INT
 void* vt_group_hip_stream(vt_group* g) { return g ? (void*)g->e->stream : nullptr; }
+
+// One axis of vt_scan_windows: the window centres along a side of length L
+static int scan_axis(double L, double side, double stride, std::vector<double>* c) {
+    c->clear();
+    if (L <= side) { c->push_back(0.5 * L); return 1; }
+    const int n = (int)std::ceil((L - side) / stride) + 1;
+    for (int i = 0; i < n; ++i) c->push_back(0.5 * side + (double)i * (L - side) / (double)(n - 1));
+    return n;
+}
+
+int vt_scan_windows(int frame_w, int frame_h, float box_w, float box_h, int overlap_pct, float* boxes4, int cap) try {
+    if (frame_w < 16 || frame_h < 16 || frame_w > 65536 || frame_h > 65536 || overlap_pct < 0 || overlap_pct > 90 || cap < 0 || (cap > 0 && !boxes4)) return 0;
+    if (!std::isfinite(box_w) || !std::isfinite(box_h) || !(box_w >= 1.0f) || !(box_h >= 1.0f) || box_w > 32768.0f ||
+        box_h > 32768.0f)
+        return 0;
+    const double side = 4.0 * std::sqrt((double)box_w * (double)box_h);
+    const double stride = side * (double)(100 - overlap_pct) / 100.0;
+    std::vector<double> cx, cy;
+    const int nx = scan_axis((double)frame_w, side, stride, &cx), ny = scan_axis((double)frame_h, side, stride, &cy);
+    int k = 0;
+    for (int iy = 0; iy < ny && k < cap; ++iy)
+        for (int ix = 0; ix < nx && k < cap; ++ix, ++k) {
+            float* o = boxes4 + 4 * (size_t)k;
+            o[0] = (float)(cx[(size_t)ix] - 0.5 * (double)box_w);
+            o[1] = (float)(cy[(size_t)iy] - 0.5 * (double)box_h);
+            o[2] = box_w;
+            o[3] = box_h;
+        }
+    return (int)std::min<long long>((long long)nx * ny, 0x7fffffff);
+} VT_NOTHROW_INT
 
 int vt_group_enable_taps(vt_group* g, int enable) try {
     if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
@@ -335,12 +372,7 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4) try {
     if (stream < 0 || stream >= e->B) return set_err(VT_ERR_INVALID_ARG, "bad stream index");
     if (!e->h_initialized[stream]) return set_err(VT_ERR_NOT_INITIALIZED, "stream %d not initialised", stream);
     if (int rc = refuse_while_pipelined(e, "set_state_box")) return rc;
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(box4[k])) return set_err(VT_ERR_INVALID_ARG, "state box: non-finite value");
-    if (!(box4[2] >= 1.0f) || !(box4[3] >= 1.0f) || box4[2] > 32768.0f || box4[3] > 32768.0f ||
-        fabsf(box4[0]) > 65536.0f || fabsf(box4[1]) > 65536.0f)
-        return set_err(VT_ERR_INVALID_ARG, "state box %g,%g %gx%g out of range", box4[0], box4[1],
-                       box4[2], box4[3]);
+    if (int rc = check_state_box(box4)) return rc;
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(e->d_states[stream].box, box4, 4 * sizeof(float), hipMemcpyHostToDevice));
@@ -434,10 +466,14 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
     if (hipStreamSynchronize(e->stream) != hipSuccess)
         return set_err(VT_ERR_HIP, "read_tensor: sync failed");
     const ModelDims& d = e->d;
-    const std::string n(name);
+    std::string n(name);
     // every tensor but the stream's state and the replay counters belongs to the last pass: the stream's slot in it
     size_t b = (size_t)stream;
-    if (n != "state" && n != "graph_replays") {
+    if (n.rfind("slot.", 0) == 0) {     // "slot.<tensor>": `stream` IS a slot of the last pass (the losing slots of a candidate pass)
+        n = n.substr(5);
+        if (n == "state" || n == "graph_replays" || stream >= e->pass_n)
+            return set_err(VT_ERR_INVALID_ARG, "read_tensor: '%s' of slot %d: no such slot tensor in the last pass", name, stream);
+    } else if (n != "state" && n != "graph_replays") {
         const int slot = e->slot_of(stream);
         if (slot < 0) return set_err(VT_ERR_INVALID_ARG, "read_tensor: stream %d was not in the last pass", stream);
         b = (size_t)slot;

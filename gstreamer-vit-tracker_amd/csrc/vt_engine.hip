@@ -37,9 +37,11 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results};
+                    d_results, d_cand_states, d_cands, d_winner};
     for (void* p : devp)
         if (p) (void)hipFree(p);
+    if (h_cands) (void)hipHostFree(h_cands);
+    if (h_winner) (void)hipHostFree(h_winner);
     if (h_frames) (void)hipHostFree(h_frames);
     if (h_results) (void)hipHostFree(h_results);
     if (h_state) (void)hipHostFree(h_state);
@@ -95,10 +97,21 @@ int Engine::pick_crop_tier(const int32_t* streams, int n) const {
     return t;
 }
 
+// A candidate pass looks at its slots' own boxes: a slot without one works on its stream's known box.
+int Engine::pick_crop_tier(const vt_candidate* cands, int n) const {
+    if (crop_tier_forced >= 0) return std::min(crop_tier_forced, TIERS - 1);
+    int t = 0;
+    for (int i = 0; i < n && t < TIERS - 1; ++i) {
+        const float* box = cands[i].has_box ? cands[i].box : known[(size_t)cands[i].stream].box;
+        t = std::max(t, std::min(preproc_tier_for_box(d, box[2], box[3], false), TIERS - 1));
+    }
+    return t;
+}
+
 int Engine::slot_of(int stream) const {
     if (pass_streams.empty()) return stream < pass_n ? stream : -1;
     for (size_t i = 0; i < pass_streams.size(); ++i)
-        if (pass_streams[i] == stream) return (int)i;
+        if (pass_streams[i] == stream) return i < pass_winner.size() ? (int)pass_winner[i] : (int)i;
     return -1;
 }
 
@@ -323,10 +336,14 @@ double Engine::flops_head() const {
 
 // One hot-path pass over ps.n slots: all B streams (slot_stream null: slot b is stream b), or a subset pass, whose slot i
 // works for stream slot_stream[i] (device map). Between the crop and the decode every kernel is slot-indexed and
-// sized by M = n * ntok. With prof != nullptr every launch is bracketed by HIP events on this engine's stream.
+// sized by M = n * ntok. A candidate pass (ps.cand) runs the same kernels on its slots' candidate states - the map then
+// only says whose template a slot takes - between the fill and the commit of k_cand.hip. With prof != nullptr every launch is bracketed by HIP events on this engine's stream.
 int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     const int n = ps.n;
     const int32_t* slot_stream = ps.slot_stream;
+    // whose state a slot reads and writes: its stream's through the map, or its own candidate state
+    StreamState* const states = ps.cand ? ps.cand->cand_states : d_states;
+    const int32_t* const state_map = ps.cand ? nullptr : slot_stream;
     const int M = n * d.ntok, Ms = n * d.ns, D = d.D;
     hipError_t lerr = hipSuccess;
     auto L = [&](const char* name, double flops, double bytes, auto&& fn) {
@@ -410,8 +427,10 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     if (slot_stream)        // the slots' template rows from the store (a full pass finds them in place)
         L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
           [&] { return launch_gather_template_rows(d_tpl, d_patches, slot_stream, n, d, stream); });
+    if (ps.cand)
+        L("cand_fill", 0, 2.0 * n * sizeof(StreamState), [&] { return launch_cand_fill(*ps.cand, stream); });
     L("preproc_search", 0, (double)n * (d.S * d.S * 3 * 2 + 1.5 * d.S * d.S),
-      [&] { return launch_preproc(d_frames, d_states, d_patches, d, 0, n, false, stream, ps.tier, slot_stream, ps.any_layout); });
+      [&] { return launch_preproc(d_frames, states, d_patches, d, 0, n, false, stream, ps.tier, state_map, ps.any_layout); });
     // K2: patch embedding (+bias +pos) -> residual stream (3-byte pair + chunk statistics)
     {
         GemmArgs a{};
@@ -464,9 +483,9 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     dec.w4 = (const float*)find("head.w4")->ptr;
     dec.b4 = (const float*)find("head.b4")->ptr;
     dec.hann = (const float*)find("hann")->ptr;
-    dec.head_out = d_headout; dec.states = d_states; dec.results = d_results;
+    dec.head_out = d_headout; dec.states = states; dec.results = d_results;
     dec.out = (const PassOut*)(d_frames + B);      // behind the B descriptors whatever the pass's slot count
-    dec.slot_stream = slot_stream;
+    dec.slot_stream = state_map;
     dec.B = n; dec.ns = d.ns; dec.grid = d.gs; dec.C = d.C;
     dec.success_threshold = success_threshold;
     bf16_t* cur = d_ta;
@@ -519,6 +538,8 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         dec.t3 = cur;
         L("decode", 2.0 * Ms * d.C * 5, (double)Ms * d.C * 2, [&] { return launch_decode(dec, stream); });
     }
+    if (ps.cand)
+        L("cand_commit", 0, 2.0 * n * sizeof(StreamState), [&] { return launch_cand_commit(*ps.cand, stream); });
     if (lerr != hipSuccess)
         return set_err(VT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
@@ -531,7 +552,7 @@ hipError_t Engine::final_layernorm(int n) {
 
 int Engine::capture_graph(int tier, bool any_layout) {
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    int rc = run_pass(nullptr, PassShape{B, nullptr, tier, any_layout});
+    int rc = run_pass(nullptr, PassShape{B, nullptr, tier, any_layout, nullptr});
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(stream, &g);
     if (rc != VT_OK) {
@@ -721,7 +742,9 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
     ring_pos = (ring_pos + 1) % RING;
     HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copy that last used this block is done
     FrameDesc* hf = h_block(slot);
-    *ps = PassShape{n, full ? nullptr : d_map(), 0, false};
+    *ps = PassShape{n, full ? nullptr : d_map(), 0, false, nullptr};
+    pass_winner.clear();
+    cand_pending = false;
     for (int i = 0; i < n; ++i) {
         to_desc(frames[i], hf + i);
         ps->any_layout = ps->any_layout || pix_any_layout(frames[i].format);
@@ -775,6 +798,107 @@ int Engine::wait(vt_result* out, int n) {
         for (int b = 0; b < n; ++b) out[b] = h_results[b];
     if (host_seq == host_collected)                 // no pipelined pass owns the stream states
         for (int b = 0; b < B; ++b) known[b] = h_states_all[b];
+    return VT_OK;
+}
+
+// ---- candidate passes --------------------------------------------------------------------------------
+
+int check_state_box(const float* box4) {
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(box4[k])) return set_err(VT_ERR_INVALID_ARG, "state box: non-finite value");
+    if (!(box4[2] >= 1.0f) || !(box4[3] >= 1.0f) || box4[2] > 32768.0f || box4[3] > 32768.0f ||
+        fabsf(box4[0]) > 65536.0f || fabsf(box4[1]) > 65536.0f)
+        return set_err(VT_ERR_INVALID_ARG, "state box %g,%g %gx%g out of range", box4[0], box4[1],
+                       box4[2], box4[3]);
+    return VT_OK;
+}
+
+int Engine::ensure_candidate_buffers() {
+    if (h_winner) return VT_OK;
+    if (!d_cand_states) HIPCHK(dalloc0(&d_cand_states, (size_t)B, stream));
+    if (!d_cands) HIPCHK(dalloc0(&d_cands, (size_t)B, stream));
+    if (!d_winner) HIPCHK(dalloc0(&d_winner, (size_t)B, stream));
+    if (!h_cands) HIPCHK(hipHostMalloc((void**)&h_cands, sizeof(vt_candidate) * (size_t)B * RING));
+    HIPCHK(hipHostMalloc((void**)&h_winner, sizeof(int32_t) * (size_t)B));
+    memset(h_winner, 0, sizeof(int32_t) * (size_t)B);
+    return VT_OK;
+}
+
+int Engine::check_candidates(const vt_candidate* cands, int n) const {
+    if (!cands) return set_err(VT_ERR_INVALID_ARG, "null candidate list");
+    if (n < 1 || n > B) return set_err(VT_ERR_INVALID_ARG, "pass over %d candidate slots: need 1..%d", n, B);
+    for (int i = 0; i < n; ++i) {
+        const int s = cands[i].stream;
+        if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "cands[%d].stream = %d out of range (0..%d)", i, s, B - 1);
+        if (cands[i].has_box)
+            if (int rc = check_state_box(cands[i].box)) return rc;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!h_initialized[cands[i].stream])
+            return set_err(VT_ERR_NOT_INITIALIZED, "stream %d: update before init", cands[i].stream);
+    return VT_OK;
+}
+
+// every stream once and no slot with a box: the list is a subset pass over `streams`
+bool Engine::plain_list(const vt_candidate* cands, int n, std::vector<int32_t>* streams) {
+    streams->assign((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (cands[i].has_box) return false;
+        for (int j = 0; j < i; ++j)
+            if (cands[j].stream == cands[i].stream) return false;
+        (*streams)[(size_t)i] = cands[i].stream;
+    }
+    return true;
+}
+
+int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames, int n) {
+    if (int rc = check_candidates(cands, n)) return rc;
+    if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
+    for (int i = 0; i < n; ++i)
+        if (int rc = check_frame(frames[i])) return rc;
+    std::vector<int32_t> streams;
+    if (plain_list(cands, n, &streams)) return enqueue(streams.data(), frames, n);
+    for (int i = 0; i < n; ++i) streams[(size_t)i] = cands[i].stream;
+    DEVICE_SCOPE(device);
+    if (int rc = ensure_candidate_buffers()) return rc;
+    const int slot = ring_pos;
+    ring_pos = (ring_pos + 1) % RING;
+    HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copies that last used these blocks are done
+    FrameDesc* hf = h_block(slot);
+    vt_candidate* hc = h_cands + (size_t)slot * B;
+    // the template gather keeps the slot -> stream map; the decode stores results by slot and NO state to the host:
+    // only the commit kernel writes by-stream copies
+    const CandArgs ca{d_cands, d_states, d_cand_states, d_results, d_winner, h_states_all, h_winner, n};
+    PassShape ps{n, d_map(), 0, false, &ca};
+    int32_t* map = (int32_t*)((char*)hf + map_offset());
+    for (int i = 0; i < n; ++i) {
+        to_desc(frames[i], hf + i);
+        ps.any_layout = ps.any_layout || pix_any_layout(frames[i].format);
+        map[i] = cands[i].stream;
+        hc[i] = cands[i];
+    }
+    *(PassOut*)(hf + B) = PassOut{h_results, nullptr};
+    HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_cands, hc, sizeof(vt_candidate) * (size_t)n, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ring_ev[slot], stream));
+    segments_moved = true;          // the next full pass restores every stream's template rows
+    pass_streams = streams;
+    pass_winner.clear();
+    cand_pending = true;
+    pass_n = n;
+    feat_in_head = head_ln_fused();
+    ps.tier = pick_crop_tier(cands, n);
+    return run_pass(nullptr, ps);
+}
+
+int Engine::wait_candidates(vt_result* out, int32_t* winner, int n) {
+    if (int rc = wait(out, n)) return rc;
+    if (cand_pending) {             // the winner table of the commit kernel; slot_of reads a stream's winning slot from now on
+        pass_winner.assign(h_winner, h_winner + pass_n);
+        cand_pending = false;
+    }
+    if (winner)
+        for (int i = 0; i < std::min(n, pass_n); ++i) winner[i] = pass_winner.empty() ? i : pass_winner[(size_t)i];
     return VT_OK;
 }
 

@@ -5,7 +5,7 @@
 //   vt_abi.hip      the extern "C" boundary of include/vittrack_hip.h (create / init / update, device-frame passes of a
 //                   group, diagnostics, colour converter, overlays, dma-buf and host-mapping ingest)
 //   vt_ingest.hip   host-frame ingest: the staging arena, window planning and packing, the host-frame passes of a group
-//                   (synchronous, pipelined enqueue_host / wait_next, queued init)
+//                   (synchronous, pipelined enqueue_host / wait_next, queued init, candidate passes on host frames)
 //   vt_rccl.hip     the start-up weight broadcast over a lazily loaded librccl
 //   vt_ops.hip      operator-level entry points of include/vittrack_hip_ops.h - linked into
 //                   libvittrack_hip_ops.so (tests, tuning tools) only, NOT into the product library
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "vt_common.hpp"
+#include "k_cand.hpp"
 
 // ---- error plumbing ------------------------------------------------------------------------------
 
@@ -121,6 +122,10 @@ struct PassShape {
     const int32_t* slot_stream = nullptr;   // device map slot -> stream of a subset pass; null: the full pass (n == B, slot b is stream b)
     int tier = 0;                           // crop-buffer tier (Engine::pick_crop_tier)
     bool any_layout = false;                // some slot's frame is not RGB8 / NV12 / YUY2 (k_preproc.hip: fetch_rgb<true>)
+    // a candidate pass (k_cand.hip): slot_stream says whose TEMPLATE a slot takes; its STATE is the slot's own candidate
+    // state (cand->cand_states, identity map), filled ahead of the crop and committed behind the decode. Null: a
+    // slot's state is its stream's.
+    const CandArgs* cand = nullptr;
 };
 
 // Where the packed windows of host frames go: a pinned host arena and its device twin of the same capacity
@@ -164,6 +169,12 @@ struct Engine {
     bf16_t* d_tpl = nullptr;
     bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
     vt_result* d_results = nullptr;
+    // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
+    // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
+    StreamState* d_cand_states = nullptr;
+    vt_candidate *d_cands = nullptr, *h_cands = nullptr;
+    int32_t *d_winner = nullptr, *h_winner = nullptr;
+    int ensure_candidate_buffers();
     // pinned host
     static const int RING = 8;
     FrameDesc* h_frames = nullptr;  // [RING] blocks of B descriptors + PassOut + the slot map (16-B multiples)
@@ -175,7 +186,11 @@ struct Engine {
     int pass_n = 1;
     std::vector<int32_t> pass_streams;
     bool feat_in_head = false;
-    int slot_of(int stream) const;      // slot of `stream` in the last pass, -1 if it was not in it
+    // after a candidate pass: pass_streams[i] is slot i's stream (streams may repeat) and pass_winner[i] the winning slot
+    // of that stream; empty after every other pass
+    std::vector<int32_t> pass_winner;
+    bool cand_pending = false;          // the last pass enqueued was a candidate pass whose winners have not been collected
+    int slot_of(int stream) const;      // slot of `stream` in the last pass (a candidate pass: its winning slot), -1 if it was not in it
     FrameDesc* h_block(int slot) const { return (FrameDesc*)((char*)h_frames + (size_t)slot * frames_block_bytes()); }
     hipEvent_t ring_ev[RING]{};
     int ring_pos = 0;
@@ -255,6 +270,7 @@ struct Engine {
     int capture_all_graphs();
     int capture_graphs_for(int format);           // the graphs[1] set, once, when a stream starts on a format that needs it
     int pick_crop_tier(const int32_t* streams = nullptr, int n = 0) const;   // streams == null: all B
+    int pick_crop_tier(const vt_candidate* cands, int n) const;              // a candidate pass: from the slots' boxes
     void drop_graphs();
     // One pass over streams[0..n), frames[i] for streams[i]; streams == null: all B streams in order (n == B), and no
     // list is built for it. VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input (checked in
@@ -267,6 +283,13 @@ struct Engine {
     int enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
                 StreamState* host_st = nullptr);
     int wait(vt_result* out, int n);
+    // A candidate pass over cands[0..n) (k_cand.hip): checked (list, boxes, initialisation, frames - nothing enqueued
+    // on bad input), built and launched eagerly. A list that is a plain subset pass - every stream once, no box - goes
+    // through enqueue() as that pass. wait_candidates collects results and winners and gives slot_of the winner's meaning.
+    int check_candidates(const vt_candidate* cands, int n) const;
+    static bool plain_list(const vt_candidate* cands, int n, std::vector<int32_t>* streams);
+    int enqueue_candidates(const vt_candidate* cands, const vt_frame* frames, int n);
+    int wait_candidates(vt_result* out, int32_t* winner, int n);
     int init_stream(int b, const vt_frame* f, vt_bbox box);
     const TensorRef* find(const std::string& n) const {
         auto it = tens.find(n);
@@ -292,6 +315,7 @@ int check_device(int device_id);
 int make_engine(const char* path, const void* d_src, size_t bytes, int device_id, const vt_config* cfg, int B, Engine** out);
 void fill_info(const Engine* e, vt_model_info* o);
 int check_frame(const vt_frame& f);
+int check_state_box(const float* box4);     // the one check of a caller's state box (vt_group_set_state_box, candidate slots)
 void to_desc(const vt_frame& f, FrameDesc* o);
 
 // ---- handles of the C ABI --------------------------------------------------------------------------
@@ -306,7 +330,8 @@ struct vt_tracker {                 // view: the tracker as a group of one
 int refuse_while_pipelined(const Engine* e, const char* what);
 
 // ---- host-frame ingest (vt_ingest.hip) ---------------------------------------------------------------
-int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev);
+// share: slots that name the same host frame are staged once, as the bounding rectangle of their windows
+int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev, bool share = false);
 const uint8_t* mapped_device_ptr(int device, const uint8_t* p, size_t bytes);
 
 struct DevBuf {

@@ -23,6 +23,21 @@ static size_t packed_row_bytes(int fmt, int ww) {
     return pix_row_bpp(fmt) == 4 ? (rb + 15) & ~(size_t)15 : rb;
 }
 
+// bytes of a window's packed form in the arena, from its extent
+static void size_window(HostWin* win) {
+    if (pix_family(win->fmt) == PIXF_420SP) {
+        // rows of the packed window start on 16-byte boundaries: the pixel kernel then fetches 8 pixels per load
+        const int uvh = (win->wh + 1) / 2;
+        const size_t ys = ((size_t)win->ww + 15) & ~(size_t)15, uvs = ((size_t)((win->ww + 1) & ~1) + 15) & ~(size_t)15;
+        win->uv_off = (ys * win->wh + 255) & ~(size_t)255;
+        win->bytes = win->uv_off + uvs * uvh;
+    } else {
+        win->uv_off = 0;
+        win->bytes = packed_row_bytes(win->fmt, win->ww) * win->wh;
+    }
+    win->bytes = (win->bytes + 255) & ~(size_t)255;
+}
+
 // `grow`: enlargement of the crop side for a SPECULATIVE window (the box of the pass that is still
 // running is not known): 0 = the exact crop
 static int plan_window(const Engine* e, const vt_frame& hf, const float* box, float grow, HostWin* win) {
@@ -57,18 +72,13 @@ static int plan_window(const Engine* e, const vt_frame& hf, const float* box, fl
     win->fmt = fmt; win->w = w; win->h = h; win->s0 = s0; win->s1 = s1; win->p0 = p0; win->p1 = p1;
     win->x_lo = (int)x_lo; win->y_lo = (int)y_lo;
     win->ww = (int)(x_hi - x_lo); win->wh = (int)(y_hi - y_lo);
-    if (fam == PIXF_420SP) {
-        // rows of the packed window start on 16-byte boundaries: the pixel kernel then fetches 8 pixels per load
-        const int uvh = (win->wh + 1) / 2;
-        const size_t ys = ((size_t)win->ww + 15) & ~(size_t)15, uvs = ((size_t)((win->ww + 1) & ~1) + 15) & ~(size_t)15;
-        win->uv_off = (ys * win->wh + 255) & ~(size_t)255;
-        win->bytes = win->uv_off + uvs * uvh;
-    } else {
-        win->uv_off = 0;
-        win->bytes = packed_row_bytes(fmt, win->ww) * win->wh;
-    }
-    win->bytes = (win->bytes + 255) & ~(size_t)255;
+    size_window(win);
     return VT_OK;
+}
+
+static bool same_host_frame(const vt_frame& a, const vt_frame& b) {
+    return a.plane0 == b.plane0 && a.plane1 == b.plane1 && a.width == b.width && a.height == b.height &&
+           a.stride0 == b.stride0 && a.stride1 == b.stride1 && a.format == b.format;
 }
 
 // The one growth rule of a staging arena: half as much again as asked for. The old pair is freed here - hipFree waits
@@ -120,11 +130,20 @@ static void pack_window(const StageArena& a, const HostWin& wn, size_t off, vt_f
 // boxes[i]: the box that decides frame i's window (the new box at init, the last state at update);
 // grow[i]: its enlargement (plan_window), null: every window exact. pack_all: no zero-copy route, whatever the
 // configuration says (the kernels must not read the caller's memory after the call has returned).
+// share (candidate passes): slots that name the same host frame are staged ONCE, as the bounding rectangle of their
+// windows, and all take that one descriptor - every slot's own window lies inside it, so each still samples exactly
+// the pixels it would from a window of its own.
 static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, const vt_frame* host, int n,
                                 const float (*boxes)[4], const float* grow, vt_frame* dev, size_t* bytes_out,
-                                bool pack_all = false) {
+                                bool pack_all = false, bool share = false) {
     std::vector<HostWin> wins((size_t)n);
     std::vector<char> mapped((size_t)n, 0);
+    std::vector<int> first((size_t)n);          // the first slot with the same frame (itself: staged on its own)
+    for (int i = 0; i < n; ++i) {
+        first[(size_t)i] = i;
+        for (int j = 0; share && j < i; ++j)
+            if (first[(size_t)j] == j && same_host_frame(host[i], host[j])) { first[(size_t)i] = j; break; }
+    }
     size_t total = 0;
     for (int i = 0; i < n; ++i) {
         const vt_frame& hf = host[i];
@@ -133,7 +152,7 @@ static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, c
         // single-stream engines, or where the caller asked for it: for a batched engine the packed upload beside
         // the previous pass is faster than PCIe reads inside the pass (vt_config.host_zero_copy, vittrack_hip.h)
         const bool zc = !pack_all && (e->host_zero_copy > 0 || (e->host_zero_copy == 0 && e->B == 1));
-        if (!zc) { total += wins[i].bytes; continue; }
+        if (!zc) continue;
         // bytes the kernels may touch: every row of the frame, the last one only as far as it is wide
         const bool sp = pix_family(hf.format) == PIXF_420SP;
         const size_t rowb = (size_t)hf.width * pix_row_bpp(hf.format);
@@ -146,10 +165,20 @@ static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, c
             memset(&dev[i], 0, sizeof(vt_frame));
             dev[i].plane0 = d0; dev[i].plane1 = d1; dev[i].width = hf.width; dev[i].height = hf.height;
             dev[i].stride0 = hf.stride0; dev[i].stride1 = hf.stride1; dev[i].format = hf.format;
-            continue;
         }
-        total += wins[i].bytes;
     }
+    for (int i = 0; i < n; ++i) {               // a shared frame's window grows to hold every slot's
+        const int f = first[(size_t)i];
+        if (f == i || mapped[(size_t)i]) continue;
+        HostWin& u = wins[(size_t)f];
+        const HostWin& w = wins[(size_t)i];
+        const int x_hi = std::max(u.x_lo + u.ww, w.x_lo + w.ww), y_hi = std::max(u.y_lo + u.wh, w.y_lo + w.wh);
+        u.x_lo = std::min(u.x_lo, w.x_lo); u.y_lo = std::min(u.y_lo, w.y_lo);
+        u.ww = x_hi - u.x_lo; u.wh = y_hi - u.y_lo;
+        size_window(&u);
+    }
+    for (int i = 0; i < n; ++i)
+        if (!mapped[(size_t)i] && first[(size_t)i] == i) total += wins[(size_t)i].bytes;
     if (bytes_out) *bytes_out = total;
     if (total == 0) return VT_OK;            // every frame mapped: nothing to pack, nothing to copy
     DEVICE_SCOPE(e->device);
@@ -161,6 +190,7 @@ static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, c
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         if (mapped[(size_t)i]) continue;
+        if (first[(size_t)i] != i) { dev[i] = dev[first[(size_t)i]]; continue; }    // packed already: first[i] < i
         pack_window(a, wins[i], off, &dev[i]);
         off += wins[i].bytes;
     }
@@ -170,8 +200,8 @@ static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, c
 
 // the synchronous entry points: one arena, copy on the engine's own stream (every such call waits
 // for its pass before returning, so the arena is free again at the next call)
-int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev) {
-    return stage_host_frames_to(e, e->stage, e->stream, host, n, boxes, nullptr, dev, nullptr);
+int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxes)[4], vt_frame* dev, bool share) {
+    return stage_host_frames_to(e, e->stage, e->stream, host, n, boxes, nullptr, dev, nullptr, false, share);
 }
 
 // ---- pipelined host passes -------------------------------------------------------------------------
@@ -327,6 +357,26 @@ int vt_group_update_host_streams(vt_group* g, const int32_t* streams, const vt_f
                                  vt_result* out) try {
     if (!g || !streams || !host_frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
     return update_host_pass(g->e, streams, host_frames, n, out, "update_host_streams");
+} VT_NOTHROW_INT
+
+// A candidate pass on host frames: every slot's window is cut around the slot's own box (exact: nothing is
+// speculative, no redo), slots on one host frame share one staged rectangle; then the device form.
+int vt_group_update_host_candidates(vt_group* g, const vt_candidate* cands, const vt_frame* host_frames, int n,
+                                    vt_result* out, int32_t* winner) try {
+    if (!g || !cands || !host_frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    Engine* e = g->e;
+    if (int rc = refuse_while_pipelined(e, "update_host_candidates")) return rc;
+    if (int rc = e->check_candidates(cands, n)) return rc;
+    DEVICE_SCOPE(e->device);
+    if (int rc = e->wait(nullptr, 0)) return rc;   // last pass done: its boxes are in `known`
+    std::vector<float> boxes((size_t)n * 4);
+    for (int i = 0; i < n; ++i)
+        memcpy(&boxes[(size_t)i * 4], cands[i].has_box ? cands[i].box : e->known[(size_t)cands[i].stream].box, 4 * sizeof(float));
+    std::vector<vt_frame> dev((size_t)n);
+    if (int rc = stage_host_frames(e, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data(), true))
+        return rc;
+    if (int rc = e->enqueue_candidates(cands, dev.data(), n)) return rc;
+    return e->wait_candidates(out, winner, n);
 } VT_NOTHROW_INT
 
 int vt_group_enqueue_host(vt_group* g, const vt_frame* host_frames, int n) try {

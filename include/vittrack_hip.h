@@ -341,6 +341,61 @@ int vt_group_enqueue_host_streams(vt_group* g, const int32_t* streams, const vt_
  * needs an idle stream, so that one call waits for the outstanding passes (they stay uncollected). */
 int vt_group_enqueue_init_host(vt_group* g, int stream, const vt_frame* host_frame, vt_bbox box);
 
+/* ---- candidate passes: several search windows per stream, the best one committed -----------------
+ * A stream owns one search window per update, cut around its own state box (side 4*sqrt(w*h)); once the target is
+ * outside it every later update fails in the same place (≙ the reference host's Lost state, which makes no tracker
+ * call for 61 frames and then waits for a new selection, src/tracker_context.rs:142-153). A candidate pass evaluates
+ * several windows for such a stream in ONE pass, beside the cameras that are tracking, and decides on the device. */
+typedef struct vt_candidate {
+    int32_t stream;    /* the stream this slot works for; may repeat within a pass */
+    int32_t has_box;   /* 0: window around the stream's own state box (what an update does); 1: around box */
+    float box[4];      /* x, y, w, h in frame pixels, top-left + size; read only when has_box == 1 */
+} vt_candidate;        /* 24 bytes */
+/* One pass over the n slots cands[0..n), 1 <= n <= vt_group_streams(g): a pass has as many slots as the engine has
+ * streams, whichever streams fill them. frames[i] feeds slot i, out[i] (not null) is slot i's result. Synchronous,
+ * like vt_group_update_device_streams.
+ * Slot results: every slot is a complete, independent update of cands[i].stream's template on frames[i], its window
+ * cut around the slot's box. Slot i's result and per-pass tensors are bit-identical to those of slot i of an n-stream
+ * group whose stream i holds cands[i].stream's template and had its box set to the slot's box (M = n x the tokens of
+ * one frame, rows independent: the contract of the subset passes).
+ * Winner: among the slots of one stream the one with the greatest vt_result.score; a NaN score loses to any number;
+ * equal scores: the lowest slot index. winner[i] (winner may be null) is the winning slot of cands[i].stream, so
+ * winner[i] == i marks the winners.
+ * Commit: a listed stream's state after the pass is the winner's - crop geometry, frame size, argmax cell, unrounded
+ * box, score, window-miss mark. Its update count advances by ONE per pass however many slots it had, its success
+ * count by the winner's success. Its state box becomes the winner's integer box if the winner succeeded; if not it
+ * stays what it was BEFORE the pass, never a candidate's box. Losing slots leave no trace in any stream's state.
+ * Streams not listed are untouched, bit for bit, and need not be initialised.
+ * A list in which every stream occurs once with has_box == 0 IS vt_group_update_device_streams over those streams
+ * (same results, same state words; the identity list replays the captured graph). Every other list launches eagerly:
+ * vt_group_graph_captures stays constant.
+ * Errors return with nothing enqueued, no state changed and no result written. VT_ERR_INVALID_ARG: a null pointer, n
+ * out of range, a stream index out of range, an invalid frame, a box that vt_group_set_state_box would refuse (a
+ * non-finite value, a side outside 1..32768, |x| or |y| above 65536); VT_ERR_NOT_INITIALIZED: a listed stream that
+ * was never initialised. Refused (VT_ERR_INVALID_ARG) while a pipelined host pass is outstanding; candidate passes
+ * have no pipelined form.
+ * vt_group_read_tensor(g, stream, ...) after a candidate pass reads the WINNING slot's tensors; "state" is the
+ * committed state. */
+int vt_group_update_device_candidates(vt_group* g, const vt_candidate* cands, const vt_frame* frames, int n,
+                                      vt_result* out, int32_t* winner);
+/* The same with HOST frames: slot i's window is cut from host_frames[i] around the slot's box and is exact, so no
+ * redo can occur. Slots that name the SAME host frame (equal planes, strides, size and format) are staged once, as
+ * the bounding rectangle of their windows - a scan whose windows overlap by half would otherwise upload every pixel
+ * four times. Frames inside a vt_host_register range take the zero-copy route under the vt_config.host_zero_copy
+ * rule, unchanged. Bit-identical to the device form on the same pixels. */
+int vt_group_update_host_candidates(vt_group* g, const vt_candidate* cands, const vt_frame* host_frames, int n,
+                                    vt_result* out, int32_t* winner);
+/* The candidate state boxes whose search windows tile a frame; needs no GPU. In double precision:
+ * side = 4*sqrt(box_w*box_h), stride = side*(100 - overlap_pct)/100. Per axis of length L: one centre L/2 if
+ * L <= side; else n = ceil((L - side)/stride) + 1 centres side/2 + i*(L - side)/(n - 1): the first and last windows
+ * are flush with the frame edges and the spacing never exceeds stride. Boxes come row by row (y outer), each
+ * (cx - box_w/2, cy - box_h/2, box_w, box_h) rounded to float. An update still returns the exact box with its window
+ * centre off the target by a quarter of the side, so overlap_pct = 50 covers every target position.
+ * Returns the number of windows and writes min(count, cap) of them to boxes4 (4 floats each; boxes4 may be null with
+ * cap 0). Returns 0 on bad arguments (overlap_pct outside 0..90, a frame side below 16 or above 65536, a box side that is not
+ * finite or outside 1..32768), like vt_plan_engines. */
+int vt_scan_windows(int frame_w, int frame_h, float box_w, float box_h, int overlap_pct, float* boxes4, int cap);
+
 /* ---- dma-buf ingest ------------------------------------------------------------------------
  * The reference's capture side can hand out dma-bufs (v4l2src io-mode=dmabuf, src/pipeline_ir.rs:24)
  * but then maps them on the CPU (src/pipeline.rs:95-101). vt_import_dmabuf maps a dma-buf fd into
@@ -481,7 +536,9 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * "state" (the stream's device state record as raw 32-bit words), "graph_replays" [3] (passes replayed so far
  * per crop-buffer tier: which of the captured graphs ran). After a subset pass (vt_group_*_streams) every
  * tensor but "state" and "graph_replays" is that of the stream's slot in it; a stream that was not in the pass
- * returns VT_ERR_INVALID_ARG.
+ * returns VT_ERR_INVALID_ARG. After a candidate pass (vt_group_update_*_candidates) the stream's slot is its WINNING
+ * slot. A per-pass tensor name prefixed with "slot." ("slot.head_out", ...) takes `stream` as a SLOT index of the last
+ * pass instead: the way to a losing slot's tensors.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);
