@@ -109,7 +109,7 @@ EXPORTS = [
 OPS_EXPORTS = [
     "vt_op_gemm_bf16", "vt_op_gemm_bench", "vt_op_qkv_bf16", "vt_op_attention_bf16",
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
-    "vt_op_headconv_ln_bf16",
+    "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
 ]
 
 
@@ -232,6 +232,7 @@ def ops_lib():
     L.vt_last_error.restype = c_char_p
     u16p, fp = POINTER(c_uint16), POINTER(c_float)
     L.vt_op_gemm_bf16.argtypes = [c_int, u16p, u16p, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_float]
+    L.vt_op_gemm_bf16_lo.argtypes = L.vt_op_gemm_bf16.argtypes + [c_int]
     L.vt_op_gemm_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int, fp]
     L.vt_op_qkv_bf16.argtypes = [c_int, u16p, u16p, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, fp]
     L.vt_op_attention_bf16.argtypes = [c_int, u16p, u16p, u16p, fp, c_int, c_int, c_int, c_int]
@@ -905,6 +906,15 @@ class Group:
         _check(lib().vt_group_read_tensor(self._h, stream, name.encode(), _f32(out), n))
         return out
 
+    def residual_range(self, stream: int = 0) -> list:
+        """vt_group_read_tensor "xrange": what the stream's stored residual pair holds, one dict per stage (with taps:
+        tokens0, layer0 .. of the last pass; without: the final residual) - lo_shift, max_abs, n_sat (elements on the
+        clamp, |lo8| == 127) and n_ge_pow2[k - 1] = n(|x| >= 2^k), k = 1..9. weights.recommend_lo_shift takes the list."""
+        rows = self.read_tensor("xrange", stream).reshape(-1, weights.XRANGE_COLS)
+        names = ["tokens0"] + [f"layer{i}" for i in range(len(rows) - 1)] if len(rows) > 1 else ["x"]
+        return [dict(stage=nm, lo_shift=int(r[0]), max_abs=float(r[1]), n_sat=int(r[2]),
+                     n_ge_pow2=[int(v) for v in r[3:]]) for nm, r in zip(names, rows)]
+
     def read_state(self, stream: int = 0) -> dict:
         raw = self.read_tensor("state", stream)
         i = raw.view(np.int32)
@@ -959,9 +969,9 @@ def overlay_rgb8(rgb: np.ndarray, cmds, device: int = 0) -> np.ndarray:
 # ---- operator-level entry points (numerics tests) -------------------------------------------
 
 def op_gemm_bf16(a_bits, w_bits, bias, c_init=None, epilogue=0, device=0, cfg=-1, rowstat=None,
-                 colsum=None, want_rowstat=False, eps=1e-6):
-    """vt_op_gemm_bf16. epilogue 0 / 1 / 4: the X-epilogues (x comes back as the value of the 3-byte pair the
-    engine stores; want_rowstat: also the finalized (rstd, -mean * rstd) per row -> (x, rowstat));
+                 colsum=None, want_rowstat=False, eps=1e-6, lo_shift=12):
+    """vt_op_gemm_bf16[_lo]. epilogue 0 / 1 / 4: the X-epilogues (x comes back as the value of the 3-byte pair the
+    engine stores, its quantum 2^-lo_shift; want_rowstat: also the finalized (rstd, -mean * rstd) per row -> (x, rowstat));
     2 / 3: GELU / ReLU to bf16, with a folded LayerNorm if rowstat [M,2] and colsum [N] are given"""
     a_bits = np.ascontiguousarray(a_bits, np.uint16)
     w_bits = np.ascontiguousarray(w_bits, np.uint16)
@@ -973,10 +983,10 @@ def op_gemm_bf16(a_bits, w_bits, bias, c_init=None, epilogue=0, device=0, cfg=-1
     rs = None if rowstat is None else np.ascontiguousarray(rowstat, np.float32)
     cs = None if colsum is None else np.ascontiguousarray(colsum, np.float32)
     ro = np.zeros((M, 2), np.float32) if want_rowstat else None
-    _check_op(ops_lib().vt_op_gemm_bf16(device, _u16(a_bits), _u16(w_bits),
+    _check_op(ops_lib().vt_op_gemm_bf16_lo(device, _u16(a_bits), _u16(w_bits),
                                  _f32(b) if b is not None else None, _f32(c), M, N, K, epilogue, cfg,
                                  _f32(rs) if rs is not None else None, _f32(cs) if cs is not None else None,
-                                 _f32(ro) if ro is not None else None, eps))
+                                 _f32(ro) if ro is not None else None, eps, int(lo_shift)))
     return (c, ro) if want_rowstat else c
 
 
@@ -1057,8 +1067,8 @@ def op_headconv(t_bf16_bits, w_bf16_bits, bias, B, grid, conv3x3=True, R=0, ncb=
 
 
 def op_headconv_ln(xh_bits, xl_lo8, gamma, beta, w_bf16_bits, bias, B, grid, ntok, off, fused=True, eps=1e-6, R=0, ncb=0,
-                   device=0):
-    """vt_op_headconv_ln_bf16: relu(LayerNorm(xh + lo8 * 2^-12)[search rows] . w^T + bias) -> [B*grid*grid][N] float32 (the
+                   device=0, lo_shift=12):
+    """vt_op_headconv_ln_bf16[_lo]: relu(LayerNorm(xh + lo8 * 2^-lo_shift)[search rows] . w^T + bias) -> [B*grid*grid][N] float32 (the
     residual pair of specification v3: bf16 bits + signed bytes); fused: one launch (the band kernel normalises its rows
     itself), else the LayerNorm kernel followed by the band kernel"""
     xh = np.ascontiguousarray(xh_bits, np.uint16)
@@ -1068,11 +1078,11 @@ def op_headconv_ln(xh_bits, xl_lo8, gamma, beta, w_bf16_bits, bias, B, grid, nto
     assert xh.shape == xl.shape == (B * ntok, D) and w.shape[1] == D
     out = np.empty((B * grid * grid, N), np.float32)
     u16 = POINTER(ctypes.c_uint16)
-    _check_op(ops_lib().vt_op_headconv_ln_bf16(device, xh.ctypes.data_as(u16), xl.ctypes.data_as(POINTER(ctypes.c_int8)),
+    _check_op(ops_lib().vt_op_headconv_ln_bf16_lo(device, xh.ctypes.data_as(u16), xl.ctypes.data_as(POINTER(ctypes.c_int8)),
                                         _f32(np.ascontiguousarray(gamma, np.float32)),
                                         _f32(np.ascontiguousarray(beta, np.float32)), c_float(eps), ntok, off,
                                         w.ctypes.data_as(u16), _f32(np.ascontiguousarray(bias, np.float32)), _f32(out),
-                                        B, grid, D, N, 1 if fused else 0, R, ncb, 0, None))
+                                        B, grid, D, N, 1 if fused else 0, R, ncb, 0, None, int(lo_shift)))
     return out
 
 

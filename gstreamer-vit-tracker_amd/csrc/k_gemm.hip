@@ -524,7 +524,7 @@ __global__ __launch_bounds__(WVM * WVN * 64 * (LW ? 2 : 1), 2) void gemm_bf16_ke
                     hi = *reinterpret_cast<const u32x4_t*>(p.Xh + (size_t)mc * p.ldx + n8);
                     lo = *reinterpret_cast<const u32x2_t*>(p.Xl + (size_t)mc * p.ldx + n8);
                 }
-                x_join8(hi, lo, add);
+                x_join8(hi, lo, p.lq.q, add);
             }
             float x[8];
 #pragma unroll
@@ -536,7 +536,7 @@ __global__ __launch_bounds__(WVM * WVN * 64 * (LW ? 2 : 1), 2) void gemm_bf16_ke
             x_chunk_stats(x, csum, cm2);
             u32x4_t hi;
             u32x2_t lo;
-            x_split8(x, hi, lo);
+            x_split8(x, p.lq, hi, lo);
             if (m < p.M) {
                 *reinterpret_cast<u32x4_t*>(p.Xh + (size_t)m * p.ldx + n8) = hi;
                 *reinterpret_cast<u32x2_t*>(p.Xl + (size_t)m * p.ldx + n8) = lo;

@@ -341,7 +341,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 const f32x4_t f1 = *reinterpret_cast<const f32x4_t*>(smem + lr * 1024 + (((2 * c8 + 1) ^ (lr & 7)) << 4));
                 float add[8], x[8];
                 if constexpr (EPI == EPI_RESID) {
-                    x_join8(ad[it][0], u32x2_t{ad[it][1][0], ad[it][1][1]}, add);
+                    x_join8(ad[it][0], u32x2_t{ad[it][1][0], ad[it][1][1]}, p.lq.q, add);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { add[e] = __uint_as_float(ad[it][0][e]); add[4 + e] = __uint_as_float(ad[it][1][e]); }
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 x_chunk_stats(x, csum, cm2);
                 u32x4_t hi;
                 u32x2_t lo;
-                x_split8(x, hi, lo);
+                x_split8(x, p.lq, hi, lo);
                 // chunk partials: two chunks (this quad's and the next one's) per 16-B WRITE-THROUGH (sc1) store -
                 // the row panel's last workgroup may read them in this launch (finalize below); as 8-B sc1 stores
                 // they were 518 k single fabric writes per launch (an 8-B write-through store costs 2.7x a 16-B

@@ -371,7 +371,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
                 const int r = it * 16 + hwv;
                 f32x4_t v[LNC][2];
 #pragma unroll
-                for (int j = 0; j < LNC; ++j) ln_unpack_split(rh[it % 3][j], rl[it % 3][j], v[j]);
+                for (int j = 0; j < LNC; ++j) ln_unpack_split(rh[it % 3][j], rl[it % 3][j], p.lo_q, v[j]);
                 uint4 o[LNC];
                 ln_row<LNC>(v, k, D, p.ln_eps, o);
                 if (r < cells) {

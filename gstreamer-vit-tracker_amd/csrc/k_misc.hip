@@ -1,8 +1,9 @@
 // k_misc.hip — LayerNorm, row statistics and the LayerNorm fold for gfx950 (the head lives in k_head.hip).
 #include "vt_common.hpp"
+#include <algorithm>
 
 // ---- LayerNorm: one wave per row, row kept in registers, two-pass variance -----------------------
-// Residual stream in (float32, or SPLIT: the 3-byte pair of the engine, x = xh + xl * 2^-12: vt_common.hpp), bf16 GEMM
+// Residual stream in (float32, or SPLIT: the 3-byte pair of the engine, x = xh + xl * lo_q: vt_common.hpp), bf16 GEMM
 // operand out. In the engine only the FINAL LayerNorm (search tokens, before the head) runs as a kernel:
 // the two LayerNorms of every block are folded into the GEMMs that consume them (vt_common.hpp).
 // NCH = D / 128 float2 chunks per lane.
@@ -14,7 +15,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
                                                         const float* __restrict__ beta,
                                                         bf16_t* __restrict__ y, int rows, int D,
                                                         int group, int in_stride, int in_off,
-                                                        float eps) {
+                                                        float eps, float lo_q) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
@@ -27,8 +28,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const uint32_t h = hr[lane + 64 * j], l = lr[lane + 64 * j];
-            v[j].x = __builtin_fmaf(lo8_f32(l, 0), VT_LO_Q, __uint_as_float(h << 16));
-            v[j].y = __builtin_fmaf(lo8_f32(l, 1), VT_LO_Q, __uint_as_float(h & 0xffff0000u));
+            v[j].x = __builtin_fmaf(lo8_f32(l, 0), lo_q, __uint_as_float(h << 16));
+            v[j].y = __builtin_fmaf(lo8_f32(l, 1), lo_q, __uint_as_float(h & 0xffff0000u));
         }
     } else {
         const float2* xr = reinterpret_cast<const float2*>(x + in_row * D);
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void layernorm_wide_kernel(const float* __rest
                                                              const float* __restrict__ beta,
                                                              bf16_t* __restrict__ y, int rows, int D,
                                                              int group, int in_stride, int in_off,
-                                                             float eps) {
+                                                             float eps, float lo_q) {
     const int l32 = threadIdx.x & 31;
     int r = blockIdx.x * 8 + (threadIdx.x >> 5);
     const bool live = r < rows;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void layernorm_wide_kernel(const float* __rest
         const u32x4_t* hr = reinterpret_cast<const u32x4_t*>(xh + in_row * D);
         const u32x2_t* lr = reinterpret_cast<const u32x2_t*>(xl + in_row * D);
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) ln_unpack_split(hr[l32 + 32 * j], lr[l32 + 32 * j], v[j]);
+        for (int j = 0; j < NCH; ++j) ln_unpack_split(hr[l32 + 32 * j], lr[l32 + 32 * j], lo_q, v[j]);
     } else {
         const f32x4_t* xr = reinterpret_cast<const f32x4_t*>(x + in_row * D);
 #pragma unroll
@@ -112,14 +113,14 @@ __global__ __launch_bounds__(256) void layernorm_wide_kernel(const float* __rest
 template <bool SPLIT>
 static hipError_t launch_layernorm_any(const float* x, const bf16_t* xh, const uint8_t* xl, const float* gamma,
                                        const float* beta, bf16_t* y, int rows, int D, int group, int in_stride,
-                                       int in_off, float eps, hipStream_t st) {
+                                       int in_off, float eps, float lo_q, hipStream_t st) {
     if (rows <= 0 || D % 128 != 0) return hipErrorInvalidValue;
     if (D % 256 == 0 && D / 256 <= 4) {
         dim3 gridw((rows + 7) / 8), block(256);
 #define LNW_CASE(n)                                                                                      \
     case n:                                                                                              \
         vt_launch((layernorm_wide_kernel<n, SPLIT>), gridw, block, 0, st, x, xh, xl, gamma, beta, y, \
-                           rows, D, group, in_stride, in_off, eps);                                      \
+                           rows, D, group, in_stride, in_off, eps, lo_q);                                \
         break;
         switch (D / 256) { LNW_CASE(1) LNW_CASE(2) LNW_CASE(3) LNW_CASE(4) }
 #undef LNW_CASE
@@ -129,7 +130,7 @@ static hipError_t launch_layernorm_any(const float* x, const bf16_t* xh, const u
 #define LN_CASE(n)                                                                                       \
     case n:                                                                                              \
         vt_launch((layernorm_kernel<n, SPLIT>), grid, block, 0, st, x, xh, xl, gamma, beta, y, rows, \
-                           D, group, in_stride, in_off, eps);                                            \
+                           D, group, in_stride, in_off, eps, lo_q);                                      \
         break;
     switch (D / 128) {
         LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(6) LN_CASE(8) LN_CASE(10) LN_CASE(12)
@@ -142,13 +143,73 @@ static hipError_t launch_layernorm_any(const float* x, const bf16_t* xh, const u
 hipError_t launch_layernorm(const float* x, const float* gamma, const float* beta, bf16_t* y,
                             int rows, int D, int group, int in_stride, int in_off, float eps,
                             hipStream_t st) {
-    return launch_layernorm_any<false>(x, nullptr, nullptr, gamma, beta, y, rows, D, group, in_stride, in_off, eps, st);
+    return launch_layernorm_any<false>(x, nullptr, nullptr, gamma, beta, y, rows, D, group, in_stride, in_off, eps, 0.0f, st);
 }
 
 hipError_t launch_layernorm_split(const bf16_t* xh, const uint8_t* xl, const float* gamma, const float* beta,
                                   bf16_t* y, int rows, int D, int group, int in_stride, int in_off,
-                                  float eps, hipStream_t st) {
-    return launch_layernorm_any<true>(nullptr, xh, xl, gamma, beta, y, rows, D, group, in_stride, in_off, eps, st);
+                                  float eps, float lo_q, hipStream_t st) {
+    return launch_layernorm_any<true>(nullptr, xh, xl, gamma, beta, y, rows, D, group, in_stride, in_off, eps, lo_q, st);
+}
+
+// ---- range report of a stored residual pair (vt_group_read_tensor "xrange") --------------------------
+// What a host needs to choose a model's lo_shift and to be told when a stream leaves the exact range: per stage the
+// largest |x| of the STORED value x = hi + lo8 * q, how many elements sit on the clamp (|lo8| == 127) and how many reach
+// 2^k, k = 1..9. Launched by the read, never by a pass. blockIdx.y is the stage (stage_stride bytes apart in both
+// planes: the tap copies; 1 stage: the live pair). A lane takes 8 consecutive elements per step (16 B of hi, 8 B of
+// lo8), counts in integers and keeps the maximum as the bit pattern of a non-negative float (unsigned order = float
+// order); each half-wave combines its lanes (the sums by half_wave_sum on counts that are exact in float32: a half-wave
+// sees < 2^24 elements; FULL EXEC: the loop has ended for every lane) and one lane of it adds into the stage's words
+// with ordinary vector atomics. Integer adds and a max: the result does not depend on the order of arrival.
+__global__ __launch_bounds__(256) void xrange_kernel(const bf16_t* __restrict__ xh, const uint8_t* __restrict__ xl,
+                                                     unsigned* __restrict__ out, long long nchunk, float lo_q,
+                                                     long long stage_stride) {
+    const u32x4_t* hp = reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(xh) + blockIdx.y * stage_stride);
+    const u32x2_t* lp = reinterpret_cast<const u32x2_t*>(xl + blockIdx.y * stage_stride);
+    unsigned mx = 0, n127 = 0, nk[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += step) {
+        const u32x4_t h = hp[c];
+        const u32x2_t l = lp[c];
+        float x[8];
+        x_join8(h, l, lo_q, x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int b = (int)(l[e >> 2] << (24 - 8 * (e & 3))) >> 24;
+            n127 += (b == 127 || b == -127) ? 1u : 0u;
+            const unsigned u = __float_as_uint(x[e]) & 0x7fffffffu;
+            mx = u > mx ? u : mx;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) nk[k] += u >= ((unsigned)(128 + k) << 23) ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)mx, o); mx = t > mx ? t : mx; }
+    const unsigned s127 = (unsigned)half_wave_sum((float)n127);
+    unsigned sk[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sk[k] = (unsigned)half_wave_sum((float)nk[k]);
+    if ((threadIdx.x & 31) == 0) {
+        unsigned* o = out + (size_t)blockIdx.y * VT_XRANGE_WORDS;
+        if (mx) atomicMax(o, mx);
+        if (s127) atomicAdd(o + 1, s127);
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+            if (sk[k]) atomicAdd(o + 2 + k, sk[k]);
+    }
+}
+
+hipError_t launch_xrange(const bf16_t* xh, const uint8_t* xl, unsigned* out, int rows, int D, float lo_q, int stages,
+                         size_t stage_stride, hipStream_t st) {
+    if (rows <= 0 || D <= 0 || D % 8 || stages < 1 || (stage_stride & 15)) return hipErrorInvalidValue;
+    const long long nchunk = (long long)rows * D / 8;
+    // a half-wave's counts stay exact in float32: at most 2^24 / 32 steps of 8 elements per lane - far above any engine
+    // a stage of ntok x D elements is at most ~120 blocks of one step: the cap only bounds the atomics of a larger caller
+    const long long blocks = std::min<long long>((nchunk + 255) / 256, 128);
+    if (nchunk / (blocks * 256) + 1 > (1 << 16)) return hipErrorInvalidValue;
+    vt_launch(xrange_kernel, dim3((unsigned)blocks, (unsigned)stages), dim3(256), 0, st, xh, xl, out, nchunk, lo_q,
+              (long long)stage_stride);
+    return hipGetLastError();
 }
 
 // ---- row statistics of the residual stream from the X-epilogues' chunk partials --------------------

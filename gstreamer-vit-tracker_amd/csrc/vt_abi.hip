@@ -347,6 +347,7 @@ int vt_group_enable_taps(vt_group* g, int enable) try {
     HIPCHK(hipStreamSynchronize(e->stream));
     if (enable && !e->d_taps)      // per slot: the hi and the lo half of the residual stream
         HIPCHK(dalloc0(&e->d_taps, (size_t)(e->d.L + 1) * e->tap_slot_bytes(), e->stream));
+    if (!e->taps || !enable) e->taps_filled = false;    // the copies belong to the passes of THIS enabling
     e->taps = enable != 0;
     return VT_OK;
 } VT_NOTHROW_INT
@@ -428,8 +429,8 @@ static int64_t copy_out_f32(const float* dsrc, int64_t count, float* out, int64_
     return count;
 }
 // the residual stream in float32: the value the 3-byte pair stands for
-// (the 3-byte pair of specification v3: hi bf16 + lo8 * 2^-12)
-static int64_t copy_out_pair(const bf16_t* dhi, const uint8_t* dlo, int64_t count, float* out, int64_t cap) {
+// (the 3-byte pair of specification v3: hi bf16 + lo8 * q, q = 2^-s of the engine)
+static int64_t copy_out_pair(const bf16_t* dhi, const uint8_t* dlo, int64_t count, float q, float* out, int64_t cap) {
     if (!out) return count;
     if (cap < count) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity %lld < %lld", (long long)cap, (long long)count);
     std::vector<bf16_t> hi((size_t)count);
@@ -441,7 +442,7 @@ static int64_t copy_out_pair(const bf16_t* dhi, const uint8_t* dlo, int64_t coun
         const uint32_t uh = ((uint32_t)hi[i]) << 16;
         float fh;
         memcpy(&fh, &uh, 4);
-        out[i] = fh + (float)lo[i] * VT_LO_Q;
+        out[i] = fh + (float)lo[i] * q;
     }
     return count;
 }
@@ -487,8 +488,37 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
     if (n == "attn") return copy_out_bf16(e->d_attn + b * d.ntok * d.D, (int64_t)d.ntok * d.D, out, capacity);
     if (n == "head_t3") return copy_out_bf16(e->d_tb + b * d.ns * d.C, (int64_t)d.ns * d.C, out, capacity);
     if (n == "head_out") return copy_out_f32(e->d_headout + b * d.ns * 8, (int64_t)d.ns * 8, out, capacity);
-    if (n == "x") return copy_out_pair(e->d_xh + b * d.ntok * d.D, e->d_xl + b * d.ntok * d.D, (int64_t)d.ntok * d.D, out, capacity);
+    if (n == "x") return copy_out_pair(e->d_xh + b * d.ntok * d.D, e->d_xl + b * d.ntok * d.D, (int64_t)d.ntok * d.D, e->lq.q, out, capacity);
     if (n == "rowstat") return copy_out_f32((const float*)(e->d_rstat + b * d.ntok), (int64_t)d.ntok * 2, out, capacity);
+    if (n == "xrange") {
+        // range report of the stream's stored residual pair: [stages][12] = lo_shift, max |x|, n(|lo8| == 127),
+        // n(|x| >= 2^k) k = 1..9. With taps: tokens0, layer0 .. layer{L-1} from the tap copies of the last pass;
+        // without: one row, the final pair ("x"). One launch of k_misc.hip's reduction, here - never in a pass.
+        const bool tapped = e->taps && e->d_taps;
+        if (tapped && !e->taps_filled)      // nothing but the buffer's initial zeros (or an older enabling's copies) to report
+            return set_err(VT_ERR_INVALID_ARG, "read_tensor: 'xrange' with taps enabled needs a pass since vt_group_enable_taps");
+        const int stages = tapped ? d.L + 1 : 1;
+        const int64_t count = (int64_t)stages * 12;
+        if (!out) return count;
+        if (capacity < count) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity %lld < %lld", (long long)capacity, (long long)count);
+        if (!e->d_xrange) HIPCHK(hipMalloc((void**)&e->d_xrange, sizeof(unsigned) * VT_XRANGE_WORDS * (size_t)(d.L + 1)));
+        HIPCHK(hipMemsetAsync(e->d_xrange, 0, sizeof(unsigned) * VT_XRANGE_WORDS * (size_t)stages, e->stream));
+        const size_t M = (size_t)e->pass_n * d.ntok, off = b * d.ntok * d.D;
+        const bf16_t* hi = tapped ? reinterpret_cast<const bf16_t*>(e->d_taps) + off : e->d_xh + off;
+        const uint8_t* lo = tapped ? e->d_taps + sizeof(bf16_t) * M * d.D + off : e->d_xl + off;
+        HIPCHK(launch_xrange(hi, lo, e->d_xrange, d.ntok, d.D, e->lq.q, stages, tapped ? e->tap_slot_bytes() : 0, e->stream));
+        std::vector<unsigned> w((size_t)stages * VT_XRANGE_WORDS);
+        HIPCHK(hipMemcpyAsync(w.data(), e->d_xrange, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (int s = 0; s < stages; ++s) {
+            const unsigned* r = &w[(size_t)s * VT_XRANGE_WORDS];
+            float* o = out + (size_t)s * 12;
+            o[0] = (float)e->lq.shift;
+            memcpy(o + 1, r, 4);                        // max |x|: the bit pattern of a non-negative float
+            for (int k = 1; k < VT_XRANGE_WORDS; ++k) o[1 + k] = (float)r[k];
+        }
+        return count;
+    }
     if (n == "graph_replays") {        // passes replayed so far per crop tier (diagnostics: which captured pass ran)
         if (!out) return Engine::TIERS;
         if (capacity < Engine::TIERS) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
@@ -508,7 +538,7 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         const uint8_t* base = e->d_taps + (size_t)slot * e->tap_slot_bytes();
         const bf16_t* hi = reinterpret_cast<const bf16_t*>(base) + b * d.ntok * d.D;
         const uint8_t* lo = base + sizeof(bf16_t) * M * d.D + b * d.ntok * d.D;
-        return copy_out_pair(hi, lo, (int64_t)d.ntok * d.D, out, capacity);
+        return copy_out_pair(hi, lo, (int64_t)d.ntok * d.D, e->lq.q, out, capacity);
     }
     return set_err(VT_ERR_INVALID_ARG, "unknown tensor '%s'", name);
 } VT_NOTHROW_INT

@@ -102,20 +102,43 @@ struct ModelDims {
 // (the attention kernels use v_exp_f32 = 2^x directly); float(log2 e) / 8 is exact in float32
 #define ATT_Q_SCALE (0.125f * 1.4426950408889634f)
 
-// NUMERICAL SPECIFICATION v3 (round 6). The residual stream x is stored as a 3-BYTE pair: Xh = bf16(x) [M][ldx] and
-// Xl = lo8 [M][ldx] bytes, lo8 = clamp(rint((x - Xh) * 2^12), -127, 127) as a signed integer: x = Xh + lo8 * 2^-12.
+// NUMERICAL SPECIFICATION v3 (round 6; the per-model shift: round 7). The residual stream x is stored as a 3-BYTE pair:
+// Xh = bf16(x) [M][ldx] and Xl = lo8 [M][ldx] bytes, lo8 = clamp(rint((x - Xh) * 2^s), -127, 127) as a signed integer:
+// x = Xh + lo8 * 2^-s. The shift s is a property of the MODEL: header int 12 of the weight blob (0 = 12, else 6..14),
+// fixed for the life of an engine and carried to every kernel that reads or writes the pair as LoQuant (below).
 // Until round 5 the low half was a second bf16 (4 bytes per element, 17 significant bits); the byte plane moves a
 // quarter less through the X-epilogues' read-modify-write and the final LayerNorm, the phases of the pass that are
 // bound by memory requests (profiles/r06_lo8_residual.txt: whole frame + 2.0 %). x - Xh is exact (Xh is x rounded to 8
-// significant bits), the scaling is a power of two, rint is round-to-nearest-even, Xh + lo8 * 2^-12 is exact in
+// significant bits), the scaling is a power of two, rint is round-to-nearest-even, Xh + lo8 * 2^-s is exact in
 // float32: oracle (oracle/vit_ref.py split_residual) and kernels can differ only through the x they start from.
-// |x - Xh| <= ulp(Xh) / 2: at most 64 quanta for |x| < 8 (this model: |x| < 3.5) - the byte holds it with room to spare
-// and the stored value is within half a quantum of x. For 8 <= |x| < 16 the remainder reaches 128 quanta next to a bf16
-// tie, where the clamp costs at most one quantum; beyond 16 it leaves part of the low half behind - the value degrades
-// towards plain bf16, it never wraps.
-#define VT_LO_SHIFT 12
-#define VT_LO_Q (1.0f / 4096.0f)
-#define VT_LO_MAX (127.0f / 4096.0f)
+// |x - Xh| <= ulp(Xh) / 2: at most 64 quanta for |x| < 2^(15 - s) - the EXACT RANGE: the byte holds the remainder with
+// room to spare and the stored value is within half a quantum of x. For 2^(15 - s) <= |x| < 2^(16 - s) the remainder
+// reaches 128 quanta next to a bf16 tie, where the clamp costs at most one quantum (the ONE-QUANTUM BAND); beyond
+// 2^(16 - s) the clamp leaves part of the low half behind - the value SATURATES towards plain bf16, it never wraps.
+// The trade: a coarser quantum protects large values at the price of small ones. The pair adds nothing to bf16 once
+// the quantum exceeds half an ulp of Xh: at s = 8 an element with |x| < 1 is stored as plain bf16, at the default
+// s = 12 that only happens below 2^-4. s = 12 suits the seeded models (|x| < 3.5, exact range 8); a checkpoint with
+// residual outlier channels wants the largest s whose exact range still covers them ("xrange" of
+// vt_group_read_tensor reports what a model's streams hold; weights.recommend_lo_shift picks s from it).
+#define VT_LO_SHIFT_DEFAULT 12
+#define VT_LO_SHIFT_MIN 6
+#define VT_LO_SHIFT_MAX 14
+// what the kernels need of s, derived once on the host (all three exact powers of two times a small integer):
+// wave-uniform kernel arguments, so they sit in SGPRs
+struct LoQuant {
+    float q = 1.0f / 4096.0f;          // 2^-s: the quantum
+    float lo_max = 127.0f / 4096.0f;   // 127 q: the clamp of the remainder
+    float magic = 3072.0f;             // 1.5 * 2^(23 - s): the float whose ulp is q (x_split8)
+    int shift = VT_LO_SHIFT_DEFAULT;
+};
+inline LoQuant lo_quant(int s) {
+    LoQuant l;
+    l.q = 1.0f / (float)(1 << s);
+    l.lo_max = 127.0f * l.q;
+    l.magic = 1.5f * (float)(1 << (23 - s));
+    l.shift = s;
+    return l;
+}
 // (comment of the v2 form, for the history of the format:)
 // The residual stream x is stored as a PAIR of bf16 matrices: Xh = bf16(x), Xl = bf16(x - Xh) (17
 // significant bits; Xh alone is the A operand of the GEMM that consumes the following LayerNorm). The
@@ -166,6 +189,7 @@ struct GemmArgs {
     // kernel of k_gemm.hip: which tiles an XCD's contiguous run of workgroups covers - 0: the launcher decides (bf16-output
     // epilogues with M < N: column tiles), 1: row panels x all columns, 2: column tiles x all rows
     int tile_order;
+    LoQuant lq;                   // X-epilogues: the pair's quantum (the engine's lo_shift; default 12)
 };
 
 hipError_t launch_gemm(const GemmArgs& a, int epilogue, hipStream_t st);
@@ -195,10 +219,17 @@ int gemm_effective_config(const GemmArgs& a, int epilogue);
 hipError_t launch_layernorm(const float* x, const float* gamma, const float* beta, bf16_t* y,
                             int rows, int D, int group, int in_stride, int in_off, float eps,
                             hipStream_t st);
-// the same on the split residual stream: x = xh + xl * 2^-12 (3-byte pair)
+// the same on the split residual stream: x = xh + xl * lo_q (3-byte pair, lo_q = 2^-s)
 hipError_t launch_layernorm_split(const bf16_t* xh, const uint8_t* xl, const float* gamma, const float* beta,
                                   bf16_t* y, int rows, int D, int group, int in_stride, int in_off,
-                                  float eps, hipStream_t st);
+                                  float eps, float lo_q, hipStream_t st);
+// Range report of a stored pair (k_misc.hip, off the hot path): out[0] = max |x| as the bit pattern of a non-negative
+// float, out[1] = n(|lo8| == 127), out[1 + k] = n(|x| >= 2^k), k = 1..9, accumulated into out (zero it first) over
+// rows [0, rows) of xh / xl (contiguous rows of length D, D % 8 == 0), for `stages` copies of the pair that lie
+// stage_stride bytes apart in BOTH planes (the tap slots), into out[stage][VT_XRANGE_WORDS]
+#define VT_XRANGE_WORDS 11
+hipError_t launch_xrange(const bf16_t* xh, const uint8_t* xl, unsigned* out, int rows, int D, float lo_q, int stages,
+                         size_t stage_stride, hipStream_t st);
 // rowstat[m] = (rstd, -mean * rstd) from the chunk partials of an X-epilogue (D = 32 * nchunk columns)
 hipError_t launch_rowstat_finalize(const float2* cstat, float2* rowstat, int M, int nchunk, float eps,
                                    hipStream_t st);
@@ -298,6 +329,7 @@ struct HeadConvArgs {
     const float *ln_g, *ln_b;
     float ln_eps;
     int in_stride, in_off;
+    float lo_q = 1.0f / 4096.0f;    // the pair's quantum 2^-s (LoQuant.q)
 };
 bool headconv_supported(int grid, int C, int N, int K, bool conv3x3);
 bool headconv_ln_supported(int grid, int N, int D);
@@ -395,35 +427,38 @@ __device__ __forceinline__ void ln_load_coef(const float* gamma, const float* be
 }
 
 // ---- the 3-byte residual pair (specification v3, top of this file) -------------------------------------------------
-// decode: element k of a lane's 8 consecutive columns = bf16 half k of h (16 B) + signed byte k of l (8 B) * 2^-12
+// decode: element k of a lane's 8 consecutive columns = bf16 half k of h (16 B) + signed byte k of l (8 B) * q, q = 2^-s
 __device__ __forceinline__ float lo8_f32(uint32_t w, int byte) {
     return (float)((int)(w << (24 - 8 * byte)) >> 24);          // sign-extended byte (v_bfe_i32 / SDWA sext) -> float
 }
-__device__ __forceinline__ void x_join8(const u32x4_t& hi, const u32x2_t& lo, float (&x)[8]) {
+__device__ __forceinline__ void x_join8(const u32x4_t& hi, const u32x2_t& lo, float q, float (&x)[8]) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const uint32_t lw = lo[e >> 1];
-        x[2 * e] = __builtin_fmaf(lo8_f32(lw, (2 * e) & 3), VT_LO_Q, __uint_as_float(hi[e] << 16));
-        x[2 * e + 1] = __builtin_fmaf(lo8_f32(lw, (2 * e + 1) & 3), VT_LO_Q, __uint_as_float(hi[e] & 0xffff0000u));
+        x[2 * e] = __builtin_fmaf(lo8_f32(lw, (2 * e) & 3), q, __uint_as_float(hi[e] << 16));
+        x[2 * e + 1] = __builtin_fmaf(lo8_f32(lw, (2 * e + 1) & 3), q, __uint_as_float(hi[e] & 0xffff0000u));
     }
 }
 // encode: hi = bf16(x) (round to nearest even); d = x - hi (exact); lo8 = rint(clamp(d, +-127 q) / q) by the float add of
-// 1.5 * 2^11: the sum's ulp is q = 2^-12, the add rounds to nearest even, and the low byte of the sum's bit pattern
-// (0x45400000 + n) is the two's-complement lo8. The add is issued in its SDWA form with dst_sel:BYTE_k, which writes that
+// magic = 1.5 * 2^(23 - s): the sum's ulp is q = 2^-s, the add rounds to nearest even, and the low byte of the sum's bit
+// pattern (at s = 12: 0x45400000 + n) is the two's-complement lo8 - for every s in 6..14 alike. The clamp and the magic
+// are wave-uniform (LoQuant): v_med3_f32 takes the one SGPR as -lo_max and lo_max (a source modifier, one constant-bus
+// read), the SDWA add its magic from a register as before. The add is issued in its SDWA form with dst_sel:BYTE_k, which writes that
 // low byte straight into byte k of the destination dword - no extraction, no packing: 2 vector operations per element
 // (v_med3_f32 + v_add_f32_sdwa) where clamp + add + v_perm gathering took 2.75 (same-box A/B in profiles/r06_lo8_residual.txt:
 // + 0.5 % of the whole frame; without the clamp another + 0.2 %, not taken: a value beyond the range must saturate, not wrap).
-__device__ __forceinline__ void x_split8(const float (&x)[8], u32x4_t& hi, u32x2_t& lo) {
+__device__ __forceinline__ void x_split8(const float (&x)[8], const LoQuant& lq, u32x4_t& hi, u32x2_t& lo) {
     uint32_t h[4];
     float c[8];
+    const float lo_max = lq.lo_max;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         h[e] = pack_bf16x2(x[2 * e], x[2 * e + 1]);
-        c[2 * e] = __builtin_amdgcn_fmed3f(x[2 * e] - __uint_as_float(h[e] << 16), -VT_LO_MAX, VT_LO_MAX);
-        c[2 * e + 1] = __builtin_amdgcn_fmed3f(x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u), -VT_LO_MAX, VT_LO_MAX);
+        c[2 * e] = __builtin_amdgcn_fmed3f(x[2 * e] - __uint_as_float(h[e] << 16), -lo_max, lo_max);
+        c[2 * e + 1] = __builtin_amdgcn_fmed3f(x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u), -lo_max, lo_max);
     }
     hi = u32x4_t{h[0], h[1], h[2], h[3]};
-    const float magic = 3072.0f;            // SDWA takes no literal: a register
+    const float magic = lq.magic;           // SDWA takes no literal: a register
     uint32_t w0, w1;
 #define VT_LO8_BYTE(W, K, UNUSED, C) asm("v_add_f32_sdwa %0, %1, %2 dst_sel:BYTE_" #K " dst_unused:" #UNUSED " src0_sel:DWORD src1_sel:DWORD" : W : "v"(C), "v"(magic))
     VT_LO8_BYTE("=v"(w0), 0, UNUSED_PAD, c[0]); VT_LO8_BYTE("+v"(w0), 1, UNUSED_PRESERVE, c[1]);
@@ -434,9 +469,9 @@ __device__ __forceinline__ void x_split8(const float (&x)[8], u32x4_t& hi, u32x2
     lo = u32x2_t{w0, w1};
 }
 // the LayerNorm readers' form: 8 values of a chunk as two float4
-__device__ __forceinline__ void ln_unpack_split(const u32x4_t h, const u32x2_t l, f32x4_t (&v)[2]) {
+__device__ __forceinline__ void ln_unpack_split(const u32x4_t h, const u32x2_t l, float q, f32x4_t (&v)[2]) {
     float x[8];
-    x_join8(h, l, x);
+    x_join8(h, l, q, x);
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e >> 2][e & 3] = x[e];
 }

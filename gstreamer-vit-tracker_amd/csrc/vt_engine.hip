@@ -37,7 +37,7 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner};
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange};
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_cands) (void)hipHostFree(h_cands);
@@ -129,6 +129,11 @@ int Engine::index_blob(const uint8_t* hc, size_t bytes) {
     for (int i = 0; i < 3; ++i) { d.norm_a[i] = fl[i]; d.norm_b[i] = fl[3 + i]; }
     d.success_threshold = fl[6];
     d.ln_eps = fl[7];
+    // header int 12: the shift of the residual pair's quantum (vt_common.hpp, specification v3). 0: the default
+    if (ints[12] != 0 && (ints[12] < VT_LO_SHIFT_MIN || ints[12] > VT_LO_SHIFT_MAX))
+        return set_err(VT_ERR_FORMAT, "weight blob: lo_shift %d out of range (0 = %d, or %d..%d)", ints[12],
+                       VT_LO_SHIFT_DEFAULT, VT_LO_SHIFT_MIN, VT_LO_SHIFT_MAX);
+    lq = lo_quant(ints[12] ? ints[12] : VT_LO_SHIFT_DEFAULT);
     // every dimension is bounded BEFORE anything is derived from it (a corrupt or crafted blob must
     // not overflow the int arithmetic below or make layers.resize() throw)
     if (d.patch < 2 || d.patch > 64 || d.T < d.patch || d.S < d.patch || d.T > 4096 || d.S > 4096 ||
@@ -370,6 +375,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         }
     };
     auto gemm = [&](int epi, GemmArgs a) {
+        a.lq = lq;
         const double fl = 2.0 * a.M * a.N * a.K;
         // algorithmic bytes: operands once, output once; the 3-byte residual pair is read and written (3 + 3 B)
         const double by = 2.0 * ((double)a.M * a.K + (double)a.N * a.K) +
@@ -498,7 +504,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         if (ln_fused) {
             h.in = nullptr;
             h.xh = d_xh; h.xl = d_xl; h.ln_g = (const float*)find("norm_g")->ptr; h.ln_b = (const float*)find("norm_b")->ptr;
-            h.ln_eps = d.ln_eps; h.in_stride = d.ntok; h.in_off = d.nt;
+            h.ln_eps = d.ln_eps; h.in_stride = d.ntok; h.in_off = d.nt; h.lo_q = lq.q;
         }
         L(prof ? (ln_fused ? "head_ln_conv1x1" : "head_conv1x1") : "", 2.0 * Ms * d.C * D,
           2.0 * ((double)Ms * D * (ln_fused ? 2 : 1) + (double)d.C * D + (double)Ms * d.C),
@@ -547,7 +553,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
 
 hipError_t Engine::final_layernorm(int n) {
     return launch_layernorm_split(d_xh, d_xl, (const float*)find("norm_g")->ptr, (const float*)find("norm_b")->ptr, d_feat,
-                                  (int)((size_t)n * d.ns), d.D, d.ns, d.ntok, d.nt, d.ln_eps, stream);
+                                  (int)((size_t)n * d.ns), d.D, d.ns, d.ntok, d.nt, d.ln_eps, lq.q, stream);
 }
 
 int Engine::capture_graph(int tier, bool any_layout) {
@@ -764,6 +770,7 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
         pass_streams.assign(streams, streams + n);
     }
     pass_n = n;
+    if (taps) taps_filled = true;
     feat_in_head = head_ln_fused();
     ps->tier = pick_crop_tier(full ? nullptr : streams, n);     // a subset pass: from the boxes of its own streams
     return VT_OK;
@@ -886,6 +893,7 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
     pass_winner.clear();
     cand_pending = true;
     pass_n = n;
+    if (taps) taps_filled = true;
     feat_in_head = head_ln_fused();
     ps.tier = pick_crop_tier(cands, n);
     return run_pass(nullptr, ps);

@@ -151,10 +151,13 @@ struct Engine {
     bf16_t *d_patches = nullptr, *d_qk = nullptr, *d_vt = nullptr,
            *d_attn = nullptr, *d_mlp = nullptr, *d_feat = nullptr, *d_ta = nullptr,
            *d_tb = nullptr, *d_zeros = nullptr;     // d_zeros: 256 B of zeros (out-of-map taps of the 3x3 convs)
-    // residual stream as the 3-byte pair (x = xh + xl * 2^-12), its chunk partial statistics and the row terms of the
+    // residual stream as the 3-byte pair (x = xh + xl * 2^-s, s = the blob's lo_shift: lq), its chunk partial statistics and the row terms of the
     // folded LayerNorm (vt_common.hpp); folded weights of all layers
     bf16_t *d_xh = nullptr, *d_foldw = nullptr;
     uint8_t* d_xl = nullptr;                      // the low half of the pair: one signed byte per element (spec v3, vt_common.hpp)
+    LoQuant lq;                                   // the pair's quantum, from header int 12 of the blob (index_blob); baked into the captured passes
+    bool taps_filled = false;                     // a pass has written the tap copies since taps were last enabled
+    unsigned* d_xrange = nullptr;                 // [L + 1][VT_XRANGE_WORDS] of the range report (vt_group_read_tensor "xrange"), allocated by the first read
     uint8_t* d_taps = nullptr;                    // [slot][hi: M*D bf16 | lo8: M*D bytes]
     size_t tap_slot_bytes() const { return (size_t)B * d.ntok * d.D * 3; }
     unsigned* d_band_cnt = nullptr;               // per stream: bands of the last head layer that have arrived (k_head.hip)

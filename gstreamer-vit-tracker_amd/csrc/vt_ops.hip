@@ -21,13 +21,14 @@ static inline float host_f32(bf16_t b) {
 }
 
 // epilogue: 0 x = acc + bias, 1 x = (acc + bias) + c_inout, 4 x = (acc + bias) + pos (pos = c_inout, one
-// row per output row) - the X-epilogues: c_inout goes in and comes back through the 3-byte pair (hi + lo8 * 2^-12: bf16 and
-// an absolute quantum of 2^-12), rowstat_out (if given) receives the finalized row terms (rstd, -mean * rstd) of x;
+// row per output row) - the X-epilogues: c_inout goes in and comes back through the 3-byte pair (hi + lo8 * 2^-s: bf16 and
+// an absolute quantum of 2^-s, s = lo_shift), rowstat_out (if given) receives the finalized row terms (rstd, -mean * rstd) of x;
 // 2 gelu, 3 relu -> bf16, with an optional folded LayerNorm (rowstat_in [M][2], colsum [N]).
-int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias, float* c_inout,
-                    int M, int N, int K, int epilogue, int cfg, const float* rowstat_in, const float* colsum,
-                    float* rowstat_out, float eps) try {
+int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, const float* bias, float* c_inout,
+                       int M, int N, int K, int epilogue, int cfg, const float* rowstat_in, const float* colsum,
+                       float* rowstat_out, float eps, int lo_shift) try {
     if (!a || !w || !c_inout || M <= 0 || N <= 0 || K <= 0) return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "gemm: lo_shift %d out of range", lo_shift);
     if (N % 64 || K % 64) return set_err(VT_ERR_INVALID_ARG, "gemm: N and K must be multiples of 64");
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
@@ -43,6 +44,7 @@ int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const f
     GemmArgs g{};
     g.A = (const bf16_t*)da.p; g.lda = K; g.W = (const bf16_t*)dw.p; g.ldw = K; g.bias = (const float*)db.p;
     g.M = M; g.N = N; g.K = K; g.Xh = (bf16_t*)dxh.p; g.Xl = (uint8_t*)dxl.p; g.ldx = N; g.Cb = (bf16_t*)dcb.p; g.ldcb = N;
+    g.lq = lo_quant(lo_shift);
     int epi;
     switch (epilogue) {
         case 0: epi = EPI_F32; break;
@@ -53,14 +55,14 @@ int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const f
         default: return set_err(VT_ERR_INVALID_ARG, "gemm: unknown epilogue %d", epilogue);
     }
     const bool x_epi = epi == EPI_F32 || epi == EPI_RESID || epi == EPI_F32_POS;
-    // the 3-byte pair of specification v3 (vt_common.hpp): hi = bf16(x), lo8 = clamp(rint((x - hi) * 2^12), -127, 127)
+    // the 3-byte pair of specification v3 (vt_common.hpp): hi = bf16(x), lo8 = clamp(rint((x - hi) * 2^s), -127, 127)
     std::vector<bf16_t> hi;
     std::vector<int8_t> lo;
     if (epi == EPI_RESID) {
         hi.resize(MN); lo.resize(MN);
         for (size_t i = 0; i < MN; ++i) {
             hi[i] = host_bf16(c_inout[i]);
-            const float q = nearbyintf((c_inout[i] - host_f32(hi[i])) * 4096.0f);
+            const float q = nearbyintf((c_inout[i] - host_f32(hi[i])) * (float)(1 << lo_shift));
             lo[i] = (int8_t)(q < -127.0f ? -127.0f : q > 127.0f ? 127.0f : q);
         }
         HIPCHK(hipMemcpy(dxh.p, hi.data(), MN * 2, hipMemcpyHostToDevice));
@@ -108,7 +110,7 @@ int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const f
         hi.resize(MN); lo.resize(MN);
         HIPCHK(hipMemcpy(hi.data(), dxh.p, MN * 2, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(lo.data(), dxl.p, MN, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < MN; ++i) c_inout[i] = host_f32(hi[i]) + (float)lo[i] * VT_LO_Q;
+        for (size_t i = 0; i < MN; ++i) c_inout[i] = host_f32(hi[i]) + (float)lo[i] * g.lq.q;
         if (rowstat_out) HIPCHK(hipMemcpy(rowstat_out, dro.p, (size_t)M * 8, hipMemcpyDeviceToHost));
     } else {
         std::vector<bf16_t> tmp(MN);
@@ -117,6 +119,13 @@ int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const f
     }
     return VT_OK;
 } VT_NOTHROW_INT
+
+int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias, float* c_inout,
+                    int M, int N, int K, int epilogue, int cfg, const float* rowstat_in, const float* colsum,
+                    float* rowstat_out, float eps) {
+    return vt_op_gemm_bf16_lo(device_id, a, w, bias, c_inout, M, N, K, epilogue, cfg, rowstat_in, colsum, rowstat_out, eps,
+                              VT_LO_SHIFT_DEFAULT);
+}
 
 // Timing helper for kernel tuning: runs the GEMM kernel `iters` times on device-resident random
 // operands with tile configuration `cfg` (<0: the launcher's own choice) and returns the mean time
@@ -495,13 +504,15 @@ int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, con
     return VT_OK;
 } VT_NOTHROW_INT
 
-// The head's first layer with the final LayerNorm: out[b * ns + cell][n] = ReLU(LayerNorm(xh + xl)[b * ntok + off + cell] . w[n] + bias[n])
+// The head's first layer with the final LayerNorm: out[b * ns + cell][n] = ReLU(LayerNorm(xh + xl * 2^-lo_shift)[b * ntok + off + cell] . w[n] + bias[n])
 // as bf16. fused != 0: one launch (the band kernel normalises its rows itself); fused == 0: the LayerNorm kernel, then the
 // band kernel on its output - the form the fused one must reproduce bit for bit. xh == nullptr: synthetic operands (timing).
-int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
-                           float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
-                           int D, int N, int fused, int R, int ncb, int iters, float* us_out) try {
+int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
+                              float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
+                              int D, int N, int fused, int R, int ncb, int iters, float* us_out, int lo_shift) try {
     const int ns = grid * grid;
+    if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "headconv_ln: lo_shift %d out of range", lo_shift);
+    const float lo_q = lo_quant(lo_shift).q;
     if (B < 1 || grid < 1 || off < 0 || ntok < off + ns || (xh && (!xl || !gamma || !beta || !w || !bias)))
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
     if (!headconv_ln_supported(grid, N, D))
@@ -539,14 +550,14 @@ int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, 
     h.B = B; h.grid = grid; h.C = N; h.N = N; h.K = D; h.conv3x3 = 0; h.R = R; h.ncb = ncb;
     if (fused) {
         h.xh = (const bf16_t*)dh.p; h.xl = (const uint8_t*)dl.p; h.ln_g = (const float*)dg.p; h.ln_b = (const float*)dbt.p;
-        h.ln_eps = eps; h.in_stride = ntok; h.in_off = off;
+        h.ln_eps = eps; h.in_stride = ntok; h.in_off = off; h.lo_q = lo_q;
     } else {
         h.in = (const bf16_t*)dfeat.p; h.ldin = D;
     }
     auto run = [&]() -> hipError_t {
         if (!fused) {
             hipError_t e = launch_layernorm_split((const bf16_t*)dh.p, (const uint8_t*)dl.p, (const float*)dg.p, (const float*)dbt.p,
-                                                  (bf16_t*)dfeat.p, (int)M, D, ns, ntok, off, eps, nullptr);
+                                                  (bf16_t*)dfeat.p, (int)M, D, ns, ntok, off, eps, lo_q, nullptr);
             if (e != hipSuccess) return e;
         }
         return launch_headconv(h, nullptr, nullptr);
@@ -573,5 +584,12 @@ int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, 
     }
     return VT_OK;
 } VT_NOTHROW_INT
+
+int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
+                           float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
+                           int D, int N, int fused, int R, int ncb, int iters, float* us_out) {
+    return vt_op_headconv_ln_bf16_lo(device_id, xh, xl, gamma, beta, eps, ntok, off, w, bias, out, B, grid, D, N, fused, R, ncb,
+                                     iters, us_out, VT_LO_SHIFT_DEFAULT);
+}
 
 }  // extern "C"

@@ -9,7 +9,8 @@ bits — plus a small convolutional centre head whose trained weights are commit
 assets/ (they were fitted against exactly these encoder weights, tests/golden/fit_head.py).
 
 Blob layout (little endian):
-  [0,256)    header: magic "VTWB0001", 20 x int32 model fields, 8 x float32
+  [0,256)    header: magic "VTWB0001", 20 x int32 model fields, 8 x float32; int 12 is lo_shift, the shift s of
+             the residual pair's quantum 2^-s (0 = the default 12, else 6..14)
   [256, ...) tensor table, 64 B per entry: name[32], dtype u32 (0=f32, 1=bf16), rows u32,
              cols u32, pad u32, offset u64, nbytes u64
   data       each tensor 256-B aligned
@@ -267,7 +268,21 @@ def generate_tensors(cfg: ModelConfig, head: dict | None = None, use_asset: bool
     return out
 
 
-def pack_blob(cfg: ModelConfig, tensors: dict) -> bytes:
+LO_SHIFT_DEFAULT, LO_SHIFT_MIN, LO_SHIFT_MAX = 12, 6, 14
+_LO_SHIFT_OFFSET = 8 + 4 * 12     # header int 12
+
+
+def _check_lo_shift(s: int) -> int:
+    s = int(s)
+    if s != 0 and not LO_SHIFT_MIN <= s <= LO_SHIFT_MAX:
+        raise ValueError(f"lo_shift {s}: 0 (= {LO_SHIFT_DEFAULT}) or {LO_SHIFT_MIN}..{LO_SHIFT_MAX}")
+    return s
+
+
+def pack_blob(cfg: ModelConfig, tensors: dict, lo_shift: int = 0) -> bytes:
+    """lo_shift: the residual pair's quantum is 2^-lo_shift (header int 12; 0 keeps the default 12 and the bytes of
+    every blob written before the field existed)"""
+    lo_shift = _check_lo_shift(lo_shift)
     names = list(tensors.keys())
     table_off = HEADER_BYTES
     data_off = (table_off + ENTRY_BYTES * len(names) + ALIGN - 1) // ALIGN * ALIGN
@@ -285,7 +300,7 @@ def pack_blob(cfg: ModelConfig, tensors: dict) -> bytes:
         off += padded
     na, nb = norm_constants()
     ints = [1, cfg.patch, cfg.template, cfg.search, cfg.dim, cfg.heads, cfg.layers, cfg.mlp_dim,
-            cfg.head_ch, cfg.kpad, len(names), cfg.seed] + [0] * 8
+            cfg.head_ch, cfg.kpad, len(names), cfg.seed, lo_shift] + [0] * 7
     floats = list(na) + list(nb) + [0.20, 1e-6]  # default success threshold, LayerNorm eps
     header = MAGIC + struct.pack("<20i", *ints) + struct.pack("<8f", *floats)
     header += b"\0" * (HEADER_BYTES - len(header))
@@ -295,14 +310,14 @@ def pack_blob(cfg: ModelConfig, tensors: dict) -> bytes:
 
 
 def parse_blob(blob: bytes | memoryview):
-    """-> (header dict, {name: float32 or uint16 array})."""
+    """-> (header dict, {name: float32 or uint16 array}). hdr["lo_shift"] is the effective shift (slot 0 reads as 12)."""
     mv = memoryview(blob)
     assert bytes(mv[:8]) == MAGIC, "bad magic"
     ints = struct.unpack_from("<20i", mv, 8)
     floats = struct.unpack_from("<8f", mv, 8 + 80)
     hdr = dict(version=ints[0], patch=ints[1], template=ints[2], search=ints[3], dim=ints[4],
                heads=ints[5], layers=ints[6], mlp_dim=ints[7], head_ch=ints[8], kpad=ints[9],
-               n_tensors=ints[10], seed=ints[11], norm_a=np.array(floats[0:3], np.float32),
+               n_tensors=ints[10], seed=ints[11], lo_shift=ints[12] or LO_SHIFT_DEFAULT, norm_a=np.array(floats[0:3], np.float32),
                norm_b=np.array(floats[3:6], np.float32), success_threshold=floats[6],
                ln_eps=floats[7])
     tensors = {}
@@ -321,23 +336,53 @@ def default_cache_dir() -> str:
 
 
 def ensure_weights(cfg_name: str, path: str | None = None, head: dict | None = None,
-                   use_asset: bool = True, force: bool = False) -> str:
-    """Generate (once) and return the path of the weight blob for a named config."""
+                   use_asset: bool = True, force: bool = False, lo_shift: int = 0) -> str:
+    """Generate (once) and return the path of the weight blob for a named config. A non-zero lo_shift goes into the
+    header and into the cache file's name."""
     cfg = get_config(cfg_name)
+    lo_shift = _check_lo_shift(lo_shift)
     if path is None:
         os.makedirs(default_cache_dir(), exist_ok=True)
-        tag = "" if use_asset else "_randhead"
+        tag = ("" if use_asset else "_randhead") + (f"_lo{lo_shift}" if lo_shift else "")
         path = os.path.join(default_cache_dir(), f"{cfg.name}_seed{cfg.seed}{tag}.vtw")
     asset = head_asset_path(cfg)
     stale = (use_asset and head is None and os.path.exists(asset) and os.path.exists(path)
              and os.path.getmtime(asset) > os.path.getmtime(path))
     if force or stale or head is not None or not os.path.exists(path):
-        blob = pack_blob(cfg, generate_tensors(cfg, head=head, use_asset=use_asset))
+        blob = pack_blob(cfg, generate_tensors(cfg, head=head, use_asset=use_asset), lo_shift=lo_shift)
         tmp = path + f".tmp{os.getpid()}"
         with open(tmp, "wb") as f:
             f.write(blob)
         os.replace(tmp, path)
     return path
+
+
+def set_lo_shift(path: str, s: int) -> None:
+    """Stamp an existing blob with lo_shift s (0 or 6..14) in place: only header int 12 changes."""
+    s = _check_lo_shift(s)
+    with open(path, "r+b") as f:
+        if f.read(8) != MAGIC:
+            raise ValueError(f"{path}: not a {MAGIC.decode()} blob")
+        f.seek(_LO_SHIFT_OFFSET)
+        f.write(struct.pack("<i", s))
+
+
+XRANGE_COLS = 12      # vt_group_read_tensor "xrange": lo_shift, max |x|, n(|lo8| == 127), n(|x| >= 2^k) k = 1..9
+
+
+def recommend_lo_shift(xrange_rows) -> int:
+    """The largest s in 6..12 whose exact range |x| < 2^(15 - s) covers every value of every stage of an "xrange"
+    report ([stages][12] rows, or Group.residual_range's dicts): n(|x| >= 2^(15 - s)) == 0 in all rows. Raises
+    ValueError if some value reaches 2^9, which not even s = 6 covers."""
+    rows = [[r["lo_shift"], r["max_abs"], r["n_sat"]] + list(r["n_ge_pow2"]) if isinstance(r, dict) else list(r)
+            for r in xrange_rows]
+    if not rows or any(len(r) != XRANGE_COLS for r in rows):
+        raise ValueError("recommend_lo_shift: need rows of 12 columns")
+    for s in range(LO_SHIFT_DEFAULT, LO_SHIFT_MIN - 1, -1):
+        k = 15 - s                                  # column of n(|x| >= 2^k): 2 + k
+        if all(r[2 + k] == 0 for r in rows):
+            return s
+    raise ValueError("recommend_lo_shift: values reach 2^9; no shift in 6..12 holds them exactly")
 
 
 def engine_stream_cap(cfg: "ModelConfig | str", max_streams: int = 1024) -> int:

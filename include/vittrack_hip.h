@@ -531,7 +531,12 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
 /* Copy an intermediate tensor of the last pass to the host as float32.
  * names: "patches" [N,Kpad], "tokens0" [N,D], "layer<i>" [N,D] (residual stream after block i;
  * both need taps), "x" [N,D] (final residual stream; like the taps the value of the 3-byte pair it is stored
- * as: bf16 + a signed byte in units of 2^-12), "rowstat" [N,2] (row terms of the last folded LayerNorm), "attn" [N,D] (last block's attention output),
+ * as: bf16 + a signed byte in units of 2^-s, s the lo_shift of the weight blob's header int 12: 0 = 12, else 6..14),
+ * "xrange" [stages,12] (range report of the stream's stored residual, computed by this call: per stage lo_shift, max |x|,
+ * n(|lo8| == 127) and n(|x| >= 2^k) for k = 1..9; with taps enabled the stages are tokens0, layer0 .. layer<L-1> of the
+ * last pass, without them one row for "x" - a host can poll it after any pass to learn that a stream has left the
+ * exact range |x| < 2^(15 - s); with taps enabled it needs a pass since vt_group_enable_taps, else VT_ERR_INVALID_ARG),
+ * "rowstat" [N,2] (row terms of the last folded LayerNorm), "attn" [N,D] (last block's attention output),
  * "feat" [Ns,D], "head_t3" [Ns,C], "head_out" [Ns,8] (score,ox,oy,w,h logits),
  * "state" (the stream's device state record as raw 32-bit words), "graph_replays" [3] (passes replayed so far
  * per crop-buffer tier: which of the captured graphs ran). After a subset pass (vt_group_*_streams) every

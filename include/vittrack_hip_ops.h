@@ -32,6 +32,11 @@ extern "C" {
 int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias,
                     float* c_inout, int M, int N, int K, int epilogue, int cfg,
                     const float* rowstat_in, const float* colsum, float* rowstat_out, float eps);
+/* The same with the pair's quantum 2^-lo_shift (6..14; vt_op_gemm_bf16 is lo_shift = 12): lo8 = clamp(rint((x - hi) *
+ * 2^lo_shift), +-127), x comes back as hi + lo8 * 2^-lo_shift, and epilogue 1 decodes c_inout's pair with it. */
+int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, const float* bias,
+                       float* c_inout, int M, int N, int K, int epilogue, int cfg,
+                       const float* rowstat_in, const float* colsum, float* rowstat_out, float eps, int lo_shift);
 /* Kernel-tuning helper: mean microseconds per launch of the GEMM kernel on device-resident random
  * operands. epilogue uses the library's internal numbering (0 f32+pos, 1 residual, 2 GELU, 3 ReLU,
  * 4 QKV, 5 f32); cfg: 0 = 64x64 ring 4, 1 = 128x128 ring 3, 2 = 64x64 ring 2, 3 = 128x128 ring 2
@@ -64,6 +69,11 @@ int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, con
 int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
                            float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
                            int D, int N, int fused, int R, int ncb, int iters, float* us_out);
+/* The same on a pair whose quantum is 2^-lo_shift (6..14; vt_op_headconv_ln_bf16 is lo_shift = 12). fused == 0 runs the
+ * stand-alone LayerNorm kernel's pair reader (csrc/k_misc.hip), fused != 0 the band kernel's. */
+int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
+                              float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
+                              int D, int N, int fused, int R, int ncb, int iters, float* us_out, int lo_shift);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
