@@ -204,6 +204,26 @@ impl VitTrack {
         }
         Ok(mi)
     }
+
+    /// Let the device re-cut the template every `period` updates (0: off, else 2..=1_000_000) whose result succeeds with
+    /// `score >= min_score` (vt_set_template_refresh): what a re-`init` with that update's frame and box would write,
+    /// without leaving the update path. For a camera that tracks one target for hours.
+    pub fn set_template_refresh(&mut self, period: i32, min_score: f32) -> Result<(), TrackError> {
+        let rc = unsafe { sys::vt_set_template_refresh(self.h, period, min_score) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(())
+    }
+
+    pub fn template_refresh_stats(&mut self) -> Result<sys::VtRefreshStats, TrackError> {
+        let mut st = sys::VtRefreshStats::default();
+        let rc = unsafe { sys::vt_template_refresh_stats(self.h, &mut st) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(st)
+    }
 }
 
 impl Drop for VitTrack {
@@ -308,4 +328,18 @@ pub unsafe fn group_reacquire_host(g: *mut sys::vt_group, stream: i32, host_fram
         }
     }
     best.ok_or_else(|| bad("no scan window"))
+}
+
+/// The refresh policy of one camera of a group, or of all with `stream = -1` (vt_group_set_template_refresh): the
+/// device re-cuts the template inside the pass, so the pipelined passes keep running full. Refused while a pipelined
+/// pass is outstanding.
+///
+/// # Safety
+/// `g` is a live group handle.
+pub unsafe fn group_set_template_refresh(g: *mut sys::vt_group, stream: i32, period: i32, min_score: f32) -> Result<(), TrackError> {
+    let rc = sys::vt_group_set_template_refresh(g, stream, period, min_score);
+    if rc != sys::VT_OK {
+        return Err(last(rc));
+    }
+    Ok(())
 }

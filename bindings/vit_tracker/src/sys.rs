@@ -113,6 +113,18 @@ pub struct VtCandidate {
     pub r#box: [f32; 4],
 }
 
+/// ≙ vt_refresh_stats: a stream's template refresh policy and what it has done since init (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct VtRefreshStats {
+    pub period: i32,
+    pub min_score: f32,
+    pub generation: i32,
+    pub last_frame: i32,
+    pub skipped_geometry: i32,
+    pub reserved: [i32; 3],
+}
+
 /// ≙ vt_draw_cmd
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -211,6 +223,10 @@ extern "C" {
                                            out: *mut VtResult, winner: *mut i32) -> c_int;
     pub fn vt_scan_windows(frame_w: c_int, frame_h: c_int, box_w: f32, box_h: f32, overlap_pct: c_int, boxes4: *mut f32,
                            cap: c_int) -> c_int;
+    pub fn vt_set_template_refresh(t: *mut vt_tracker, period: c_int, min_score: f32) -> c_int;
+    pub fn vt_template_refresh_stats(t: *mut vt_tracker, out: *mut VtRefreshStats) -> c_int;
+    pub fn vt_group_set_template_refresh(g: *mut vt_group, stream: c_int, period: c_int, min_score: f32) -> c_int;
+    pub fn vt_group_template_refresh_stats(g: *mut vt_group, stream: c_int, out: *mut VtRefreshStats) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

@@ -73,6 +73,12 @@ class CCandidate(Structure):
     _fields_ = [("stream", c_int32), ("has_box", c_int32), ("box", c_float * 4)]
 
 
+class CRefreshStats(Structure):
+    """vt_refresh_stats (32 bytes): a stream's refresh policy and what it has done since init"""
+    _fields_ = [("period", c_int32), ("min_score", c_float), ("generation", c_int32), ("last_frame", c_int32),
+                ("skipped_geometry", c_int32), ("reserved", c_int32 * 3)]
+
+
 class CDrawCmd(Structure):
     _fields_ = [("type", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
                 ("p", c_int32), ("value", c_int32), ("text", c_char * 36)]
@@ -104,6 +110,8 @@ EXPORTS = [
     "vt_group_enqueue_host_streams", "vt_group_enqueue_init_host",
     "vt_group_update_device_candidates", "vt_group_update_host_candidates", "vt_scan_windows",
     "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob", "vt_init_frame", "vt_update_frame",
+    "vt_set_template_refresh", "vt_template_refresh_stats", "vt_group_set_template_refresh",
+    "vt_group_template_refresh_stats",
 ]
 # every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
 OPS_EXPORTS = [
@@ -185,6 +193,10 @@ def lib():
                                                     POINTER(c_int32)]
     L.vt_group_update_host_candidates.argtypes = L.vt_group_update_device_candidates.argtypes
     L.vt_scan_windows.argtypes = [c_int, c_int, c_float, c_float, c_int, POINTER(c_float), c_int]
+    L.vt_set_template_refresh.argtypes = [c_void_p, c_int, c_float]
+    L.vt_template_refresh_stats.argtypes = [c_void_p, POINTER(CRefreshStats)]
+    L.vt_group_set_template_refresh.argtypes = [c_void_p, c_int, c_int, c_float]
+    L.vt_group_template_refresh_stats.argtypes = [c_void_p, c_int, POINTER(CRefreshStats)]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -595,6 +607,16 @@ class VitTrack:
         self._call("update", frame, byref(r))
         return TrackResult(r)
 
+    def set_template_refresh(self, period: int, min_score: float = 0.5) -> None:
+        """vt_set_template_refresh: re-cut the template on the device every `period` updates (0: off, else >= 2) whose
+        result succeeds with score >= min_score; see Group.set_template_refresh"""
+        _check(lib().vt_set_template_refresh(self._h, int(period), float(min_score)))
+
+    def template_refresh_stats(self) -> dict:
+        st = CRefreshStats()
+        _check(lib().vt_template_refresh_stats(self._h, byref(st)))
+        return _refresh_stats_dict(st)
+
     # device-resident frames (pointers into this GPU's HBM, e.g. torch tensors' data_ptr())
     def init_nv12_device(self, d_y, d_uv, w, h, y_stride, uv_stride, bbox: BBox):
         _check(lib().vt_init_nv12_device(self._h, d_y, d_uv, w, h, y_stride, uv_stride, bbox._c()))
@@ -621,6 +643,11 @@ class VitTrack:
         r = CResult()
         _check(lib().vt_update_rgb8_device(self._h, d_rgb, w, h, stride, byref(r)))
         return TrackResult(r)
+
+
+def _refresh_stats_dict(st: "CRefreshStats") -> dict:
+    return dict(period=int(st.period), min_score=float(st.min_score), generation=int(st.generation),
+                last_frame=int(st.last_frame), skipped_geometry=int(st.skipped_geometry))
 
 
 def frame_nv12(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
@@ -873,6 +900,24 @@ class Group:
             keep["done"] = done + 1
         return [TrackResult(r) for r in out]
 
+    def set_template_refresh(self, period: int, min_score: float = 0.5, stream: int | None = None) -> None:
+        """vt_group_set_template_refresh: the refresh policy of `stream` (None: every stream). period 0 switches it off;
+        otherwise the device re-cuts the stream's template from the frame of an update, at the box that update returned,
+        once at least `period` (>= 2) updates have passed since the last refresh, the update succeeded with score >=
+        min_score and the new template crop lies inside the search crop that update sampled - inside the pass, on every
+        kind of pass, the pipelined ones included. Exactly init(stream, that frame, that box) as far as the template
+        goes. The first enabling makes the engine refresh-capable (a second template buffer per stream, graphs
+        recaptured); refused while a pipelined pass is outstanding."""
+        _check(lib().vt_group_set_template_refresh(self._h, -1 if stream is None else int(stream), int(period),
+                                                   float(min_score)))
+
+    def template_refresh_stats(self, stream: int = 0) -> dict:
+        """vt_group_template_refresh_stats: period, min_score, generation (refreshes since init), last_frame (frames_done
+        at the last one), skipped_geometry (due refreshes skipped by the geometry rule)"""
+        st = CRefreshStats()
+        _check(lib().vt_group_template_refresh_stats(self._h, int(stream), byref(st)))
+        return _refresh_stats_dict(st)
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""
@@ -921,7 +966,7 @@ class Group:
         return dict(box=raw[0:4].copy(), geo=raw[4:8].copy(), frame_w=int(i[8]),
                     frame_h=int(i[9]), initialized=int(i[10]), frames_done=int(i[11]),
                     success_count=int(i[12]), last_idx=int(i[13]), last_fbox=raw[14:18].copy(),
-                    last_score=float(raw[18]))
+                    last_score=float(raw[18]), window_miss=int(i[19]), tpl_gen=int(i[20]), tpl_frame=int(i[21]))
 
 
 # ---- reference colour converter -------------------------------------------------------------

@@ -16,21 +16,7 @@
 #include <algorithm>
 
 #include "vt_common.hpp"
-
-// /root/reference/src/nv12_convert.rs:24-29 (table entries) and :124-131 (per pixel)
-__device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, int& r, int& g, int& b) {
-    const int yv = 298 * (y - 16);
-    r = yv + 409 * (v - 128) + 128;
-    g = yv - 100 * (u - 128) - 208 * (v - 128) + 128;
-    b = yv + 516 * (u - 128) + 128;
-    // clamp_u8(x >> 8) written as clamp first, shift second (same value: the arithmetic shift is
-    // monotonic). The shift-then-clamp form is pattern-matched by hipcc (ROCm 7.2) into
-    // v_ashr_pk_u8_i32, whose upper 16 result bits are not zero on MI355X although the
-    // compiler ORs the result as if they were — measured: wrong bytes 2/3 of every packed dword.
-    r = min(max(r, 0), 0xffff) >> 8;
-    g = min(max(g, 0), 0xffff) >> 8;
-    b = min(max(b, 0), 0xffff) >> 8;
-}
+#include "k_preproc_dev.hpp"
 
 // One lane converts 4 horizontally adjacent pixels (two UV pairs). Packed NV12, stride == width
 // (src/nv12_convert.rs:53-54,105-106). g: index of the 4-pixel group in the frame, row-major.
@@ -270,111 +256,23 @@ hipError_t launch_nv12_to_rgb8(const uint8_t* nv12, int w, int h, uint8_t* rgb, 
     return hipGetLastError();
 }
 
-// frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding).
-// ANY = false: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
-// constants); ANY = true: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_common.hpp). The
-// engine launches the ANY kernels only for passes that carry one of the other formats: reading the offsets at run time
-// costs the crop kernels 3-19 SGPRs (kernel-resource-usage), and those of the three original formats keep their budget.
-template <bool ANY>
-__device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, float* rgb, int& miss) {
-    if (px < 0 || py < 0 || px >= f.w || py >= f.h) {
-        rgb[0] = rgb[1] = rgb[2] = 0.0f;
-        return;
-    }
-    int r, g, b;
-    const int sx = px - f.x0, sy = py - f.y0;   // position inside the stored window
-    // inside the frame but outside what the caller stored (a window narrower than the crop): black,
-    // never an out-of-bounds read. The library's own window planner always covers the crop.
-    if ((unsigned)sx >= (unsigned)f.ww || (unsigned)sy >= (unsigned)f.wh) {
-        rgb[0] = rgb[1] = rgb[2] = 0.0f;
-        miss = 1;
-        return;
-    }
-    if constexpr (ANY) {    // the masks keep every offset inside its pixel / pair
-        const int lay = f.lay;
-        if (f.fmt == PIXF_RGB) {            // RGB8, BGR8, RGBX, BGRX: colour bytes 0-2, permuted by the offsets
-            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * (unsigned)(lay >> 24);
-            const uint32_t c = __builtin_amdgcn_perm(0u, (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16),
-                                                     ((uint32_t)lay & 0x00ffffffu) | 0x0c000000u);
-            r = c & 255; g = (c >> 8) & 255; b = c >> 16;
-        } else if (f.fmt == PIXF_420SP) {   // NV12, NV21
-            const int y = f.p0[(size_t)sy * f.s0 + sx];
-            const uint8_t* uv = f.p1 + (size_t)(sy >> 1) * f.s1 + (sx & ~1);   // x0, y0 even
-            const uint32_t c = __builtin_amdgcn_perm(0u, (uint32_t)uv[0] | ((uint32_t)uv[1] << 8), ((uint32_t)lay & 0xffffu) | 0x0c0c0000u);
-            yuv_to_rgb(y, c & 255, c >> 8, r, g, b);
-        } else {                            // YUY2 (Y0 U Y1 V), UYVY (U Y0 V Y1) per pixel pair
-            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
-            yuv_to_rgb(p[(sx & 1) ? (lay >> 16) & 3 : lay & 3], p[(lay >> 8) & 3], p[(lay >> 24) & 3], r, g, b);
-        }
-    } else if (f.fmt == VT_PIX_RGB8) {
-        const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * 3;
-        r = p[0]; g = p[1]; b = p[2];
-    } else if (f.fmt == VT_PIX_NV12) {
-        const int y = f.p0[(size_t)sy * f.s0 + sx];
-        const uint8_t* uv = f.p1 + (size_t)(sy >> 1) * f.s1 + (sx & ~1);   // x0, y0 even
-        yuv_to_rgb(y, uv[0], uv[1], r, g, b);
-    } else {  // YUY2: Y0 U Y1 V per pixel pair
-        const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
-        yuv_to_rgb(p[(sx & 1) * 2], p[1], p[3], r, g, b);
-    }
-    rgb[0] = (float)r; rgb[1] = (float)g; rgb[2] = (float)b;
-}
-
+// The crop kernels. Their bodies are the TEXT of k_preproc_body.inc, included below into each kernel - and, by
+// k_refresh.hip, into a lambda of the template refresh kernel, so that the refresh writes the bits init writes. What a
+// maintainer of these kernels has to know: the body sees the names declared in front of the include (ANY, f, s, patches,
+// b, the kernel's parameters, PX, src / LDSPX) and nothing else of the kernel; a `return` in it ends this kernel here
+// and only the lambda there (the refresh kernel goes on to its commit), so nothing that every thread must reach may
+// follow a body. As inlined device functions the tile body compiled to other code (profiles/template_refresh.txt).
+#define PRE_KERNEL_PARAMS const FrameDesc* __restrict__ frames, StreamState* __restrict__ states, bf16_t* __restrict__ patches, \
+    int b0, int size, int patch, int kpad, int ntok, int row_off, float factor, float na0, float na1, float na2, float nb0, \
+    float nb1, float nb2, int is_template, const int32_t* __restrict__ slot_stream
 // grid: (ceil(size*size/256), nb); one lane per output pixel, 3 channels each.
 template <bool ANY>
-__global__ __launch_bounds__(256) void preproc_kernel(const FrameDesc* __restrict__ frames,
-                                                      StreamState* __restrict__ states,
-                                                      bf16_t* __restrict__ patches, int b0,
-                                                      int size, int patch, int kpad, int ntok,
-                                                      int row_off, float factor, float na0,
-                                                      float na1, float na2, float nb0, float nb1,
-                                                      float nb2, int is_template,
-                                                      const int32_t* __restrict__ slot_stream) {
+__global__ __launch_bounds__(256) void preproc_kernel(PRE_KERNEL_PARAMS) {
     const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
     StreamState& s = states[slot_stream ? slot_stream[b] : b];     // the stream it works for (null map: the slot)
-    // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
-    const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
-    const float area = bw * bh;
-    const float side = factor * sqrtf(area);
-    const float scale = side / (float)size;
-    const float cx = bx + 0.5f * bw;
-    const float cy = by + 0.5f * bh;
-    const float half = 0.5f * side;
-    const float x0m = (cx - half) - 0.5f;
-    const float y0m = (cy - half) - 0.5f;
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix == 0 && !is_template) {
-        s.geo[0] = x0m; s.geo[1] = y0m; s.geo[2] = scale; s.geo[3] = side;
-        s.frame_w = f.w; s.frame_h = f.h;
-    }
-    if (pix >= size * size) return;
-    const int oy = pix / size, ox = pix % size;
-    const float fy = ((float)oy + 0.5f) * scale + y0m;
-    const float fx = ((float)ox + 0.5f) * scale + x0m;
-    const float fy0 = floorf(fy), fx0 = floorf(fx);
-    const float wy = fy - fy0, wx = fx - fx0;
-    const int iy = (int)fy0, ix = (int)fx0;
-    float p00[3], p01[3], p10[3], p11[3];
-    int miss = 0;
-    fetch_rgb<ANY>(f, ix, iy, p00, miss);
-    fetch_rgb<ANY>(f, ix + 1, iy, p01, miss);
-    fetch_rgb<ANY>(f, ix, iy + 1, p10, miss);
-    fetch_rgb<ANY>(f, ix + 1, iy + 1, p11, miss);
-    if (miss && !is_template) s.window_miss = s.frames_done + 1;   // every writer stores the same value
-    const int grid = size / patch;
-    const int token = (oy / patch) * grid + (ox / patch);
-    const int kin = (oy % patch) * patch + (ox % patch);
-    bf16_t* row = patches + ((size_t)b * ntok + row_off + token) * kpad;
-    const float na[3] = {na0, na1, na2}, nb[3] = {nb0, nb1, nb2};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float top = p00[c] + wx * (p01[c] - p00[c]);
-        const float bot = p10[c] + wx * (p11[c] - p10[c]);
-        const float v = top + wy * (bot - top);
-        const float o = v * na[c] + nb[c];
-        row[c * patch * patch + kin] = f32_to_bf16(o);
-    }
+#define PRE_BODY 1
+#include "k_preproc_body.inc"
 }
 
 // Wide-store variant: one lane produces PX horizontally adjacent output pixels of one patch row for
@@ -385,78 +283,12 @@ __global__ __launch_bounds__(256) void preproc_kernel(const FrameDesc* __restric
 // preproc_kernel (bit-exact with oracle/vt_oracle.c); neighbouring pixels re-fetch shared taps from
 // L1. grid: (ceil(size*size/PX/256), nb).
 template <int PX, bool ANY>
-__global__ __launch_bounds__(256) void preproc_wide_kernel(const FrameDesc* __restrict__ frames,
-                                                           StreamState* __restrict__ states,
-                                                           bf16_t* __restrict__ patches, int b0,
-                                                           int size, int patch, int kpad, int ntok,
-                                                           int row_off, float factor, float na0,
-                                                           float na1, float na2, float nb0, float nb1,
-                                                           float nb2, int is_template,
-                                                           const int32_t* __restrict__ slot_stream) {
+__global__ __launch_bounds__(256) void preproc_wide_kernel(PRE_KERNEL_PARAMS) {
     const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
     StreamState& s = states[slot_stream ? slot_stream[b] : b];     // the stream it works for (null map: the slot)
-    // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
-    const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
-    const float area = bw * bh;
-    const float side = factor * sqrtf(area);
-    const float scale = side / (float)size;
-    const float cx = bx + 0.5f * bw;
-    const float cy = by + 0.5f * bh;
-    const float half = 0.5f * side;
-    const float x0m = (cx - half) - 0.5f;
-    const float y0m = (cy - half) - 0.5f;
-    const int grp = blockIdx.x * blockDim.x + threadIdx.x;        // group of PX pixels
-    if (grp == 0 && !is_template) {
-        s.geo[0] = x0m; s.geo[1] = y0m; s.geo[2] = scale; s.geo[3] = side;
-        s.frame_w = f.w; s.frame_h = f.h;
-    }
-    const int gpr = size / PX;                                     // groups per output row
-    if (grp >= gpr * size) return;
-    const int oy = grp / gpr, ox0 = (grp % gpr) * PX;
-    const float fy = ((float)oy + 0.5f) * scale + y0m;
-    const float fy0 = floorf(fy);
-    const float wy = fy - fy0;
-    const int iy = (int)fy0;
-    const float na[3] = {na0, na1, na2}, nb[3] = {nb0, nb1, nb2};
-    bf16_t o[3][PX];
-    int miss = 0;
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-        const float fx = ((float)(ox0 + k) + 0.5f) * scale + x0m;
-        const float fx0 = floorf(fx);
-        const float wx = fx - fx0;
-        const int ix = (int)fx0;
-        float p00[3], p01[3], p10[3], p11[3];
-        fetch_rgb<ANY>(f, ix, iy, p00, miss);
-        fetch_rgb<ANY>(f, ix + 1, iy, p01, miss);
-        fetch_rgb<ANY>(f, ix, iy + 1, p10, miss);
-        fetch_rgb<ANY>(f, ix + 1, iy + 1, p11, miss);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float top = p00[c] + wx * (p01[c] - p00[c]);
-            const float bot = p10[c] + wx * (p11[c] - p10[c]);
-            const float v = top + wy * (bot - top);
-            o[c][k] = f32_to_bf16(v * na[c] + nb[c]);
-        }
-    }
-    if (miss && !is_template) s.window_miss = s.frames_done + 1;   // every writer stores the same value
-    const int grid = size / patch;
-    const int token = (oy / patch) * grid + (ox0 / patch);         // PX divides patch: one token per group
-    const int kin = (oy % patch) * patch + (ox0 % patch);
-    bf16_t* row = patches + ((size_t)b * ntok + row_off + token) * kpad;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        bf16_t* dst = row + c * patch * patch + kin;
-        if constexpr (PX == 8) {
-            uint4 v;
-            v.x = o[c][0] | ((uint32_t)o[c][1] << 16); v.y = o[c][2] | ((uint32_t)o[c][3] << 16);
-            v.z = o[c][4] | ((uint32_t)o[c][5] << 16); v.w = o[c][6] | ((uint32_t)o[c][7] << 16);
-            *reinterpret_cast<uint4*>(dst) = v;
-        } else {
-            *reinterpret_cast<uint32_t*>(dst) = o[c][0] | ((uint32_t)o[c][1] << 16);
-        }
-    }
+#define PRE_BODY 2
+#include "k_preproc_body.inc"
 }
 
 // Tile variant (size % 64 == 0, patch % 8 == 0): a block produces a 64 x 32 tile of output pixels.
@@ -479,223 +311,27 @@ __global__ __launch_bounds__(256) void preproc_wide_kernel(const FrameDesc* __re
 // shipped. What shipped: the kernel in three buffer tiers (below), one captured graph each, chosen per pass by the
 // engine from the boxes the host already knows: 160 px at cfg3 29.5 us, 96 px at cfg2 19.5 us, the 64-px case on
 // the unchanged tier-0 kernel.
-#define PRE_TILE_W 64
-#define PRE_TILE_H 32
-// 16 KiB of LDS per block: eight 256-thread blocks per CU (the thread limit), so the 2,160 blocks of a
+// Tier 0 (PRE_TILE_LDS, k_preproc_dev.hpp) - 16 KiB of LDS per block: eight 256-thread blocks per CU (the thread limit), so the 2,160 blocks of a
 // 30-stream pass are resident at once - a block is one dependent chain (descriptor -> state -> fetch -> LDS ->
 // interpolate -> store, ~7 us) and with 32 KiB (5 blocks per CU) the pass took two rounds of it. A 64-px target
 // at 1080p needs ~1,000 source pixels per tile, a 128-px one ~3,900.
-#define PRE_TILE_LDS 4096       // source pixels (16 KiB): tier 0, the benchmark's 64-px targets
-// Round 5 - larger buffers for larger targets, chosen PER LAUNCH by the engine from the boxes the host already knows
+// Tiers 1 and 2 (round 5) - larger buffers for larger targets, chosen PER LAUNCH by the engine from the boxes the host already knows
 // (vt_engine.hip: one captured graph per tier): tier 1 = 8,192 pixels (32 KiB, five blocks per CU: scales up to ~1.9
 // source pixels per output pixel, targets up to ~185 px at search 384 / ~120 px at search 256), tier 2 = 16,384 pixels
 // (64 KiB, two blocks per CU: scales up to ~2.75, ~260 / ~175 px). A tile that still does not fit takes the per-pixel
 // path below - correct at any size, a 3-4x cliff in time (profiles/r05_preproc_by_target.txt) that tier 0 alone hit
 // from ~130-px targets. The tier changes which path a tile takes, never a value: every path is bit-exact.
 template <int LDSPX, bool ANY>
-__global__ __launch_bounds__(256) void preproc_tile_kernel(const FrameDesc* __restrict__ frames,
-                                                           StreamState* __restrict__ states,
-                                                           bf16_t* __restrict__ patches, int b0,
-                                                           int size, int patch, int kpad, int ntok,
-                                                           int row_off, float factor, float na0,
-                                                           float na1, float na2, float nb0, float nb1,
-                                                           float nb2, int is_template,
-                                                           const int32_t* __restrict__ slot_stream) {
+__global__ __launch_bounds__(256) void preproc_tile_kernel(PRE_KERNEL_PARAMS) {
     __shared__ uint32_t src[LDSPX];
     constexpr int PX = 8;
     const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
     StreamState& s = states[slot_stream ? slot_stream[b] : b];     // the stream it works for (null map: the slot)
-    // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
-    const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
-    const float area = bw * bh;
-    const float side = factor * sqrtf(area);
-    const float scale = side / (float)size;
-    const float cx = bx + 0.5f * bw;
-    const float cy = by + 0.5f * bh;
-    const float half = 0.5f * side;
-    const float x0m = (cx - half) - 0.5f;
-    const float y0m = (cy - half) - 0.5f;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && !is_template) {
-        s.geo[0] = x0m; s.geo[1] = y0m; s.geo[2] = scale; s.geo[3] = side;
-        s.frame_w = f.w; s.frame_h = f.h;
-    }
-    const int tiles_x = size / PRE_TILE_W;
-    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    // lane -> 8-pixel run of the tile. patch 16 (round 4): the tile is 4 x 2 tokens and a half-wave takes ONE
-    // token - lane pair (2 py, 2 py + 1) of 16 patch rows - so that a channel's store instruction writes the
-    // 512 contiguous bytes of that token's channel block instead of 16-B pieces of four different patch rows
-    // (rows of the patch matrix lie kpad * 2 bytes apart); other patch sizes keep the row-major assignment.
-    int oy, ox0;
-    if (patch == 16) {
-        const int tok = threadIdx.x >> 5, py = (threadIdx.x >> 1) & 15, hx = threadIdx.x & 1;
-        oy = ty * PRE_TILE_H + (tok >> 2) * 16 + py;
-        ox0 = tx * PRE_TILE_W + (tok & 3) * 16 + hx * PX;
-    } else {
-        oy = ty * PRE_TILE_H + (threadIdx.x >> 3);
-        ox0 = tx * PRE_TILE_W + (threadIdx.x & 7) * PX;
-    }
-    // source rectangle of the tile: taps of its first and last output pixel (fx, fy grow with ox, oy)
-    const int sx_lo = (int)floorf(((float)(tx * PRE_TILE_W) + 0.5f) * scale + x0m);
-    const int sx_hi = (int)floorf(((float)(tx * PRE_TILE_W + PRE_TILE_W - 1) + 0.5f) * scale + x0m) + 1;
-    const int sy_lo = (int)floorf(((float)(ty * PRE_TILE_H) + 0.5f) * scale + y0m);
-    const int sy_hi = (int)floorf(((float)(ty * PRE_TILE_H + PRE_TILE_H - 1) + 0.5f) * scale + y0m) + 1;
-    const long sw = (long)sx_hi - sx_lo + 1, sh = (long)sy_hi - sy_lo + 1;
-    const bool staged = sw > 0 && sh > 0 && sw * sh <= LDSPX;      // block-uniform
-    if (staged) {
-        const int n = (int)(sw * sh), w_ = (int)sw;
-        // NV12 planes whose rows start on 8-byte boundaries (the library's packed windows: pack_window; whole
-        // frames with such strides): the rectangle is fetched in groups of 8 pixels - ONE 8-byte load of Y
-        // and ONE of the interleaved UV row (4 pairs) per group, where the per-pixel path issues 24 byte
-        // loads - and converted with the same integer formulas. A group that is not entirely inside the
-        // frame and the stored window goes through fetch_rgb pixel by pixel (frame border: black; outside the
-        // window: black + miss), so every entry of the LDS image is what the per-pixel loop writes.
-        // NV21 takes the same path (ANY kernels): the descriptor says which byte of a pair is U
-        const bool fast = f.fmt == PIXF_420SP && (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 7) == 0;
-        // ANY kernels, 4-byte RGB formats (RGBX, BGRX) whose rows start on 16-byte boundaries (the library's packed
-        // windows; whole frames with such strides): ONE 16-byte load per 4 pixels, where the per-pixel path issues 12
-        // byte loads; the same edge rule as the NV12 groups
-        const bool fast4 = ANY && f.fmt == PIXF_RGB && (f.lay >> 24) == 4 && (((uintptr_t)f.p0 | (uintptr_t)f.s0) & 15) == 0;
-        if (fast) {
-            const int us = ANY ? (f.lay & 1) * 8 : 0, vs = ANY ? ((f.lay >> 8) & 1) * 8 : 8;   // bit offsets of U, V in a pair
-            const int g_lo = (sx_lo - f.x0) >> 3, g_hi = (sx_hi - f.x0) >> 3;     // arithmetic shift: floor for negatives
-            const int gpr = g_hi - g_lo + 1, ng = gpr * (int)sh;
-            for (int i = threadIdx.x; i < ng; i += 256) {
-                const int ry = i / gpr, wx0 = (g_lo + i % gpr) << 3;                // window column of the group
-                const int py = sy_lo + ry, wy_ = py - f.y0, px0 = wx0 + f.x0;
-                const bool inside = (unsigned)wy_ < (unsigned)f.wh && (unsigned)py < (unsigned)f.h && wx0 >= 0 &&
-                                    wx0 + 7 < f.ww && px0 >= 0 && px0 + 7 < f.w;
-                uint32_t* dst = src + ry * w_ + (px0 - sx_lo);
-                if (inside) {
-                    const uint2 y8 = *reinterpret_cast<const uint2*>(f.p0 + (size_t)wy_ * f.s0 + wx0);
-                    const uint2 uv8 = *reinterpret_cast<const uint2*>(f.p1 + (size_t)(wy_ >> 1) * f.s1 + wx0);
-                    const uint32_t yw[2] = {y8.x, y8.y}, uw[2] = {uv8.x, uv8.y};
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const int col = px0 - sx_lo + k;
-                        if (col < 0 || col >= w_) continue;
-                        const uint32_t pair = uw[k >> 2] >> (((k >> 1) & 1) * 16);   // U, V of the pixel pair
-                        int r, g, b;
-                        yuv_to_rgb((int)((yw[k >> 2] >> ((k & 3) * 8)) & 255u), (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
-                        dst[k] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
-                    }
-                } else {
-                    for (int k = 0; k < 8; ++k) {
-                        const int col = px0 - sx_lo + k;
-                        if (col < 0 || col >= w_) continue;
-                        float p[3];
-                        int miss = 0;
-                        fetch_rgb<ANY>(f, px0 + k, py, p, miss);
-                        dst[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
-                    }
-                }
-            }
-        } else if (fast4) {
-            const uint32_t sel = ((uint32_t)f.lay & 0x00ffffffu) | 0x0c000000u;   // bytes R, G, B, zero of a pixel
-            const int g_lo = (sx_lo - f.x0) >> 2, g_hi = (sx_hi - f.x0) >> 2;     // arithmetic shift: floor for negatives
-            const int gpr = g_hi - g_lo + 1, ng = gpr * (int)sh;
-            for (int i = threadIdx.x; i < ng; i += 256) {
-                const int ry = i / gpr, wx0 = (g_lo + i % gpr) << 2;                // window column of the group
-                const int py = sy_lo + ry, wy_ = py - f.y0, px0 = wx0 + f.x0;
-                const bool inside = (unsigned)wy_ < (unsigned)f.wh && (unsigned)py < (unsigned)f.h && wx0 >= 0 &&
-                                    wx0 + 3 < f.ww && px0 >= 0 && px0 + 3 < f.w;
-                uint32_t* dst = src + ry * w_ + (px0 - sx_lo);
-                if (inside) {
-                    const u32x4_t q = *reinterpret_cast<const u32x4_t*>(f.p0 + (size_t)wy_ * f.s0 + (size_t)wx0 * 4);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int col = px0 - sx_lo + k;
-                        if (col < 0 || col >= w_) continue;
-                        dst[k] = __builtin_amdgcn_perm(0u, q[k], sel);              // r | g << 8 | b << 16
-                    }
-                } else {
-                    for (int k = 0; k < 4; ++k) {
-                        const int col = px0 - sx_lo + k;
-                        if (col < 0 || col >= w_) continue;
-                        float p[3];
-                        int miss = 0;
-                        fetch_rgb<ANY>(f, px0 + k, py, p, miss);
-                        dst[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
-                    }
-                }
-            }
-        } else {
-            for (int i = threadIdx.x; i < n; i += 256) {
-                float p[3];
-                int miss = 0;
-                fetch_rgb<ANY>(f, sx_lo + i % w_, sy_lo + i / w_, p, miss);
-                src[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
-            }
-        }
-        __syncthreads();
-    }
-    const float fy = ((float)oy + 0.5f) * scale + y0m;
-    const float fy0 = floorf(fy);
-    const float wy = fy - fy0;
-    const int iy = (int)fy0;
-    const float na[3] = {na0, na1, na2}, nb[3] = {nb0, nb1, nb2};
-    const int grid = size / patch;
-    const int token = (oy / patch) * grid + (ox0 / patch);         // PX divides patch: one token per group
-    const int kin = (oy % patch) * patch + (ox0 % patch);
-    bf16_t* row = patches + ((size_t)b * ntok + row_off + token) * kpad;
-    int miss = 0;
-    if (!staged) {
-        // rectangles over 4,096 source pixels (targets from ~130 px at search 384, ~90 px at search 256: see the
-        // kernel's header): direct fetches, pixel by pixel, 2-byte stores. Kept out of
-        // the staged path's code: inlined into its unrolled loop the 32 fetch_rgb bodies cost 70 VGPRs and
-        // with them a block per CU.
-#pragma unroll 1
-        for (int k = 0; k < PX; ++k) {
-            const float fx = ((float)(ox0 + k) + 0.5f) * scale + x0m;
-            const float fx0 = floorf(fx);
-            const float wx = fx - fx0;
-            const int ix = (int)fx0;
-            float p00[3], p01[3], p10[3], p11[3];
-            fetch_rgb<ANY>(f, ix, iy, p00, miss);
-            fetch_rgb<ANY>(f, ix + 1, iy, p01, miss);
-            fetch_rgb<ANY>(f, ix, iy + 1, p10, miss);
-            fetch_rgb<ANY>(f, ix + 1, iy + 1, p11, miss);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float top = p00[c] + wx * (p01[c] - p00[c]);
-                const float bot = p10[c] + wx * (p11[c] - p10[c]);
-                const float v = top + wy * (bot - top);
-                row[c * patch * patch + kin + k] = f32_to_bf16(v * na[c] + nb[c]);
-            }
-        }
-        if (miss && !is_template) s.window_miss = s.frames_done + 1;
-        return;
-    }
-    bf16_t o[3][PX];
-    const int w_ = (int)sw;
-    const uint32_t* r0base = src + (iy - sy_lo) * w_ - sx_lo;
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-        const float fx = ((float)(ox0 + k) + 0.5f) * scale + x0m;
-        const float fx0 = floorf(fx);
-        const float wx = fx - fx0;
-        const uint32_t* r0 = r0base + (int)fx0;
-        const uint32_t t00 = r0[0], t01 = r0[1], t10 = r0[w_], t11 = r0[w_ + 1];
-        miss |= (int)((t00 | t01 | t10 | t11) >> 24);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float p00 = (float)((t00 >> (8 * c)) & 255u), p01 = (float)((t01 >> (8 * c)) & 255u);
-            const float p10 = (float)((t10 >> (8 * c)) & 255u), p11 = (float)((t11 >> (8 * c)) & 255u);
-            const float top = p00 + wx * (p01 - p00);
-            const float bot = p10 + wx * (p11 - p10);
-            const float v = top + wy * (bot - top);
-            o[c][k] = f32_to_bf16(v * na[c] + nb[c]);
-        }
-    }
-    if (miss && !is_template) s.window_miss = s.frames_done + 1;   // every writer stores the same value
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        uint4 v;
-        v.x = o[c][0] | ((uint32_t)o[c][1] << 16); v.y = o[c][2] | ((uint32_t)o[c][3] << 16);
-        v.z = o[c][4] | ((uint32_t)o[c][5] << 16); v.w = o[c][6] | ((uint32_t)o[c][7] << 16);
-        *reinterpret_cast<uint4*>(row + c * patch * patch + kin) = v;
-    }
+#define PRE_BODY 3
+#include "k_preproc_body.inc"
 }
+#undef PRE_KERNEL_PARAMS
 
 // The smallest buffer tier (0, 1, 2; 3 = none: per-pixel path) whose tile buffer holds the source rectangle of a 64 x
 // 32 output tile of a w x h box, with a few per cent of headroom for a box that grows between the host's knowledge of
@@ -766,5 +402,31 @@ hipError_t launch_gather_template_rows(const bf16_t* tpl, bf16_t* patches, const
     const int pieces = d.nt * d.kpad / 8;
     vt_launch(gather_template_rows_kernel, dim3((pieces + 255) / 256, n), dim3(256), 0, st, tpl, patches, slot_stream,
               pieces, d.ntok * d.kpad, d.nt * d.kpad);
+    return hipGetLastError();
+}
+
+// The two-buffer store of an engine with template refresh (k_refresh.hip): tpl[B][2][nt][kpad], the stream's current rows
+// in buffer states[stream].tpl_gen & 1 - read here, on the device, so that a pass queued behind a refresh takes the
+// new rows and a rewound state the old ones. Full passes come here too (slot_stream null: slot i is stream i).
+__global__ __launch_bounds__(256) void gather_template_rows_gen_kernel(const bf16_t* __restrict__ tpl, bf16_t* __restrict__ patches,
+                                                                       const int32_t* __restrict__ slot_stream,
+                                                                       const StreamState* __restrict__ states, int pieces,
+                                                                       int seg_elems, int tpl_elems) {
+    const int i = blockIdx.y;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pieces) return;
+    const int s = slot_stream ? slot_stream[i] : i;
+    const int buf = states[s].tpl_gen & 1;
+    const u32x4_t* src = reinterpret_cast<const u32x4_t*>(tpl + ((size_t)s * 2 + buf) * tpl_elems);
+    u32x4_t* dst = reinterpret_cast<u32x4_t*>(patches + (size_t)i * seg_elems);
+    dst[p] = src[p];
+}
+
+hipError_t launch_gather_template_rows_gen(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream,
+                                           const StreamState* states, int n, const ModelDims& d, hipStream_t st) {
+    if (n < 1 || !tpl || !patches || !states || d.kpad % 8) return hipErrorInvalidValue;
+    const int pieces = d.nt * d.kpad / 8;
+    vt_launch(gather_template_rows_gen_kernel, dim3((pieces + 255) / 256, n), dim3(256), 0, st, tpl, patches, slot_stream,
+              states, pieces, d.ntok * d.kpad, d.nt * d.kpad);
     return hipGetLastError();
 }

@@ -1,0 +1,74 @@
+// k_preproc_dev.hpp — what the crop kernels of k_preproc.hip and the template refresh of k_refresh.hip share besides the
+// kernel bodies of k_preproc_body.inc: the pixel fetch and the tile constants.
+#pragma once
+#include "vt_common.hpp"
+
+// /root/reference/src/nv12_convert.rs:24-29 (table entries) and :124-131 (per pixel)
+__device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, int& r, int& g, int& b) {
+    const int yv = 298 * (y - 16);
+    r = yv + 409 * (v - 128) + 128;
+    g = yv - 100 * (u - 128) - 208 * (v - 128) + 128;
+    b = yv + 516 * (u - 128) + 128;
+    // clamp_u8(x >> 8) written as clamp first, shift second (same value: the arithmetic shift is
+    // monotonic). The shift-then-clamp form is pattern-matched by hipcc (ROCm 7.2) into
+    // v_ashr_pk_u8_i32, whose upper 16 result bits are not zero on MI355X although the
+    // compiler ORs the result as if they were — measured: wrong bytes 2/3 of every packed dword.
+    r = min(max(r, 0), 0xffff) >> 8;
+    g = min(max(g, 0), 0xffff) >> 8;
+    b = min(max(b, 0), 0xffff) >> 8;
+}
+
+// frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding).
+// ANY = false: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
+// constants); ANY = true: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_common.hpp). The
+// engine launches the ANY kernels only for passes that carry one of the other formats: reading the offsets at run time
+// costs the crop kernels 3-19 SGPRs (kernel-resource-usage), and those of the three original formats keep their budget.
+template <bool ANY>
+__device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, float* rgb, int& miss) {
+    if (px < 0 || py < 0 || px >= f.w || py >= f.h) {
+        rgb[0] = rgb[1] = rgb[2] = 0.0f;
+        return;
+    }
+    int r, g, b;
+    const int sx = px - f.x0, sy = py - f.y0;   // position inside the stored window
+    // inside the frame but outside what the caller stored (a window narrower than the crop): black,
+    // never an out-of-bounds read. The library's own window planner always covers the crop.
+    if ((unsigned)sx >= (unsigned)f.ww || (unsigned)sy >= (unsigned)f.wh) {
+        rgb[0] = rgb[1] = rgb[2] = 0.0f;
+        miss = 1;
+        return;
+    }
+    if constexpr (ANY) {    // the masks keep every offset inside its pixel / pair
+        const int lay = f.lay;
+        if (f.fmt == PIXF_RGB) {            // RGB8, BGR8, RGBX, BGRX: colour bytes 0-2, permuted by the offsets
+            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * (unsigned)(lay >> 24);
+            const uint32_t c = __builtin_amdgcn_perm(0u, (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16),
+                                                     ((uint32_t)lay & 0x00ffffffu) | 0x0c000000u);
+            r = c & 255; g = (c >> 8) & 255; b = c >> 16;
+        } else if (f.fmt == PIXF_420SP) {   // NV12, NV21
+            const int y = f.p0[(size_t)sy * f.s0 + sx];
+            const uint8_t* uv = f.p1 + (size_t)(sy >> 1) * f.s1 + (sx & ~1);   // x0, y0 even
+            const uint32_t c = __builtin_amdgcn_perm(0u, (uint32_t)uv[0] | ((uint32_t)uv[1] << 8), ((uint32_t)lay & 0xffffu) | 0x0c0c0000u);
+            yuv_to_rgb(y, c & 255, c >> 8, r, g, b);
+        } else {                            // YUY2 (Y0 U Y1 V), UYVY (U Y0 V Y1) per pixel pair
+            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
+            yuv_to_rgb(p[(sx & 1) ? (lay >> 16) & 3 : lay & 3], p[(lay >> 8) & 3], p[(lay >> 24) & 3], r, g, b);
+        }
+    } else if (f.fmt == VT_PIX_RGB8) {
+        const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * 3;
+        r = p[0]; g = p[1]; b = p[2];
+    } else if (f.fmt == VT_PIX_NV12) {
+        const int y = f.p0[(size_t)sy * f.s0 + sx];
+        const uint8_t* uv = f.p1 + (size_t)(sy >> 1) * f.s1 + (sx & ~1);   // x0, y0 even
+        yuv_to_rgb(y, uv[0], uv[1], r, g, b);
+    } else {  // YUY2: Y0 U Y1 V per pixel pair
+        const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
+        yuv_to_rgb(p[(sx & 1) * 2], p[1], p[3], r, g, b);
+    }
+    rgb[0] = (float)r; rgb[1] = (float)g; rgb[2] = (float)b;
+}
+
+// output tile of the tile body and its smallest LDS buffer in source pixels (k_preproc.hip: the tiers)
+#define PRE_TILE_W 64
+#define PRE_TILE_H 32
+#define PRE_TILE_LDS 4096       // source pixels (16 KiB): tier 0, the benchmark's 64-px targets

@@ -472,9 +472,9 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
     size_t b = (size_t)stream;
     if (n.rfind("slot.", 0) == 0) {     // "slot.<tensor>": `stream` IS a slot of the last pass (the losing slots of a candidate pass)
         n = n.substr(5);
-        if (n == "state" || n == "graph_replays" || stream >= e->pass_n)
+        if (n == "state" || n == "template" || n == "graph_replays" || stream >= e->pass_n)
             return set_err(VT_ERR_INVALID_ARG, "read_tensor: '%s' of slot %d: no such slot tensor in the last pass", name, stream);
-    } else if (n != "state" && n != "graph_replays") {
+    } else if (n != "state" && n != "template" && n != "graph_replays") {
         const int slot = e->slot_of(stream);
         if (slot < 0) return set_err(VT_ERR_INVALID_ARG, "read_tensor: stream %d was not in the last pass", stream);
         b = (size_t)slot;
@@ -525,6 +525,12 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         for (int t = 0; t < Engine::TIERS; ++t) out[t] = (float)e->graph_replays[t];
         return Engine::TIERS;
     }
+    if (n == "template") {      // the stream's current rows in the store: buffer tpl_gen & 1 of a refresh-capable engine
+        int32_t gen = 0;
+        if (e->refresh_capable) HIPCHK(hipMemcpy(&gen, &e->d_states[b].tpl_gen, sizeof(gen), hipMemcpyDeviceToHost));
+        const bf16_t* rows = e->tpl_init_rows((int)b) + (size_t)(gen & 1) * d.nt * d.kpad;
+        return copy_out_bf16(rows, (int64_t)d.nt * d.kpad, out, capacity);
+    }
     if (n == "state") {
         static_assert(sizeof(StreamState) % 4 == 0, "state size");
         return copy_out_f32((const float*)(e->d_states + b), sizeof(StreamState) / 4, out, capacity);
@@ -561,6 +567,25 @@ int vt_get_model_info(const vt_tracker* t, vt_model_info* out) try {
     if (!t || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
     fill_info(t->e, out);
     return VT_OK;
+} VT_NOTHROW_INT
+
+int vt_group_set_template_refresh(vt_group* g, int stream, int period, float min_score) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (int rc = refuse_while_pipelined(g->e, "set_template_refresh")) return rc;
+    return g->e->set_refresh(stream, period, min_score);
+} VT_NOTHROW_INT
+int vt_group_template_refresh_stats(vt_group* g, int stream, vt_refresh_stats* out) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    return g->e->refresh_stats(stream, out);
+} VT_NOTHROW_INT
+int vt_set_template_refresh(vt_tracker* t, int period, float min_score) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    if (int rc = refuse_while_pipelined(t->e, "set_template_refresh")) return rc;   // reachable through vt_tracker_as_group
+    return t->e->set_refresh(0, period, min_score);
+} VT_NOTHROW_INT
+int vt_template_refresh_stats(vt_tracker* t, vt_refresh_stats* out) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    return t->e->refresh_stats(0, out);
 } VT_NOTHROW_INT
 
 int vt_group_host_redos(const vt_group* g) { return g ? (int)g->e->host_redos : 0; }

@@ -85,8 +85,13 @@ struct StreamState {
     // lies inside the frame but outside the window the caller stored: such samples read as black, so
     // a host that uploaded a SPECULATIVE window (vt_group_enqueue_host) must redo that pass
     int32_t window_miss;
-    int32_t pad[2];
+    // template refresh (k_refresh.hip): refreshes since init - the stream's current template is buffer
+    // tpl_gen & 1 of a two-buffer store - and frames_done at the last one. Zero after init. They rewind and commit with
+    // the state they are part of.
+    int32_t tpl_gen;
+    int32_t tpl_frame;
 };
+static_assert(sizeof(StreamState) == 88, "StreamState layout");
 
 struct ModelDims {
     int patch, T, S, D, H, L, mlp, C, kpad;
@@ -265,6 +270,10 @@ hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* 
 // subset passes: slot i's template rows [nt][kpad] of the patch matrix <- the template store tpl[slot_stream[i]]
 hipError_t launch_gather_template_rows(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream, int n,
                                        const ModelDims& d, hipStream_t st);
+// the same from a store of TWO buffers per stream, tpl[B][2][nt][kpad] (engines with template refresh): a stream's rows are
+// those of buffer states[stream].tpl_gen & 1. slot_stream null: the identity (a full pass)
+hipError_t launch_gather_template_rows_gen(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream,
+                                           const StreamState* states, int n, const ModelDims& d, hipStream_t st);
 int preproc_tier_for_box(const ModelDims& d, float w, float h, bool is_template);
 
 hipError_t launch_nv12_to_rgb8(const uint8_t* nv12, int w, int h, uint8_t* rgb, hipStream_t st);
@@ -305,6 +314,32 @@ struct DecodeArgs {
     float success_threshold;
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t st);     // head_out_kernel + decode_kernel (two launches)
+
+// ---- template refresh (k_refresh.hip) ---------------------------------------------------------------------------------
+// per stream, device memory, written by the host only (never rewound) - but for the diagnostic counter
+struct RefreshPolicy {
+    int32_t period;             // 0: off, else 2..VT_REFRESH_MAX_PERIOD updates between refreshes
+    float min_score;            // a refresh needs result.score >= min_score
+    int32_t skipped_geometry;   // due refreshes skipped because the template crop left the sampled search crop
+    int32_t reserved;
+};
+#define VT_REFRESH_MAX_PERIOD 1000000
+struct RefreshArgs {
+    const FrameDesc* frames;    // [n] by slot: the frames of this pass
+    StreamState* states;        // [B] by stream, as decode / cand_commit left them
+    const vt_result* results;   // [n] by slot
+    const int32_t* slot_stream; // [n] slot -> stream, null: the identity
+    const int32_t* winner;      // candidate pass: [n] the winning slot of slot i's stream (only winners refresh); else null
+    RefreshPolicy* policy;      // [B] by stream
+    unsigned* tickets;          // [B] by slot, zero between launches
+    bf16_t* tpl;                // the two-buffer store [B][2][nt][kpad]
+    const PassOut* out;         // device copy of the pass's PassOut: host_states gets the two words too
+    StreamState* host_states;   // non-null: used instead of out->host_states (candidate passes: the commit's mirror)
+    int n;
+};
+// behind the decode (candidate pass: behind the commit): per slot the gate of DESIGN.md section 3 and, where it fires, the
+// template crop of this pass's frame at the committed box into the stream's other buffer + the state's two words
+hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int tier, bool any_layout, hipStream_t st);
 
 // The head's convolutions on the band kernel of k_head.hip: out[B*grid*grid][N] bf16 = relu(conv(in) + bias).
 // conv3x3: in [B*grid*grid][C] (ldin >= C), W [N][9*C] with column (ky*3+kx)*C + c, zero padding (zeros: >= 256 B

@@ -37,7 +37,7 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange};
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets};
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_cands) (void)hipHostFree(h_cands);
@@ -325,6 +325,7 @@ int Engine::alloc_buffers() {
     h_initialized.assign(B, 0);
     pass_n = B;                     // no pass yet: reads as a full pass (pass_streams is empty)
     known.assign((size_t)B, StreamState{});
+    h_policy.assign((size_t)B, RefreshPolicy{});
     HIPCHK(hipStreamSynchronize(stream));       // every fill has landed before the handle is handed out
     return VT_OK;
 }
@@ -430,7 +431,10 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     GemmArgs qkv = qkv_args(0);             // LayerNorm 1 is folded into the QKV GEMM
 
     // K1: crop + resize + normalise the search window of every stream -> patch rows
-    if (slot_stream)        // the slots' template rows from the store (a full pass finds them in place)
+    if (refresh_capable)    // every pass, from the stream's current buffer of the two-buffer store
+        L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
+          [&] { return launch_gather_template_rows_gen(d_tpl, d_patches, slot_stream, d_states, n, d, stream); });
+    else if (slot_stream)   // the slots' template rows from the store (a full pass finds them in place)
         L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
           [&] { return launch_gather_template_rows(d_tpl, d_patches, slot_stream, n, d, stream); });
     if (ps.cand)
@@ -546,6 +550,12 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     }
     if (ps.cand)
         L("cand_commit", 0, 2.0 * n * sizeof(StreamState), [&] { return launch_cand_commit(*ps.cand, stream); });
+    if (refresh_capable) {  // the streams' policies, on what the decode (the commit) left: k_refresh.hip
+        const RefreshArgs ra{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_policy,
+                             d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
+        L("refresh_template", 0, 2.0 * n * (sizeof(StreamState) + sizeof(vt_result)),
+          [&] { return launch_template_refresh(ra, d, ps.tier, ps.any_layout, stream); });
+    }
     if (lerr != hipSuccess)
         return set_err(VT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
@@ -680,7 +690,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
                           pix_any_layout(f->format)));
     // the stream's template rows, kept for the subset passes that run it in another slot (and for the full pass that
     // follows one: restore_segments puts every stream's rows back from here, these included)
-    HIPCHK(hipMemcpyAsync(d_tpl + (size_t)b * d.nt * d.kpad, d_patches + (size_t)b * d.ntok * d.kpad,
+    HIPCHK(hipMemcpyAsync(tpl_init_rows(b), d_patches + (size_t)b * d.ntok * d.kpad,
                           sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
     return VT_OK;
 }
@@ -704,6 +714,7 @@ int Engine::init_stream(int b, const vt_frame* f, vt_bbox box) {
 // After a subset pass the segments of d_patches hold other streams' template rows: one strided copy puts every stream's
 // rows back into its own segment before a full pass (its captured graph expects them in place).
 int Engine::restore_segments() {
+    if (refresh_capable) segments_moved = false;    // every pass gathers its rows: nothing is ever "in place"
     if (!segments_moved) return VT_OK;
     const size_t row = sizeof(bf16_t) * d.nt * d.kpad;
     HIPCHK(hipMemcpy2DAsync(d_patches, sizeof(bf16_t) * (size_t)d.ntok * d.kpad, d_tpl, row, row, (size_t)B,
@@ -805,6 +816,111 @@ int Engine::wait(vt_result* out, int n) {
         for (int b = 0; b < n; ++b) out[b] = h_results[b];
     if (host_seq == host_collected)                 // no pipelined pass owns the stream states
         for (int b = 0; b < B; ++b) known[b] = h_states_all[b];
+    return VT_OK;
+}
+
+// ---- template refresh --------------------------------------------------------------------------------
+
+int Engine::reset_refresh_tickets() {
+    if (d_tickets) HIPCHK(hipMemsetAsync(d_tickets, 0, sizeof(unsigned) * (size_t)B, stream));
+    return VT_OK;
+}
+
+// The first enabled policy: the store grows to two buffers per stream (buffer 0 = the rows init wrote), policy array
+// and tickets are allocated, and every graph is captured again with the gather and the refresh launch in it - here,
+// on the idle stream, never inside an update. Nothing changes on failure.
+int Engine::enable_refresh() {
+    if (refresh_capable) return VT_OK;
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    const size_t extra = refresh_bytes(), rows = (size_t)d.nt * d.kpad;
+    if (max_device_bytes && activation_bytes() + blob_bytes + extra > max_device_bytes)
+        return set_err(VT_ERR_OOM, "template refresh needs %.2f MiB more HBM for the second template buffers; "
+                       "vt_config.max_device_mib allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && extra > free_b)
+        return set_err(VT_ERR_OOM, "template refresh needs %.2f MiB more HBM; %.1f MiB are free", extra / 1048576.0,
+                       free_b / 1048576.0);
+    bf16_t* tpl2 = nullptr;
+    RefreshPolicy* pol = nullptr;
+    unsigned* tick = nullptr;
+    hipError_t he = dalloc0(&tpl2, 2 * rows * (size_t)B, stream);
+    if (he == hipSuccess) he = dalloc0(&pol, (size_t)B, stream);
+    if (he == hipSuccess) he = dalloc0(&tick, (size_t)B, stream);
+    if (he == hipSuccess)
+        he = hipMemcpy2DAsync(tpl2, 2 * rows * sizeof(bf16_t), d_tpl, rows * sizeof(bf16_t), rows * sizeof(bf16_t),
+                              (size_t)B, hipMemcpyDeviceToDevice, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) {
+        if (tpl2) (void)hipFree(tpl2);
+        if (pol) (void)hipFree(pol);
+        if (tick) (void)hipFree(tick);
+        return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "template refresh: %s", hipGetErrorString(he));
+    }
+    // the captured passes are those of an engine without refresh: drop them and capture again, as vt_group_set_tuning
+    // does. The old store is kept until the new passes exist: a failed capture puts everything back.
+    bf16_t* const tpl1 = d_tpl;
+    const bool moved = segments_moved;
+    d_tpl = tpl2; d_policy = pol; d_tickets = tick;
+    refresh_capable = true;
+    segments_moved = false;
+    drop_graphs();
+    if (int rc = capture_all_graphs()) {
+        char keep[512];
+        memcpy(keep, g_err, sizeof(keep));
+        drop_graphs();
+        d_tpl = tpl1; d_policy = nullptr; d_tickets = nullptr;
+        refresh_capable = false;
+        segments_moved = moved;
+        (void)hipFree(tpl2); (void)hipFree(pol); (void)hipFree(tick);
+        (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
+        memcpy(g_err, keep, sizeof(keep));
+        return rc;
+    }
+    (void)hipFree(tpl1);
+    return VT_OK;
+}
+
+int Engine::set_refresh(int s, int period, float min_score) {
+    if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "template refresh: stream %d out of range (-1..%d)", s, B - 1);
+    if (period < 0 || period == 1 || period > VT_REFRESH_MAX_PERIOD)
+        return set_err(VT_ERR_INVALID_ARG, "template refresh: period %d (0 = off, else 2..%d)", period, VT_REFRESH_MAX_PERIOD);
+    if (!std::isfinite(min_score) || min_score < 0.0f || min_score > 1.0f)
+        return set_err(VT_ERR_INVALID_ARG, "template refresh: min_score must be finite and in 0..1");
+    if (period > 0)
+        if (int rc = enable_refresh()) return rc;
+    const int s0 = s < 0 ? 0 : s, s1 = s < 0 ? B : s + 1;
+    if (refresh_capable) {      // period and min_score only: the diagnostic counter behind them is the device's
+        DEVICE_SCOPE(device);
+        HIPCHK(hipStreamSynchronize(stream));
+        for (int b = s0; b < s1; ++b) {
+            const RefreshPolicy p{period, min_score, 0, 0};
+            HIPCHK(hipMemcpy(d_policy + b, &p, 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        if (int rc = reset_refresh_tickets()) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    for (int b = s0; b < s1; ++b) { h_policy[(size_t)b].period = period; h_policy[(size_t)b].min_score = min_score; }
+    return VT_OK;
+}
+
+int Engine::refresh_stats(int s, vt_refresh_stats* out) {
+    if (!out) return set_err(VT_ERR_INVALID_ARG, "null argument");
+    if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "template refresh: stream %d out of range (0..%d)", s, B - 1);
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    memset(out, 0, sizeof(*out));
+    out->period = h_policy[(size_t)s].period;
+    out->min_score = h_policy[(size_t)s].min_score;
+    if (refresh_capable) {
+        RefreshPolicy p{};
+        HIPCHK(hipMemcpy(&p, d_policy + s, sizeof(p), hipMemcpyDeviceToHost));
+        out->skipped_geometry = p.skipped_geometry;
+    }
+    StreamState st{};
+    HIPCHK(hipMemcpy(&st, d_states + s, sizeof(st), hipMemcpyDeviceToHost));
+    out->generation = st.tpl_gen;
+    out->last_frame = st.tpl_frame;
     return VT_OK;
 }
 

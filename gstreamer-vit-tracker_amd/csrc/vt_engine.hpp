@@ -171,6 +171,21 @@ struct Engine {
     // slots' segments of d_patches, and the next full pass puts every segment back from here
     bf16_t* d_tpl = nullptr;
     bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
+    // template refresh (k_refresh.hip). The first policy that is enabled makes the engine
+    // refresh-capable for good: d_tpl becomes [B][2][nt][kpad] (a stream's rows: buffer tpl_gen & 1 of its state), every
+    // pass - full ones too - gathers its template rows from there and runs the refresh launch behind its decode.
+    // restore_segments / segments_moved are for engines that never enabled; those launch what they always did.
+    bool refresh_capable = false;
+    RefreshPolicy* d_policy = nullptr;            // [B] (capable engines)
+    std::vector<RefreshPolicy> h_policy;          // what the host set: period, min_score
+    unsigned* d_tickets = nullptr;                // [B] arrival counters of the refresh launch, zero between launches
+    int tpl_bufs() const { return refresh_capable ? 2 : 1; }
+    bf16_t* tpl_init_rows(int b) const { return d_tpl + (size_t)b * tpl_bufs() * d.nt * d.kpad; }   // buffer 0: init's
+    size_t refresh_bytes() const { return (size_t)B * (sizeof(bf16_t) * d.nt * d.kpad + sizeof(RefreshPolicy) + sizeof(unsigned)); }
+    int enable_refresh();                         // outside any update: second buffer, policy, tickets, graphs recaptured
+    int set_refresh(int stream, int period, float min_score);     // stream -1: all
+    int refresh_stats(int stream, vt_refresh_stats* out);
+    int reset_refresh_tickets();                  // wherever a pass may have been abandoned half-way
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)

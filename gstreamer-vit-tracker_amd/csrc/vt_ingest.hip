@@ -465,6 +465,8 @@ int vt_group_wait_next(vt_group* g, vt_result* out, int n) try {
             // bits depend on the pass size. Streams in neither pass are not touched.
             e->host_redos += 1;
             HIPCHK(hipStreamSynchronize(e->stream));
+            if (int rc = e->reset_refresh_tickets()) return rc;      // nothing is running: no half-counted refresh survives
+            // (a rewound tpl_gen names the stream's old template buffer again: a span holds at most one refresh of a stream)
             std::vector<char> rewind((size_t)e->B, 0);
             for (int s : sl.list) rewind[(size_t)s] = 1;
             if (has_younger)

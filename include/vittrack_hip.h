@@ -396,6 +396,44 @@ int vt_group_update_host_candidates(vt_group* g, const vt_candidate* cands, cons
  * finite or outside 1..32768), like vt_plan_engines. */
 int vt_scan_windows(int frame_w, int frame_h, float box_w, float box_h, int overlap_pct, float* boxes4, int cap);
 
+/* ---- template refresh ------------------------------------------------------------------------
+ * A stream's template is cut at init. With a refresh policy the DEVICE cuts it again, behind the decode and inside the
+ * pass - full, subset, candidate and pipelined passes alike - so a long-running stream follows its target's appearance
+ * without the host draining its pipeline for a re-init.
+ * Per stream: period (0 = off, else 2..1,000,000 updates) and min_score (finite, 0..1). After an update of the stream
+ * with result r that left the state st, the template is refreshed iff ALL of:
+ *   1. period >= 2;                      2. in a candidate pass: the slot is its stream's winner;
+ *   3. r.success and r.score >= min_score (a NaN score fails);
+ *   4. st.frames_done - last_frame >= period (last_frame: frames_done at the last refresh, 0 after init);
+ *   5. the pass's search crop met no window miss (a speculative pipelined pass that will be redone never refreshes;
+ *      its redo does);
+ *   6. the tap rectangle of the template crop (factor 2, side template_size) at the new box lies inside the tap
+ *      rectangle of the search crop the pass sampled; per axis, in binary32, lo = floor(0.5*scale + x0) and
+ *      hi = floor((size - 0.5)*scale + x0) + 1. A due refresh that fails only this is counted in skipped_geometry
+ *      (a diagnostic: a redone pass may count twice) and tried again at the stream's next update.
+ *   7. the in-frame part of that template rectangle lies inside the window the pass's frame stores. Whole frames and the
+ *      windows the library cuts for the stream's own box always do; a speculative pipelined window that does not is
+ *      reported as a window miss, so the pass is redone with an exact window and the redo refreshes.
+ * A refresh is exactly vt_group_init_*(stream, the whole frame of that update, r.bbox) as far as the template goes -
+ * the same rows, bit for bit, taps outside the frame black - but box, counters and the rest of the state stay as the
+ * update left them; generation += 1, last_frame = frames_done. The next pass runs on the new template.
+ * The first call that enables a policy on an engine makes it refresh-capable for good: it allocates a second template
+ * buffer per stream (within vt_config.max_device_mib, else VT_ERR_OOM and nothing changes) and recaptures the engine's
+ * graphs; from then on every pass of that engine carries one gather and one refresh launch. Engines that never
+ * enable launch what they always did.
+ * stream -1: every stream of the group. VT_ERR_INVALID_ARG (nothing changed) on a bad stream, period 1, a negative
+ * period or one above 1,000,000, min_score not finite or outside 0..1, and while a pipelined host pass is outstanding.
+ * vt_group_read_tensor "template" returns the rows the stream's next pass will use. */
+typedef struct vt_refresh_stats {   /* 32 bytes */
+    int32_t period; float min_score;
+    int32_t generation, last_frame;      /* refreshes since init; frames_done at the last one */
+    int32_t skipped_geometry; int32_t reserved[3];
+} vt_refresh_stats;
+int vt_set_template_refresh(vt_tracker* t, int period, float min_score);
+int vt_template_refresh_stats(vt_tracker* t, vt_refresh_stats* out);
+int vt_group_set_template_refresh(vt_group* g, int stream /* -1: all */, int period, float min_score);
+int vt_group_template_refresh_stats(vt_group* g, int stream, vt_refresh_stats* out);
+
 /* ---- dma-buf ingest ------------------------------------------------------------------------
  * The reference's capture side can hand out dma-bufs (v4l2src io-mode=dmabuf, src/pipeline_ir.rs:24)
  * but then maps them on the CPU (src/pipeline.rs:95-101). vt_import_dmabuf maps a dma-buf fd into
@@ -539,8 +577,9 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * "rowstat" [N,2] (row terms of the last folded LayerNorm), "attn" [N,D] (last block's attention output),
  * "feat" [Ns,D], "head_t3" [Ns,C], "head_out" [Ns,8] (score,ox,oy,w,h logits),
  * "state" (the stream's device state record as raw 32-bit words), "graph_replays" [3] (passes replayed so far
- * per crop-buffer tier: which of the captured graphs ran). After a subset pass (vt_group_*_streams) every
- * tensor but "state" and "graph_replays" is that of the stream's slot in it; a stream that was not in the pass
+ * per crop-buffer tier: which of the captured graphs ran), "template" [Nt,Kpad] (the stream's current template rows in
+ * the template store: what its next pass will use). After a subset pass (vt_group_*_streams) every
+ * tensor but "state", "template" and "graph_replays" is that of the stream's slot in it; a stream that was not in the pass
  * returns VT_ERR_INVALID_ARG. After a candidate pass (vt_group_update_*_candidates) the stream's slot is its WINNING
  * slot. A per-pass tensor name prefixed with "slot." ("slot.head_out", ...) takes `stream` as a SLOT index of the last
  * pass instead: the way to a losing slot's tensors.
