@@ -118,6 +118,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16", "vt_op_gemm_bench", "vt_op_qkv_bf16", "vt_op_attention_bf16",
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
+    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16",
 ]
 
 
@@ -249,6 +250,10 @@ def ops_lib():
     L.vt_op_qkv_bf16.argtypes = [c_int, u16p, u16p, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, fp]
     L.vt_op_attention_bf16.argtypes = [c_int, u16p, u16p, u16p, fp, c_int, c_int, c_int, c_int]
     L.vt_op_attention_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, fp]
+    L.vt_op_attention_queries_bf16.argtypes = [c_int, u16p, u16p, u16p, fp, c_int, c_int, c_int, c_int, c_int]
+    i8p = POINTER(ctypes.c_int8)
+    L.vt_op_gemm_resid_seg_bf16.argtypes = [c_int, u16p, u16p, fp, u16p, i8p, c_int, u16p, i8p, fp, fp, c_int, c_int, c_int,
+                                            c_int, c_int, c_float, c_int]
     L.vt_op_layernorm.argtypes = [c_int, fp, fp, fp, fp, c_int, c_int]
     L.vt_op_conv3x3_relu_bf16.argtypes = [c_int, u16p, u16p, fp, fp, c_int, c_int, c_int, c_int, c_int]
     L.vt_op_nv12_to_rgb8_bench.argtypes = [c_int, c_int, c_int, c_int, fp]
@@ -1063,6 +1068,36 @@ def op_attention_bf16(q_bits, k_bits, v_bits, B, N, H, device=0, mode=-1):
     _check_op(ops_lib().vt_op_attention_bf16(device, _u16(q_bits), _u16(k_bits), _u16(v_bits), _f32(out),
                                       B, N, H, mode))
     return out
+
+
+def op_attention_queries(q_bits, k_bits, v_bits, B, N, H, q0, nq, device=0):
+    """vt_op_attention_queries_bf16: attention mode 3 on the queries q0 .. q0 + nq - 1 of every stream -> [B * nq, H * 64]"""
+    q_bits, k_bits, v_bits = (np.ascontiguousarray(x, np.uint16) for x in (q_bits, k_bits, v_bits))
+    out = np.empty((B * nq, H * 64), np.float32)
+    _check_op(ops_lib().vt_op_attention_queries_bf16(device, _u16(q_bits), _u16(k_bits), _u16(v_bits), _f32(out),
+                                                     B, N, H, int(q0), int(nq)))
+    return out
+
+
+def op_gemm_resid_seg(a_bits, w_bits, bias, xh_bits, xl_lo8, M, seg_rows=0, seg_skip=0, eps=1e-6, lo_shift=12, device=0):
+    """vt_op_gemm_resid_seg_bf16: the residual GEMM of the 256x256 kernel on the stored pair xh_bits (uint16) / xl_lo8 (int8)
+    [rows_in, N], output row m taking its addend from input row m + (m // seg_rows + 1) * seg_skip (seg_rows = 0: rows
+    0 .. M-1, in place) -> (xh [M, N] uint16, xl [M, N] int8, chunk partials [M, N // 32, 2], row terms [M, 2])"""
+    a_bits = np.ascontiguousarray(a_bits, np.uint16)
+    w_bits = np.ascontiguousarray(w_bits, np.uint16)
+    xh = np.ascontiguousarray(xh_bits, np.uint16)
+    xl = np.ascontiguousarray(xl_lo8, np.int8)
+    K, N = a_bits.shape[1], w_bits.shape[0]
+    assert a_bits.shape[0] == M and xh.shape == xl.shape and xh.shape[1] == N
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    oh, ol = np.empty((M, N), np.uint16), np.empty((M, N), np.int8)
+    cst, ro = np.empty((M, N // 32, 2), np.float32), np.empty((M, 2), np.float32)
+    i8p = POINTER(ctypes.c_int8)
+    _check_op(ops_lib().vt_op_gemm_resid_seg_bf16(device, _u16(a_bits), _u16(w_bits), _f32(b) if b is not None else None,
+                                                  _u16(xh), xl.ctypes.data_as(i8p), xh.shape[0], _u16(oh),
+                                                  ol.ctypes.data_as(i8p), _f32(cst), _f32(ro), M, N, K, int(seg_rows),
+                                                  int(seg_skip), c_float(eps), int(lo_shift)))
+    return oh, ol, cst, ro
 
 
 def op_attention_bench(B, N, H, mode=-1, iters=30, device=0) -> float:

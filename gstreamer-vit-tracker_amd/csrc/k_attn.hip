@@ -438,14 +438,19 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
 // two lane halves added once at the end) instead of a third P.V MFMA against a tile of ones - 4 of the 20
 // MFMAs of a step; without the running-maximum bookkeeping the step is bound by the matrix pipe, not by
 // vector issue (profiles/r03_attention_ab.txt).
-template <bool CAREFUL>
+// SUBQ: the queries are tokens q0 .. q0 + nq - 1 of every stream only (keys and values: all `tokens`, in the same tile
+// order, with the same half-last-tile rule - a query sees the arithmetic it sees in the full kernel) and the output is
+// compact, row b * nq + (q - q0). Without it q0 = 0 and nq = tokens are compile-time facts: the code of the full kernel.
+template <bool CAREFUL, bool SUBQ>
 __device__ __forceinline__ bool at3_pass(char* smem, const bf16_t* __restrict__ qk, const bf16_t* __restrict__ vt,
-                                         bf16_t* __restrict__ out, int tokens, int H, int npad, int tid, int block) {
+                                         bf16_t* __restrict__ out, int tokens, int H, int npad, int tid, int block,
+                                         int q0_, int nq_) {
+    const int q0 = SUBQ ? q0_ : 0, nq = SUBQ ? nq_ : tokens;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
     const int D = H * 64, ld = 2 * D;
-    const int nqb = (tokens + 31) >> 5, nxb = (nqb + 3) >> 2;
+    const int nqb = (nq + 31) >> 5, nxb = (nqb + 3) >> 2;
     // Workgroups are dealt round-robin over the 8 XCDs. The nxb query blocks of one (stream, head)
     // read the same K and Vt (184 KB at 720 tokens): give each XCD a contiguous run of the 1-D grid
     // so that they share one L2 instead of pulling the head's K/Vt into six of them (measured
@@ -461,8 +466,8 @@ __device__ __forceinline__ bool at3_pass(char* smem, const bf16_t* __restrict__ 
 
     f32x16_t o0, o1;
     constexpr bool careful = CAREFUL;
-    const int q = qb * 32 + l31;
-    const int qc = q < tokens ? q : tokens - 1;     // idle rows repeat the last query, never stored
+    const int q = q0 + qb * 32 + l31;
+    const int qc = q < q0 + nq ? q : q0 + nq - 1;   // idle rows repeat the last query, never stored
     const bf16_t* qrow = qk + ((size_t)b * tokens + qc) * ld + h * 64 + half * 8;
     bf16x8_t qf[4];
 #pragma unroll
@@ -686,9 +691,9 @@ __device__ __forceinline__ bool at3_pass(char* smem, const bf16_t* __restrict__ 
         for (int it = 0; it < 4; ++it) {
             const int r = it * 8 + (lane >> 3), c = lane & 7;
             const uint4 v = *reinterpret_cast<const uint4*>(ow + r * 128 + ((c ^ (r & 7)) << 4));
-            const int qq = qb * 32 + r;
-            if (qb < nqb && qq < tokens)
-                *reinterpret_cast<uint4*>(out + ((size_t)b * tokens + qq) * D + h * 64 + c * 8) = v;
+            const int qq = qb * 32 + r;             // query index from q0 = row inside the stream's nq output rows
+            if (qb < nqb && qq < nq)
+                *reinterpret_cast<uint4*>(out + ((size_t)b * nq + qq) * D + h * 64 + c * 8) = v;
         }
     }
     return false;
@@ -701,7 +706,7 @@ __global__ __launch_bounds__(256, 3) void attention_dma_kernel(const bf16_t* __r
     __shared__ __attribute__((aligned(16))) char smem[AT3_NS * AT3_STAGE];
     // launch bound of 3 waves per SIMD: the first pass fits 168 registers without a spill; what hipcc then spills
     // (100 B of scratch) sits in the rare second pass only (checked in the ISA)
-    if (at3_pass<false>(smem, qk, vt, out, tokens, H, npad, (int)threadIdx.x, (int)blockIdx.x)) {
+    if (at3_pass<false, false>(smem, qk, vt, out, tokens, H, npad, (int)threadIdx.x, (int)blockIdx.x, 0, 0)) {
         __syncthreads();
         // the (rare) second pass rebuilds every address from opaque copies of its inputs: if the
         // compiler could see that the two inlined passes compute the same values it would keep the
@@ -710,7 +715,31 @@ __global__ __launch_bounds__(256, 3) void attention_dma_kernel(const bf16_t* __r
         const bf16_t* q2 = qk; const bf16_t* v2 = vt; bf16_t* o2 = out;
         asm volatile("" : "+v"(t2));
         asm volatile("" : "+s"(b2), "+s"(tk), "+s"(hh), "+s"(np2), "+s"(q2), "+s"(v2), "+s"(o2));
-        at3_pass<true>(smem, q2, v2, o2, tk, hh, np2, t2, b2);
+        at3_pass<true, false>(smem, q2, v2, o2, tk, hh, np2, t2, b2, 0, 0);
+    }
+}
+
+// The same kernel on the queries q0 .. q0 + nq - 1 of every stream, output compact [B * nq][D] (at3_pass, SUBQ): the last
+// encoder block, behind which nobody reads the template rows. An entry of its own, so that the kernel of the other
+// blocks keeps its code and its budget of three waves per SIMD.
+// WHAT DIFFERS from the full kernel: whether the unchecked first pass is kept or repeated as the careful one is decided
+// per workgroup of 128 queries, and the groups are cut from q0 here, not from token 0. While every query's scores stay
+// inside the +-32 window (ATT_WIN) the two passes are the same arithmetic, so a query's output is the same bits whichever
+// group it falls into; outside the window a query may take the other pass than it takes in the full kernel (both are
+// softmax(q k^T) v to the kernel's accuracy, they differ in rounding).
+__global__ __launch_bounds__(256, 3) void attention_dma_q_kernel(const bf16_t* __restrict__ qk,
+                                                              const bf16_t* __restrict__ vt,
+                                                              bf16_t* __restrict__ out, int tokens,
+                                                              int H, int npad, int q0, int nq) {
+    __shared__ __attribute__((aligned(16))) char smem[AT3_NS * AT3_STAGE];
+    if (at3_pass<false, true>(smem, qk, vt, out, tokens, H, npad, (int)threadIdx.x, (int)blockIdx.x, q0, nq)) {
+        __syncthreads();
+        // opaque copies, as above
+        int t2 = threadIdx.x, b2 = blockIdx.x, tk = tokens, hh = H, np2 = npad, qa = q0, qn = nq;
+        const bf16_t* q2 = qk; const bf16_t* v2 = vt; bf16_t* o2 = out;
+        asm volatile("" : "+v"(t2));
+        asm volatile("" : "+s"(b2), "+s"(tk), "+s"(hh), "+s"(np2), "+s"(q2), "+s"(v2), "+s"(o2), "+s"(qa), "+s"(qn));
+        at3_pass<true, true>(smem, q2, v2, o2, tk, hh, np2, t2, b2, qa, qn);
     }
 }
 
@@ -748,6 +777,15 @@ hipError_t launch_attention_mode(const bf16_t* qk, const bf16_t* vt, bf16_t* out
     } else {
         return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// mode 3 on the queries q0 .. q0 + nq - 1 of every stream: out is compact, [B * nq][H * 64]
+hipError_t launch_attention_queries(const bf16_t* qk, const bf16_t* vt, bf16_t* out, int B, int tokens, int H, int npad,
+                                    int q0, int nq, hipStream_t st) {
+    if (npad % 64 != 0 || tokens % 4 != 0 || q0 < 0 || nq < 1 || q0 + nq > tokens) return hipErrorInvalidValue;
+    const int nqb = (nq + 31) / 32;
+    vt_launch(attention_dma_q_kernel, dim3(((nqb + 3) / 4) * H * B), dim3(256), 0, st, qk, vt, out, tokens, H, npad, q0, nq);
     return hipGetLastError();
 }
 

@@ -902,6 +902,8 @@ hipError_t launch_gemm_cfg(const GemmArgs& a, int epilogue, int cfg, hipStream_t
         return hipErrorInvalidValue;
     if (!x_epi && (!a.bias || ((a.rowstat || a.cstat_in) && !a.colsum))) return hipErrorInvalidValue;
     if (a.cstat_in && (cfg > GEMM_CFG_SMALL_MAX || a.rowstat || (a.K % (4 * VT_STAT_CHUNK)) != 0 || a.K > 1024)) return hipErrorInvalidValue;
+    // the remapped addend read of EPI_RESID (GemmArgs.seg_rows, Xh_in) exists in the 256x256 kernel only
+    if (gemm_addend_remapped(a) && cfg < GEMM_CFG_256_MIN) return hipErrorInvalidValue;
     if (cfg == GEMM_CFG_256P4) return launch_gemm256(a, epilogue, false, st);
     if (cfg == GEMM_CFG_256PP) return launch_gemm256(a, epilogue, true, st);
     switch (epilogue) {

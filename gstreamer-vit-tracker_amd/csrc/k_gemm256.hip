@@ -225,7 +225,10 @@ __device__ __forceinline__ void g256_mainloop2(const GemmArgs& p, char* smem, in
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int EPI>
+// REMAP (EPI_RESID only): the addend pair is p.Xh_in / p.Xl_in and, with p.seg_rows > 0, its rows are those of a
+// layout with p.seg_skip unread rows in front of every segment of p.seg_rows rows (GemmArgs, vt_common.hpp). A template
+// parameter, so that every other X-epilogue launch runs the very code it ran before the remap existed.
+template <int EPI, bool REMAP = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tiles_n = p.N >> 8;
@@ -303,11 +306,17 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
                 // rows past M read a valid row (value unused): the pair's base clamped on the scalar side, the
                 // second row folded onto the first where it alone is past M
                 const int mu = row_u(i, it), mc = mu < p.M ? mu : p.M - 1;
-                const size_t ro = (size_t)mc * p.ldx * 2;
+                // REMAP: the uniform row's place in the input layout (scalar arithmetic; mc is even or the last row,
+                // seg_rows is even: both rows of the pair lie in the same segment)
+                int mi = mc;
+                if constexpr (REMAP) { if (p.seg_rows > 0) mi = mc + (int)((uint32_t)mc / (uint32_t)p.seg_rows + 1u) * p.seg_skip; }
+                const size_t ro = (size_t)mi * p.ldx * 2;
                 const uint32_t lo_ = (mc + 1 < p.M) ? lane_off : lane_off0;
-                a0 = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.Xh) + ro + lo_);
+                const char* const xh_in = reinterpret_cast<const char*>(REMAP ? p.Xh_in : p.Xh);
+                const char* const xl_in = reinterpret_cast<const char*>(REMAP ? p.Xl_in : p.Xl);
+                a0 = *reinterpret_cast<const u32x4_t*>(xh_in + ro + lo_);
                 // the lo8 plane: one byte per element, the same (row, column) at half the byte offset: 8 B per lane
-                const u32x2_t l8 = *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const char*>(p.Xl) + (ro >> 1) + (lo_ >> 1));
+                const u32x2_t l8 = *reinterpret_cast<const u32x2_t*>(xl_in + (ro >> 1) + (lo_ >> 1));
                 a1 = u32x4_t{l8[0], l8[1], 0u, 0u};
             } else if constexpr (EPI == EPI_F32_POS) {
                 const int m = out_row(i, it);
@@ -1119,16 +1128,16 @@ hipError_t launch_persistent(const GemmArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int EPI>
+template <int EPI, bool REMAP = false>
 hipError_t prepare_one() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI, REMAP>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS);
 }
 
-template <int EPI>
+template <int EPI, bool REMAP = false>
 hipError_t launch_one(const GemmArgs& a, hipStream_t st) {
     const int tiles = ((a.M + 255) / 256) * (a.N / 256);
-    vt_launch((gemm256_kernel<EPI>), dim3(tiles), dim3(512), G256_LDS, st, a);
+    vt_launch((gemm256_kernel<EPI, REMAP>), dim3(tiles), dim3(512), G256_LDS, st, a);
     return hipGetLastError();
 }
 
@@ -1143,6 +1152,7 @@ hipError_t gemm256_prepare() {
     hipError_t e;
     if ((e = prepare_one<EPI_F32_POS>()) != hipSuccess) return e;
     if ((e = prepare_one<EPI_RESID>()) != hipSuccess) return e;
+    if ((e = prepare_one<EPI_RESID, true>()) != hipSuccess) return e;
     if ((e = prepare_one<EPI_GELU_BF16>()) != hipSuccess) return e;
     if ((e = prepare_one<EPI_RELU_BF16>()) != hipSuccess) return e;
     if ((e = prepare_one<EPI_QKV>()) != hipSuccess) return e;
@@ -1160,6 +1170,9 @@ bool gemm256_fits(const GemmArgs& a, int epilogue) {
     if ((long long)a.M * a.lda * 2 >= VT_GEMM256_MAX_OPERAND_BYTES || (long long)a.N * a.ldw * 2 >= VT_GEMM256_MAX_OPERAND_BYTES)
         return false;
     if ((a.lda & 7) || (a.ldw & 7) || a.conv_grid > 0) return false;
+    if (gemm_addend_remapped(a) &&      // the remapped addend read: EPI_RESID, even segments (row pairs stay inside one)
+        (epilogue != EPI_RESID || a.seg_rows < 0 || a.seg_skip < 0 || (a.seg_rows & 1) || (a.seg_skip > 0 && a.seg_rows == 0)))
+        return false;
     switch (epilogue) {
         case EPI_F32_POS:
         case EPI_RESID:
@@ -1190,7 +1203,14 @@ hipError_t launch_gemm256(const GemmArgs& a, int epilogue, bool persistent, hipS
     }
     switch (epilogue) {
         case EPI_F32_POS: return launch_one<EPI_F32_POS>(a, st);
-        case EPI_RESID: return launch_one<EPI_RESID>(a, st);
+        case EPI_RESID:
+            if (gemm_addend_remapped(a)) {      // a kernel of its own: the in-place launches keep their code
+                GemmArgs r = a;
+                if (!r.Xh_in) r.Xh_in = r.Xh;
+                if (!r.Xl_in) r.Xl_in = r.Xl;
+                return launch_one<EPI_RESID, true>(r, st);
+            }
+            return launch_one<EPI_RESID>(a, st);
         case EPI_GELU_BF16: return launch_one<EPI_GELU_BF16>(a, st);
         case EPI_RELU_BF16: return launch_one<EPI_RELU_BF16>(a, st);
         case EPI_QKV: return launch_one<EPI_QKV>(a, st);

@@ -360,6 +360,7 @@ int vt_group_set_tuning(vt_group* g, const char* key, int value) try {
     HIPCHK(hipStreamSynchronize(e->stream));
     const std::string k = key;
     if (k == "head_band") e->head_band_kernel = value < 0 ? 2 : value;   // 0 / 1 / 2, see Engine::head_band_kernel
+    else if (k == "last_rows") e->last_rows = value != 0;        // 0: the last block runs all rows; else (default) the search rows where eligible
     else if (k == "crop_tier") e->crop_tier_forced = value;      // < 0: chosen per pass from the known boxes (default)
     else return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key);
     // the captured passes hold the old choice: drop them and capture again here, not inside the next pass
@@ -472,16 +473,37 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
     size_t b = (size_t)stream;
     if (n.rfind("slot.", 0) == 0) {     // "slot.<tensor>": `stream` IS a slot of the last pass (the losing slots of a candidate pass)
         n = n.substr(5);
-        if (n == "state" || n == "template" || n == "graph_replays" || stream >= e->pass_n)
+        if (n == "state" || n == "template" || n == "graph_replays" || n == "last_block_rows" || stream >= e->pass_n)
             return set_err(VT_ERR_INVALID_ARG, "read_tensor: '%s' of slot %d: no such slot tensor in the last pass", name, stream);
-    } else if (n != "state" && n != "template" && n != "graph_replays") {
+    } else if (n != "state" && n != "template" && n != "graph_replays" && n != "last_block_rows") {
         const int slot = e->slot_of(stream);
         if (slot < 0) return set_err(VT_ERR_INVALID_ARG, "read_tensor: stream %d was not in the last pass", stream);
         b = (size_t)slot;
     }
     if (n == "patches") return copy_out_bf16(e->d_patches + b * d.ntok * d.kpad, (int64_t)d.ntok * d.kpad, out, capacity);
+    if (n == "last_block_rows") {      // rows per slot the last block of the last pass computed: ns (search rows only) or ntok
+        if (!out) return 1;
+        if (capacity < 1) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        out[0] = (float)(e->pass_compact ? d.ns : d.ntok);
+        return 1;
+    }
+    // A compacted pass (Engine::pass_compact) left the last block's tensors compact, search rows only. The whole-layout
+    // names keep their shapes: "x" / "xrange" after the search rows have been copied to their places (the template rows
+    // hold what block L-2 left), "attn" / "rowstat" with zero template rows.
+    if (e->pass_compact && (n == "x" || (n == "xrange" && !(e->taps && e->d_taps))))
+        if (int rc = e->expand_last_block()) return rc;
+    if (e->pass_compact && (n == "attn" || n == "rowstat")) {
+        const bool at = n == "attn";
+        const int64_t w = at ? d.D : 2, count = (int64_t)d.ntok * w, head = (int64_t)d.nt * w;
+        if (!out) return count;
+        if (capacity < count) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity %lld < %lld", (long long)capacity, (long long)count);
+        memset(out, 0, sizeof(float) * (size_t)head);
+        const int64_t rc = at ? copy_out_bf16(e->d_attn + b * d.ns * d.D, (int64_t)d.ns * w, out + head, count - head)
+                              : copy_out_f32((const float*)(e->d_rstat + b * d.ns), (int64_t)d.ns * w, out + head, count - head);
+        return rc < 0 ? rc : count;
+    }
     if (n == "feat" && e->feat_in_head) {       // the pass normalised the rows inside the head's first kernel: same arithmetic, now
-        HIPCHK(e->final_layernorm(e->pass_n));        // as a launch (the residual stream of the last pass is still in place)
+        HIPCHK(e->final_layernorm(e->pass_n, e->pass_compact));     // as a launch (the residual stream of the last pass is still in place)
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     if (n == "feat") return copy_out_bf16(e->d_feat + b * d.ns * d.D, (int64_t)d.ns * d.D, out, capacity);

@@ -195,7 +195,19 @@ struct GemmArgs {
     // epilogues with M < N: column tiles), 1: row panels x all columns, 2: column tiles x all rows
     int tile_order;
     LoQuant lq;                   // X-epilogues: the pair's quantum (the engine's lo_shift; default 12)
+    // EPI_RESID on the 256x256 kernel only (anything else refuses them: hipErrorInvalidValue): the residual ADDEND is
+    // read from another pair than the one written (null: Xh / Xl, read then written in place), and, with seg_rows > 0,
+    // from a layout that has seg_skip rows nobody computes in front of every segment of seg_rows rows: output row m
+    // takes its addend from input row m + (m / seg_rows + 1) * seg_skip. seg_rows is even (a row pair never straddles
+    // two segments). Writes, chunk partials, the panel ticket and the row terms stay at row m. The last encoder block
+    // on search rows only: seg_rows = ns, seg_skip = nt (vt_engine.hip, run_pass).
+    const bf16_t* Xh_in; const uint8_t* Xl_in;
+    int seg_rows, seg_skip;
 };
+// the arguments ask for the remapped / out-of-place addend read of EPI_RESID
+inline bool gemm_addend_remapped(const GemmArgs& a) {
+    return a.seg_rows != 0 || a.seg_skip != 0 || (a.Xh_in && a.Xh_in != a.Xh) || (a.Xl_in && a.Xl_in != a.Xl);
+}
 
 hipError_t launch_gemm(const GemmArgs& a, int epilogue, hipStream_t st);
 // true: launch_gemm() will run an X-epilogue of these arguments on the 256x256 kernel, whose row panels
@@ -258,6 +270,12 @@ __host__ __device__ inline int attn_perm16(int t) { return (t & ~12) | ((t & 4) 
 hipError_t attention_prepare();   // once per device, before the first launch / any stream capture
 hipError_t launch_attention_mode(const bf16_t* qk, const bf16_t* vt, bf16_t* out, int B, int tokens,
                                  int H, int npad, int mode, hipStream_t st);
+
+// mode 3 (tokens % 4 == 0, npad % 64 == 0) on the queries q0 .. q0 + nq - 1 of every stream only, keys and values all
+// `tokens`: out is compact, [B * nq][H * 64], row b * nq + (q - q0). Same bits as those rows of launch_attention_mode(3)
+// while every query's scores stay inside the kernel's +-32 window (k_attn.hip, attention_dma_q_kernel)
+hipError_t launch_attention_queries(const bf16_t* qk, const bf16_t* vt, bf16_t* out, int B, int tokens, int H, int npad,
+                                    int q0, int nq, hipStream_t st);
 
 // crop + bilinear + normalise -> patch rows; one launch covers slots [b0, b0+nb)
 // tier: the tile kernel's LDS buffer (0: 16 KiB, 1: 32 KiB, 2 or more: 64 KiB), a choice of speed only

@@ -330,6 +330,8 @@ int Engine::alloc_buffers() {
     return VT_OK;
 }
 
+// the algorithmic count, every block on all ntok rows: the last block on search rows only (last_block_compact) does not
+// change it - what the benchmark divides by stays what it was
 double Engine::flops_encoder() const {
     const double n = d.ntok, D = d.D;
     const double per_layer = 2 * n * D * 3 * D + 2 * n * D * D + 4 * n * D * d.mlp + 4 * n * n * D;
@@ -400,7 +402,8 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     // rowstat or cstat_in set accordingly.
     auto xgemm = [&](int epi, GemmArgs a, GemmArgs* consumer, int consumer_epi) {
         const bool stats = consumer != nullptr;
-        a.Xh = d_xh; a.Xl = d_xl; a.ldx = D;
+        if (!a.Xh) { a.Xh = d_xh; a.Xl = d_xl; }    // the compacted last block names its own pair
+        a.ldx = D;
         a.cstat = stats ? d_cstat : nullptr;
         a.rowstat_out = stats ? d_rstat : nullptr;
         a.panel_cnt = d_panel_cnt;
@@ -416,8 +419,8 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         }
         consumer->rowstat = d_rstat;
         if (!fused)
-            L("rowstat", 0, (double)M * (nchunk + 1) * 8,
-              [&] { return launch_rowstat_finalize(d_cstat, d_rstat, M, nchunk, d.ln_eps, stream); });
+            L("rowstat", 0, (double)a.M * (nchunk + 1) * 8,
+              [&] { return launch_rowstat_finalize(d_cstat, d_rstat, a.M, nchunk, d.ln_eps, stream); });
     };
     auto qkv_args = [&](int l) {
         const LayerW& w = layers[l];
@@ -455,23 +458,33 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     for (int l = 0; l < d.L; ++l) {
         const LayerW& w = layers[l];
         gemm(EPI_QKV, qkv);
-        L("attention", 4.0 * n * (double)d.ntok * d.ntok * D, (double)M * D * 8, [&] {
-            return launch_attention(d_qk, d_vt, d_attn, n, d.ntok, d.H, d.npad, stream);
+        // The last block of a compacted pass (vt_engine.hpp, last_block_compact): the search queries only, from here on
+        // every buffer is compact - Ml = n * ns rows - and the kernels behind the attention are the ordinary ones
+        const bool cl = ps.compact && l == d.L - 1;
+        const int Ml = cl ? Ms : M, rows = cl ? d.ns : d.ntok;
+        L(cl ? "attention_search" : "attention", 4.0 * n * (double)rows * d.ntok * D, ((double)M * 6 + (double)Ml * 2) * D, [&] {
+            return cl ? launch_attention_queries(d_qk, d_vt, d_attn, n, d.ntok, d.H, d.npad, d.nt, d.ns, stream)
+                      : launch_attention(d_qk, d_vt, d_attn, n, d.ntok, d.H, d.npad, stream);
         });
         {
             GemmArgs a{};
             a.A = d_attn; a.lda = D; a.W = w.proj_w; a.ldw = D; a.bias = w.proj_b;
-            a.M = M; a.N = D; a.K = D;
+            a.M = Ml; a.N = D; a.K = D;
+            if (cl) {       // addend: the whole-layout pair, search rows through the remap; output: the compact pair (d_qk is dead)
+                a.Xh = xc_hi(); a.Xl = xc_lo();
+                a.Xh_in = d_xh; a.Xl_in = d_xl; a.seg_rows = d.ns; a.seg_skip = d.nt;
+            }
             GemmArgs f{};                   // LayerNorm 2 is folded into fc1
-            f.A = d_xh; f.lda = D; f.W = w.fc1_wf; f.ldw = D; f.bias = w.fc1_c; f.colsum = w.fc1_cs;
-            f.M = M; f.N = d.mlp; f.K = D; f.Cb = d_mlp; f.ldcb = d.mlp;
+            f.A = cl ? xc_hi() : d_xh; f.lda = D; f.W = w.fc1_wf; f.ldw = D; f.bias = w.fc1_c; f.colsum = w.fc1_cs;
+            f.M = Ml; f.N = d.mlp; f.K = D; f.Cb = d_mlp; f.ldcb = d.mlp;
             xgemm(EPI_RESID, a, &f, EPI_GELU_BF16);      // + the row terms of LayerNorm 2
             gemm(EPI_GELU_BF16, f);
         }
         {
             GemmArgs a{};
             a.A = d_mlp; a.lda = d.mlp; a.W = w.fc2_w; a.ldw = d.mlp; a.bias = w.fc2_b;
-            a.M = M; a.N = D; a.K = d.mlp;
+            a.M = Ml; a.N = D; a.K = d.mlp;
+            if (cl) { a.Xh = xc_hi(); a.Xl = xc_lo(); }
             if (l + 1 < d.L) {              // + the next block's LayerNorm 1 (the final LayerNorm reads the rows itself)
                 qkv = qkv_args(l + 1);
                 xgemm(EPI_RESID, a, &qkv, EPI_QKV);
@@ -485,7 +498,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     // first layer normalises its rows itself (k_head.hip, LNC)
     const bool band = head_band(), ln_fused = head_ln_fused();
     if (!ln_fused)
-        L("layernorm", 0, (double)Ms * D * 6, [&] { return final_layernorm(n); });
+        L("layernorm", 0, (double)Ms * D * 6, [&] { return final_layernorm(n, ps.compact); });
     // centre head: 1x1 conv, three 3x3 convs, then the f32 5-logit layer + decode. On the band kernel of
     // k_head.hip (the A image of a band resident in LDS, logits + decode fused behind the last layer: 4 launches)
     // where the shape allows it, else as implicit GEMMs on the 4-wave kernel + head_out + decode (6 launches).
@@ -509,6 +522,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
             h.in = nullptr;
             h.xh = d_xh; h.xl = d_xl; h.ln_g = (const float*)find("norm_g")->ptr; h.ln_b = (const float*)find("norm_b")->ptr;
             h.ln_eps = d.ln_eps; h.in_stride = d.ntok; h.in_off = d.nt; h.lo_q = lq.q;
+            if (ps.compact) { h.xh = xc_hi(); h.xl = xc_lo(); h.in_stride = d.ns; h.in_off = 0; }
         }
         L(prof ? (ln_fused ? "head_ln_conv1x1" : "head_conv1x1") : "", 2.0 * Ms * d.C * D,
           2.0 * ((double)Ms * D * (ln_fused ? 2 : 1) + (double)d.C * D + (double)Ms * d.C),
@@ -561,14 +575,36 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
 }
 
-hipError_t Engine::final_layernorm(int n) {
-    return launch_layernorm_split(d_xh, d_xl, (const float*)find("norm_g")->ptr, (const float*)find("norm_b")->ptr, d_feat,
-                                  (int)((size_t)n * d.ns), d.D, d.ns, d.ntok, d.nt, d.ln_eps, lq.q, stream);
+hipError_t Engine::final_layernorm(int n, bool compact) {
+    return launch_layernorm_split(compact ? xc_hi() : d_xh, compact ? xc_lo() : d_xl, (const float*)find("norm_g")->ptr,
+                                  (const float*)find("norm_b")->ptr, d_feat, (int)((size_t)n * d.ns), d.D, d.ns,
+                                  compact ? d.ns : d.ntok, compact ? 0 : d.nt, d.ln_eps, lq.q, stream);
+}
+
+bool Engine::last_block_compact(int n, bool with_taps) const {
+    if (!last_rows || with_taps || n < 1 || d.nt < 1 || (d.ns & 1)) return false;
+    if (attention_pick_mode(d.ntok, d.npad) != 3) return false;
+    GemmArgs a{};       // the compact proj as run_pass launches it
+    a.A = d_attn; a.lda = d.D; a.W = layers[(size_t)d.L - 1].proj_w; a.ldw = d.D; a.bias = layers[(size_t)d.L - 1].proj_b;
+    a.M = n * d.ns; a.N = d.D; a.K = d.D;
+    a.Xh = xc_hi(); a.Xl = xc_lo(); a.ldx = d.D;
+    a.Xh_in = d_xh; a.Xl_in = d_xl; a.seg_rows = d.ns; a.seg_skip = d.nt;
+    return gemm_effective_config(a, EPI_RESID) >= GEMM_CFG_256_MIN;
+}
+
+int Engine::expand_last_block() {
+    if (!pass_compact) return VT_OK;
+    const size_t seg = (size_t)d.ns * d.D, full = (size_t)d.ntok * d.D, off = (size_t)d.nt * d.D;
+    HIPCHK(hipMemcpy2DAsync(d_xh + off, full * sizeof(bf16_t), xc_hi(), seg * sizeof(bf16_t), seg * sizeof(bf16_t), (size_t)pass_n,
+                            hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpy2DAsync(d_xl + off, full, xc_lo(), seg, seg, (size_t)pass_n, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return VT_OK;
 }
 
 int Engine::capture_graph(int tier, bool any_layout) {
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    int rc = run_pass(nullptr, PassShape{B, nullptr, tier, any_layout, nullptr});
+    int rc = run_pass(nullptr, PassShape{B, nullptr, tier, any_layout, nullptr, last_block_compact(B, false)});
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(stream, &g);
     if (rc != VT_OK) {
@@ -783,6 +819,7 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
     pass_n = n;
     if (taps) taps_filled = true;
     feat_in_head = head_ln_fused();
+    ps->compact = pass_compact = last_block_compact(n, taps);
     ps->tier = pick_crop_tier(full ? nullptr : streams, n);     // a subset pass: from the boxes of its own streams
     return VT_OK;
 }
@@ -1011,6 +1048,7 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
     pass_n = n;
     if (taps) taps_filled = true;
     feat_in_head = head_ln_fused();
+    ps.compact = pass_compact = last_block_compact(n, taps);
     ps.tier = pick_crop_tier(cands, n);
     return run_pass(nullptr, ps);
 }

@@ -126,6 +126,8 @@ struct PassShape {
     // state (cand->cand_states, identity map), filled ahead of the crop and committed behind the decode. Null: a
     // slot's state is its stream's.
     const CandArgs* cand = nullptr;
+    // the last encoder block runs on the search rows only (Engine::last_block_compact: the ONE place that decides it)
+    bool compact = false;
 };
 
 // Where the packed windows of host frames go: a pinned host arena and its device twin of the same capacity
@@ -204,6 +206,23 @@ struct Engine {
     int pass_n = 1;
     std::vector<int32_t> pass_streams;
     bool feat_in_head = false;
+    // The last block on search rows only. Behind the last attention nobody reads the template rows:
+    // where the pass is eligible its last attention writes the search queries' rows compactly ([n * ns][D] in d_attn),
+    // proj reads its residual addend from the whole-layout pair through the row remap of the 256x256 kernel
+    // (GemmArgs.seg_rows) and writes a compact pair, and fc1, fc2, the final LayerNorm and the head run on n * ns rows.
+    // The compact pair lives in d_qk, which is dead behind the last attention: hi at its start, lo8 behind B * ns * D
+    // bf16 elements (3 B * ns * D bytes of the 4 B * ntok * D the buffer has).
+    int last_rows = 1;                  // vt_group_set_tuning "last_rows": 0 = every pass runs all rows
+    bool pass_compact = false;          // the last pass's last block ran on the search rows only (written by the pass builders)
+    bf16_t* xc_hi() const { return d_qk; }
+    uint8_t* xc_lo() const { return reinterpret_cast<uint8_t*>(d_qk + (size_t)B * d.ns * d.D); }
+    // a pass over n slots runs its last block on the search rows only: "last_rows" is on, no taps (they copy whole-layout
+    // rows of every block), attention mode 3, and the compact proj (M = n * ns) still takes the 256x256 kernel, the only
+    // one with the remapped addend read. with_taps false for the captured passes: they are never replayed under taps.
+    bool last_block_compact(int n, bool with_taps) const;
+    // reads of the whole-layout residual ("x", untapped "xrange") after a compacted pass: the compact search rows are
+    // copied to their places in d_xh / d_xl, whose template rows still hold what block L-2 left. Idempotent.
+    int expand_last_block();
     // after a candidate pass: pass_streams[i] is slot i's stream (streams may repeat) and pass_winner[i] the winning slot
     // of that stream; empty after every other pass
     std::vector<int32_t> pass_winner;
@@ -270,7 +289,7 @@ struct Engine {
     bool head_band() const { return head_band_kernel && head_band_ok; }
     // the head's first kernel normalises its rows itself: the passes run no final LayerNorm and write no d_feat
     bool head_ln_fused() const { return head_band() && head_band_kernel >= 2 && headconv_ln_supported(d.gs, d.C, d.D); }
-    hipError_t final_layernorm(int n);
+    hipError_t final_layernorm(int n, bool compact);     // compact: from the compact pair of a compacted pass
     int host_zero_copy = 0;                       // vt_config.host_zero_copy: 0 auto (single-stream engines), 1 always, -1 never
     float success_threshold = 0.2f;
     std::vector<int> h_initialized;

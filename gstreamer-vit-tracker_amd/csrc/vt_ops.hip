@@ -127,6 +127,56 @@ int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const f
                               VT_LO_SHIFT_DEFAULT);
 }
 
+// The residual GEMM of the 256x256 kernel on a pair given as it is stored, with the remapped addend read of the last
+// encoder block (GemmArgs.seg_rows / seg_skip / Xh_in): see include/vittrack_hip_ops.h
+int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias, const uint16_t* xh_in,
+                              const int8_t* xl_in, int rows_in, uint16_t* xh_out, int8_t* xl_out, float* cstat_out,
+                              float* rowstat_out, int M, int N, int K, int seg_rows, int seg_skip, float eps, int lo_shift) try {
+    if (!a || !w || !xh_in || !xl_in || !xh_out || !xl_out || M <= 0 || N <= 0 || K <= 0 || rows_in <= 0 || seg_rows < 0 || seg_skip < 0)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "gemm: lo_shift %d out of range", lo_shift);
+    // every input row the kernel may read exists: the last output row's place in the input layout
+    const long long last_in = seg_rows > 0 ? (long long)(M - 1) + ((long long)((M - 1) / seg_rows) + 1) * seg_skip : (long long)M - 1;
+    if (last_in >= rows_in) return set_err(VT_ERR_INVALID_ARG, "gemm: the input pair has %d rows, the addend read reaches row %lld", rows_in, last_in);
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    HIPCHK(gemm_prepare());
+    const size_t MN = (size_t)M * N, IN = (size_t)rows_in * N, nchunk = (size_t)N / VT_STAT_CHUNK;
+    DevBuf da, dw, db, dih, dil, doh, dol, dcst, dro, dcnt;
+    HIPCHK(da.alloc((size_t)M * K * 2)); HIPCHK(dw.alloc((size_t)N * K * 2)); HIPCHK(db.alloc((size_t)N * 4));
+    HIPCHK(dih.alloc(IN * 2)); HIPCHK(dil.alloc(IN)); HIPCHK(doh.alloc(MN * 2)); HIPCHK(dol.alloc(MN));
+    HIPCHK(dcst.alloc((size_t)M * nchunk * 8)); HIPCHK(dro.alloc((size_t)M * 8));
+    HIPCHK(dcnt.alloc((size_t)((M + 255) / 256 + 1) * 4));
+    HIPCHK(hipMemcpy(da.p, a, (size_t)M * K * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
+    std::vector<float> zb((size_t)N, 0.0f);
+    HIPCHK(hipMemcpy(db.p, bias ? bias : zb.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dih.p, xh_in, IN * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dil.p, xl_in, IN, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dcnt.p, 0, (size_t)((M + 255) / 256 + 1) * 4));
+    HIPCHK(hipMemset(dcst.p, 0xff, (size_t)M * nchunk * 8)); HIPCHK(hipMemset(dro.p, 0xff, (size_t)M * 8));
+    GemmArgs g{};
+    g.A = (const bf16_t*)da.p; g.lda = K; g.W = (const bf16_t*)dw.p; g.ldw = K; g.bias = (const float*)db.p;
+    g.M = M; g.N = N; g.K = K; g.Xh = (bf16_t*)doh.p; g.Xl = (uint8_t*)dol.p; g.ldx = N;
+    g.cstat = (float2*)dcst.p; g.rowstat_out = (float2*)dro.p; g.panel_cnt = (unsigned*)dcnt.p; g.ln_eps = eps;
+    g.lq = lo_quant(lo_shift);
+    if (seg_rows > 0) {     // addend from the input pair through the remap, output compact
+        g.Xh_in = (const bf16_t*)dih.p; g.Xl_in = (const uint8_t*)dil.p; g.seg_rows = seg_rows; g.seg_skip = seg_skip;
+        HIPCHK(hipMemset(doh.p, 0xff, MN * 2)); HIPCHK(hipMemset(dol.p, 0xff, MN));
+    } else {                // the launch as it always was: rows 0 .. M-1 of the pair, read and written in place
+        HIPCHK(hipMemcpy(doh.p, dih.p, MN * 2, hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(dol.p, dil.p, MN, hipMemcpyDeviceToDevice));
+    }
+    if (launch_gemm_cfg(g, EPI_RESID, GEMM_CFG_256P4, nullptr) != hipSuccess)
+        return set_err(VT_ERR_INVALID_ARG, "gemm: the 256x256 kernel does not take M=%d N=%d K=%d seg_rows=%d seg_skip=%d", M, N, K, seg_rows, seg_skip);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(xh_out, doh.p, MN * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(xl_out, dol.p, MN, hipMemcpyDeviceToHost));
+    if (cstat_out) HIPCHK(hipMemcpy(cstat_out, dcst.p, (size_t)M * nchunk * 8, hipMemcpyDeviceToHost));
+    if (rowstat_out) HIPCHK(hipMemcpy(rowstat_out, dro.p, (size_t)M * 8, hipMemcpyDeviceToHost));
+    return VT_OK;
+} VT_NOTHROW_INT
+
 // Timing helper for kernel tuning: runs the GEMM kernel `iters` times on device-resident random
 // operands with tile configuration `cfg` (<0: the launcher's own choice) and returns the mean time
 // per launch in microseconds (HIP events on the null stream).
@@ -277,6 +327,37 @@ int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, co
     HIPCHK(launch_attention_mode((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.p, B, N, H, npad, mode, nullptr));
     HIPCHK(hipDeviceSynchronize());
     std::vector<bf16_t> tmp((size_t)M * D);
+    HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
+    return VT_OK;
+} VT_NOTHROW_INT
+
+// Attention mode 3 on the queries q0 .. q0 + nq - 1 of every stream (the last encoder block): out compact [B*nq][H*64]
+int vt_op_attention_queries_bf16(int device_id, const uint16_t* q, const uint16_t* k, const uint16_t* v, float* out,
+                                 int B, int N, int H, int q0, int nq) try {
+    if (!q || !k || !v || !out || B <= 0 || N <= 0 || H <= 0 || (N & 3) || q0 < 0 || nq < 1 || q0 + nq > N)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    HIPCHK(attention_prepare());
+    const int D = H * 64, M = B * N, npad = (N + 63) / 64 * 64;
+    std::vector<bf16_t> qk((size_t)M * 2 * D), vt((size_t)B * H * 64 * npad, 0);
+    for (int m = 0; m < M; ++m) {       // the layouts the QKV epilogue produces for mode 3
+        memcpy(&qk[(size_t)m * 2 * D], q + (size_t)m * D, (size_t)D * 2);
+        memcpy(&qk[(size_t)m * 2 * D + D], k + (size_t)m * D, (size_t)D * 2);
+        const int b = m / N, tp = attn_perm16(m % N);
+        for (int c = 0; c < D; ++c)
+            vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
+    }
+    const size_t MO = (size_t)B * nq * D;
+    DevBuf dqk, dvt, dout;
+    HIPCHK(dqk.alloc(qk.size() * 2)); HIPCHK(dvt.alloc(vt.size() * 2)); HIPCHK(dout.alloc(MO * 2));
+    HIPCHK(hipMemcpy(dqk.p, qk.data(), qk.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dvt.p, vt.data(), vt.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dout.p, 0xff, MO * 2));
+    HIPCHK(launch_attention_queries((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.p, B, N, H, npad, q0, nq, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<bf16_t> tmp(MO);
     HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
     return VT_OK;

@@ -93,7 +93,9 @@ typedef struct vt_model_info {
     int32_t patch, template_size, search_size, dim, heads, layers, mlp_dim;
     int32_t head_channels, tokens_template, tokens_search, kpad;
     int32_t score_grid;        /* search_size / patch */
-    double flops_per_frame;    /* algorithmic FLOPs of one update (encoder+patch+head) */
+    double flops_per_frame;    /* algorithmic FLOPs of one update (encoder+patch+head): every block on all
+                                * tokens - also where the last block computes the search rows only (vt_group_set_tuning
+                                * "last_rows"), so a rate derived from it keeps its denominator */
     double encoder_flops_per_frame; /* encoder + patch-embed only */
     uint64_t weight_bytes;
 } vt_model_info;
@@ -554,7 +556,11 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
  * with the LayerNorm as a launch of its own, 0 = implicit GEMMs + head_out + decode launches; key "crop_tier": >= 0 forces the crop
  * kernel's LDS buffer tier (0: 16 KiB, 1: 32 KiB, 2: 64 KiB), < 0 (default) = chosen per pass from the boxes the host
- * knows. Not while a pipelined pass is outstanding. */
+ * knows; key "last_rows": 1 (default; any negative value selects it) = the last encoder block computes the search rows only
+ * where the pass is eligible - no taps, the attention kernel of the hot path, enough streams in the pass for the compacted
+ * projection to stay on the 256x256 GEMM kernel (19 of ViT-B/16 at search 384) - 0 = every pass runs all rows. Results, "feat",
+ * "head_out" and the states are the same bits either way; "last_block_rows" of vt_group_read_tensor says what the last pass
+ * did. Every key drops the captured passes and captures them again here. Not while a pipelined pass is outstanding. */
 int vt_group_set_tuning(vt_group* g, const char* key, int value);
 /* A single tracker viewed as a group of one (taps, profiling, stream handle). The view belongs to
  * the tracker: valid until vt_destroy(t), the same pointer on every call, never to be destroyed
@@ -575,6 +581,11 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * last pass, without them one row for "x" - a host can poll it after any pass to learn that a stream has left the
  * exact range |x| < 2^(15 - s); with taps enabled it needs a pass since vt_group_enable_taps, else VT_ERR_INVALID_ARG),
  * "rowstat" [N,2] (row terms of the last folded LayerNorm), "attn" [N,D] (last block's attention output),
+ * "last_block_rows" [1] (rows per slot the last encoder block of the last pass computed: Ns where it ran on the search rows
+ * only, see vt_group_set_tuning "last_rows", else N; no stream's slot is looked up for it). After such a pass "x", "attn",
+ * "rowstat" and the untapped "xrange" keep their shapes: the read of "x" / "xrange" first copies the search rows to their
+ * places, so the Nt template rows of "x" hold what block L-2 left there (nothing computed them in block L-1); the template
+ * rows of "attn" and "rowstat" read as zero.
  * "feat" [Ns,D], "head_t3" [Ns,C], "head_out" [Ns,8] (score,ox,oy,w,h logits),
  * "state" (the stream's device state record as raw 32-bit words), "graph_replays" [3] (passes replayed so far
  * per crop-buffer tier: which of the captured graphs ran), "template" [Nt,Kpad] (the stream's current template rows in

@@ -37,6 +37,17 @@ int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const f
 int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, const float* bias,
                        float* c_inout, int M, int N, int K, int epilogue, int cfg,
                        const float* rowstat_in, const float* colsum, float* rowstat_out, float eps, int lo_shift);
+/* The residual GEMM (epilogue 1) on the 256x256 kernel, on a pair given as it is stored, with the remapped addend read
+ * the last encoder block uses: x[m] = (A W^T + bias)[m] + pair_in[m + (m / seg_rows + 1) * seg_skip], m < M - the input
+ * layout has seg_skip rows nobody computes in front of every segment of seg_rows rows (seg_rows even). xh_in (bf16 bits)
+ * / xl_in (signed bytes): [rows_in][N]; xh_out / xl_out [M][N]; cstat_out (may be NULL) [M][N / 32][2] the chunk
+ * partials (sum, M2); rowstat_out (may be NULL) [M][2] the row terms with `eps`, finalized inside the launch.
+ * seg_rows = 0 (seg_skip = 0): the launch as vt_op_gemm_bf16_lo(epilogue 1, cfg 18) runs it - rows 0 .. M-1 of the input
+ * pair, read and written in place. N % 256 == 0, K % 64 == 0, K >= 128; anything the kernel does not take:
+ * VT_ERR_INVALID_ARG. */
+int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias, const uint16_t* xh_in,
+                              const int8_t* xl_in, int rows_in, uint16_t* xh_out, int8_t* xl_out, float* cstat_out,
+                              float* rowstat_out, int M, int N, int K, int seg_rows, int seg_skip, float eps, int lo_shift);
 /* Kernel-tuning helper: mean microseconds per launch of the GEMM kernel on device-resident random
  * operands. epilogue uses the library's internal numbering (0 f32+pos, 1 residual, 2 GELU, 3 ReLU,
  * 4 QKV, 5 f32); cfg: 0 = 64x64 ring 4, 1 = 128x128 ring 3, 2 = 64x64 ring 2, 3 = 128x128 ring 2
@@ -86,6 +97,11 @@ int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const fl
  * (q already scaled). mode as in vt_op_attention_bench. */
 int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                          float* out, int B, int N, int H, int mode);
+/* Attention mode 3 on the queries q0 .. q0 + nq - 1 of every stream only (keys and values: all N tokens):
+ * out [B, nq, H*64], row b * nq + (q - q0). N % 4 == 0. The same bits as those rows of vt_op_attention_bf16(mode 3)
+ * while every query's scores stay within +-32 log2 units; beyond, a query may take the kernel's other pass. */
+int vt_op_attention_queries_bf16(int device_id, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                                 float* out, int B, int N, int H, int q0, int nq);
 /* Kernel-tuning helper: mean microseconds per launch of the attention kernel on random data;
  * mode 0 key-split, 1 independent waves, 2 LDS-shared tiles, 3 LDS-DMA ring (permuted Vt),
  * <0 the launcher's choice. */
