@@ -17,7 +17,7 @@
 pub mod sys;
 
 use ndarray::ArrayView3;
-use std::ffi::{c_int, CStr, CString};
+use std::ffi::{c_int, c_void, CStr, CString};
 
 pub use sys::BBox;
 
@@ -223,6 +223,36 @@ impl VitTrack {
             return Err(last(rc));
         }
         Ok(st)
+    }
+
+    /// This tracker's stream as a snapshot (vt_export_state): state, refresh policy and the current template rows, one
+    /// self-contained byte string. A later `VitTrack` of the same input geometry - another process, another GPU, another
+    /// checkpoint - continues the track from it with `import_state`, without the operator selecting again.
+    pub fn export_state(&self) -> Result<Vec<u8>, TrackError> {
+        let mut need: usize = 0;
+        let rc = unsafe { sys::vt_export_state(self.h, std::ptr::null_mut(), 0, &mut need) };
+        if rc != sys::VT_ERR_SHORT_BUFFER {
+            return Err(last(rc));
+        }
+        let mut buf = vec![0u8; need];
+        let mut written: usize = 0;
+        let rc = unsafe { sys::vt_export_state(self.h, buf.as_mut_ptr() as *mut c_void, buf.len(), &mut written) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        buf.truncate(written);
+        Ok(buf)
+    }
+
+    /// Become the stream `snapshot` was exported from (vt_import_state). A snapshot that is malformed or of another
+    /// input geometry is an `Err` (VT_ERR_FORMAT) and changes nothing.
+    pub fn import_state(&mut self, snapshot: &[u8]) -> Result<(), TrackError> {
+        let rc = unsafe { sys::vt_import_state(self.h, snapshot.as_ptr() as *const c_void, snapshot.len()) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        self.pending = None;
+        Ok(())
     }
 }
 

@@ -125,6 +125,37 @@ pub struct VtRefreshStats {
     pub reserved: [i32; 3],
 }
 
+/// ≙ vt_snapshot_desc: what vt_snapshot_info reports of a stream snapshot (128 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct VtSnapshotDesc {
+    pub total_bytes: u32,
+    pub header_bytes: u32,
+    pub state_bytes: u32,
+    pub policy_bytes: u32,
+    pub rows_bytes: u32,
+    pub flags: u32,
+    pub patch: i32,
+    pub template_size: i32,
+    pub search_size: i32,
+    pub kpad: i32,
+    pub tokens_template: i32,
+    pub norm_a: [f32; 3],
+    pub norm_b: [f32; 3],
+    pub r#box: [f32; 4],
+    pub frame_width: i32,
+    pub frame_height: i32,
+    pub frames_done: i32,
+    pub success_count: i32,
+    pub last_score: f32,
+    pub period: i32,
+    pub min_score: f32,
+    pub skipped_geometry: i32,
+    pub generation: i32,
+    pub last_frame: i32,
+    pub reserved: [i32; 1],
+}
+
 /// ≙ vt_draw_cmd
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -227,6 +258,14 @@ extern "C" {
     pub fn vt_template_refresh_stats(t: *mut vt_tracker, out: *mut VtRefreshStats) -> c_int;
     pub fn vt_group_set_template_refresh(g: *mut vt_group, stream: c_int, period: c_int, min_score: f32) -> c_int;
     pub fn vt_group_template_refresh_stats(g: *mut vt_group, stream: c_int, out: *mut VtRefreshStats) -> c_int;
+    pub fn vt_snapshot_bytes(info: *const VtModelInfo) -> usize;
+    pub fn vt_group_snapshot_bytes(g: *const vt_group) -> usize;
+    pub fn vt_snapshot_info(buf: *const c_void, bytes: usize, out: *mut VtSnapshotDesc) -> c_int;
+    pub fn vt_group_export_stream(g: *mut vt_group, stream: c_int, buf: *mut c_void, cap: usize, written: *mut usize) -> c_int;
+    pub fn vt_group_import_stream(g: *mut vt_group, stream: c_int, buf: *const c_void, bytes: usize) -> c_int;
+    pub fn vt_group_copy_stream(src: *mut vt_group, s: c_int, dst: *mut vt_group, t: c_int) -> c_int;
+    pub fn vt_export_state(t: *mut vt_tracker, buf: *mut c_void, cap: usize, written: *mut usize) -> c_int;
+    pub fn vt_import_state(t: *mut vt_tracker, buf: *const c_void, bytes: usize) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import weights  # noqa: F401  (blob writer / configs)
 from . import synth    # noqa: F401
+from . import snapshot  # noqa: F401  (the snapshot format in NumPy)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VITTRACK_HIP_LIB", os.path.join(PKG_DIR, "libvittrack_hip.so"))
@@ -79,6 +80,18 @@ class CRefreshStats(Structure):
                 ("skipped_geometry", c_int32), ("reserved", c_int32 * 3)]
 
 
+class CSnapshotDesc(Structure):
+    """vt_snapshot_desc (128 bytes): what vt_snapshot_info reports of a stream snapshot"""
+    _fields_ = [("total_bytes", c_uint32), ("header_bytes", c_uint32), ("state_bytes", c_uint32),
+                ("policy_bytes", c_uint32), ("rows_bytes", c_uint32), ("flags", c_uint32),
+                ("patch", c_int32), ("template_size", c_int32), ("search_size", c_int32), ("kpad", c_int32),
+                ("tokens_template", c_int32), ("norm_a", c_float * 3), ("norm_b", c_float * 3), ("box", c_float * 4),
+                ("frame_width", c_int32), ("frame_height", c_int32), ("frames_done", c_int32),
+                ("success_count", c_int32), ("last_score", c_float), ("period", c_int32), ("min_score", c_float),
+                ("skipped_geometry", c_int32), ("generation", c_int32), ("last_frame", c_int32),
+                ("reserved", c_int32 * 1)]
+
+
 class CDrawCmd(Structure):
     _fields_ = [("type", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
                 ("p", c_int32), ("value", c_int32), ("text", c_char * 36)]
@@ -112,6 +125,8 @@ EXPORTS = [
     "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob", "vt_init_frame", "vt_update_frame",
     "vt_set_template_refresh", "vt_template_refresh_stats", "vt_group_set_template_refresh",
     "vt_group_template_refresh_stats",
+    "vt_snapshot_bytes", "vt_group_snapshot_bytes", "vt_snapshot_info", "vt_group_export_stream",
+    "vt_group_import_stream", "vt_group_copy_stream", "vt_export_state", "vt_import_state",
 ]
 # every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
 OPS_EXPORTS = [
@@ -198,6 +213,16 @@ def lib():
     L.vt_template_refresh_stats.argtypes = [c_void_p, POINTER(CRefreshStats)]
     L.vt_group_set_template_refresh.argtypes = [c_void_p, c_int, c_int, c_float]
     L.vt_group_template_refresh_stats.argtypes = [c_void_p, c_int, POINTER(CRefreshStats)]
+    L.vt_snapshot_bytes.argtypes = [POINTER(CModelInfo)]
+    L.vt_snapshot_bytes.restype = c_size_t
+    L.vt_group_snapshot_bytes.argtypes = [c_void_p]
+    L.vt_group_snapshot_bytes.restype = c_size_t
+    L.vt_snapshot_info.argtypes = [c_void_p, c_size_t, POINTER(CSnapshotDesc)]
+    L.vt_group_export_stream.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_size_t)]
+    L.vt_group_import_stream.argtypes = [c_void_p, c_int, c_void_p, c_size_t]
+    L.vt_group_copy_stream.argtypes = [c_void_p, c_int, c_void_p, c_int]
+    L.vt_export_state.argtypes = [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]
+    L.vt_import_state.argtypes = [c_void_p, c_void_p, c_size_t]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -303,6 +328,38 @@ def plan_engines(info: "CModelInfo", n_streams: int) -> list:
     if k <= 0:
         raise ValueError(f"vt_plan_engines({n_streams}) failed")
     return [int(sizes[i]) for i in range(k)]
+
+
+def snapshot_bytes(info: "CModelInfo") -> int:
+    """vt_snapshot_bytes: size of a stream snapshot of a model with info's tokens_template and kpad; needs no GPU"""
+    return int(lib().vt_snapshot_bytes(byref(info)))
+
+
+def snapshot_info(blob) -> dict:
+    """vt_snapshot_info: validate a stream snapshot (everything but the comparison with an engine) and describe it:
+    sizes, flags, input geometry, box, frame size, counters, last score, the refresh policy, generation and last_frame.
+    Needs no GPU. Raises VtError (VT_ERR_FORMAT, -4) with the reason for a snapshot no engine would take."""
+    raw = bytes(blob)
+    d = CSnapshotDesc()
+    _check(lib().vt_snapshot_info(raw, len(raw), byref(d)))
+    out = {}
+    for name, _ in CSnapshotDesc._fields_:
+        if name == "reserved":
+            continue
+        v = getattr(d, name)
+        out[name] = [float(x) for x in v] if hasattr(v, "__len__") else (float(v) if isinstance(v, float) else int(v))
+    return out
+
+
+def _export_snapshot(fn, *head) -> bytes:
+    """the two-call form of vt_group_export_stream / vt_export_state: the size, then the bytes"""
+    need = c_size_t(0)
+    rc = fn(*head, None, 0, byref(need))
+    if rc != -7:            # VT_ERR_SHORT_BUFFER carries the size; anything else is the answer
+        _check(rc)
+    buf = ctypes.create_string_buffer(int(need.value))
+    _check(fn(*head, buf, need.value, byref(need)))
+    return buf.raw[:int(need.value)]
 
 
 def scan_windows(w: int, h: int, box_w: float, box_h: float, overlap_pct: int = 50) -> np.ndarray:
@@ -622,6 +679,16 @@ class VitTrack:
         _check(lib().vt_template_refresh_stats(self._h, byref(st)))
         return _refresh_stats_dict(st)
 
+    def export_state(self) -> bytes:
+        """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
+        later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
+        return _export_snapshot(lib().vt_export_state, self._h)
+
+    def import_state(self, blob) -> None:
+        """vt_import_state: become the stream the snapshot was exported from; the next update continues its track"""
+        raw = bytes(blob)
+        _check(lib().vt_import_state(self._h, raw, len(raw)))
+
     # device-resident frames (pointers into this GPU's HBM, e.g. torch tensors' data_ptr())
     def init_nv12_device(self, d_y, d_uv, w, h, y_stride, uv_stride, bbox: BBox):
         _check(lib().vt_init_nv12_device(self._h, d_y, d_uv, w, h, y_stride, uv_stride, bbox._c()))
@@ -922,6 +989,26 @@ class Group:
         st = CRefreshStats()
         _check(lib().vt_group_template_refresh_stats(self._h, int(stream), byref(st)))
         return _refresh_stats_dict(st)
+
+    def snapshot_bytes(self) -> int:
+        return int(lib().vt_group_snapshot_bytes(self._h))
+
+    def export_stream(self, stream: int) -> bytes:
+        """vt_group_export_stream: the stream's state record, refresh policy and current template rows as one
+        self-contained byte string (layout: include/vittrack_hip.h, snapshot.py). The stream is not changed."""
+        return _export_snapshot(lib().vt_group_export_stream, self._h, int(stream))
+
+    def import_stream(self, stream: int, blob) -> None:
+        """vt_group_import_stream: make `stream` what the snapshot's stream was when it was exported - any slot of any
+        engine of the same input geometry, whatever its weights. With pipelined passes outstanding the import is
+        queued behind them (the stream must be in none), like enqueue_init_host."""
+        raw = bytes(blob)
+        _check(lib().vt_group_import_stream(self._h, int(stream), raw, len(raw)))
+
+    def copy_stream(self, stream: int, dst: "Group", dst_stream: int) -> None:
+        """vt_group_copy_stream: export + import without a host buffer - device to device when both engines are on
+        one GPU, through pinned staging otherwise; dst may be this group (another slot)"""
+        _check(lib().vt_group_copy_stream(self._h, int(stream), dst._h, int(dst_stream)))
 
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats

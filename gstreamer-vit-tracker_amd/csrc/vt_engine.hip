@@ -65,6 +65,15 @@ void Engine::destroy() {
         delete q;
     }
     qinits.clear();
+    for (SnapStage* sg : snaps) {
+        if (!sg) continue;
+        if (sg->d) (void)hipFree(sg->d);
+        if (sg->h) (void)hipHostFree(sg->h);
+        if (sg->up_ev) (void)hipEventDestroy(sg->up_ev);
+        if (sg->done_ev) (void)hipEventDestroy(sg->done_ev);
+        delete sg;
+    }
+    snaps.clear();
     if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
     for (int i = 0; i < RING; ++i)
         if (ring_ev[i]) (void)hipEventDestroy(ring_ev[i]);
@@ -863,7 +872,7 @@ int Engine::reset_refresh_tickets() {
     return VT_OK;
 }
 
-// The first enabled policy: the store grows to two buffers per stream (buffer 0 = the rows init wrote), policy array
+// The first enabled policy: the store grows to two buffers per stream (buffer tpl_gen & 1 = the stream's rows), policy array
 // and tickets are allocated, and every graph is captured again with the gather and the refresh launch in it - here,
 // on the idle stream, never inside an update. Nothing changes on failure.
 int Engine::enable_refresh() {
@@ -878,6 +887,7 @@ int Engine::enable_refresh() {
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && extra > free_b)
         return set_err(VT_ERR_OOM, "template refresh needs %.2f MiB more HBM; %.1f MiB are free", extra / 1048576.0,
                        free_b / 1048576.0);
+    std::vector<StreamState> sts((size_t)B);     // before the device allocations: may throw
     bf16_t* tpl2 = nullptr;
     RefreshPolicy* pol = nullptr;
     unsigned* tick = nullptr;
@@ -887,6 +897,14 @@ int Engine::enable_refresh() {
     if (he == hipSuccess)
         he = hipMemcpy2DAsync(tpl2, 2 * rows * sizeof(bf16_t), d_tpl, rows * sizeof(bf16_t), rows * sizeof(bf16_t),
                               (size_t)B, hipMemcpyDeviceToDevice, stream);
+    // a stream that was imported (vt_snapshot.hip) may carry an odd tpl_gen in this single-buffer engine: its current rows
+    // belong into buffer tpl_gen & 1 of the new store, where every reader will look for them (buffer 0 keeps a copy)
+    if (he == hipSuccess) he = hipMemcpyAsync(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    for (int b = 0; b < B && he == hipSuccess; ++b)
+        if (sts[(size_t)b].tpl_gen & 1)
+            he = hipMemcpyAsync(tpl2 + ((size_t)b * 2 + 1) * rows, d_tpl + (size_t)b * rows, rows * sizeof(bf16_t),
+                                hipMemcpyDeviceToDevice, stream);
     if (he == hipSuccess) he = hipStreamSynchronize(stream);
     if (he != hipSuccess) {
         if (tpl2) (void)hipFree(tpl2);

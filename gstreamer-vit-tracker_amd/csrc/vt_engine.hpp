@@ -6,6 +6,7 @@
 //                   group, diagnostics, colour converter, overlays, dma-buf and host-mapping ingest)
 //   vt_ingest.hip   host-frame ingest: the staging arena, window planning and packing, the host-frame passes of a group
 //                   (synchronous, pipelined enqueue_host / wait_next, queued init, candidate passes on host frames)
+//   vt_snapshot.hip stream snapshots: the byte format's validation, export / import / copy of a stream (k_snapshot.hip)
 //   vt_rccl.hip     the start-up weight broadcast over a lazily loaded librccl
 //   vt_ops.hip      operator-level entry points of include/vittrack_hip_ops.h - linked into
 //                   libvittrack_hip_ops.so (tests, tuning tools) only, NOT into the product library
@@ -275,6 +276,22 @@ struct Engine {
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
     };
     std::vector<QueuedInit*> qinits;
+    // staging of the stream snapshots (vt_snapshot.hip): a device record and its pinned twin, vt_group_snapshot_bytes
+    // each, and the event behind the last work that reads or writes them. Allocated by the first export / import / copy
+    // (an engine that never calls one has none); one is reused once its event has passed, so the synchronous calls
+    // share one and every queued import has its own
+    struct SnapStage {
+        uint8_t *d = nullptr, *h = nullptr;
+        hipEvent_t up_ev = nullptr, done_ev = nullptr;
+    };
+    std::vector<SnapStage*> snaps;
+    size_t snapshot_bytes() const { return 256 + sizeof(bf16_t) * (size_t)d.nt * d.kpad; }
+    int snap_staging(SnapStage** out);
+    bool in_outstanding_pass(int stream) const {
+        for (const HostSlot& sl : hs)
+            if (sl.pending && sl.lists(stream)) return true;
+        return false;
+    }
     int check_init_box(vt_bbox box) const;
     // the state write, the template crop and its copy to d_tpl, on the group's stream; h_st / h_desc: pinned staging
     // that stays untouched until that work is done

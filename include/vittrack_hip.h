@@ -436,6 +436,109 @@ int vt_template_refresh_stats(vt_tracker* t, vt_refresh_stats* out);
 int vt_group_set_template_refresh(vt_group* g, int stream /* -1: all */, int period, float min_score);
 int vt_group_template_refresh_stats(vt_group* g, int stream, vt_refresh_stats* out);
 
+/* ---- stream snapshots: export, import and copy a stream between engines ---------------------------
+ * A stream is a box a person chose (src/selection_state.rs) plus the template cut at that box (tracker.init,
+ * src/tracker_context.rs:88) - with template refresh also the product of hours of tracking. A snapshot takes that state
+ * out of one slot of one engine and puts it into any slot of any engine of the same INPUT GEOMETRY: the template is rows
+ * of the patch matrix (normalised pixels in bf16, in front of the patch embedding) and neither it nor the state record
+ * depends on the network's weights, so a snapshot moves between engines, GPUs, processes and checkpoints. The weights are
+ * deliberately not part of any check: importing into an engine that runs another checkpoint is the upgrade path.
+ *
+ * One self-contained little-endian byte string per stream, vt_snapshot_bytes() long:
+ *   offset  size  field
+ *        0     4  magic "VTSS"
+ *        4     4  version "0001"
+ *        8     4  u32 total_bytes    = header_bytes + state_bytes + policy_bytes + rows_bytes
+ *       12     4  u32 header_bytes   = 152
+ *       16     4  u32 state_bytes    = 88
+ *       20     4  u32 policy_bytes   = 16
+ *       24     4  u32 rows_bytes     = tokens_template * kpad * 2
+ *       28     4  u32 flags          bit 0: the source engine had captured the second graph set (a stream of it was
+ *                                    initialised on a format other than RGB8 / NV12 / YUY2); every other bit zero
+ *       32    20  i32 patch, template_size, search_size, kpad, tokens_template
+ *       52    24  f32 norm_a[3], norm_b[3]      the pixel normalisation of the weight blob's header
+ *       76     4  u32 reserved, zero
+ *       80     8  u64 checksum: FNV-1a-64 (offset basis 0xcbf29ce484222325, prime 0x100000001b3) over all total_bytes
+ *                 bytes with these eight read as zero
+ *       88    64  u32 reserved[16], zero
+ *      152    88  the stream's state record, verbatim, as 22 32-bit words (vt_group_read_tensor "state"):
+ *                 f32 box[4], f32 geo[4], i32 frame_w, frame_h, initialized, frames_done, success_count, last_idx,
+ *                 f32 last_fbox[4], f32 last_score, i32 window_miss, generation (refreshes since init), last_frame
+ *      240    16  the stream's refresh policy: i32 period, f32 min_score, i32 skipped_geometry, i32 reserved (zero);
+ *                 all zero from an engine that never enabled template refresh
+ *      256     -  the stream's current template rows, [tokens_template][kpad] bf16: the bits
+ *                 vt_group_read_tensor "template" returns (24,576 B at template 64 / patch 16, 221,184 B at 192 / 16)
+ *
+ * Validation. vt_snapshot_info and vt_group_import_stream / vt_import_state return VT_ERR_FORMAT, with nothing changed
+ * and the reason in vt_last_error, for: a bad magic or version; sizes that do not add up or differ from `bytes`; a
+ * non-zero reserved word or flag bit; a checksum mismatch; a geometry that is not one (or, on import, differs from the
+ * engine's in patch, template_size, search_size, kpad, tokens_template or the bits of the six normalisation floats); a
+ * state no pass could have left (initialized != 1, a box vt_group_set_state_box would refuse, a non-finite geo,
+ * last_fbox or last_score, a frame side outside 16..65536, frames_done < 0, success_count outside 0..frames_done,
+ * last_idx outside the score grid, generation < 0, last_frame outside 0..frames_done, window_miss outside
+ * 0..frames_done + 1); a policy vt_group_set_template_refresh would refuse (or a negative skipped_geometry, a non-zero
+ * reserved word); a non-finite bf16 in the rows. */
+typedef struct vt_snapshot_desc {   /* what vt_snapshot_info reports: 128 bytes */
+    uint32_t total_bytes, header_bytes, state_bytes, policy_bytes, rows_bytes, flags;
+    int32_t patch, template_size, search_size, kpad, tokens_template;
+    float norm_a[3], norm_b[3];
+    float box[4];                        /* the stream's state box: x, y, w, h in frame pixels */
+    int32_t frame_width, frame_height;
+    int32_t frames_done, success_count;
+    float last_score;
+    int32_t period; float min_score; int32_t skipped_geometry;   /* the refresh policy */
+    int32_t generation, last_frame;      /* as in vt_refresh_stats */
+    int32_t reserved[1];
+} vt_snapshot_desc;
+/* Bytes of a snapshot of a model with info's tokens_template and kpad; 0 on bad arguments. Needs no GPU. */
+size_t vt_snapshot_bytes(const vt_model_info* info);
+/* The same for this engine's model. */
+size_t vt_group_snapshot_bytes(const vt_group* g);
+/* Validate a snapshot (everything above but the comparison with an engine) and describe it. Needs no GPU, like
+ * vt_scan_windows. VT_ERR_INVALID_ARG on a null pointer. */
+int vt_snapshot_info(const void* buf, size_t bytes, vt_snapshot_desc* out);
+/* Write stream `stream` of the group as a snapshot into buf[0..cap); *written (may be null) gets its size. The source
+ * is not changed in any bit. VT_ERR_NOT_INITIALIZED for a stream that was never initialised; VT_ERR_SHORT_BUFFER if cap
+ * is too small, *written is then the size needed; VT_ERR_INVALID_ARG for a bad stream index or a null buffer.
+ * While pipelined host passes are outstanding: allowed for a stream that is in none of them (VT_ERR_INVALID_ARG
+ * otherwise); the call waits for the device but collects nothing and leaves those passes' results as they are.
+ * State, policy and the rows of the stream's current template buffer are gathered by one launch on the group's HIP stream
+ * (ordered against its passes) into staging that the first snapshot call of an engine allocates: an engine that never
+ * exports or imports allocates nothing and launches what it always did. A staging record is one snapshot of device and one
+ * of pinned host memory; the synchronous calls share one, every queued import that has not run yet holds one. Like the
+ * staging arenas of the host-frame calls they are outside the vt_config.max_device_mib accounting, which covers weights,
+ * activations and the template buffers. */
+int vt_group_export_stream(vt_group* g, int stream, void* buf, size_t cap, size_t* written);
+/* Make stream `stream` of the group what the snapshot's stream was when it was exported: state record, refresh policy
+ * (period, min_score, skipped_geometry) and template rows - into template buffer generation & 1 of a refresh-capable
+ * engine, into the only buffer otherwise. The stream is initialised afterwards, whatever it was; no other stream is
+ * touched. A snapshot with period >= 2 imported into an engine that never enabled template refresh enables it first, as
+ * vt_group_set_template_refresh would (VT_ERR_OOM leaves nothing changed); an engine that is not refresh-capable keeps a
+ * snapshot's min_score but has no place for its skipped_geometry, a diagnostic. Flag bit 0 is treated like an init on
+ * a format other than RGB8 / NV12 / YUY2: the second graph set is captured inside this call if the engine has none
+ * (vt_group_graph_captures); without the bit, and without a first enabling, the call captures nothing.
+ * Checked in this order: null pointers and the stream index (VT_ERR_INVALID_ARG), the snapshot (VT_ERR_FORMAT).
+ * With nothing outstanding the call is synchronous, like vt_group_init_device.
+ * With pipelined host passes outstanding it follows vt_group_enqueue_init_host: allowed only for a stream in no
+ * outstanding pass (VT_ERR_INVALID_ARG otherwise, nothing changed); the bytes go into pinned staging of the call's own
+ * before it returns, their upload on the copy stream, the state and row writes on the group's stream behind the passes
+ * already queued; the call does not wait for them. The stream may be listed from the next
+ * vt_group_enqueue_host_streams on, its first window is exact, and a redo behind the import restores the imported
+ * state (the template store is not rewound, as for a queued init). A first enabling of template refresh recaptures
+ * graphs and is refused with VT_ERR_INVALID_ARG while passes are outstanding; flag bit 0 on an engine without the
+ * second graph set makes this one call wait for the outstanding passes, as documented at vt_group_enqueue_init_host. */
+int vt_group_import_stream(vt_group* g, int stream, const void* buf, size_t bytes);
+/* Export stream s of src and import it as stream t of dst with no caller buffer; src == dst with s != t is allowed
+ * (s == t is refused). Errors and ordering are those of the two calls. Engines on one GPU: device to device - the
+ * record is packed behind src's stream, dst's stream waits for an event behind it and unpacks; only the 104 bytes of
+ * state and policy visit the host, for dst's host-side copies. Engines on different GPUs: through the library's pinned
+ * staging, the bytes of vt_group_export_stream into vt_group_import_stream; no peer access needed. The caller
+ * serialises both handles. */
+int vt_group_copy_stream(vt_group* src, int s, vt_group* dst, int t);
+/* The same two calls on the single tracker (its group-of-one view, stream 0): checkpoint and resume of a VitTrack. */
+int vt_export_state(vt_tracker* t, void* buf, size_t cap, size_t* written);
+int vt_import_state(vt_tracker* t, const void* buf, size_t bytes);
+
 /* ---- dma-buf ingest ------------------------------------------------------------------------
  * The reference's capture side can hand out dma-bufs (v4l2src io-mode=dmabuf, src/pipeline_ir.rs:24)
  * but then maps them on the CPU (src/pipeline.rs:95-101). vt_import_dmabuf maps a dma-buf fd into
