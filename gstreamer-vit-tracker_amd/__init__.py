@@ -133,7 +133,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16", "vt_op_gemm_bench", "vt_op_qkv_bf16", "vt_op_attention_bf16",
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
-    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16",
+    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode",
 ]
 
 
@@ -283,6 +283,9 @@ def ops_lib():
     L.vt_op_conv3x3_relu_bf16.argtypes = [c_int, u16p, u16p, fp, fp, c_int, c_int, c_int, c_int, c_int]
     L.vt_op_nv12_to_rgb8_bench.argtypes = [c_int, c_int, c_int, c_int, fp]
     L.vt_op_nv12_to_rgb8_batch_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, fp]
+    L.vt_op_head_decode.argtypes = [c_int, c_int, u16p, u16p, fp, fp, fp, fp, c_void_p, c_int, POINTER(c_int32), c_float,
+                                    c_int, c_int, c_int, c_int, c_int, c_int, fp, c_void_p, c_void_p, c_void_p,
+                                    POINTER(ctypes.c_uint32)]
     _ops = L
     return L
 
@@ -1230,6 +1233,52 @@ def op_headconv(t_bf16_bits, w_bf16_bits, bias, B, grid, conv3x3=True, R=0, ncb=
     _check_op(ops_lib().vt_op_headconv_bf16(device, t.ctypes.data_as(u16), w.ctypes.data_as(u16),
                                      _f32(np.ascontiguousarray(bias, np.float32)), _f32(out), B, grid, Cin, N,
                                      1 if conv3x3 else 0, R, ncb, 0, None))
+    return out
+
+
+# vt_result as the decode writes it (include/vittrack_hip.h), 6 words
+RESULT_DTYPE = np.dtype([("success", "<i4"), ("score", "<f4"), ("bbox", "<i4", 4)])
+
+
+def op_head_decode(t_bf16_bits, w4, b4, hann, states, B, grid, form=0, w3_bf16_bits=None, b3=None, slot_stream=None,
+                   success_threshold=0.5, R=0, launches=1, host_results=True, host_states=True, mirror_fill=0xA5, device=0):
+    """vt_op_head_decode: the decode stage (k_head.hip) on given operands. form 0: head_out_kernel + decode_kernel on
+    t = t3 [B*grid*grid][C]; form 1: the last 3x3 layer (w3 [C][9C], b3 [C]) on the band kernel with the fused tail, R rows
+    per band (<= 0: the launcher's plan), `launches` launches on the same buffers. states: snapshot.STATE records (raw 88-byte
+    StreamState), indexed by stream; slot_stream [B]: slot -> stream (None: the identity). The two pinned host mirrors start
+    filled with the byte mirror_fill; host_results / host_states False runs with that mirror null. -> dict(head_out
+    [B*ns][8] float32, results / host_results [B] RESULT_DTYPE, states / host_states [n_states] snapshot.STATE, band_cnt [B]
+    uint32)"""
+    from .snapshot import STATE
+    t = np.ascontiguousarray(t_bf16_bits, np.uint16)
+    ns, C = grid * grid, t.shape[1]
+    assert t.shape == (B * ns, C)
+    w4 = np.ascontiguousarray(w4, np.float32)
+    b4 = np.ascontiguousarray(b4, np.float32)
+    hann = np.ascontiguousarray(hann, np.float32).reshape(-1)
+    assert w4.shape == (8, C) and b4.shape == (8,) and hann.shape == (ns,)
+    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    u16 = POINTER(c_uint16)
+    w3 = b3p = None
+    if form == 1:
+        w3 = np.ascontiguousarray(w3_bf16_bits, np.uint16)
+        b3a = np.ascontiguousarray(b3, np.float32)
+        assert w3.shape == (C, 9 * C) and b3a.shape == (C,)
+        b3p = _f32(b3a)
+    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
+    assert smap is None or smap.shape == (B,)
+    out = dict(head_out=np.empty((B * ns, 8), np.float32), results=np.zeros(B, RESULT_DTYPE),
+               host_results=np.frombuffer(bytes([mirror_fill]) * (B * RESULT_DTYPE.itemsize), RESULT_DTYPE).copy(),
+               host_states=np.frombuffer(bytes([mirror_fill]) * (len(st) * STATE.itemsize), STATE).copy(),
+               band_cnt=np.full(B, 0xFFFFFFFF, np.uint32))
+    flags = (0 if host_results else 1) | (0 if host_states else 2)
+    _check_op(ops_lib().vt_op_head_decode(
+        device, int(form), t.ctypes.data_as(u16), w3.ctypes.data_as(u16) if w3 is not None else None, b3p, _f32(w4), _f32(b4),
+        _f32(hann), st.ctypes.data_as(c_void_p), len(st), smap.ctypes.data_as(POINTER(c_int32)) if smap is not None else None,
+        c_float(success_threshold), B, grid, C, int(R), int(launches), flags, _f32(out["head_out"]),
+        out["results"].ctypes.data_as(c_void_p), out["host_results"].ctypes.data_as(c_void_p),
+        out["host_states"].ctypes.data_as(c_void_p), out["band_cnt"].ctypes.data_as(POINTER(ctypes.c_uint32))))
+    out["states"] = st
     return out
 
 

@@ -56,6 +56,10 @@ __device__ __forceinline__ float hc_sigmoid(float x) { return 1.0f / (1.0f + exp
 // better(a, b): candidate a = (response, cell) beats b: larger response, the lower cell on a tie - what "first
 // maximum in ascending cell order" (vto_decode) selects, whatever the order the candidates are combined in
 __device__ __forceinline__ bool hc_better(float ra, int ia, float rb, int ib) { return ra > rb || (ra == rb && ia < ib); }
+// the reductions start from (below every response, HC_NO_CELL); a stream none of whose cells compared (NaN responses: NaN
+// score logits) decodes cell 0, vto_decode's initial `best`: score NaN, success 0, last_idx 0
+#define HC_NO_CELL 0x7fffffff
+__device__ __forceinline__ int hc_decoded_cell(int idx) { return idx == HC_NO_CELL ? 0 : idx; }
 
 // The 3x3 window around the argmax cell and the box: threads 0..8 evaluate the window's cells, thread 0 adds the
 // terms in vto_decode's order (dy, dx ascending: bit-identical to the serial form) and writes the result. s_win:
@@ -82,9 +86,9 @@ __device__ __forceinline__ void decode_box(const DecodeArgs& a, int b, int sb, i
             const float cxj = ((float)ix + offx) / (float)grid;
             const float cyj = ((float)iy + offy) / (float)grid;
             t[0] = w; t[1] = w * cxj; t[2] = w * cyj; t[3] = w * hc_sigmoid(o[3]); t[4] = w * hc_sigmoid(o[4]);
-            if (tid == 4) s_win[45] = o[0];       // the window's centre is the argmax cell
-        } else if (tid == 4) {
-            s_win[45] = __builtin_nanf("");       // no cell had a comparable response (NaN logits): score NaN, success 0
+            // the window's centre is the decoded cell: always inside the map. Where no cell had a comparable response (every
+            // response NaN) that cell is 0, as in vto_decode, whose `best` starts there: hc_decoded_cell below
+            if (tid == 4) s_win[45] = o[0];
         }
 #pragma unroll
         for (int k = 0; k < 5; ++k) s_win[tid * 5 + k] = t[k];
@@ -158,7 +162,7 @@ __device__ __forceinline__ void decode_stream(const DecodeArgs& a, int b, int ti
     float* s_win = reinterpret_cast<float*>(smem + 2048);
     const int ns = a.ns;
     float best = -1.0f;
-    int bidx = 0x7fffffff;
+    int bidx = HC_NO_CELL;
     for (int i = tid; i < ns; i += 256) {
         float o[5];
         load_logits<SC1>(a.head_out + ((size_t)b * ns + i) * 8, o);
@@ -175,7 +179,7 @@ __device__ __forceinline__ void decode_stream(const DecodeArgs& a, int b, int ti
         }
         __syncthreads();
     }
-    const int idx = s_idx[0];
+    const int idx = hc_decoded_cell(s_idx[0]);
     __syncthreads();
     decode_box<SC1>(a, b, a.slot_stream ? a.slot_stream[b] : b, idx, tid, s_win);
 }
@@ -659,7 +663,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
         __syncthreads();
         if (wave == 0) {                          // first maximum of the band -> one 8-B candidate
             float best = -2.0f;
-            int bidx = 0x7fffffff;
+            int bidx = HC_NO_CELL;
 #pragma unroll
             for (int c = 0; c < MB * 16; c += 64) {
                 const int cell = c + lane;
@@ -695,7 +699,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
         // the stream's argmax from the bands' candidates (one sc1 load per band), then the window and the box
         if (wave == 0) {
             float best = -2.0f;
-            int bidx = 0x7fffffff;
+            int bidx = HC_NO_CELL;
             for (int c = lane; c < p.bands; c += 64) {
                 uint2 v;
                 asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)"
@@ -709,7 +713,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
                 const int oi = __shfl_xor(bidx, off);
                 if (hc_better(ob, oi, best, bidx)) { best = ob; bidx = oi; }
             }
-            if (lane == 0) s_last[1] = bidx;
+            if (lane == 0) s_last[1] = hc_decoded_cell(bidx);
         }
         __syncthreads();
         const int idx = s_last[1];

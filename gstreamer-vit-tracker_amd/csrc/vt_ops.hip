@@ -673,4 +673,102 @@ int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, 
                                      iters, us_out, VT_LO_SHIFT_DEFAULT);
 }
 
+// pinned, device-visible host memory (what PassOut points the decode at)
+struct PinnedBuf {
+    void* p = nullptr;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t n) { return hipHostMalloc(&p, n ? n : 4); }
+};
+
+// The decode stage on given operands: see include/vittrack_hip_ops.h. A thin launcher: everything is checked here or by
+// the launchers themselves before a kernel runs.
+int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t* w3, const float* b3, const float* w4,
+                      const float* b4, const float* hann, void* states, int n_states, const int32_t* slot_stream,
+                      float success_threshold, int B, int grid, int C, int R, int launches, int flags, float* head_out,
+                      vt_result* results, vt_result* host_results, void* host_states, uint32_t* band_cnt) try {
+    if ((form != 0 && form != 1) || !t || !w4 || !b4 || !hann || !states || !head_out || !results || !host_results ||
+        !host_states || !band_cnt || B < 1 || B > 4096 || grid < 1 || grid > 16 * 7 || C < 2 || C > 4096 || n_states < 1 ||
+        launches < 1 || launches > 64 || (form == 1 && (!w3 || !b3)))
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (C % 2) return set_err(VT_ERR_INVALID_ARG, "head_decode: C must be even");
+    if (!slot_stream && n_states < B)
+        return set_err(VT_ERR_INVALID_ARG, "head_decode: %d states for %d slots", n_states, B);
+    if (slot_stream) {      // every slot's stream exists, and no two slots write one state
+        std::vector<char> seen((size_t)n_states, 0);
+        for (int b = 0; b < B; ++b) {
+            const int32_t s = slot_stream[b];
+            if (s < 0 || s >= n_states) return set_err(VT_ERR_INVALID_ARG, "head_decode: slot %d names stream %d of %d", b, (int)s, n_states);
+            if (seen[(size_t)s]) return set_err(VT_ERR_INVALID_ARG, "head_decode: stream %d listed twice", (int)s);
+            seen[(size_t)s] = 1;
+        }
+    }
+    if (form == 1 && !headconv_plannable(grid, C, C, 9 * C, true, true))
+        return set_err(VT_ERR_INVALID_ARG, "head_decode: grid %d, C %d is no shape of the band kernel's fused tail", grid, C);
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    HIPCHK(headconv_prepare());
+    const int ns = grid * grid;
+    const size_t M = (size_t)B * ns;
+    DevBuf dt, dt3, dw3, db3, dw4, db4, dhann, dho, dst, dres, dpo, dmap, dcnt, dbest, dz;
+    PinnedBuf hres, hst;
+    HIPCHK(dt.alloc(M * C * 2)); HIPCHK(dw4.alloc((size_t)8 * C * 4)); HIPCHK(db4.alloc(8 * 4)); HIPCHK(dhann.alloc((size_t)ns * 4));
+    HIPCHK(dho.alloc(M * 8 * 4)); HIPCHK(dst.alloc((size_t)n_states * sizeof(StreamState))); HIPCHK(dres.alloc((size_t)B * sizeof(vt_result)));
+    HIPCHK(dpo.alloc(sizeof(PassOut))); HIPCHK(dcnt.alloc((size_t)B * 4)); HIPCHK(dbest.alloc((size_t)B * grid * 2 * 4));
+    HIPCHK(hres.alloc((size_t)B * sizeof(vt_result))); HIPCHK(hst.alloc((size_t)n_states * sizeof(StreamState)));
+    HIPCHK(hipMemcpy(dt.p, t, M * C * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw4.p, w4, (size_t)8 * C * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db4.p, b4, 8 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dhann.p, hann, (size_t)ns * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dst.p, states, (size_t)n_states * sizeof(StreamState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dho.p, 0xff, M * 8 * 4));
+    HIPCHK(hipMemset(dres.p, 0xff, (size_t)B * sizeof(vt_result)));
+    HIPCHK(hipMemset(dcnt.p, 0, (size_t)B * 4));
+    HIPCHK(hipMemset(dbest.p, 0, (size_t)B * grid * 2 * 4));
+    memcpy(hres.p, host_results, (size_t)B * sizeof(vt_result));
+    memcpy(hst.p, host_states, (size_t)n_states * sizeof(StreamState));
+    const PassOut po{(flags & 1) ? nullptr : (vt_result*)hres.p, (flags & 2) ? nullptr : (StreamState*)hst.p};
+    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
+    if (slot_stream) {
+        HIPCHK(dmap.alloc((size_t)B * 4));
+        HIPCHK(hipMemcpy(dmap.p, slot_stream, (size_t)B * 4, hipMemcpyHostToDevice));
+    }
+    DecodeArgs dec{};
+    dec.w4 = (const float*)dw4.p; dec.b4 = (const float*)db4.p; dec.hann = (const float*)dhann.p;
+    dec.head_out = (float*)dho.p; dec.states = (StreamState*)dst.p; dec.results = (vt_result*)dres.p;
+    dec.out = (const PassOut*)dpo.p; dec.slot_stream = slot_stream ? (const int32_t*)dmap.p : nullptr;
+    dec.B = B; dec.ns = ns; dec.grid = grid; dec.C = C; dec.success_threshold = success_threshold;
+    HeadConvArgs h{};
+    if (form == 0) {
+        dec.t3 = (const bf16_t*)dt.p;
+    } else {
+        HIPCHK(dt3.alloc(M * C * 2)); HIPCHK(dw3.alloc((size_t)C * 9 * C * 2)); HIPCHK(db3.alloc((size_t)C * 4)); HIPCHK(dz.alloc(256));
+        HIPCHK(hipMemcpy(dw3.p, w3, (size_t)C * 9 * C * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(db3.p, b3, (size_t)C * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(dz.p, 0, 256));
+        HIPCHK(hipMemset(dt3.p, 0xff, M * C * 2));
+        dec.t3 = (const bf16_t*)dt3.p;
+        h.in = (const bf16_t*)dt.p; h.ldin = C; h.W = (const bf16_t*)dw3.p; h.ldw = 9 * C; h.bias = (const float*)db3.p;
+        h.out = (bf16_t*)dt3.p; h.ldout = C; h.zeros = (const bf16_t*)dz.p;
+        h.B = B; h.grid = grid; h.C = C; h.N = C; h.K = 9 * C; h.conv3x3 = 1;
+        h.R = R > 0 ? R : 0; h.ncb = R > 0 ? C / 64 : 0;      // a given R keeps the tail's one column group; else both planned
+        h.band_cnt = (unsigned*)dcnt.p; h.band_best = (float*)dbest.p;
+    }
+    for (int i = 0; i < launches; ++i) {
+        const hipError_t e = form == 0 ? launch_decode(dec, nullptr) : launch_headconv(h, &dec, nullptr);
+        if (e == hipErrorInvalidValue) {      // refused before any kernel ran; earlier launches of this call drain first
+            (void)hipDeviceSynchronize();
+            return set_err(VT_ERR_INVALID_ARG, "head_decode: the launcher refuses grid %d, C %d, R %d", grid, C, R);
+        }
+        HIPCHK(e);
+    }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(head_out, dho.p, M * 8 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(results, dres.p, (size_t)B * sizeof(vt_result), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(states, dst.p, (size_t)n_states * sizeof(StreamState), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(band_cnt, dcnt.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    memcpy(host_results, hres.p, (size_t)B * sizeof(vt_result));
+    memcpy(host_states, hst.p, (size_t)n_states * sizeof(StreamState));
+    return VT_OK;
+} VT_NOTHROW_INT
+
 }  // extern "C"

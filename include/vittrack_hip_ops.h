@@ -85,6 +85,24 @@ int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, 
 int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
                               float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
                               int D, int N, int fused, int R, int ncb, int iters, float* us_out, int lo_shift);
+/* The head's decode stage (csrc/k_head.hip) on operands of the caller's choosing: the 5-logit layer, the Hann-weighted
+ * argmax, the 3x3 window, the box and the write-back of states, results and the two host mirrors.
+ *   form 0  launch_decode: head_out_kernel + decode_kernel on t = t3 [B*grid*grid][C] (C even; w3 / b3 / R ignored)
+ *   form 1  launch_headconv with the fused tail: the last 3x3 layer (w3 [C][9*C] bf16 bits, b3 [C]) on t, then logits,
+ *           hand-off and decode inside the launch, with band counters and candidates of its own (zeroed once, before
+ *           the first launch). R rows per band, <= 0: the launcher's plan.
+ * `launches` (>= 1) launches run back to back on the same buffers. t: bf16 bits; w4 [8][C], b4 [8], hann [grid*grid];
+ * states: n_states records of 88 bytes (StreamState as vt_export_state lays it out), in and out; slot_stream (nullable)
+ * [B]: slot -> stream, distinct indices < n_states (NULL: the identity, n_states >= B). Out: head_out [B*grid*grid][8],
+ * results [B] (the device array), host_results [B] / host_states [n_states] (the pinned mirrors the kernel stores to;
+ * their initial contents are the caller's, so untouched records are recognisable; flags bit 0 / bit 1: run with that
+ * mirror null, the buffer comes back as it went in), band_cnt [B] the counters after the last launch (form 0: zeros).
+ * Whatever the launchers refuse (form 1: a shape headconv_plannable rejects, R * grid > 112 cells, a band that does
+ * not fit LDS) and a slot map that does not fit n_states: VT_ERR_INVALID_ARG. */
+int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t* w3, const float* b3, const float* w4,
+                      const float* b4, const float* hann, void* states, int n_states, const int32_t* slot_stream,
+                      float success_threshold, int B, int grid, int C, int R, int launches, int flags, float* head_out,
+                      vt_result* results, vt_result* host_results, void* host_states, uint32_t* band_cnt);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
