@@ -216,6 +216,44 @@ impl VitTrack {
         Ok(())
     }
 
+    /// Let the device cut a target chip of side `size` (a multiple of 8, 32..=512) behind every due update
+    /// (vt_enable_chip): `kind` is sys::VT_CHIP_NORM_BF16 (planar [3][size][size] bf16 of v * norm_a[c] + norm_b[c]) or
+    /// sys::VT_CHIP_RGB8 (packed [size][size][3] bytes; the norms are ignored). Fixed by the first call.
+    pub fn enable_chip(&mut self, size: i32, kind: i32, norm_a: &[f32; 3], norm_b: &[f32; 3]) -> Result<(), TrackError> {
+        let rc = unsafe { sys::vt_enable_chip(self.h, size, kind, norm_a.as_ptr(), norm_b.as_ptr()) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(())
+    }
+
+    /// The chip policy (vt_set_chip): `factor` 0 switches chips off, else (0.5..=4) the crop side is factor * sqrt(w * h)
+    /// of the new box; a chip is cut after every update whose frames_done % period == phase.
+    pub fn set_chip(&mut self, factor: f32, period: i32, phase: i32) -> Result<(), TrackError> {
+        let rc = unsafe { sys::vt_set_chip(self.h, factor, period, phase) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(())
+    }
+
+    /// The chip as the last update left it, into `out` (at least 6 * size * size bytes for the bf16 kind, 3 * size * size
+    /// for RGB8: a shorter buffer is refused here, the library cannot see its length), and its info (vt_read_chip). The
+    /// bytes are current only where info.status == 1.
+    pub fn read_chip(&mut self, size: i32, kind: i32, out: &mut [u8]) -> Result<sys::VtChipInfo, TrackError> {
+        let per = if kind == sys::VT_CHIP_NORM_BF16 { 6usize } else { 3usize };
+        let need = (size.max(0) as usize).saturating_mul(size.max(0) as usize).saturating_mul(per);
+        if out.len() < need {
+            return Err(bad("chip buffer too short"));
+        }
+        let mut info = sys::VtChipInfo::default();
+        let rc = unsafe { sys::vt_read_chip(self.h, out.as_mut_ptr() as *mut c_void, &mut info) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(info)
+    }
+
     pub fn template_refresh_stats(&mut self) -> Result<sys::VtRefreshStats, TrackError> {
         let mut st = sys::VtRefreshStats::default();
         let rc = unsafe { sys::vt_template_refresh_stats(self.h, &mut st) };
@@ -368,6 +406,19 @@ pub unsafe fn group_reacquire_host(g: *mut sys::vt_group, stream: i32, host_fram
 /// `g` is a live group handle.
 pub unsafe fn group_set_template_refresh(g: *mut sys::vt_group, stream: i32, period: i32, min_score: f32) -> Result<(), TrackError> {
     let rc = sys::vt_group_set_template_refresh(g, stream, period, min_score);
+    if rc != sys::VT_OK {
+        return Err(last(rc));
+    }
+    Ok(())
+}
+
+/// The chip policy of one camera of a group, or of all with `stream = -1` (vt_group_set_chips), after
+/// sys::vt_group_enable_chips. Refused while a pipelined pass is outstanding.
+///
+/// # Safety
+/// `g` is a live group handle.
+pub unsafe fn group_set_chips(g: *mut sys::vt_group, stream: i32, factor: f32, period: i32, phase: i32) -> Result<(), TrackError> {
+    let rc = sys::vt_group_set_chips(g, stream, factor, period, phase);
     if rc != sys::VT_OK {
         return Err(last(rc));
     }

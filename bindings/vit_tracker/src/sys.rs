@@ -156,6 +156,23 @@ pub struct VtSnapshotDesc {
     pub reserved: [i32; 1],
 }
 
+/// ≙ vt_chip_info: what the last pass of a stream did about its target chip (48 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct VtChipInfo {
+    pub status: i32,
+    pub frames_done: i32,
+    pub success: i32,
+    pub score: f32,
+    pub r#box: [i32; 4],
+    pub geo: [f32; 3],
+    pub reserved: [i32; 1],
+}
+
+/// vt_chip_kind
+pub const VT_CHIP_NORM_BF16: c_int = 0;
+pub const VT_CHIP_RGB8: c_int = 1;
+
 /// ≙ vt_draw_cmd
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -266,6 +283,15 @@ extern "C" {
     pub fn vt_group_copy_stream(src: *mut vt_group, s: c_int, dst: *mut vt_group, t: c_int) -> c_int;
     pub fn vt_export_state(t: *mut vt_tracker, buf: *mut c_void, cap: usize, written: *mut usize) -> c_int;
     pub fn vt_import_state(t: *mut vt_tracker, buf: *const c_void, bytes: usize) -> c_int;
+    pub fn vt_group_enable_chips(g: *mut vt_group, size: c_int, kind: c_int, norm_a: *const f32, norm_b: *const f32) -> c_int;
+    pub fn vt_group_set_chips(g: *mut vt_group, stream: c_int, factor: f32, period: c_int, phase: c_int) -> c_int;
+    pub fn vt_group_read_chips(g: *mut vt_group, streams: *const c_int, n: c_int, out: *mut c_void, out_stride: usize,
+                               infos: *mut VtChipInfo) -> c_int;
+    pub fn vt_group_chips_device(g: *mut vt_group, d_chips: *mut *mut c_void, stride_bytes: *mut usize,
+                                 d_infos: *mut *const VtChipInfo) -> c_int;
+    pub fn vt_enable_chip(t: *mut vt_tracker, size: c_int, kind: c_int, norm_a: *const f32, norm_b: *const f32) -> c_int;
+    pub fn vt_set_chip(t: *mut vt_tracker, factor: f32, period: c_int, phase: c_int) -> c_int;
+    pub fn vt_read_chip(t: *mut vt_tracker, out: *mut c_void, info: *mut VtChipInfo) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

@@ -92,6 +92,15 @@ class CSnapshotDesc(Structure):
                 ("reserved", c_int32 * 1)]
 
 
+class CChipInfo(Structure):
+    """vt_chip_info (48 bytes): what the last pass of a stream did about its chip"""
+    _fields_ = [("status", c_int32), ("frames_done", c_int32), ("success", c_int32), ("score", c_float),
+                ("box", c_int32 * 4), ("geo", c_float * 3), ("reserved", c_int32 * 1)]
+
+
+CHIP_NORM_BF16, CHIP_RGB8 = 0, 1     # vt_chip_kind
+
+
 class CDrawCmd(Structure):
     _fields_ = [("type", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
                 ("p", c_int32), ("value", c_int32), ("text", c_char * 36)]
@@ -125,6 +134,8 @@ EXPORTS = [
     "vt_rccl_unique_id", "vt_broadcast_weights_rccl", "vt_free_device_blob", "vt_init_frame", "vt_update_frame",
     "vt_set_template_refresh", "vt_template_refresh_stats", "vt_group_set_template_refresh",
     "vt_group_template_refresh_stats",
+    "vt_group_enable_chips", "vt_group_set_chips", "vt_group_read_chips", "vt_group_chips_device",
+    "vt_enable_chip", "vt_set_chip", "vt_read_chip",
     "vt_snapshot_bytes", "vt_group_snapshot_bytes", "vt_snapshot_info", "vt_group_export_stream",
     "vt_group_import_stream", "vt_group_copy_stream", "vt_export_state", "vt_import_state",
 ]
@@ -223,6 +234,13 @@ def lib():
     L.vt_group_copy_stream.argtypes = [c_void_p, c_int, c_void_p, c_int]
     L.vt_export_state.argtypes = [c_void_p, c_void_p, c_size_t, POINTER(c_size_t)]
     L.vt_import_state.argtypes = [c_void_p, c_void_p, c_size_t]
+    L.vt_group_enable_chips.argtypes = [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float)]
+    L.vt_group_set_chips.argtypes = [c_void_p, c_int, c_float, c_int, c_int]
+    L.vt_group_read_chips.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_size_t, POINTER(CChipInfo)]
+    L.vt_group_chips_device.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p)]
+    L.vt_enable_chip.argtypes = [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float)]
+    L.vt_set_chip.argtypes = [c_void_p, c_float, c_int, c_int]
+    L.vt_read_chip.argtypes = [c_void_p, c_void_p, POINTER(CChipInfo)]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -682,6 +700,25 @@ class VitTrack:
         _check(lib().vt_template_refresh_stats(self._h, byref(st)))
         return _refresh_stats_dict(st)
 
+    def enable_chips(self, size: int, kind: int = CHIP_NORM_BF16, norm_a=(1.0, 1.0, 1.0), norm_b=(0.0, 0.0, 0.0)) -> None:
+        """vt_enable_chip: see Group.enable_chips"""
+        a, b = _chip_norms(kind, norm_a, norm_b)
+        _check(lib().vt_enable_chip(self._h, int(size), int(kind), a, b))
+
+    def set_chips(self, factor: float, period: int = 1, phase: int = 0) -> None:
+        _check(lib().vt_set_chip(self._h, float(factor), int(period), int(phase)))
+
+    def read_chips(self):
+        """vt_read_chip -> (chip array [1, ...], [info dict])"""
+        size, kind, _, _, _ = _chip_shape(lib().vt_tracker_as_group(self._h))
+        out, ci = _chip_array(size, kind, 1), CChipInfo()
+        _check(lib().vt_read_chip(self._h, out.ctypes.data, byref(ci)))
+        return out, [_chip_info_dict(ci)]
+
+    def chips_device(self) -> "DeviceChips":
+        size, kind, stride, ptr, infos = _chip_shape(lib().vt_tracker_as_group(self._h))
+        return DeviceChips(ptr, stride, infos, 1, size, kind)
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -718,6 +755,54 @@ class VitTrack:
         r = CResult()
         _check(lib().vt_update_rgb8_device(self._h, d_rgb, w, h, stride, byref(r)))
         return TrackResult(r)
+
+
+def _chip_info_dict(ci: "CChipInfo") -> dict:
+    return dict(status=int(ci.status), frames_done=int(ci.frames_done), success=int(ci.success), score=float(ci.score),
+                box=tuple(int(v) for v in ci.box), geo=tuple(float(v) for v in ci.geo))
+
+
+def _chip_norms(kind, norm_a, norm_b):
+    if int(kind) == CHIP_RGB8 and norm_a is None and norm_b is None:
+        return None, None
+    return (c_float * 3)(*[float(v) for v in norm_a]), (c_float * 3)(*[float(v) for v in norm_b])
+
+
+def _chip_array(size: int, kind: int, n: int):
+    """host array for n chips: bf16 chips as their uint16 bit patterns [n, 3, C, C], u8 chips as [n, C, C, 3]"""
+    import numpy as np
+    if int(kind) == CHIP_NORM_BF16:
+        return np.zeros((n, 3, size, size), np.uint16)
+    return np.zeros((n, size, size, 3), np.uint8)
+
+
+def _chip_shape(group_handle):
+    """(C, kind, stride, device address of the chips, of the infos) of a chip-capable engine, from vt_group_chips_device:
+    the stride is 6 C^2 (bf16) or 3 C^2 (u8), and no 6 C^2 equals a 3 C'^2, so it names both"""
+    p, st, inf = c_void_p(), c_size_t(), c_void_p()
+    _check(lib().vt_group_chips_device(group_handle, byref(p), byref(st), byref(inf)))
+    stride = int(st.value)
+    c = int(round((stride / 3) ** 0.5))
+    if 3 * c * c == stride and c % 8 == 0:
+        size, kind = c, CHIP_RGB8
+    else:
+        size, kind = int(round((stride / 6) ** 0.5)), CHIP_NORM_BF16
+    return size, kind, stride, int(p.value or 0), int(inf.value or 0)
+
+
+class DeviceChips:
+    """The chip store of a group as a device array: `__cuda_array_interface__` over vt_group_chips_device, so that
+    torch.as_tensor(g.chips_device(), device="cuda") is a view of the store - [B, 3, C, C] int16 (the bf16 bit patterns:
+    .view(torch.bfloat16)) or [B, C, C, 3] uint8 - without a copy. `infos` is the device address of the [B] vt_chip_info
+    records. Contents: those of the last pass once wait / wait_next / a synchronous update has returned, until the next
+    enqueue."""
+
+    def __init__(self, ptr: int, stride: int, infos: int, n: int, size: int, kind: int):
+        self.ptr, self.stride, self.infos, self.n, self.size, self.kind = ptr, stride, infos, n, size, kind
+        bf = kind == CHIP_NORM_BF16
+        self.__cuda_array_interface__ = dict(
+            shape=(n, 3, size, size) if bf else (n, size, size, 3), typestr="<i2" if bf else "|u1",
+            data=(ptr, False), version=2, strides=None)
 
 
 def _refresh_stats_dict(st: "CRefreshStats") -> dict:
@@ -1012,6 +1097,40 @@ class Group:
         """vt_group_copy_stream: export + import without a host buffer - device to device when both engines are on
         one GPU, through pinned staging otherwise; dst may be this group (another slot)"""
         _check(lib().vt_group_copy_stream(self._h, int(stream), dst._h, int(dst_stream)))
+
+    def enable_chips(self, size: int, kind: int = CHIP_NORM_BF16, norm_a=(1.0, 1.0, 1.0), norm_b=(0.0, 0.0, 0.0)) -> None:
+        """vt_group_enable_chips: make the engine cut target chips - a resized crop of a stream's frame at the box its
+        update committed, on the device, inside the pass. size: the chip side C (a multiple of 8, 32..512); kind:
+        CHIP_NORM_BF16 (planar [3][C][C] bf16 = v * norm_a[c] + norm_b[c], the caller's normalisation) or CHIP_RGB8 (packed
+        [C][C][3] u8, norms ignored). Fixed for the engine by the first call, which allocates the store (within
+        max_device_mib) and recaptures the graphs; refused while a pipelined pass is outstanding. Streams cut nothing
+        until set_chips gives them a factor."""
+        a, b = _chip_norms(kind, norm_a, norm_b)
+        _check(lib().vt_group_enable_chips(self._h, int(size), int(kind), a, b))
+
+    def set_chips(self, factor: float, period: int = 1, phase: int = 0, stream: int | None = None) -> None:
+        """vt_group_set_chips: the chip policy of `stream` (None: every stream). factor 0 switches it off; otherwise (0.5..4)
+        the crop side is factor * sqrt(w * h) of the new box and a chip is cut after every update whose frames_done %
+        period == phase - also after a failed one, at the last good box (info["success"] says so)."""
+        _check(lib().vt_group_set_chips(self._h, -1 if stream is None else int(stream), float(factor), int(period), int(phase)))
+
+    def read_chips(self, streams=None):
+        """vt_group_read_chips: the chips and infos of `streams` (None: all) as the last pass left them -> (ndarray, [dict]).
+        bf16 chips come as their uint16 bit patterns [n, 3, C, C], u8 chips as [n, C, C, 3]. A chip is current only where
+        its info has status 1 (0: not due, 2: due but skipped by the geometry rule - the bytes are then those of an earlier
+        cut and not to be used). Size and kind come from the engine, so any wrapper of an enabled engine can read."""
+        size, kind, _, _, _ = _chip_shape(self._h)
+        lst = list(range(self.streams)) if streams is None else [int(v) for v in streams]
+        n = len(lst)
+        out, infos = _chip_array(size, kind, max(n, 1)), (CChipInfo * max(n, 1))()
+        if n:
+            _check(lib().vt_group_read_chips(self._h, (c_int * n)(*lst), n, out.ctypes.data, out[0].nbytes, infos))
+        return out[:n], [_chip_info_dict(infos[i]) for i in range(n)]
+
+    def chips_device(self) -> "DeviceChips":
+        """vt_group_chips_device: the store as a device array for a consumer on the same GPU (DeviceChips)"""
+        size, kind, stride, ptr, infos = _chip_shape(self._h)
+        return DeviceChips(ptr, stride, infos, self.streams, size, kind)
 
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats

@@ -30,7 +30,7 @@ LIB_OPS = os.path.join(PKG, "libvittrack_hip_ops.so")
 LIB_HOST = os.path.join(HOST, "libvittrack_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_cand.hip", "k_overlay.hip",
+HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_cand.hip", "k_overlay.hip",
                "k_snapshot.hip", "vt_engine.hip", "vt_abi.hip", "vt_ingest.hip", "vt_snapshot.hip", "vt_rccl.hip"]
 OPS_SOURCES = ["vt_ops.hip"]          # libvittrack_hip_ops.so only
 HEADER = os.path.join(PKG, "..", "include", "vittrack_hip.h")

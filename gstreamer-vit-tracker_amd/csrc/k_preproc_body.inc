@@ -6,6 +6,14 @@
 // In scope at the include: ANY, f (the slot's FrameDesc), s (the stream's StreamState&), patches, b (the slot), size,
 // patch, kpad, ntok, row_off, factor, na0..na2, nb0..nb2, is_template; bodies 2 and 3: PX; body 3: src (LDS) and LDSPX.
 // A body may `return`. PRE_BODY: 1 one lane per pixel, 2 wide stores, 3 tiles of 64 x 32 staged in LDS.
+// Preprocessor parameters of bodies 2 and 3 (k_chip.hip, the u8 chips; nobody else defines them, and undefined they
+// expand to the text that stood here): PRE_OUT(v, c), what is kept of a channel's bilinear value v (default: the
+// normalised bf16), and PRE_STORE_RGB8, the store of a lane's run as packed RGB bytes to chip8[size][size][3]
+// (default: planar bf16 patch rows).
+#ifndef PRE_OUT
+#define PRE_OUT(v, c) f32_to_bf16(v * na[c] + nb[c])
+#define PRE_OUT_DEFAULT
+#endif
 #if PRE_BODY == 1
     // crop geometry — same operations, same order as vto_crop_geometry (oracle/vt_oracle.c)
     const float bx = s.box[0], by = s.box[1], bw = s.box[2], bh = s.box[3];
@@ -91,10 +99,14 @@
             const float top = p00[c] + wx * (p01[c] - p00[c]);
             const float bot = p10[c] + wx * (p11[c] - p10[c]);
             const float v = top + wy * (bot - top);
-            o[c][k] = f32_to_bf16(v * na[c] + nb[c]);
+            o[c][k] = PRE_OUT(v, c);
         }
     }
     if (miss && !is_template) s.window_miss = s.frames_done + 1;   // every writer stores the same value
+#ifdef PRE_STORE_RGB8
+    PRE_STORE_RGB8_RUN(o, chip8 + ((size_t)oy * size + ox0) * 3);
+    return;
+#endif
     const int grid = size / patch;
     const int token = (oy / patch) * grid + (ox0 / patch);         // PX divides patch: one token per group
     const int kin = (oy % patch) * patch + (ox0 % patch);
@@ -266,7 +278,11 @@
                 const float top = p00[c] + wx * (p01[c] - p00[c]);
                 const float bot = p10[c] + wx * (p11[c] - p10[c]);
                 const float v = top + wy * (bot - top);
-                row[c * patch * patch + kin + k] = f32_to_bf16(v * na[c] + nb[c]);
+#ifdef PRE_STORE_RGB8
+                chip8[((size_t)oy * size + ox0 + k) * 3 + c] = (uint8_t)PRE_OUT(v, c);
+#else
+                row[c * patch * patch + kin + k] = PRE_OUT(v, c);
+#endif
             }
         }
         if (miss && !is_template) s.window_miss = s.frames_done + 1;
@@ -290,10 +306,14 @@
             const float top = p00 + wx * (p01 - p00);
             const float bot = p10 + wx * (p11 - p10);
             const float v = top + wy * (bot - top);
-            o[c][k] = f32_to_bf16(v * na[c] + nb[c]);
+            o[c][k] = PRE_OUT(v, c);
         }
     }
     if (miss && !is_template) s.window_miss = s.frames_done + 1;   // every writer stores the same value
+#ifdef PRE_STORE_RGB8
+    PRE_STORE_RGB8_RUN(o, chip8 + ((size_t)oy * size + ox0) * 3);
+    return;
+#endif
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         uint4 v;
@@ -303,3 +323,7 @@
     }
 #endif
 #undef PRE_BODY
+#ifdef PRE_OUT_DEFAULT
+#undef PRE_OUT
+#undef PRE_OUT_DEFAULT
+#endif

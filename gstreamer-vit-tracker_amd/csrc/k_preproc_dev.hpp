@@ -1,5 +1,6 @@
-// k_preproc_dev.hpp — what the crop kernels of k_preproc.hip and the template refresh of k_refresh.hip share besides the
-// kernel bodies of k_preproc_body.inc: the pixel fetch and the tile constants.
+// k_preproc_dev.hpp — what the crop kernels of k_preproc.hip, the template refresh of k_refresh.hip and the target chips of
+// k_chip.hip share besides the kernel bodies of k_preproc_body.inc: the pixel fetch, the tile constants and the tap
+// rectangle of a crop.
 #pragma once
 #include "vt_common.hpp"
 
@@ -72,3 +73,10 @@ __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, fl
 #define PRE_TILE_W 64
 #define PRE_TILE_H 32
 #define PRE_TILE_LDS 4096       // source pixels (16 KiB): tier 0, the benchmark's 64-px targets
+
+// tap rectangle of a crop along one axis: the source pixels its first and last output pixel touch - the expressions of
+// the tile body's sx_lo / sx_hi (k_preproc_body.inc) for the whole crop (the geometry rules of k_refresh.hip, k_chip.hip)
+__device__ __forceinline__ void tap_range(float scale, float x0m, int size, int& lo, int& hi) {
+    lo = (int)floorf(((float)0 + 0.5f) * scale + x0m);
+    hi = (int)floorf(((float)(size - 1) + 0.5f) * scale + x0m) + 1;
+}

@@ -17,13 +17,6 @@
 #include "vt_common.hpp"
 #include "k_preproc_dev.hpp"
 
-// tap rectangle of a crop along one axis: the source pixels its first and last output pixel touch - the expressions of
-// the tile body's sx_lo / sx_hi (k_preproc_body.inc) for the whole crop
-__device__ __forceinline__ void tap_range(float scale, float x0m, int size, int& lo, int& hi) {
-    lo = (int)floorf(((float)0 + 0.5f) * scale + x0m);
-    hi = (int)floorf(((float)(size - 1) + 0.5f) * scale + x0m) + 1;
-}
-
 // MODE: which crop body, as launch_preproc picks it for the template - 0, 1, 2: the tile body with 16 / 32 / 64 KiB of
 // LDS (the pass's tier; a tile that does not fit takes the body's per-pixel path), 3: wide stores of 8 pixels, 4: of 2
 // pixels (patch 14), 5: one lane per pixel

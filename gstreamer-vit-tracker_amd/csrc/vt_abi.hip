@@ -610,6 +610,41 @@ int vt_template_refresh_stats(vt_tracker* t, vt_refresh_stats* out) try {
     return t->e->refresh_stats(0, out);
 } VT_NOTHROW_INT
 
+int vt_group_enable_chips(vt_group* g, int size, int kind, const float* norm_a, const float* norm_b) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (int rc = refuse_while_pipelined(g->e, "enable_chips")) return rc;
+    return g->e->enable_chips(size, kind, norm_a, norm_b);
+} VT_NOTHROW_INT
+int vt_group_set_chips(vt_group* g, int stream, float factor, int period, int phase) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (int rc = refuse_while_pipelined(g->e, "set_chips")) return rc;
+    return g->e->set_chips(stream, factor, period, phase);
+} VT_NOTHROW_INT
+int vt_group_read_chips(vt_group* g, const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    return g->e->read_chips(streams, n, out, out_stride, infos);
+} VT_NOTHROW_INT
+int vt_group_chips_device(vt_group* g, void** d_chips, size_t* stride_bytes, const vt_chip_info** d_infos) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (!g->e->chip_capable) return set_err(VT_ERR_INVALID_ARG, "chips: not enabled on this engine (vt_group_enable_chips)");
+    if (d_chips) *d_chips = g->e->d_chips;
+    if (stride_bytes) *stride_bytes = g->e->chip_bytes();
+    if (d_infos) *d_infos = g->e->d_chip_infos;
+    return VT_OK;
+} VT_NOTHROW_INT
+int vt_enable_chip(vt_tracker* t, int size, int kind, const float* norm_a, const float* norm_b) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    return vt_group_enable_chips(&t->view, size, kind, norm_a, norm_b);
+} VT_NOTHROW_INT
+int vt_set_chip(vt_tracker* t, float factor, int period, int phase) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    return vt_group_set_chips(&t->view, 0, factor, period, phase);
+} VT_NOTHROW_INT
+int vt_read_chip(vt_tracker* t, void* out, vt_chip_info* info) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    return t->e->read_chips(nullptr, 1, out, t->e->chip_bytes(), info);
+} VT_NOTHROW_INT
+
 int vt_group_host_redos(const vt_group* g) { return g ? (int)g->e->host_redos : 0; }
 int vt_group_graph_captures(const vt_group* g) { return g ? g->e->graph_captures : 0; }
 

@@ -37,9 +37,10 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets};
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy};     // d_chip_infos: part of d_chips
     for (void* p : devp)
         if (p) (void)hipFree(p);
+    if (h_chip_stage) (void)hipHostFree(h_chip_stage);
     if (h_cands) (void)hipHostFree(h_cands);
     if (h_winner) (void)hipHostFree(h_winner);
     if (h_frames) (void)hipHostFree(h_frames);
@@ -579,6 +580,13 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         L("refresh_template", 0, 2.0 * n * (sizeof(StreamState) + sizeof(vt_result)),
           [&] { return launch_template_refresh(ra, d, ps.tier, ps.any_layout, stream); });
     }
+    if (chip_capable) {     // the streams' chips at the boxes the decode (the commit) left: k_chip.hip
+        const ChipArgs ca{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_chip_policy,
+                          d_chips, d_chip_infos, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
+        L("target_chips", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + sizeof(vt_chip_info)), [&] {
+            return launch_target_chips(ca, chip_size, chip_kind, chip_na, chip_nb, d.S, ps.tier, ps.any_layout, stream);
+        });
+    }
     if (lerr != hipSuccess)
         return set_err(VT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
@@ -880,7 +888,7 @@ int Engine::enable_refresh() {
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     const size_t extra = refresh_bytes(), rows = (size_t)d.nt * d.kpad;
-    if (max_device_bytes && activation_bytes() + blob_bytes + extra > max_device_bytes)
+    if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
         return set_err(VT_ERR_OOM, "template refresh needs %.2f MiB more HBM for the second template buffers; "
                        "vt_config.max_device_mib allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
     size_t free_b = 0, total_b = 0;
@@ -976,6 +984,114 @@ int Engine::refresh_stats(int s, vt_refresh_stats* out) {
     HIPCHK(hipMemcpy(&st, d_states + s, sizeof(st), hipMemcpyDeviceToHost));
     out->generation = st.tpl_gen;
     out->last_frame = st.tpl_frame;
+    return VT_OK;
+}
+
+// ---- target chips ------------------------------------------------------------------------------------
+
+// The first enable: the store is allocated and every graph is captured again with the chip launch in it - on the idle
+// stream, never inside an update. A second enable with the same parameters is a no-op. Nothing changes on failure.
+int Engine::enable_chips(int size, int kind, const float* na, const float* nb) {
+    if (size < 32 || size > 512 || size % 8 != 0)
+        return set_err(VT_ERR_INVALID_ARG, "chips: size %d (a multiple of 8 in 32..512)", size);
+    if (kind != VT_CHIP_NORM_BF16 && kind != VT_CHIP_RGB8) return set_err(VT_ERR_INVALID_ARG, "chips: unknown kind %d", kind);
+    float a3[3] = {1.0f, 1.0f, 1.0f}, b3[3] = {0.0f, 0.0f, 0.0f};
+    if (kind == VT_CHIP_NORM_BF16) {
+        if (!na || !nb) return set_err(VT_ERR_INVALID_ARG, "chips: the bf16 kind needs norm_a and norm_b");
+        for (int c = 0; c < 3; ++c) {
+            if (!std::isfinite(na[c]) || !std::isfinite(nb[c])) return set_err(VT_ERR_INVALID_ARG, "chips: norms must be finite");
+            a3[c] = na[c]; b3[c] = nb[c];
+        }
+    }
+    if (chip_capable) {
+        if (size != chip_size || kind != chip_kind || memcmp(a3, chip_na, sizeof(a3)) != 0 || memcmp(b3, chip_nb, sizeof(b3)) != 0)
+            return set_err(VT_ERR_INVALID_ARG, "chips: the engine's chips are fixed at size %d, kind %d and the norms of the "
+                           "first enable", chip_size, chip_kind);
+        return VT_OK;
+    }
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    const size_t extra = chip_store_bytes_of(B, size, kind), cb = chip_bytes_of(size, kind);
+    if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
+        return set_err(VT_ERR_OOM, "chips need %.2f MiB more HBM for the chip store; vt_config.max_device_mib allows %.1f "
+                       "in all", extra / 1048576.0, max_device_bytes / 1048576.0);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && extra > free_b)
+        return set_err(VT_ERR_OOM, "chips need %.2f MiB more HBM; %.1f MiB are free", extra / 1048576.0, free_b / 1048576.0);
+    uint8_t* chips = nullptr;       // one allocation: [B][cb] chips | [B] infos (cb is a multiple of 192: the infos are aligned)
+    ChipPolicy* pol = nullptr;
+    hipError_t he = dalloc0(&chips, (cb + sizeof(vt_chip_info)) * (size_t)B, stream);
+    if (he == hipSuccess) he = dalloc0(&pol, (size_t)B, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    auto undo = [&] {
+        if (chips) (void)hipFree(chips);
+        if (pol) (void)hipFree(pol);
+        d_chips = nullptr; d_chip_infos = nullptr; d_chip_policy = nullptr;
+        chip_capable = false;
+        chip_size = chip_kind = 0;
+    };
+    if (he != hipSuccess) {
+        undo();
+        return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "chips: %s", hipGetErrorString(he));
+    }
+    // the captured passes are those of an engine without chips: drop them and capture again, as enable_refresh does
+    d_chips = chips; d_chip_infos = reinterpret_cast<vt_chip_info*>(chips + cb * (size_t)B); d_chip_policy = pol;
+    chip_size = size; chip_kind = kind;
+    memcpy(chip_na, a3, sizeof(a3)); memcpy(chip_nb, b3, sizeof(b3));
+    chip_capable = true;
+    drop_graphs();
+    if (int rc = capture_all_graphs()) {
+        char keep[512];
+        memcpy(keep, vt_err_text(), sizeof(keep));
+        drop_graphs();
+        undo();
+        (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
+        memcpy(vt_err_text(), keep, sizeof(keep));
+        return rc;
+    }
+    return VT_OK;
+}
+
+int Engine::set_chips(int s, float factor, int period, int phase) {
+    if (!chip_capable) return set_err(VT_ERR_INVALID_ARG, "chips: not enabled on this engine (vt_group_enable_chips)");
+    if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "chips: stream %d out of range (-1..%d)", s, B - 1);
+    if (!(factor == 0.0f || (factor >= 0.5f && factor <= 4.0f)))     // a NaN fails both
+        return set_err(VT_ERR_INVALID_ARG, "chips: factor must be 0 (off) or in 0.5..4");
+    if (period < 1 || period > VT_CHIP_MAX_PERIOD)
+        return set_err(VT_ERR_INVALID_ARG, "chips: period %d (1..%d)", period, VT_CHIP_MAX_PERIOD);
+    if (phase < 0 || phase >= period) return set_err(VT_ERR_INVALID_ARG, "chips: phase %d (0..period-1 = %d)", phase, period - 1);
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    const ChipPolicy p{factor == 0.0f ? 0.0f : factor, period, phase, 0};
+    for (int b = s < 0 ? 0 : s; b < (s < 0 ? B : s + 1); ++b)
+        HIPCHK(hipMemcpy(d_chip_policy + b, &p, sizeof(p), hipMemcpyHostToDevice));
+    return VT_OK;
+}
+
+// behind every queued pass on the group's stream: ONE device-to-host copy of the store's bytes from the first listed
+// stream's chip (infos only: info) to the last listed stream's info (chips only: chip) into the pinned mirror, then handed out
+int Engine::read_chips(const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos) {
+    if (!chip_capable) return set_err(VT_ERR_INVALID_ARG, "chips: not enabled on this engine (vt_group_enable_chips)");
+    const size_t cb = chip_bytes(), ib = sizeof(vt_chip_info), info0 = (size_t)B * cb;
+    if (n < 1 || n > B || (out && out_stride < cb) || (!out && !infos))
+        return set_err(VT_ERR_INVALID_ARG, "read_chips: bad count, stride or no output");
+    int lo = B, hi = -1;
+    for (int i = 0; i < n; ++i) {
+        const int s = streams ? streams[i] : i;
+        if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "read_chips: stream %d out of range (0..%d)", s, B - 1);
+        lo = std::min(lo, s); hi = std::max(hi, s);
+    }
+    DEVICE_SCOPE(device);
+    if (!h_chip_stage) HIPCHK(hipHostMalloc((void**)&h_chip_stage, (size_t)B * (cb + ib), hipHostMallocDefault));
+    const size_t from = out ? (size_t)lo * cb : info0 + (size_t)lo * ib;
+    const size_t to = infos ? info0 + (size_t)(hi + 1) * ib : (size_t)(hi + 1) * cb;
+    HIPCHK(hipMemcpyAsync(h_chip_stage + from, d_chips + from, to - from, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < n; ++i) {
+        const int s = streams ? streams[i] : i;
+        if (out) memcpy((uint8_t*)out + (size_t)i * out_stride, h_chip_stage + (size_t)s * cb, cb);
+        if (infos) memcpy(infos + i, h_chip_stage + info0 + (size_t)s * ib, ib);
+    }
     return VT_OK;
 }
 

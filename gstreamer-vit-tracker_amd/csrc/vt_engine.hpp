@@ -189,6 +189,28 @@ struct Engine {
     int set_refresh(int stream, int period, float min_score);     // stream -1: all
     int refresh_stats(int stream, vt_refresh_stats* out);
     int reset_refresh_tickets();                  // wherever a pass may have been abandoned half-way
+    // target chips (k_chip.hip). The first enable fixes the chip side and kind, allocates the store
+    // [B][chip_bytes] + [B] infos + [B] policies and makes the engine chip-capable for good: every pass runs the chip launch
+    // behind its decode (and behind the refresh launch). Engines that never enable launch what they always did.
+    bool chip_capable = false;
+    int chip_size = 0, chip_kind = 0;
+    float chip_na[3] = {1.0f, 1.0f, 1.0f}, chip_nb[3] = {0.0f, 0.0f, 0.0f};
+    uint8_t* d_chips = nullptr;                   // ONE allocation: [B][chip_bytes()], then the [B] infos
+    vt_chip_info* d_chip_infos = nullptr;         // [B], inside d_chips behind the chips
+    ChipPolicy* d_chip_policy = nullptr;          // [B], written by set_chips only
+    uint8_t* h_chip_stage = nullptr;              // pinned mirror of the store for read_chips, allocated by its first call
+    static size_t chip_bytes_of(int size, int kind) { return (size_t)size * size * (kind == VT_CHIP_NORM_BF16 ? 6 : 3); }
+    size_t chip_bytes() const { return chip_capable ? chip_bytes_of(chip_size, chip_kind) : 0; }
+    static size_t chip_store_bytes_of(int B, int size, int kind) {
+        return (size_t)B * (chip_bytes_of(size, kind) + sizeof(vt_chip_info) + sizeof(ChipPolicy));
+    }
+    // HBM of the optional features this engine has enabled, beside activation_bytes() under max_device_mib
+    size_t feature_bytes() const {
+        return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0);
+    }
+    int enable_chips(int size, int kind, const float* na, const float* nb);   // outside any update: the store, graphs recaptured
+    int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
+    int read_chips(const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)

@@ -71,9 +71,9 @@ static int cmp_double(const void* a, const void* b) {
 
 int main(int argc, char** argv) {
     if (argc >= 2 && strcmp(argv[1], "sizes") == 0) {
-        printf("vt_bbox %zu vt_result %zu vt_config %zu vt_model_info %zu vt_frame %zu abi %d max_streams %d vt_candidate %zu vt_refresh_stats %zu vt_snapshot_desc %zu\n",
+        printf("vt_bbox %zu vt_result %zu vt_config %zu vt_model_info %zu vt_frame %zu abi %d max_streams %d vt_candidate %zu vt_refresh_stats %zu vt_snapshot_desc %zu vt_chip_info %zu\n",
                sizeof(vt_bbox), sizeof(vt_result), sizeof(vt_config), sizeof(vt_model_info), sizeof(vt_frame),
-               VT_ABI_VERSION, VT_MAX_STREAMS, sizeof(vt_candidate), sizeof(vt_refresh_stats), sizeof(vt_snapshot_desc));
+               VT_ABI_VERSION, VT_MAX_STREAMS, sizeof(vt_candidate), sizeof(vt_refresh_stats), sizeof(vt_snapshot_desc), sizeof(vt_chip_info));
         return 0;
     }
     if (argc != 12 || (strcmp(argv[1], "run") != 0 && strcmp(argv[1], "threads") != 0)) {

@@ -436,6 +436,69 @@ int vt_template_refresh_stats(vt_tracker* t, vt_refresh_stats* out);
 int vt_group_set_template_refresh(vt_group* g, int stream /* -1: all */, int period, float min_score);
 int vt_group_template_refresh_stats(vt_group* g, int stream, vt_refresh_stats* out);
 
+/* ---- target chips -----------------------------------------------------------------------------
+ * An engine answers where the target is; a chip answers what it looks like now: a resized crop of the stream's frame at
+ * the box the update committed, cut on the DEVICE behind the decode and inside the pass - full, subset, candidate and
+ * pipelined passes alike - for a re-identification or classification network, an operator's thumbnail or a zoomed
+ * picture-in-picture. The host neither crops 1080p frames on the CPU nor pushes pixels over the link a second time.
+ * Per ENGINE, fixed by the first vt_group_enable_chips: the chip side C (a multiple of 8, 32..512) and the kind:
+ *   VT_CHIP_NORM_BF16  planar [3][C][C] bf16, out = bf16(v * norm_a[c] + norm_b[c]) - the CALLER's normalisation, not the
+ *                      tracker's;                                                              chip_bytes = 6 C^2
+ *   VT_CHIP_RGB8       packed [C][C][3] u8, out = (uint8)min(max(rintf(v), 0), 255);           chip_bytes = 3 C^2
+ * v is the crop's bilinear value: geometry, tap order and float operation order of the tracker's own crops (taps outside
+ * the frame are black), with (factor, C) in place of the search crop's (4, search_size).
+ * Per STREAM a policy (vt_group_set_chips): factor (0 = off, else finite in 0.5..4: the crop side is factor * sqrt(w * h)
+ * of the new box), period >= 1 (at most 1,000,000) and phase in 0..period-1. The timing is stateless: a chip is due when
+ * frames_done % period == phase (frames_done: the stream's updates since init, this one included).
+ * After an update of the stream with result r that left the state st, a chip is cut iff ALL of:
+ *   1. factor > 0 and the chip is due;   2. in a candidate pass: the slot is its stream's winner;
+ *   3. the pass's search crop met no window miss (a speculative pipelined pass that will be redone cuts nothing; its redo
+ *      does);
+ *   4. the chip's tap rectangle at st.box lies inside the tap rectangle of the search crop the pass sampled (rule 6 of
+ *      template refresh with (factor, C) in place of (2, template_size)); else status = 2 and nothing is cut;
+ *   5. the in-frame part of that rectangle lies inside the window the pass's frame stores (rule 7 of template refresh: a
+ *      speculative pipelined window that fails is reported as a window miss, the pass is redone with an exact window and
+ *      the redo cuts the chip).
+ * There is no success rule: after a failed update st.box is the last good box, the chip is cut there and info.success
+ * says so. Every pass of a chip-capable engine writes the vt_chip_info of each of its streams with factor > 0 (the winner's
+ * in a candidate pass), whether or not a chip is cut; the chip bytes are written only when status == 1. Where status != 1
+ * the buffer holds an EARLIER cut - after a redone pipelined pass possibly that of the abandoned speculative pass -: the
+ * record is what says whether the bytes are current, never the bytes. A stream with factor 0 keeps its record and its bytes untouched.
+ * The first enable makes the engine chip-capable for good: it allocates the store - one chip buffer, one info and one
+ * policy per stream, within vt_config.max_device_mib, else VT_ERR_OOM and nothing changes - and recaptures the engine's
+ * graphs; from then on every pass carries one more launch. Engines that never enable launch what they always did.
+ * Snapshots (below) carry neither the chip policy nor chips: a stream imported into an engine takes the policy its slot
+ * there has. */
+typedef enum vt_chip_kind { VT_CHIP_NORM_BF16 = 0, VT_CHIP_RGB8 = 1 } vt_chip_kind;
+typedef struct vt_chip_info {       /* 48 bytes */
+    int32_t status;                 /* 0: not due (or the pass is being redone), 1: cut by this pass, 2: due, skipped by rule 4 */
+    int32_t frames_done;            /* of the update that wrote this record */
+    int32_t success; float score;   /* that update's result */
+    int32_t box[4];                 /* st.box: x, y, width, height the chip is (or would be) cut at */
+    float geo[3];                   /* the chip crop's geometry: x0m, y0m, scale (source pixels per chip pixel) */
+    int32_t reserved[1];
+} vt_chip_info;
+/* VT_ERR_INVALID_ARG, nothing changed: size not a multiple of 8 in 32..512, an unknown kind, a non-finite norm (bf16 kind;
+ * the norms are ignored for VT_CHIP_RGB8 and may be null), a second enable with other parameters (the same: VT_OK), a
+ * pipelined host pass outstanding. */
+int vt_group_enable_chips(vt_group* g, int size, int kind, const float norm_a[3], const float norm_b[3]);
+/* VT_ERR_INVALID_ARG, nothing changed: a bad stream, a NaN or a factor outside {0} and 0.5..4, period < 1 or above
+ * 1,000,000, phase outside 0..period-1, a call before the enable, a pipelined host pass outstanding. */
+int vt_group_set_chips(vt_group* g, int stream /* -1: all */, float factor, int period, int phase);
+/* Chips and infos of streams[0..n) (null: streams 0..n-1) to the host: chip i at out + i * out_stride (out_stride >=
+ * chip_bytes; out may be null: infos only), infos[i] (may be null). Ordered on the group's stream behind every queued
+ * pass, synchronous, ONE device-to-host copy through pinned staging of the call's own (allocated on first use, outside
+ * max_device_mib like the snapshot staging). */
+int vt_group_read_chips(vt_group* g, const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos);
+/* Device addresses of the store for a consumer on the same GPU: chip of stream s at *d_chips + s * *stride_bytes, its
+ * info at (*d_infos)[s] (any out pointer may be null). ORDERING: the contents are those of the last pass once
+ * vt_group_wait / vt_group_wait_next / a synchronous update has returned, and stay valid until the next enqueue of a pass
+ * on this group; a consumer on another HIP stream orders itself behind that return. */
+int vt_group_chips_device(vt_group* g, void** d_chips, size_t* stride_bytes, const vt_chip_info** d_infos);
+int vt_enable_chip(vt_tracker* t, int size, int kind, const float norm_a[3], const float norm_b[3]);
+int vt_set_chip(vt_tracker* t, float factor, int period, int phase);
+int vt_read_chip(vt_tracker* t, void* out, vt_chip_info* info);
+
 /* ---- stream snapshots: export, import and copy a stream between engines ---------------------------
  * A stream is a box a person chose (src/selection_state.rs) plus the template cut at that box (tracker.init,
  * src/tracker_context.rs:88) - with template refresh also the product of hours of tracking. A snapshot takes that state
