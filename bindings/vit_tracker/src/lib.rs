@@ -254,6 +254,28 @@ impl VitTrack {
         Ok(info)
     }
 
+    /// The response-peaks policy (vt_set_peaks): `max_peaks` 0 switches the list off, else (1..=8) every update lists up to
+    /// that many maxima of the score map with their decoded boxes, each suppressing the square of `radius` (1..=4) cells
+    /// around it; a peak behind the first needs a response of at least `min_resp` (0..=1).
+    pub fn set_peaks(&mut self, max_peaks: i32, radius: i32, min_resp: f32) -> Result<(), TrackError> {
+        let rc = unsafe { sys::vt_set_peaks(self.h, max_peaks, radius, min_resp) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(())
+    }
+
+    /// The peaks of the last update (vt_last_peaks): peak 0 is the update's own box; a close runner-up says how near the
+    /// call was. A peak's box can be handed to a candidate slot as it is.
+    pub fn last_peaks(&mut self) -> Result<sys::VtPeaks, TrackError> {
+        let mut p = sys::VtPeaks::default();
+        let rc = unsafe { sys::vt_last_peaks(self.h, &mut p) };
+        if rc != sys::VT_OK {
+            return Err(last(rc));
+        }
+        Ok(p)
+    }
+
     pub fn template_refresh_stats(&mut self) -> Result<sys::VtRefreshStats, TrackError> {
         let mut st = sys::VtRefreshStats::default();
         let rc = unsafe { sys::vt_template_refresh_stats(self.h, &mut st) };
@@ -419,6 +441,32 @@ pub unsafe fn group_set_template_refresh(g: *mut sys::vt_group, stream: i32, per
 /// `g` is a live group handle.
 pub unsafe fn group_set_chips(g: *mut sys::vt_group, stream: i32, factor: f32, period: i32, phase: i32) -> Result<(), TrackError> {
     let rc = sys::vt_group_set_chips(g, stream, factor, period, phase);
+    if rc != sys::VT_OK {
+        return Err(last(rc));
+    }
+    Ok(())
+}
+
+/// The response-peaks policy of one camera of a group, or of all with `stream = -1` (vt_group_set_peaks). The first call
+/// with `max_peaks > 0` makes the engine peaks-capable. Refused while a pipelined pass is outstanding.
+///
+/// # Safety
+/// `g` is a live group handle.
+pub unsafe fn group_set_peaks(g: *mut sys::vt_group, stream: i32, max_peaks: i32, radius: i32, min_resp: f32) -> Result<(), TrackError> {
+    let rc = sys::vt_group_set_peaks(g, stream, max_peaks, radius, min_resp);
+    if rc != sys::VT_OK {
+        return Err(last(rc));
+    }
+    Ok(())
+}
+
+/// The peak records of the last collected pass, one per slot in the pass's order, into `out` (vt_group_last_peaks).
+///
+/// # Safety
+/// `g` is a live group handle.
+pub unsafe fn group_last_peaks(g: *mut sys::vt_group, out: &mut [sys::VtPeaks]) -> Result<(), TrackError> {
+    let n = i32::try_from(out.len()).unwrap_or(i32::MAX);
+    let rc = sys::vt_group_last_peaks(g, out.as_mut_ptr(), n);
     if rc != sys::VT_OK {
         return Err(last(rc));
     }

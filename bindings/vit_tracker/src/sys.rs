@@ -173,6 +173,30 @@ pub struct VtChipInfo {
 pub const VT_CHIP_NORM_BF16: c_int = 0;
 pub const VT_CHIP_RGB8: c_int = 1;
 
+pub const VT_PEAKS_MAX: usize = 8;
+
+/// ≙ vt_peak: one maximum of a slot's response map with its decoded box (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct VtPeak {
+    pub score: f32,
+    pub resp: f32,
+    pub r#box: [f32; 4],
+    pub cell: i32,
+    pub reserved: i32,
+}
+
+/// ≙ vt_peaks: the peaks a pass listed for one of its slots (272 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct VtPeaks {
+    pub n: i32,
+    pub stream: i32,
+    pub frames_done: i32,
+    pub radius: i32,
+    pub peak: [VtPeak; VT_PEAKS_MAX],
+}
+
 /// ≙ vt_draw_cmd
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -292,6 +316,10 @@ extern "C" {
     pub fn vt_enable_chip(t: *mut vt_tracker, size: c_int, kind: c_int, norm_a: *const f32, norm_b: *const f32) -> c_int;
     pub fn vt_set_chip(t: *mut vt_tracker, factor: f32, period: c_int, phase: c_int) -> c_int;
     pub fn vt_read_chip(t: *mut vt_tracker, out: *mut c_void, info: *mut VtChipInfo) -> c_int;
+    pub fn vt_group_set_peaks(g: *mut vt_group, stream: c_int, max_peaks: c_int, radius: c_int, min_resp: f32) -> c_int;
+    pub fn vt_group_last_peaks(g: *mut vt_group, out: *mut VtPeaks, n: c_int) -> c_int;
+    pub fn vt_set_peaks(t: *mut vt_tracker, max_peaks: c_int, radius: c_int, min_resp: f32) -> c_int;
+    pub fn vt_last_peaks(t: *mut vt_tracker, out: *mut VtPeaks) -> c_int;
     pub fn vt_group_host_redos(g: *const vt_group) -> c_int;
     pub fn vt_group_graph_captures(g: *const vt_group) -> c_int;
 

@@ -100,6 +100,18 @@ class CChipInfo(Structure):
 
 CHIP_NORM_BF16, CHIP_RGB8 = 0, 1     # vt_chip_kind
 
+PEAKS_MAX = 8                        # VT_PEAKS_MAX
+
+
+class CPeak(Structure):
+    """vt_peak (32 bytes): one maximum of a slot's response map with its decoded box"""
+    _fields_ = [("score", c_float), ("resp", c_float), ("box", c_float * 4), ("cell", c_int32), ("reserved", c_int32)]
+
+
+class CPeaks(Structure):
+    """vt_peaks (272 bytes): the peaks a pass listed for one of its slots"""
+    _fields_ = [("n", c_int32), ("stream", c_int32), ("frames_done", c_int32), ("radius", c_int32), ("peak", CPeak * PEAKS_MAX)]
+
 
 class CDrawCmd(Structure):
     _fields_ = [("type", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
@@ -136,6 +148,7 @@ EXPORTS = [
     "vt_group_template_refresh_stats",
     "vt_group_enable_chips", "vt_group_set_chips", "vt_group_read_chips", "vt_group_chips_device",
     "vt_enable_chip", "vt_set_chip", "vt_read_chip",
+    "vt_group_set_peaks", "vt_group_last_peaks", "vt_set_peaks", "vt_last_peaks",
     "vt_snapshot_bytes", "vt_group_snapshot_bytes", "vt_snapshot_info", "vt_group_export_stream",
     "vt_group_import_stream", "vt_group_copy_stream", "vt_export_state", "vt_import_state",
 ]
@@ -144,7 +157,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16", "vt_op_gemm_bench", "vt_op_qkv_bf16", "vt_op_attention_bf16",
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
-    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode",
+    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks",
 ]
 
 
@@ -241,6 +254,10 @@ def lib():
     L.vt_enable_chip.argtypes = [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float)]
     L.vt_set_chip.argtypes = [c_void_p, c_float, c_int, c_int]
     L.vt_read_chip.argtypes = [c_void_p, c_void_p, POINTER(CChipInfo)]
+    L.vt_group_set_peaks.argtypes = [c_void_p, c_int, c_int, c_int, c_float]
+    L.vt_group_last_peaks.argtypes = [c_void_p, c_void_p, c_int]
+    L.vt_set_peaks.argtypes = [c_void_p, c_int, c_int, c_float]
+    L.vt_last_peaks.argtypes = [c_void_p, c_void_p]
     L.vt_group_host_redos.argtypes = [c_void_p]
     L.vt_group_graph_captures.argtypes = [c_void_p]
     L.vt_group_hip_stream.argtypes = [c_void_p]
@@ -304,6 +321,8 @@ def ops_lib():
     L.vt_op_head_decode.argtypes = [c_int, c_int, u16p, u16p, fp, fp, fp, fp, c_void_p, c_int, POINTER(c_int32), c_float,
                                     c_int, c_int, c_int, c_int, c_int, c_int, fp, c_void_p, c_void_p, c_void_p,
                                     POINTER(ctypes.c_uint32)]
+    L.vt_op_response_peaks.argtypes = [c_int, fp, fp, c_void_p, c_int, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int,
+                                       c_int, c_void_p, c_void_p]
     _ops = L
     return L
 
@@ -719,6 +738,16 @@ class VitTrack:
         size, kind, stride, ptr, infos = _chip_shape(lib().vt_tracker_as_group(self._h))
         return DeviceChips(ptr, stride, infos, 1, size, kind)
 
+    def set_peaks(self, max_peaks: int, radius: int = 2, min_resp: float = 0.0) -> None:
+        """vt_set_peaks: see Group.set_peaks"""
+        _check(lib().vt_set_peaks(self._h, int(max_peaks), int(radius), float(min_resp)))
+
+    def last_peaks(self):
+        """vt_last_peaks -> PEAKS_DTYPE array of one record: the peaks of the last update"""
+        out = np.zeros(1, PEAKS_DTYPE)
+        _check(lib().vt_last_peaks(self._h, out.ctypes.data))
+        return out
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -1132,6 +1161,24 @@ class Group:
         size, kind, stride, ptr, infos = _chip_shape(self._h)
         return DeviceChips(ptr, stride, infos, self.streams, size, kind)
 
+    def set_peaks(self, max_peaks: int, radius: int = 2, min_resp: float = 0.0, stream: int | None = None) -> None:
+        """vt_group_set_peaks: the response-peaks policy of `stream` (None: every stream). max_peaks 0 switches it off, else
+        (1..8) every pass lists up to that many maxima of the stream's Hann-weighted score map with their decoded boxes:
+        greedy, each peak suppressing the (2 radius + 1)^2 square of cells around it (radius 1..4); a peak behind the first
+        needs a response of at least min_resp (0..1). The first call with max_peaks > 0 makes the engine peaks-capable
+        (records within max_device_mib, graphs recaptured); refused while a pipelined pass is outstanding."""
+        _check(lib().vt_group_set_peaks(self._h, -1 if stream is None else int(stream), int(max_peaks), int(radius), float(min_resp)))
+
+    def last_peaks(self, n: int | None = None):
+        """vt_group_last_peaks: the records of the pass whose results the last wait / wait_next / synchronous update
+        returned, in that pass's slot order -> PEAKS_DTYPE array [n] (None: one per stream; entries beyond the pass's size stay
+        zero). rec["n"] == 0: the slot's stream has the policy off, or the slot lost a candidate pass. A peak's box (x1, y1,
+        w, h floats) can be passed to a candidate slot as it is."""
+        n = self.streams if n is None else int(n)
+        out = np.zeros(max(n, 1), PEAKS_DTYPE)
+        _check(lib().vt_group_last_peaks(self._h, out.ctypes.data if n > 0 else None, n))
+        return out[:n]
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""
@@ -1357,6 +1404,45 @@ def op_headconv(t_bf16_bits, w_bf16_bits, bias, B, grid, conv3x3=True, R=0, ncb=
 
 # vt_result as the decode writes it (include/vittrack_hip.h), 6 words
 RESULT_DTYPE = np.dtype([("success", "<i4"), ("score", "<f4"), ("bbox", "<i4", 4)])
+
+
+# vt_peak / vt_peaks (include/vittrack_hip.h): 32 / 272 bytes; vt_peaks_policy: the 16-byte per-stream policy record
+PEAK_DTYPE = np.dtype([("score", "<f4"), ("resp", "<f4"), ("box", "<f4", 4), ("cell", "<i4"), ("reserved", "<i4")])
+PEAKS_DTYPE = np.dtype([("n", "<i4"), ("stream", "<i4"), ("frames_done", "<i4"), ("radius", "<i4"), ("peak", PEAK_DTYPE, PEAKS_MAX)])
+PEAKS_POLICY_DTYPE = np.dtype([("max_peaks", "<i4"), ("radius", "<i4"), ("min_resp", "<f4"), ("reserved", "<i4")])
+
+
+def op_response_peaks(head_out, hann, states, policies, B, grid, slot_stream=None, winner=None, mirror_fill=0xA5, device=0):
+    """vt_op_response_peaks: the response-peaks launch (k_peaks.hip) on given operands, nothing else. head_out [B*ns][8]
+    float32 logits by slot, hann [ns], states: snapshot.STATE records by stream, policies: PEAKS_POLICY_DTYPE records by
+    stream (or (max_peaks, radius, min_resp) for all), slot_stream [B]: slot -> stream (None: the identity), winner [B]: a
+    candidate pass's winner table (None: every slot lists). Device records and pinned mirror start filled with the byte
+    mirror_fill. -> dict(records / host_records [B] PEAKS_DTYPE, states [n_states] as they came back)"""
+    from .snapshot import STATE
+    ho = np.ascontiguousarray(head_out, np.float32)
+    ns = grid * grid
+    assert ho.shape == (B * ns, 8)
+    hann = np.ascontiguousarray(hann, np.float32).reshape(-1)
+    assert hann.shape == (ns,)
+    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    if isinstance(policies, tuple):
+        pol = np.zeros(len(st), PEAKS_POLICY_DTYPE)
+        pol["max_peaks"], pol["radius"], pol["min_resp"] = policies
+    else:
+        pol = np.ascontiguousarray(policies, PEAKS_POLICY_DTYPE).reshape(-1)
+    assert len(pol) == len(st)
+    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
+    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
+    assert (smap is None or smap.shape == (B,)) and (win is None or win.shape == (B,))
+    fill = lambda: np.frombuffer(bytes([mirror_fill]) * (B * PEAKS_DTYPE.itemsize), PEAKS_DTYPE).copy()
+    out = dict(records=fill(), host_records=fill())
+    i32 = POINTER(c_int32)
+    _check_op(ops_lib().vt_op_response_peaks(
+        device, _f32(ho), _f32(hann), st.ctypes.data_as(c_void_p), len(st), pol.ctypes.data_as(c_void_p),
+        smap.ctypes.data_as(i32) if smap is not None else None, win.ctypes.data_as(i32) if win is not None else None,
+        B, grid, out["records"].ctypes.data_as(c_void_p), out["host_records"].ctypes.data_as(c_void_p)))
+    out["states"] = st
+    return out
 
 
 def op_head_decode(t_bf16_bits, w4, b4, hann, states, B, grid, form=0, w3_bf16_bits=None, b3=None, slot_stream=None,

@@ -587,7 +587,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
     // The stream of a subset pass's slot comes from the pass's map through an ORDINARY load: the compiler waits for it
     // itself before the address it feeds; it is not one of the hand-counted asm loads.
     uint2 pre_s[11], pre_o[2];                     // 8-B loads: both structs are 8-B aligned in their arrays
-    static_assert(sizeof(StreamState) == 88 && sizeof(PassOut) == 16, "prefetch layout");
+    static_assert(sizeof(StreamState) == 88 && offsetof(PassOut, host_states) == 8 && sizeof(PassOut) >= 16, "prefetch layout");      // the decode's two pointers lead
     int sb = b;                                    // thread 0: the stream this slot works for
     if constexpr (TAIL) {
         if (tid == 0) {

@@ -392,7 +392,7 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
     PassShape ps;       // the full pass, built as Engine::enqueue builds it, launched eagerly under the profiler
-    if (int rc = e->prepare_pass(nullptr, frames, n, nullptr, nullptr, &ps)) return rc;
+    if (int rc = e->prepare_pass(nullptr, frames, n, nullptr, nullptr, nullptr, &ps)) return rc;
     Profiler prof;
     for (int it = 0; it < iters; ++it)
         if (int rc = e->run_pass(&prof, ps)) return rc;
@@ -643,6 +643,24 @@ int vt_set_chip(vt_tracker* t, float factor, int period, int phase) try {
 int vt_read_chip(vt_tracker* t, void* out, vt_chip_info* info) try {
     if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
     return t->e->read_chips(nullptr, 1, out, t->e->chip_bytes(), info);
+} VT_NOTHROW_INT
+
+int vt_group_set_peaks(vt_group* g, int stream, int max_peaks, int radius, float min_resp) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    if (int rc = refuse_while_pipelined(g->e, "set_peaks")) return rc;
+    return g->e->set_peaks(stream, max_peaks, radius, min_resp);
+} VT_NOTHROW_INT
+int vt_group_last_peaks(vt_group* g, vt_peaks* out, int n) try {
+    if (!g) return set_err(VT_ERR_INVALID_ARG, "null group");
+    return g->e->last_peaks(out, n);
+} VT_NOTHROW_INT
+int vt_set_peaks(vt_tracker* t, int max_peaks, int radius, float min_resp) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    return vt_group_set_peaks(&t->view, 0, max_peaks, radius, min_resp);
+} VT_NOTHROW_INT
+int vt_last_peaks(vt_tracker* t, vt_peaks* out) try {
+    if (!t) return set_err(VT_ERR_INVALID_ARG, "null tracker");
+    return t->e->last_peaks(out, 1);
 } VT_NOTHROW_INT
 
 int vt_group_host_redos(const vt_group* g) { return g ? (int)g->e->host_redos : 0; }

@@ -314,6 +314,7 @@ hipError_t launch_overlay_rgb(uint8_t* rgb, int width, int height, int stride, c
 struct PassOut {
     vt_result* host_results;    // [slots of the pass] or null
     StreamState* host_states;   // [B] (by stream) or null
+    vt_peaks* host_peaks;       // [slots of the pass] or null: the response-peaks launch's records (k_peaks.hip)
 };
 
 struct DecodeArgs {
@@ -385,6 +386,30 @@ struct ChipArgs {
 // pass's frame at the committed box, side C, kind VT_CHIP_NORM_BF16 (na, nb: the caller's) or VT_CHIP_RGB8
 hipError_t launch_target_chips(const ChipArgs& a, int C, int kind, const float* na, const float* nb, int search_size,
                                int tier, bool any_layout, hipStream_t st);
+
+// ---- response peaks (k_peaks.hip) ---------------------------------------------------------------------------------------
+// per stream, device memory, written by the host only (never rewound, not part of a snapshot)
+struct PeaksPolicy {
+    int32_t max_peaks;          // 0: off, else 1..VT_PEAKS_MAX
+    int32_t radius;             // 1..4: half side of the suppression square
+    float min_resp;             // a peak behind the first needs resp > 0 and resp >= min_resp
+    int32_t reserved;
+};
+struct PeaksArgs {
+    const float* head_out;      // [n * ns][8] by slot: the logits the decode of this pass read
+    const float* hann;          // [ns]
+    const StreamState* states;  // [B] by stream, as decode / cand_commit (and the refresh and chip launches) left them
+    const int32_t* slot_stream; // [n] slot -> stream, null: the identity
+    const int32_t* winner;      // candidate pass: [n] the winning slot of slot i's stream (only winners list); else null
+    const PeaksPolicy* policy;  // [B] by stream
+    vt_peaks* records;          // [n] by slot (device)
+    const PassOut* out;         // device copy of the pass's PassOut: host_peaks [n] by slot, or null
+    int n, ns, grid;
+};
+// behind the decode (candidate pass: behind the commit; behind the refresh and chip launches where there are any): per
+// slot up to VT_PEAKS_MAX maxima of the response map with their decoded boxes - DESIGN.md section 3 "Response peaks".
+// One workgroup per slot; writes the slot's record (device + pinned host) and nothing else.
+hipError_t launch_response_peaks(const PeaksArgs& a, hipStream_t st);
 
 // The head's convolutions on the band kernel of k_head.hip: out[B*grid*grid][N] bf16 = relu(conv(in) + bias).
 // conv3x3: in [B*grid*grid][C] (ldin >= C), W [N][9*C] with column (ky*3+kx)*C + c, zero padding (zeros: >= 256 B

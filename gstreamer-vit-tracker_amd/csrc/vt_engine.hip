@@ -37,10 +37,11 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy};     // d_chip_infos: part of d_chips
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
+    if (h_peaks) (void)hipHostFree(h_peaks);
     if (h_cands) (void)hipHostFree(h_cands);
     if (h_winner) (void)hipHostFree(h_winner);
     if (h_frames) (void)hipHostFree(h_frames);
@@ -52,6 +53,7 @@ void Engine::destroy() {
         sl.arena.release();
         if (sl.h_res) (void)hipHostFree(sl.h_res);
         if (sl.h_st) (void)hipHostFree(sl.h_st);
+        if (sl.h_peaks) (void)hipHostFree(sl.h_peaks);
         if (sl.up_ev) (void)hipEventDestroy(sl.up_ev);
         if (sl.done_ev) (void)hipEventDestroy(sl.done_ev);
         sl = HostSlot();
@@ -587,6 +589,12 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
             return launch_target_chips(ca, chip_size, chip_kind, chip_na, chip_nb, d.S, ps.tier, ps.any_layout, stream);
         });
     }
+    if (peaks_capable) {    // the slots' runner-up maxima, on the logits and states the launches above left: k_peaks.hip
+        const PeaksArgs pa{d_headout, dec.hann, d_states, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_peaks_policy,
+                           d_peaks, (const PassOut*)(d_frames + B), n, d.ns, d.gs};
+        L("response_peaks", 0, (double)n * (d.ns * 8.0 * sizeof(float) + 2.0 * sizeof(vt_peaks)),
+          [&] { return launch_response_peaks(pa, stream); });
+    }
     if (lerr != hipSuccess)
         return set_err(VT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
@@ -801,7 +809,7 @@ int Engine::check_streams(const int32_t* streams, int n) const {
 // full pass: every stream's template rows in its own segment, no slot map. The pass's block (descriptors, PassOut,
 // slot map) goes up from a block of the pinned ring, behind whatever the stream is doing.
 int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                         PassShape* ps) {
+                         vt_peaks* host_pk, PassShape* ps) {
     if (int rc = check_streams(streams, n)) return rc;
     if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
     for (int i = 0; i < n; ++i)
@@ -819,7 +827,8 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
         to_desc(frames[i], hf + i);
         ps->any_layout = ps->any_layout || pix_any_layout(frames[i].format);
     }
-    *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all};
+    *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all,
+                                  peaks_capable ? (host_pk ? host_pk : h_peaks) : nullptr};
     if (!full) {
         int32_t* map = (int32_t*)((char*)hf + map_offset());
         for (int i = 0; i < n; ++i) map[i] = streams[i];
@@ -843,10 +852,11 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
 
 // The one entry every pass takes. The full pass replays its captured graph; a subset pass runs eagerly - never a
 // capture inside an update - behind the gather of its template rows.
-int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st) {
+int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
+                    vt_peaks* host_pk) {
     DEVICE_SCOPE(device);
     PassShape ps;
-    if (int rc = prepare_pass(streams, frames, n, host_res, host_st, &ps)) return rc;
+    if (int rc = prepare_pass(streams, frames, n, host_res, host_st, host_pk, &ps)) return rc;
     if (!ps.slot_stream && use_graph && !taps) {
         const PassGraph& g = graphs[ps.any_layout][ps.tier];
         if (!ps.any_layout && !g.exec)   // not reached after a successful creation (capture_all_graphs); kept as the safe path
@@ -868,8 +878,10 @@ int Engine::wait(vt_result* out, int n) {
     HIPCHK(hipStreamSynchronize(stream));
     if (out)
         for (int b = 0; b < n; ++b) out[b] = h_results[b];
-    if (host_seq == host_collected)                 // no pipelined pass owns the stream states
+    if (host_seq == host_collected) {               // no pipelined pass owns the stream states
         for (int b = 0; b < B; ++b) known[b] = h_states_all[b];
+        peaks_n = pass_n;                           // h_peaks holds the records of the pass just waited for
+    }
     return VT_OK;
 }
 
@@ -1095,6 +1107,87 @@ int Engine::read_chips(const int* streams, int n, void* out, size_t out_stride, 
     return VT_OK;
 }
 
+// ---- response peaks ----------------------------------------------------------------------------------
+
+// The policy of stream s (-1: all). The first policy with max_peaks > 0: the records and policies are allocated, the pinned
+// mirrors too, and every graph is captured again with the peaks launch in it - on the idle stream, never inside an
+// update, as enable_chips does. Nothing changes on failure.
+int Engine::set_peaks(int s, int max_peaks, int radius, float min_resp) {
+    if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "peaks: stream %d out of range (-1..%d)", s, B - 1);
+    if (max_peaks < 0 || max_peaks > VT_PEAKS_MAX)
+        return set_err(VT_ERR_INVALID_ARG, "peaks: max_peaks %d (0: off, else 1..%d)", max_peaks, VT_PEAKS_MAX);
+    if (radius < 1 || radius > 4) return set_err(VT_ERR_INVALID_ARG, "peaks: radius %d (1..4)", radius);
+    if (!(min_resp >= 0.0f && min_resp <= 1.0f))       // a NaN fails both
+        return set_err(VT_ERR_INVALID_ARG, "peaks: min_resp must be finite in 0..1");
+    if (!peaks_capable && max_peaks == 0)
+        return set_err(VT_ERR_INVALID_ARG, "peaks: not enabled on this engine (a policy with max_peaks > 0 enables it)");
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!peaks_capable) {
+        const size_t extra = peaks_bytes();
+        if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
+            return set_err(VT_ERR_OOM, "peaks need %.3f MiB more HBM for the records; vt_config.max_device_mib allows %.1f "
+                           "in all", extra / 1048576.0, max_device_bytes / 1048576.0);
+        uint8_t* store = nullptr;       // one allocation: [B] records | [B] policies, all zero (every policy off)
+        vt_peaks* hp = nullptr;
+        vt_peaks* hsp[2] = {nullptr, nullptr};
+        hipError_t he = dalloc0(&store, extra, stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(stream);
+        if (he == hipSuccess) he = hipHostMalloc((void**)&hp, sizeof(vt_peaks) * (size_t)B);
+        for (int i = 0; i < 2 && he == hipSuccess; ++i)      // pipelined slots that exist already; later ones: host_slot_prepare
+            if (hs[i].h_res) he = hipHostMalloc((void**)&hsp[i], sizeof(vt_peaks) * (size_t)B);
+        auto undo = [&] {
+            if (store) (void)hipFree(store);
+            if (hp) (void)hipHostFree(hp);
+            for (int i = 0; i < 2; ++i) {
+                if (hsp[i]) (void)hipHostFree(hsp[i]);
+                hs[i].h_peaks = nullptr;
+            }
+            d_peaks = nullptr; d_peaks_policy = nullptr; h_peaks = nullptr;
+            peaks_policy.clear();
+            peaks_capable = false;
+        };
+        if (he != hipSuccess) {
+            undo();
+            return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "peaks: %s", hipGetErrorString(he));
+        }
+        memset(hp, 0, sizeof(vt_peaks) * (size_t)B);
+        for (int i = 0; i < 2; ++i) {
+            if (hsp[i]) memset(hsp[i], 0, sizeof(vt_peaks) * (size_t)B);
+            hs[i].h_peaks = hsp[i];
+        }
+        d_peaks = reinterpret_cast<vt_peaks*>(store);
+        d_peaks_policy = reinterpret_cast<PeaksPolicy*>(store + sizeof(vt_peaks) * (size_t)B);
+        h_peaks = hp;
+        peaks_policy.assign((size_t)B, PeaksPolicy{0, 0, 0.0f, 0});
+        peaks_n = 0;
+        peaks_capable = true;
+        drop_graphs();
+        if (int rc = capture_all_graphs()) {
+            char keep[512];
+            memcpy(keep, vt_err_text(), sizeof(keep));
+            drop_graphs();
+            undo();
+            (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
+            memcpy(vt_err_text(), keep, sizeof(keep));
+            return rc;
+        }
+    }
+    const PeaksPolicy p{max_peaks, radius, min_resp == 0.0f ? 0.0f : min_resp, 0};
+    for (int b = s < 0 ? 0 : s; b < (s < 0 ? B : s + 1); ++b) {
+        HIPCHK(hipMemcpy(d_peaks_policy + b, &p, sizeof(p), hipMemcpyHostToDevice));
+        peaks_policy[(size_t)b] = p;
+    }
+    return VT_OK;
+}
+
+int Engine::last_peaks(vt_peaks* out, int n) const {
+    if (!peaks_capable) return set_err(VT_ERR_INVALID_ARG, "peaks: not enabled on this engine (vt_group_set_peaks)");
+    if (!out || n < 1) return set_err(VT_ERR_INVALID_ARG, "last_peaks: null output or n < 1");
+    for (int i = 0; i < std::min(n, peaks_n); ++i) out[i] = h_peaks[i];
+    return VT_OK;
+}
+
 // ---- candidate passes --------------------------------------------------------------------------------
 
 int check_state_box(const float* box4) {
@@ -1171,7 +1264,7 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
         map[i] = cands[i].stream;
         hc[i] = cands[i];
     }
-    *(PassOut*)(hf + B) = PassOut{h_results, nullptr};
+    *(PassOut*)(hf + B) = PassOut{h_results, nullptr, peaks_capable ? h_peaks : nullptr};
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_cands, hc, sizeof(vt_candidate) * (size_t)n, hipMemcpyHostToDevice, stream));
     HIPCHK(hipEventRecord(ring_ev[slot], stream));

@@ -206,11 +206,24 @@ struct Engine {
     }
     // HBM of the optional features this engine has enabled, beside activation_bytes() under max_device_mib
     size_t feature_bytes() const {
-        return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0);
+        return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0) +
+               (peaks_capable ? peaks_bytes() : 0);
     }
     int enable_chips(int size, int kind, const float* na, const float* nb);   // outside any update: the store, graphs recaptured
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
     int read_chips(const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos);
+    // response peaks (k_peaks.hip). The first policy with max_peaks > 0 allocates the records [B] by
+    // slot + the policies [B] by stream and makes the engine peaks-capable for good: every pass runs the peaks launch
+    // behind its decode (and behind the refresh and chip launches). Engines that never enable launch what they always did.
+    bool peaks_capable = false;
+    vt_peaks* d_peaks = nullptr;                  // ONE allocation: [B] records by slot, then the [B] policies
+    PeaksPolicy* d_peaks_policy = nullptr;        // [B] by stream, inside d_peaks; written by set_peaks only
+    std::vector<PeaksPolicy> peaks_policy;        // the host's copy (what set_peaks wrote)
+    vt_peaks* h_peaks = nullptr;                  // pinned [B]: the records of the last pass the host collected, by slot
+    int peaks_n = 0;                              // ... and that pass's slot count
+    size_t peaks_bytes() const { return (size_t)B * (sizeof(vt_peaks) + sizeof(PeaksPolicy)); }
+    int set_peaks(int stream, int max_peaks, int radius, float min_resp);     // stream -1: all; the first enable is in here
+    int last_peaks(vt_peaks* out, int n) const;
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -282,6 +295,7 @@ struct Engine {
         StageArena arena;
         vt_result* h_res = nullptr;     // the pass's results, by SLOT (list order)
         StreamState* h_st = nullptr;    // [B] by STREAM: valid at the listed streams' indices only
+        vt_peaks* h_peaks = nullptr;    // the pass's peak records, by SLOT (peaks-capable engines only)
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
         std::vector<vt_frame> host;     // the caller's frames, valid until the pass is collected
         std::vector<int32_t> list;      // the pass's streams (the identity list: the full pass)
@@ -351,13 +365,14 @@ struct Engine {
     // One pass over streams[0..n), frames[i] for streams[i]; streams == null: all B streams in order (n == B), and no
     // list is built for it. VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input (checked in
     // the order list, initialisation, frames). host_res / host_st: pinned buffers the pass's results and states are
-    // stored to (null: the engine's own h_results / h_states_all).
+    // stored to (null: the engine's own h_results / h_states_all); host_pk: the same for the peak records of a
+    // peaks-capable engine (null: h_peaks).
     int check_streams(const int32_t* streams, int n) const;
     // checks + the pass's block uploaded behind the stream's work + the last-pass record; the engine's device is current
     int prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                     PassShape* ps);
+                     vt_peaks* host_pk, PassShape* ps);
     int enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
-                StreamState* host_st = nullptr);
+                StreamState* host_st = nullptr, vt_peaks* host_pk = nullptr);
     int wait(vt_result* out, int n);
     // A candidate pass over cands[0..n) (k_cand.hip): checked (list, boxes, initialisation, frames - nothing enqueued
     // on bad input), built and launched eagerly. A list that is a plain subset pass - every stream once, no box - goes

@@ -207,8 +207,12 @@ int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxe
 // ---- pipelined host passes -------------------------------------------------------------------------
 
 static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
-    if (sl.h_res) return VT_OK;
     DEVICE_SCOPE(e->device);
+    if (e->peaks_capable && !sl.h_peaks) {      // a slot first used after the enable (set_peaks covers those that existed)
+        HIPCHK(hipHostMalloc((void**)&sl.h_peaks, sizeof(vt_peaks) * e->B));
+        memset(sl.h_peaks, 0, sizeof(vt_peaks) * e->B);
+    }
+    if (sl.h_res) return VT_OK;
     // HIP multiplexes a process's streams onto a few hardware queues (four by default): with more
     // streams than that alive - e.g. four engines, each with a compute and a copy stream - an upload
     // can share a queue with some engine's compute stream and is then ordered behind that engine's
@@ -249,6 +253,11 @@ static int update_host_pass(Engine* e, const int32_t* streams, const vt_frame* h
 
 // a collected (or redone) pass becomes what the host knows: the entries of ITS streams move, no others. The
 // decode kernel stores a slot's results by slot and its states by stream (k_head.hip: decode_box).
+static void adopt_peaks(Engine* e, const Engine::HostSlot& sl) {
+    if (!e->peaks_capable || !sl.h_peaks) return;
+    for (size_t i = 0; i < sl.list.size(); ++i) e->h_peaks[i] = sl.h_peaks[i];
+    e->peaks_n = (int)sl.list.size();
+}
 static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
     for (size_t i = 0; i < sl.list.size(); ++i) {
         const int s = sl.list[i];
@@ -256,6 +265,7 @@ static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
         e->h_states_all[s] = sl.h_st[s];        // the engine's own mirrors follow
         e->h_results[i] = sl.h_res[i];
     }
+    adopt_peaks(e, sl);                         // the peak records are by slot, like the results
 }
 
 // exact (non-speculative) synchronous pass over the slot's frames and list with the states the device holds
@@ -266,7 +276,7 @@ static int host_pass_exact_sync(Engine* e, Engine::HostSlot& sl) {
     const std::vector<float> boxes = known_boxes(e, sl.list.data(), n);
     if (int rc = stage_host_frames(e, sl.host.data(), n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
         return rc;
-    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st)) return rc;
+    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     adopt_slot(e, sl);
     sl.redone = true;
@@ -300,7 +310,7 @@ static int enqueue_host_pass(Engine* e, const int32_t* streams, const vt_frame* 
         return rc;
     HIPCHK(hipEventRecord(sl.up_ev, e->copy_stream));
     HIPCHK(hipStreamWaitEvent(e->stream, sl.up_ev, 0));          // the pass starts behind ITS upload only
-    if (int rc = e->enqueue(streams, dev.data(), n, sl.h_res, sl.h_st)) return rc;   // results land in THIS slot's buffers
+    if (int rc = e->enqueue(streams, dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks)) return rc;   // results land in THIS slot's buffers
     HIPCHK(hipEventRecord(sl.done_ev, e->stream));
     sl.host.assign(host_frames, host_frames + n);
     sl.list.assign(streams, streams + n);
@@ -484,6 +494,7 @@ int vt_group_wait_next(vt_group* g, vt_result* out, int n) try {
     // boxes the next window is planned around: this pass's - unless a younger pass was redone just
     // now, whose states are newer (host_pass_exact_sync adopted both already, in order)
     if (!(has_younger && younger.redone)) adopt_slot(e, sl);
+    else adopt_peaks(e, sl);                    // last_peaks follows the results handed out above, whichever states are newer
     sl.pending = false;
     e->host_collected += 1;
     return VT_OK;

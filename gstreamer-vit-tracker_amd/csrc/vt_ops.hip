@@ -771,4 +771,60 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The response-peaks launch on given operands: see include/vittrack_hip_ops.h. Nothing runs but launch_response_peaks.
+int vt_op_response_peaks(int device_id, const float* head_out, const float* hann, void* states, int n_states,
+                         const void* policies, const int32_t* slot_stream, const int32_t* winner, int B, int grid,
+                         vt_peaks* records, vt_peaks* host_records) try {
+    if (!head_out || !hann || !states || !policies || !records || !host_records || B < 1 || B > 4096 || grid < 1 || grid > 110 ||
+        n_states < 1)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && n_states < B) return set_err(VT_ERR_INVALID_ARG, "response_peaks: %d states for %d slots", n_states, B);
+    const PeaksPolicy* pol = (const PeaksPolicy*)policies;
+    for (int s = 0; s < n_states; ++s)
+        if (pol[s].max_peaks < 0 || pol[s].max_peaks > VT_PEAKS_MAX || pol[s].radius < 1 || pol[s].radius > 4)
+            return set_err(VT_ERR_INVALID_ARG, "response_peaks: policy %d: max_peaks %d, radius %d", s, pol[s].max_peaks, pol[s].radius);
+    for (int b = 0; b < B; ++b) {
+        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_states))
+            return set_err(VT_ERR_INVALID_ARG, "response_peaks: slot %d names stream %d of %d", b, (int)slot_stream[b], n_states);
+        if (winner && (winner[b] < 0 || winner[b] >= B))
+            return set_err(VT_ERR_INVALID_ARG, "response_peaks: winner[%d] = %d of %d slots", b, (int)winner[b], B);
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const int ns = grid * grid;
+    const size_t M = (size_t)B * ns;
+    DevBuf dho, dhann, dst, dpol, dmap, dwin, drec, dpo;
+    PinnedBuf hrec;
+    HIPCHK(dho.alloc(M * 8 * 4)); HIPCHK(dhann.alloc((size_t)ns * 4)); HIPCHK(dst.alloc((size_t)n_states * sizeof(StreamState)));
+    HIPCHK(dpol.alloc((size_t)n_states * sizeof(PeaksPolicy))); HIPCHK(drec.alloc((size_t)B * sizeof(vt_peaks)));
+    HIPCHK(dpo.alloc(sizeof(PassOut))); HIPCHK(hrec.alloc((size_t)B * sizeof(vt_peaks)));
+    HIPCHK(hipMemcpy(dho.p, head_out, M * 8 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dhann.p, hann, (size_t)ns * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dst.p, states, (size_t)n_states * sizeof(StreamState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dpol.p, policies, (size_t)n_states * sizeof(PeaksPolicy), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(drec.p, records, (size_t)B * sizeof(vt_peaks), hipMemcpyHostToDevice));
+    memcpy(hrec.p, host_records, (size_t)B * sizeof(vt_peaks));
+    const PassOut po{nullptr, nullptr, (vt_peaks*)hrec.p};
+    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
+    if (slot_stream) {
+        HIPCHK(dmap.alloc((size_t)B * 4));
+        HIPCHK(hipMemcpy(dmap.p, slot_stream, (size_t)B * 4, hipMemcpyHostToDevice));
+    }
+    if (winner) {
+        HIPCHK(dwin.alloc((size_t)B * 4));
+        HIPCHK(hipMemcpy(dwin.p, winner, (size_t)B * 4, hipMemcpyHostToDevice));
+    }
+    const PeaksArgs pa{(const float*)dho.p, (const float*)dhann.p, (const StreamState*)dst.p,
+                       slot_stream ? (const int32_t*)dmap.p : nullptr, winner ? (const int32_t*)dwin.p : nullptr,
+                       (const PeaksPolicy*)dpol.p, (vt_peaks*)drec.p, (const PassOut*)dpo.p, B, ns, grid};
+    const hipError_t e = launch_response_peaks(pa, nullptr);
+    if (e == hipErrorInvalidValue) return set_err(VT_ERR_INVALID_ARG, "response_peaks: the launcher refuses grid %d", grid);
+    HIPCHK(e);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(records, drec.p, (size_t)B * sizeof(vt_peaks), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(states, dst.p, (size_t)n_states * sizeof(StreamState), hipMemcpyDeviceToHost));
+    memcpy(host_records, hrec.p, (size_t)B * sizeof(vt_peaks));
+    return VT_OK;
+} VT_NOTHROW_INT
+
 }  // extern "C"

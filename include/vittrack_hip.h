@@ -499,6 +499,49 @@ int vt_enable_chip(vt_tracker* t, int size, int kind, const float norm_a[3], con
 int vt_set_chip(vt_tracker* t, float factor, int period, int phase);
 int vt_read_chip(vt_tracker* t, void* out, vt_chip_info* info);
 
+/* ---- response peaks: how close was the call ---------------------------------------------------
+ * A result names the box at the Hann-weighted maximum of the score map. When a look-alike crosses the target the map has
+ * two maxima of nearly equal height and the tracker jumps between them with success = 1 on both sides. An engine can list,
+ * behind the decode and inside the pass - full, subset, candidate and pipelined passes alike - up to VT_PEAKS_MAX maxima of
+ * each slot's map with their decoded boxes, into pinned host memory beside the pass's results: no device-to-host copy.
+ * DEFINITION: the specification's decode iterated. Peak k is the decode (score, float clamped box, cell) of the slot's
+ * logits with the SCORE logit of every cell (ix, iy), |ix - bx_j| <= radius and |iy - by_j| <= radius, around each earlier
+ * peak j < k set to -inf (sigmoid(-inf) = 0: such a cell has response 0, is never listed and has weight 0 in a later 3x3
+ * window), at the geo / frame size of the stream's state as the pass left it. resp = score * hann[cell] (one float
+ * multiply). Peak 0 is the update's own decode and always listed: score, box and cell are bit-identical to vt_result.score
+ * and the state's last_fbox / last_idx. Peak k >= 1 is listed while resp > 0 and resp >= min_resp (a NaN fails both);
+ * responses do not increase with k, so the list ends at the first failure. Ties go to the lowest cell.
+ * box = (x1, y1, width, height), the float clamped box: round with floor(v + 0.5) for what vt_result.bbox would hold, or
+ * pass it to vt_candidate.box as it is to have that place evaluated as a candidate slot of the next frame.
+ * Per STREAM a policy (vt_group_set_peaks) in a device array of its own, written by the host only: never rewound, not part
+ * of a snapshot. max_peaks 0 = off, else 1..VT_PEAKS_MAX; radius 1..4; min_resp finite in 0..1.
+ * The first call with max_peaks > 0 makes the engine peaks-capable for good: it allocates the records and policies within
+ * vt_config.max_device_mib (else VT_ERR_OOM and nothing changes) and recaptures the engine's graphs; from then on every pass
+ * carries one more small launch. Engines that never enable launch what they always did.
+ * RECORDS are by SLOT of a pass, like results. n == 0: the slot's stream has the policy off, or the slot lost a candidate
+ * pass (only winner[i] == i slots list peaks; their geo is the committed state's) - the other words of such a record are
+ * not written. There is no gate on window misses: a speculative pipelined pass that will be redone writes its records like
+ * its results, and the redo overwrites both. */
+#define VT_PEAKS_MAX 8
+typedef struct vt_peak {            /* 32 bytes */
+    float score, resp;              /* sigmoid of the cell's score logit; score * hann[cell] */
+    float box[4];                   /* x1, y1, width, height: the float clamped box (what last_fbox holds for peak 0) */
+    int32_t cell, reserved;         /* cell = y * score_grid + x */
+} vt_peak;
+typedef struct vt_peaks {           /* 272 bytes */
+    int32_t n, stream, frames_done, radius;   /* peaks listed; the slot's stream; the state's count after the pass; the policy's */
+    vt_peak peak[8];                /* [VT_PEAKS_MAX]: peak[0..n) in listing order, zeros behind */
+} vt_peaks;
+/* The policy of `stream` (-1: all). VT_ERR_INVALID_ARG, nothing changed: a bad stream, max_peaks outside 0..8, radius
+ * outside 1..4, min_resp NaN or outside 0..1, max_peaks = 0 before any enable, a pipelined host pass outstanding. */
+int vt_group_set_peaks(vt_group* g, int stream /* -1: all */, int max_peaks, int radius, float min_resp);
+/* The records of the pass whose results the last vt_group_wait / vt_group_wait_next / synchronous update returned, in
+ * that pass's slot order: min(n, pass size) entries. Reads the engine's host mirror only, never the device or its stream.
+ * VT_ERR_INVALID_ARG: an engine that never enabled, a null pointer, n < 1. */
+int vt_group_last_peaks(vt_group* g, vt_peaks* out, int n);
+int vt_set_peaks(vt_tracker* t, int max_peaks, int radius, float min_resp);
+int vt_last_peaks(vt_tracker* t, vt_peaks* out);
+
 /* ---- stream snapshots: export, import and copy a stream between engines ---------------------------
  * A stream is a box a person chose (src/selection_state.rs) plus the template cut at that box (tracker.init,
  * src/tracker_context.rs:88) - with template refresh also the product of hours of tracking. A snapshot takes that state

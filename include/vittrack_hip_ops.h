@@ -103,6 +103,17 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
                       const float* b4, const float* hann, void* states, int n_states, const int32_t* slot_stream,
                       float success_threshold, int B, int grid, int C, int R, int launches, int flags, float* head_out,
                       vt_result* results, vt_result* host_results, void* host_states, uint32_t* band_cnt);
+/* The response-peaks launch (csrc/k_peaks.hip, vt_group_set_peaks of vittrack_hip.h) on given operands, and nothing
+ * else: head_out [B*grid*grid][8] float logits by slot (what a decode left), hann [grid*grid], states: n_states records of
+ * 88 bytes (in and out: the launch writes none of them, they come back as they went in), policies: n_states records of 16
+ * bytes by stream (int32 max_peaks 0..8, int32 radius 1..4, float min_resp, int32 reserved), slot_stream (nullable) [B]:
+ * slot -> stream < n_states (NULL: the identity, n_states >= B), winner (nullable) [B]: a candidate pass's winner table,
+ * only slots with winner[i] == i list. In and out: records [B] (the device array) and host_records [B] (the pinned mirror
+ * the kernel stores to); their initial contents are the caller's, so untouched words are recognisable. A policy or map out
+ * of range, grid > 110: VT_ERR_INVALID_ARG. */
+int vt_op_response_peaks(int device_id, const float* head_out, const float* hann, void* states, int n_states,
+                         const void* policies, const int32_t* slot_stream, const int32_t* winner, int B, int grid,
+                         vt_peaks* records, vt_peaks* host_records);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
