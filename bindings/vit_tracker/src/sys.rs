@@ -29,6 +29,14 @@ pub const VT_PIX_RGBX: i32 = 4;
 pub const VT_PIX_BGRX: i32 = 5;
 pub const VT_PIX_NV21: i32 = 6;
 pub const VT_PIX_UYVY: i32 = 7;
+// vt_pixfmt2: further values of VtFrame.format, each a byte re-arrangement of RGB8, NV12 or YUY2 (vittrack_hip.h)
+pub const VT_PIX2_I420: i32 = 16;
+pub const VT_PIX2_YV12: i32 = 17;
+pub const VT_PIX2_P010: i32 = 18;
+pub const VT_PIX2_NV16: i32 = 19;
+pub const VT_PIX2_GRAY8: i32 = 20;
+pub const VT_PIX2_XRGB: i32 = 21;
+pub const VT_PIX2_XBGR: i32 = 22;
 
 /// ≙ vt_bbox ≙ vit_tracker::BBox (src/selection_state.rs:44, src/tracker_context.rs:85)
 #[repr(C)]

@@ -29,6 +29,8 @@ OPS_LIB_PATH = os.environ.get("VITTRACK_HIP_OPS_LIB") or os.environ.get("VITTRAC
 PIX_RGB8, PIX_NV12, PIX_YUY2 = 0, 1, 2
 # byte permutations / paddings of the three above (include/vittrack_hip.h: vt_pixfmt)
 PIX_BGR8, PIX_RGBX, PIX_BGRX, PIX_NV21, PIX_UYVY = 3, 4, 5, 6, 7
+# vt_pixfmt2: further values of vt_frame.format (three-plane 4:2:0, 16-bit NV12, 4:2:2 semi-planar, grey, pad-first RGB)
+PIX_I420, PIX_YV12, PIX_P010, PIX_NV16, PIX_GRAY8, PIX_XRGB, PIX_XBGR = 16, 17, 18, 19, 20, 21, 22
 
 
 class VtError(RuntimeError):
@@ -653,6 +655,81 @@ class UYVYFrame:
         return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
 
 
+class I420Frame:
+    """packed I420 host buffer: Y plane (stride == width), then the U plane, then the V plane, each ceil(w/2) x
+    ceil(h/2) bytes with stride ceil(w/2) (libav / GStreamer software decoders, raw .yuv files)"""
+    FMT = PIX_I420
+
+    def __init__(self, buf: np.ndarray, width: int, height: int):
+        self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+        self.w, self.h = width, height
+        assert self.buf.size >= width * height + 2 * ((width + 1) // 2) * ((height + 1) // 2)
+
+    def cframe(self) -> "CFrame":
+        c = self.buf[self.w * self.h:]
+        return CFrame(self.buf.ctypes.data, c.ctypes.data, self.w, self.h, self.w, (self.w + 1) // 2, self.FMT,
+                      0, 0, 0, 0, 0)
+
+
+class YV12Frame(I420Frame):
+    """packed YV12 host buffer: I420 with the V plane in front of the U plane"""
+    FMT = PIX_YV12
+
+
+class P010Frame:
+    """packed P010 (P012, P016) host buffer: NV12's layout with 16-bit little-endian samples, rows of 2*width bytes; only
+    the high byte of a sample is read. `buf`: uint8 bytes or uint16 samples"""
+
+    def __init__(self, buf: np.ndarray, width: int, height: int):
+        buf = np.ascontiguousarray(buf)
+        if buf.dtype == np.uint16:
+            buf = buf.astype("<u2", copy=False).view(np.uint8)
+        self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+        self.w, self.h = width, height
+        assert self.buf.size >= 2 * (width * height + ((width + 1) & ~1) * ((height + 1) // 2))
+
+    def cframe(self) -> "CFrame":
+        uv = self.buf[2 * self.w * self.h:]
+        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, 2 * self.w, 2 * ((self.w + 1) & ~1), PIX_P010,
+                      0, 0, 0, 0, 0)
+
+
+class NV16Frame:
+    """packed NV16 host buffer: Y plane then interleaved U,V with one chroma row per luma row, stride == width (even)"""
+
+    def __init__(self, buf: np.ndarray, width: int, height: int):
+        self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+        self.w, self.h = width, height
+        assert self.buf.size >= 2 * width * height and width % 2 == 0
+
+    def cframe(self) -> "CFrame":
+        uv = self.buf[self.w * self.h:]
+        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, self.w, self.w, PIX_NV16, 0, 0, 0, 0, 0)
+
+
+class Gray8Frame(_PackedFrame):
+    """(H,W) or (H,W,1) host array, one grey byte per pixel (mono and thermal cameras): r = g = b = that byte"""
+    C, FMT = 1, PIX_GRAY8
+
+    def __init__(self, a: np.ndarray, stride: int | None = None):
+        a = np.asarray(a)
+        if a.ndim == 2:     # a trailing axis of stride 1, so that a padded buffer's view stays a view
+            a = a[:, :, None]
+            if a.dtype == np.uint8 and a.strides[1] == 1:
+                a = np.lib.stride_tricks.as_strided(a, a.shape, (a.strides[0], 1, 1), writeable=False)
+        super().__init__(a, stride)
+
+
+class XRGBFrame(_PackedFrame):
+    """(H,W,4) host array x,R,G,B (ARGB: alpha ignored; GStreamer xRGB / ARGB)"""
+    C, FMT = 4, PIX_XRGB
+
+
+class XBGRFrame(_PackedFrame):
+    """(H,W,4) host array x,B,G,R (ABGR: alpha ignored; GStreamer xBGR / ABGR)"""
+    C, FMT = 4, PIX_XBGR
+
+
 class VitTrack:
     """≙ vit_tracker::VitTrack (src/tracker_context.rs:21,88,90,120)."""
 
@@ -700,7 +777,7 @@ class VitTrack:
 
     def init(self, frame, bbox: BBox) -> None:
         """frame: (H,W,3) uint8 RGB array (≙ ArrayView3<u8>), NV12Frame, YUY2Frame, or one of BGR8Frame, RGBXFrame,
-        BGRXFrame, NV21Frame, UYVYFrame. Like the reference's call site (src/tracker_context.rs:88) the caller gets
+        BGRXFrame, NV21Frame, UYVYFrame, I420Frame, YV12Frame, P010Frame, NV16Frame, Gray8Frame, XRGBFrame, XBGRFrame. Like the reference's call site (src/tracker_context.rs:88) the caller gets
         nothing back; errors raise."""
         self._call("init", frame, bbox._c())
 
@@ -865,6 +942,37 @@ def frame_nv21(d_y, d_vu, w, h, y_stride=None, vu_stride=None) -> CFrame:
 
 def frame_uyvy(d_uyvy, w, h, stride=None) -> CFrame:
     return CFrame(d_uyvy, None, w, h, stride or 2 * w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
+
+
+def frame_i420(d_y, d_u, w, h, y_stride=None, c_stride=None) -> CFrame:
+    """d_u: the U plane; the V plane lies c_stride * ceil(h / 2) bytes behind it"""
+    return CFrame(d_y, d_u, w, h, y_stride or w, c_stride or (w + 1) // 2, PIX_I420, 0, 0, 0, 0, 0)
+
+
+def frame_yv12(d_y, d_v, w, h, y_stride=None, c_stride=None) -> CFrame:
+    """d_v: the V plane; the U plane lies c_stride * ceil(h / 2) bytes behind it"""
+    return CFrame(d_y, d_v, w, h, y_stride or w, c_stride or (w + 1) // 2, PIX_YV12, 0, 0, 0, 0, 0)
+
+
+def frame_p010(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
+    """strides in bytes"""
+    return CFrame(d_y, d_uv, w, h, y_stride or 2 * w, uv_stride or 2 * ((w + 1) & ~1), PIX_P010, 0, 0, 0, 0, 0)
+
+
+def frame_nv16(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
+    return CFrame(d_y, d_uv, w, h, y_stride or w, uv_stride or w, PIX_NV16, 0, 0, 0, 0, 0)
+
+
+def frame_gray8(d_y, w, h, stride=None) -> CFrame:
+    return CFrame(d_y, None, w, h, stride or w, 0, PIX_GRAY8, 0, 0, 0, 0, 0)
+
+
+def frame_xrgb(d_xrgb, w, h, stride=None) -> CFrame:
+    return CFrame(d_xrgb, None, w, h, stride or 4 * w, 0, PIX_XRGB, 0, 0, 0, 0, 0)
+
+
+def frame_xbgr(d_xbgr, w, h, stride=None) -> CFrame:
+    return CFrame(d_xbgr, None, w, h, stride or 4 * w, 0, PIX_XBGR, 0, 0, 0, 0, 0)
 
 
 class Group:

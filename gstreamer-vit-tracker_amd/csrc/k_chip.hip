@@ -41,7 +41,7 @@ __device__ __forceinline__ void chip_store_run(const bf16_t (&o)[3][8], uint8_t*
 
 // MODE: which crop body - 0, 1, 2: the tile body with 16 / 32 / 64 KiB of LDS (the pass's tier; a tile that does not fit
 // takes the body's per-pixel path), 3: wide stores of 8 pixels. KIND: vt_chip_kind
-template <int MODE, bool ANY, int KIND>
+template <int MODE, int ANY, int KIND>
 __global__ __launch_bounds__(256) void target_chip_kernel(ChipArgs a, int size, int ssize, int chip_bytes, float na0, float na1,
                                                           float na2, float nb0, float nb1, float nb2) {
     constexpr int LDSPX = MODE == 0 ? PRE_TILE_LDS : (MODE == 1 ? 2 * PRE_TILE_LDS : 4 * PRE_TILE_LDS);
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void target_chip_kernel(ChipArgs a, int size, 
     }
 }
 
-template <bool ANY, int KIND>
+template <int ANY, int KIND>
 static void launch_chips_t(const ChipArgs& a, int C, int chip_bytes, const float* na, const float* nb, int ssize, int tier,
                            hipStream_t st) {
 #define CH_ARGS a, C, ssize, chip_bytes, na[0], na[1], na[2], nb[0], nb[1], nb[2]
@@ -156,17 +156,19 @@ static void launch_chips_t(const ChipArgs& a, int C, int chip_bytes, const float
 }
 
 hipError_t launch_target_chips(const ChipArgs& a, int C, int kind, const float* na, const float* nb, int search_size,
-                               int tier, bool any_layout, hipStream_t st) {
+                               int tier, int any_layout, hipStream_t st) {
     if (a.n < 1 || !a.frames || !a.states || !a.results || !a.policy || !a.chips || !a.infos || !a.out || !na || !nb ||
         C < 32 || C > 512 || C % 8 != 0 || (kind != VT_CHIP_NORM_BF16 && kind != VT_CHIP_RGB8))
         return hipErrorInvalidValue;
     const int chip_bytes = C * C * (kind == VT_CHIP_NORM_BF16 ? 6 : 3);
     if (kind == VT_CHIP_NORM_BF16) {
-        if (any_layout) launch_chips_t<true, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
-        else launch_chips_t<false, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        if (any_layout >= 2) launch_chips_t<2, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        else if (any_layout == 1) launch_chips_t<1, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        else launch_chips_t<0, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
     } else {
-        if (any_layout) launch_chips_t<true, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
-        else launch_chips_t<false, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        if (any_layout >= 2) launch_chips_t<2, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        else if (any_layout == 1) launch_chips_t<1, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        else launch_chips_t<0, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
     }
     return hipGetLastError();
 }

@@ -266,7 +266,7 @@ hipError_t launch_nv12_to_rgb8(const uint8_t* nv12, int w, int h, uint8_t* rgb, 
     int b0, int size, int patch, int kpad, int ntok, int row_off, float factor, float na0, float na1, float na2, float nb0, \
     float nb1, float nb2, int is_template, const int32_t* __restrict__ slot_stream
 // grid: (ceil(size*size/256), nb); one lane per output pixel, 3 channels each.
-template <bool ANY>
+template <int ANY>
 __global__ __launch_bounds__(256) void preproc_kernel(PRE_KERNEL_PARAMS) {
     const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256) void preproc_kernel(PRE_KERNEL_PARAMS) {
 // the stores were 2-B scatters, 48 per 32-B segment. Same per-pixel arithmetic and tap order as
 // preproc_kernel (bit-exact with oracle/vt_oracle.c); neighbouring pixels re-fetch shared taps from
 // L1. grid: (ceil(size*size/PX/256), nb).
-template <int PX, bool ANY>
+template <int PX, int ANY>
 __global__ __launch_bounds__(256) void preproc_wide_kernel(PRE_KERNEL_PARAMS) {
     const int b = b0 + blockIdx.y;                                 // slot: frame descriptor and patch rows
     const FrameDesc f = frames[b];
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void preproc_wide_kernel(PRE_KERNEL_PARAMS) {
 // (64 KiB, two blocks per CU: scales up to ~2.75, ~260 / ~175 px). A tile that still does not fit takes the per-pixel
 // path below - correct at any size, a 3-4x cliff in time (profiles/r05_preproc_by_target.txt) that tier 0 alone hit
 // from ~130-px targets. The tier changes which path a tile takes, never a value: every path is bit-exact.
-template <int LDSPX, bool ANY>
+template <int LDSPX, int ANY>
 __global__ __launch_bounds__(256) void preproc_tile_kernel(PRE_KERNEL_PARAMS) {
     __shared__ uint32_t src[LDSPX];
     constexpr int PX = 8;
@@ -343,7 +343,7 @@ int preproc_tier_for_box(const ModelDims& d, float w, float h, bool is_template)
     return px <= PRE_TILE_LDS ? 0 : (px <= 2 * PRE_TILE_LDS ? 1 : (px <= 4 * PRE_TILE_LDS ? 2 : 3));
 }
 
-template <bool ANY>
+template <int ANY>
 static void launch_preproc_t(const FrameDesc* frames, StreamState* states, bf16_t* patches,
                              const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
                              const int32_t* slot_stream) {
@@ -373,9 +373,10 @@ static void launch_preproc_t(const FrameDesc* frames, StreamState* states, bf16_
 
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
                           const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
-                          const int32_t* slot_stream, bool any_layout) {
-    if (any_layout) launch_preproc_t<true>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
-    else launch_preproc_t<false>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
+                          const int32_t* slot_stream, int any_layout) {
+    if (any_layout >= 2) launch_preproc_t<2>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
+    else if (any_layout == 1) launch_preproc_t<1>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
+    else launch_preproc_t<0>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
     return hipGetLastError();
 }
 

@@ -169,11 +169,25 @@
         // frame and the stored window goes through fetch_rgb pixel by pixel (frame border: black; outside the
         // window: black + miss), so every entry of the LDS image is what the per-pixel loop writes.
         // NV21 takes the same path (ANY kernels): the descriptor says which byte of a pair is U
-        const bool fast = f.fmt == PIXF_420SP && (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 7) == 0;
-        // ANY kernels, 4-byte RGB formats (RGBX, BGRX) whose rows start on 16-byte boundaries (the library's packed
+        // and so does NV16, with one chroma row per luma row; the planar and 16-bit layouts have groups of their own below
+        const bool fast = f.fmt == PIXF_420SP && (ANY < 2 || (f.lay & (PIXL_PLANAR | PIXL_S16)) == 0) && (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 7) == 0;
+        // ANY kernels, 4-byte RGB formats (RGBX, BGRX, XRGB, XBGR) whose rows start on 16-byte boundaries (the library's packed
         // windows; whole frames with such strides): ONE 16-byte load per 4 pixels, where the per-pixel path issues 12
         // byte loads; the same edge rule as the NV12 groups
         const bool fast4 = ANY && f.fmt == PIXF_RGB && (f.lay >> 24) == 4 && (((uintptr_t)f.p0 | (uintptr_t)f.s0) & 15) == 0;
+        // ANY = 2 kernels, groups of 8 pixels for the other layouts with a luma / grey plane, under the same edge rule, each
+        // on the alignment its loads need: 1 I420 / YV12 (8 B of Y + 4 B of U + 4 B of V), 2 P010 (16 B of Y + 16 B of
+        // chroma, of which the high bytes), 3 GRAY8 (8 B)
+        int xmode = 0;
+        if constexpr (ANY >= 2) {
+            if (f.fmt == PIXF_420SP && (f.lay & PIXL_PLANAR))
+                xmode = ((((uintptr_t)f.p0 | (uintptr_t)f.s0) & 7) | (((uintptr_t)f.p1 | (uintptr_t)f.s1) & 3)) == 0 ? 1 : 0;
+            else if (f.fmt == PIXF_420SP && (f.lay & PIXL_S16))
+                xmode = (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 15) == 0 ? 2 : 0;
+            else if (f.fmt == PIXF_RGB && (f.lay >> 24) == 1)
+                xmode = (((uintptr_t)f.p0 | (uintptr_t)f.s0) & 7) == 0 ? 3 : 0;
+        }
+        const int crs = ANY >= 2 ? ((f.lay >> 24) & 1) ^ 1 : 1;      // chroma row shift: 0 for NV16
         if (fast) {
             const int us = ANY ? (f.lay & 1) * 8 : 0, vs = ANY ? ((f.lay >> 8) & 1) * 8 : 8;   // bit offsets of U, V in a pair
             const int g_lo = (sx_lo - f.x0) >> 3, g_hi = (sx_hi - f.x0) >> 3;     // arithmetic shift: floor for negatives
@@ -186,7 +200,7 @@
                 uint32_t* dst = src + ry * w_ + (px0 - sx_lo);
                 if (inside) {
                     const uint2 y8 = *reinterpret_cast<const uint2*>(f.p0 + (size_t)wy_ * f.s0 + wx0);
-                    const uint2 uv8 = *reinterpret_cast<const uint2*>(f.p1 + (size_t)(wy_ >> 1) * f.s1 + wx0);
+                    const uint2 uv8 = *reinterpret_cast<const uint2*>(f.p1 + (size_t)(wy_ >> crs) * f.s1 + wx0);
                     const uint32_t yw[2] = {y8.x, y8.y}, uw[2] = {uv8.x, uv8.y};
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
@@ -196,6 +210,65 @@
                         int r, g, b;
                         yuv_to_rgb((int)((yw[k >> 2] >> ((k & 3) * 8)) & 255u), (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
                         dst[k] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+                    }
+                } else {
+                    for (int k = 0; k < 8; ++k) {
+                        const int col = px0 - sx_lo + k;
+                        if (col < 0 || col >= w_) continue;
+                        float p[3];
+                        int miss = 0;
+                        fetch_rgb<ANY>(f, px0 + k, py, p, miss);
+                        dst[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)miss << 24);
+                    }
+                }
+            }
+        } else if (ANY >= 2 && xmode) {
+            // the group's samples in NV12's form - 8 luma bytes, 4 (U, V) pairs - then NV12's conversion
+            const int us = xmode == 2 ? (f.lay & 1) * 8 : 0, vs = xmode == 2 ? ((f.lay >> 8) & 1) * 8 : 8;
+            const size_t second = (size_t)f.s1 * (size_t)((((f.lay & PIXL_FULLH) ? f.h : f.wh) + 1) >> 1);
+            const uint8_t* pu = f.p1 + ((f.lay & 1) ? second : 0);
+            const uint8_t* pv = f.p1 + ((f.lay & 0x100) ? second : 0);
+            const int g_lo = (sx_lo - f.x0) >> 3, g_hi = (sx_hi - f.x0) >> 3;     // arithmetic shift: floor for negatives
+            const int gpr = g_hi - g_lo + 1, ng = gpr * (int)sh;
+            for (int i = threadIdx.x; i < ng; i += 256) {
+                const int ry = i / gpr, wx0 = (g_lo + i % gpr) << 3;                // window column of the group
+                const int py = sy_lo + ry, wy_ = py - f.y0, px0 = wx0 + f.x0;
+                const bool inside = (unsigned)wy_ < (unsigned)f.wh && (unsigned)py < (unsigned)f.h && wx0 >= 0 &&
+                                    wx0 + 7 < f.ww && px0 >= 0 && px0 + 7 < f.w;
+                uint32_t* dst = src + ry * w_ + (px0 - sx_lo);
+                if (inside) {
+                    uint32_t yw[2], uw[2] = {0u, 0u};
+                    if (xmode == 2) {
+                        const u32x4_t y16 = *reinterpret_cast<const u32x4_t*>(f.p0 + (size_t)wy_ * f.s0 + (size_t)wx0 * 2);
+                        const u32x4_t c16 = *reinterpret_cast<const u32x4_t*>(f.p1 + (size_t)(wy_ >> crs) * f.s1 + (size_t)wx0 * 2);
+                        yw[0] = __builtin_amdgcn_perm(y16[1], y16[0], 0x07050301u);  // byte 1 of each of four samples
+                        yw[1] = __builtin_amdgcn_perm(y16[3], y16[2], 0x07050301u);
+                        uw[0] = __builtin_amdgcn_perm(c16[1], c16[0], 0x07050301u);
+                        uw[1] = __builtin_amdgcn_perm(c16[3], c16[2], 0x07050301u);
+                    } else {
+                        const uint2 y8 = *reinterpret_cast<const uint2*>(f.p0 + (size_t)wy_ * f.s0 + wx0);
+                        yw[0] = y8.x; yw[1] = y8.y;
+                        if (xmode == 1) {
+                            const size_t co = (size_t)(wy_ >> 1) * f.s1 + (wx0 >> 1);
+                            const uint32_t u4 = *reinterpret_cast<const uint32_t*>(pu + co);
+                            const uint32_t v4 = *reinterpret_cast<const uint32_t*>(pv + co);
+                            uw[0] = __builtin_amdgcn_perm(v4, u4, 0x05010400u);     // u0 v0 u1 v1
+                            uw[1] = __builtin_amdgcn_perm(v4, u4, 0x07030602u);     // u2 v2 u3 v3
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int col = px0 - sx_lo + k;
+                        if (col < 0 || col >= w_) continue;
+                        const uint32_t yk = (yw[k >> 2] >> ((k & 3) * 8)) & 255u;
+                        if (xmode == 3) {
+                            dst[k] = yk * 0x010101u;
+                        } else {
+                            const uint32_t pair = uw[k >> 2] >> (((k >> 1) & 1) * 16);   // U, V of the pixel pair
+                            int r, g, b;
+                            yuv_to_rgb((int)yk, (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
+                            dst[k] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+                        }
                     }
                 } else {
                     for (int k = 0; k < 8; ++k) {

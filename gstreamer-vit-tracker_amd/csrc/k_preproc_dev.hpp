@@ -20,11 +20,13 @@ __device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, int& r, int& g, 
 }
 
 // frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding).
-// ANY = false: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
-// constants); ANY = true: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_common.hpp). The
-// engine launches the ANY kernels only for passes that carry one of the other formats: reading the offsets at run time
-// costs the crop kernels 3-19 SGPRs (kernel-resource-usage), and those of the three original formats keep their budget.
-template <bool ANY>
+// ANY = 0: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
+// constants); ANY = 1: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_common.hpp); ANY = 2:
+// every vt_pixfmt2 as well, through the whole layout word. The engine launches the kernels of the lowest level that reads
+// every format of the pass (pix_level): reading the offsets at run time costs the crop kernels 3-19 SGPRs, the planar,
+// 16-bit and grey layouts another 6 and 23 spilled (kernel-resource-usage; profiles/planar_formats_cfg3.txt), and the
+// kernels of the formats that were there before keep their budgets and their instructions.
+template <int ANY>
 __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, float* rgb, int& miss) {
     if (px < 0 || py < 0 || px >= f.w || py >= f.h) {
         rgb[0] = rgb[1] = rgb[2] = 0.0f;
@@ -39,7 +41,31 @@ __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, fl
         miss = 1;
         return;
     }
-    if constexpr (ANY) {    // the masks keep every offset inside its pixel / pair
+    if constexpr (ANY == 2) {    // the masks keep every offset inside its pixel / pair / sample: no other byte is read
+        const int lay = f.lay;
+        if (f.fmt == PIXF_RGB) {            // RGB8 .. BGRX, XRGB, XBGR, GRAY8: the colour bytes at their offsets in the pixel
+            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * (unsigned)(lay >> 24);
+            r = p[lay & 3]; g = p[(lay >> 8) & 3]; b = p[(lay >> 16) & 3];
+        } else if (f.fmt == PIXF_420SP) {   // NV12, NV21, I420, YV12, P010, NV16; x0 (and y0, but NV16's) even
+            const int ss = (lay >> 20) & 1, hb = (lay >> 22) & 1;       // 16-bit samples: the shift and the byte read
+            const int y = f.p0[(size_t)sy * f.s0 + ((size_t)sx << ss) + hb];
+            int u, v;
+            if (lay & PIXL_PLANAR) {        // the second chroma plane lies behind the first one's stored rows
+                const uint8_t* c = f.p1 + (size_t)(sy >> 1) * f.s1 + (sx >> 1);
+                const size_t second = (size_t)f.s1 * (size_t)((((lay & PIXL_FULLH) ? f.h : f.wh) + 1) >> 1);
+                u = c[(lay & 1) ? second : 0];
+                v = c[(lay & 0x100) ? second : 0];
+            } else {
+                const uint8_t* uv = f.p1 + (size_t)(sy >> (((lay >> 24) & 1) ^ 1)) * f.s1 + ((size_t)(sx & ~1) << ss) + hb;
+                u = uv[(lay & 1) << ss];
+                v = uv[((lay >> 8) & 1) << ss];
+            }
+            yuv_to_rgb(y, u, v, r, g, b);
+        } else {                            // YUY2 (Y0 U Y1 V), UYVY (U Y0 V Y1) per pixel pair
+            const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
+            yuv_to_rgb(p[(sx & 1) ? (lay >> 16) & 3 : lay & 3], p[(lay >> 8) & 3], p[(lay >> 24) & 3], r, g, b);
+        }
+    } else if constexpr (ANY == 1) {    // the masks keep every offset inside its pixel / pair
         const int lay = f.lay;
         if (f.fmt == PIXF_RGB) {            // RGB8, BGR8, RGBX, BGRX: colour bytes 0-2, permuted by the offsets
             const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * (unsigned)(lay >> 24);

@@ -20,7 +20,7 @@
 // MODE: which crop body, as launch_preproc picks it for the template - 0, 1, 2: the tile body with 16 / 32 / 64 KiB of
 // LDS (the pass's tier; a tile that does not fit takes the body's per-pixel path), 3: wide stores of 8 pixels, 4: of 2
 // pixels (patch 14), 5: one lane per pixel
-template <int MODE, bool ANY>
+template <int MODE, int ANY>
 __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshArgs a, int size, int ssize, int patch, int kpad,
                                                                int tpl_elems, float na0, float na1, float na2, float nb0,
                                                                float nb1, float nb2) {
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshArgs a, in
     __hip_atomic_store(a.tickets + slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool ANY>
+template <int ANY>
 static void launch_refresh_t(const RefreshArgs& a, const ModelDims& d, int tier, hipStream_t st) {
     const int size = d.T, tpl_elems = d.nt * d.kpad;
 #define RF_ARGS a, size, d.S, d.patch, d.kpad, tpl_elems, d.norm_a[0], d.norm_a[1], d.norm_a[2], d.norm_b[0], d.norm_b[1], d.norm_b[2]
@@ -132,10 +132,11 @@ static void launch_refresh_t(const RefreshArgs& a, const ModelDims& d, int tier,
 #undef RF_ARGS
 }
 
-hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int tier, bool any_layout, hipStream_t st) {
+hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int tier, int any_layout, hipStream_t st) {
     if (a.n < 1 || !a.frames || !a.states || !a.results || !a.policy || !a.tickets || !a.tpl || !a.out)
         return hipErrorInvalidValue;
-    if (any_layout) launch_refresh_t<true>(a, d, tier, st);
-    else launch_refresh_t<false>(a, d, tier, st);
+    if (any_layout >= 2) launch_refresh_t<2>(a, d, tier, st);
+    else if (any_layout == 1) launch_refresh_t<1>(a, d, tier, st);
+    else launch_refresh_t<0>(a, d, tier, st);
     return hipGetLastError();
 }

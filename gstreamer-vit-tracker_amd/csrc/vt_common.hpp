@@ -14,19 +14,34 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 
-// Pixel layout families: every vt_pixfmt is one family plus the byte offsets of its components (FrameDesc.lay). The
-// family codes are the vt_pixfmt values of the formats that defined them, so those formats' descriptors are unchanged.
+// Pixel layout families: every value of vt_frame.format (vt_pixfmt, vt_pixfmt2) is one family plus a layout word
+// (FrameDesc.lay). The family codes are the vt_pixfmt values of the formats that defined them, so those formats'
+// descriptors are unchanged.
 enum PixFamily {
-    PIXF_RGB = VT_PIX_RGB8,       // packed R,G,B(,x): lay = R | G << 8 | B << 16 (byte offsets) | bytes per pixel << 24
-    PIXF_420SP = VT_PIX_NV12,     // Y plane + interleaved chroma pairs: lay = U offset in the pair | V offset << 8
+    // packed R,G,B(,x) / x,R,G,B / one grey byte: lay = R | G << 8 | B << 16 (byte offsets inside the pixel, 0..3) |
+    // bytes per pixel << 24 (GRAY8: 1, every offset 0)
+    PIXF_RGB = VT_PIX_RGB8,
+    // a luma plane + chroma at half the horizontal rate. lay = U offset | V offset << 8 (0 or 1: the position in an
+    // interleaved pair, or - PIXL_PLANAR - which of the two chroma planes) | the PIXL_* bits below. NV12, NV21, I420,
+    // YV12, P010 and NV16 (whose sibling is YUY2: the same luma, the same chroma pair per pixel pair, one row per row)
+    PIXF_420SP = VT_PIX_NV12,
     PIXF_422 = VT_PIX_YUY2        // packed pixel pairs: lay = Y0 | U << 8 | Y1 << 16 | V << 24 (byte offsets)
 };
+// PIXF_420SP layout bits (zero for NV12 / NV21)
+#define PIXL_PLANAR (1 << 16)     // U and V in planes of their own: p1 is the first, the second lies s1 * ceil(R / 2) bytes
+                                  // behind it, R = the stored rows: wh, or - PIXL_FULLH - h
+#define PIXL_S16 (1 << 20)        // 16-bit little-endian samples (strides in bytes), of which ...
+#define PIXL_HIBYTE (1 << 22)     // ... byte 1 is read
+#define PIXL_ROWS422 (1 << 24)    // one chroma row per luma row (no row shift)
+#define PIXL_FULLH (1 << 25)      // set by to_desc: the planes belong to a whole frame (vt_frame.windowed != 1)
 
-// family of a vt_pixfmt (-1: unknown) and its layout word
+// family of a format (-1: unknown) and its layout word
 inline int pix_family(int fmt) {
     switch (fmt) {
-    case VT_PIX_RGB8: case VT_PIX_BGR8: case VT_PIX_RGBX: case VT_PIX_BGRX: return PIXF_RGB;
-    case VT_PIX_NV12: case VT_PIX_NV21: return PIXF_420SP;
+    case VT_PIX_RGB8: case VT_PIX_BGR8: case VT_PIX_RGBX: case VT_PIX_BGRX:
+    case VT_PIX2_GRAY8: case VT_PIX2_XRGB: case VT_PIX2_XBGR: return PIXF_RGB;
+    case VT_PIX_NV12: case VT_PIX_NV21:
+    case VT_PIX2_I420: case VT_PIX2_YV12: case VT_PIX2_P010: case VT_PIX2_NV16: return PIXF_420SP;
     case VT_PIX_YUY2: case VT_PIX_UYVY: return PIXF_422;
     default: return -1;
     }
@@ -41,26 +56,46 @@ inline int32_t pix_layout(int fmt) {
     case VT_PIX_NV21: return 1 | 0 << 8;
     case VT_PIX_YUY2: return 0 | 1 << 8 | 2 << 16 | 3 << 24;
     case VT_PIX_UYVY: return 1 | 0 << 8 | 3 << 16 | 2 << 24;
+    case VT_PIX2_I420: return 0 | 1 << 8 | PIXL_PLANAR;
+    case VT_PIX2_YV12: return 1 | 0 << 8 | PIXL_PLANAR;
+    case VT_PIX2_P010: return 0 | 1 << 8 | PIXL_S16 | PIXL_HIBYTE;
+    case VT_PIX2_NV16: return 0 | 1 << 8 | PIXL_ROWS422;
+    case VT_PIX2_GRAY8: return 0 | 0 << 8 | 0 << 16 | 1 << 24;
+    case VT_PIX2_XRGB: return 1 | 2 << 8 | 3 << 16 | 4 << 24;
+    case VT_PIX2_XBGR: return 3 | 2 << 8 | 1 << 16 | 4 << 24;
     default: return 0;
     }
 }
-// name of a vt_pixfmt for error texts
+// name of a format for error texts
 inline const char* pix_name(int fmt) {
     static const char* const names[] = {"rgb8", "nv12", "yuy2", "bgr8", "rgbx", "bgrx", "nv21", "uyvy"};
-    return fmt >= 0 && fmt < 8 ? names[fmt] : "?";
+    static const char* const names2[] = {"i420", "yv12", "p010", "nv16", "gray8", "xrgb", "xbgr"};
+    return fmt >= 0 && fmt < 8 ? names[fmt] : fmt >= VT_PIX2_I420 && fmt <= VT_PIX2_XBGR ? names2[fmt - VT_PIX2_I420] : "?";
 }
-// the crop kernels that read f.lay (k_preproc.hip) are needed for this format
-inline bool pix_any_layout(int fmt) { return fmt != VT_PIX_RGB8 && fmt != VT_PIX_NV12 && fmt != VT_PIX_YUY2; }
-// bytes per pixel of plane 0's rows (4:2:0 semi-planar: the Y plane)
+// which crop kernels (k_preproc.hip, fetch_rgb<level>) read this format: 0 those of RGB8, NV12 and YUY2, 1 those that read
+// the byte offsets of f.lay (every vt_pixfmt), 2 those that read the whole layout word (every vt_pixfmt2 as well). A
+// kernel of a level reads every format of the levels below it.
+#define PIX_LEVELS 3
+inline int pix_level(int fmt) { return fmt >= VT_PIX2_I420 ? 2 : fmt != VT_PIX_RGB8 && fmt != VT_PIX_NV12 && fmt != VT_PIX_YUY2 ? 1 : 0; }
+// bytes per pixel of plane 0's rows (PIXF_420SP: the luma plane)
 inline int pix_row_bpp(int fmt) {
     const int fam = pix_family(fmt);
-    return fam == PIXF_RGB ? pix_layout(fmt) >> 24 : fam == PIXF_422 ? 2 : 1;
+    return fam == PIXF_RGB ? pix_layout(fmt) >> 24 : fam == PIXF_422 ? 2 : (pix_layout(fmt) & PIXL_S16) ? 2 : 1;
+}
+// PIXF_420SP: U and V lie in two planes behind each other / chroma rows of `rows` luma rows / window rules of YUY2
+// (no rule on rows) instead of NV12's
+inline bool pix_planar(int fmt) { return pix_family(fmt) == PIXF_420SP && (pix_layout(fmt) & PIXL_PLANAR); }
+inline bool pix_rows422(int fmt) { return pix_family(fmt) == PIXF_420SP && (pix_layout(fmt) & PIXL_ROWS422); }
+inline int pix_chroma_rows(int fmt, int rows) { return pix_rows422(fmt) ? rows : (rows + 1) / 2; }
+// PIXF_420SP: bytes of a chroma row (of one plane) that belong to `ww` pixels
+inline int pix_chroma_row_bytes(int fmt, int ww) {
+    return pix_planar(fmt) ? (ww + 1) / 2 : ((ww + 1) & ~1) * pix_row_bpp(fmt);
 }
 
 // one device-resident input frame (mirrors vt_frame, 64-bit pointers)
 struct FrameDesc {
-    const uint8_t* p0;  // packed pixels, or the Y plane of 4:2:0 semi-planar
-    const uint8_t* p1;  // 4:2:0 semi-planar: the interleaved chroma plane
+    const uint8_t* p0;  // packed pixels, or the luma plane of PIXF_420SP
+    const uint8_t* p1;  // PIXF_420SP: the interleaved chroma plane, or the first of the two chroma planes
     int32_t w, h, s0, s1;
     int32_t fmt;        // PixFamily
     int32_t x0, y0;     // frame coordinates of the first stored pixel (window upload)
@@ -281,10 +316,10 @@ hipError_t launch_attention_queries(const bf16_t* qk, const bf16_t* vt, bf16_t* 
 // tier: the tile kernel's LDS buffer (0: 16 KiB, 1: 32 KiB, 2 or more: 64 KiB), a choice of speed only
 // slot_stream (device, [nb + b0] or null = identity): the stream a slot works for. Frame descriptor and patch rows are
 // the slot's; the StreamState read (and its geo / frame_w / frame_h / window_miss written) is the stream's.
-// any_layout: some slot's frame is not RGB8, NV12 or YUY2 (its layout is read from FrameDesc.lay: k_preproc.hip, fetch_rgb)
+// any_layout: the highest pix_level of the slots' formats (above 0 the layout is read from FrameDesc.lay: k_preproc.hip, fetch_rgb)
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
                           const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier = 0,
-                          const int32_t* slot_stream = nullptr, bool any_layout = false);
+                          const int32_t* slot_stream = nullptr, int any_layout = 0);
 // subset passes: slot i's template rows [nt][kpad] of the patch matrix <- the template store tpl[slot_stream[i]]
 hipError_t launch_gather_template_rows(const bf16_t* tpl, bf16_t* patches, const int32_t* slot_stream, int n,
                                        const ModelDims& d, hipStream_t st);
@@ -358,7 +393,7 @@ struct RefreshArgs {
 };
 // behind the decode (candidate pass: behind the commit): per slot the gate of DESIGN.md section 3 and, where it fires, the
 // template crop of this pass's frame at the committed box into the stream's other buffer + the state's two words
-hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int tier, bool any_layout, hipStream_t st);
+hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int tier, int any_layout, hipStream_t st);
 
 // ---- target chips (k_chip.hip) ------------------------------------------------------------------------------------------
 // per stream, device memory, written by the host only (never rewound)
@@ -385,7 +420,7 @@ struct ChipArgs {
 // of DESIGN.md section 3 "Target chips", the stream's info record and, where the gate fires, the chip - a crop of this
 // pass's frame at the committed box, side C, kind VT_CHIP_NORM_BF16 (na, nb: the caller's) or VT_CHIP_RGB8
 hipError_t launch_target_chips(const ChipArgs& a, int C, int kind, const float* na, const float* nb, int search_size,
-                               int tier, bool any_layout, hipStream_t st);
+                               int tier, int any_layout, hipStream_t st);
 
 // ---- response peaks (k_peaks.hip) ---------------------------------------------------------------------------------------
 // per stream, device memory, written by the host only (never rewound, not part of a snapshot)

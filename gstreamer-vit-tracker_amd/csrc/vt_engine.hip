@@ -627,7 +627,7 @@ int Engine::expand_last_block() {
     return VT_OK;
 }
 
-int Engine::capture_graph(int tier, bool any_layout) {
+int Engine::capture_graph(int tier, int any_layout) {
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     int rc = run_pass(nullptr, PassShape{B, nullptr, tier, any_layout, nullptr, last_block_compact(B, false)});
     hipGraph_t g = nullptr;
@@ -651,29 +651,31 @@ int Engine::capture_graph(int tier, bool any_layout) {
 // Every crop-buffer tier's pass, captured and instantiated NOW (engine creation, vt_group_set_tuning): the hot path only
 // replays. A live stream whose target grows across a tier boundary (~130 / ~200 px at search 384) must not pay a
 // capture + instantiate inside an update (60 fps: /root/reference/src/pipeline.rs:26-37).
-// With want_any_graphs, the passes of the crop kernels that read any vt_pixfmt too (Engine::init_stream sets it).
+// With a bit of want_levels, the passes of the crop kernels of that level too (Engine::init_stream sets it).
 int Engine::capture_all_graphs() {
     if (!use_graph) return VT_OK;
-    for (int any = 0; any < (want_any_graphs ? 2 : 1); ++any)
-        for (int t = 0; t < TIERS; ++t)
+    for (int any = 0; any < PIX_LEVELS; ++any)
+        for (int t = 0; t < TIERS && (any == 0 || (want_levels >> any & 1)); ++t)
             if (!graphs[any][t].exec)
-                if (int rc = capture_graph(t, any == 1)) return rc;
+                if (int rc = capture_graph(t, any)) return rc;
     return VT_OK;
 }
 
-// The first stream on a format other than RGB8 / NV12 / YUY2: every tier's pass with the crop kernels that read the
-// layout is captured at its init, on the idle stream, so that no update of such a stream captures (a failure leaves the
+// The first stream on a format of a level (pix_level) above 0: every tier's pass with the crop kernels of that level
+// is captured at its init, on the idle stream, so that no update of such a stream captures (a failure leaves the
 // engine as it was, apart from the tiers already captured, which stay valid).
 int Engine::capture_graphs_for(int format) {
-    if (!use_graph || want_any_graphs || !pix_any_layout(format)) return VT_OK;
+    const int level = pix_level(format);
+    if (!use_graph || level == 0 || (want_levels >> level & 1)) return VT_OK;
     HIPCHK(hipStreamSynchronize(stream));
-    want_any_graphs = true;
-    if (int rc = capture_all_graphs()) { want_any_graphs = false; return rc; }
+    want_levels |= 1u << level;
+    if (int rc = capture_all_graphs()) { want_levels &= ~(1u << level); return rc; }
     return VT_OK;
 }
 
-// every format is checked by its family (vt_common.hpp: PixFamily): 4:2:0 semi-planar by the rules of NV12, packed
-// 4:2:2 by those of YUY2, packed RGB by its bytes per pixel
+// every format is checked by its family (vt_common.hpp: PixFamily): a luma plane with chroma planes by the rules of NV12
+// (NV16: the window rules of YUY2) on the bytes of its samples and planes, packed 4:2:2 by those of YUY2, packed RGB and
+// grey by the bytes per pixel
 int check_frame(const vt_frame& f) {
     if (!f.plane0 || f.width < 16 || f.height < 16 || f.width > 16384 || f.height > 16384)
         return set_err(VT_ERR_INVALID_ARG, "frame: null plane or size out of range");
@@ -681,10 +683,11 @@ int check_frame(const vt_frame& f) {
     if (fam < 0)
         return set_err(VT_ERR_INVALID_ARG, "unknown pixel format %d", f.format);
     const bool window = f.origin_x != 0 || f.origin_y != 0 || f.windowed == 1;
+    const bool rows422 = pix_rows422(f.format);     // NV16: pairs along x only
     if (f.origin_x < 0 || f.origin_y < 0 || f.origin_x >= f.width || f.origin_y >= f.height ||
-        (fam == PIXF_420SP && ((f.origin_x | f.origin_y) & 1)) ||
+        (fam == PIXF_420SP && ((f.origin_x | (rows422 ? 0 : f.origin_y)) & 1)) ||
         (fam == PIXF_422 && (f.origin_x & 1)))
-        return set_err(VT_ERR_INVALID_ARG, "frame window origin %d,%d invalid", f.origin_x, f.origin_y);
+        return set_err(VT_ERR_INVALID_ARG, "%s frame window origin %d,%d invalid", pix_name(f.format), f.origin_x, f.origin_y);
     // extent of what the planes hold: the kernels never read outside it (fetch_rgb, k_preproc.hip)
     int ww = f.width, wh = f.height;
     (void)wh;
@@ -696,7 +699,7 @@ int check_frame(const vt_frame& f) {
                            f.width, f.height);
         ww = f.window_w; wh = f.window_h;
         if (fam == PIXF_420SP && (((ww & 1) && f.origin_x + ww != f.width) ||
-                                  ((wh & 1) && f.origin_y + wh != f.height)))
+                                  (!rows422 && (wh & 1) && f.origin_y + wh != f.height)))
             return set_err(VT_ERR_INVALID_ARG, "%s window extent must be even unless it ends at the frame edge",
                            pix_name(f.format));
     } else if (f.window_w != 0 || f.window_h != 0) {
@@ -707,8 +710,10 @@ int check_frame(const vt_frame& f) {
         const int bpp = pix_row_bpp(f.format);
         if (f.stride0 < ww * bpp) return set_err(VT_ERR_INVALID_ARG, "%s stride < %d*width", pix_name(f.format), bpp);
     } else if (fam == PIXF_420SP) {
-        if (!f.plane1 || f.stride0 < ww || f.stride1 < ((ww + 1) & ~1))
+        if (!f.plane1 || f.stride0 < ww * pix_row_bpp(f.format) || f.stride1 < pix_chroma_row_bytes(f.format, ww))
             return set_err(VT_ERR_INVALID_ARG, "%s: null UV plane or stride too small", pix_name(f.format));
+        if (rows422 && (f.width & 1))
+            return set_err(VT_ERR_INVALID_ARG, "%s: odd width", pix_name(f.format));
     } else {
         if ((f.width & 1) || f.stride0 < ((ww + 1) & ~1) * 2)
             return set_err(VT_ERR_INVALID_ARG, "%s: odd width or stride < 2*width", pix_name(f.format));
@@ -726,6 +731,9 @@ void to_desc(const vt_frame& f, FrameDesc* o) {
     o->ww = window ? f.window_w : f.width;
     o->wh = window ? f.window_h : f.height;
     o->lay = pix_layout(f.format);
+    // two chroma planes: the second one lies behind the rows of the first, those of the whole frame unless the planes hold a
+    // packed window (vittrack_hip.h: vt_pixfmt2)
+    if (pix_planar(f.format) && f.windowed != 1) o->lay |= PIXL_FULLH;
 }
 
 int Engine::check_init_box(vt_bbox box) const {
@@ -748,7 +756,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
     HIPCHK(launch_preproc(d_frames, d_states, d_patches, d, b, 1, true, stream,
                           preproc_tier_for_box(d, (float)box.width, (float)box.height, true), nullptr,
-                          pix_any_layout(f->format)));
+                          pix_level(f->format)));
     // the stream's template rows, kept for the subset passes that run it in another slot (and for the full pass that
     // follows one: restore_segments puts every stream's rows back from here, these included)
     HIPCHK(hipMemcpyAsync(tpl_init_rows(b), d_patches + (size_t)b * d.ntok * d.kpad,
@@ -820,12 +828,12 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
     ring_pos = (ring_pos + 1) % RING;
     HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copy that last used this block is done
     FrameDesc* hf = h_block(slot);
-    *ps = PassShape{n, full ? nullptr : d_map(), 0, false, nullptr};
+    *ps = PassShape{n, full ? nullptr : d_map(), 0, 0, nullptr};
     pass_winner.clear();
     cand_pending = false;
     for (int i = 0; i < n; ++i) {
         to_desc(frames[i], hf + i);
-        ps->any_layout = ps->any_layout || pix_any_layout(frames[i].format);
+        ps->any_layout = std::max(ps->any_layout, pix_level(frames[i].format));
     }
     *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all,
                                   peaks_capable ? (host_pk ? host_pk : h_peaks) : nullptr};
@@ -858,9 +866,12 @@ int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_re
     PassShape ps;
     if (int rc = prepare_pass(streams, frames, n, host_res, host_st, host_pk, &ps)) return rc;
     if (!ps.slot_stream && use_graph && !taps) {
-        const PassGraph& g = graphs[ps.any_layout][ps.tier];
+        // the captured set of the lowest level that reads every format of the pass
+        int level = ps.any_layout;
+        while (level > 0 && level + 1 < PIX_LEVELS && !graphs[level][ps.tier].exec) ++level;
+        const PassGraph& g = graphs[level][ps.tier];
         if (!ps.any_layout && !g.exec)   // not reached after a successful creation (capture_all_graphs); kept as the safe path
-            if (int rc = capture_graph(ps.tier, false)) return rc;
+            if (int rc = capture_graph(ps.tier, 0)) return rc;
         // passes with another format replay the graphs captured when a stream was initialised on one; without them
         // (every stream was initialised on RGB8 / NV12 / YUY2) the pass launches eagerly: no capture inside an update
         if (g.exec) {
@@ -1256,11 +1267,11 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
     // the template gather keeps the slot -> stream map; the decode stores results by slot and NO state to the host:
     // only the commit kernel writes by-stream copies
     const CandArgs ca{d_cands, d_states, d_cand_states, d_results, d_winner, h_states_all, h_winner, n};
-    PassShape ps{n, d_map(), 0, false, &ca};
+    PassShape ps{n, d_map(), 0, 0, &ca};
     int32_t* map = (int32_t*)((char*)hf + map_offset());
     for (int i = 0; i < n; ++i) {
         to_desc(frames[i], hf + i);
-        ps.any_layout = ps.any_layout || pix_any_layout(frames[i].format);
+        ps.any_layout = std::max(ps.any_layout, pix_level(frames[i].format));
         map[i] = cands[i].stream;
         hc[i] = cands[i];
     }

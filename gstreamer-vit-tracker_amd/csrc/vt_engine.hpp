@@ -122,7 +122,7 @@ struct PassShape {
     int n = 0;                              // slots (M = n * ntok)
     const int32_t* slot_stream = nullptr;   // device map slot -> stream of a subset pass; null: the full pass (n == B, slot b is stream b)
     int tier = 0;                           // crop-buffer tier (Engine::pick_crop_tier)
-    bool any_layout = false;                // some slot's frame is not RGB8 / NV12 / YUY2 (k_preproc.hip: fetch_rgb<true>)
+    int any_layout = 0;                     // the highest pix_level of the slots' formats (k_preproc.hip: fetch_rgb<level>)
     // a candidate pass (k_cand.hip): slot_stream says whose TEMPLATE a slot takes; its STATE is the slot's own candidate
     // state (cand->cand_states, identity map), filled ahead of the crop and committed behind the decode. Null: a
     // slot's state is its stream's.
@@ -272,12 +272,13 @@ struct Engine {
     // graph
     // one captured pass per crop-buffer tier (k_preproc.hip: 16 / 32 / 64 KiB of LDS per tile), all captured at creation
     static constexpr int TIERS = 3;
-    // graphs[1]: the same passes with the crop kernels that read any vt_pixfmt (k_preproc.hip: fetch_rgb<true>), for
-    // passes that carry a format other than RGB8 / NV12 / YUY2: all tiers captured together (capture_all_graphs) when
-    // the first stream is initialised on such a format - never inside an update
+    // graphs[1], graphs[2]: the same passes with the crop kernels that read any vt_pixfmt / any vt_pixfmt2 as well
+    // (k_preproc.hip: fetch_rgb<level>, vt_common.hpp: pix_level), for passes that carry a format other than RGB8 / NV12 /
+    // YUY2: all tiers of a level captured together (capture_all_graphs) when the first stream is initialised on a format
+    // of that level - never inside an update
     struct PassGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
-    PassGraph graphs[2][TIERS];                   // [any_layout][tier]
-    bool want_any_graphs = false;                 // a stream was initialised on such a format: capture_all_graphs takes them too
+    PassGraph graphs[PIX_LEVELS][TIERS];          // [pix_level][tier]
+    unsigned want_levels = 0;                     // bit l: a stream was initialised on a format of level l > 0: capture_all_graphs takes that set too
     int crop_tier_forced = -1;                    // >= 0: tests / A-B runs (vt_group_set_tuning "crop_tier")
     int graph_captures = 0;                       // hipGraph captures since creation (vt_group_graph_captures)
     long graph_replays[TIERS] = {0, 0, 0};        // passes replayed per tier (vt_group_read_tensor "graph_replays")
@@ -356,9 +357,9 @@ struct Engine {
     int alloc_buffers();
     int run_pass(Profiler* prof, const PassShape& ps);
     int restore_segments();             // every stream's template rows back into its own segment (after a subset pass)
-    int capture_graph(int tier, bool any_layout);     // the full pass of that shape into graphs[any_layout][tier]
+    int capture_graph(int tier, int any_layout);      // the full pass of that shape into graphs[any_layout][tier]
     int capture_all_graphs();
-    int capture_graphs_for(int format);           // the graphs[1] set, once, when a stream starts on a format that needs it
+    int capture_graphs_for(int format);           // the graph set of the format's level, once, when a stream starts on a format that needs it
     int pick_crop_tier(const int32_t* streams = nullptr, int n = 0) const;   // streams == null: all B
     int pick_crop_tier(const vt_candidate* cands, int n) const;              // a candidate pass: from the slots' boxes
     void drop_graphs();

@@ -16,21 +16,31 @@ struct HostWin {
     size_t bytes, uv_off;
 };
 
-// row pitch of a packed format's window in the arena: 4-byte pixels on 16-byte boundaries (the crop kernel then fetches
-// 4 pixels per load), the others back to back
+// row pitch of a packed format's window in the arena: 4-byte pixels and grey bytes on 16-byte boundaries (the crop kernel
+// then fetches 4 / 8 pixels per load), the others back to back
 static size_t packed_row_bytes(int fmt, int ww) {
     const size_t rb = (size_t)ww * pix_row_bpp(fmt);
-    return pix_row_bpp(fmt) == 4 ? (rb + 15) & ~(size_t)15 : rb;
+    return pix_row_bpp(fmt) == 4 || pix_row_bpp(fmt) == 1 ? (rb + 15) & ~(size_t)15 : rb;
+}
+
+// PIXF_420SP: row pitches of a packed window's luma plane and of its chroma plane(s), and the chroma planes' rows. Every
+// plane's bytes are packed as they are - 16-bit samples stay 16-bit, two chroma planes stay two, the second one
+// pitch * rows behind the first, which is where a windowed frame has it (vittrack_hip.h: vt_pixfmt2)
+static void packed_planes(int fmt, int ww, int wh, size_t* ys, size_t* cs, int* crows) {
+    *ys = ((size_t)ww * pix_row_bpp(fmt) + 15) & ~(size_t)15;
+    *cs = ((size_t)pix_chroma_row_bytes(fmt, ww) + 15) & ~(size_t)15;
+    *crows = pix_chroma_rows(fmt, wh);
 }
 
 // bytes of a window's packed form in the arena, from its extent
 static void size_window(HostWin* win) {
     if (pix_family(win->fmt) == PIXF_420SP) {
         // rows of the packed window start on 16-byte boundaries: the pixel kernel then fetches 8 pixels per load
-        const int uvh = (win->wh + 1) / 2;
-        const size_t ys = ((size_t)win->ww + 15) & ~(size_t)15, uvs = ((size_t)((win->ww + 1) & ~1) + 15) & ~(size_t)15;
+        size_t ys, cs;
+        int crows;
+        packed_planes(win->fmt, win->ww, win->wh, &ys, &cs, &crows);
         win->uv_off = (ys * win->wh + 255) & ~(size_t)255;
-        win->bytes = win->uv_off + uvs * uvh;
+        win->bytes = win->uv_off + cs * crows * (pix_planar(win->fmt) ? 2 : 1);
     } else {
         win->uv_off = 0;
         win->bytes = packed_row_bytes(win->fmt, win->ww) * win->wh;
@@ -53,7 +63,9 @@ static int plan_window(const Engine* e, const vt_frame& hf, const float* box, fl
     } else if (fam == PIXF_422) {
         if ((w & 1) || s0 < 2 * w) return set_err(VT_ERR_INVALID_ARG, "%s: odd width or stride < 2*width", pix_name(fmt));
     } else if (fam == PIXF_420SP) {
-        if (!p1 || s0 < w || s1 < ((w + 1) & ~1)) return set_err(VT_ERR_INVALID_ARG, "%s: bad plane or stride", pix_name(fmt));
+        if (!p1 || s0 < w * bpp || s1 < pix_chroma_row_bytes(fmt, w))
+            return set_err(VT_ERR_INVALID_ARG, "%s: bad plane or stride", pix_name(fmt));
+        if (pix_rows422(fmt) && (w & 1)) return set_err(VT_ERR_INVALID_ARG, "%s: odd width", pix_name(fmt));
     } else {
         return set_err(VT_ERR_INVALID_ARG, "unknown pixel format %d", fmt);
     }
@@ -112,15 +124,24 @@ static void pack_window(const StageArena& a, const HostWin& wn, size_t off, vt_f
             memcpy(dst + r * rs, wn.p0 + (size_t)(wn.y_lo + r) * wn.s0 + (size_t)wn.x_lo * bpp, rb);
         f->plane0 = a.d + off; f->stride0 = (int)rs;
     } else {
-        const int uvw = (wn.ww + 1) & ~1, uvh = (wn.wh + 1) / 2;
-        const size_t ys = ((size_t)wn.ww + 15) & ~(size_t)15, uvs = ((size_t)uvw + 15) & ~(size_t)15;   // as plan_window
+        size_t ys, uvs;                                                                     // as size_window
+        int uvh;
+        packed_planes(wn.fmt, wn.ww, wn.wh, &ys, &uvs, &uvh);
+        const size_t bpp = (size_t)pix_row_bpp(wn.fmt);
+        const bool planar = pix_planar(wn.fmt);
         for (int r = 0; r < wn.wh; ++r)
-            memcpy(dst + (size_t)r * ys, wn.p0 + (size_t)(wn.y_lo + r) * wn.s0 + wn.x_lo, (size_t)wn.ww);
-        // odd frame width: the last pixel's V byte lies one past the row's last full pair
-        const int uv_avail = (int)std::min<long>(uvw, (long)wn.s1 - wn.x_lo);
-        for (int r = 0; r < uvh; ++r)
-            memcpy(dst + wn.uv_off + (size_t)r * uvs, wn.p1 + (size_t)(wn.y_lo / 2 + r) * wn.s1 + wn.x_lo,
-                   (size_t)uv_avail);
+            memcpy(dst + (size_t)r * ys, wn.p0 + (size_t)(wn.y_lo + r) * wn.s0 + (size_t)wn.x_lo * bpp, (size_t)wn.ww * bpp);
+        // chroma bytes of the window's columns (x_lo is even): pairs of samples, or one byte per pair in each of two planes.
+        // Odd frame width: the last pixel's V byte lies one past the row's last full pair
+        const long c_lo = planar ? wn.x_lo / 2 : (long)wn.x_lo * (long)bpp;
+        const int uv_avail = (int)std::min<long>(pix_chroma_row_bytes(wn.fmt, wn.ww), (long)wn.s1 - c_lo);
+        const int r_lo = pix_rows422(wn.fmt) ? wn.y_lo : wn.y_lo / 2;
+        // the caller's second chroma plane lies behind the rows of the whole frame's first, the packed one behind uvh rows
+        const size_t second_src = (size_t)wn.s1 * (size_t)pix_chroma_rows(wn.fmt, wn.h), second_dst = uvs * (size_t)uvh;
+        for (int pl = 0; pl < (planar ? 2 : 1); ++pl)
+            for (int r = 0; r < uvh; ++r)
+                memcpy(dst + wn.uv_off + pl * second_dst + (size_t)r * uvs,
+                       wn.p1 + pl * second_src + (size_t)(r_lo + r) * wn.s1 + c_lo, (size_t)uv_avail);
         f->plane0 = a.d + off; f->plane1 = a.d + off + wn.uv_off;
         f->stride0 = (int)ys; f->stride1 = (int)uvs;
     }
@@ -157,7 +178,8 @@ static int stage_host_frames_to(Engine* e, StageArena& a, hipStream_t copy_on, c
         const bool sp = pix_family(hf.format) == PIXF_420SP;
         const size_t rowb = (size_t)hf.width * pix_row_bpp(hf.format);
         const size_t ext0 = (size_t)(hf.height - 1) * (size_t)hf.stride0 + rowb;
-        const size_t ext1 = sp ? (size_t)((hf.height + 1) / 2 - 1) * (size_t)hf.stride1 + (size_t)((hf.width + 1) & ~1) : 0;
+        const size_t crows = (size_t)pix_chroma_rows(hf.format, hf.height) * (pix_planar(hf.format) ? 2 : 1);
+        const size_t ext1 = sp ? (crows - 1) * (size_t)hf.stride1 + (size_t)pix_chroma_row_bytes(hf.format, hf.width) : 0;
         const uint8_t* d0 = mapped_device_ptr(e->device, (const uint8_t*)hf.plane0, ext0);
         const uint8_t* d1 = sp ? mapped_device_ptr(e->device, (const uint8_t*)hf.plane1, ext1) : nullptr;
         if (d0 && (!sp || d1)) {

@@ -52,7 +52,7 @@ static void snap_fill_header(const Engine* e, SnapHeader* h) {
     h->policy_bytes = sizeof(RefreshPolicy);
     h->rows_bytes = (uint32_t)(sizeof(bf16_t) * (size_t)e->d.nt * e->d.kpad);
     h->total_bytes = (uint32_t)e->snapshot_bytes();
-    h->flags = e->want_any_graphs ? VT_SNAP_FLAG_ANY_GRAPHS : 0u;
+    h->flags = e->want_levels ? VT_SNAP_FLAG_ANY_GRAPHS : 0u;
     h->patch = e->d.patch; h->template_size = e->d.T; h->search_size = e->d.S; h->kpad = e->d.kpad;
     h->tokens_template = e->d.nt;
     memcpy(h->norm_a, e->d.norm_a, sizeof(h->norm_a));

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); VT_PIX_BGR8 .. VT_PIX_UYVY, vt_init_frame / vt_update_frame, then vt_group_enqueue_host_streams / vt_group_enqueue_init_host (added later still, additions only for the same reason); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
+#define VT_ABI_VERSION 5   /* 5: vt_nv12_to_rgb8_batch_device, vt_group_graph_captures, vt_group_*_streams (passes over a subset of a group's streams: added later, additions only - no struct, no existing signature or behaviour changed, so the version stays); VT_PIX_BGR8 .. VT_PIX_UYVY, vt_init_frame / vt_update_frame, then vt_group_enqueue_host_streams / vt_group_enqueue_init_host (added later still, additions only for the same reason); vt_pixfmt2 (VT_PIX2_I420 .. VT_PIX2_XBGR: further values of vt_frame.format, additions only - no function, no struct and no existing value changed, so the version stays); the operator-level test hooks (vt_op_*) moved to vittrack_hip_ops.h / libvittrack_hip_ops.so - the product library exports this header's symbols only; 4: vt_config.host_zero_copy (a former reserved slot: zero = the old default for single trackers), vt_group_set_tuning, vt_op_headconv_bf16, vt_op_headconv_ln_bf16 - additions only, a host built against 3 keeps working; 3: vt_op_gemm_bf16 / vt_op_qkv_bf16 take folded-LayerNorm terms; 2: vt_frame.window_w/h, vt_config.max_device_mib, explicit cfg/mode on vt_op_* */
 
 typedef enum vt_status {
     VT_OK = 0,
@@ -203,28 +203,52 @@ typedef enum vt_pixfmt {
     VT_PIX_UYVY = 7    /* packed U Y0 V Y1, w even: YUY2 with the bytes reordered, window rules of YUY2 */
 } vt_pixfmt;
 
+/* Further values of vt_frame.format (vt_pixfmt itself is closed at the eight formats above). Each is DEFINED as a byte
+ * re-arrangement of RGB8, NV12 or YUY2 - its sibling - and samples exactly as the sibling does. Values 8..15 and
+ * everything above 22 are invalid.
+ * I420 / YV12: the chroma planes are ceil(w/2) x ceil(h/2) bytes and share stride1 (>= ceil(w/2)). plane1 is the FIRST
+ * chroma plane (U for I420, V for YV12); the second begins stride1 * ceil(R/2) bytes behind plane1, R = window_h when
+ * windowed == 1, else height: the contiguous layout of GStreamer's default GstVideoInfo, of av_image_fill_arrays and of
+ * raw .yuv files. A frame whose chroma planes are allocated apart cannot be described. Window rules of NV12; plane1
+ * points at the chroma sample of (origin_x, origin_y).
+ * P010 (P012 and P016 read alike): only the high byte of every 16-bit sample is read - the sample truncated to 8 bits.
+ * Strides in bytes: stride0 >= 2*w, stride1 >= 2*((w+1)&~1). Window rules of NV12, the pointers at byte 2*origin_x.
+ * NV16: w even, stride0 >= w, stride1 >= w, window rules of YUY2. GRAY8, XRGB, XBGR: no window restriction; byte 0 of
+ * an XRGB / XBGR pixel is never read. */
+typedef enum vt_pixfmt2 {
+    VT_PIX2_I420  = 16, /* Y plane; plane1 = U plane, then the V plane: three-plane 4:2:0             -> NV12 */
+    VT_PIX2_YV12  = 17, /* the same with V first                                                        -> NV12 */
+    VT_PIX2_P010  = 18, /* NV12's layout with 16-bit little-endian samples, value in the high bits      -> NV12 */
+    VT_PIX2_NV16  = 19, /* Y plane + interleaved U,V pairs with one chroma row PER luma row (4:2:2)     -> YUY2 */
+    VT_PIX2_GRAY8 = 20, /* one plane, one byte per pixel: r = g = b = that byte                         -> RGB8 */
+    VT_PIX2_XRGB  = 21, /* packed x,R,G,B (ARGB: alpha ignored), stride >= 4*w                          -> RGB8 */
+    VT_PIX2_XBGR  = 22  /* packed x,B,G,R (ABGR: alpha ignored), stride >= 4*w                          -> RGB8 */
+} vt_pixfmt2;
+
 typedef struct vt_frame {        /* one device-resident frame (or a window of it) */
-    const void* plane0;          /* packed formats: the pixels; NV12 / NV21: Y plane */
-    const void* plane1;          /* NV12 / NV21: interleaved UV / VU plane; packed formats: NULL */
+    const void* plane0;          /* packed formats and GRAY8: the pixels; NV12 / NV21 / I420 / YV12 / P010 / NV16: Y plane */
+    const void* plane1;          /* NV12 / NV21 / P010 / NV16: interleaved chroma plane; I420 / YV12: the first chroma
+                                  * plane (the second follows it, see vt_pixfmt2); packed formats and GRAY8: NULL */
     int32_t width, height;       /* size of the FULL frame in pixels */
     int32_t stride0, stride1;    /* bytes */
-    int32_t format;              /* vt_pixfmt */
+    int32_t format;              /* vt_pixfmt or vt_pixfmt2 */
     /* The planes may hold only a window of the frame: plane0 points at frame pixel
-     * (origin_x, origin_y) (NV12 / NV21: both even, plane1 at the matching chroma pair; YUY2 /
-     * UYVY: origin_x even). Pixels of the frame
+     * (origin_x, origin_y) (NV12 / NV21 / I420 / YV12 / P010: both even, plane1 at the matching chroma
+     * sample; YUY2 / UYVY / NV16: origin_x even). Pixels of the frame
      * outside the stored window must not be needed by the call (the tracker reads the search
      * window, side 4*sqrt(w*h) around the last box, plus one pixel). 0,0 = the whole frame. */
     int32_t origin_x, origin_y;
     int32_t windowed;            /* 1: the planes hold only window_w x window_h pixels (strides
                                   * describe that window); 0 with origin 0,0: the whole frame */
     /* Extent of the stored window in pixels (required when windowed == 1 or an origin is set; both
-     * even for NV12 / NV21, window_w even for YUY2 / UYVY, unless the window ends at the frame's edge). A sample
+     * even for NV12 / NV21 / I420 / YV12 / P010, window_w even for YUY2 / UYVY / NV16, unless the window ends at the
+     * frame's edge). A sample
      * that falls inside the frame but outside the stored window reads as black - never out of
      * bounds. 0,0 with no origin: width x height. */
     int32_t window_w, window_h;
 } vt_frame;
 
-/* The single tracker on a frame of any vt_pixfmt. on_device == 0: the planes are host addresses, read
+/* The single tracker on a frame of any vt_pixfmt / vt_pixfmt2. on_device == 0: the planes are host addresses, read
  * like vt_init_rgb8 reads its buffer (only the search window crosses PCIe; origin fields ignored);
  * on_device == 1: they are device addresses, used like the *_device calls' (windows honoured). */
 int vt_init_frame(vt_tracker* t, const vt_frame* frame, int on_device, vt_bbox box);
@@ -727,7 +751,8 @@ typedef struct vt_draw_cmd {
 } vt_draw_cmd;
 
 /* Apply n commands to a device-resident luma plane (width x height, `stride` bytes per row),
- * enqueued on hip_stream (NULL = default stream); the command list is copied before returning. */
+ * enqueued on hip_stream (NULL = default stream); the command list is copied before returning.
+ * It draws on any 8-bit luma plane: the Y plane of I420 / YV12 / NV16 and a GRAY8 frame as well, not P010's. */
 int vt_overlay_nv12_device(int device_id, void* d_y, int width, int height, int stride,
                            const vt_draw_cmd* cmds, int n, void* hip_stream);
 /* Host-pointer form: draws into the packed NV12 buffer (stride == width) in place. */

@@ -1,8 +1,8 @@
 """Crop / resize kernel time by target size (rectangles that do not fit the tile kernel's LDS buffer).
-python tools/preproc_bench.py cfg3|cfg2 [streams] [--format nv12|nv21|rgb8|bgr8|rgbx|bgrx|yuy2|uyvy] [--sizes 64,160]
-(run on the GPU box; VITTRACK_HIP_LIB selects the build). --format: whole 1080p device frames of that vt_pixfmt, made
-from the clip's NV12 frame by the byte permutations of tests/test_gpu_pixel_formats.py (default nv12); --sizes: only
-these targets, no mixed-size runs."""
+python tools/preproc_bench.py cfg3|cfg2 [streams] [--format nv12|nv21|rgb8|bgr8|rgbx|bgrx|yuy2|uyvy|i420|yv12|p010|nv16|gray8|xrgb|xbgr] [--sizes 64,160]
+(run on the GPU box; VITTRACK_HIP_LIB selects the build). --format: whole 1080p device frames of that vt_pixfmt /
+vt_pixfmt2, made from the clip's NV12 frame by the byte re-arrangements of tests/test_gpu_pixel_formats.py and
+tests/planar_formats_util.py (default nv12); --sizes: only these targets, no mixed-size runs."""
 import sys
 sys.path.insert(0, str(__import__('pathlib').Path(__file__).resolve().parents[1]))   # repo root
 import numpy as np
@@ -34,6 +34,21 @@ def device_frame(sc):
             b[w * h:] = nv12[w * h:].reshape(-1, 2)[:, ::-1].reshape(-1)
         d = torch.from_numpy(b).cuda()
         return (vt.frame_nv12 if FMT == "nv12" else vt.frame_nv21)(d.data_ptr(), d.data_ptr() + w * h, w, h), d
+    if FMT in ("i420", "yv12"):
+        uv = nv12[w * h:].reshape(h // 2, w // 2, 2)
+        first, second = (uv[..., 0], uv[..., 1]) if FMT == "i420" else (uv[..., 1], uv[..., 0])
+        d = torch.from_numpy(np.concatenate([nv12[:w * h], first.reshape(-1), second.reshape(-1)])).cuda()
+        return (vt.frame_i420 if FMT == "i420" else vt.frame_yv12)(d.data_ptr(), d.data_ptr() + w * h, w, h), d
+    if FMT == "p010":
+        d = torch.from_numpy((nv12.astype(np.uint16) << 8).astype("<u2").view(np.uint8)).cuda()
+        return vt.frame_p010(d.data_ptr(), d.data_ptr() + 2 * w * h, w, h), d
+    if FMT == "nv16":
+        uv = nv12[w * h:].reshape(h // 2, w)[np.arange(h) // 2]
+        d = torch.from_numpy(np.concatenate([nv12[:w * h], uv.reshape(-1)])).cuda()
+        return vt.frame_nv16(d.data_ptr(), d.data_ptr() + w * h, w, h), d
+    if FMT == "gray8":
+        d = torch.from_numpy(nv12[:w * h].copy()).cuda()
+        return vt.frame_gray8(d.data_ptr(), w, h), d
     if FMT in ("yuy2", "uyvy"):
         y = nv12[:w * h].reshape(h, w)
         uv = nv12[w * h:].reshape(h // 2, w // 2, 2)[np.arange(h) // 2]
@@ -44,11 +59,14 @@ def device_frame(sc):
         return vt.CFrame(d.data_ptr(), None, w, h, 2 * w, 0, vt.PIX_YUY2 if FMT == "yuy2" else vt.PIX_UYVY,
                          0, 0, 0, 0, 0), d
     rgb = vt.nv12_full_to_rgb(nv12, w, h)
-    c = rgb[..., ::-1] if FMT in ("bgr8", "bgrx") else rgb
+    c = rgb[..., ::-1] if FMT in ("bgr8", "bgrx", "xbgr") else rgb
     if FMT in ("rgbx", "bgrx"):
         c = np.concatenate([c, np.zeros((h, w, 1), np.uint8)], axis=2)
+    if FMT in ("xrgb", "xbgr"):
+        c = np.concatenate([np.zeros((h, w, 1), np.uint8), c], axis=2)
     d = torch.from_numpy(np.ascontiguousarray(c)).cuda()
-    helper = {"rgb8": vt.frame_rgb8, "bgr8": vt.frame_bgr8, "rgbx": vt.frame_rgbx, "bgrx": vt.frame_bgrx}[FMT]
+    helper = {"rgb8": vt.frame_rgb8, "bgr8": vt.frame_bgr8, "rgbx": vt.frame_rgbx, "bgrx": vt.frame_bgrx,
+              "xrgb": vt.frame_xrgb, "xbgr": vt.frame_xbgr}[FMT]
     return helper(d.data_ptr(), w, h), d
 
 
