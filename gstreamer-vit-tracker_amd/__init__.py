@@ -159,7 +159,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16", "vt_op_gemm_bench", "vt_op_qkv_bf16", "vt_op_attention_bf16",
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
-    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks",
+    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
 ]
 
 
@@ -325,6 +325,8 @@ def ops_lib():
                                     POINTER(ctypes.c_uint32)]
     L.vt_op_response_peaks.argtypes = [c_int, fp, fp, c_void_p, c_int, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int,
                                        c_int, c_void_p, c_void_p]
+    L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_void_p,
+                                       c_int, c_int]
     _ops = L
     return L
 
@@ -825,6 +827,13 @@ class VitTrack:
         _check(lib().vt_last_peaks(self._h, out.ctypes.data))
         return out
 
+    def set_result_overlay(self, **kw) -> None:
+        """the result overlay of this tracker's engine: see Group.set_result_overlay"""
+        self.as_group().set_result_overlay(**kw)
+
+    def result_overlay_stats(self) -> dict:
+        return self.as_group().result_overlay_stats(0)
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -1287,6 +1296,37 @@ class Group:
         _check(lib().vt_group_last_peaks(self._h, out.ctypes.data if n > 0 else None, n))
         return out[:n]
 
+    def set_result_overlay(self, rect: bool = True, crosshair: bool = True, score: bool = True, thickness: int | None = None,
+                           size: int | None = None, scale: int | None = None, luma: int | None = None, rgb: int | None = None,
+                           min_score_pct: int | None = None) -> None:
+        """the "result_overlay*" keys of vt_group_set_tuning: every DEVICE-frame pass of this engine ends by drawing each
+        stream's new box into its frame - a rectangle (thickness 1..16), a crosshair at the centre (size 1..64) and the
+        text "score: N%" (scale 1..4) - where the result succeeds with score > min_score_pct / 100. luma (0..255): the
+        brightness on luma surfaces and of the text everywhere; rgb (0xRRGGBB): rectangle and crosshair on packed RGB.
+        None keeps a value (style: the reference's 3 / 15 / 2 unless all three were set before). All three shapes off
+        stops the drawing. The first enable makes the engine overlay-capable (graphs recaptured); such an engine WRITES
+        the frames its device passes are given. Refused while a pipelined pass is outstanding."""
+        for key, v in (("result_overlay_luma", luma), ("result_overlay_rgb", rgb), ("result_overlay_min_score_pct", min_score_pct)):
+            if v is not None:
+                if int(v) < 0:
+                    raise ValueError(f"{key}: {v}")
+                self.set_tuning(key, int(v))
+        if thickness is not None or size is not None or scale is not None:
+            st = getattr(self, "_overlay_style", (3, 15, 2))
+            st = tuple(int(n) if n is not None else o for n, o in zip((thickness, size, scale), st))
+            if min(st) < 0 or st[0] > 255 or st[1] > 255:
+                raise ValueError(f"result_overlay_style: {st}")
+            self.set_tuning("result_overlay_style", st[0] | st[1] << 8 | st[2] << 16)
+            self._overlay_style = st
+        self.set_tuning("result_overlay", (1 if rect else 0) | (2 if crosshair else 0) | (4 if score else 0))
+
+    def result_overlay_stats(self, stream: int = 0) -> dict:
+        """vt_group_read_tensor "result_overlay": the engine's flags and the stream's counters since the first enable -
+        drawn (by the stream's last pass), n_drawn, n_gated (score gate), n_unsupported (P010), last_n (N of the last
+        label drawn)"""
+        v = self.read_tensor("result_overlay", stream)
+        return dict(zip(("flags", "drawn", "n_drawn", "n_gated", "n_unsupported", "last_n"), (int(x) for x in v)))
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""
@@ -1551,6 +1591,41 @@ def op_response_peaks(head_out, hann, states, policies, B, grid, slot_stream=Non
         B, grid, out["records"].ctypes.data_as(c_void_p), out["host_records"].ctypes.data_as(c_void_p)))
     out["states"] = st
     return out
+
+
+# the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)
+OVERLAY_POLICY_DTYPE = np.dtype([("flags", "<i4"), ("thickness", "<i4"), ("size", "<i4"), ("scale", "<i4"), ("luma", "<i4"),
+                                 ("rgb", "<i4"), ("min_score_pct", "<i4"), ("reserved", "<i4")])
+OVERLAY_STATS_DTYPE = np.dtype([("drawn", "<i4"), ("n_drawn", "<i4"), ("n_gated", "<i4"), ("n_unsupported", "<i4"),
+                                ("last_n", "<i4"), ("reserved", "<i4", 3)])
+
+
+def op_result_overlay(frames, results, flags=7, thickness=3, size=15, scale=2, luma=255, rgb=0x00FF00, min_score_pct=25,
+                      slot_stream=None, winner=None, stats=None, n_streams=None, device_frames=True, device=0):
+    """vt_op_result_overlay: the result-overlay launch (k_result_overlay.hip) on given operands, nothing else. frames: CFrame
+    per slot with DEVICE planes (they are drawn into), results [n] RESULT_DTYPE by slot, slot_stream [n]: slot -> stream
+    (None: the identity), winner [n]: a candidate pass's winner table (None: every slot may draw), stats: OVERLAY_STATS_DTYPE
+    records by stream to start from (None: zeros), device_frames False: the launch of a host pass. -> the stats as they
+    came back"""
+    n = len(frames)
+    arr = (CFrame * n)(*frames)
+    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+    assert res.shape == (n,)
+    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
+    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
+    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
+    if n_streams is None:
+        n_streams = n if stats is None else len(stats)
+    st = np.zeros(n_streams, OVERLAY_STATS_DTYPE) if stats is None else np.ascontiguousarray(stats, OVERLAY_STATS_DTYPE).reshape(-1).copy()
+    assert len(st) == n_streams
+    pol = np.zeros(1, OVERLAY_POLICY_DTYPE)
+    pol[0] = (flags, thickness, size, scale, luma, rgb, min_score_pct, 0)
+    i32 = POINTER(c_int32)
+    _check_op(ops_lib().vt_op_result_overlay(
+        device, arr, res.ctypes.data_as(c_void_p), smap.ctypes.data_as(i32) if smap is not None else None,
+        win.ctypes.data_as(i32) if win is not None else None, n, pol.ctypes.data_as(c_void_p), st.ctypes.data_as(c_void_p),
+        n_streams, 1 if device_frames else 0))
+    return st
 
 
 def op_head_decode(t_bf16_bits, w4, b4, hann, states, B, grid, form=0, w3_bf16_bits=None, b3=None, slot_stream=None,

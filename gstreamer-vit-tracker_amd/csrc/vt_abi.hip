@@ -266,6 +266,16 @@ int refuse_while_pipelined(const Engine* e, const char* what) {
     return VT_OK;
 }
 
+// A device entry point builds its pass inside one of these: the pass's block then says that its frames are the caller's
+// device memory, which the result overlay may draw into (Engine::frames_on_device)
+struct DeviceFramesScope {
+    Engine* e;
+    explicit DeviceFramesScope(Engine* en) : e(en) { e->frames_on_device = 1; }
+    ~DeviceFramesScope() { e->frames_on_device = 0; }
+    DeviceFramesScope(const DeviceFramesScope&) = delete;
+    DeviceFramesScope& operator=(const DeviceFramesScope&) = delete;
+};
+
 extern "C" {
 
 int vt_group_init_device(vt_group* g, int stream, const vt_frame* frame, vt_bbox box) try {
@@ -276,6 +286,7 @@ int vt_group_init_device(vt_group* g, int stream, const vt_frame* frame, vt_bbox
 int vt_group_enqueue_device(vt_group* g, const vt_frame* frames, int n) try {
     if (!g || !frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "enqueue_device")) return rc;
+    DeviceFramesScope on_device(g->e);
     return g->e->enqueue(nullptr, frames, n);
 } VT_NOTHROW_INT
 int vt_group_wait(vt_group* g, vt_result* out, int n) try {
@@ -286,18 +297,21 @@ int vt_group_wait(vt_group* g, vt_result* out, int n) try {
 int vt_group_update_device(vt_group* g, const vt_frame* frames, int n, vt_result* out) try {
     if (!g || !frames) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "update_device")) return rc;
+    DeviceFramesScope on_device(g->e);
     if (int rc = g->e->enqueue(nullptr, frames, n)) return rc;
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
 int vt_group_enqueue_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n) try {
     if (!g || !streams) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "enqueue_device_streams")) return rc;
+    DeviceFramesScope on_device(g->e);
     return g->e->enqueue(streams, frames, n);
 } VT_NOTHROW_INT
 int vt_group_update_device_streams(vt_group* g, const int32_t* streams, const vt_frame* frames, int n,
                                    vt_result* out) try {
     if (!g || !streams || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "update_device_streams")) return rc;
+    DeviceFramesScope on_device(g->e);
     if (int rc = g->e->enqueue(streams, frames, n)) return rc;
     return g->e->wait(out, n);
 } VT_NOTHROW_INT
@@ -305,6 +319,7 @@ int vt_group_update_device_candidates(vt_group* g, const vt_candidate* cands, co
                                       vt_result* out, int32_t* winner) try {
     if (!g || !cands || !frames || !out) return set_err(VT_ERR_INVALID_ARG, "null argument");
     if (int rc = refuse_while_pipelined(g->e, "update_device_candidates")) return rc;
+    DeviceFramesScope on_device(g->e);
     if (int rc = g->e->enqueue_candidates(cands, frames, n)) return rc;
     return g->e->wait_candidates(out, winner, n);
 } VT_NOTHROW_INT
@@ -359,6 +374,7 @@ int vt_group_set_tuning(vt_group* g, const char* key, int value) try {
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
     const std::string k = key;
+    if (Engine::overlay_key(k)) return e->set_overlay(k, value);    // engine options: the passes are captured again by the first enable only
     if (k == "head_band") e->head_band_kernel = value < 0 ? 2 : value;   // 0 / 1 / 2, see Engine::head_band_kernel
     else if (k == "last_rows") e->last_rows = value != 0;        // 0: the last block runs all rows; else (default) the search rows where eligible
     else if (k == "crop_tier") e->crop_tier_forced = value;      // < 0: chosen per pass from the known boxes (default)
@@ -391,6 +407,7 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
     if (int rc = refuse_while_pipelined(e, "profile")) return rc;
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
+    DeviceFramesScope on_device(e);
     PassShape ps;       // the full pass, built as Engine::enqueue builds it, launched eagerly under the profiler
     if (int rc = e->prepare_pass(nullptr, frames, n, nullptr, nullptr, nullptr, &ps)) return rc;
     Profiler prof;
@@ -469,6 +486,12 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         return set_err(VT_ERR_HIP, "read_tensor: sync failed");
     const ModelDims& d = e->d;
     std::string n(name);
+    if (n == "result_overlay") {        // by stream, whatever the last pass was: the overlay's flags and the stream's counters
+        if (!out) return e->overlay_capable ? 6 : e->overlay_stats(stream, nullptr);
+        if (capacity < 6) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        if (int rc = e->overlay_stats(stream, out)) return rc;
+        return 6;
+    }
     // every tensor but the stream's state and the replay counters belongs to the last pass: the stream's slot in it
     size_t b = (size_t)stream;
     if (n.rfind("slot.", 0) == 0) {     // "slot.<tensor>": `stream` IS a slot of the last pass (the losing slots of a candidate pass)
@@ -689,6 +712,8 @@ static int tracker_update(vt_tracker* t, const vt_frame& frame, int on_device, v
     }
     if (!out) return set_err(VT_ERR_INVALID_ARG, "null result pointer");
     memset(out, 0, sizeof(*out));
+    DeviceFramesScope scope(e);
+    e->frames_on_device = on_device;        // a host frame went through the staging above: never drawn into
     if (int rc = e->enqueue(nullptr, &f, 1)) return rc;
     return e->wait(out, 1);
 }

@@ -37,7 +37,7 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
@@ -595,6 +595,12 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         L("response_peaks", 0, (double)n * (d.ns * 8.0 * sizeof(float) + 2.0 * sizeof(vt_peaks)),
           [&] { return launch_response_peaks(pa, stream); });
     }
+    if (overlay_capable) {  // LAST: the slots' boxes into their frames - the refresh and chip launches above cut undrawn pixels
+        const ResultOverlayArgs oa{d_frames, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_overlay_policy(),
+                                   d_overlay_stats(), d_devflag(), n};
+        L("result_overlay", 0, (double)n * (sizeof(FrameDesc) + sizeof(vt_result) + sizeof(OverlayStats)),
+          [&] { return launch_result_overlay(oa, stream); });
+    }
     if (lerr != hipSuccess)
         return set_err(VT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(lerr));
     return VT_OK;     // results and states reach the host through the decode kernel's own stores (PassOut)
@@ -841,6 +847,7 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
         int32_t* map = (int32_t*)((char*)hf + map_offset());
         for (int i = 0; i < n; ++i) map[i] = streams[i];
     }
+    *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipEventRecord(ring_ev[slot], stream));
     if (full) {
@@ -1199,6 +1206,82 @@ int Engine::last_peaks(vt_peaks* out, int n) const {
     return VT_OK;
 }
 
+// ---- result overlay ----------------------------------------------------------------------------------
+
+// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero flags: the policy record and the
+// counters are allocated and every graph is captured again with the overlay launch at its end - on the idle stream,
+// never inside an update, as set_peaks does. Every later change is one small copy: the passes read the record.
+int Engine::set_overlay(const std::string& key, int value) {
+    OverlayPolicy p = overlay_policy;
+    const OverlayPolicy def = VT_OVERLAY_DEFAULT_POLICY;
+    if (key == "result_overlay") {
+        p.flags = value < 0 ? def.flags : value;
+        if (p.flags > 7) return set_err(VT_ERR_INVALID_ARG, "result_overlay: flags %d (1 rectangle | 2 crosshair | 4 label, 0: off)", value);
+    } else if (key == "result_overlay_style") {
+        const int th = value & 255, size = (value >> 8) & 255, scale = value >> 16;
+        if (value < 0) { p.thickness = def.thickness; p.size = def.size; p.scale = def.scale; }
+        else if (th < 1 || th > 16 || size < 1 || size > 64 || scale < 1 || scale > 4)
+            return set_err(VT_ERR_INVALID_ARG, "result_overlay_style: thickness %d (1..16), size %d (1..64), scale %d (1..4)", th, size, scale);
+        else { p.thickness = th; p.size = size; p.scale = scale; }
+    } else if (key == "result_overlay_luma") {
+        p.luma = value < 0 ? def.luma : value;
+        if (p.luma > 255) return set_err(VT_ERR_INVALID_ARG, "result_overlay_luma: %d (0..255)", value);
+    } else if (key == "result_overlay_rgb") {
+        p.rgb = value < 0 ? def.rgb : value;
+        if (p.rgb > 0xFFFFFF) return set_err(VT_ERR_INVALID_ARG, "result_overlay_rgb: 0x%x (0..0xFFFFFF)", (unsigned)value);
+    } else if (key == "result_overlay_min_score_pct") {
+        p.min_score_pct = value < 0 ? def.min_score_pct : value;
+        if (p.min_score_pct > 100) return set_err(VT_ERR_INVALID_ARG, "result_overlay_min_score_pct: %d (0..100)", value);
+    } else {
+        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
+    }
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!overlay_capable && p.flags != 0) {
+        const size_t extra = overlay_bytes();
+        if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
+            return set_err(VT_ERR_OOM, "the result overlay needs %.3f MiB more HBM for its records; vt_config.max_device_mib "
+                           "allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
+        uint8_t* store = nullptr;       // the policy | [B] counters, all zero
+        hipError_t he = dalloc0(&store, extra, stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(stream);
+        if (he != hipSuccess) {
+            if (store) (void)hipFree(store);
+            return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "result overlay: %s", hipGetErrorString(he));
+        }
+        d_overlay = store;
+        overlay_capable = true;
+        drop_graphs();
+        if (int rc = capture_all_graphs()) {
+            char keep[512];
+            memcpy(keep, vt_err_text(), sizeof(keep));
+            drop_graphs();
+            (void)hipFree(store);
+            d_overlay = nullptr;
+            overlay_capable = false;
+            (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
+            memcpy(vt_err_text(), keep, sizeof(keep));
+            return rc;
+        }
+    } else if (overlay_capable) {
+        HIPCHK(hipMemcpy(d_overlay_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
+    }
+    overlay_policy = p;
+    return VT_OK;
+}
+
+// [6]: flags, drawn by the stream's last pass, passes drawn / gated / on a format that is not drawable, N of the last label
+int Engine::overlay_stats(int s, float* out6) {
+    if (!overlay_capable)
+        return set_err(VT_ERR_INVALID_ARG, "result overlay: not enabled on this engine (vt_group_set_tuning \"result_overlay\")");
+    OverlayStats st{};
+    HIPCHK(hipMemcpy(&st, d_overlay_stats() + s, sizeof(st), hipMemcpyDeviceToHost));
+    out6[0] = (float)overlay_policy.flags; out6[1] = (float)st.drawn_last; out6[2] = (float)st.n_drawn;
+    out6[3] = (float)st.n_gated; out6[4] = (float)st.n_unsupported; out6[5] = (float)st.last_n;
+    return VT_OK;
+}
+
 // ---- candidate passes --------------------------------------------------------------------------------
 
 int check_state_box(const float* box4) {
@@ -1276,6 +1359,7 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
         hc[i] = cands[i];
     }
     *(PassOut*)(hf + B) = PassOut{h_results, nullptr, peaks_capable ? h_peaks : nullptr};
+    *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_cands, hc, sizeof(vt_candidate) * (size_t)n, hipMemcpyHostToDevice, stream));
     HIPCHK(hipEventRecord(ring_ev[slot], stream));

@@ -25,6 +25,7 @@
 
 #include "vt_common.hpp"
 #include "k_cand.hpp"
+#include "k_result_overlay.hpp"
 
 // ---- error plumbing ------------------------------------------------------------------------------
 
@@ -169,7 +170,7 @@ struct Engine {
     unsigned* d_panel_cnt = nullptr;   // arrival counters of the 256-row panels (X-epilogues of the 256x256 kernel)
     float *d_foldv = nullptr, *d_headout = nullptr;
     StreamState* d_states = nullptr;
-    FrameDesc* d_frames = nullptr;      // per-pass block: [B] frame descriptors (by slot) | PassOut | [B] slot -> stream
+    FrameDesc* d_frames = nullptr;      // per-pass block: [B] frame descriptors (by slot) | PassOut | [B] slot -> stream | device-frames word
     // template rows of every stream as init wrote them, [B][nt][kpad]: a subset pass gathers its streams' rows into its
     // slots' segments of d_patches, and the next full pass puts every segment back from here
     bf16_t* d_tpl = nullptr;
@@ -207,7 +208,7 @@ struct Engine {
     // HBM of the optional features this engine has enabled, beside activation_bytes() under max_device_mib
     size_t feature_bytes() const {
         return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0) +
-               (peaks_capable ? peaks_bytes() : 0);
+               (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0);
     }
     int enable_chips(int size, int kind, const float* na, const float* nb);   // outside any update: the store, graphs recaptured
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
@@ -224,6 +225,23 @@ struct Engine {
     size_t peaks_bytes() const { return (size_t)B * (sizeof(vt_peaks) + sizeof(PeaksPolicy)); }
     int set_peaks(int stream, int max_peaks, int radius, float min_resp);     // stream -1: all; the first enable is in here
     int last_peaks(vt_peaks* out, int n) const;
+    // result overlay (k_result_overlay.hip). ONE policy per engine. The first non-zero flags allocate the
+    // policy record + the [B] counters by stream and make the engine overlay-capable for good: every pass ends with the
+    // overlay launch, behind the refresh, chip and peaks launches. Engines that never enable launch what they always did.
+    // A style, colour or gate value set before that is kept in overlay_policy and goes up with the enable.
+    bool overlay_capable = false;
+    OverlayPolicy overlay_policy = VT_OVERLAY_DEFAULT_POLICY;     // the host's copy
+    uint8_t* d_overlay = nullptr;                 // ONE allocation: the policy record, then the [B] OverlayStats
+    OverlayPolicy* d_overlay_policy() const { return reinterpret_cast<OverlayPolicy*>(d_overlay); }
+    OverlayStats* d_overlay_stats() const { return reinterpret_cast<OverlayStats*>(d_overlay + sizeof(OverlayPolicy)); }
+    size_t overlay_bytes() const { return sizeof(OverlayPolicy) + (size_t)B * sizeof(OverlayStats); }
+    // 1 while a device entry point builds its pass (vt_abi.hip: DeviceFramesScope): prepare_pass / enqueue_candidates write
+    // it into the pass's block, where the overlay launch reads it. Host-pointer passes hand the kernels staging or
+    // mapped host memory: they never draw.
+    int frames_on_device = 0;
+    static bool overlay_key(const std::string& key) { return key.rfind("result_overlay", 0) == 0; }
+    int set_overlay(const std::string& key, int value);     // the keys of vt_group_set_tuning; the first enable is in here
+    int overlay_stats(int stream, float* out6);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -234,8 +252,10 @@ struct Engine {
     // pinned host
     static const int RING = 8;
     FrameDesc* h_frames = nullptr;  // [RING] blocks of B descriptors + PassOut + the slot map (16-B multiples)
-    size_t frames_block_bytes() const { return (sizeof(FrameDesc) * (size_t)B + sizeof(PassOut) + 4 * (size_t)B + 15) & ~(size_t)15; }
+    size_t frames_block_bytes() const { return (sizeof(FrameDesc) * (size_t)B + sizeof(PassOut) + 4 * (size_t)B + 4 + 15) & ~(size_t)15; }
     size_t map_offset() const { return sizeof(FrameDesc) * (size_t)B + sizeof(PassOut); }
+    size_t devflag_offset() const { return map_offset() + 4 * (size_t)B; }     // the pass's device-frames word (result overlay)
+    const int32_t* d_devflag() const { return (const int32_t*)((const char*)d_frames + devflag_offset()); }
     const int32_t* d_map() const { return (const int32_t*)((const char*)d_frames + map_offset()); }
     // the last pass (written by prepare_pass only): its slot count and, for a subset pass, the stream of every slot
     // (empty: all B streams in order); feat_in_head: it did not write d_feat (recomputed when read)

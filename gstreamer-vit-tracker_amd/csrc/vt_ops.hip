@@ -827,4 +827,55 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The result-overlay launch on given operands: see include/vittrack_hip_ops.h. Nothing runs but launch_result_overlay.
+int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result* results, const int32_t* slot_stream,
+                         const int32_t* winner, int n, const int32_t* policy, int32_t* stats, int n_streams,
+                         int device_frames) try {
+    if (!frames || !results || !policy || !stats || n < 1 || n > VT_RESULT_OVERLAY_MAX_SLOTS || n_streams < 1)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "result_overlay: %d streams for %d slots", n_streams, n);
+    OverlayPolicy pol;
+    memcpy(&pol, policy, sizeof(pol));
+    if (pol.flags < 0 || pol.flags > 7 || pol.thickness < 1 || pol.thickness > 16 || pol.size < 1 || pol.size > 64 || pol.scale < 1 ||
+        pol.scale > 4 || pol.luma < 0 || pol.luma > 255 || pol.rgb < 0 || pol.rgb > 0xFFFFFF || pol.min_score_pct < 0 ||
+        pol.min_score_pct > 100)
+        return set_err(VT_ERR_INVALID_ARG, "result_overlay: policy out of range");
+    std::vector<FrameDesc> desc((size_t)n);
+    for (int b = 0; b < n; ++b) {
+        if (int rc = check_frame(frames[b])) return rc;
+        to_desc(frames[b], &desc[(size_t)b]);
+        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_streams))
+            return set_err(VT_ERR_INVALID_ARG, "result_overlay: slot %d names stream %d of %d", b, (int)slot_stream[b], n_streams);
+        if (winner && (winner[b] < 0 || winner[b] >= n))
+            return set_err(VT_ERR_INVALID_ARG, "result_overlay: winner[%d] = %d of %d slots", b, (int)winner[b], n);
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    DevBuf dfr, dres, dmap, dwin, dpol, dst, dflag;
+    HIPCHK(dfr.alloc((size_t)n * sizeof(FrameDesc))); HIPCHK(dres.alloc((size_t)n * sizeof(vt_result)));
+    HIPCHK(dpol.alloc(sizeof(OverlayPolicy))); HIPCHK(dst.alloc((size_t)n_streams * sizeof(OverlayStats))); HIPCHK(dflag.alloc(4));
+    HIPCHK(hipMemcpy(dfr.p, desc.data(), (size_t)n * sizeof(FrameDesc), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dres.p, results, (size_t)n * sizeof(vt_result), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dst.p, stats, (size_t)n_streams * sizeof(OverlayStats), hipMemcpyHostToDevice));
+    const int32_t flag = device_frames != 0;
+    HIPCHK(hipMemcpy(dflag.p, &flag, 4, hipMemcpyHostToDevice));
+    if (slot_stream) {
+        HIPCHK(dmap.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(dmap.p, slot_stream, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    if (winner) {
+        HIPCHK(dwin.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(dwin.p, winner, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    const ResultOverlayArgs oa{(const FrameDesc*)dfr.p, (const vt_result*)dres.p, slot_stream ? (const int32_t*)dmap.p : nullptr,
+                               winner ? (const int32_t*)dwin.p : nullptr, (const OverlayPolicy*)dpol.p, (OverlayStats*)dst.p,
+                               (const int32_t*)dflag.p, n};
+    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(launch_result_overlay(oa, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(stats, dst.p, (size_t)n_streams * sizeof(OverlayStats), hipMemcpyDeviceToHost));
+    return VT_OK;
+} VT_NOTHROW_INT
+
 }  // extern "C"

@@ -785,7 +785,52 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
 /* Stage taps: when enabled the pass runs eagerly and keeps a copy of the residual stream after the
  * patch embedding and after every encoder block (for stage-level parity tests). */
 int vt_group_enable_taps(vt_group* g, int enable);
-/* Diagnostics (A/B measurements and parity tests of alternative kernels; results are the same quantity either
+/* Engine options and diagnostics.
+ *
+ * ENGINE OPTIONS - the result overlay (DESIGN.md section 3 "Result overlay"). The reference draws directly behind its update
+ * (src/pipeline.rs:145-172, src/pipeline_ir.rs:182-202): a rectangle of thickness 3 at the new box, a crosshair of size 15 at
+ * its centre, the text "score: NN%". With these keys a pass does that itself, as its LAST launch, for every slot at once.
+ * The policy is per engine (a single tracker: through vt_tracker_as_group):
+ *   key                              value                                                         default (a negative value selects it)
+ *   "result_overlay"                 flags: 1 rectangle | 2 crosshair | 4 score label; 0 = off     0
+ *   "result_overlay_style"           thickness | size << 8 | scale << 16: rectangle thickness       3, 15, 2 (the reference's)
+ *                                    1..16, crosshair size 1..64, text scale 1..4
+ *   "result_overlay_luma"            0..255: brightness on luma surfaces, of the text everywhere    255
+ *   "result_overlay_rgb"             0..0xFFFFFF: rectangle and crosshair on packed-RGB surfaces    0x00FF00 (src/pipeline_ir.rs:195)
+ *   "result_overlay_min_score_pct"   0..100: the score gate                                         25 (src/tracker_context.rs: score > 0.25)
+ * A value outside its range returns VT_ERR_INVALID_ARG and changes nothing. A style, colour or gate value set before the
+ * engine is overlay-capable is remembered. The first non-zero "result_overlay" makes the engine overlay-capable for good
+ * (records within max_device_mib, else VT_ERR_OOM and nothing changes; the captured passes are captured again, here): from
+ * then on every pass carries one more launch. Engines that never enable launch exactly what they always did. Later
+ * changes of any of the keys, flags 0 included, are one small copy and capture nothing.
+ *   A slot draws iff ALL of: (1) the flags are non-zero; (2) the pass received its frames through a device entry point -
+ * vt_group_update_device*, vt_group_enqueue_device*, vt_group_update_device_candidates, vt_update_*_device, vt_update_frame
+ * with on_device == 1, vt_group_profile_device; host-pointer passes never draw, the zero-copy route included (their frames
+ * are the library's staging or the caller's host memory); (3) in a candidate pass the slot is its stream's winner;
+ * (4) r.success != 0 and r.score > (float)pct / 100.0f (a NaN fails); (5) the frame's format is drawable: every format but
+ * P010, which is counted instead.
+ *   What is drawn, with b = r.bbox: the frame's bytes after the pass are those this vt_draw_cmd list leaves, applied in this
+ * order to the frame before the pass - flag 1: VT_DRAW_RECT {x = b.x, y = b.y, w = b.width, h = b.height, p = thickness};
+ * flag 2: VT_DRAW_CROSSHAIR {x = b.x + b.width / 2, y = b.y + b.height / 2, p = size} (C integer division, as in the
+ * reference); flag 4: VT_DRAW_TEXT "score: N%", N = clamp((int)rintf(r.score * 100.0f), 0, 100) (one binary32 multiply,
+ * ties to even), p = scale, x = max(b.x, 0), y = b.y - 7 * scale - 4 if that is >= 0, else b.y + b.height + 4.
+ *   Surfaces. LUMA: the Y plane of NV12 / NV21 / I420 / YV12 / NV16, the Y bytes of YUY2 / UYVY, and GRAY8 - the semantics
+ * of vt_overlay_nv12_device (its usize quirks included), every value the luma key, chroma never touched. PACKED RGB: RGB8 /
+ * BGR8 / RGBX / BGRX / XRGB / XBGR - the semantics of vt_overlay_rgb8_device on the RGB8 sibling, rectangle and crosshair in
+ * the rgb key, the text in the luma key as r = g = b, the pad byte never written. W and H of the predicates are the FULL
+ * frame's; of a windowed frame (origin_*, windowed, window_w / window_h) only pixels inside the stored window are written,
+ * at their address in that window. No store ever leaves the stored window.
+ *   Several slots on one frame (several targets per camera; candidate slots): slots whose vt_frame are field-for-field equal
+ * draw as if their lists were concatenated in slot order - where shapes overlap, the higher slot's pixel stands. Slots whose
+ * descriptors differ but alias the same memory have an UNDEFINED order where their shapes overlap.
+ *   Ordering: the overlay runs behind the candidate commit, the template refresh, the target chips and the response peaks
+ * of the same pass, so a refreshed template and a chip are cut from UNDRAWN pixels. The frame is complete when vt_group_wait,
+ * vt_group_wait_next or the synchronous call returns. THE CALLER'S NEW RULE: on an overlay-enabled engine a device pass
+ * WRITES the frames it is given, although vt_frame's pointers are const - hand it memory that may be written, and do not
+ * read the frame concurrently with the pass.
+ *   Read-out: vt_group_read_tensor(g, stream, "result_overlay", ...). Not part of a stream snapshot (policy and counters).
+ *
+ * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
  * with the LayerNorm as a launch of its own, 0 = implicit GEMMs + head_out + decode launches; key "crop_tier": >= 0 forces the crop
@@ -794,7 +839,8 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * where the pass is eligible - no taps, the attention kernel of the hot path, enough streams in the pass for the compacted
  * projection to stay on the 256x256 GEMM kernel (19 of ViT-B/16 at search 384) - 0 = every pass runs all rows. Results, "feat",
  * "head_out" and the states are the same bits either way; "last_block_rows" of vt_group_read_tensor says what the last pass
- * did. Every key drops the captured passes and captures them again here. Not while a pipelined pass is outstanding. */
+ * did. Every diagnostic key drops the captured passes and captures them again here. No key - option or diagnostic - while
+ * a pipelined pass is outstanding. */
 int vt_group_set_tuning(vt_group* g, const char* key, int value);
 /* A single tracker viewed as a group of one (taps, profiling, stream handle). The view belongs to
  * the tracker: valid until vt_destroy(t), the same pointer on every call, never to be destroyed
@@ -828,6 +874,10 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * returns VT_ERR_INVALID_ARG. After a candidate pass (vt_group_update_*_candidates) the stream's slot is its WINNING
  * slot. A per-pass tensor name prefixed with "slot." ("slot.head_out", ...) takes `stream` as a SLOT index of the last
  * pass instead: the way to a losing slot's tensors.
+ * "result_overlay" [6] (by STREAM, whatever the last pass was; counted since the engine became overlay-capable, see
+ * vt_group_set_tuning): the engine's flags, drawn by the stream's last pass (0 or 1), number of passes drawn, number gated
+ * (rule 4), number on a format that is not drawable (rule 5), N of the last label drawn. VT_ERR_INVALID_ARG on an engine
+ * that never enabled the overlay.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

@@ -114,6 +114,17 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
 int vt_op_response_peaks(int device_id, const float* head_out, const float* hann, void* states, int n_states,
                          const void* policies, const int32_t* slot_stream, const int32_t* winner, int B, int grid,
                          vt_peaks* records, vt_peaks* host_records);
+/* The result-overlay launch (csrc/k_result_overlay.hip, the "result_overlay" keys of vt_group_set_tuning in vittrack_hip.h)
+ * on given operands, and nothing else. frames [n] by slot: DEVICE planes, checked like a pass's frames - they are WRITTEN;
+ * results [n] by slot; slot_stream (nullable) [n]: slot -> stream < n_streams (NULL: the identity, n_streams >= n); winner
+ * (nullable) [n]: a candidate pass's winner table, only slots with winner[i] == i draw; policy: 8 int32 - flags 0..7,
+ * thickness 1..16, size 1..64, scale 1..4, luma 0..255, rgb 0..0xFFFFFF, min_score_pct 0..100, reserved; stats (in and
+ * out): n_streams records of 8 int32 by stream - drawn by this launch, passes drawn, gated, on a format that is not
+ * drawable, N of the last label, 3 reserved; device_frames: the pass's device-frames word (0: a host pass, nothing draws).
+ * The boxes are the caller's: any int32 values. A policy, map or frame out of range: VT_ERR_INVALID_ARG. */
+int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result* results, const int32_t* slot_stream,
+                         const int32_t* winner, int n, const int32_t* policy, int32_t* stats, int n_streams,
+                         int device_frames);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
