@@ -160,6 +160,7 @@ OPS_EXPORTS = [
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
+    "vt_op_motion_prior",
 ]
 
 
@@ -325,6 +326,8 @@ def ops_lib():
                                     POINTER(ctypes.c_uint32)]
     L.vt_op_response_peaks.argtypes = [c_int, fp, fp, c_void_p, c_int, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int,
                                        c_int, c_void_p, c_void_p]
+    L.vt_op_motion_prior.argtypes = [c_int, c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, POINTER(c_int32), POINTER(c_int32),
+                                     c_void_p, c_int, c_int, c_void_p, c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_void_p,
                                        c_int, c_int]
     _ops = L
@@ -834,6 +837,14 @@ class VitTrack:
     def result_overlay_stats(self) -> dict:
         return self.as_group().result_overlay_stats(0)
 
+    def set_motion_prior(self, on: bool = True, gain_pct: int | None = None, coast: int | None = None,
+                         max_pct: int | None = None) -> None:
+        """the motion prior of this tracker's engine: see Group.set_motion_prior"""
+        self.as_group().set_motion_prior(on, gain_pct, coast, max_pct)
+
+    def motion(self) -> dict:
+        return self.as_group().motion(0)
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -1327,6 +1338,28 @@ class Group:
         v = self.read_tensor("result_overlay", stream)
         return dict(zip(("flags", "drawn", "n_drawn", "n_gated", "n_unsupported", "last_n"), (int(x) for x in v)))
 
+    def set_motion_prior(self, on: bool = True, gain_pct: int | None = None, coast: int | None = None,
+                         max_pct: int | None = None) -> None:
+        """the "motion_*" keys of vt_group_set_tuning: every pass of this engine first moves each of its streams' boxes by
+        a per-stream velocity estimate kept on the device, so the search window is cut where the target is heading, and
+        keeps the box moving through `coast` (0..60) failed updates. gain_pct (1..100): weight of the newest displacement;
+        max_pct (0..200): per-axis limit of the velocity in percent of sqrt(w*h) of the new box. None keeps a value. The
+        first enable makes the engine motion-capable (graphs recaptured, two more launches per pass from then on); on=False
+        zeroes every stream's record. Refused while a pipelined pass is outstanding."""
+        for key, v in (("motion_gain_pct", gain_pct), ("motion_coast", coast), ("motion_max_pct", max_pct)):
+            if v is not None:
+                if int(v) < 0:
+                    raise ValueError(f"{key}: {v}")
+                self.set_tuning(key, int(v))
+        self.set_tuning("motion_prior", 1 if on else 0)
+
+    def motion(self, stream: int = 0) -> dict:
+        """vt_group_read_tensor "motion": the engine flag and the stream's record - on, v (vx, vy), live, shift (of the
+        stream's last pass), n_shift (passes with a non-zero shift), n_coast (failed updates that advanced the box)"""
+        v = self.read_tensor("motion", stream)
+        return dict(on=int(v[0]), v=(float(v[1]), float(v[2])), live=int(v[3]), shift=(float(v[4]), float(v[5])),
+                    n_shift=int(v[6]), n_coast=int(v[7]))
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""
@@ -1591,6 +1624,41 @@ def op_response_peaks(head_out, hann, states, policies, B, grid, slot_stream=Non
         B, grid, out["records"].ctypes.data_as(c_void_p), out["host_records"].ctypes.data_as(c_void_p)))
     out["states"] = st
     return out
+
+
+# the motion prior's records (csrc/vt_common.hpp: MotionRec 48 bytes by stream, MotionPolicy 16 bytes per engine)
+MOTION_REC_DTYPE = np.dtype([("v", "<f4", 2), ("prior", "<f4", 4), ("shift", "<f4", 2), ("live", "<i4"), ("n_shift", "<i4"),
+                             ("n_coast", "<i4"), ("reserved", "<i4")])
+CANDIDATE_DTYPE = np.dtype([("stream", "<i4"), ("has_box", "<i4"), ("box", "<f4", 4)])
+
+
+def op_motion_prior(states, records, results, on=1, gain_pct=50, coast=5, max_pct=100, slot_stream=None, cands=None, winner=None,
+                    stages=3, host_states=None, host_records=None, device=0):
+    """vt_op_motion_prior: the place (stages & 1) and settle (stages & 2) launches of k_motion.hip on given operands,
+    nothing else. states: snapshot.STATE records by stream, records: MOTION_REC_DTYPE by stream, results [n] RESULT_DTYPE by
+    slot, slot_stream [n]: slot -> stream (None: the identity); the candidate form: cands [n] CANDIDATE_DTYPE + winner [n].
+    host_states / host_records: what the pinned mirrors hold before (None: that mirror is null). -> dict(states, records,
+    host_states, host_records) as they came back"""
+    from .snapshot import STATE
+    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    rec = np.ascontiguousarray(records, MOTION_REC_DTYPE).reshape(-1).copy()
+    assert len(rec) == len(st)
+    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+    n = len(res)
+    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
+    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
+    cd = None if cands is None else np.ascontiguousarray(cands, CANDIDATE_DTYPE).reshape(-1)
+    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,)) and (cd is None or cd.shape == (n,))
+    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
+    hrec = None if host_records is None else np.ascontiguousarray(host_records, MOTION_REC_DTYPE).reshape(-1).copy()
+    assert (hst is None or len(hst) == len(st)) and (hrec is None or len(hrec) == len(st))
+    pol = np.array([on, gain_pct, coast, max_pct], np.int32)
+    i32 = POINTER(c_int32)
+    vp = lambda a: a.ctypes.data_as(c_void_p) if a is not None else None
+    _check_op(ops_lib().vt_op_motion_prior(
+        device, vp(st), vp(rec), len(st), pol.ctypes.data_as(i32), vp(res), smap.ctypes.data_as(i32) if smap is not None else None,
+        win.ctypes.data_as(i32) if win is not None else None, vp(cd), n, stages, vp(hst), vp(hrec)))
+    return dict(states=st, records=rec, host_states=hst, host_records=hrec)
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)

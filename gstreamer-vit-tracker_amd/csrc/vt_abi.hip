@@ -375,6 +375,7 @@ int vt_group_set_tuning(vt_group* g, const char* key, int value) try {
     HIPCHK(hipStreamSynchronize(e->stream));
     const std::string k = key;
     if (Engine::overlay_key(k)) return e->set_overlay(k, value);    // engine options: the passes are captured again by the first enable only
+    if (Engine::motion_key(k)) return e->set_motion(k, value);
     if (k == "head_band") e->head_band_kernel = value < 0 ? 2 : value;   // 0 / 1 / 2, see Engine::head_band_kernel
     else if (k == "last_rows") e->last_rows = value != 0;        // 0: the last block runs all rows; else (default) the search rows where eligible
     else if (k == "crop_tier") e->crop_tier_forced = value;      // < 0: chosen per pass from the known boxes (default)
@@ -396,6 +397,8 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4) try {
     HIPCHK(hipMemcpy(e->d_states[stream].box, box4, 4 * sizeof(float), hipMemcpyHostToDevice));
     memcpy(e->h_states_all[stream].box, box4, 4 * sizeof(float));
     memcpy(e->known[stream].box, box4, 4 * sizeof(float));
+    if (int rc = e->zero_motion(stream)) return rc;     // the caller placed the box: the jump is no motion
+    HIPCHK(hipStreamSynchronize(e->stream));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -491,6 +494,12 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         if (capacity < 6) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
         if (int rc = e->overlay_stats(stream, out)) return rc;
         return 6;
+    }
+    if (n == "motion") {                // by stream, whatever the last pass was: the engine flag and the stream's record
+        if (!out) return e->motion_capable ? 8 : e->motion_stats(stream, nullptr);
+        if (capacity < 8) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        if (int rc = e->motion_stats(stream, out)) return rc;
+        return 8;
     }
     // every tensor but the stream's state and the replay counters belongs to the last pass: the stream's slot in it
     size_t b = (size_t)stream;

@@ -37,7 +37,7 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay, d_motion};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
@@ -49,11 +49,13 @@ void Engine::destroy() {
     if (h_state) (void)hipHostFree(h_state);
     stage.release();
     if (h_states_all) (void)hipHostFree(h_states_all);
+    if (h_motion_all) (void)hipHostFree(h_motion_all);
     for (HostSlot& sl : hs) {
         sl.arena.release();
         if (sl.h_res) (void)hipHostFree(sl.h_res);
         if (sl.h_st) (void)hipHostFree(sl.h_st);
         if (sl.h_peaks) (void)hipHostFree(sl.h_peaks);
+        if (sl.h_mo) (void)hipHostFree(sl.h_mo);
         if (sl.up_ev) (void)hipEventDestroy(sl.up_ev);
         if (sl.done_ev) (void)hipEventDestroy(sl.done_ev);
         sl = HostSlot();
@@ -337,6 +339,7 @@ int Engine::alloc_buffers() {
     h_initialized.assign(B, 0);
     pass_n = B;                     // no pass yet: reads as a full pass (pass_streams is empty)
     known.assign((size_t)B, StreamState{});
+    known_motion.assign((size_t)B, MotionRec{});
     h_policy.assign((size_t)B, RefreshPolicy{});
     HIPCHK(hipStreamSynchronize(stream));       // every fill has landed before the handle is handed out
     return VT_OK;
@@ -445,6 +448,13 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     };
     GemmArgs qkv = qkv_args(0);             // LayerNorm 1 is folded into the QKV GEMM
 
+    // the motion prior: the listed streams' boxes move ahead before anything reads them (k_motion.hip)
+    MotionArgs ma{};
+    if (motion_capable)
+        ma = MotionArgs{d_states, d_motion_recs(), d_motion_policy(), d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr,
+                        ps.cand ? ps.cand->cands : nullptr, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
+    if (motion_capable)
+        L("motion_place", 0, (double)n * (sizeof(StreamState) + 2.0 * sizeof(MotionRec)), [&] { return launch_motion_place(ma, stream); });
     // K1: crop + resize + normalise the search window of every stream -> patch rows
     if (refresh_capable)    // every pass, from the stream's current buffer of the two-buffer store
         L("gather_template", 0, 4.0 * n * d.nt * d.kpad,
@@ -576,6 +586,9 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     }
     if (ps.cand)
         L("cand_commit", 0, 2.0 * n * sizeof(StreamState), [&] { return launch_cand_commit(*ps.cand, stream); });
+    if (motion_capable)     // ahead of everything that reads the new box: the velocity, the coast or the restore
+        L("motion_settle", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + 3.0 * sizeof(MotionRec)),
+          [&] { return launch_motion_settle(ma, stream); });
     if (refresh_capable) {  // the streams' policies, on what the decode (the commit) left: k_refresh.hip
         const RefreshArgs ra{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_policy,
                              d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
@@ -757,6 +770,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     h_st->frame_w = f->width; h_st->frame_h = f->height;
     h_st->initialized = 1;
     HIPCHK(hipMemcpyAsync(d_states + b, h_st, sizeof(StreamState), hipMemcpyHostToDevice, stream));
+    if (int rc = zero_motion(b)) return rc;
     to_desc(*f, h_desc);
     // entry b of the per-pass block: every pass uploads its own block ahead of its kernels, in stream order
     HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
@@ -823,7 +837,7 @@ int Engine::check_streams(const int32_t* streams, int n) const {
 // full pass: every stream's template rows in its own segment, no slot map. The pass's block (descriptors, PassOut,
 // slot map) goes up from a block of the pinned ring, behind whatever the stream is doing.
 int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                         vt_peaks* host_pk, PassShape* ps) {
+                         vt_peaks* host_pk, PassShape* ps, MotionRec* host_mo) {
     if (int rc = check_streams(streams, n)) return rc;
     if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
     for (int i = 0; i < n; ++i)
@@ -842,7 +856,8 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
         ps->any_layout = std::max(ps->any_layout, pix_level(frames[i].format));
     }
     *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all,
-                                  peaks_capable ? (host_pk ? host_pk : h_peaks) : nullptr};
+                                  peaks_capable ? (host_pk ? host_pk : h_peaks) : nullptr,
+                                  motion_capable ? (host_mo ? host_mo : h_motion_all) : nullptr};
     if (!full) {
         int32_t* map = (int32_t*)((char*)hf + map_offset());
         for (int i = 0; i < n; ++i) map[i] = streams[i];
@@ -868,10 +883,10 @@ int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, 
 // The one entry every pass takes. The full pass replays its captured graph; a subset pass runs eagerly - never a
 // capture inside an update - behind the gather of its template rows.
 int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                    vt_peaks* host_pk) {
+                    vt_peaks* host_pk, MotionRec* host_mo) {
     DEVICE_SCOPE(device);
     PassShape ps;
-    if (int rc = prepare_pass(streams, frames, n, host_res, host_st, host_pk, &ps)) return rc;
+    if (int rc = prepare_pass(streams, frames, n, host_res, host_st, host_pk, &ps, host_mo)) return rc;
     if (!ps.slot_stream && use_graph && !taps) {
         // the captured set of the lowest level that reads every format of the pass
         int level = ps.any_layout;
@@ -898,6 +913,7 @@ int Engine::wait(vt_result* out, int n) {
         for (int b = 0; b < n; ++b) out[b] = h_results[b];
     if (host_seq == host_collected) {               // no pipelined pass owns the stream states
         for (int b = 0; b < B; ++b) known[b] = h_states_all[b];
+        for (int b = 0; b < B && motion_capable; ++b) known_motion[(size_t)b] = h_motion_all[b];
         peaks_n = pass_n;                           // h_peaks holds the records of the pass just waited for
     }
     return VT_OK;
@@ -1282,6 +1298,119 @@ int Engine::overlay_stats(int s, float* out6) {
     return VT_OK;
 }
 
+// ---- motion prior ------------------------------------------------------------------------------------
+
+// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "motion_prior": the policy record, the
+// records and their pinned mirrors are allocated and every graph is captured again with the two launches in it - on the
+// idle stream, never inside an update, as set_overlay does. Every later change is one small copy: the passes read the
+// record. "motion_prior" 0 zeroes every stream's record.
+int Engine::set_motion(const std::string& key, int value) {
+    MotionPolicy p = motion_policy;
+    const MotionPolicy def = VT_MOTION_DEFAULT_POLICY;
+    if (key == "motion_prior") {
+        p.on = value < 0 ? def.on : value;
+        if (p.on > 1) return set_err(VT_ERR_INVALID_ARG, "motion_prior: %d (0: off, 1: on)", value);
+    } else if (key == "motion_gain_pct") {
+        p.gain_pct = value < 0 ? def.gain_pct : value;
+        if (p.gain_pct < 1 || p.gain_pct > 100) return set_err(VT_ERR_INVALID_ARG, "motion_gain_pct: %d (1..100)", value);
+    } else if (key == "motion_coast") {
+        p.coast = value < 0 ? def.coast : value;
+        if (p.coast > 60) return set_err(VT_ERR_INVALID_ARG, "motion_coast: %d (0..60)", value);
+    } else if (key == "motion_max_pct") {
+        p.max_pct = value < 0 ? def.max_pct : value;
+        if (p.max_pct > 200) return set_err(VT_ERR_INVALID_ARG, "motion_max_pct: %d (0..200)", value);
+    } else {
+        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
+    }
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!motion_capable && p.on != 0) {
+        const size_t extra = motion_bytes();
+        if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
+            return set_err(VT_ERR_OOM, "the motion prior needs %.3f MiB more HBM for its records; vt_config.max_device_mib "
+                           "allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
+        uint8_t* store = nullptr;       // the policy | [B] records, all zero
+        MotionRec* hm = nullptr;
+        MotionRec* hsm[2] = {nullptr, nullptr};
+        hipError_t he = dalloc0(&store, extra, stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(stream);
+        if (he == hipSuccess) he = hipHostMalloc((void**)&hm, sizeof(MotionRec) * (size_t)B);
+        for (int i = 0; i < 2 && he == hipSuccess; ++i)      // pipelined slots that exist already; later ones: host_slot_prepare
+            if (hs[i].h_res) he = hipHostMalloc((void**)&hsm[i], sizeof(MotionRec) * (size_t)B);
+        auto undo = [&] {
+            if (store) (void)hipFree(store);
+            if (hm) (void)hipHostFree(hm);
+            for (int i = 0; i < 2; ++i) {
+                if (hsm[i]) (void)hipHostFree(hsm[i]);
+                hs[i].h_mo = nullptr;
+            }
+            d_motion = nullptr; h_motion_all = nullptr;
+            motion_capable = false;
+        };
+        if (he != hipSuccess) {
+            undo();
+            return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "motion prior: %s", hipGetErrorString(he));
+        }
+        memset(hm, 0, sizeof(MotionRec) * (size_t)B);
+        for (int i = 0; i < 2; ++i) {
+            if (hsm[i]) memset(hsm[i], 0, sizeof(MotionRec) * (size_t)B);
+            hs[i].h_mo = hsm[i];
+        }
+        d_motion = store; h_motion_all = hm;
+        known_motion.assign((size_t)B, MotionRec{});
+        motion_capable = true;
+        drop_graphs();
+        if (int rc = capture_all_graphs()) {
+            char keep[512];
+            memcpy(keep, vt_err_text(), sizeof(keep));
+            drop_graphs();
+            undo();
+            (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
+            memcpy(vt_err_text(), keep, sizeof(keep));
+            return rc;
+        }
+    } else if (motion_capable) {
+        HIPCHK(hipMemcpy(d_motion_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
+        if (key == "motion_prior" && p.on == 0) {
+            HIPCHK(hipMemset(d_motion_recs(), 0, sizeof(MotionRec) * (size_t)B));
+            memset(h_motion_all, 0, sizeof(MotionRec) * (size_t)B);
+            known_motion.assign((size_t)B, MotionRec{});
+        }
+    }
+    motion_policy = p;
+    return VT_OK;
+}
+
+int Engine::zero_motion(int b) {
+    if (!motion_capable) return VT_OK;
+    HIPCHK(hipMemsetAsync(d_motion_recs() + b, 0, sizeof(MotionRec), stream));
+    h_motion_all[b] = MotionRec{};
+    known_motion[(size_t)b] = MotionRec{};
+    return VT_OK;
+}
+
+void Engine::predicted_box(int s, float* box4, int steps) const {
+    const StreamState& k = known[(size_t)s];
+    memcpy(box4, k.box, 4 * sizeof(float));
+    for (int i = 0; i < steps && motion_capable; ++i) {
+        float from[4];
+        memcpy(from, box4, sizeof(from));
+        if (!motion_predict(motion_policy.on, from, known_motion[(size_t)s].v, k.frame_w, k.frame_h, box4)) break;
+    }
+}
+
+// [8]: the engine flag, vx, vy, live, the shift of the stream's last pass, passes with a shift, failed updates that advanced
+int Engine::motion_stats(int s, float* out8) {
+    if (!motion_capable)
+        return set_err(VT_ERR_INVALID_ARG, "motion prior: not enabled on this engine (vt_group_set_tuning \"motion_prior\")");
+    MotionRec r{};
+    HIPCHK(hipMemcpy(&r, d_motion_recs() + s, sizeof(r), hipMemcpyDeviceToHost));
+    out8[0] = (float)motion_policy.on; out8[1] = r.v[0]; out8[2] = r.v[1]; out8[3] = (float)r.live;
+    out8[4] = r.shift[0]; out8[5] = r.shift[1]; out8[6] = (float)r.n_shift; out8[7] = (float)r.n_coast;
+    return VT_OK;
+}
+
 // ---- candidate passes --------------------------------------------------------------------------------
 
 int check_state_box(const float* box4) {
@@ -1358,7 +1487,7 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
         map[i] = cands[i].stream;
         hc[i] = cands[i];
     }
-    *(PassOut*)(hf + B) = PassOut{h_results, nullptr, peaks_capable ? h_peaks : nullptr};
+    *(PassOut*)(hf + B) = PassOut{h_results, nullptr, peaks_capable ? h_peaks : nullptr, motion_capable ? h_motion_all : nullptr};
     *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_cands, hc, sizeof(vt_candidate) * (size_t)n, hipMemcpyHostToDevice, stream));

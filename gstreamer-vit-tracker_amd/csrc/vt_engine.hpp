@@ -208,7 +208,8 @@ struct Engine {
     // HBM of the optional features this engine has enabled, beside activation_bytes() under max_device_mib
     size_t feature_bytes() const {
         return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0) +
-               (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0);
+               (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0) +
+               (motion_capable ? motion_bytes() : 0);
     }
     int enable_chips(int size, int kind, const float* na, const float* nb);   // outside any update: the store, graphs recaptured
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
@@ -242,6 +243,29 @@ struct Engine {
     static bool overlay_key(const std::string& key) { return key.rfind("result_overlay", 0) == 0; }
     int set_overlay(const std::string& key, int value);     // the keys of vt_group_set_tuning; the first enable is in here
     int overlay_stats(int stream, float* out6);
+    // motion prior (k_motion.hip). ONE policy per engine, one record per stream. The first non-zero
+    // "motion_prior" allocates the policy record + the [B] records and their pinned mirror and makes the engine
+    // motion-capable for good: every pass starts with the place launch and runs the settle launch directly behind its
+    // decode (its commit). Engines that never enable launch what they always did. A gain, coast or limit set before that
+    // is kept in motion_policy and goes up with the enable.
+    bool motion_capable = false;
+    MotionPolicy motion_policy = VT_MOTION_DEFAULT_POLICY;       // the host's copy
+    uint8_t* d_motion = nullptr;                  // ONE allocation: the policy record, then the [B] MotionRec by stream
+    MotionPolicy* d_motion_policy() const { return reinterpret_cast<MotionPolicy*>(d_motion); }
+    MotionRec* d_motion_recs() const { return reinterpret_cast<MotionRec*>(d_motion + sizeof(MotionPolicy)); }
+    size_t motion_bytes() const { return sizeof(MotionPolicy) + (size_t)B * sizeof(MotionRec); }
+    MotionRec* h_motion_all = nullptr;            // pinned [B] by stream: beside h_states_all, written by the settle launch
+    std::vector<MotionRec> known_motion;          // beside `known`: the records after the last pass the HOST has collected
+    static bool motion_key(const std::string& key) { return key.rfind("motion_", 0) == 0; }
+    int set_motion(const std::string& key, int value);      // the keys of vt_group_set_tuning; the first enable is in here
+    int motion_stats(int stream, float* out8);
+    // stream b's record zeroed on the device (behind the stream's work) and in the host's copies: every call that gives
+    // the stream a new state from outside (init, set_state_box, import)
+    int zero_motion(int b);
+    // the box the next pass of `stream` is cut around, from what the host knows: the place rule on known / known_motion.
+    // steps == 2: the stream is in the pass still running, whose outcome nobody knows - the rule applied twice, once for
+    // that pass's own move and once for the next one's (a target at constant velocity lands there)
+    void predicted_box(int stream, float* box4, int steps = 1) const;
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -317,6 +341,7 @@ struct Engine {
         vt_result* h_res = nullptr;     // the pass's results, by SLOT (list order)
         StreamState* h_st = nullptr;    // [B] by STREAM: valid at the listed streams' indices only
         vt_peaks* h_peaks = nullptr;    // the pass's peak records, by SLOT (peaks-capable engines only)
+        MotionRec* h_mo = nullptr;      // [B] by STREAM, like h_st: the motion records (motion-capable engines only)
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
         std::vector<vt_frame> host;     // the caller's frames, valid until the pass is collected
         std::vector<int32_t> list;      // the pass's streams (the identity list: the full pass)
@@ -387,13 +412,13 @@ struct Engine {
     // list is built for it. VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input (checked in
     // the order list, initialisation, frames). host_res / host_st: pinned buffers the pass's results and states are
     // stored to (null: the engine's own h_results / h_states_all); host_pk: the same for the peak records of a
-    // peaks-capable engine (null: h_peaks).
+    // peaks-capable engine (null: h_peaks), host_mo for the motion records of a motion-capable one (null: h_motion_all).
     int check_streams(const int32_t* streams, int n) const;
     // checks + the pass's block uploaded behind the stream's work + the last-pass record; the engine's device is current
     int prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                     vt_peaks* host_pk, PassShape* ps);
+                     vt_peaks* host_pk, PassShape* ps, MotionRec* host_mo = nullptr);
     int enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
-                StreamState* host_st = nullptr, vt_peaks* host_pk = nullptr);
+                StreamState* host_st = nullptr, vt_peaks* host_pk = nullptr, MotionRec* host_mo = nullptr);
     int wait(vt_result* out, int n);
     // A candidate pass over cands[0..n) (k_cand.hip): checked (list, boxes, initialisation, frames - nothing enqueued
     // on bad input), built and launched eagerly. A list that is a plain subset pass - every stream once, no box - goes

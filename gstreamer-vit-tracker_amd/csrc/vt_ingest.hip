@@ -234,6 +234,10 @@ static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
         HIPCHK(hipHostMalloc((void**)&sl.h_peaks, sizeof(vt_peaks) * e->B));
         memset(sl.h_peaks, 0, sizeof(vt_peaks) * e->B);
     }
+    if (e->motion_capable && !sl.h_mo) {        // the same for the motion records (set_motion covers those that existed)
+        HIPCHK(hipHostMalloc((void**)&sl.h_mo, sizeof(MotionRec) * e->B));
+        memset(sl.h_mo, 0, sizeof(MotionRec) * e->B);
+    }
     if (sl.h_res) return VT_OK;
     // HIP multiplexes a process's streams onto a few hardware queues (four by default): with more
     // streams than that alive - e.g. four engines, each with a compute and a copy stream - an upload
@@ -250,10 +254,13 @@ static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
 }
 
 // the boxes the windows of a pass over streams[0..n) (null: all streams in order) are planned around: the last the
-// host knows
-static std::vector<float> known_boxes(const Engine* e, const int32_t* streams, int n) {
+// host knows - on a motion-capable engine moved as the pass's place launch will move them (Engine::predicted_box: the
+// same binary32 operations on the mirrored record, so an exact window stays exact)
+// spec (per listed stream, may be null): the stream is in the pass still running, so what the host knows is one pass
+// old - its box is moved by the known velocity for that pass as well
+static std::vector<float> known_boxes(const Engine* e, const int32_t* streams, int n, const char* spec = nullptr) {
     std::vector<float> boxes((size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(&boxes[(size_t)i * 4], e->known[streams ? streams[i] : i].box, 4 * sizeof(float));
+    for (int i = 0; i < n; ++i) e->predicted_box(streams ? streams[i] : i, &boxes[(size_t)i * 4], spec && spec[i] ? 2 : 1);
     return boxes;
 }
 
@@ -285,6 +292,7 @@ static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
         const int s = sl.list[i];
         e->known[s] = sl.h_st[s];
         e->h_states_all[s] = sl.h_st[s];        // the engine's own mirrors follow
+        if (e->motion_capable && sl.h_mo) e->known_motion[(size_t)s] = e->h_motion_all[s] = sl.h_mo[s];
         e->h_results[i] = sl.h_res[i];
     }
     adopt_peaks(e, sl);                         // the peak records are by slot, like the results
@@ -298,7 +306,7 @@ static int host_pass_exact_sync(Engine* e, Engine::HostSlot& sl) {
     const std::vector<float> boxes = known_boxes(e, sl.list.data(), n);
     if (int rc = stage_host_frames(e, sl.host.data(), n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
         return rc;
-    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks)) return rc;
+    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks, sl.h_mo)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     adopt_slot(e, sl);
     sl.redone = true;
@@ -326,13 +334,13 @@ static int enqueue_host_pass(Engine* e, const int32_t* streams, const vt_frame* 
     for (int i = 0; i < n; ++i)
         if (outstanding == 1 && older.lists(streams[i])) { spec[(size_t)i] = 1; grow[(size_t)i] = e->margin; }
     std::vector<vt_frame> dev((size_t)n);
-    const std::vector<float> boxes = known_boxes(e, streams, n);
+    const std::vector<float> boxes = known_boxes(e, streams, n, spec.data());
     if (int rc = stage_host_frames_to(e, sl.arena, e->copy_stream, host_frames, n,
                                       reinterpret_cast<const float(*)[4]>(boxes.data()), grow.data(), dev.data(), nullptr))
         return rc;
     HIPCHK(hipEventRecord(sl.up_ev, e->copy_stream));
     HIPCHK(hipStreamWaitEvent(e->stream, sl.up_ev, 0));          // the pass starts behind ITS upload only
-    if (int rc = e->enqueue(streams, dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks)) return rc;   // results land in THIS slot's buffers
+    if (int rc = e->enqueue(streams, dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks, sl.h_mo)) return rc;   // results land in THIS slot's buffers
     HIPCHK(hipEventRecord(sl.done_ev, e->stream));
     sl.host.assign(host_frames, host_frames + n);
     sl.list.assign(streams, streams + n);
@@ -402,8 +410,10 @@ int vt_group_update_host_candidates(vt_group* g, const vt_candidate* cands, cons
     DEVICE_SCOPE(e->device);
     if (int rc = e->wait(nullptr, 0)) return rc;   // last pass done: its boxes are in `known`
     std::vector<float> boxes((size_t)n * 4);
-    for (int i = 0; i < n; ++i)
-        memcpy(&boxes[(size_t)i * 4], cands[i].has_box ? cands[i].box : e->known[(size_t)cands[i].stream].box, 4 * sizeof(float));
+    for (int i = 0; i < n; ++i) {       // a slot without a box is cut around its stream's (predicted) box
+        if (cands[i].has_box) memcpy(&boxes[(size_t)i * 4], cands[i].box, 4 * sizeof(float));
+        else e->predicted_box(cands[i].stream, &boxes[(size_t)i * 4]);
+    }
     std::vector<vt_frame> dev((size_t)n);
     if (int rc = stage_host_frames(e, host_frames, n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data(), true))
         return rc;
@@ -504,8 +514,11 @@ int vt_group_wait_next(vt_group* g, vt_result* out, int n) try {
             if (has_younger)
                 for (int s : younger.list) rewind[(size_t)s] = 1;
             for (int b = 0; b < e->B; ++b)
-                if (rewind[(size_t)b])
+                if (rewind[(size_t)b]) {
                     HIPCHK(hipMemcpy(e->d_states + b, &e->known[(size_t)b], sizeof(StreamState), hipMemcpyHostToDevice));
+                    if (e->motion_capable)      // the records rewind with the states they belong to
+                        HIPCHK(hipMemcpy(e->d_motion_recs() + b, &e->known_motion[(size_t)b], sizeof(MotionRec), hipMemcpyHostToDevice));
+                }
             if (int rc = host_pass_exact_sync(e, sl)) return rc;
             if (has_younger)
                 if (int rc = host_pass_exact_sync(e, younger)) return rc;

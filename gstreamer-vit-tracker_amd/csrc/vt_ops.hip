@@ -878,4 +878,65 @@ int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result*
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The two launches of the motion prior on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_motion_place (stages & 1) and launch_motion_settle (stages & 2), in that order.
+int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams, const int32_t* policy, const vt_result* results,
+                       const int32_t* slot_stream, const int32_t* winner, const vt_candidate* cands, int n, int stages,
+                       void* host_states, void* host_records) try {
+    if (!states || !records || !policy || !results || n < 1 || n > VT_MAX_STREAMS || n_streams < 1 || stages < 1 || stages > 3)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && !cands && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "motion_prior: %d streams for %d slots", n_streams, n);
+    if ((cands != nullptr) != (winner != nullptr))
+        return set_err(VT_ERR_INVALID_ARG, "motion_prior: the candidate form needs both the slots and the winner list");
+    MotionPolicy pol;
+    memcpy(&pol, policy, sizeof(pol));
+    if (pol.on < 0 || pol.on > 1 || pol.gain_pct < 1 || pol.gain_pct > 100 || pol.coast < 0 || pol.coast > 60 || pol.max_pct < 0 ||
+        pol.max_pct > 200)
+        return set_err(VT_ERR_INVALID_ARG, "motion_prior: policy out of range");
+    std::vector<int32_t> map;
+    if (cands || slot_stream) map.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!map.empty()) map[(size_t)i] = cands ? cands[i].stream : slot_stream[i];
+        if (!map.empty() && (map[(size_t)i] < 0 || map[(size_t)i] >= n_streams))
+            return set_err(VT_ERR_INVALID_ARG, "motion_prior: slot %d names stream %d of %d", i, (int)map[(size_t)i], n_streams);
+        if (winner && (winner[i] < 0 || winner[i] >= n))
+            return set_err(VT_ERR_INVALID_ARG, "motion_prior: winner[%d] = %d of %d slots", i, (int)winner[i], n);
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t sb = (size_t)n_streams * sizeof(StreamState), rb = (size_t)n_streams * sizeof(MotionRec);
+    DevBuf dst, drec, dpol, dres, dmap, dwin, dcand, dpo;
+    PinnedBuf hst, hrec;
+    HIPCHK(dst.alloc(sb)); HIPCHK(drec.alloc(rb)); HIPCHK(dpol.alloc(sizeof(pol))); HIPCHK(dres.alloc((size_t)n * sizeof(vt_result)));
+    HIPCHK(dpo.alloc(sizeof(PassOut)));
+    HIPCHK(hipMemcpy(dst.p, states, sb, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(drec.p, records, rb, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dres.p, results, (size_t)n * sizeof(vt_result), hipMemcpyHostToDevice));
+    if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
+    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    const PassOut po{nullptr, (StreamState*)hst.p, nullptr, (MotionRec*)hrec.p};
+    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
+    if (!map.empty()) {
+        HIPCHK(dmap.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(dmap.p, map.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    if (cands) {
+        HIPCHK(dwin.alloc((size_t)n * 4)); HIPCHK(dcand.alloc((size_t)n * sizeof(vt_candidate)));
+        HIPCHK(hipMemcpy(dwin.p, winner, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dcand.p, cands, (size_t)n * sizeof(vt_candidate), hipMemcpyHostToDevice));
+    }
+    const MotionArgs ma{(StreamState*)dst.p, (MotionRec*)drec.p, (const MotionPolicy*)dpol.p, (const vt_result*)dres.p,
+                        map.empty() ? nullptr : (const int32_t*)dmap.p, cands ? (const int32_t*)dwin.p : nullptr,
+                        cands ? (const vt_candidate*)dcand.p : nullptr, (const PassOut*)dpo.p, nullptr, n};
+    if (stages & 1) HIPCHK(launch_motion_place(ma, nullptr));
+    if (stages & 2) HIPCHK(launch_motion_settle(ma, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(states, dst.p, sb, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(records, drec.p, rb, hipMemcpyDeviceToHost));
+    if (host_states) memcpy(host_states, hst.p, sb);
+    if (host_records) memcpy(host_records, hrec.p, rb);
+    return VT_OK;
+} VT_NOTHROW_INT
+
 }  // extern "C"

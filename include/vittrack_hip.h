@@ -830,6 +830,55 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * read the frame concurrently with the pass.
  *   Read-out: vt_group_read_tensor(g, stream, "result_overlay", ...). Not part of a stream snapshot (policy and counters).
  *
+ * ENGINE OPTIONS - the motion prior (DESIGN.md section 3 "Motion prior"). A stream's search window is cut around its last
+ * accepted box (side 4*sqrt(w*h)): a target that moves more than about 1.5 box sides between two updates of its stream - a
+ * fast target, a panning gimbal, a camera served every n-th frame through a subset pass - leaves it, and every later update
+ * fails in the same place (above vt_candidate). With these keys every pass first moves each of its streams' boxes by a
+ * per-stream velocity estimate kept on the device, so the window is cut where the target is heading, and keeps the box
+ * moving through a few failed updates (coasting through a short occlusion). The policy is per engine:
+ *   key                 value                                                                    default (a negative value selects it)
+ *   "motion_prior"      0 = off, 1 = on                                                          0
+ *   "motion_gain_pct"   1..100: weight of the newest displacement in the velocity                 50
+ *   "motion_coast"      0..60: failed updates through which the box keeps advancing               5
+ *   "motion_max_pct"    0..200: per-axis limit of the velocity, percent of sqrt(w*h) of the new box  100
+ * A value outside its range returns VT_ERR_INVALID_ARG and changes nothing. A value set before the engine is motion-capable
+ * is remembered. The first non-zero "motion_prior" makes the engine motion-capable for good (records within max_device_mib,
+ * else VT_ERR_OOM and nothing changes; the captured passes are captured again, here): from then on every pass - full,
+ * subset, candidate, synchronous and pipelined host, vt_group_profile_device - carries two more launches. Engines that
+ * never enable launch exactly what they always did. Later changes of any key are one small copy and capture nothing;
+ * "motion_prior" 0 also zeroes every stream's record, and while it is 0 the two launches leave velocities, live counts
+ * and counters alone.
+ *   THE RULE. All arithmetic is binary32, every operation rounded on its own. Per stream a record (device memory, mirrored
+ * to pinned host memory beside the states; no part of the 88-byte state, of a snapshot or of vt_snapshot_bytes): v[2],
+ * prior[4], shift[2], live, two counters. It is zeroed by vt_group_init_*, vt_group_enqueue_init_host,
+ * vt_group_set_state_box, vt_group_import_stream, vt_import_state, and on the destination of vt_group_copy_stream.
+ *   PLACE - the first launch of a pass, per listed initialised stream with state box b = (x, y, w, h): (1) prior = b,
+ * shift = 0. (2) If the flag is on and v != (0, 0): px = x + vx, py = y + vy, cx = px + 0.5f*w, cy = py + 0.5f*h; if
+ * 0 <= cx < (float)frame_w and 0 <= cy < (float)frame_h (the state's frame size) the state box becomes (px, py, w, h) and
+ * shift = v; otherwise v = 0, live = 0 and the box stays. Crop, decode, candidate fill, refresh, chips, peaks and overlay
+ * read the state as they always did. In a candidate pass a has_box == 0 slot is therefore cut around the predicted box, a
+ * has_box == 1 slot around its own.
+ *   SETTLE - one launch directly behind the decode (candidate pass: behind the commit), ahead of refresh, chips, peaks and
+ * overlay, per stream of the pass with its final result r and state box b' (candidate pass: the winner's; losing slots
+ * leave no trace). Success, and the winning slot was cut around the stream's own box (every pass but a has_box == 1
+ * winner): c_old = (prior.x + 0.5f*prior.w, prior.y + 0.5f*prior.h), c_new the same of b', d = c_new - c_old,
+ * a = (float)gain_pct / 100.0f, v = v + a*(d - v) (a subtract, a multiply, an add per axis),
+ * lim = ((float)max_pct / 100.0f) * sqrtf(b'.w * b'.h), v = fminf(fmaxf(v, -lim), lim), live = coast. Success with a
+ * has_box == 1 winner (the caller placed it: the jump is no motion): v = 0, live = coast. Failure (r.success == 0; a NaN
+ * score fails): if live > 0, live -= 1 and the state box stays the shifted one - the box coasts (counted when
+ * shift != 0); otherwise the state box becomes prior and v = 0. The final box and the record also go to the pinned mirrors.
+ *   CONSEQUENCE: on a motion-enabled engine a failed update may leave the state box advanced by v. frames_done,
+ * success_count and everything else are untouched. THE TWIN IDENTITY: such an engine behaves, bit for bit (results, state
+ * words, templates, chips, peaks), like a plain engine whose host calls vt_group_set_state_box(stream, prior + shift)
+ * before every pass in which shift != 0 and vt_group_set_state_box(stream, prior) after a failure that restores.
+ *   Host passes plan their windows around the predicted box, computed by the host from the mirrored record with the same
+ * operations: an exact window stays exact. A speculative window (vt_group_enqueue_host: the stream is in the pass still
+ * running) is planned around the known box moved by the known velocity - once for the pass still running, once for this one:
+ * where a target at constant velocity will be - then enlarged by the margin; a miss takes the redo path, and the records
+ * rewind and commit with the states they belong to. Pipelined runs stay bit-identical to the
+ * synchronous calls.
+ *   Read-out: vt_group_read_tensor(g, stream, "motion", ...).
+ *
  * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
@@ -878,6 +927,9 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * vt_group_set_tuning): the engine's flags, drawn by the stream's last pass (0 or 1), number of passes drawn, number gated
  * (rule 4), number on a format that is not drawable (rule 5), N of the last label drawn. VT_ERR_INVALID_ARG on an engine
  * that never enabled the overlay.
+ * "motion" [8] (by STREAM, whatever the last pass was; see vt_group_set_tuning "motion_prior"): the engine flag, vx, vy,
+ * live, shift x and shift y of the stream's last pass, number of passes with a non-zero shift, number of failed updates
+ * that advanced the box. VT_ERR_INVALID_ARG on an engine that never enabled the motion prior.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

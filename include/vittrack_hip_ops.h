@@ -125,6 +125,19 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
 int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result* results, const int32_t* slot_stream,
                          const int32_t* winner, int n, const int32_t* policy, int32_t* stats, int n_streams,
                          int device_frames);
+/* The two launches of the motion prior (csrc/k_motion.hip, the "motion_*" keys of vt_group_set_tuning in vittrack_hip.h) on
+ * given operands, and nothing else: stages bit 0 = place, bit 1 = settle, run in that order. states: n_streams records of 88
+ * bytes, records: n_streams records of 48 bytes by stream (float v[2], prior[4], shift[2], int32 live, passes shifted,
+ * failures coasted, reserved) - both in and out; policy: 4 int32 (on 0..1, gain_pct 1..100, coast 0..60, max_pct 0..200);
+ * results [n] by slot (settle reads success); slot_stream (nullable) [n]: slot -> stream < n_streams (NULL: the identity,
+ * n_streams >= n). The candidate form: cands [n] (the map is cands[i].stream, slot_stream is ignored; streams may repeat,
+ * place works once per stream) with winner [n], the commit's winner table - only slots with winner[i] == i settle, with
+ * their own has_box. cands and winner are both NULL or both given. host_states / host_records (nullable, in and out):
+ * [n_streams] the pinned mirrors the settle launch stores the final box and the record to; their initial contents are the
+ * caller's, so untouched words are recognisable. A policy or map out of range, n > 1024: VT_ERR_INVALID_ARG. */
+int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams, const int32_t* policy, const vt_result* results,
+                       const int32_t* slot_stream, const int32_t* winner, const vt_candidate* cands, int n, int stages,
+                       void* host_states, void* host_records);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
