@@ -302,6 +302,38 @@ int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const fl
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The output buffer of an attention hook between two guard bands: the bands carry a byte pattern, the output 0xff (a
+// bf16 NaN), so a row the kernel never stores arrives as NaN instead of whatever a reused allocation held, and a store
+// just outside the buffer (a slip in a row or block index) is reported instead of landing in a neighbour's memory.
+struct GuardedOut {
+    static constexpr size_t kGuard = 4096;      // bytes on each side; keeps out() 4 KiB aligned
+    static constexpr int kPattern = 0xA5;
+    DevBuf buf;
+    size_t bytes = 0;
+    hipError_t alloc(size_t n) {
+        bytes = n;
+        hipError_t e = buf.alloc(n + 2 * kGuard);
+        if (e != hipSuccess) return e;
+        e = hipMemset(buf.p, kPattern, n + 2 * kGuard);
+        if (e != hipSuccess) return e;
+        return hipMemset(out(), 0xff, n);
+    }
+    void* out() const { return static_cast<char*>(buf.p) + kGuard; }
+    // after the synchronise: *where = 0 when both bands are intact, otherwise the signed distance in bytes of the first
+    // changed byte from the output (negative: in front of it, positive: 1 = the first byte behind it)
+    hipError_t check(long* where) const {
+        std::vector<unsigned char> g(2 * kGuard);
+        hipError_t e = hipMemcpy(g.data(), buf.p, kGuard, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        e = hipMemcpy(g.data() + kGuard, static_cast<char*>(buf.p) + kGuard + bytes, kGuard, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        *where = 0;
+        for (size_t i = 0; i < 2 * kGuard && !*where; ++i)
+            if (g[i] != kPattern) *where = i < kGuard ? (long)i - (long)kGuard : (long)(i - kGuard) + 1;
+        return hipSuccess;
+    }
+};
+
 int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, const uint16_t* v, float* out,
                          int B, int N, int H, int mode) try {
     if (!q || !k || !v || !out || B <= 0 || N <= 0 || H <= 0) return set_err(VT_ERR_INVALID_ARG, "bad argument");
@@ -320,14 +352,18 @@ int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, co
         for (int c = 0; c < D; ++c)
             vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
     }
-    DevBuf dqk, dvt, dout;
+    DevBuf dqk, dvt;
+    GuardedOut dout;
     HIPCHK(dqk.alloc(qk.size() * 2)); HIPCHK(dvt.alloc(vt.size() * 2)); HIPCHK(dout.alloc((size_t)M * D * 2));
     HIPCHK(hipMemcpy(dqk.p, qk.data(), qk.size() * 2, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dvt.p, vt.data(), vt.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(launch_attention_mode((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.p, B, N, H, npad, mode, nullptr));
+    HIPCHK(launch_attention_mode((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.out(), B, N, H, npad, mode, nullptr));
     HIPCHK(hipDeviceSynchronize());
+    long where = 0;
+    HIPCHK(dout.check(&where));
+    if (where) return set_err(VT_ERR_HIP, "attention mode %d wrote outside its output: guard byte %ld changed", mode, where);
     std::vector<bf16_t> tmp((size_t)M * D);
-    HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), dout.out(), tmp.size() * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
     return VT_OK;
 } VT_NOTHROW_INT
@@ -350,15 +386,18 @@ int vt_op_attention_queries_bf16(int device_id, const uint16_t* q, const uint16_
             vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
     }
     const size_t MO = (size_t)B * nq * D;
-    DevBuf dqk, dvt, dout;
+    DevBuf dqk, dvt;
+    GuardedOut dout;
     HIPCHK(dqk.alloc(qk.size() * 2)); HIPCHK(dvt.alloc(vt.size() * 2)); HIPCHK(dout.alloc(MO * 2));
     HIPCHK(hipMemcpy(dqk.p, qk.data(), qk.size() * 2, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dvt.p, vt.data(), vt.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dout.p, 0xff, MO * 2));
-    HIPCHK(launch_attention_queries((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.p, B, N, H, npad, q0, nq, nullptr));
+    HIPCHK(launch_attention_queries((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.out(), B, N, H, npad, q0, nq, nullptr));
     HIPCHK(hipDeviceSynchronize());
+    long where = 0;
+    HIPCHK(dout.check(&where));
+    if (where) return set_err(VT_ERR_HIP, "attention on queries %d..%d wrote outside its output: guard byte %ld changed", q0, q0 + nq - 1, where);
     std::vector<bf16_t> tmp(MO);
-    HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), dout.out(), tmp.size() * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
     return VT_OK;
 } VT_NOTHROW_INT

@@ -147,7 +147,9 @@ int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const fl
                    float* qk_out, float* vt_out, int B, int tokens, int D, int cfg, int vt_perm,
                    const float* rowstat_in, const float* colsum);
 /* out[B,N,H*64] (bf16 widened to f32) = softmax(q k^T) v per head; q,k,v: [B,N,H*64] bf16 bits
- * (q already scaled). mode as in vt_op_attention_bench. */
+ * (q already scaled). mode as in vt_op_attention_bench.
+ * This hook and the next one put the device output between two 4 KiB guard bands and fill it with 0xff before the
+ * launch: a row the kernel never stores comes back as NaN, a store into a guard band as VT_ERR_HIP with a message. */
 int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, const uint16_t* v,
                          float* out, int B, int N, int H, int mode);
 /* Attention mode 3 on the queries q0 .. q0 + nq - 1 of every stream only (keys and values: all N tokens):
