@@ -412,7 +412,7 @@ int vt_group_profile_device(vt_group* g, const vt_frame* frames, int n, int iter
     HIPCHK(hipStreamSynchronize(e->stream));
     DeviceFramesScope on_device(e);
     PassShape ps;       // the full pass, built as Engine::enqueue builds it, launched eagerly under the profiler
-    if (int rc = e->prepare_pass(nullptr, frames, n, nullptr, nullptr, nullptr, &ps)) return rc;
+    if (int rc = e->prepare_pass(nullptr, frames, n, nullptr, &ps)) return rc;
     Profiler prof;
     for (int it = 0; it < iters; ++it)
         if (int rc = e->run_pass(&prof, ps)) return rc;

@@ -41,21 +41,16 @@ void Engine::destroy() {
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
-    if (h_peaks) (void)hipHostFree(h_peaks);
     if (h_cands) (void)hipHostFree(h_cands);
     if (h_winner) (void)hipHostFree(h_winner);
     if (h_frames) (void)hipHostFree(h_frames);
-    if (h_results) (void)hipHostFree(h_results);
     if (h_state) (void)hipHostFree(h_state);
     stage.release();
-    if (h_states_all) (void)hipHostFree(h_states_all);
-    if (h_motion_all) (void)hipHostFree(h_motion_all);
+    PassOut own = own_sinks();
+    sinks_free(&own, SINK_ALL);
     for (HostSlot& sl : hs) {
         sl.arena.release();
-        if (sl.h_res) (void)hipHostFree(sl.h_res);
-        if (sl.h_st) (void)hipHostFree(sl.h_st);
-        if (sl.h_peaks) (void)hipHostFree(sl.h_peaks);
-        if (sl.h_mo) (void)hipHostFree(sl.h_mo);
+        sinks_free(&sl.out, SINK_ALL);
         if (sl.up_ev) (void)hipEventDestroy(sl.up_ev);
         if (sl.done_ev) (void)hipEventDestroy(sl.done_ev);
         sl = HostSlot();
@@ -832,61 +827,61 @@ int Engine::check_streams(const int32_t* streams, int n) const {
     return VT_OK;
 }
 
-// The one place a pass is built. A pass over the streams streams[0..n) on n compacted slots: slot i takes frames[i]
-// and works for stream streams[i]; no other stream's state is touched. A null list or the full identity list is the
-// full pass: every stream's template rows in its own segment, no slot map. The pass's block (descriptors, PassOut,
-// slot map) goes up from a block of the pinned ring, behind whatever the stream is doing.
-int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                         vt_peaks* host_pk, PassShape* ps, MotionRec* host_mo) {
+// The one place a pass's block is built (vt_engine.hpp), behind whatever the stream is doing: prepare_pass and
+// enqueue_candidates add only what is theirs.
+int Engine::build_block(const int32_t* map, const vt_frame* frames, int n, const PassOut* sinks, bool by_stream_states,
+                        PassShape* ps) {
+    const int slot = ring_pos;
+    ring_pos = (ring_pos + 1) % RING;
+    HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copies that last used this ring position are done
+    FrameDesc* hf = h_block(slot);
+    *ps = PassShape{n, map ? d_map() : nullptr, 0, 0, nullptr};
+    for (int i = 0; i < n; ++i) {
+        to_desc(frames[i], hf + i);
+        ps->any_layout = std::max(ps->any_layout, pix_level(frames[i].format));
+    }
+    const PassOut own = own_sinks();
+    const PassOut& to = sinks ? *sinks : own;
+    *(PassOut*)(hf + B) = PassOut{to.host_results, by_stream_states ? to.host_states : nullptr,
+                                  peaks_capable ? to.host_peaks : nullptr, motion_capable ? to.host_motion : nullptr};
+    if (map) std::copy(map, map + n, (int32_t*)((char*)hf + map_offset()));
+    *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
+    HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ring_ev[slot], stream));
+    pass_n = n;
+    if (map) pass_streams.assign(map, map + n);
+    else pass_streams.clear();
+    pass_winner.clear();
+    if (taps) taps_filled = true;
+    feat_in_head = head_ln_fused();
+    ps->compact = pass_compact = last_block_compact(n, taps);
+    return VT_OK;
+}
+
+// A pass over the streams streams[0..n) on n compacted slots: slot i takes frames[i] and works for stream streams[i];
+// no other stream's state is touched. A null list or the full identity list is the full pass: every stream's template
+// rows in its own segment, no slot map.
+int Engine::prepare_pass(const int32_t* streams, const vt_frame* frames, int n, const PassOut* sinks, PassShape* ps) {
     if (int rc = check_streams(streams, n)) return rc;
     if (!frames) return set_err(VT_ERR_INVALID_ARG, "null frames");
     for (int i = 0; i < n; ++i)
         if (int rc = check_frame(frames[i])) return rc;
     bool full = n == B;
     for (int i = 0; streams && i < n && full; ++i) full = streams[i] == i;
-    const int slot = ring_pos;
-    ring_pos = (ring_pos + 1) % RING;
-    HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copy that last used this block is done
-    FrameDesc* hf = h_block(slot);
-    *ps = PassShape{n, full ? nullptr : d_map(), 0, 0, nullptr};
-    pass_winner.clear();
+    if (int rc = build_block(full ? nullptr : streams, frames, n, sinks, true, ps)) return rc;
     cand_pending = false;
-    for (int i = 0; i < n; ++i) {
-        to_desc(frames[i], hf + i);
-        ps->any_layout = std::max(ps->any_layout, pix_level(frames[i].format));
-    }
-    *(PassOut*)(hf + B) = PassOut{host_res ? host_res : h_results, host_st ? host_st : h_states_all,
-                                  peaks_capable ? (host_pk ? host_pk : h_peaks) : nullptr,
-                                  motion_capable ? (host_mo ? host_mo : h_motion_all) : nullptr};
-    if (!full) {
-        int32_t* map = (int32_t*)((char*)hf + map_offset());
-        for (int i = 0; i < n; ++i) map[i] = streams[i];
-    }
-    *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
-    HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ring_ev[slot], stream));
-    if (full) {
-        if (int rc = restore_segments()) return rc;
-        pass_streams.clear();
-    } else {
-        segments_moved = true;
-        pass_streams.assign(streams, streams + n);
-    }
-    pass_n = n;
-    if (taps) taps_filled = true;
-    feat_in_head = head_ln_fused();
-    ps->compact = pass_compact = last_block_compact(n, taps);
+    if (!full) segments_moved = true;
+    else if (int rc = restore_segments()) return rc;
     ps->tier = pick_crop_tier(full ? nullptr : streams, n);     // a subset pass: from the boxes of its own streams
     return VT_OK;
 }
 
 // The one entry every pass takes. The full pass replays its captured graph; a subset pass runs eagerly - never a
 // capture inside an update - behind the gather of its template rows.
-int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                    vt_peaks* host_pk, MotionRec* host_mo) {
+int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, const PassOut* sinks) {
     DEVICE_SCOPE(device);
     PassShape ps;
-    if (int rc = prepare_pass(streams, frames, n, host_res, host_st, host_pk, &ps, host_mo)) return rc;
+    if (int rc = prepare_pass(streams, frames, n, sinks, &ps)) return rc;
     if (!ps.slot_stream && use_graph && !taps) {
         // the captured set of the lowest level that reads every format of the pass
         int level = ps.any_layout;
@@ -919,6 +914,65 @@ int Engine::wait(vt_result* out, int n) {
     return VT_OK;
 }
 
+// ---- the first enable of an optional feature -------------------------------------------------------------
+
+// The one transaction (vt_engine.hpp: Feature). The captured passes are those of an engine without the feature: they
+// are dropped and captured again, as vt_group_set_tuning does.
+int Engine::enable_feature(const Feature& f) {
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    const double mib = f.extra / 1048576.0;
+    if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + f.extra > max_device_bytes)
+        return set_err(VT_ERR_OOM, "%s: needs %.3f MiB more HBM; vt_config.max_device_mib allows %.1f in all", f.name, mib,
+                       max_device_bytes / 1048576.0);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && f.extra > free_b)
+        return set_err(VT_ERR_OOM, "%s: needs %.3f MiB more HBM; %.1f MiB are free", f.name, mib, free_b / 1048576.0);
+    hipError_t he = f.alloc();
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);    // the fills and copies have landed
+    if (he != hipSuccess) {
+        f.uninstall();
+        return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "%s: %s", f.name, hipGetErrorString(he));
+    }
+    f.install();
+    drop_graphs();
+    if (int rc = capture_all_graphs()) {
+        char keep[512];
+        memcpy(keep, vt_err_text(), sizeof(keep));
+        drop_graphs();
+        f.uninstall();
+        (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
+        memcpy(vt_err_text(), keep, sizeof(keep));
+        return rc;
+    }
+    if (f.commit) f.commit();
+    return VT_OK;
+}
+
+template <typename T>
+static hipError_t pinned0(T** p, size_t count) {
+    if (*p) return hipSuccess;
+    hipError_t e = hipHostMalloc((void**)p, count * sizeof(T));
+    if (e == hipSuccess) memset(*p, 0, count * sizeof(T));
+    return e;
+}
+
+hipError_t Engine::sinks_alloc(PassOut* o, unsigned members) const {
+    hipError_t e = hipSuccess;
+    if (members & SINK_BASE) e = pinned0(&o->host_results, (size_t)B);
+    if (e == hipSuccess && (members & SINK_BASE)) e = pinned0(&o->host_states, (size_t)B);
+    if (e == hipSuccess && (members & SINK_PEAKS)) e = pinned0(&o->host_peaks, (size_t)B);
+    if (e == hipSuccess && (members & SINK_MOTION)) e = pinned0(&o->host_motion, (size_t)B);
+    return e;
+}
+
+void Engine::sinks_free(PassOut* o, unsigned members) const {
+    auto drop = [](auto** p) { if (*p) (void)hipHostFree(*p); *p = nullptr; };
+    if (members & SINK_BASE) { drop(&o->host_results); drop(&o->host_states); }
+    if (members & SINK_PEAKS) drop(&o->host_peaks);
+    if (members & SINK_MOTION) drop(&o->host_motion);
+}
+
 // ---- template refresh --------------------------------------------------------------------------------
 
 int Engine::reset_refresh_tickets() {
@@ -926,68 +980,45 @@ int Engine::reset_refresh_tickets() {
     return VT_OK;
 }
 
-// The first enabled policy: the store grows to two buffers per stream (buffer tpl_gen & 1 = the stream's rows), policy array
-// and tickets are allocated, and every graph is captured again with the gather and the refresh launch in it - here,
-// on the idle stream, never inside an update. Nothing changes on failure.
+// The first enabled policy: the store grows to two buffers per stream (buffer tpl_gen & 1 = the stream's rows), policy
+// array and tickets are allocated. The old store is kept until the new passes exist: a failed capture puts it back.
 int Engine::enable_refresh() {
     if (refresh_capable) return VT_OK;
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    const size_t extra = refresh_bytes(), rows = (size_t)d.nt * d.kpad;
-    if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
-        return set_err(VT_ERR_OOM, "template refresh needs %.2f MiB more HBM for the second template buffers; "
-                       "vt_config.max_device_mib allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && extra > free_b)
-        return set_err(VT_ERR_OOM, "template refresh needs %.2f MiB more HBM; %.1f MiB are free", extra / 1048576.0,
-                       free_b / 1048576.0);
-    std::vector<StreamState> sts((size_t)B);     // before the device allocations: may throw
-    bf16_t* tpl2 = nullptr;
+    const size_t rows = (size_t)d.nt * d.kpad;
+    bf16_t *tpl2 = nullptr, *const tpl1 = d_tpl;
     RefreshPolicy* pol = nullptr;
     unsigned* tick = nullptr;
-    hipError_t he = dalloc0(&tpl2, 2 * rows * (size_t)B, stream);
-    if (he == hipSuccess) he = dalloc0(&pol, (size_t)B, stream);
-    if (he == hipSuccess) he = dalloc0(&tick, (size_t)B, stream);
-    if (he == hipSuccess)
-        he = hipMemcpy2DAsync(tpl2, 2 * rows * sizeof(bf16_t), d_tpl, rows * sizeof(bf16_t), rows * sizeof(bf16_t),
-                              (size_t)B, hipMemcpyDeviceToDevice, stream);
-    // a stream that was imported (vt_snapshot.hip) may carry an odd tpl_gen in this single-buffer engine: its current rows
-    // belong into buffer tpl_gen & 1 of the new store, where every reader will look for them (buffer 0 keeps a copy)
-    if (he == hipSuccess) he = hipMemcpyAsync(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    for (int b = 0; b < B && he == hipSuccess; ++b)
-        if (sts[(size_t)b].tpl_gen & 1)
-            he = hipMemcpyAsync(tpl2 + ((size_t)b * 2 + 1) * rows, d_tpl + (size_t)b * rows, rows * sizeof(bf16_t),
-                                hipMemcpyDeviceToDevice, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    if (he != hipSuccess) {
-        if (tpl2) (void)hipFree(tpl2);
-        if (pol) (void)hipFree(pol);
-        if (tick) (void)hipFree(tick);
-        return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "template refresh: %s", hipGetErrorString(he));
-    }
-    // the captured passes are those of an engine without refresh: drop them and capture again, as vt_group_set_tuning
-    // does. The old store is kept until the new passes exist: a failed capture puts everything back.
-    bf16_t* const tpl1 = d_tpl;
     const bool moved = segments_moved;
-    d_tpl = tpl2; d_policy = pol; d_tickets = tick;
-    refresh_capable = true;
-    segments_moved = false;
-    drop_graphs();
-    if (int rc = capture_all_graphs()) {
-        char keep[512];
-        memcpy(keep, g_err, sizeof(keep));
-        drop_graphs();
+    auto alloc = [&] {
+        std::vector<StreamState> sts((size_t)B);     // before the device allocations: may throw
+        hipError_t he = dalloc0(&tpl2, 2 * rows * (size_t)B, stream);
+        if (he == hipSuccess) he = dalloc0(&pol, (size_t)B, stream);
+        if (he == hipSuccess) he = dalloc0(&tick, (size_t)B, stream);
+        if (he == hipSuccess)
+            he = hipMemcpy2DAsync(tpl2, 2 * rows * sizeof(bf16_t), tpl1, rows * sizeof(bf16_t), rows * sizeof(bf16_t),
+                                  (size_t)B, hipMemcpyDeviceToDevice, stream);
+        // a stream that was imported (vt_snapshot.hip) may carry an odd tpl_gen in this single-buffer engine: its current rows
+        // belong into buffer tpl_gen & 1 of the new store, where every reader will look for them (buffer 0 keeps a copy)
+        if (he == hipSuccess) he = hipMemcpyAsync(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost, stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(stream);
+        for (int b = 0; b < B && he == hipSuccess; ++b)
+            if (sts[(size_t)b].tpl_gen & 1)
+                he = hipMemcpyAsync(tpl2 + ((size_t)b * 2 + 1) * rows, tpl1 + (size_t)b * rows, rows * sizeof(bf16_t),
+                                    hipMemcpyDeviceToDevice, stream);
+        return he;
+    };
+    auto install = [&] {
+        d_tpl = tpl2; d_policy = pol; d_tickets = tick;
+        refresh_capable = true;
+        segments_moved = false;
+    };
+    auto uninstall = [&] {
         d_tpl = tpl1; d_policy = nullptr; d_tickets = nullptr;
         refresh_capable = false;
         segments_moved = moved;
-        (void)hipFree(tpl2); (void)hipFree(pol); (void)hipFree(tick);
-        (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
-        memcpy(g_err, keep, sizeof(keep));
-        return rc;
-    }
-    (void)hipFree(tpl1);
-    return VT_OK;
+        (void)hipFree(tpl2); (void)hipFree(pol); (void)hipFree(tick);     // null: no operation
+    };
+    return enable_feature({"template refresh", refresh_bytes(), alloc, install, uninstall, [&] { (void)hipFree(tpl1); }});
 }
 
 int Engine::set_refresh(int s, int period, float min_score) {
@@ -1035,8 +1066,7 @@ int Engine::refresh_stats(int s, vt_refresh_stats* out) {
 
 // ---- target chips ------------------------------------------------------------------------------------
 
-// The first enable: the store is allocated and every graph is captured again with the chip launch in it - on the idle
-// stream, never inside an update. A second enable with the same parameters is a no-op. Nothing changes on failure.
+// The first enable allocates the store (enable_feature). A second enable with the same parameters is a no-op.
 int Engine::enable_chips(int size, int kind, const float* na, const float* nb) {
     if (size < 32 || size > 512 || size % 8 != 0)
         return set_err(VT_ERR_INVALID_ARG, "chips: size %d (a multiple of 8 in 32..512)", size);
@@ -1055,47 +1085,26 @@ int Engine::enable_chips(int size, int kind, const float* na, const float* nb) {
                            "first enable", chip_size, chip_kind);
         return VT_OK;
     }
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    const size_t extra = chip_store_bytes_of(B, size, kind), cb = chip_bytes_of(size, kind);
-    if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
-        return set_err(VT_ERR_OOM, "chips need %.2f MiB more HBM for the chip store; vt_config.max_device_mib allows %.1f "
-                       "in all", extra / 1048576.0, max_device_bytes / 1048576.0);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && extra > free_b)
-        return set_err(VT_ERR_OOM, "chips need %.2f MiB more HBM; %.1f MiB are free", extra / 1048576.0, free_b / 1048576.0);
+    const size_t cb = chip_bytes_of(size, kind);
     uint8_t* chips = nullptr;       // one allocation: [B][cb] chips | [B] infos (cb is a multiple of 192: the infos are aligned)
     ChipPolicy* pol = nullptr;
-    hipError_t he = dalloc0(&chips, (cb + sizeof(vt_chip_info)) * (size_t)B, stream);
-    if (he == hipSuccess) he = dalloc0(&pol, (size_t)B, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    auto undo = [&] {
-        if (chips) (void)hipFree(chips);
-        if (pol) (void)hipFree(pol);
+    auto alloc = [&] {
+        hipError_t he = dalloc0(&chips, (cb + sizeof(vt_chip_info)) * (size_t)B, stream);
+        return he == hipSuccess ? dalloc0(&pol, (size_t)B, stream) : he;
+    };
+    auto install = [&] {
+        d_chips = chips; d_chip_infos = reinterpret_cast<vt_chip_info*>(chips + cb * (size_t)B); d_chip_policy = pol;
+        chip_size = size; chip_kind = kind;
+        memcpy(chip_na, a3, sizeof(a3)); memcpy(chip_nb, b3, sizeof(b3));
+        chip_capable = true;
+    };
+    auto uninstall = [&] {
+        (void)hipFree(chips); (void)hipFree(pol);       // null: no operation
         d_chips = nullptr; d_chip_infos = nullptr; d_chip_policy = nullptr;
         chip_capable = false;
         chip_size = chip_kind = 0;
     };
-    if (he != hipSuccess) {
-        undo();
-        return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "chips: %s", hipGetErrorString(he));
-    }
-    // the captured passes are those of an engine without chips: drop them and capture again, as enable_refresh does
-    d_chips = chips; d_chip_infos = reinterpret_cast<vt_chip_info*>(chips + cb * (size_t)B); d_chip_policy = pol;
-    chip_size = size; chip_kind = kind;
-    memcpy(chip_na, a3, sizeof(a3)); memcpy(chip_nb, b3, sizeof(b3));
-    chip_capable = true;
-    drop_graphs();
-    if (int rc = capture_all_graphs()) {
-        char keep[512];
-        memcpy(keep, vt_err_text(), sizeof(keep));
-        drop_graphs();
-        undo();
-        (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
-        memcpy(vt_err_text(), keep, sizeof(keep));
-        return rc;
-    }
-    return VT_OK;
+    return enable_feature({"chips", chip_store_bytes_of(B, size, kind), alloc, install, uninstall});
 }
 
 int Engine::set_chips(int s, float factor, int period, int phase) {
@@ -1143,9 +1152,8 @@ int Engine::read_chips(const int* streams, int n, void* out, size_t out_stride, 
 
 // ---- response peaks ----------------------------------------------------------------------------------
 
-// The policy of stream s (-1: all). The first policy with max_peaks > 0: the records and policies are allocated, the pinned
-// mirrors too, and every graph is captured again with the peaks launch in it - on the idle stream, never inside an
-// update, as enable_chips does. Nothing changes on failure.
+// The policy of stream s (-1: all). The first policy with max_peaks > 0 allocates the records, the policies and the
+// pinned mirrors (enable_feature).
 int Engine::set_peaks(int s, int max_peaks, int radius, float min_resp) {
     if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "peaks: stream %d out of range (-1..%d)", s, B - 1);
     if (max_peaks < 0 || max_peaks > VT_PEAKS_MAX)
@@ -1158,54 +1166,32 @@ int Engine::set_peaks(int s, int max_peaks, int radius, float min_resp) {
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     if (!peaks_capable) {
-        const size_t extra = peaks_bytes();
-        if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
-            return set_err(VT_ERR_OOM, "peaks need %.3f MiB more HBM for the records; vt_config.max_device_mib allows %.1f "
-                           "in all", extra / 1048576.0, max_device_bytes / 1048576.0);
         uint8_t* store = nullptr;       // one allocation: [B] records | [B] policies, all zero (every policy off)
-        vt_peaks* hp = nullptr;
-        vt_peaks* hsp[2] = {nullptr, nullptr};
-        hipError_t he = dalloc0(&store, extra, stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(stream);
-        if (he == hipSuccess) he = hipHostMalloc((void**)&hp, sizeof(vt_peaks) * (size_t)B);
-        for (int i = 0; i < 2 && he == hipSuccess; ++i)      // pipelined slots that exist already; later ones: host_slot_prepare
-            if (hs[i].h_res) he = hipHostMalloc((void**)&hsp[i], sizeof(vt_peaks) * (size_t)B);
-        auto undo = [&] {
-            if (store) (void)hipFree(store);
-            if (hp) (void)hipHostFree(hp);
-            for (int i = 0; i < 2; ++i) {
-                if (hsp[i]) (void)hipHostFree(hsp[i]);
-                hs[i].h_peaks = nullptr;
-            }
+        PassOut own{};                  // the engine's own mirror
+        auto alloc = [&] {
+            peaks_policy.assign((size_t)B, PeaksPolicy{0, 0, 0.0f, 0});     // before the device allocation: may throw
+            hipError_t he = dalloc0(&store, peaks_bytes(), stream);
+            if (he == hipSuccess) he = sinks_alloc(&own, SINK_PEAKS);
+            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
+                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_PEAKS);
+            return he;
+        };
+        auto install = [&] {
+            d_peaks = reinterpret_cast<vt_peaks*>(store);
+            d_peaks_policy = reinterpret_cast<PeaksPolicy*>(store + sizeof(vt_peaks) * (size_t)B);
+            h_peaks = own.host_peaks;
+            peaks_n = 0;
+            peaks_capable = true;
+        };
+        auto uninstall = [&] {
+            (void)hipFree(store);       // null: no operation
+            sinks_free(&own, SINK_PEAKS);
+            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_PEAKS);
             d_peaks = nullptr; d_peaks_policy = nullptr; h_peaks = nullptr;
             peaks_policy.clear();
             peaks_capable = false;
         };
-        if (he != hipSuccess) {
-            undo();
-            return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "peaks: %s", hipGetErrorString(he));
-        }
-        memset(hp, 0, sizeof(vt_peaks) * (size_t)B);
-        for (int i = 0; i < 2; ++i) {
-            if (hsp[i]) memset(hsp[i], 0, sizeof(vt_peaks) * (size_t)B);
-            hs[i].h_peaks = hsp[i];
-        }
-        d_peaks = reinterpret_cast<vt_peaks*>(store);
-        d_peaks_policy = reinterpret_cast<PeaksPolicy*>(store + sizeof(vt_peaks) * (size_t)B);
-        h_peaks = hp;
-        peaks_policy.assign((size_t)B, PeaksPolicy{0, 0, 0.0f, 0});
-        peaks_n = 0;
-        peaks_capable = true;
-        drop_graphs();
-        if (int rc = capture_all_graphs()) {
-            char keep[512];
-            memcpy(keep, vt_err_text(), sizeof(keep));
-            drop_graphs();
-            undo();
-            (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
-            memcpy(vt_err_text(), keep, sizeof(keep));
-            return rc;
-        }
+        if (int rc = enable_feature({"peaks", peaks_bytes(), alloc, install, uninstall})) return rc;
     }
     const PeaksPolicy p{max_peaks, radius, min_resp == 0.0f ? 0.0f : min_resp, 0};
     for (int b = s < 0 ? 0 : s; b < (s < 0 ? B : s + 1); ++b) {
@@ -1224,9 +1210,8 @@ int Engine::last_peaks(vt_peaks* out, int n) const {
 
 // ---- result overlay ----------------------------------------------------------------------------------
 
-// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero flags: the policy record and the
-// counters are allocated and every graph is captured again with the overlay launch at its end - on the idle stream,
-// never inside an update, as set_peaks does. Every later change is one small copy: the passes read the record.
+// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero flags allocate the policy record and
+// the counters (enable_feature). Every later change is one small copy: the passes read the record.
 int Engine::set_overlay(const std::string& key, int value) {
     OverlayPolicy p = overlay_policy;
     const OverlayPolicy def = VT_OVERLAY_DEFAULT_POLICY;
@@ -1254,32 +1239,18 @@ int Engine::set_overlay(const std::string& key, int value) {
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     if (!overlay_capable && p.flags != 0) {
-        const size_t extra = overlay_bytes();
-        if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
-            return set_err(VT_ERR_OOM, "the result overlay needs %.3f MiB more HBM for its records; vt_config.max_device_mib "
-                           "allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
         uint8_t* store = nullptr;       // the policy | [B] counters, all zero
-        hipError_t he = dalloc0(&store, extra, stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(stream);
-        if (he != hipSuccess) {
-            if (store) (void)hipFree(store);
-            return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "result overlay: %s", hipGetErrorString(he));
-        }
-        d_overlay = store;
-        overlay_capable = true;
-        drop_graphs();
-        if (int rc = capture_all_graphs()) {
-            char keep[512];
-            memcpy(keep, vt_err_text(), sizeof(keep));
-            drop_graphs();
-            (void)hipFree(store);
+        auto alloc = [&] {
+            hipError_t he = dalloc0(&store, overlay_bytes(), stream);
+            return he == hipSuccess ? hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream) : he;
+        };
+        auto install = [&] { d_overlay = store; overlay_capable = true; };
+        auto uninstall = [&] {
+            (void)hipFree(store);       // null: no operation
             d_overlay = nullptr;
             overlay_capable = false;
-            (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
-            memcpy(vt_err_text(), keep, sizeof(keep));
-            return rc;
-        }
+        };
+        if (int rc = enable_feature({"result overlay", overlay_bytes(), alloc, install, uninstall})) return rc;
     } else if (overlay_capable) {
         HIPCHK(hipMemcpy(d_overlay_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
     }
@@ -1300,10 +1271,9 @@ int Engine::overlay_stats(int s, float* out6) {
 
 // ---- motion prior ------------------------------------------------------------------------------------
 
-// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "motion_prior": the policy record, the
-// records and their pinned mirrors are allocated and every graph is captured again with the two launches in it - on the
-// idle stream, never inside an update, as set_overlay does. Every later change is one small copy: the passes read the
-// record. "motion_prior" 0 zeroes every stream's record.
+// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "motion_prior" allocates the policy
+// record, the records and their pinned mirrors (enable_feature). Every later change is one small copy: the passes read
+// the record. "motion_prior" 0 zeroes every stream's record.
 int Engine::set_motion(const std::string& key, int value) {
     MotionPolicy p = motion_policy;
     const MotionPolicy def = VT_MOTION_DEFAULT_POLICY;
@@ -1325,51 +1295,29 @@ int Engine::set_motion(const std::string& key, int value) {
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     if (!motion_capable && p.on != 0) {
-        const size_t extra = motion_bytes();
-        if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + extra > max_device_bytes)
-            return set_err(VT_ERR_OOM, "the motion prior needs %.3f MiB more HBM for its records; vt_config.max_device_mib "
-                           "allows %.1f in all", extra / 1048576.0, max_device_bytes / 1048576.0);
         uint8_t* store = nullptr;       // the policy | [B] records, all zero
-        MotionRec* hm = nullptr;
-        MotionRec* hsm[2] = {nullptr, nullptr};
-        hipError_t he = dalloc0(&store, extra, stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(stream);
-        if (he == hipSuccess) he = hipHostMalloc((void**)&hm, sizeof(MotionRec) * (size_t)B);
-        for (int i = 0; i < 2 && he == hipSuccess; ++i)      // pipelined slots that exist already; later ones: host_slot_prepare
-            if (hs[i].h_res) he = hipHostMalloc((void**)&hsm[i], sizeof(MotionRec) * (size_t)B);
-        auto undo = [&] {
-            if (store) (void)hipFree(store);
-            if (hm) (void)hipHostFree(hm);
-            for (int i = 0; i < 2; ++i) {
-                if (hsm[i]) (void)hipHostFree(hsm[i]);
-                hs[i].h_mo = nullptr;
-            }
+        PassOut own{};                  // the engine's own mirror
+        auto alloc = [&] {
+            hipError_t he = dalloc0(&store, motion_bytes(), stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
+            if (he == hipSuccess) he = sinks_alloc(&own, SINK_MOTION);
+            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
+                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_MOTION);
+            return he;
+        };
+        auto install = [&] {
+            d_motion = store; h_motion_all = own.host_motion;
+            known_motion.assign((size_t)B, MotionRec{});    // B entries since alloc_buffers: no allocation
+            motion_capable = true;
+        };
+        auto uninstall = [&] {
+            (void)hipFree(store);       // null: no operation
+            sinks_free(&own, SINK_MOTION);
+            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_MOTION);
             d_motion = nullptr; h_motion_all = nullptr;
             motion_capable = false;
         };
-        if (he != hipSuccess) {
-            undo();
-            return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "motion prior: %s", hipGetErrorString(he));
-        }
-        memset(hm, 0, sizeof(MotionRec) * (size_t)B);
-        for (int i = 0; i < 2; ++i) {
-            if (hsm[i]) memset(hsm[i], 0, sizeof(MotionRec) * (size_t)B);
-            hs[i].h_mo = hsm[i];
-        }
-        d_motion = store; h_motion_all = hm;
-        known_motion.assign((size_t)B, MotionRec{});
-        motion_capable = true;
-        drop_graphs();
-        if (int rc = capture_all_graphs()) {
-            char keep[512];
-            memcpy(keep, vt_err_text(), sizeof(keep));
-            drop_graphs();
-            undo();
-            (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
-            memcpy(vt_err_text(), keep, sizeof(keep));
-            return rc;
-        }
+        if (int rc = enable_feature({"motion prior", motion_bytes(), alloc, install, uninstall})) return rc;
     } else if (motion_capable) {
         HIPCHK(hipMemcpy(d_motion_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
         if (key == "motion_prior" && p.on == 0) {
@@ -1471,35 +1419,19 @@ int Engine::enqueue_candidates(const vt_candidate* cands, const vt_frame* frames
     for (int i = 0; i < n; ++i) streams[(size_t)i] = cands[i].stream;
     DEVICE_SCOPE(device);
     if (int rc = ensure_candidate_buffers()) return rc;
-    const int slot = ring_pos;
-    ring_pos = (ring_pos + 1) % RING;
-    HIPCHK(hipEventSynchronize(ring_ev[slot]));  // the copies that last used these blocks are done
-    FrameDesc* hf = h_block(slot);
-    vt_candidate* hc = h_cands + (size_t)slot * B;
     // the template gather keeps the slot -> stream map; the decode stores results by slot and NO state to the host:
     // only the commit kernel writes by-stream copies
-    const CandArgs ca{d_cands, d_states, d_cand_states, d_results, d_winner, h_states_all, h_winner, n};
-    PassShape ps{n, d_map(), 0, 0, &ca};
-    int32_t* map = (int32_t*)((char*)hf + map_offset());
-    for (int i = 0; i < n; ++i) {
-        to_desc(frames[i], hf + i);
-        ps.any_layout = std::max(ps.any_layout, pix_level(frames[i].format));
-        map[i] = cands[i].stream;
-        hc[i] = cands[i];
-    }
-    *(PassOut*)(hf + B) = PassOut{h_results, nullptr, peaks_capable ? h_peaks : nullptr, motion_capable ? h_motion_all : nullptr};
-    *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
-    HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
+    const int slot = ring_pos;      // the ring position build_block takes and waits for: the list's copy shares it
+    PassShape ps;
+    if (int rc = build_block(streams.data(), frames, n, nullptr, false, &ps)) return rc;
+    vt_candidate* hc = h_cands + (size_t)slot * B;
+    std::copy(cands, cands + n, hc);
     HIPCHK(hipMemcpyAsync(d_cands, hc, sizeof(vt_candidate) * (size_t)n, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ring_ev[slot], stream));
+    HIPCHK(hipEventRecord(ring_ev[slot], stream));      // the position's event again: now behind the list's copy too
+    const CandArgs ca{d_cands, d_states, d_cand_states, d_results, d_winner, h_states_all, h_winner, n};
+    ps.cand = &ca;
     segments_moved = true;          // the next full pass restores every stream's template rows
-    pass_streams = streams;
-    pass_winner.clear();
     cand_pending = true;
-    pass_n = n;
-    if (taps) taps_filled = true;
-    feat_in_head = head_ln_fused();
-    ps.compact = pass_compact = last_block_compact(n, taps);
     ps.tier = pick_crop_tier(cands, n);
     return run_pass(nullptr, ps);
 }

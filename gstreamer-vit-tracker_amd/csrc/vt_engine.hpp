@@ -1,7 +1,9 @@
 // vt_engine.hpp — what the host-side translation units of libvittrack_hip.so share: error plumbing, the device
 // scope, the Engine (one GPU's batch of tracked streams) and the handles of the C ABI.
-//   vt_engine.hip   the Engine: weight blob, buffers, the per-frame launch plan (run_pass), graphs, and the one way a
-//                   pass is built and submitted (prepare_pass / enqueue), wait
+//   vt_engine.hip   the Engine: weight blob, buffers, the per-frame launch plan (run_pass), graphs, the one way a pass is
+//                   submitted (prepare_pass / enqueue; enqueue_candidates for a candidate pass - both put their block
+//                   together in build_block), wait, and the one transaction behind the first enable of every optional
+//                   in-the-pass feature (enable_feature)
 //   vt_abi.hip      the extern "C" boundary of include/vittrack_hip.h (create / init / update, device-frame passes of a
 //                   group, diagnostics, colour converter, overlays, dma-buf and host-mapping ingest)
 //   vt_ingest.hip   host-frame ingest: the staging arena, window planning and packing, the host-frame passes of a group
@@ -16,6 +18,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <atomic>
@@ -175,10 +178,24 @@ struct Engine {
     // slots' segments of d_patches, and the next full pass puts every segment back from here
     bf16_t* d_tpl = nullptr;
     bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
-    // template refresh (k_refresh.hip). The first policy that is enabled makes the engine
-    // refresh-capable for good: d_tpl becomes [B][2][nt][kpad] (a stream's rows: buffer tpl_gen & 1 of its state), every
-    // pass - full ones too - gathers its template rows from there and runs the refresh launch behind its decode.
-    // restore_segments / segments_moved are for engines that never enabled; those launch what they always did.
+    // The first enable of an optional in-the-pass feature, for all five below: on the idle stream,
+    // never inside an update - `extra` bytes checked against max_device_mib (beside activation_bytes() and
+    // feature_bytes()) and against free memory (VT_ERR_OOM), alloc(), install() (pointers, *_capable = true), every
+    // graph dropped and captured again with the feature's launches in it, commit() if there is one. Should alloc() or
+    // the capture fail, uninstall() frees and resets whatever alloc() and install() left - it runs after a partial
+    // alloc() too -, the passes the engine had are captured again and the first error is the one reported: nothing
+    // changes on failure. An engine is capable for good; engines that never enable launch what they always did.
+    struct Feature {
+        const char* name;                       // for the messages
+        size_t extra;
+        std::function<hipError_t()> alloc;
+        std::function<void()> install, uninstall, commit;
+    };
+    int enable_feature(const Feature& f);
+    // template refresh (k_refresh.hip). The first policy that is enabled makes the engine refresh-capable: d_tpl becomes
+    // [B][2][nt][kpad] (a stream's rows: buffer tpl_gen & 1 of its state), every pass - full ones too - gathers its
+    // template rows from there and runs the refresh launch behind its decode. restore_segments / segments_moved are
+    // for engines that never enabled.
     bool refresh_capable = false;
     RefreshPolicy* d_policy = nullptr;            // [B] (capable engines)
     std::vector<RefreshPolicy> h_policy;          // what the host set: period, min_score
@@ -186,13 +203,12 @@ struct Engine {
     int tpl_bufs() const { return refresh_capable ? 2 : 1; }
     bf16_t* tpl_init_rows(int b) const { return d_tpl + (size_t)b * tpl_bufs() * d.nt * d.kpad; }   // buffer 0: init's
     size_t refresh_bytes() const { return (size_t)B * (sizeof(bf16_t) * d.nt * d.kpad + sizeof(RefreshPolicy) + sizeof(unsigned)); }
-    int enable_refresh();                         // outside any update: second buffer, policy, tickets, graphs recaptured
+    int enable_refresh();                         // enable_feature: second buffer, policy, tickets
     int set_refresh(int stream, int period, float min_score);     // stream -1: all
     int refresh_stats(int stream, vt_refresh_stats* out);
     int reset_refresh_tickets();                  // wherever a pass may have been abandoned half-way
-    // target chips (k_chip.hip). The first enable fixes the chip side and kind, allocates the store
-    // [B][chip_bytes] + [B] infos + [B] policies and makes the engine chip-capable for good: every pass runs the chip launch
-    // behind its decode (and behind the refresh launch). Engines that never enable launch what they always did.
+    // target chips (k_chip.hip). The first enable fixes the chip side and kind and allocates the store [B][chip_bytes] +
+    // [B] infos + [B] policies: every pass runs the chip launch behind its decode (and behind the refresh launch).
     bool chip_capable = false;
     int chip_size = 0, chip_kind = 0;
     float chip_na[3] = {1.0f, 1.0f, 1.0f}, chip_nb[3] = {0.0f, 0.0f, 0.0f};
@@ -211,12 +227,12 @@ struct Engine {
                (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0) +
                (motion_capable ? motion_bytes() : 0);
     }
-    int enable_chips(int size, int kind, const float* na, const float* nb);   // outside any update: the store, graphs recaptured
+    int enable_chips(int size, int kind, const float* na, const float* nb);   // enable_feature: the store
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
     int read_chips(const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos);
-    // response peaks (k_peaks.hip). The first policy with max_peaks > 0 allocates the records [B] by
-    // slot + the policies [B] by stream and makes the engine peaks-capable for good: every pass runs the peaks launch
-    // behind its decode (and behind the refresh and chip launches). Engines that never enable launch what they always did.
+    // response peaks (k_peaks.hip). The first policy with max_peaks > 0 allocates the records [B] by slot + the policies
+    // [B] by stream and the pinned mirrors: every pass runs the peaks launch behind its decode (and behind the refresh
+    // and chip launches).
     bool peaks_capable = false;
     vt_peaks* d_peaks = nullptr;                  // ONE allocation: [B] records by slot, then the [B] policies
     PeaksPolicy* d_peaks_policy = nullptr;        // [B] by stream, inside d_peaks; written by set_peaks only
@@ -226,9 +242,8 @@ struct Engine {
     size_t peaks_bytes() const { return (size_t)B * (sizeof(vt_peaks) + sizeof(PeaksPolicy)); }
     int set_peaks(int stream, int max_peaks, int radius, float min_resp);     // stream -1: all; the first enable is in here
     int last_peaks(vt_peaks* out, int n) const;
-    // result overlay (k_result_overlay.hip). ONE policy per engine. The first non-zero flags allocate the
-    // policy record + the [B] counters by stream and make the engine overlay-capable for good: every pass ends with the
-    // overlay launch, behind the refresh, chip and peaks launches. Engines that never enable launch what they always did.
+    // result overlay (k_result_overlay.hip). ONE policy per engine. The first non-zero flags allocate the policy record +
+    // the [B] counters by stream: every pass ends with the overlay launch, behind the refresh, chip and peaks launches.
     // A style, colour or gate value set before that is kept in overlay_policy and goes up with the enable.
     bool overlay_capable = false;
     OverlayPolicy overlay_policy = VT_OVERLAY_DEFAULT_POLICY;     // the host's copy
@@ -236,18 +251,17 @@ struct Engine {
     OverlayPolicy* d_overlay_policy() const { return reinterpret_cast<OverlayPolicy*>(d_overlay); }
     OverlayStats* d_overlay_stats() const { return reinterpret_cast<OverlayStats*>(d_overlay + sizeof(OverlayPolicy)); }
     size_t overlay_bytes() const { return sizeof(OverlayPolicy) + (size_t)B * sizeof(OverlayStats); }
-    // 1 while a device entry point builds its pass (vt_abi.hip: DeviceFramesScope): prepare_pass / enqueue_candidates write
-    // it into the pass's block, where the overlay launch reads it. Host-pointer passes hand the kernels staging or
-    // mapped host memory: they never draw.
+    // 1 while a device entry point builds its pass (vt_abi.hip: DeviceFramesScope): build_block writes it into the
+    // pass's block, where the overlay launch reads it. Host-pointer passes hand the kernels staging or mapped host
+    // memory: they never draw.
     int frames_on_device = 0;
     static bool overlay_key(const std::string& key) { return key.rfind("result_overlay", 0) == 0; }
     int set_overlay(const std::string& key, int value);     // the keys of vt_group_set_tuning; the first enable is in here
     int overlay_stats(int stream, float* out6);
-    // motion prior (k_motion.hip). ONE policy per engine, one record per stream. The first non-zero
-    // "motion_prior" allocates the policy record + the [B] records and their pinned mirror and makes the engine
-    // motion-capable for good: every pass starts with the place launch and runs the settle launch directly behind its
-    // decode (its commit). Engines that never enable launch what they always did. A gain, coast or limit set before that
-    // is kept in motion_policy and goes up with the enable.
+    // motion prior (k_motion.hip). ONE policy per engine, one record per stream. The first non-zero "motion_prior"
+    // allocates the policy record + the [B] records and their pinned mirrors: every pass starts with the place launch and
+    // runs the settle launch directly behind its decode (its commit). A gain, coast or limit set before that is kept in
+    // motion_policy and goes up with the enable.
     bool motion_capable = false;
     MotionPolicy motion_policy = VT_MOTION_DEFAULT_POLICY;       // the host's copy
     uint8_t* d_motion = nullptr;                  // ONE allocation: the policy record, then the [B] MotionRec by stream
@@ -281,7 +295,7 @@ struct Engine {
     size_t devflag_offset() const { return map_offset() + 4 * (size_t)B; }     // the pass's device-frames word (result overlay)
     const int32_t* d_devflag() const { return (const int32_t*)((const char*)d_frames + devflag_offset()); }
     const int32_t* d_map() const { return (const int32_t*)((const char*)d_frames + map_offset()); }
-    // the last pass (written by prepare_pass only): its slot count and, for a subset pass, the stream of every slot
+    // the last pass (written by build_block only): its slot count and, for a subset pass, the stream of every slot
     // (empty: all B streams in order); feat_in_head: it did not write d_feat (recomputed when read)
     int pass_n = 1;
     std::vector<int32_t> pass_streams;
@@ -293,7 +307,7 @@ struct Engine {
     // The compact pair lives in d_qk, which is dead behind the last attention: hi at its start, lo8 behind B * ns * D
     // bf16 elements (3 B * ns * D bytes of the 4 B * ntok * D the buffer has).
     int last_rows = 1;                  // vt_group_set_tuning "last_rows": 0 = every pass runs all rows
-    bool pass_compact = false;          // the last pass's last block ran on the search rows only (written by the pass builders)
+    bool pass_compact = false;          // the last pass's last block ran on the search rows only (written by build_block)
     bf16_t* xc_hi() const { return d_qk; }
     uint8_t* xc_lo() const { return reinterpret_cast<uint8_t*>(d_qk + (size_t)B * d.ns * d.D); }
     // a pass over n slots runs its last block on the search rows only: "last_rows" is on, no taps (they copy whole-layout
@@ -313,6 +327,15 @@ struct Engine {
     int ring_pos = 0;
     vt_result* h_results = nullptr;
     StreamState* h_state = nullptr;
+    // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
+    // slot, states and motion records [B] by stream. The engine's own are h_results, h_states_all, h_peaks and
+    // h_motion_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
+    // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them.
+    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_ALL = 7 };
+    unsigned sink_members() const { return SINK_BASE | (peaks_capable ? SINK_PEAKS : 0u) | (motion_capable ? SINK_MOTION : 0u); }
+    PassOut own_sinks() const { return {h_results, h_states_all, h_peaks, h_motion_all}; }
+    hipError_t sinks_alloc(PassOut* o, unsigned members) const;
+    void sinks_free(PassOut* o, unsigned members) const;
     // graph
     // one captured pass per crop-buffer tier (k_preproc.hip: 16 / 32 / 64 KiB of LDS per tile), all captured at creation
     static constexpr int TIERS = 3;
@@ -338,10 +361,9 @@ struct Engine {
     // pinned + device arena, result buffers, state snapshot and events; uploads go on copy_stream
     struct HostSlot {
         StageArena arena;
-        vt_result* h_res = nullptr;     // the pass's results, by SLOT (list order)
-        StreamState* h_st = nullptr;    // [B] by STREAM: valid at the listed streams' indices only
-        vt_peaks* h_peaks = nullptr;    // the pass's peak records, by SLOT (peaks-capable engines only)
-        MotionRec* h_mo = nullptr;      // [B] by STREAM, like h_st: the motion records (motion-capable engines only)
+        // the pass's sinks (sinks_alloc): results and peak records by SLOT (list order); states and motion records [B]
+        // by STREAM, valid at the listed streams' indices only
+        PassOut out{};
         hipEvent_t up_ev = nullptr, done_ev = nullptr;
         std::vector<vt_frame> host;     // the caller's frames, valid until the pass is collected
         std::vector<int32_t> list;      // the pass's streams (the identity list: the full pass)
@@ -410,15 +432,17 @@ struct Engine {
     void drop_graphs();
     // One pass over streams[0..n), frames[i] for streams[i]; streams == null: all B streams in order (n == B), and no
     // list is built for it. VT_ERR_INVALID_ARG / VT_ERR_NOT_INITIALIZED with nothing enqueued on bad input (checked in
-    // the order list, initialisation, frames). host_res / host_st: pinned buffers the pass's results and states are
-    // stored to (null: the engine's own h_results / h_states_all); host_pk: the same for the peak records of a
-    // peaks-capable engine (null: h_peaks), host_mo for the motion records of a motion-capable one (null: h_motion_all).
+    // the order list, initialisation, frames). sinks: where the pass's outputs land (null: the engine's own buffers).
     int check_streams(const int32_t* streams, int n) const;
-    // checks + the pass's block uploaded behind the stream's work + the last-pass record; the engine's device is current
-    int prepare_pass(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res, StreamState* host_st,
-                     vt_peaks* host_pk, PassShape* ps, MotionRec* host_mo = nullptr);
-    int enqueue(const int32_t* streams, const vt_frame* frames, int n, vt_result* host_res = nullptr,
-                StreamState* host_st = nullptr, vt_peaks* host_pk = nullptr, MotionRec* host_mo = nullptr);
+    // The one place a pass's block is put together, for n checked frames: a block of the pinned ring once the copy that
+    // last used it is done - descriptors, PassOut (host_states only with by_stream_states; peak and motion records only
+    // on engines capable of them), the slot map (map: slot -> stream; null: the full pass) and the device-frames word -
+    // uploaded behind the stream's work, its event recorded, and the last-pass record written. *ps: n, slot_stream,
+    // any_layout and compact filled; tier and cand are the caller's. The engine's device is current.
+    int build_block(const int32_t* map, const vt_frame* frames, int n, const PassOut* sinks, bool by_stream_states, PassShape* ps);
+    // checks + build_block + the template rows' bookkeeping + the tier; the engine's device is current
+    int prepare_pass(const int32_t* streams, const vt_frame* frames, int n, const PassOut* sinks, PassShape* ps);
+    int enqueue(const int32_t* streams, const vt_frame* frames, int n, const PassOut* sinks = nullptr);
     int wait(vt_result* out, int n);
     // A candidate pass over cands[0..n) (k_cand.hip): checked (list, boxes, initialisation, frames - nothing enqueued
     // on bad input), built and launched eagerly. A list that is a plain subset pass - every stream once, no box - goes

@@ -230,15 +230,10 @@ int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxe
 
 static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
     DEVICE_SCOPE(e->device);
-    if (e->peaks_capable && !sl.h_peaks) {      // a slot first used after the enable (set_peaks covers those that existed)
-        HIPCHK(hipHostMalloc((void**)&sl.h_peaks, sizeof(vt_peaks) * e->B));
-        memset(sl.h_peaks, 0, sizeof(vt_peaks) * e->B);
-    }
-    if (e->motion_capable && !sl.h_mo) {        // the same for the motion records (set_motion covers those that existed)
-        HIPCHK(hipHostMalloc((void**)&sl.h_mo, sizeof(MotionRec) * e->B));
-        memset(sl.h_mo, 0, sizeof(MotionRec) * e->B);
-    }
-    if (sl.h_res) return VT_OK;
+    // whatever of the slot's sinks is missing: all of them at its first use, the peak or motion records at its first use
+    // after that feature's enable (the enable itself covers the slots that exist)
+    HIPCHK(e->sinks_alloc(&sl.out, e->sink_members()));
+    if (sl.done_ev) return VT_OK;
     // HIP multiplexes a process's streams onto a few hardware queues (four by default): with more
     // streams than that alive - e.g. four engines, each with a compute and a copy stream - an upload
     // can share a queue with some engine's compute stream and is then ordered behind that engine's
@@ -246,9 +241,7 @@ static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
     // change that). Two engines per process (2 + 2 streams) keep the overlap: 99.5 % of the
     // HBM-resident rate.
     if (!e->copy_stream) HIPCHK(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipHostMalloc((void**)&sl.h_res, sizeof(vt_result) * e->B));
-    HIPCHK(hipHostMalloc((void**)&sl.h_st, sizeof(StreamState) * e->B));
-    HIPCHK(hipEventCreateWithFlags(&sl.up_ev, hipEventDisableTiming));
+    if (!sl.up_ev) HIPCHK(hipEventCreateWithFlags(&sl.up_ev, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&sl.done_ev, hipEventDisableTiming));
     return VT_OK;
 }
@@ -283,17 +276,17 @@ static int update_host_pass(Engine* e, const int32_t* streams, const vt_frame* h
 // a collected (or redone) pass becomes what the host knows: the entries of ITS streams move, no others. The
 // decode kernel stores a slot's results by slot and its states by stream (k_head.hip: decode_box).
 static void adopt_peaks(Engine* e, const Engine::HostSlot& sl) {
-    if (!e->peaks_capable || !sl.h_peaks) return;
-    for (size_t i = 0; i < sl.list.size(); ++i) e->h_peaks[i] = sl.h_peaks[i];
+    if (!e->peaks_capable || !sl.out.host_peaks) return;
+    for (size_t i = 0; i < sl.list.size(); ++i) e->h_peaks[i] = sl.out.host_peaks[i];
     e->peaks_n = (int)sl.list.size();
 }
 static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
     for (size_t i = 0; i < sl.list.size(); ++i) {
         const int s = sl.list[i];
-        e->known[s] = sl.h_st[s];
-        e->h_states_all[s] = sl.h_st[s];        // the engine's own mirrors follow
-        if (e->motion_capable && sl.h_mo) e->known_motion[(size_t)s] = e->h_motion_all[s] = sl.h_mo[s];
-        e->h_results[i] = sl.h_res[i];
+        e->known[s] = sl.out.host_states[s];
+        e->h_states_all[s] = sl.out.host_states[s];        // the engine's own mirrors follow
+        if (e->motion_capable && sl.out.host_motion) e->known_motion[(size_t)s] = e->h_motion_all[s] = sl.out.host_motion[s];
+        e->h_results[i] = sl.out.host_results[i];
     }
     adopt_peaks(e, sl);                         // the peak records are by slot, like the results
 }
@@ -306,7 +299,7 @@ static int host_pass_exact_sync(Engine* e, Engine::HostSlot& sl) {
     const std::vector<float> boxes = known_boxes(e, sl.list.data(), n);
     if (int rc = stage_host_frames(e, sl.host.data(), n, reinterpret_cast<const float(*)[4]>(boxes.data()), dev.data()))
         return rc;
-    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks, sl.h_mo)) return rc;
+    if (int rc = e->enqueue(sl.list.data(), dev.data(), n, &sl.out)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     adopt_slot(e, sl);
     sl.redone = true;
@@ -340,7 +333,7 @@ static int enqueue_host_pass(Engine* e, const int32_t* streams, const vt_frame* 
         return rc;
     HIPCHK(hipEventRecord(sl.up_ev, e->copy_stream));
     HIPCHK(hipStreamWaitEvent(e->stream, sl.up_ev, 0));          // the pass starts behind ITS upload only
-    if (int rc = e->enqueue(streams, dev.data(), n, sl.h_res, sl.h_st, sl.h_peaks, sl.h_mo)) return rc;   // results land in THIS slot's buffers
+    if (int rc = e->enqueue(streams, dev.data(), n, &sl.out)) return rc;   // results land in THIS slot's buffers
     HIPCHK(hipEventRecord(sl.done_ev, e->stream));
     sl.host.assign(host_frames, host_frames + n);
     sl.list.assign(streams, streams + n);
@@ -496,7 +489,7 @@ int vt_group_wait_next(vt_group* g, vt_result* out, int n) try {
         HIPCHK(hipEventSynchronize(sl.done_ev));
         bool miss = false;
         for (int i = 0; i < pass_n; ++i) {
-            const StreamState& st = sl.h_st[sl.list[(size_t)i]];
+            const StreamState& st = sl.out.host_states[sl.list[(size_t)i]];
             miss = miss || (sl.spec[(size_t)i] && st.window_miss != 0 && st.window_miss == st.frames_done);
         }
         if (miss) {
@@ -525,7 +518,7 @@ int vt_group_wait_next(vt_group* g, vt_result* out, int n) try {
         }
     }
     if (out)
-        for (int i = 0; i < std::min(n, pass_n); ++i) out[i] = sl.h_res[i];
+        for (int i = 0; i < std::min(n, pass_n); ++i) out[i] = sl.out.host_results[i];
     // boxes the next window is planned around: this pass's - unless a younger pass was redone just
     // now, whose states are newer (host_pass_exact_sync adopted both already, in order)
     if (!(has_younger && younger.redone)) adopt_slot(e, sl);
