@@ -160,7 +160,7 @@ OPS_EXPORTS = [
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
-    "vt_op_motion_prior",
+    "vt_op_motion_prior", "vt_op_appearance_score",
 ]
 
 
@@ -328,6 +328,7 @@ def ops_lib():
                                        c_int, c_void_p, c_void_p]
     L.vt_op_motion_prior.argtypes = [c_int, c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, POINTER(c_int32), POINTER(c_int32),
                                      c_void_p, c_int, c_int, c_void_p, c_void_p]
+    L.vt_op_appearance_score.argtypes = [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_void_p,
                                        c_int, c_int]
     _ops = L
@@ -845,6 +846,16 @@ class VitTrack:
     def motion(self) -> dict:
         return self.as_group().motion(0)
 
+    def set_appearance(self, on: bool = True, period: int | None = None, gate: float | None = None) -> None:
+        """the appearance check of this tracker's engine: see Group.set_appearance"""
+        self.as_group().set_appearance(on, period, gate)
+
+    def appearance(self) -> dict:
+        return self.as_group().appearance(0)
+
+    def anchor(self) -> np.ndarray:
+        return self.as_group().anchor(0)
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -1360,6 +1371,43 @@ class Group:
         return dict(on=int(v[0]), v=(float(v[1]), float(v[2])), live=int(v[3]), shift=(float(v[4]), float(v[5])),
                     n_shift=int(v[6]), n_coast=int(v[7]))
 
+    def set_appearance(self, on: bool = True, period: int | None = None, gate: float | None = None) -> None:
+        """the "appearance*" keys of vt_group_set_tuning: every pass of this engine cuts a template-sized crop at each
+        stream's new box (the probe) and scores it against the rows the stream was started from (the anchor): zero-mean
+        normalised correlation, 1 = the same pixels. period (1..1,000,000): evaluated when frames_done % period == 0; gate
+        (0..1, stored per mille): a template refresh additionally needs similarity >= gate, 0 = report only. None keeps a
+        value. The first enable makes the engine appearance-capable (graphs recaptured, two more launches per pass from then
+        on). Refused while a pipelined pass is outstanding."""
+        if period is not None:
+            if int(period) < 0:
+                raise ValueError(f"appearance_period: {period}")
+            self.set_tuning("appearance_period", int(period))
+        if gate is not None:
+            if not 0.0 <= float(gate) <= 1.0:
+                raise ValueError(f"appearance gate: {gate}")
+            self.set_tuning("appearance_gate_pm", int(round(float(gate) * 1000.0)))
+        self.set_tuning("appearance", 1 if on else 0)
+
+    def set_anchor(self, stream: int = -1) -> None:
+        """the "appearance_anchor" action: the stream's (-1: every initialised stream's) anchor becomes its CURRENT template"""
+        self.set_tuning("appearance_anchor", int(stream))
+
+    def appearance(self, stream: int = 0) -> dict:
+        """vt_group_read_tensor "appearance": the engine flag, the stream's record of its last pass - status (0 not due or
+        not evaluated, 1 evaluated, 2 the crop left the sampled search crop, 3 a flat anchor or probe), similarity,
+        frames_done - and its counters (evaluated; gated: refreshes the gate refused), the period and the gate per mille"""
+        v = self.read_tensor("appearance", stream)
+        return dict(on=int(v[0]), status=int(v[1]), similarity=float(v[2]), frames_done=int(v[3]), evaluated=int(v[4]),
+                    gated=int(v[5]), period=int(v[6]), gate_pm=int(v[7]))
+
+    def anchor(self, stream: int = 0) -> np.ndarray:
+        """vt_group_read_tensor "anchor": the [Nt * Kpad] rows the stream's probes are compared with"""
+        return self.read_tensor("anchor", stream)
+
+    def probe(self, stream: int = 0) -> np.ndarray:
+        """vt_group_read_tensor "probe": the rows of the stream's last cut probe (valid where the record's status is 1 or 3)"""
+        return self.read_tensor("probe", stream)
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""
@@ -1659,6 +1707,22 @@ def op_motion_prior(states, records, results, on=1, gain_pct=50, coast=5, max_pc
         device, vp(st), vp(rec), len(st), pol.ctypes.data_as(i32), vp(res), smap.ctypes.data_as(i32) if smap is not None else None,
         win.ctypes.data_as(i32) if win is not None else None, vp(cd), n, stages, vp(hst), vp(hrec)))
     return dict(states=st, records=rec, host_states=hst, host_records=hrec)
+
+
+def op_appearance_score(anchor, probe, cols, device=0):
+    """vt_op_appearance_score: the score launch of k_appearance.hip on given rows, nothing else. anchor, probe:
+    [n_slots, nt, kpad] uint16 bf16 bit patterns; the sums run over columns [0, cols). -> dict(sums [n_slots, 5] float64 =
+    Sa, Sp, Saa, Spp, Sap, similarity [n_slots] float32, status [n_slots] int32)"""
+    a = np.ascontiguousarray(anchor, np.uint16)
+    p = np.ascontiguousarray(probe, np.uint16)
+    assert a.ndim == 3 and a.shape == p.shape
+    n, nt, kpad = a.shape
+    sums = np.empty((n, 5), np.float64)
+    sim = np.empty(n, np.float32)
+    status = np.empty(n, np.int32)
+    vp = lambda x: x.ctypes.data_as(c_void_p)
+    _check_op(ops_lib().vt_op_appearance_score(device, vp(a), vp(p), n, nt, kpad, int(cols), vp(sums), vp(sim), vp(status)))
+    return dict(sums=sums, similarity=sim, status=status)
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)

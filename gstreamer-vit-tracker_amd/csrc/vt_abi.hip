@@ -376,6 +376,7 @@ int vt_group_set_tuning(vt_group* g, const char* key, int value) try {
     const std::string k = key;
     if (Engine::overlay_key(k)) return e->set_overlay(k, value);    // engine options: the passes are captured again by the first enable only
     if (Engine::motion_key(k)) return e->set_motion(k, value);
+    if (Engine::appearance_key(k)) return e->set_appearance(k, value);
     if (k == "head_band") e->head_band_kernel = value < 0 ? 2 : value;   // 0 / 1 / 2, see Engine::head_band_kernel
     else if (k == "last_rows") e->last_rows = value != 0;        // 0: the last block runs all rows; else (default) the search rows where eligible
     else if (k == "crop_tier") e->crop_tier_forced = value;      // < 0: chosen per pass from the known boxes (default)
@@ -500,6 +501,16 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         if (capacity < 8) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
         if (int rc = e->motion_stats(stream, out)) return rc;
         return 8;
+    }
+    if (n == "appearance") {            // by stream, whatever the last pass was: the engine flag, the stream's record and counters
+        if (!out) return e->appear_capable ? 8 : e->appearance_stats(stream, nullptr);
+        if (capacity < 8) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        if (int rc = e->appearance_stats(stream, out)) return rc;
+        return 8;
+    }
+    if (n == "anchor" || n == "probe") {    // by stream: the rows the stream is compared with / the rows of its last cut probe
+        if (!e->appear_capable) return e->appearance_stats(stream, nullptr);
+        return copy_out_bf16(n == "anchor" ? e->d_anchor(stream) : e->d_probe(stream), (int64_t)d.nt * d.kpad, out, capacity);
     }
     // every tensor but the stream's state and the replay counters belongs to the last pass: the stream's slot in it
     size_t b = (size_t)stream;

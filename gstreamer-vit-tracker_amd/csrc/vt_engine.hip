@@ -37,7 +37,7 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay, d_motion};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay, d_motion, d_appear};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
@@ -584,9 +584,21 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     if (motion_capable)     // ahead of everything that reads the new box: the velocity, the coast or the restore
         L("motion_settle", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + 3.0 * sizeof(MotionRec)),
           [&] { return launch_motion_settle(ma, stream); });
+    if (appear_capable) {   // ahead of everything that cuts or draws: the probe at the new box and its similarity to the anchor
+        const AppearArgs aa{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_appear_policy(),
+                            d_appear_counts(), d_appear_recs(), refresh_capable ? d_policy : nullptr, d_appear_tickets(),
+                            d_appear_partials(), d_anchor(), d_probe(), (const PassOut*)(d_frames + B),
+                            ps.cand ? ps.cand->host_states : nullptr, nullptr, n};
+        const int cols = 3 * d.patch * d.patch;
+        L("appearance_probe", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + sizeof(AppearRec)),
+          [&] { return launch_appearance_probe(aa, d, ps.tier, ps.any_layout, stream); });
+        L("appearance_score", 10.0 * n * d.nt * cols, 4.0 * n * d.nt * cols,
+          [&] { return launch_appearance_score(aa, d.nt, cols, d.kpad, stream); });
+    }
     if (refresh_capable) {  // the streams' policies, on what the decode (the commit) left: k_refresh.hip
-        const RefreshArgs ra{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_policy,
-                             d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
+        RefreshArgs ra{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_policy,
+                       d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
+        if (appear_capable) { ra.ap_policy = d_appear_policy(); ra.ap_counts = d_appear_counts(); ra.ap_recs = d_appear_recs(); }
         L("refresh_template", 0, 2.0 * n * (sizeof(StreamState) + sizeof(vt_result)),
           [&] { return launch_template_refresh(ra, d, ps.tier, ps.any_layout, stream); });
     }
@@ -776,6 +788,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     // follows one: restore_segments puts every stream's rows back from here, these included)
     HIPCHK(hipMemcpyAsync(tpl_init_rows(b), d_patches + (size_t)b * d.ntok * d.kpad,
                           sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(anchor_from_template(b, 0));     // the appearance anchor: the init's rows (buffer 0)
     return VT_OK;
 }
 
@@ -843,7 +856,8 @@ int Engine::build_block(const int32_t* map, const vt_frame* frames, int n, const
     const PassOut own = own_sinks();
     const PassOut& to = sinks ? *sinks : own;
     *(PassOut*)(hf + B) = PassOut{to.host_results, by_stream_states ? to.host_states : nullptr,
-                                  peaks_capable ? to.host_peaks : nullptr, motion_capable ? to.host_motion : nullptr};
+                                  peaks_capable ? to.host_peaks : nullptr, motion_capable ? to.host_motion : nullptr,
+                                  appear_capable ? to.host_appearance : nullptr};
     if (map) std::copy(map, map + n, (int32_t*)((char*)hf + map_offset()));
     *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
@@ -963,6 +977,7 @@ hipError_t Engine::sinks_alloc(PassOut* o, unsigned members) const {
     if (e == hipSuccess && (members & SINK_BASE)) e = pinned0(&o->host_states, (size_t)B);
     if (e == hipSuccess && (members & SINK_PEAKS)) e = pinned0(&o->host_peaks, (size_t)B);
     if (e == hipSuccess && (members & SINK_MOTION)) e = pinned0(&o->host_motion, (size_t)B);
+    if (e == hipSuccess && (members & SINK_APPEAR)) e = pinned0(&o->host_appearance, (size_t)B);
     return e;
 }
 
@@ -971,12 +986,14 @@ void Engine::sinks_free(PassOut* o, unsigned members) const {
     if (members & SINK_BASE) { drop(&o->host_results); drop(&o->host_states); }
     if (members & SINK_PEAKS) drop(&o->host_peaks);
     if (members & SINK_MOTION) drop(&o->host_motion);
+    if (members & SINK_APPEAR) drop(&o->host_appearance);
 }
 
 // ---- template refresh --------------------------------------------------------------------------------
 
 int Engine::reset_refresh_tickets() {
     if (d_tickets) HIPCHK(hipMemsetAsync(d_tickets, 0, sizeof(unsigned) * (size_t)B, stream));
+    if (appear_capable) HIPCHK(hipMemsetAsync(d_appear_tickets(), 0, sizeof(unsigned) * (size_t)B, stream));
     return VT_OK;
 }
 
@@ -1356,6 +1373,103 @@ int Engine::motion_stats(int s, float* out8) {
     HIPCHK(hipMemcpy(&r, d_motion_recs() + s, sizeof(r), hipMemcpyDeviceToHost));
     out8[0] = (float)motion_policy.on; out8[1] = r.v[0]; out8[2] = r.v[1]; out8[3] = (float)r.live;
     out8[4] = r.shift[0]; out8[5] = r.shift[1]; out8[6] = (float)r.n_shift; out8[7] = (float)r.n_coast;
+    return VT_OK;
+}
+
+// ---- appearance check ---------------------------------------------------------------------------------
+
+hipError_t Engine::anchor_from_template(int b, int gen) {
+    if (!appear_capable) return hipSuccess;
+    const bf16_t* rows = tpl_init_rows(b) + (refresh_capable ? (size_t)(gen & 1) * appear_rows() : 0);
+    hipError_t he = hipMemcpyAsync(d_anchor(b), rows, sizeof(bf16_t) * appear_rows(), hipMemcpyDeviceToDevice, stream);
+    if (he == hipSuccess) he = hipMemsetAsync(d_appear_recs() + b, 0, sizeof(AppearRec), stream);
+    h_appear_all[b] = AppearRec{};      // the stream is in no outstanding pass: nothing else writes its entry
+    return he;
+}
+
+// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "appearance" is the enable
+// (enable_feature): the store, the anchors of the streams that are initialised, the pinned mirrors. Every later change is
+// one small copy: the passes read the record. "appearance_anchor" is an action: the anchor of stream `value` (-1: of every
+// initialised stream) becomes the stream's CURRENT template rows.
+int Engine::set_appearance(const std::string& key, int value) {
+    AppearPolicy p = appear_policy;
+    const AppearPolicy def = VT_APPEAR_DEFAULT_POLICY;
+    if (key == "appearance") {
+        p.on = value < 0 ? def.on : value;
+        if (p.on > 1) return set_err(VT_ERR_INVALID_ARG, "appearance: %d (0: off, 1: on)", value);
+    } else if (key == "appearance_period") {
+        p.period = value < 0 ? def.period : value;
+        if (p.period < 1 || p.period > VT_APPEAR_MAX_PERIOD)
+            return set_err(VT_ERR_INVALID_ARG, "appearance_period: %d (1..%d)", value, VT_APPEAR_MAX_PERIOD);
+    } else if (key == "appearance_gate_pm") {
+        p.gate_pm = value < 0 ? def.gate_pm : value;
+        if (p.gate_pm > 1000) return set_err(VT_ERR_INVALID_ARG, "appearance_gate_pm: %d (0..1000)", value);
+        p.tau = (float)p.gate_pm / 1000.0f;
+    } else if (key == "appearance_anchor") {
+        if (!appear_capable)
+            return set_err(VT_ERR_INVALID_ARG, "appearance_anchor: the check is not enabled on this engine (vt_group_set_tuning \"appearance\")");
+        if (value < -1 || value >= B) return set_err(VT_ERR_INVALID_ARG, "appearance_anchor: stream %d (-1: all, else 0..%d)", value, B - 1);
+        if (value >= 0 && !h_initialized[(size_t)value]) return set_err(VT_ERR_NOT_INITIALIZED, "appearance_anchor: stream %d not initialised", value);
+        DEVICE_SCOPE(device);
+        HIPCHK(hipStreamSynchronize(stream));
+        std::vector<StreamState> sts((size_t)B);
+        HIPCHK(hipMemcpy(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost));
+        for (int b = value < 0 ? 0 : value; b < (value < 0 ? B : value + 1); ++b)
+            if (h_initialized[(size_t)b]) HIPCHK(anchor_from_template(b, sts[(size_t)b].tpl_gen));
+        HIPCHK(hipStreamSynchronize(stream));
+        return VT_OK;
+    } else {
+        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
+    }
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!appear_capable && p.on != 0) {
+        uint8_t* store = nullptr;       // all zero but the policy and the anchors of the initialised streams
+        PassOut own{};                  // the engine's own mirror
+        auto alloc = [&] {
+            std::vector<StreamState> sts((size_t)B);     // before the device allocation: may throw
+            hipError_t he = dalloc0(&store, appear_bytes(), stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost, stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(stream);
+            bf16_t* anchors = reinterpret_cast<bf16_t*>(store + appear_off_anchor());
+            for (int b = 0; b < B && he == hipSuccess; ++b)
+                if (h_initialized[(size_t)b])
+                    he = hipMemcpyAsync(anchors + (size_t)b * appear_rows(),
+                                        tpl_init_rows(b) + (refresh_capable ? (size_t)(sts[(size_t)b].tpl_gen & 1) * appear_rows() : 0),
+                                        sizeof(bf16_t) * appear_rows(), hipMemcpyDeviceToDevice, stream);
+            if (he == hipSuccess) he = sinks_alloc(&own, SINK_APPEAR);
+            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
+                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_APPEAR);
+            return he;
+        };
+        auto install = [&] { d_appear = store; h_appear_all = own.host_appearance; appear_capable = true; };
+        auto uninstall = [&] {
+            (void)hipFree(store);       // null: no operation
+            sinks_free(&own, SINK_APPEAR);
+            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_APPEAR);
+            d_appear = nullptr; h_appear_all = nullptr;
+            appear_capable = false;
+        };
+        if (int rc = enable_feature({"appearance check", appear_bytes(), alloc, install, uninstall})) return rc;
+    } else if (appear_capable) {
+        HIPCHK(hipMemcpy(d_appear_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
+    }
+    appear_policy = p;
+    return VT_OK;
+}
+
+// [8]: the engine flag, the stream's record (status, similarity, frames_done), its counters (evaluated, gated), period, gate_pm
+int Engine::appearance_stats(int s, float* out8) {
+    if (!appear_capable)
+        return set_err(VT_ERR_INVALID_ARG, "appearance check: not enabled on this engine (vt_group_set_tuning \"appearance\")");
+    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected (a pipelined pass still
+    // running has written the device record already, and may yet be redone); the counters: the device's
+    const AppearRec r = h_appear_all[s];
+    AppearCount c{};
+    HIPCHK(hipMemcpy(&c, d_appear_counts() + s, sizeof(c), hipMemcpyDeviceToHost));
+    out8[0] = (float)appear_policy.on; out8[1] = (float)r.status; out8[2] = r.similarity; out8[3] = (float)r.frames_done;
+    out8[4] = (float)c.evaluated; out8[5] = (float)c.gated; out8[6] = (float)appear_policy.period; out8[7] = (float)appear_policy.gate_pm;
     return VT_OK;
 }
 

@@ -206,7 +206,7 @@ struct Engine {
     int enable_refresh();                         // enable_feature: second buffer, policy, tickets
     int set_refresh(int stream, int period, float min_score);     // stream -1: all
     int refresh_stats(int stream, vt_refresh_stats* out);
-    int reset_refresh_tickets();                  // wherever a pass may have been abandoned half-way
+    int reset_refresh_tickets();                  // wherever a pass may have been abandoned half-way (the appearance launches' tickets too)
     // target chips (k_chip.hip). The first enable fixes the chip side and kind and allocates the store [B][chip_bytes] +
     // [B] infos + [B] policies: every pass runs the chip launch behind its decode (and behind the refresh launch).
     bool chip_capable = false;
@@ -225,7 +225,7 @@ struct Engine {
     size_t feature_bytes() const {
         return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0) +
                (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0) +
-               (motion_capable ? motion_bytes() : 0);
+               (motion_capable ? motion_bytes() : 0) + (appear_capable ? appear_bytes() : 0);
     }
     int enable_chips(int size, int kind, const float* na, const float* nb);   // enable_feature: the store
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
@@ -280,6 +280,39 @@ struct Engine {
     // steps == 2: the stream is in the pass still running, whose outcome nobody knows - the rule applied twice, once for
     // that pass's own move and once for the next one's (a target at constant velocity lands there)
     void predicted_box(int stream, float* box4, int steps = 1) const;
+    // appearance check (k_appearance.hip). ONE policy per engine; per stream an anchor and a probe of template rows, a
+    // record and two counters. The first non-zero "appearance" allocates all of it, fills the anchors of the streams that
+    // are initialised from their current template rows and makes the engine appearance-capable for good: every pass runs
+    // the probe and the score launch behind its decode (its commit, motion_settle), ahead of the refresh launch, whose rule
+    // 8 reads the records. A period or gate set before that is kept in appear_policy and goes up with the enable.
+    bool appear_capable = false;
+    AppearPolicy appear_policy = VT_APPEAR_DEFAULT_POLICY;      // the host's copy
+    // ONE allocation: the policy | [B] counters | [B] records | [B] tickets | [B][chunks][5] partials (binary64) |
+    // [B][nt][kpad] anchors | [B][nt][kpad] probes (bf16, by stream)
+    uint8_t* d_appear = nullptr;
+    size_t appear_rows() const { return (size_t)d.nt * d.kpad; }
+    size_t appear_off_counts() const { return 64; }
+    size_t appear_off_recs() const { return appear_off_counts() + sizeof(AppearCount) * (size_t)B; }
+    size_t appear_off_tickets() const { return appear_off_recs() + sizeof(AppearRec) * (size_t)B; }
+    size_t appear_off_partials() const { return (appear_off_tickets() + sizeof(unsigned) * (size_t)B + 63) & ~(size_t)63; }
+    size_t appear_off_anchor() const { return (appear_off_partials() + sizeof(double) * 5 * (size_t)B * appear_chunks(d.nt) + 63) & ~(size_t)63; }
+    size_t appear_bytes() const { return appear_off_anchor() + 2 * sizeof(bf16_t) * appear_rows() * (size_t)B; }
+    AppearPolicy* d_appear_policy() const { return reinterpret_cast<AppearPolicy*>(d_appear); }
+    AppearCount* d_appear_counts() const { return reinterpret_cast<AppearCount*>(d_appear + appear_off_counts()); }
+    AppearRec* d_appear_recs() const { return reinterpret_cast<AppearRec*>(d_appear + appear_off_recs()); }
+    unsigned* d_appear_tickets() const { return reinterpret_cast<unsigned*>(d_appear + appear_off_tickets()); }
+    double* d_appear_partials() const { return reinterpret_cast<double*>(d_appear + appear_off_partials()); }
+    bf16_t* d_anchor(int b = 0) const { return reinterpret_cast<bf16_t*>(d_appear + appear_off_anchor()) + (size_t)b * appear_rows(); }
+    bf16_t* d_probe(int b = 0) const { return d_anchor(B) + (size_t)b * appear_rows(); }
+    // pinned [B] by stream: the records of the last passes the host collected - what "appearance" of vt_group_read_tensor
+    // reports (the kernels store to the pass's sink; adopt_slot copies a collected pipelined pass's entries here)
+    AppearRec* h_appear_all = nullptr;
+    static bool appearance_key(const std::string& key) { return key.rfind("appearance", 0) == 0; }
+    int set_appearance(const std::string& key, int value);  // the keys of vt_group_set_tuning; the first enable is in here
+    int appearance_stats(int stream, float* out8);
+    // stream b's anchor <- its current template rows (buffer gen & 1 of a refresh-capable engine's store), its record
+    // zeroed; behind the stream's work. init, queued init, import, copy, the "appearance_anchor" action
+    hipError_t anchor_from_template(int b, int gen);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -328,12 +361,14 @@ struct Engine {
     vt_result* h_results = nullptr;
     StreamState* h_state = nullptr;
     // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
-    // slot, states and motion records [B] by stream. The engine's own are h_results, h_states_all, h_peaks and
-    // h_motion_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
+    // slot, states, motion and appearance records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
+    // h_motion_all and h_appear_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
     // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them.
-    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_ALL = 7 };
-    unsigned sink_members() const { return SINK_BASE | (peaks_capable ? SINK_PEAKS : 0u) | (motion_capable ? SINK_MOTION : 0u); }
-    PassOut own_sinks() const { return {h_results, h_states_all, h_peaks, h_motion_all}; }
+    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_ALL = 15 };
+    unsigned sink_members() const {
+        return SINK_BASE | (peaks_capable ? SINK_PEAKS : 0u) | (motion_capable ? SINK_MOTION : 0u) | (appear_capable ? SINK_APPEAR : 0u);
+    }
+    PassOut own_sinks() const { return {h_results, h_states_all, h_peaks, h_motion_all, h_appear_all}; }
     hipError_t sinks_alloc(PassOut* o, unsigned members) const;
     void sinks_free(PassOut* o, unsigned members) const;
     // graph

@@ -978,4 +978,47 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The score launch of the appearance check on given rows: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_appearance_score, on records the hook marks "cut" for every slot (the identity map: slot i is stream i).
+int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t* probe, int n_slots, int nt, int kpad, int cols,
+                           double* sums, float* similarity, int32_t* status) try {
+    if (!anchor || !probe || !sums || !similarity || !status || n_slots < 1 || n_slots > VT_MAX_STREAMS || nt < 1 || nt > 65536 ||
+        cols < 1 || kpad < cols || kpad > 65536)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t n = (size_t)n_slots, rows = n * (size_t)nt * (size_t)kpad * sizeof(bf16_t);
+    const size_t nch = (size_t)appear_chunks(nt);
+    DevBuf da, dp, dpol, drec, dcnt, dtick, dpart, dsum;
+    HIPCHK(da.alloc(rows)); HIPCHK(dp.alloc(rows)); HIPCHK(dpol.alloc(sizeof(AppearPolicy))); HIPCHK(drec.alloc(n * sizeof(AppearRec)));
+    HIPCHK(dcnt.alloc(n * sizeof(AppearCount))); HIPCHK(dtick.alloc(n * sizeof(unsigned)));
+    HIPCHK(dpart.alloc(n * nch * 5 * sizeof(double))); HIPCHK(dsum.alloc(n * 5 * sizeof(double)));
+    HIPCHK(hipMemcpy(da.p, anchor, rows, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dp.p, probe, rows, hipMemcpyHostToDevice));
+    const AppearPolicy pol{1, 1, 0, 0.0f};
+    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
+    std::vector<AppearRec> recs(n, AppearRec{1, 0, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}, 0});
+    HIPCHK(hipMemcpy(drec.p, recs.data(), n * sizeof(AppearRec), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dcnt.p, 0, n * sizeof(AppearCount)));
+    HIPCHK(hipMemset(dtick.p, 0, n * sizeof(unsigned)));
+    HIPCHK(hipMemset(dpart.p, 0xff, n * nch * 5 * sizeof(double)));      // NaN: a partial nobody wrote would show
+    HIPCHK(hipMemset(dsum.p, 0xff, n * 5 * sizeof(double)));
+    AppearArgs a{};
+    a.policy = (const AppearPolicy*)dpol.p; a.counts = (AppearCount*)dcnt.p; a.recs = (AppearRec*)drec.p;
+    a.tickets = (unsigned*)dtick.p; a.partials = (double*)dpart.p;
+    a.anchor = (const bf16_t*)da.p; a.probe = (bf16_t*)dp.p; a.sums = (double*)dsum.p; a.n = n_slots;
+    HIPCHK(launch_appearance_score(a, nt, cols, kpad, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(recs.data(), drec.p, n * sizeof(AppearRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sums, dsum.p, n * 5 * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<unsigned> ticks(n);
+    HIPCHK(hipMemcpy(ticks.data(), dtick.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        if (ticks[i] != 0) return set_err(VT_ERR_HIP, "appearance_score: slot %zu left its ticket at %u", i, ticks[i]);
+        similarity[i] = recs[i].similarity;
+        status[i] = recs[i].status;
+    }
+    return VT_OK;
+} VT_NOTHROW_INT
+
 }  // extern "C"

@@ -879,6 +879,61 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * synchronous calls.
  *   Read-out: vt_group_read_tensor(g, stream, "motion", ...).
  *
+ * ENGINE OPTIONS - the appearance check (DESIGN.md section 3 "Appearance check"). A centre-head tracker that has slid onto a
+ * look-alike keeps returning success with a high score, and a template refresh would cut the look-alike into the template.
+ * With these keys every pass compares what is inside each stream's new box with what the stream was started from: the
+ * zero-mean normalised correlation of two template-sized crops, in the pixel domain, reported per stream and - with a
+ * gate - required of a refresh. The policy is per engine:
+ *   key                   value                                                                  default (a negative value selects it)
+ *   "appearance"          0 = off, 1 = on                                                        0
+ *   "appearance_period"   1..1,000,000: evaluated when frames_done % period == 0                 1
+ *   "appearance_gate_pm"  0..1000 per mille; 0 = report only; tau = (float)pm / 1000.0f          0
+ *   "appearance_anchor"   ACTION: a stream index, or -1 for every initialised stream (any other negative value is
+ *                         invalid): the stream's anchor <- its CURRENT template rows, its record zeroed
+ * A value outside its range returns VT_ERR_INVALID_ARG and changes nothing. A period or gate set before the engine is
+ * appearance-capable is remembered; the action needs a capable engine (else VT_ERR_INVALID_ARG) and an initialised stream
+ * (VT_ERR_NOT_INITIALIZED). The first non-zero "appearance" makes the engine appearance-capable for good: per stream an
+ * anchor and a probe of [Nt][Kpad] bf16, a record, counters and the reduction's partials, within max_device_mib, else
+ * VT_ERR_OOM and nothing changes; the anchors of the streams that are initialised are filled from their current template
+ * rows; the captured passes are captured again, here. From then on every pass - full, subset, candidate, synchronous and
+ * pipelined host, vt_group_profile_device - carries two more launches; engines that never enable launch exactly what they
+ * always did. Later changes of any key are one small copy and capture nothing.
+ *   THE ANCHOR of a stream holds the rows vt_group_read_tensor "template" returned at the moment it was set: by
+ * vt_group_init_* and vt_group_enqueue_init_host (the init's rows; the queued init on the group's stream, behind the
+ * queued passes), by vt_group_import_stream, vt_import_state and on the destination of vt_group_copy_stream (the imported
+ * rows), by the enable and by the action. A template refresh never writes it. It is no part of a snapshot (format 0001).
+ *   THE RULE, per slot i of a pass, behind the decode (candidate pass: behind the commit) and the motion prior's settle
+ * launch, ahead of refresh, chips, peaks and overlay (the probe is cut from undrawn pixels), with s the slot's stream,
+ * st its state as the pass left it and r = results[i]. The slot is DUE iff ALL of: (a) "appearance" is 1; (b) in a
+ * candidate pass winner[i] == i; (c) r.success != 0; (d) st.window_miss != st.frames_done; (e) st.frames_done % period == 0,
+ * OR tau > 0 and rules 1, 3 and 4 of vt_group_set_template_refresh hold for s (a refresh that the gate has to judge in
+ * this pass). A due slot applies refresh rules 6 and 7 unchanged: where rule 6 fails the record's status is 2; where rule
+ * 7 fails the pass is marked a window miss (st.window_miss = st.frames_done, record status 0), so a speculative pipelined
+ * pass is redone with an exact window and the redo evaluates. A passing slot cuts the PROBE: the crop of its frame at
+ * st.box, factor 2, side template_size - bit for bit the template rows vt_group_init_*(s, that frame, r.bbox) would write.
+ *   THE SCORE, over the first 3 * patch * patch columns of the Nt rows (pad columns are never read), a = anchor, p = probe,
+ * every element the exact value of its bf16, in binary64: Sa = sum a, Sp = sum p, Saa = sum a*a, Spp = sum p*p,
+ * Sap = sum a*p, n the element count; cov = Sap - Sa*Sp/n, va = Saa - Sa*Sa/n, vp = Spp - Sp*Sp/n;
+ * sim = (va > 0 && vp > 0) ? cov / sqrt(va * vp) : 0, clamped to [-1, 1] and rounded once to binary32; status 1, or 3 when a
+ * variance is not positive. The order of the additions is fixed (csrc/k_appearance.hip) and no floating-point atomic is
+ * used: the record is a function of the inputs alone, and pipelined runs equal synchronous ones bit for bit.
+ *   THE RECORD, per stream, on the device and mirrored to pinned host memory: status (0 = not due or not evaluated, 1, 2,
+ * 3), frames_done, similarity, box[4]. Every pass writes the records of its streams (a candidate pass: at the winning slot).
+ * Two diagnostic counters per stream, `evaluated` (records with status 1 or 3) and `gated`; like skipped_geometry they are
+ * never rewound and may count a redone pass twice.
+ *   REFRESH RULE 8. With "appearance" 1 and tau > 0 a refresh that rules 1-7 of vt_group_set_template_refresh allow
+ * additionally needs THIS pass's record of the stream to have status 1 and similarity >= tau. Otherwise nothing is cut, gated += 1, and the
+ * refresh is tried again at the stream's next update. With tau == 0, with "appearance" 0 (switching the check off switches
+ * its gate off: no refresh is held back by records nobody writes), and on engines that never enabled the check, the
+ * refresh behaves bit for bit as before. THE TWIN IDENTITY: an enabled engine with gate 0 equals a plain engine in results,
+ * state words and templates, bit for bit - with ONE exception: where a due slot fails rule 7 the probe launch sets
+ * st.window_miss = st.frames_done, as the refresh and chip launches do in that place. Whole frames and the library's own
+ * exact windows never fail rule 7, and a speculative pipelined pass that does is redone, after which the state is the
+ * plain engine's again; but a DEVICE pass on a caller-windowed frame (vt_frame.windowed, origin_*) whose window holds the
+ * search crop's taps and not all of the template crop's is not redone by anybody: there the enabled engine differs from a
+ * plain one in that one state word (and a following refresh or chip of the same pass, seeing the miss, does not cut).
+ *   Read-out: vt_group_read_tensor(g, stream, "appearance" / "anchor" / "probe", ...).
+ *
  * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
@@ -930,6 +985,13 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * "motion" [8] (by STREAM, whatever the last pass was; see vt_group_set_tuning "motion_prior"): the engine flag, vx, vy,
  * live, shift x and shift y of the stream's last pass, number of passes with a non-zero shift, number of failed updates
  * that advanced the box. VT_ERR_INVALID_ARG on an engine that never enabled the motion prior.
+ * "appearance" [8] (by STREAM, whatever the last pass was; see vt_group_set_tuning "appearance"): the engine flag, then the
+ * stream's record - status, similarity, frames_done - as the pinned mirror holds it: that of the stream's last pass the host
+ * has COLLECTED (vt_group_wait, vt_group_wait_next, a synchronous call; a pipelined pass still outstanding does not show
+ * yet), its counters evaluated and gated (the device's), the period and the gate per mille.
+ * "anchor" [Nt,Kpad]: the rows the stream's probes are compared with. "probe" [Nt,Kpad]: the rows of the stream's last cut
+ * probe - valid where the record's status is 1 or 3, stale otherwise, and the record says which. Each of the three returns
+ * VT_ERR_INVALID_ARG on an engine that never enabled the appearance check.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

@@ -138,6 +138,14 @@ int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result*
 int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams, const int32_t* policy, const vt_result* results,
                        const int32_t* slot_stream, const int32_t* winner, const vt_candidate* cands, int n, int stages,
                        void* host_states, void* host_records);
+/* The score launch of the appearance check (csrc/k_appearance.hip, the "appearance*" keys of vt_group_set_tuning in
+ * vittrack_hip.h) on caller-supplied rows, and nothing else. anchor, probe: [n_slots][nt][kpad] bf16 bit patterns; the sums
+ * run over columns [0, cols) of every row, columns [cols, kpad) are never read. Per slot: sums[5] = Sa, Sp, Saa, Spp, Sap
+ * in binary64 (every element the exact value of its bf16, the kernel's fixed order of additions), similarity (binary32,
+ * clamped to [-1, 1]) and status (1, or 3 where a variance is not positive: similarity 0).
+ * n_slots > 1024, nt or kpad > 65536, kpad < cols: VT_ERR_INVALID_ARG. */
+int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t* probe, int n_slots, int nt, int kpad, int cols,
+                           double* sums, float* similarity, int32_t* status);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
