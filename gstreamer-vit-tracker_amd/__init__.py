@@ -160,7 +160,7 @@ OPS_EXPORTS = [
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
-    "vt_op_motion_prior", "vt_op_appearance_score",
+    "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals",
 ]
 
 
@@ -329,6 +329,9 @@ def ops_lib():
     L.vt_op_motion_prior.argtypes = [c_int, c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, POINTER(c_int32), POINTER(c_int32),
                                      c_void_p, c_int, c_int, c_void_p, c_void_p]
     L.vt_op_appearance_score.argtypes = [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.vt_op_proposals.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int,
+                                  c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_void_p,
                                        c_int, c_int]
     _ops = L
@@ -856,6 +859,13 @@ class VitTrack:
     def anchor(self) -> np.ndarray:
         return self.as_group().anchor(0)
 
+    def set_proposals(self, mode: int = 1, **keys) -> None:
+        """the reacquire proposals of this tracker's engine: see Group.set_proposals"""
+        self.as_group().set_proposals(mode, **keys)
+
+    def proposals(self) -> dict:
+        return self.as_group().proposals(0)
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -1168,22 +1178,34 @@ class Group:
         self._last_n = n
         return [TrackResult(out[i]) for i in range(n)], [int(win[i]) for i in range(n)]
 
-    def reacquire(self, stream: int, frame, box_wh=None, overlap_pct: int = 50, host: bool = False):
+    def reacquire(self, stream: int, frame, box_wh=None, overlap_pct: int = 50, host: bool = False, proposals: bool = False):
         """Look for a lost stream's target over the whole frame: the windows of scan_windows, in grid order, in candidate
         passes of `streams` slots each; stops at the first chunk whose winner succeeds and returns that result, or the
         last chunk's winner if none does. box_wh: the (w, h) of the candidate boxes, default the size of the stream's
         state box. Each chunk is one update of the stream. frame: a CFrame of device memory, or with host=True a host
-        frame object. `last_scan` keeps every chunk's (results, winners) for inspection."""
+        frame object. `last_scan` keeps every chunk's (results, winners) for inspection.
+        proposals=True (a proposals-capable engine, set_proposals): first ONE candidate pass over the boxes the stream's
+        record lists - written by its last device pass, the failed update as a rule - and the scan only if there are none
+        or that pass's winner fails too. `last_proposal_pass` keeps its (results, winners), None if none ran."""
+        self.last_scan = []
+        self.last_proposal_pass = None
+        fn = self.update_host_candidates if host else self.update_device_candidates
+        if proposals:
+            rec = self.proposals(stream)
+            listed = [p["box"] for p in rec["proposals"]][:self.streams] if rec["status"] == 1 else []
+            if listed:
+                res, win = fn([(stream, b) for b in listed], [frame] * len(listed))
+                self.last_proposal_pass = (res, win)
+                if res[win[0]].success:
+                    return res[win[0]]
         if box_wh is None:
             box_wh = self.read_state(stream)["box"][2:4]
         cf = self._host_frame(frame)[0] if host else frame
         boxes = scan_windows(cf.width, cf.height, float(box_wh[0]), float(box_wh[1]), overlap_pct)
         step, best = self.streams, None
-        self.last_scan = []
         for c0 in range(0, len(boxes), step):
             chunk = boxes[c0:c0 + step]
             cands = [(stream, b) for b in chunk]
-            fn = self.update_host_candidates if host else self.update_device_candidates
             res, win = fn(cands, [frame] * len(chunk))
             self.last_scan.append((res, win))
             best = res[win[0]]
@@ -1407,6 +1429,57 @@ class Group:
     def probe(self, stream: int = 0) -> np.ndarray:
         """vt_group_read_tensor "probe": the rows of the stream's last cut probe (valid where the record's status is 1 or 3)"""
         return self.read_tensor("probe", stream)
+
+    def set_proposals(self, mode: int = 1, period: int | None = None, max_n: int | None = None, min_sim: float | None = None,
+                      max_cells: int | None = None) -> None:
+        """the "proposals*" keys of vt_group_set_tuning: behind the decode of every device pass the engine slides each due
+        stream's own template, pooled to an M x M pattern, over a coarse thumbnail of the whole frame and lists the best
+        places as boxes of the stream's size (proposals()). mode 0 off, 1 streams whose update failed, 2 every update;
+        period (1..1,000,000): due when frames_done % period == 0; max_n (1..8) proposals listed; min_sim (0..1, stored
+        per mille): the least similarity listed; max_cells (16,384..4,194,304): thumbnail cells per slot, before the first
+        enable only. None keeps a value. The first non-zero mode makes the engine proposals-capable (graphs recaptured, four
+        more launches per pass from then on). Refused while a pipelined pass is outstanding."""
+        if max_cells is not None:
+            self.set_tuning("proposals_max_cells", int(max_cells))
+        if period is not None:
+            if int(period) < 0:
+                raise ValueError(f"proposals_period: {period}")
+            self.set_tuning("proposals_period", int(period))
+        if max_n is not None:
+            if int(max_n) < 0:
+                raise ValueError(f"proposals_max: {max_n}")
+            self.set_tuning("proposals_max", int(max_n))
+        if min_sim is not None:
+            if not 0.0 <= float(min_sim) <= 1.0:
+                raise ValueError(f"proposals min_sim: {min_sim}")
+            self.set_tuning("proposals_min_sim_pm", int(round(float(min_sim) * 1000.0)))
+        self.set_tuning("proposals", int(mode))
+
+    def proposals(self, stream: int = 0) -> dict:
+        """vt_group_read_tensor "proposals": the policy (mode, period, max_n, min_sim_pm, max_cells), the stream's record of
+        its last collected pass - status (0 not due, 1 evaluated, 2 the grid is larger than max_cells or smaller than the
+        pattern, 3 a flat pattern, 4 no whole device frame), frames_done, c (cell side in pixels), grid (Wg, Hg) and the
+        listed proposals, best first: dict(sim, box (x, y, w, h floats), pos) - and the counter `evaluated`"""
+        v = self.read_tensor("proposals", stream)
+        n = int(v[3])
+        props = [dict(sim=float(v[12 + 6 * k]), box=tuple(float(x) for x in v[13 + 6 * k:17 + 6 * k]), pos=int(v[17 + 6 * k]))
+                 for k in range(n)]
+        return dict(mode=int(v[0]), status=int(v[1]), frames_done=int(v[2]), n=n, c=float(v[4]), grid=(int(v[5]), int(v[6])),
+                    evaluated=int(v[7]), period=int(v[8]), max_n=int(v[9]), min_sim_pm=int(v[10]), max_cells=int(v[11]),
+                    proposals=props)
+
+    def proposals_pattern(self, stream: int = 0) -> np.ndarray:
+        """vt_group_read_tensor "proposals_pattern": the [M, M] pattern (integers in floats) the stream's last pass pooled"""
+        v = self.read_tensor("proposals_pattern", stream)
+        m = int(round(len(v) ** 0.5))
+        return v.reshape(m, m)
+
+    def proposals_map(self, stream: int = 0) -> np.ndarray:
+        """vt_group_read_tensor "proposals_map": the [Hg - M + 1, Wg - M + 1] similarity map of the stream's last pass"""
+        wg, hg = self.proposals(stream)["grid"]
+        v = self.read_tensor("proposals_map", stream)
+        m = self.proposals_pattern(stream).shape[0]
+        return v.reshape(hg - m + 1, wg - m + 1)
 
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
@@ -1723,6 +1796,47 @@ def op_appearance_score(anchor, probe, cols, device=0):
     vp = lambda x: x.ctypes.data_as(c_void_p)
     _check_op(ops_lib().vt_op_appearance_score(device, vp(a), vp(p), n, nt, kpad, int(cols), vp(sums), vp(sim), vp(status)))
     return dict(sums=sums, similarity=sim, status=status)
+
+
+# the 224-byte record of the reacquire proposals (csrc/vt_common.hpp: PropRec)
+PROPOSAL_DTYPE = np.dtype([("sim", "<f4"), ("box", "<f4", 4), ("pos", "<i4")])
+PROPOSALS_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n", "<i4"), ("c", "<f4"), ("Wg", "<i4"), ("Hg", "<i4"),
+                                ("reserved", "<i4", 2), ("p", PROPOSAL_DTYPE, 8)])
+
+
+def op_proposals(frames, states, results, tpl, T, patch, norm, mode=2, period=1, max_n=4, min_sim_pm=500, max_cells=16384,
+                 slot_stream=None, winner=None, tpl_bufs=1, device_frames=True, evaluated=None, device=0):
+    """vt_op_proposals: the four launches of k_proposals.hip on given operands, nothing else. frames: CFrame per slot with
+    DEVICE planes; states: snapshot.STATE records by stream; results [n] RESULT_DTYPE by slot; tpl [n_streams, tpl_bufs,
+    nt, kpad] uint16 bf16 bit patterns; norm: (a0, a1, a2, b0, b1, b2). -> dict(pattern [n, 256] int16, thumb [n, max_cells]
+    int16, map [n, max_cells] float32, records [n_streams] PROPOSALS_REC_DTYPE, evaluated [n_streams] int32); what no
+    launch stored is 0xff bytes"""
+    from .snapshot import STATE
+    n = len(frames)
+    arr = (CFrame * n)(*frames)
+    st = np.ascontiguousarray(states, STATE).reshape(-1)
+    ns = len(st)
+    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+    assert res.shape == (n,)
+    t = np.ascontiguousarray(tpl, np.uint16)
+    kpad = t.shape[-1]
+    assert t.size == ns * tpl_bufs * (T // patch) ** 2 * kpad
+    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
+    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
+    nrm = np.ascontiguousarray(norm, np.float32).reshape(6)
+    pol = np.array([mode, period, max_n, min_sim_pm, 0, max_cells, 0, 0], np.int32)
+    pattern = np.empty((n, 256), np.int16)
+    thumb = np.empty((n, max_cells), np.int16)
+    smap_out = np.empty((n, max_cells), np.float32)
+    recs = np.empty(ns, PROPOSALS_REC_DTYPE)
+    ev = np.zeros(ns, np.int32) if evaluated is None else np.ascontiguousarray(evaluated, np.int32).copy()
+    vp = lambda x: x.ctypes.data_as(c_void_p)
+    i32 = POINTER(c_int32)
+    _check_op(ops_lib().vt_op_proposals(
+        device, arr, vp(st), ns, vp(res), smap.ctypes.data_as(i32) if smap is not None else None,
+        win.ctypes.data_as(i32) if win is not None else None, n, vp(t), tpl_bufs, T, patch, kpad, vp(nrm), vp(pol),
+        1 if device_frames else 0, vp(pattern), vp(thumb), vp(smap_out), vp(recs), vp(ev)))
+    return dict(pattern=pattern, thumb=thumb, map=smap_out, records=recs, evaluated=ev)
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)

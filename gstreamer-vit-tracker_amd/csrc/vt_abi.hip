@@ -377,6 +377,7 @@ int vt_group_set_tuning(vt_group* g, const char* key, int value) try {
     if (Engine::overlay_key(k)) return e->set_overlay(k, value);    // engine options: the passes are captured again by the first enable only
     if (Engine::motion_key(k)) return e->set_motion(k, value);
     if (Engine::appearance_key(k)) return e->set_appearance(k, value);
+    if (Engine::proposals_key(k)) return e->set_proposals(k, value);
     if (k == "head_band") e->head_band_kernel = value < 0 ? 2 : value;   // 0 / 1 / 2, see Engine::head_band_kernel
     else if (k == "last_rows") e->last_rows = value != 0;        // 0: the last block runs all rows; else (default) the search rows where eligible
     else if (k == "crop_tier") e->crop_tier_forced = value;      // < 0: chosen per pass from the known boxes (default)
@@ -511,6 +512,30 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
     if (n == "anchor" || n == "probe") {    // by stream: the rows the stream is compared with / the rows of its last cut probe
         if (!e->appear_capable) return e->appearance_stats(stream, nullptr);
         return copy_out_bf16(n == "anchor" ? e->d_anchor(stream) : e->d_probe(stream), (int64_t)d.nt * d.kpad, out, capacity);
+    }
+    if (n == "proposals") {             // by stream, whatever the last pass was: the policy, the stream's record and counter
+        if (!out) return e->prop_capable ? VT_PROP_STATS : e->proposals_stats(stream, nullptr);
+        if (capacity < VT_PROP_STATS) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        if (int rc = e->proposals_stats(stream, out)) return rc;
+        return VT_PROP_STATS;
+    }
+    if (n == "proposals_pattern" || n == "proposals_map") {     // of the stream's slot in the last pass, as its header says
+        if (!e->prop_capable) return e->proposals_stats(stream, nullptr);
+        const int slot = e->slot_of(stream);
+        if (slot < 0) return set_err(VT_ERR_INVALID_ARG, "read_tensor: stream %d was not in the last pass", stream);
+        PropHead h{};
+        HIPCHK(hipMemcpy(&h, e->d_prop_heads() + slot, sizeof(h), hipMemcpyDeviceToHost));
+        const bool pat = n == "proposals_pattern";
+        if (h.status != 1 && !(pat && h.status == 3))
+            return set_err(VT_ERR_INVALID_ARG, "read_tensor: '%s': the last pass did not evaluate stream %d (status %d)", name, stream, (int)h.status);
+        const int64_t count = pat ? (int64_t)h.M * h.M : (int64_t)(h.Wg - h.M + 1) * (h.Hg - h.M + 1);
+        if (!out) return count;
+        if (capacity < count) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity %lld < %lld", (long long)capacity, (long long)count);
+        if (!pat) return copy_out_f32(e->d_prop_map() + (size_t)slot * e->prop_policy.max_cells, count, out, capacity);
+        int16_t q[VT_PROP_M_MAX * VT_PROP_M_MAX];
+        HIPCHK(hipMemcpy(q, e->d_prop_pattern() + (size_t)slot * (VT_PROP_M_MAX * VT_PROP_M_MAX), sizeof(int16_t) * (size_t)count, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < count; ++i) out[i] = (float)q[i];
+        return count;
     }
     // every tensor but the stream's state and the replay counters belongs to the last pass: the stream's slot in it
     size_t b = (size_t)stream;

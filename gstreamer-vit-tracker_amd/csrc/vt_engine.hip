@@ -37,7 +37,7 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay, d_motion, d_appear};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay, d_motion, d_appear, d_prop};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
     for (void* p : devp)
         if (p) (void)hipFree(p);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
@@ -595,6 +595,16 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         L("appearance_score", 10.0 * n * d.nt * cols, 4.0 * n * d.nt * cols,
           [&] { return launch_appearance_score(aa, d.nt, cols, d.kpad, stream); });
     }
+    if (prop_capable) {     // ahead of the refresh: the pattern is the template this pass ran on; ahead of the overlay: undrawn pixels
+        const PropArgs pa{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_prop_policy(),
+                          d_devflag(), d_tpl, tpl_bufs(), d_prop_recs(), d_prop_counts(), d_prop_heads(), d_prop_pattern(),
+                          d_prop_thumb(), d_prop_map(), (const PassOut*)(d_frames + B), prop_policy.max_cells, n};
+        L("proposals_prepare", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + sizeof(PropHead)),
+          [&] { return launch_proposals_prepare(pa, d, stream); });
+        L("proposals_thumb", 0, 0, [&] { return launch_proposals_thumb(pa, d, ps.any_layout, stream); });
+        L("proposals_match", 0, 0, [&] { return launch_proposals_match(pa, stream); });
+        L("proposals_list", 0, (double)n * 2.0 * sizeof(PropRec), [&] { return launch_proposals_list(pa, stream); });
+    }
     if (refresh_capable) {  // the streams' policies, on what the decode (the commit) left: k_refresh.hip
         RefreshArgs ra{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_policy,
                        d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
@@ -789,6 +799,10 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     HIPCHK(hipMemcpyAsync(tpl_init_rows(b), d_patches + (size_t)b * d.ntok * d.kpad,
                           sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
     HIPCHK(anchor_from_template(b, 0));     // the appearance anchor: the init's rows (buffer 0)
+    if (prop_capable) {     // the proposals a record lists belong to the target the stream had
+        HIPCHK(hipMemsetAsync(d_prop_recs() + b, 0, sizeof(PropRec), stream));
+        h_prop_all[b] = PropRec{};          // the stream is in no outstanding pass: nothing else writes its entry
+    }
     return VT_OK;
 }
 
@@ -857,7 +871,7 @@ int Engine::build_block(const int32_t* map, const vt_frame* frames, int n, const
     const PassOut& to = sinks ? *sinks : own;
     *(PassOut*)(hf + B) = PassOut{to.host_results, by_stream_states ? to.host_states : nullptr,
                                   peaks_capable ? to.host_peaks : nullptr, motion_capable ? to.host_motion : nullptr,
-                                  appear_capable ? to.host_appearance : nullptr};
+                                  appear_capable ? to.host_appearance : nullptr, prop_capable ? to.host_proposals : nullptr};
     if (map) std::copy(map, map + n, (int32_t*)((char*)hf + map_offset()));
     *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
@@ -978,6 +992,7 @@ hipError_t Engine::sinks_alloc(PassOut* o, unsigned members) const {
     if (e == hipSuccess && (members & SINK_PEAKS)) e = pinned0(&o->host_peaks, (size_t)B);
     if (e == hipSuccess && (members & SINK_MOTION)) e = pinned0(&o->host_motion, (size_t)B);
     if (e == hipSuccess && (members & SINK_APPEAR)) e = pinned0(&o->host_appearance, (size_t)B);
+    if (e == hipSuccess && (members & SINK_PROP)) e = pinned0(&o->host_proposals, (size_t)B);
     return e;
 }
 
@@ -987,6 +1002,7 @@ void Engine::sinks_free(PassOut* o, unsigned members) const {
     if (members & SINK_PEAKS) drop(&o->host_peaks);
     if (members & SINK_MOTION) drop(&o->host_motion);
     if (members & SINK_APPEAR) drop(&o->host_appearance);
+    if (members & SINK_PROP) drop(&o->host_proposals);
 }
 
 // ---- template refresh --------------------------------------------------------------------------------
@@ -1470,6 +1486,92 @@ int Engine::appearance_stats(int s, float* out8) {
     HIPCHK(hipMemcpy(&c, d_appear_counts() + s, sizeof(c), hipMemcpyDeviceToHost));
     out8[0] = (float)appear_policy.on; out8[1] = (float)r.status; out8[2] = r.similarity; out8[3] = (float)r.frames_done;
     out8[4] = (float)c.evaluated; out8[5] = (float)c.gated; out8[6] = (float)appear_policy.period; out8[7] = (float)appear_policy.gate_pm;
+    return VT_OK;
+}
+
+// ---- reacquire proposals ------------------------------------------------------------------------------
+
+// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "proposals" is the enable
+// (enable_feature): the store and the pinned mirrors, sized by the max_cells of that moment. Every later change is one
+// small copy: the passes read the record.
+int Engine::set_proposals(const std::string& key, int value) {
+    PropPolicy p = prop_policy;
+    const PropPolicy def = VT_PROP_DEFAULT_POLICY;
+    if (key == "proposals") {
+        p.mode = value < 0 ? def.mode : value;
+        if (p.mode > 2) return set_err(VT_ERR_INVALID_ARG, "proposals: %d (0: off, 1: failed updates, 2: every update)", value);
+    } else if (key == "proposals_period") {
+        p.period = value < 0 ? def.period : value;
+        if (p.period < 1 || p.period > VT_PROP_MAX_PERIOD)
+            return set_err(VT_ERR_INVALID_ARG, "proposals_period: %d (1..%d)", value, VT_PROP_MAX_PERIOD);
+    } else if (key == "proposals_max") {
+        p.max_n = value < 0 ? def.max_n : value;
+        if (p.max_n < 1 || p.max_n > VT_PROP_MAX) return set_err(VT_ERR_INVALID_ARG, "proposals_max: %d (1..%d)", value, VT_PROP_MAX);
+    } else if (key == "proposals_min_sim_pm") {
+        p.min_sim_pm = value < 0 ? def.min_sim_pm : value;
+        if (p.min_sim_pm > 1000) return set_err(VT_ERR_INVALID_ARG, "proposals_min_sim_pm: %d (0..1000)", value);
+        p.tau = (float)p.min_sim_pm / 1000.0f;
+    } else if (key == "proposals_max_cells") {
+        if (prop_capable)
+            return set_err(VT_ERR_INVALID_ARG, "proposals_max_cells: fixed by the first enable of \"proposals\" (%d)", prop_policy.max_cells);
+        p.max_cells = value < 0 ? def.max_cells : value;
+        if (p.max_cells < VT_PROP_MIN_CELLS || p.max_cells > VT_PROP_MAX_CELLS)
+            return set_err(VT_ERR_INVALID_ARG, "proposals_max_cells: %d (%d..%d)", value, VT_PROP_MIN_CELLS, VT_PROP_MAX_CELLS);
+    } else {
+        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
+    }
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!prop_capable && p.mode != 0) {
+        if (prop_pattern_side(d.T) == 0)
+            return set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", d.T);
+        uint8_t* store = nullptr;       // all zero but the policy; the thumbnails and maps are written before they are read
+        PassOut own{};                  // the engine's own mirror
+        const PropPolicy before = prop_policy;
+        const size_t bytes = prop_bytes_of(p.max_cells);
+        auto alloc = [&] {
+            hipError_t he = hipMalloc((void**)&store, bytes);
+            if (he == hipSuccess) he = hipMemsetAsync(store, 0, prop_off_thumb(), stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
+            if (he == hipSuccess) he = sinks_alloc(&own, SINK_PROP);
+            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
+                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_PROP);
+            return he;
+        };
+        auto install = [&] { d_prop = store; h_prop_all = own.host_proposals; prop_policy = p; prop_capable = true; };
+        auto uninstall = [&] {
+            (void)hipFree(store);       // null: no operation
+            sinks_free(&own, SINK_PROP);
+            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_PROP);
+            d_prop = nullptr; h_prop_all = nullptr; prop_policy = before;
+            prop_capable = false;
+        };
+        if (int rc = enable_feature({"reacquire proposals", bytes, alloc, install, uninstall})) return rc;
+    } else if (prop_capable) {
+        HIPCHK(hipMemcpy(d_prop_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
+    }
+    prop_policy = p;
+    return VT_OK;
+}
+
+// [VT_PROP_STATS]: mode, status, frames_done, n, c, Wg, Hg, evaluated, period, max, min_sim_pm, max_cells, then per
+// proposal sim, box[4], position
+int Engine::proposals_stats(int s, float* out) {
+    if (!prop_capable)
+        return set_err(VT_ERR_INVALID_ARG, "reacquire proposals: not enabled on this engine (vt_group_set_tuning \"proposals\")");
+    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counter: the device's
+    const PropRec r = h_prop_all[s];
+    int32_t ev = 0;
+    HIPCHK(hipMemcpy(&ev, d_prop_counts() + s, sizeof(ev), hipMemcpyDeviceToHost));
+    out[0] = (float)prop_policy.mode; out[1] = (float)r.status; out[2] = (float)r.frames_done; out[3] = (float)r.n;
+    out[4] = r.c; out[5] = (float)r.Wg; out[6] = (float)r.Hg; out[7] = (float)ev;
+    out[8] = (float)prop_policy.period; out[9] = (float)prop_policy.max_n; out[10] = (float)prop_policy.min_sim_pm;
+    out[11] = (float)prop_policy.max_cells;
+    for (int k = 0; k < VT_PROP_MAX; ++k) {
+        float* o = out + 12 + 6 * k;
+        o[0] = r.p[k].sim; o[1] = r.p[k].box[0]; o[2] = r.p[k].box[1]; o[3] = r.p[k].box[2]; o[4] = r.p[k].box[3];
+        o[5] = (float)r.p[k].pos;
+    }
     return VT_OK;
 }
 

@@ -225,7 +225,7 @@ struct Engine {
     size_t feature_bytes() const {
         return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0) +
                (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0) +
-               (motion_capable ? motion_bytes() : 0) + (appear_capable ? appear_bytes() : 0);
+               (motion_capable ? motion_bytes() : 0) + (appear_capable ? appear_bytes() : 0) + (prop_capable ? prop_bytes() : 0);
     }
     int enable_chips(int size, int kind, const float* na, const float* nb);   // enable_feature: the store
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
@@ -313,6 +313,38 @@ struct Engine {
     // stream b's anchor <- its current template rows (buffer gen & 1 of a refresh-capable engine's store), its record
     // zeroed; behind the stream's work. init, queued init, import, copy, the "appearance_anchor" action
     hipError_t anchor_from_template(int b, int gen);
+    // reacquire proposals (k_proposals.hip). ONE policy per engine; per stream a record and a counter, per slot the working
+    // set of the four launches. The first non-zero "proposals" allocates all of it with the max_cells of that moment and
+    // makes the engine proposals-capable for good: every pass runs the four launches behind its decode (its commit,
+    // motion_settle, the appearance launches), ahead of the refresh launch. Keys set before that are kept in prop_policy
+    // and go up with the enable.
+    bool prop_capable = false;
+    PropPolicy prop_policy = VT_PROP_DEFAULT_POLICY;            // the host's copy
+    // ONE allocation: the policy | [B] counters | [B] records | [B] headers | [B] patterns | [B][max_cells] thumbnails
+    // (int16) | [B][max_cells] maps (float)
+    uint8_t* d_prop = nullptr;
+    static size_t prop_off_counts() { return 64; }
+    size_t prop_off_recs() const { return (prop_off_counts() + sizeof(int32_t) * (size_t)B + 63) & ~(size_t)63; }
+    size_t prop_off_heads() const { return prop_off_recs() + sizeof(PropRec) * (size_t)B; }
+    size_t prop_off_pattern() const { return (prop_off_heads() + sizeof(PropHead) * (size_t)B + 63) & ~(size_t)63; }
+    size_t prop_off_thumb() const { return prop_off_pattern() + sizeof(int16_t) * VT_PROP_M_MAX * VT_PROP_M_MAX * (size_t)B; }
+    size_t prop_off_map(int max_cells) const { return prop_off_thumb() + sizeof(int16_t) * (size_t)max_cells * (size_t)B; }
+    size_t prop_bytes_of(int max_cells) const { return prop_off_map(max_cells) + sizeof(float) * (size_t)max_cells * (size_t)B; }
+    size_t prop_bytes() const { return prop_bytes_of(prop_policy.max_cells); }
+    PropPolicy* d_prop_policy() const { return reinterpret_cast<PropPolicy*>(d_prop); }
+    int32_t* d_prop_counts() const { return reinterpret_cast<int32_t*>(d_prop + prop_off_counts()); }
+    PropRec* d_prop_recs() const { return reinterpret_cast<PropRec*>(d_prop + prop_off_recs()); }
+    PropHead* d_prop_heads() const { return reinterpret_cast<PropHead*>(d_prop + prop_off_heads()); }
+    int16_t* d_prop_pattern() const { return reinterpret_cast<int16_t*>(d_prop + prop_off_pattern()); }
+    int16_t* d_prop_thumb() const { return reinterpret_cast<int16_t*>(d_prop + prop_off_thumb()); }
+    float* d_prop_map() const { return reinterpret_cast<float*>(d_prop + prop_off_map(prop_policy.max_cells)); }
+    // pinned [B] by stream: the records of the last passes the host collected - what "proposals" of vt_group_read_tensor
+    // reports (the list launch stores to the pass's sink; adopt_slot copies a collected pipelined pass's entries here)
+    PropRec* h_prop_all = nullptr;
+    static bool proposals_key(const std::string& key) { return key.rfind("proposals", 0) == 0; }
+    int set_proposals(const std::string& key, int value);   // the keys of vt_group_set_tuning; the first enable is in here
+#define VT_PROP_STATS 60    // floats of "proposals": 12 + VT_PROP_MAX * 6
+    int proposals_stats(int stream, float* out60);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -361,14 +393,15 @@ struct Engine {
     vt_result* h_results = nullptr;
     StreamState* h_state = nullptr;
     // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
-    // slot, states, motion and appearance records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
-    // h_motion_all and h_appear_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
+    // slot, states, motion, appearance and proposal records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
+    // h_motion_all, h_appear_all and h_prop_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
     // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them.
-    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_ALL = 15 };
+    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_ALL = 31 };
     unsigned sink_members() const {
-        return SINK_BASE | (peaks_capable ? SINK_PEAKS : 0u) | (motion_capable ? SINK_MOTION : 0u) | (appear_capable ? SINK_APPEAR : 0u);
+        return SINK_BASE | (peaks_capable ? SINK_PEAKS : 0u) | (motion_capable ? SINK_MOTION : 0u) | (appear_capable ? SINK_APPEAR : 0u) |
+               (prop_capable ? SINK_PROP : 0u);
     }
-    PassOut own_sinks() const { return {h_results, h_states_all, h_peaks, h_motion_all, h_appear_all}; }
+    PassOut own_sinks() const { return {h_results, h_states_all, h_peaks, h_motion_all, h_appear_all, h_prop_all}; }
     hipError_t sinks_alloc(PassOut* o, unsigned members) const;
     void sinks_free(PassOut* o, unsigned members) const;
     // graph

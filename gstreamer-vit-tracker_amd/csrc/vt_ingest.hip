@@ -287,6 +287,7 @@ static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
         e->h_states_all[s] = sl.out.host_states[s];        // the engine's own mirrors follow
         if (e->motion_capable && sl.out.host_motion) e->known_motion[(size_t)s] = e->h_motion_all[s] = sl.out.host_motion[s];
         if (e->appear_capable && sl.out.host_appearance) e->h_appear_all[s] = sl.out.host_appearance[s];
+        if (e->prop_capable && sl.out.host_proposals) e->h_prop_all[s] = sl.out.host_proposals[s];
         e->h_results[i] = sl.out.host_results[i];
     }
     adopt_peaks(e, sl);                         // the peak records are by slot, like the results

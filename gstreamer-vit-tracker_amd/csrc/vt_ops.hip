@@ -1021,4 +1021,93 @@ int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The four launches of the reacquire proposals on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_proposals_prepare, _thumb, _match and _list, in that order. Pattern, thumbnail, map and records each sit between
+// guard bands and start as 0xff bytes: what a slot that is not due leaves untouched comes back as 0xff.
+int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, int n_streams, const vt_result* results,
+                    const int32_t* slot_stream, const int32_t* winner, int n, const uint16_t* tpl, int tpl_bufs, int T, int patch,
+                    int kpad, const float* norm, const int32_t* policy, int device_frames, int16_t* pattern, int16_t* thumb,
+                    float* map, void* records, int32_t* evaluated) try {
+    if (!frames || !states || !results || !tpl || !norm || !policy || !pattern || !thumb || !map || !records || !evaluated || n < 1 ||
+        n > VT_MAX_STREAMS || n_streams < 1 || n_streams > VT_MAX_STREAMS || patch < 1 || T < patch || T % patch != 0 ||
+        kpad < 3 * patch * patch || kpad > 65536 || (tpl_bufs != 1 && tpl_bufs != 2))
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (prop_pattern_side(T) == 0) return set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", T);
+    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "proposals: %d streams for %d slots", n_streams, n);
+    PropPolicy pol;
+    memcpy(&pol, policy, sizeof(pol));
+    if (pol.mode < 0 || pol.mode > 2 || pol.period < 1 || pol.period > VT_PROP_MAX_PERIOD || pol.max_n < 1 || pol.max_n > VT_PROP_MAX ||
+        pol.min_sim_pm < 0 || pol.min_sim_pm > 1000 || pol.max_cells < VT_PROP_M_MAX * VT_PROP_M_MAX || pol.max_cells > VT_PROP_MAX_CELLS)
+        return set_err(VT_ERR_INVALID_ARG, "proposals: policy out of range");
+    pol.tau = (float)pol.min_sim_pm / 1000.0f;
+    std::vector<FrameDesc> desc((size_t)n);
+    for (int b = 0; b < n; ++b) {
+        if (int rc = check_frame(frames[b])) return rc;
+        to_desc(frames[b], &desc[(size_t)b]);
+        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_streams))
+            return set_err(VT_ERR_INVALID_ARG, "proposals: slot %d names stream %d of %d", b, (int)slot_stream[b], n_streams);
+        if (winner && (winner[b] < 0 || winner[b] >= n))
+            return set_err(VT_ERR_INVALID_ARG, "proposals: winner[%d] = %d of %d slots", b, (int)winner[b], n);
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    ModelDims d{};
+    d.T = T; d.patch = patch; d.gt = T / patch; d.nt = d.gt * d.gt; d.kpad = kpad;
+    for (int c = 0; c < 3; ++c) { d.norm_a[c] = norm[c]; d.norm_b[c] = norm[3 + c]; }
+    const size_t ns = (size_t)n, mc = (size_t)pol.max_cells, pm = VT_PROP_M_MAX * VT_PROP_M_MAX;
+    const size_t tpl_b = (size_t)n_streams * tpl_bufs * d.nt * kpad * sizeof(bf16_t);
+    DevBuf dfr, dst, dres, dmap, dwin, dpol, dflag, dtpl, dcnt, dhead, dpo;
+    GuardedOut gpat, gth, gmap, grec;
+    HIPCHK(dfr.alloc(ns * sizeof(FrameDesc))); HIPCHK(dst.alloc((size_t)n_streams * sizeof(StreamState)));
+    HIPCHK(dres.alloc(ns * sizeof(vt_result))); HIPCHK(dpol.alloc(sizeof(pol))); HIPCHK(dflag.alloc(4)); HIPCHK(dtpl.alloc(tpl_b));
+    HIPCHK(dcnt.alloc((size_t)n_streams * 4)); HIPCHK(dhead.alloc(ns * sizeof(PropHead))); HIPCHK(dpo.alloc(sizeof(PassOut)));
+    HIPCHK(gpat.alloc(ns * pm * sizeof(int16_t))); HIPCHK(gth.alloc(ns * mc * sizeof(int16_t))); HIPCHK(gmap.alloc(ns * mc * sizeof(float)));
+    HIPCHK(grec.alloc((size_t)n_streams * sizeof(PropRec)));
+    HIPCHK(hipMemcpy(dfr.p, desc.data(), ns * sizeof(FrameDesc), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dst.p, states, (size_t)n_streams * sizeof(StreamState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dres.p, results, ns * sizeof(vt_result), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
+    const int32_t flag = device_frames != 0;
+    HIPCHK(hipMemcpy(dflag.p, &flag, 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtpl.p, tpl, tpl_b, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dcnt.p, evaluated, (size_t)n_streams * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dhead.p, 0, ns * sizeof(PropHead)));
+    const PassOut po{};
+    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
+    if (slot_stream) {
+        HIPCHK(dmap.alloc(ns * 4));
+        HIPCHK(hipMemcpy(dmap.p, slot_stream, ns * 4, hipMemcpyHostToDevice));
+    }
+    if (winner) {
+        HIPCHK(dwin.alloc(ns * 4));
+        HIPCHK(hipMemcpy(dwin.p, winner, ns * 4, hipMemcpyHostToDevice));
+    }
+    const PropArgs pa{(const FrameDesc*)dfr.p, (const StreamState*)dst.p, (const vt_result*)dres.p,
+                      slot_stream ? (const int32_t*)dmap.p : nullptr, winner ? (const int32_t*)dwin.p : nullptr,
+                      (const PropPolicy*)dpol.p, (const int32_t*)dflag.p, (const bf16_t*)dtpl.p, tpl_bufs, (PropRec*)grec.out(),
+                      (int32_t*)dcnt.p, (PropHead*)dhead.p, (int16_t*)gpat.out(), (int16_t*)gth.out(), (float*)gmap.out(),
+                      (const PassOut*)dpo.p, pol.max_cells, n};
+    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(launch_proposals_prepare(pa, d, nullptr));
+    int level = 0;
+    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
+    HIPCHK(launch_proposals_thumb(pa, d, level, nullptr));
+    HIPCHK(launch_proposals_match(pa, nullptr));
+    HIPCHK(launch_proposals_list(pa, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    const GuardedOut* outs[] = {&gpat, &gth, &gmap, &grec};
+    const char* const names[] = {"pattern", "thumbnail", "map", "records"};
+    for (int k = 0; k < 4; ++k) {
+        long where = 0;
+        HIPCHK(outs[k]->check(&where));
+        if (where) return set_err(VT_ERR_HIP, "proposals wrote outside its %s: guard byte %ld changed", names[k], where);
+    }
+    HIPCHK(hipMemcpy(pattern, gpat.out(), gpat.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(thumb, gth.out(), gth.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(map, gmap.out(), gmap.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(records, grec.out(), grec.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(evaluated, dcnt.p, (size_t)n_streams * 4, hipMemcpyDeviceToHost));
+    return VT_OK;
+} VT_NOTHROW_INT
+
 }  // extern "C"

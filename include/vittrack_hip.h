@@ -934,6 +934,68 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * plain one in that one state word (and a following refresh or chip of the same pass, seeing the miss, does not cut).
  *   Read-out: vt_group_read_tensor(g, stream, "appearance" / "anchor" / "probe", ...).
  *
+ * ENGINE OPTIONS - reacquire proposals (DESIGN.md section 3 "Reacquire proposals"). The engine can say that a target is lost,
+ * not where it went: peaks, motion prior and appearance check all work inside one search window. With this option every
+ * DEVICE pass slides each due stream's own template, pooled to an M x M pattern, over a coarse thumbnail of the WHOLE frame
+ * and lists the best places as boxes of the stream's size - candidates for ONE vt_group_update_device_candidates pass in
+ * front of the vt_scan_windows scan. Keys, per engine; a negative value selects the default; a value outside its range
+ * returns VT_ERR_INVALID_ARG and changes nothing:
+ *   key                      value                                                                 default
+ *   "proposals"              0 = off, 1 = evaluate slots whose update failed, 2 = every update     0
+ *   "proposals_period"       1..1,000,000: due when frames_done % period == 0                      1
+ *   "proposals_max"          1..8 proposals listed                                                 4
+ *   "proposals_min_sim_pm"   0..1000 per mille; tau = (float)pm / 1000.0f                          500
+ *   "proposals_max_cells"    16,384..4,194,304 cells of thumbnail storage per slot; accepted only  262,144
+ *                            before the first enable, VT_ERR_INVALID_ARG afterwards
+ * Values set before the first enable are remembered. The first non-zero "proposals" makes the engine proposals-capable
+ * for good: per slot an int16 thumbnail and a float32 similarity map of max_cells each, a 16 x 16 int16 pattern and a
+ * header, per stream a record, a counter and the record's pinned mirror (6 bytes per cell and slot; VT_ERR_OOM under
+ * vt_config.max_device_mib or when the device is full, and nothing changes; VT_ERR_INVALID_ARG where the model's template
+ * size is a multiple of neither 16 nor 14), the passes captured again in that call with four more launches behind the
+ * decode (the commit, motion_settle, the appearance launches), AHEAD of the refresh, chip, peaks and overlay launches.
+ * Later changes of any key are one small copy and capture nothing. No part of a snapshot.
+ *   THE RULE, to the bit. All arithmetic binary32 unless stated, one IEEE operation per source operation. Slot i of a
+ * pass, st the state of its stream as the pass left it, r = results[i], f its frame. The slot is DUE iff ALL of: (a)
+ * "proposals" != 0; (b) in a candidate pass, winner[i] == i; (c) mode 1: r.success == 0 (a NaN score fails), mode 2:
+ * always; (d) st.frames_done % period == 0. A slot that is not due has status 0. A due slot has status 4, with nothing
+ * evaluated, unless (e) the pass came through a device entry point (rule 2 of the result overlay: host-pointer passes, zero
+ * copy included, have only their windows on the device) and (f) its planes hold the whole frame: origin 0,0 and a stored
+ * extent equal to the frame's (vt_frame.windowed == 0, or a window that is the frame).
+ *   Geometry, (x, y, w, h) = st.box: s = sqrtf(w * h); M = 16 if template_size % 16 == 0, else 14; c = 2.0f * s / (float)M,
+ * the cell side in source pixels (the pattern is the WHOLE factor-2 template); the grid starts at X0 = Y0 =
+ * -(float)(M / 4) * c: a match window may hang a quarter of its side outside the frame, a target may touch the edge; Wg =
+ * (int)ceilf((float)frame_w / c) + M / 2, Hg likewise. Status 2, nothing evaluated, if c is not positive (a NaN too), if
+ * either quotient exceeds 4,194,304, if Wg * Hg > max_cells, or if Wg < M or Hg < M.
+ *   Thumbnail cell (i, j): sixteen sub-taps (u, v), u, v in 0..3, at px = (int)floorf(X0 + ((float)i + ((float)u + 0.5f) *
+ * 0.25f) * c), py alike with j and v; each is ONE pixel of the frame as the crop kernels read it (any vt_pixfmt /
+ * vt_pixfmt2), black outside the frame; g = (R * a0 + b0) + (G * a1 + b1) + (B * a2 + b2) with the blob's norm_a /
+ * norm_b; the cell is the sum of its 16 g, added in (v, u) order from 0.0f; Q = clamp(rintf(sum * (4096.0f / 48.0f)),
+ * -32767, 32767) as int16 (clamped in binary32: it saturates, it never wraps). A cell with ANY sub-tap outside the frame
+ * is OUTSIDE and stored as -32768, which no value clamps to: what is not in the picture is no evidence for or against a
+ * place, and such cells take part in no sum below (the cells of a frame edge that the frame only partly covers included).
+ *   Pattern cell: the (T / M)^2 pixels x 3 channels of its block of the stream's CURRENT template rows - what "template"
+ * returned before the pass: the template the pass ran on, the launches sit ahead of the refresh launch - each the exact
+ * value of its bf16, added in binary64 in ascending (y, x, channel) order, times 4096.0 / (3 (T / M)^2), rint, clamped
+ * to +-32767, int16. Status 3 if the WHOLE pattern is flat: M^2 Saa - Sa^2 == 0 over all its cells.
+ *   Similarity at every position (px, py), 0 <= px <= Wg - M, 0 <= py <= Hg - M, from EXACT int64 sums over those cells
+ * of the M x M window of the thumbnail that are not OUTSIDE, and over the pattern's cells at the same places: n their
+ * number (at least 9/16 of M^2 wherever the grid's overhang of M / 4 cells is all that leaves the frame), Sa, Saa the
+ * pattern's sums over them, Sp, Spp, Sap the window's; cov = n Sap - Sa Sp, va = n Saa - Sa^2, vp = n Spp - Sp^2 (all below
+ * 2^53); sim = (va > 0 && vp > 0) ? (double)cov / sqrt((double)va * (double)vp) : 0, clamped to [-1, 1], rounded once to
+ * binary32. A window wholly inside the frame uses the whole pattern. Integer sums: the result does not depend on any
+ * order of additions, and there is no floating-point atomic. (Comparing the overhang with black instead makes frame
+ * corners look like a dark ring around a brighter centre: 0.51 on the committed clip, where no other place exceeds 0.23.)
+ *   Listing: proposal k is the greatest sim among the positions not suppressed, the lowest py * (Wg - M + 1) + px on a
+ * tie; listed while k < proposals_max, sim >= tau and sim > 0; positions within Chebyshev distance M / 2 of a listed one
+ * are suppressed. Its box: (cx - 0.5f * w, cy - 0.5f * h, w, h), cx = X0 + (float)(px + M / 2) * c, cy alike.
+ *   Record, per stream, on the device and mirrored to pinned host memory like the appearance records: status, frames_done,
+ * n, c, Wg, Hg, and per proposal sim, box[4], position. Every pass of a capable engine writes the records of its streams
+ * (a candidate pass: at the winning slot; a redone pass again). A counter per stream counts the records written with
+ * status 1 or 3 (a diagnostic, never rewound). THE TWIN IDENTITY: the option only reads - an enabled engine equals a plain
+ * engine in results, state words, templates, chips, peaks and overlays, bit for bit, in every kind of pass; it marks no
+ * window miss and adds no redo.
+ *   Read-out: vt_group_read_tensor(g, stream, "proposals" / "proposals_pattern" / "proposals_map", ...).
+ *
  * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
@@ -992,6 +1054,12 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * "anchor" [Nt,Kpad]: the rows the stream's probes are compared with. "probe" [Nt,Kpad]: the rows of the stream's last cut
  * probe - valid where the record's status is 1 or 3, stale otherwise, and the record says which. Each of the three returns
  * VT_ERR_INVALID_ARG on an engine that never enabled the appearance check.
+ * "proposals" [60] (by STREAM, whatever the last pass was; see vt_group_set_tuning "proposals"): mode, then the stream's
+ * record as the pinned mirror holds it (that of its last COLLECTED pass) - status, frames_done, n, c, Wg, Hg -, the counter
+ * evaluated (the device's), period, max, min_sim_pm, max_cells, then 8 x (sim, x, y, w, h, position), zero behind the n
+ * listed. "proposals_pattern" [M,M] and "proposals_map" [Hg-M+1,Wg-M+1]: the pattern (integers) and the similarity map of
+ * the stream's slot in the LAST pass; VT_ERR_INVALID_ARG where that slot was not evaluated (the map: status 1; the pattern:
+ * 1 or 3). Each of the three returns VT_ERR_INVALID_ARG on an engine that never enabled the proposals.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

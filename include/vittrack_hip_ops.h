@@ -146,6 +146,21 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
  * n_slots > 1024, nt or kpad > 65536, kpad < cols: VT_ERR_INVALID_ARG. */
 int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t* probe, int n_slots, int nt, int kpad, int cols,
                            double* sums, float* similarity, int32_t* status);
+/* The four launches of the reacquire proposals (csrc/k_proposals.hip, the "proposals*" keys of vt_group_set_tuning in
+ * vittrack_hip.h) on caller-supplied operands, and nothing else. frames: [n] by slot with DEVICE planes (read only);
+ * states: [n_streams] raw 88-byte stream states, of which box, frames_done and tpl_gen are read; results: [n] by slot
+ * (success is read); slot_stream: [n] slot -> stream or null (the identity); winner: [n] a candidate pass's winner table
+ * or null; tpl: [n_streams][tpl_bufs][(T/patch)^2][kpad] bf16 bit patterns in the patch-row layout of the template rows
+ * (tpl_bufs 2: a stream's rows are buffer tpl_gen & 1); norm: a0, a1, a2, b0, b1, b2; policy: 8 int32 = mode, period, max,
+ * min_sim_pm, (tau: derived here), max_cells (256..4,194,304), 0, 0; device_frames: 0 = the launches of a host-pointer pass.
+ * Out: pattern [n][256] int16 (M x M at the front), thumb [n][max_cells] int16 (Hg x Wg at the front), map [n][max_cells]
+ * float ((Hg - M + 1) x (Wg - M + 1) at the front), records [n_streams] of 224 bytes (status, frames_done, n, c, Wg, Hg,
+ * 2 reserved words, 8 x (sim, box[4], position)), evaluated [n_streams] in and out. Every output byte no launch stored is
+ * 0xff. The four device outputs sit between guard bands; a changed guard byte is VT_ERR_HIP. */
+int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, int n_streams, const vt_result* results,
+                    const int32_t* slot_stream, const int32_t* winner, int n, const uint16_t* tpl, int tpl_bufs, int T, int patch,
+                    int kpad, const float* norm, const int32_t* policy, int device_frames, int16_t* pattern, int16_t* thumb,
+                    float* map, void* records, int32_t* evaluated);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
