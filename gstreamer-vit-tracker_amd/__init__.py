@@ -160,7 +160,7 @@ OPS_EXPORTS = [
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
-    "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals",
+    "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_ln_chain_bf16",
 ]
 
 
@@ -318,6 +318,8 @@ def ops_lib():
     L.vt_op_gemm_resid_seg_bf16.argtypes = [c_int, u16p, u16p, fp, u16p, i8p, c_int, u16p, i8p, fp, fp, c_int, c_int, c_int,
                                             c_int, c_int, c_float, c_int]
     L.vt_op_layernorm.argtypes = [c_int, fp, fp, fp, fp, c_int, c_int]
+    L.vt_op_ln_chain_bf16.argtypes = [c_int, fp, c_int, c_int, c_int, u16p, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, c_float,
+                                      c_int, c_int, fp, fp, u16p, i8p, fp, fp, u16p, fp, fp]
     L.vt_op_conv3x3_relu_bf16.argtypes = [c_int, u16p, u16p, fp, fp, c_int, c_int, c_int, c_int, c_int]
     L.vt_op_nv12_to_rgb8_bench.argtypes = [c_int, c_int, c_int, c_int, fp]
     L.vt_op_nv12_to_rgb8_batch_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, fp]
@@ -1596,6 +1598,42 @@ def op_gemm_bf16(a_bits, w_bits, bias, c_init=None, epilogue=0, device=0, cfg=-1
                                  _f32(rs) if rs is not None else None, _f32(cs) if cs is not None else None,
                                  _f32(ro) if ro is not None else None, eps, int(lo_shift)))
     return (c, ro) if want_rowstat else c
+
+
+def op_ln_chain_bf16(x, B, tokens, w_bits, gamma, beta, bias, consumer, route=0, producer_cfg=-1, consumer_cfg=-1,
+                     eps=1e-6, lo_shift=12, launches=1, device=0, check=True):
+    """vt_op_ln_chain_bf16: the folded LayerNorm as the engine runs it - X-epilogue producer on x [B * tokens, D], row terms
+    by route (0 finalize launch, 1 inside the 256x256 producer, 2 combined in the consumer), the fold of w_bits [N, D] /
+    gamma / beta / bias, then the consumer (2 GELU, 3 ReLU, 4 QKV; 0: the fold alone, x may be None). Returns a dict of
+    rc, out, vt, xh (uint16), xl (int8), cstat [M, D // 32, 2], rowstat [M, 2], wf (uint16), colsum, cvec; every array
+    starts as 0xff bytes, and stays so when the call is refused (check=False returns rc instead of raising)"""
+    w_bits = np.ascontiguousarray(w_bits, np.uint16)
+    N, D = w_bits.shape
+    g, be, bi = (np.ascontiguousarray(v, np.float32) for v in (gamma, beta, bias))
+    assert g.shape == (D,) and be.shape == (D,) and bi.shape == (N,)
+    M = B * tokens if consumer else 0
+    xx = None
+    if consumer:
+        xx = np.ascontiguousarray(x, np.float32)
+        assert xx.shape == (M, D)
+    npad = (tokens + 63) // 64 * 64
+    def ff(shape, dt):
+        return np.full(int(np.prod(shape)) * np.dtype(dt).itemsize, 0xff, np.uint8).view(dt).reshape(shape)
+    r = dict(out=ff((M, 2 * D if consumer == 4 else N), np.float32),
+             vt=ff((B * (D // 64), 64, npad) if consumer == 4 else (0, 64, npad), np.float32),
+             xh=ff((M, D), np.uint16), xl=ff((M, D), np.int8), cstat=ff((M, max(D // 32, 1), 2), np.float32),
+             rowstat=ff((M, 2), np.float32), wf=ff((N, D), np.uint16), colsum=ff((N,), np.float32), cvec=ff((N,), np.float32))
+    i8 = lambda a: a.ctypes.data_as(POINTER(ctypes.c_int8))
+    p = lambda a, conv: conv(a) if a.size else None
+    rc = ops_lib().vt_op_ln_chain_bf16(device, _f32(xx) if xx is not None else None, B, tokens, D, _u16(w_bits), _f32(g), _f32(be),
+                                       _f32(bi), N, consumer, route, producer_cfg, consumer_cfg, eps, int(lo_shift), launches,
+                                       p(r["out"], _f32), p(r["vt"], _f32), p(r["xh"], _u16), p(r["xl"], i8),
+                                       p(r["cstat"], _f32), p(r["rowstat"], _f32), _u16(r["wf"]), _f32(r["colsum"]),
+                                       _f32(r["cvec"]))
+    if check:
+        _check_op(rc)
+    r["rc"] = rc
+    return r
 
 
 def op_gemm_bench(M, N, K, epilogue, cfg=-1, iters=50, device=0) -> float:

@@ -1110,4 +1110,143 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The folded LayerNorm as the engine runs it, end to end (see include/vittrack_hip_ops.h): X-epilogue producer -> row
+// terms by one of the three routes of the xgemm lambda (vt_engine.hip) -> launch_fold_layernorm -> the consuming GEMM
+// on the hi half of the pair. Every device output lies between guard bands and starts as 0xff.
+int vt_op_ln_chain_bf16(int device_id, const float* x, int B, int tokens, int D, const uint16_t* w, const float* gamma,
+                        const float* beta, const float* bias, int N, int consumer, int route, int producer_cfg,
+                        int consumer_cfg, float eps, int lo_shift, int launches, float* out, float* vt_out,
+                        uint16_t* xh_out, int8_t* xl_out, float* cstat_out, float* rowstat_out, uint16_t* wf_out,
+                        float* colsum_out, float* cvec_out) try {
+    if (!w || !gamma || !beta || !bias || D <= 0 || (D & 1) || N <= 0 || launches < 1 || launches > 16)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    const bool fold_only = consumer == 0;
+    int epi = 0;
+    switch (consumer) {
+        case 0: break;
+        case 2: epi = EPI_GELU_BF16; break;
+        case 3: epi = EPI_RELU_BF16; break;
+        case 4: epi = EPI_QKV; break;
+        default: return set_err(VT_ERR_INVALID_ARG, "ln chain: unknown consumer %d", consumer);
+    }
+    const long long Mll = (long long)B * tokens;
+    int pcfg = producer_cfg, ccfg = consumer_cfg;
+    GemmArgs pa{}, ca{};
+    if (!fold_only) {
+        if (!x || !out || B <= 0 || tokens <= 0 || Mll > (1 << 20) || D % 64 || N % 64 || D > 2048 || !(eps >= 0.0f))
+            return set_err(VT_ERR_INVALID_ARG, "bad argument");
+        if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "ln chain: lo_shift %d out of range", lo_shift);
+        if (route < 0 || route > 2) return set_err(VT_ERR_INVALID_ARG, "ln chain: unknown route %d", route);
+        if (epi == EPI_QKV && (N != 3 * D || (tokens & 3) || !vt_out))
+            return set_err(VT_ERR_INVALID_ARG, "ln chain: QKV takes N == 3 * D, tokens %% 4 == 0 and vt_out");
+        // the shapes of the two launches, enough of them to ask the launcher which configuration it would take
+        pa.M = (int)Mll; pa.N = D; pa.K = 128; pa.lda = 128; pa.ldw = 128; pa.ldx = D; pa.pos_rows = (int)Mll;
+        ca.M = (int)Mll; ca.N = N; ca.K = D; ca.lda = D; ca.ldw = D; ca.ldcb = N;
+        ca.tokens = tokens; ca.npad = (tokens + 63) / 64 * 64; ca.D = D;
+        if (route == 1 && (D % 256 || D > 1536 || (pcfg >= 0 && pcfg < GEMM_CFG_256_MIN)))
+            return set_err(VT_ERR_INVALID_ARG, "ln chain: route 1 takes a 256x256 producer, D %% 256 == 0, D <= 1536");
+        if (route == 2 && (D % 128 || D > 1024 || ccfg > GEMM_CFG_SMALL_MAX))
+            return set_err(VT_ERR_INVALID_ARG, "ln chain: route 2 takes a 4-wave consumer, D %% 128 == 0, D <= 1024");
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t WN = (size_t)N * D;
+    DevBuf dw, dg, dbeta, dbias;
+    GuardedOut gwf, gcs, gcv;
+    HIPCHK(dw.alloc(WN * 2)); HIPCHK(dg.alloc((size_t)D * 4)); HIPCHK(dbeta.alloc((size_t)D * 4)); HIPCHK(dbias.alloc((size_t)N * 4));
+    HIPCHK(gwf.alloc(WN * 2)); HIPCHK(gcs.alloc((size_t)N * 4)); HIPCHK(gcv.alloc((size_t)N * 4));
+    HIPCHK(hipMemcpy(dw.p, w, WN * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dg.p, gamma, (size_t)D * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dbeta.p, beta, (size_t)D * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    auto fold = [&] {
+        return launch_fold_layernorm((const bf16_t*)dw.p, (const float*)dg.p, (const float*)dbeta.p, (const float*)dbias.p,
+                                     (bf16_t*)gwf.out(), (float*)gcs.out(), (float*)gcv.out(), N, D, nullptr);
+    };
+    auto guards = [&](std::initializer_list<std::pair<const GuardedOut*, const char*>> outs) -> int {
+        for (const auto& o : outs) {
+            if (!o.first->bytes) continue;
+            long where = 0;
+            HIPCHK(o.first->check(&where));
+            if (where) return set_err(VT_ERR_HIP, "ln chain wrote outside its %s: guard byte %ld changed", o.second, where);
+        }
+        return VT_OK;
+    };
+    auto fold_back = [&]() -> int {
+        if (wf_out) HIPCHK(hipMemcpy(wf_out, gwf.out(), WN * 2, hipMemcpyDeviceToHost));
+        if (colsum_out) HIPCHK(hipMemcpy(colsum_out, gcs.out(), (size_t)N * 4, hipMemcpyDeviceToHost));
+        if (cvec_out) HIPCHK(hipMemcpy(cvec_out, gcv.out(), (size_t)N * 4, hipMemcpyDeviceToHost));
+        return VT_OK;
+    };
+    if (fold_only) {
+        for (int rep = 0; rep < launches; ++rep) HIPCHK(fold());
+        HIPCHK(hipDeviceSynchronize());
+        if (int rc = guards({{&gwf, "folded weights"}, {&gcs, "column sums"}, {&gcv, "constant vector"}})) return rc;
+        return fold_back();
+    }
+    HIPCHK(gemm_prepare());
+    const int M = (int)Mll, nchunk = D / VT_STAT_CHUNK, H = D / 64, npad = ca.npad;
+    const size_t MD = (size_t)M * D, n_out = epi == EPI_QKV ? (size_t)M * 2 * D : (size_t)M * N,
+                 n_vt = epi == EPI_QKV ? (size_t)B * H * 64 * npad : 0, n_cnt = (size_t)(M + 255) / 256 + 1;
+    DevBuf dza, dzw, dzb, dpos, dcnt;
+    GuardedOut gxh, gxl, gcst, grs, gout, gvt;
+    HIPCHK(dza.alloc((size_t)M * 128 * 2)); HIPCHK(dzw.alloc((size_t)D * 128 * 2)); HIPCHK(dzb.alloc((size_t)D * 4));
+    HIPCHK(dpos.alloc(MD * 4)); HIPCHK(dcnt.alloc(n_cnt * 4));
+    HIPCHK(gxh.alloc(MD * 2)); HIPCHK(gxl.alloc(MD)); HIPCHK(gcst.alloc((size_t)M * nchunk * 8)); HIPCHK(grs.alloc((size_t)M * 8));
+    HIPCHK(gout.alloc(n_out * 2));
+    if (n_vt) HIPCHK(gvt.alloc(n_vt * 2));
+    HIPCHK(hipMemset(dza.p, 0, (size_t)M * 128 * 2)); HIPCHK(hipMemset(dzw.p, 0, (size_t)D * 128 * 2));
+    HIPCHK(hipMemset(dzb.p, 0, (size_t)D * 4)); HIPCHK(hipMemset(dcnt.p, 0, n_cnt * 4));
+    HIPCHK(hipMemcpy(dpos.p, x, MD * 4, hipMemcpyHostToDevice));
+    // producer: (0 + 0) + pos = x exactly, through the X-epilogue's statistics and split
+    pa.A = (const bf16_t*)dza.p; pa.W = (const bf16_t*)dzw.p; pa.bias = (const float*)dzb.p;
+    pa.pos = (const float*)dpos.p; pa.Xh = (bf16_t*)gxh.out(); pa.Xl = (uint8_t*)gxl.out();
+    pa.cstat = (float2*)gcst.out(); pa.ln_eps = eps; pa.lq = lo_quant(lo_shift);
+    if (pcfg >= 0) { pa.tile_order = (pcfg >> 8) & 3; pcfg &= 0xff; }
+    if (route == 1) { pa.rowstat_out = (float2*)grs.out(); pa.panel_cnt = (unsigned*)dcnt.p; }
+    if (pcfg < 0) pcfg = gemm_effective_config(pa, EPI_F32_POS);
+    if (route == 1 && !(pcfg >= GEMM_CFG_256_MIN && gemm256_fits(pa, EPI_F32_POS)))
+        return set_err(VT_ERR_INVALID_ARG, "ln chain: route 1 takes a 256x256 producer (configuration %d chosen)", pcfg);
+    // consumer: A = the hi half, W = the folded weights, bias = cvec, row terms by route
+    ca.A = (const bf16_t*)gxh.out(); ca.W = (const bf16_t*)gwf.out(); ca.bias = (const float*)gcv.out();
+    ca.colsum = (const float*)gcs.out(); ca.ln_eps = eps;
+    if (epi == EPI_QKV) { ca.qk = (bf16_t*)gout.out(); ca.vt = (bf16_t*)gvt.out(); }
+    else ca.Cb = (bf16_t*)gout.out();
+    if (ccfg >= 0) { ca.tile_order = (ccfg >> 8) & 3; ccfg &= 0xff; }
+    if (route == 2) ca.cstat_in = (const float2*)gcst.out();
+    else ca.rowstat = (const float2*)grs.out();        // the pair load of the last even row ends in the guard band
+    if (ccfg < 0) ccfg = gemm_effective_config(ca, epi);
+    if (route == 2 && ccfg > GEMM_CFG_SMALL_MAX)
+        return set_err(VT_ERR_INVALID_ARG, "ln chain: route 2 takes a 4-wave consumer (configuration %d chosen)", ccfg);
+    for (int rep = 0; rep < launches; ++rep) {
+        if (launch_gemm_cfg(pa, EPI_F32_POS, pcfg, nullptr) != hipSuccess)
+            return set_err(VT_ERR_INVALID_ARG, "ln chain: producer configuration %d does not fit M=%d D=%d", pcfg, M, D);
+        if (route == 0) HIPCHK(launch_rowstat_finalize(pa.cstat, (float2*)grs.out(), M, nchunk, eps, nullptr));
+        HIPCHK(fold());
+        if (launch_gemm_cfg(ca, epi, ccfg, nullptr) != hipSuccess)
+            return set_err(VT_ERR_INVALID_ARG, "ln chain: consumer configuration %d does not fit M=%d N=%d D=%d", ccfg, M, N, D);
+    }
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards({{&gxh, "hi half"}, {&gxl, "lo8 half"}, {&gcst, "chunk partials"}, {&grs, "row terms"}, {&gout, "output"},
+                         {&gvt, "Vt"}, {&gwf, "folded weights"}, {&gcs, "column sums"}, {&gcv, "constant vector"}})) return rc;
+    std::vector<unsigned> cnt(n_cnt);
+    HIPCHK(hipMemcpy(cnt.data(), dcnt.p, n_cnt * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_cnt; ++i)
+        if (cnt[i]) return set_err(VT_ERR_HIP, "ln chain: panel counter %zu is %u after %d launches", i, cnt[i], launches);
+    auto widen = [](const void* d, size_t count, float* o) -> hipError_t {
+        std::vector<bf16_t> tmp(count);
+        hipError_t e = hipMemcpy(tmp.data(), d, count * 2, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        for (size_t i = 0; i < count; ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(o + i, &u, 4); }
+        return hipSuccess;
+    };
+    HIPCHK(widen(gout.out(), n_out, out));
+    if (n_vt) HIPCHK(widen(gvt.out(), n_vt, vt_out));
+    if (xh_out) HIPCHK(hipMemcpy(xh_out, gxh.out(), MD * 2, hipMemcpyDeviceToHost));
+    if (xl_out) HIPCHK(hipMemcpy(xl_out, gxl.out(), MD, hipMemcpyDeviceToHost));
+    if (cstat_out) HIPCHK(hipMemcpy(cstat_out, gcst.out(), (size_t)M * nchunk * 8, hipMemcpyDeviceToHost));
+    if (rowstat_out) HIPCHK(hipMemcpy(rowstat_out, grs.out(), (size_t)M * 8, hipMemcpyDeviceToHost));
+    return fold_back();
+} VT_NOTHROW_INT
+
 }  // extern "C"

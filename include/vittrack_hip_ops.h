@@ -194,6 +194,30 @@ int vt_op_nv12_to_rgb8_batch_bench(int device_id, int w, int h, int n, int iters
 /* y[M,D] (bf16 widened) = LayerNorm(x[M,D] f32; gamma, beta, eps=1e-6) */
 int vt_op_layernorm(int device_id, const float* x, const float* gamma, const float* beta,
                     float* y, int M, int D);
+/* The folded LayerNorm of an encoder block as the engine runs it, M = B * tokens rows of x [M][D] (float32, host):
+ *   producer  the X-epilogue "+ pos" with all-zero operands and pos = x: (0 + 0) + x is x exactly, so any float32
+ *             matrix goes through the real split (xh_out bf16 bits / xl_out signed bytes, quantum 2^-lo_shift) and the
+ *             real chunk statistics (cstat_out [M][D / 32][2]: sum, M2);
+ *   row terms (rstd, -mean * rstd) with `eps`, by route: 0 a launch of the finalize kernel, 1 the last workgroup of
+ *             each 256-row panel inside the 256x256 producer, 2 the consumer's own epilogue from the chunk partials.
+ *             rowstat_out [M][2]; route 2 never writes it (it stays 0xff);
+ *   fold      Wf = bf16(gamma * W) (wf_out [N][D]), colsum_out [N] = sum_k Wf, cvec_out [N] = sum_k beta W + bias,
+ *             from w [N][D] (bf16 bits), gamma, beta [D], bias [N];
+ *   consumer  2 GELU, 3 ReLU: out [M][N] = f(rstd * (xh Wf^T) + (-mean * rstd * colsum + cvec)) (bf16 widened);
+ *             4 QKV (N == 3 * D, tokens % 4 == 0): out = qk [M][2D], vt_out = Vt [B * D / 64][64][npad] in natural key
+ *             order, as vt_op_qkv_bf16 returns them (pad columns of Vt stay 0xff);
+ *             0 the fold alone (x, B, tokens, route and the configurations are ignored; N >= 1, D even).
+ * producer_cfg / consumer_cfg as in vt_op_gemm_bf16 (< 0: the launcher's choice). The chain runs `launches` (1..16)
+ * times on the same buffers; the panel counters of route 1 must be zero afterwards (VT_ERR_HIP otherwise). Every
+ * device output starts as 0xff between guard bands; a changed guard byte is VT_ERR_HIP. VT_ERR_INVALID_ARG, with
+ * nothing launched and no output written: route 1 with a producer configuration below 18, D % 256 or D > 1536;
+ * route 2 with a consumer configuration above 8, D % 128 or D > 1024; QKV with N != 3 * D or tokens % 4; D > 2048;
+ * a configuration the launcher refuses for the shape. Output pointers other than `out` (and vt_out for QKV) may be NULL. */
+int vt_op_ln_chain_bf16(int device_id, const float* x, int B, int tokens, int D, const uint16_t* w, const float* gamma,
+                        const float* beta, const float* bias, int N, int consumer, int route, int producer_cfg,
+                        int consumer_cfg, float eps, int lo_shift, int launches, float* out, float* vt_out,
+                        uint16_t* xh_out, int8_t* xl_out, float* cstat_out, float* rowstat_out, uint16_t* wf_out,
+                        float* colsum_out, float* cvec_out);
 
 #ifdef __cplusplus
 }

@@ -391,6 +391,26 @@ def test_layernorm(gpu, M, D):
     assert np.all(np.abs(got - ref) <= np.abs(ref) * 2 ** -8 + 1e-4)
 
 
+@pytest.mark.parametrize("M", [1, 5, 9])
+@pytest.mark.parametrize("D", [384, 1536, 256, 512])
+def test_layernorm_widths_row_counts_and_row_classes(gpu, M, D):
+    """the narrow kernel at NCH = 3 and 12 (384, 1536) and the wide one at NCH = 1 and 2 (256, 512), with a partly idle last
+    block (1, 5, 9 rows: the narrow kernel takes 4 rows per block, the wide one 8), on N(0, 1), DC-dominated, constant and
+    eps-sized rows, each class in every row position: float64 reference, bound derived in ln_chain_util.layernorm_ref"""
+    import ln_chain_util as lu
+    rng = np.random.default_rng(D)
+    g = (1 + 0.2 * rng.standard_normal(D)).astype(np.float32)
+    b = (0.1 * rng.standard_normal(D)).astype(np.float32)
+    for shift in range(4):
+        x = lu.layernorm_rows(M, D, shift)
+        ref, bound = lu.layernorm_ref(x, g, b)
+        got = gpu.op_layernorm(x, g, b)
+        ratio = np.abs(got - ref) / bound
+        print(f"layernorm M={M} D={D} shift={shift}: max(err / bound) = {ratio.max():.4f}")
+        assert np.isfinite(got).all()
+        assert ratio.max() <= 1.0, (shift, np.unravel_index(ratio.argmax(), ratio.shape), ratio.max())
+
+
 @pytest.mark.parametrize("B,grid,C,N,cfg", [(1, 24, 128, 128, 2), (3, 24, 128, 128, 3), (2, 8, 64, 64, 0), (2, 24, 128, 128, 4),
                                              (30, 24, 128, 128, -1), (1, 28, 128, 128, 1), (5, 5, 64, 128, 2),
                                              (2, 24, 128, 128, 7), (1, 24, 128, 128, 8)])
