@@ -21,10 +21,6 @@ from . import snapshot  # noqa: F401  (the snapshot format in NumPy)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VITTRACK_HIP_LIB", os.path.join(PKG_DIR, "libvittrack_hip.so"))
-# operator-level entry points (include/vittrack_hip_ops.h): a library of their own, for tests and tuning tools; a tuning
-# build named by VITTRACK_HIP_LIB carries them too
-OPS_LIB_PATH = os.environ.get("VITTRACK_HIP_OPS_LIB") or os.environ.get("VITTRACK_HIP_LIB") or \
-    os.path.join(PKG_DIR, "libvittrack_hip_ops.so")
 
 PIX_RGB8, PIX_NV12, PIX_YUY2 = 0, 1, 2
 # byte permutations / paddings of the three above (include/vittrack_hip.h: vt_pixfmt)
@@ -115,6 +111,11 @@ class CPeaks(Structure):
     _fields_ = [("n", c_int32), ("stream", c_int32), ("frames_done", c_int32), ("radius", c_int32), ("peak", CPeak * PEAKS_MAX)]
 
 
+# vt_peak / vt_peaks (include/vittrack_hip.h) as NumPy records: 32 / 272 bytes
+PEAK_DTYPE = np.dtype([("score", "<f4"), ("resp", "<f4"), ("box", "<f4", 4), ("cell", "<i4"), ("reserved", "<i4")])
+PEAKS_DTYPE = np.dtype([("n", "<i4"), ("stream", "<i4"), ("frames_done", "<i4"), ("radius", "<i4"), ("peak", PEAK_DTYPE, PEAKS_MAX)])
+
+
 class CDrawCmd(Structure):
     _fields_ = [("type", c_int32), ("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32),
                 ("p", c_int32), ("value", c_int32), ("text", c_char * 36)]
@@ -153,14 +154,6 @@ EXPORTS = [
     "vt_group_set_peaks", "vt_group_last_peaks", "vt_set_peaks", "vt_last_peaks",
     "vt_snapshot_bytes", "vt_group_snapshot_bytes", "vt_snapshot_info", "vt_group_export_stream",
     "vt_group_import_stream", "vt_group_copy_stream", "vt_export_state", "vt_import_state",
-]
-# every symbol include/vittrack_hip_ops.h declares (libvittrack_hip_ops.so; the product library exports none of them)
-OPS_EXPORTS = [
-    "vt_op_gemm_bf16", "vt_op_gemm_bench", "vt_op_qkv_bf16", "vt_op_attention_bf16",
-    "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
-    "vt_op_headconv_ln_bf16", "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
-    "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
-    "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_ln_chain_bf16",
 ]
 
 
@@ -293,62 +286,9 @@ def lib():
     return L
 
 
-_ops = None
-
-
-def ops_lib():
-    """Load libvittrack_hip_ops.so: the product's objects + the operator-level entry points (tests, tuning tools)."""
-    global _ops
-    if _ops is not None:
-        return _ops
-    if not os.path.exists(OPS_LIB_PATH):
-        raise VtError(-2, f"{OPS_LIB_PATH} not built: run `python __graft_entry__.py`")
-    lib()       # torch / HIP runtime first, as above
-    L = ctypes.CDLL(OPS_LIB_PATH)
-    L.vt_last_error.restype = c_char_p
-    u16p, fp = POINTER(c_uint16), POINTER(c_float)
-    L.vt_op_gemm_bf16.argtypes = [c_int, u16p, u16p, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_float]
-    L.vt_op_gemm_bf16_lo.argtypes = L.vt_op_gemm_bf16.argtypes + [c_int]
-    L.vt_op_gemm_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int, fp]
-    L.vt_op_qkv_bf16.argtypes = [c_int, u16p, u16p, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, fp]
-    L.vt_op_attention_bf16.argtypes = [c_int, u16p, u16p, u16p, fp, c_int, c_int, c_int, c_int]
-    L.vt_op_attention_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, fp]
-    L.vt_op_attention_queries_bf16.argtypes = [c_int, u16p, u16p, u16p, fp, c_int, c_int, c_int, c_int, c_int]
-    i8p = POINTER(ctypes.c_int8)
-    L.vt_op_gemm_resid_seg_bf16.argtypes = [c_int, u16p, u16p, fp, u16p, i8p, c_int, u16p, i8p, fp, fp, c_int, c_int, c_int,
-                                            c_int, c_int, c_float, c_int]
-    L.vt_op_layernorm.argtypes = [c_int, fp, fp, fp, fp, c_int, c_int]
-    L.vt_op_ln_chain_bf16.argtypes = [c_int, fp, c_int, c_int, c_int, u16p, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, c_float,
-                                      c_int, c_int, fp, fp, u16p, i8p, fp, fp, u16p, fp, fp]
-    L.vt_op_conv3x3_relu_bf16.argtypes = [c_int, u16p, u16p, fp, fp, c_int, c_int, c_int, c_int, c_int]
-    L.vt_op_nv12_to_rgb8_bench.argtypes = [c_int, c_int, c_int, c_int, fp]
-    L.vt_op_nv12_to_rgb8_batch_bench.argtypes = [c_int, c_int, c_int, c_int, c_int, fp]
-    L.vt_op_head_decode.argtypes = [c_int, c_int, u16p, u16p, fp, fp, fp, fp, c_void_p, c_int, POINTER(c_int32), c_float,
-                                    c_int, c_int, c_int, c_int, c_int, c_int, fp, c_void_p, c_void_p, c_void_p,
-                                    POINTER(ctypes.c_uint32)]
-    L.vt_op_response_peaks.argtypes = [c_int, fp, fp, c_void_p, c_int, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int,
-                                       c_int, c_void_p, c_void_p]
-    L.vt_op_motion_prior.argtypes = [c_int, c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, POINTER(c_int32), POINTER(c_int32),
-                                     c_void_p, c_int, c_int, c_void_p, c_void_p]
-    L.vt_op_appearance_score.argtypes = [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.vt_op_proposals.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int,
-                                  c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p]
-    L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_void_p,
-                                       c_int, c_int]
-    _ops = L
-    return L
-
-
 def _check(rc):
     if rc < 0:
         raise VtError(rc, lib().vt_last_error().decode(errors="replace"))
-    return rc
-
-
-def _check_op(rc):
-    if rc < 0:
-        raise VtError(rc, ops_lib().vt_last_error().decode(errors="replace"))
     return rc
 
 
@@ -1576,425 +1516,7 @@ def overlay_rgb8(rgb: np.ndarray, cmds, device: int = 0) -> np.ndarray:
     return img
 
 
-# ---- operator-level entry points (numerics tests) -------------------------------------------
+# ---- operator-level test hooks (include/vittrack_hip_ops.h, libvittrack_hip_ops.so): ops.py -----------
+# vt.op_*, vt.ops_lib, vt.OPS_EXPORTS and the hooks' record dtypes; last, because ops.py imports the names above
+from .ops import *  # noqa: E402,F401,F403
 
-def op_gemm_bf16(a_bits, w_bits, bias, c_init=None, epilogue=0, device=0, cfg=-1, rowstat=None,
-                 colsum=None, want_rowstat=False, eps=1e-6, lo_shift=12):
-    """vt_op_gemm_bf16[_lo]. epilogue 0 / 1 / 4: the X-epilogues (x comes back as the value of the 3-byte pair the
-    engine stores, its quantum 2^-lo_shift; want_rowstat: also the finalized (rstd, -mean * rstd) per row -> (x, rowstat));
-    2 / 3: GELU / ReLU to bf16, with a folded LayerNorm if rowstat [M,2] and colsum [N] are given"""
-    a_bits = np.ascontiguousarray(a_bits, np.uint16)
-    w_bits = np.ascontiguousarray(w_bits, np.uint16)
-    M, K = a_bits.shape
-    N = w_bits.shape[0]
-    c = np.zeros((M, N), np.float32) if c_init is None else np.ascontiguousarray(c_init,
-                                                                                 np.float32).copy()
-    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
-    rs = None if rowstat is None else np.ascontiguousarray(rowstat, np.float32)
-    cs = None if colsum is None else np.ascontiguousarray(colsum, np.float32)
-    ro = np.zeros((M, 2), np.float32) if want_rowstat else None
-    _check_op(ops_lib().vt_op_gemm_bf16_lo(device, _u16(a_bits), _u16(w_bits),
-                                 _f32(b) if b is not None else None, _f32(c), M, N, K, epilogue, cfg,
-                                 _f32(rs) if rs is not None else None, _f32(cs) if cs is not None else None,
-                                 _f32(ro) if ro is not None else None, eps, int(lo_shift)))
-    return (c, ro) if want_rowstat else c
-
-
-def op_ln_chain_bf16(x, B, tokens, w_bits, gamma, beta, bias, consumer, route=0, producer_cfg=-1, consumer_cfg=-1,
-                     eps=1e-6, lo_shift=12, launches=1, device=0, check=True):
-    """vt_op_ln_chain_bf16: the folded LayerNorm as the engine runs it - X-epilogue producer on x [B * tokens, D], row terms
-    by route (0 finalize launch, 1 inside the 256x256 producer, 2 combined in the consumer), the fold of w_bits [N, D] /
-    gamma / beta / bias, then the consumer (2 GELU, 3 ReLU, 4 QKV; 0: the fold alone, x may be None). Returns a dict of
-    rc, out, vt, xh (uint16), xl (int8), cstat [M, D // 32, 2], rowstat [M, 2], wf (uint16), colsum, cvec; every array
-    starts as 0xff bytes, and stays so when the call is refused (check=False returns rc instead of raising)"""
-    w_bits = np.ascontiguousarray(w_bits, np.uint16)
-    N, D = w_bits.shape
-    g, be, bi = (np.ascontiguousarray(v, np.float32) for v in (gamma, beta, bias))
-    assert g.shape == (D,) and be.shape == (D,) and bi.shape == (N,)
-    M = B * tokens if consumer else 0
-    xx = None
-    if consumer:
-        xx = np.ascontiguousarray(x, np.float32)
-        assert xx.shape == (M, D)
-    npad = (tokens + 63) // 64 * 64
-    def ff(shape, dt):
-        return np.full(int(np.prod(shape)) * np.dtype(dt).itemsize, 0xff, np.uint8).view(dt).reshape(shape)
-    r = dict(out=ff((M, 2 * D if consumer == 4 else N), np.float32),
-             vt=ff((B * (D // 64), 64, npad) if consumer == 4 else (0, 64, npad), np.float32),
-             xh=ff((M, D), np.uint16), xl=ff((M, D), np.int8), cstat=ff((M, max(D // 32, 1), 2), np.float32),
-             rowstat=ff((M, 2), np.float32), wf=ff((N, D), np.uint16), colsum=ff((N,), np.float32), cvec=ff((N,), np.float32))
-    i8 = lambda a: a.ctypes.data_as(POINTER(ctypes.c_int8))
-    p = lambda a, conv: conv(a) if a.size else None
-    rc = ops_lib().vt_op_ln_chain_bf16(device, _f32(xx) if xx is not None else None, B, tokens, D, _u16(w_bits), _f32(g), _f32(be),
-                                       _f32(bi), N, consumer, route, producer_cfg, consumer_cfg, eps, int(lo_shift), launches,
-                                       p(r["out"], _f32), p(r["vt"], _f32), p(r["xh"], _u16), p(r["xl"], i8),
-                                       p(r["cstat"], _f32), p(r["rowstat"], _f32), _u16(r["wf"]), _f32(r["colsum"]),
-                                       _f32(r["cvec"]))
-    if check:
-        _check_op(rc)
-    r["rc"] = rc
-    return r
-
-
-def op_gemm_bench(M, N, K, epilogue, cfg=-1, iters=50, device=0) -> float:
-    us = c_float()
-    _check_op(ops_lib().vt_op_gemm_bench(device, M, N, K, epilogue, cfg, iters, byref(us)))
-    return float(us.value)
-
-
-def op_qkv_bf16(a_bits, w_bits, bias, B, tokens, D, device=0, cfg=-1, vt_perm=0, rowstat=None,
-                colsum=None):
-    a_bits = np.ascontiguousarray(a_bits, np.uint16)
-    w_bits = np.ascontiguousarray(w_bits, np.uint16)
-    bias = np.ascontiguousarray(bias, np.float32)
-    npad = (tokens + 63) // 64 * 64
-    qk = np.empty((B * tokens, 2 * D), np.float32)
-    vt = np.empty((B * (D // 64), 64, npad), np.float32)
-    rs = None if rowstat is None else np.ascontiguousarray(rowstat, np.float32)
-    cs = None if colsum is None else np.ascontiguousarray(colsum, np.float32)
-    _check_op(ops_lib().vt_op_qkv_bf16(device, _u16(a_bits), _u16(w_bits), _f32(bias), _f32(qk),
-                                _f32(vt), B, tokens, D, cfg, vt_perm,
-                                _f32(rs) if rs is not None else None, _f32(cs) if cs is not None else None))
-    return qk, vt
-
-
-def op_attention_bf16(q_bits, k_bits, v_bits, B, N, H, device=0, mode=-1):
-    q_bits, k_bits, v_bits = (np.ascontiguousarray(x, np.uint16) for x in (q_bits, k_bits, v_bits))
-    out = np.empty((B * N, H * 64), np.float32)
-    _check_op(ops_lib().vt_op_attention_bf16(device, _u16(q_bits), _u16(k_bits), _u16(v_bits), _f32(out),
-                                      B, N, H, mode))
-    return out
-
-
-def op_attention_queries(q_bits, k_bits, v_bits, B, N, H, q0, nq, device=0):
-    """vt_op_attention_queries_bf16: attention mode 3 on the queries q0 .. q0 + nq - 1 of every stream -> [B * nq, H * 64]"""
-    q_bits, k_bits, v_bits = (np.ascontiguousarray(x, np.uint16) for x in (q_bits, k_bits, v_bits))
-    out = np.empty((B * nq, H * 64), np.float32)
-    _check_op(ops_lib().vt_op_attention_queries_bf16(device, _u16(q_bits), _u16(k_bits), _u16(v_bits), _f32(out),
-                                                     B, N, H, int(q0), int(nq)))
-    return out
-
-
-def op_gemm_resid_seg(a_bits, w_bits, bias, xh_bits, xl_lo8, M, seg_rows=0, seg_skip=0, eps=1e-6, lo_shift=12, device=0):
-    """vt_op_gemm_resid_seg_bf16: the residual GEMM of the 256x256 kernel on the stored pair xh_bits (uint16) / xl_lo8 (int8)
-    [rows_in, N], output row m taking its addend from input row m + (m // seg_rows + 1) * seg_skip (seg_rows = 0: rows
-    0 .. M-1, in place) -> (xh [M, N] uint16, xl [M, N] int8, chunk partials [M, N // 32, 2], row terms [M, 2])"""
-    a_bits = np.ascontiguousarray(a_bits, np.uint16)
-    w_bits = np.ascontiguousarray(w_bits, np.uint16)
-    xh = np.ascontiguousarray(xh_bits, np.uint16)
-    xl = np.ascontiguousarray(xl_lo8, np.int8)
-    K, N = a_bits.shape[1], w_bits.shape[0]
-    assert a_bits.shape[0] == M and xh.shape == xl.shape and xh.shape[1] == N
-    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
-    oh, ol = np.empty((M, N), np.uint16), np.empty((M, N), np.int8)
-    cst, ro = np.empty((M, N // 32, 2), np.float32), np.empty((M, 2), np.float32)
-    i8p = POINTER(ctypes.c_int8)
-    _check_op(ops_lib().vt_op_gemm_resid_seg_bf16(device, _u16(a_bits), _u16(w_bits), _f32(b) if b is not None else None,
-                                                  _u16(xh), xl.ctypes.data_as(i8p), xh.shape[0], _u16(oh),
-                                                  ol.ctypes.data_as(i8p), _f32(cst), _f32(ro), M, N, K, int(seg_rows),
-                                                  int(seg_skip), c_float(eps), int(lo_shift)))
-    return oh, ol, cst, ro
-
-
-def op_attention_bench(B, N, H, mode=-1, iters=30, device=0) -> float:
-    us = c_float()
-    _check_op(ops_lib().vt_op_attention_bench(device, B, N, H, mode, iters, byref(us)))
-    return float(us.value)
-
-
-def op_nv12_to_rgb8_bench(w, h, iters=50, device=0) -> float:
-    """mean microseconds per launch of the whole-frame NV12 -> RGB8 converter (device-resident)"""
-    us = c_float()
-    _check_op(ops_lib().vt_op_nv12_to_rgb8_bench(device, w, h, iters, byref(us)))
-    return float(us.value)
-
-
-def op_nv12_to_rgb8_batch_bench(w, h, n, iters=20, device=0) -> float:
-    """mean microseconds per launch of the n-frames-per-launch converter on device-resident random frames"""
-    us = c_float(0.0)
-    _check_op(ops_lib().vt_op_nv12_to_rgb8_batch_bench(device, w, h, n, iters, byref(us)))
-    return float(us.value)
-
-
-def op_conv3x3_relu(t_bf16_bits, w_bf16_bits, bias, B, grid, cfg=-1, device=0):
-    """vt_op_conv3x3_relu_bf16: relu(conv3x3(t) + bias) as the implicit GEMM of the head; t [B*grid*grid][C],
-    w [N][9*C] as uint16 bf16 bit patterns -> [B*grid*grid][N] float32 (bf16 values)"""
-    t = np.ascontiguousarray(t_bf16_bits, np.uint16)
-    w = np.ascontiguousarray(w_bf16_bits, np.uint16)
-    C, N = t.shape[1], w.shape[0]
-    out = np.empty((t.shape[0], N), np.float32)
-    _check_op(ops_lib().vt_op_conv3x3_relu_bf16(device, t.ctypes.data_as(POINTER(ctypes.c_uint16)),
-                                         w.ctypes.data_as(POINTER(ctypes.c_uint16)),
-                                         _f32(np.ascontiguousarray(bias, np.float32)), _f32(out), B, grid, C, N, cfg))
-    return out
-
-
-def op_headconv(t_bf16_bits, w_bf16_bits, bias, B, grid, conv3x3=True, R=0, ncb=0, device=0):
-    """vt_op_headconv_bf16: the head's band kernel (k_head.hip) on given operands -> [B*grid*grid][N] float32"""
-    t = np.ascontiguousarray(t_bf16_bits, np.uint16)
-    w = np.ascontiguousarray(w_bf16_bits, np.uint16)
-    Cin, N = t.shape[1], w.shape[0]
-    out = np.empty((t.shape[0], N), np.float32)
-    u16 = POINTER(ctypes.c_uint16)
-    _check_op(ops_lib().vt_op_headconv_bf16(device, t.ctypes.data_as(u16), w.ctypes.data_as(u16),
-                                     _f32(np.ascontiguousarray(bias, np.float32)), _f32(out), B, grid, Cin, N,
-                                     1 if conv3x3 else 0, R, ncb, 0, None))
-    return out
-
-
-# vt_result as the decode writes it (include/vittrack_hip.h), 6 words
-RESULT_DTYPE = np.dtype([("success", "<i4"), ("score", "<f4"), ("bbox", "<i4", 4)])
-
-
-# vt_peak / vt_peaks (include/vittrack_hip.h): 32 / 272 bytes; vt_peaks_policy: the 16-byte per-stream policy record
-PEAK_DTYPE = np.dtype([("score", "<f4"), ("resp", "<f4"), ("box", "<f4", 4), ("cell", "<i4"), ("reserved", "<i4")])
-PEAKS_DTYPE = np.dtype([("n", "<i4"), ("stream", "<i4"), ("frames_done", "<i4"), ("radius", "<i4"), ("peak", PEAK_DTYPE, PEAKS_MAX)])
-PEAKS_POLICY_DTYPE = np.dtype([("max_peaks", "<i4"), ("radius", "<i4"), ("min_resp", "<f4"), ("reserved", "<i4")])
-
-
-def op_response_peaks(head_out, hann, states, policies, B, grid, slot_stream=None, winner=None, mirror_fill=0xA5, device=0):
-    """vt_op_response_peaks: the response-peaks launch (k_peaks.hip) on given operands, nothing else. head_out [B*ns][8]
-    float32 logits by slot, hann [ns], states: snapshot.STATE records by stream, policies: PEAKS_POLICY_DTYPE records by
-    stream (or (max_peaks, radius, min_resp) for all), slot_stream [B]: slot -> stream (None: the identity), winner [B]: a
-    candidate pass's winner table (None: every slot lists). Device records and pinned mirror start filled with the byte
-    mirror_fill. -> dict(records / host_records [B] PEAKS_DTYPE, states [n_states] as they came back)"""
-    from .snapshot import STATE
-    ho = np.ascontiguousarray(head_out, np.float32)
-    ns = grid * grid
-    assert ho.shape == (B * ns, 8)
-    hann = np.ascontiguousarray(hann, np.float32).reshape(-1)
-    assert hann.shape == (ns,)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
-    if isinstance(policies, tuple):
-        pol = np.zeros(len(st), PEAKS_POLICY_DTYPE)
-        pol["max_peaks"], pol["radius"], pol["min_resp"] = policies
-    else:
-        pol = np.ascontiguousarray(policies, PEAKS_POLICY_DTYPE).reshape(-1)
-    assert len(pol) == len(st)
-    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
-    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
-    assert (smap is None or smap.shape == (B,)) and (win is None or win.shape == (B,))
-    fill = lambda: np.frombuffer(bytes([mirror_fill]) * (B * PEAKS_DTYPE.itemsize), PEAKS_DTYPE).copy()
-    out = dict(records=fill(), host_records=fill())
-    i32 = POINTER(c_int32)
-    _check_op(ops_lib().vt_op_response_peaks(
-        device, _f32(ho), _f32(hann), st.ctypes.data_as(c_void_p), len(st), pol.ctypes.data_as(c_void_p),
-        smap.ctypes.data_as(i32) if smap is not None else None, win.ctypes.data_as(i32) if win is not None else None,
-        B, grid, out["records"].ctypes.data_as(c_void_p), out["host_records"].ctypes.data_as(c_void_p)))
-    out["states"] = st
-    return out
-
-
-# the motion prior's records (csrc/vt_common.hpp: MotionRec 48 bytes by stream, MotionPolicy 16 bytes per engine)
-MOTION_REC_DTYPE = np.dtype([("v", "<f4", 2), ("prior", "<f4", 4), ("shift", "<f4", 2), ("live", "<i4"), ("n_shift", "<i4"),
-                             ("n_coast", "<i4"), ("reserved", "<i4")])
-CANDIDATE_DTYPE = np.dtype([("stream", "<i4"), ("has_box", "<i4"), ("box", "<f4", 4)])
-
-
-def op_motion_prior(states, records, results, on=1, gain_pct=50, coast=5, max_pct=100, slot_stream=None, cands=None, winner=None,
-                    stages=3, host_states=None, host_records=None, device=0):
-    """vt_op_motion_prior: the place (stages & 1) and settle (stages & 2) launches of k_motion.hip on given operands,
-    nothing else. states: snapshot.STATE records by stream, records: MOTION_REC_DTYPE by stream, results [n] RESULT_DTYPE by
-    slot, slot_stream [n]: slot -> stream (None: the identity); the candidate form: cands [n] CANDIDATE_DTYPE + winner [n].
-    host_states / host_records: what the pinned mirrors hold before (None: that mirror is null). -> dict(states, records,
-    host_states, host_records) as they came back"""
-    from .snapshot import STATE
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
-    rec = np.ascontiguousarray(records, MOTION_REC_DTYPE).reshape(-1).copy()
-    assert len(rec) == len(st)
-    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
-    n = len(res)
-    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
-    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
-    cd = None if cands is None else np.ascontiguousarray(cands, CANDIDATE_DTYPE).reshape(-1)
-    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,)) and (cd is None or cd.shape == (n,))
-    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
-    hrec = None if host_records is None else np.ascontiguousarray(host_records, MOTION_REC_DTYPE).reshape(-1).copy()
-    assert (hst is None or len(hst) == len(st)) and (hrec is None or len(hrec) == len(st))
-    pol = np.array([on, gain_pct, coast, max_pct], np.int32)
-    i32 = POINTER(c_int32)
-    vp = lambda a: a.ctypes.data_as(c_void_p) if a is not None else None
-    _check_op(ops_lib().vt_op_motion_prior(
-        device, vp(st), vp(rec), len(st), pol.ctypes.data_as(i32), vp(res), smap.ctypes.data_as(i32) if smap is not None else None,
-        win.ctypes.data_as(i32) if win is not None else None, vp(cd), n, stages, vp(hst), vp(hrec)))
-    return dict(states=st, records=rec, host_states=hst, host_records=hrec)
-
-
-def op_appearance_score(anchor, probe, cols, device=0):
-    """vt_op_appearance_score: the score launch of k_appearance.hip on given rows, nothing else. anchor, probe:
-    [n_slots, nt, kpad] uint16 bf16 bit patterns; the sums run over columns [0, cols). -> dict(sums [n_slots, 5] float64 =
-    Sa, Sp, Saa, Spp, Sap, similarity [n_slots] float32, status [n_slots] int32)"""
-    a = np.ascontiguousarray(anchor, np.uint16)
-    p = np.ascontiguousarray(probe, np.uint16)
-    assert a.ndim == 3 and a.shape == p.shape
-    n, nt, kpad = a.shape
-    sums = np.empty((n, 5), np.float64)
-    sim = np.empty(n, np.float32)
-    status = np.empty(n, np.int32)
-    vp = lambda x: x.ctypes.data_as(c_void_p)
-    _check_op(ops_lib().vt_op_appearance_score(device, vp(a), vp(p), n, nt, kpad, int(cols), vp(sums), vp(sim), vp(status)))
-    return dict(sums=sums, similarity=sim, status=status)
-
-
-# the 224-byte record of the reacquire proposals (csrc/vt_common.hpp: PropRec)
-PROPOSAL_DTYPE = np.dtype([("sim", "<f4"), ("box", "<f4", 4), ("pos", "<i4")])
-PROPOSALS_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n", "<i4"), ("c", "<f4"), ("Wg", "<i4"), ("Hg", "<i4"),
-                                ("reserved", "<i4", 2), ("p", PROPOSAL_DTYPE, 8)])
-
-
-def op_proposals(frames, states, results, tpl, T, patch, norm, mode=2, period=1, max_n=4, min_sim_pm=500, max_cells=16384,
-                 slot_stream=None, winner=None, tpl_bufs=1, device_frames=True, evaluated=None, device=0):
-    """vt_op_proposals: the four launches of k_proposals.hip on given operands, nothing else. frames: CFrame per slot with
-    DEVICE planes; states: snapshot.STATE records by stream; results [n] RESULT_DTYPE by slot; tpl [n_streams, tpl_bufs,
-    nt, kpad] uint16 bf16 bit patterns; norm: (a0, a1, a2, b0, b1, b2). -> dict(pattern [n, 256] int16, thumb [n, max_cells]
-    int16, map [n, max_cells] float32, records [n_streams] PROPOSALS_REC_DTYPE, evaluated [n_streams] int32); what no
-    launch stored is 0xff bytes"""
-    from .snapshot import STATE
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
-    st = np.ascontiguousarray(states, STATE).reshape(-1)
-    ns = len(st)
-    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
-    assert res.shape == (n,)
-    t = np.ascontiguousarray(tpl, np.uint16)
-    kpad = t.shape[-1]
-    assert t.size == ns * tpl_bufs * (T // patch) ** 2 * kpad
-    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
-    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
-    nrm = np.ascontiguousarray(norm, np.float32).reshape(6)
-    pol = np.array([mode, period, max_n, min_sim_pm, 0, max_cells, 0, 0], np.int32)
-    pattern = np.empty((n, 256), np.int16)
-    thumb = np.empty((n, max_cells), np.int16)
-    smap_out = np.empty((n, max_cells), np.float32)
-    recs = np.empty(ns, PROPOSALS_REC_DTYPE)
-    ev = np.zeros(ns, np.int32) if evaluated is None else np.ascontiguousarray(evaluated, np.int32).copy()
-    vp = lambda x: x.ctypes.data_as(c_void_p)
-    i32 = POINTER(c_int32)
-    _check_op(ops_lib().vt_op_proposals(
-        device, arr, vp(st), ns, vp(res), smap.ctypes.data_as(i32) if smap is not None else None,
-        win.ctypes.data_as(i32) if win is not None else None, n, vp(t), tpl_bufs, T, patch, kpad, vp(nrm), vp(pol),
-        1 if device_frames else 0, vp(pattern), vp(thumb), vp(smap_out), vp(recs), vp(ev)))
-    return dict(pattern=pattern, thumb=thumb, map=smap_out, records=recs, evaluated=ev)
-
-
-# the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)
-OVERLAY_POLICY_DTYPE = np.dtype([("flags", "<i4"), ("thickness", "<i4"), ("size", "<i4"), ("scale", "<i4"), ("luma", "<i4"),
-                                 ("rgb", "<i4"), ("min_score_pct", "<i4"), ("reserved", "<i4")])
-OVERLAY_STATS_DTYPE = np.dtype([("drawn", "<i4"), ("n_drawn", "<i4"), ("n_gated", "<i4"), ("n_unsupported", "<i4"),
-                                ("last_n", "<i4"), ("reserved", "<i4", 3)])
-
-
-def op_result_overlay(frames, results, flags=7, thickness=3, size=15, scale=2, luma=255, rgb=0x00FF00, min_score_pct=25,
-                      slot_stream=None, winner=None, stats=None, n_streams=None, device_frames=True, device=0):
-    """vt_op_result_overlay: the result-overlay launch (k_result_overlay.hip) on given operands, nothing else. frames: CFrame
-    per slot with DEVICE planes (they are drawn into), results [n] RESULT_DTYPE by slot, slot_stream [n]: slot -> stream
-    (None: the identity), winner [n]: a candidate pass's winner table (None: every slot may draw), stats: OVERLAY_STATS_DTYPE
-    records by stream to start from (None: zeros), device_frames False: the launch of a host pass. -> the stats as they
-    came back"""
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
-    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
-    assert res.shape == (n,)
-    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
-    win = None if winner is None else np.ascontiguousarray(winner, np.int32)
-    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
-    if n_streams is None:
-        n_streams = n if stats is None else len(stats)
-    st = np.zeros(n_streams, OVERLAY_STATS_DTYPE) if stats is None else np.ascontiguousarray(stats, OVERLAY_STATS_DTYPE).reshape(-1).copy()
-    assert len(st) == n_streams
-    pol = np.zeros(1, OVERLAY_POLICY_DTYPE)
-    pol[0] = (flags, thickness, size, scale, luma, rgb, min_score_pct, 0)
-    i32 = POINTER(c_int32)
-    _check_op(ops_lib().vt_op_result_overlay(
-        device, arr, res.ctypes.data_as(c_void_p), smap.ctypes.data_as(i32) if smap is not None else None,
-        win.ctypes.data_as(i32) if win is not None else None, n, pol.ctypes.data_as(c_void_p), st.ctypes.data_as(c_void_p),
-        n_streams, 1 if device_frames else 0))
-    return st
-
-
-def op_head_decode(t_bf16_bits, w4, b4, hann, states, B, grid, form=0, w3_bf16_bits=None, b3=None, slot_stream=None,
-                   success_threshold=0.5, R=0, launches=1, host_results=True, host_states=True, mirror_fill=0xA5, device=0):
-    """vt_op_head_decode: the decode stage (k_head.hip) on given operands. form 0: head_out_kernel + decode_kernel on
-    t = t3 [B*grid*grid][C]; form 1: the last 3x3 layer (w3 [C][9C], b3 [C]) on the band kernel with the fused tail, R rows
-    per band (<= 0: the launcher's plan), `launches` launches on the same buffers. states: snapshot.STATE records (raw 88-byte
-    StreamState), indexed by stream; slot_stream [B]: slot -> stream (None: the identity). The two pinned host mirrors start
-    filled with the byte mirror_fill; host_results / host_states False runs with that mirror null. -> dict(head_out
-    [B*ns][8] float32, results / host_results [B] RESULT_DTYPE, states / host_states [n_states] snapshot.STATE, band_cnt [B]
-    uint32)"""
-    from .snapshot import STATE
-    t = np.ascontiguousarray(t_bf16_bits, np.uint16)
-    ns, C = grid * grid, t.shape[1]
-    assert t.shape == (B * ns, C)
-    w4 = np.ascontiguousarray(w4, np.float32)
-    b4 = np.ascontiguousarray(b4, np.float32)
-    hann = np.ascontiguousarray(hann, np.float32).reshape(-1)
-    assert w4.shape == (8, C) and b4.shape == (8,) and hann.shape == (ns,)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
-    u16 = POINTER(c_uint16)
-    w3 = b3p = None
-    if form == 1:
-        w3 = np.ascontiguousarray(w3_bf16_bits, np.uint16)
-        b3a = np.ascontiguousarray(b3, np.float32)
-        assert w3.shape == (C, 9 * C) and b3a.shape == (C,)
-        b3p = _f32(b3a)
-    smap = None if slot_stream is None else np.ascontiguousarray(slot_stream, np.int32)
-    assert smap is None or smap.shape == (B,)
-    out = dict(head_out=np.empty((B * ns, 8), np.float32), results=np.zeros(B, RESULT_DTYPE),
-               host_results=np.frombuffer(bytes([mirror_fill]) * (B * RESULT_DTYPE.itemsize), RESULT_DTYPE).copy(),
-               host_states=np.frombuffer(bytes([mirror_fill]) * (len(st) * STATE.itemsize), STATE).copy(),
-               band_cnt=np.full(B, 0xFFFFFFFF, np.uint32))
-    flags = (0 if host_results else 1) | (0 if host_states else 2)
-    _check_op(ops_lib().vt_op_head_decode(
-        device, int(form), t.ctypes.data_as(u16), w3.ctypes.data_as(u16) if w3 is not None else None, b3p, _f32(w4), _f32(b4),
-        _f32(hann), st.ctypes.data_as(c_void_p), len(st), smap.ctypes.data_as(POINTER(c_int32)) if smap is not None else None,
-        c_float(success_threshold), B, grid, C, int(R), int(launches), flags, _f32(out["head_out"]),
-        out["results"].ctypes.data_as(c_void_p), out["host_results"].ctypes.data_as(c_void_p),
-        out["host_states"].ctypes.data_as(c_void_p), out["band_cnt"].ctypes.data_as(POINTER(ctypes.c_uint32))))
-    out["states"] = st
-    return out
-
-
-def op_headconv_ln(xh_bits, xl_lo8, gamma, beta, w_bf16_bits, bias, B, grid, ntok, off, fused=True, eps=1e-6, R=0, ncb=0,
-                   device=0, lo_shift=12):
-    """vt_op_headconv_ln_bf16[_lo]: relu(LayerNorm(xh + lo8 * 2^-lo_shift)[search rows] . w^T + bias) -> [B*grid*grid][N] float32 (the
-    residual pair of specification v3: bf16 bits + signed bytes); fused: one launch (the band kernel normalises its rows
-    itself), else the LayerNorm kernel followed by the band kernel"""
-    xh = np.ascontiguousarray(xh_bits, np.uint16)
-    xl = np.ascontiguousarray(xl_lo8, np.int8)
-    w = np.ascontiguousarray(w_bf16_bits, np.uint16)
-    D, N = xh.shape[1], w.shape[0]
-    assert xh.shape == xl.shape == (B * ntok, D) and w.shape[1] == D
-    out = np.empty((B * grid * grid, N), np.float32)
-    u16 = POINTER(ctypes.c_uint16)
-    _check_op(ops_lib().vt_op_headconv_ln_bf16_lo(device, xh.ctypes.data_as(u16), xl.ctypes.data_as(POINTER(ctypes.c_int8)),
-                                        _f32(np.ascontiguousarray(gamma, np.float32)),
-                                        _f32(np.ascontiguousarray(beta, np.float32)), c_float(eps), ntok, off,
-                                        w.ctypes.data_as(u16), _f32(np.ascontiguousarray(bias, np.float32)), _f32(out),
-                                        B, grid, D, N, 1 if fused else 0, R, ncb, 0, None, int(lo_shift)))
-    return out
-
-
-def op_headconv_ln_bench(B, grid, D, N, ntok, off, fused=True, R=0, ncb=0, iters=50, device=0) -> float:
-    """mean microseconds of the head's first layer with the final LayerNorm (fused: one launch, else two)"""
-    us = c_float()
-    _check_op(ops_lib().vt_op_headconv_ln_bf16(device, None, None, None, None, c_float(1e-6), ntok, off, None, None, None, B, grid,
-                                        D, N, 1 if fused else 0, R, ncb, iters, byref(us)))
-    return float(us.value)
-
-
-def op_headconv_bench(B, grid, Cin, N, conv3x3=True, R=0, ncb=0, iters=50, device=0) -> float:
-    """mean microseconds per launch of the band kernel on pseudo-random operands"""
-    us = c_float()
-    _check_op(ops_lib().vt_op_headconv_bf16(device, None, None, None, None, B, grid, Cin, N, 1 if conv3x3 else 0, R, ncb,
-                                     iters, byref(us)))
-    return float(us.value)
-
-
-def op_layernorm(x, gamma, beta, device=0):
-    x = np.ascontiguousarray(x, np.float32)
-    g = np.ascontiguousarray(gamma, np.float32)
-    b = np.ascontiguousarray(beta, np.float32)
-    y = np.empty_like(x)
-    _check_op(ops_lib().vt_op_layernorm(device, _f32(x), _f32(g), _f32(b), _f32(y), x.shape[0],
-                                 x.shape[1]))
-    return y

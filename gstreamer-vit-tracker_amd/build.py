@@ -102,6 +102,7 @@ def build_hip(force: bool = False, save_temps: bool = False, stamps: bool = Fals
     headers = [os.path.join(CSRC, "vt_common.hpp"), os.path.join(CSRC, "k_gemm_util.hpp"), os.path.join(CSRC, "vt_engine.hpp"), os.path.join(CSRC, "k_cand.hpp"), os.path.join(CSRC, "k_snapshot.hpp"),
                os.path.join(CSRC, "k_preproc_dev.hpp"), os.path.join(CSRC, "k_overlay_dev.hpp"), os.path.join(CSRC, "k_result_overlay.hpp"), os.path.join(CSRC, "k_preproc_body.inc"),
                os.path.join(CSRC, "k_refresh_dev.hpp"), os.path.join(CSRC, "k_refresh_crop.inc"),
+               os.path.join(CSRC, "vt_ops_host.hpp"), os.path.join(CSRC, "vt_ops_util.hpp"),
                os.path.join(PKG, "..", "include", "vittrack_hip.h"), os.path.join(PKG, "..", "include", "vittrack_hip_ops.h")]
     objs, jobs = [], []
     for s in HIP_SOURCES + OPS_SOURCES:

@@ -1,24 +1,28 @@
 // vt_ops.hip — operator-level entry points (include/vittrack_hip_ops.h): numerics tests and tuning tools call the
 // same kernel launchers the pass uses. Linked into libvittrack_hip_ops.so only; the product library does not carry them.
-#include "vt_engine.hpp"
+// What the hooks share lives in vt_ops_host.hpp (host arithmetic) and vt_ops_util.hpp (device buffers, guard bands, timing).
+#include "vt_ops_util.hpp"
 #include "../../include/vittrack_hip_ops.h"
+
+// q, k, v [B*N][D] packed into the layouts the QKV epilogue produces: qk [B*N][2D], vt [B*H][64][npad] (perm: in the key
+// order attention mode 3 reads)
+static void pack_qkv(const uint16_t* q, const uint16_t* k, const uint16_t* v, int B, int N, int H, int npad, bool perm,
+                     std::vector<bf16_t>& qk, std::vector<bf16_t>& vt) {
+    const int D = H * 64, M = B * N;
+    qk.assign((size_t)M * 2 * D, 0);
+    vt.assign((size_t)B * H * 64 * npad, 0);
+    for (int m = 0; m < M; ++m) {
+        memcpy(&qk[(size_t)m * 2 * D], q + (size_t)m * D, (size_t)D * 2);
+        memcpy(&qk[(size_t)m * 2 * D + D], k + (size_t)m * D, (size_t)D * 2);
+        const int b = m / N, t = m % N, tp = perm ? attn_perm16(t) : t;
+        for (int c = 0; c < D; ++c)
+            vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
+    }
+}
 
 extern "C" {
 
 // ---- operator-level entry points ---------------------------------------------------------------------------
-
-// host-side helpers of the operator entry points: float32 <-> the 3-byte pair of the residual stream
-static inline bf16_t host_bf16(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float host_f32(bf16_t b) {
-    const uint32_t u = ((uint32_t)b) << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 
 // epilogue: 0 x = acc + bias, 1 x = (acc + bias) + c_inout, 4 x = (acc + bias) + pos (pos = c_inout, one
 // row per output row) - the X-epilogues: c_inout goes in and comes back through the 3-byte pair (hi + lo8 * 2^-s: bf16 and
@@ -28,22 +32,17 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
                        int M, int N, int K, int epilogue, int cfg, const float* rowstat_in, const float* colsum,
                        float* rowstat_out, float eps, int lo_shift) try {
     if (!a || !w || !c_inout || M <= 0 || N <= 0 || K <= 0) return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "gemm: lo_shift %d out of range", lo_shift);
+    if (!lo_shift_ok(lo_shift)) return set_err(VT_ERR_INVALID_ARG, "gemm: lo_shift %d out of range", lo_shift);
     if (N % 64 || K % 64) return set_err(VT_ERR_INVALID_ARG, "gemm: N and K must be multiples of 64");
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     HIPCHK(gemm_prepare()); HIPCHK(attention_prepare()); HIPCHK(headconv_prepare());
-    const size_t MN = (size_t)M * N;
-    DevBuf da, dw, db, dxh, dxl, dpos, dcb, dcs, drs, dcst, dro;
-    HIPCHK(da.alloc((size_t)M * K * 2)); HIPCHK(dw.alloc((size_t)N * K * 2)); HIPCHK(db.alloc((size_t)N * 4));
-    HIPCHK(dxh.alloc(MN * 2)); HIPCHK(dxl.alloc(MN * 2)); HIPCHK(dcb.alloc(MN * 2));
-    HIPCHK(hipMemcpy(da.p, a, (size_t)M * K * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    std::vector<float> zb((size_t)N, 0.0f);
-    HIPCHK(hipMemcpy(db.p, bias ? bias : zb.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    const size_t MN = (size_t)M * N, cnt_bytes = (size_t)((M + 255) / 256 + 1) * 4;
     GemmArgs g{};
-    g.A = (const bf16_t*)da.p; g.lda = K; g.W = (const bf16_t*)dw.p; g.ldw = K; g.bias = (const float*)db.p;
-    g.M = M; g.N = N; g.K = K; g.Xh = (bf16_t*)dxh.p; g.Xl = (uint8_t*)dxl.p; g.ldx = N; g.Cb = (bf16_t*)dcb.p; g.ldcb = N;
+    GemmOperands ops;
+    HIPCHK(ops.upload(g, a, w, bias, M, N, K, K));
+    DevArr dxh, dxl, dpos, dcb, dcs, drs, dcst, dro, dcnt;
+    HIPCHK(dcb.alloc(MN * 2));
     g.lq = lo_quant(lo_shift);
     int epi;
     switch (epilogue) {
@@ -55,45 +54,37 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
         default: return set_err(VT_ERR_INVALID_ARG, "gemm: unknown epilogue %d", epilogue);
     }
     const bool x_epi = epi == EPI_F32 || epi == EPI_RESID || epi == EPI_F32_POS;
-    // the 3-byte pair of specification v3 (vt_common.hpp): hi = bf16(x), lo8 = clamp(rint((x - hi) * 2^s), -127, 127)
-    std::vector<bf16_t> hi;
-    std::vector<int8_t> lo;
-    if (epi == EPI_RESID) {
-        hi.resize(MN); lo.resize(MN);
-        for (size_t i = 0; i < MN; ++i) {
-            hi[i] = host_bf16(c_inout[i]);
-            const float q = nearbyintf((c_inout[i] - host_f32(hi[i])) * (float)(1 << lo_shift));
-            lo[i] = (int8_t)(q < -127.0f ? -127.0f : q > 127.0f ? 127.0f : q);
-        }
-        HIPCHK(hipMemcpy(dxh.p, hi.data(), MN * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dxl.p, lo.data(), MN, hipMemcpyHostToDevice));
-    } else if (epi == EPI_F32_POS) {
-        HIPCHK(dpos.alloc(MN * 4));
-        HIPCHK(hipMemcpy(dpos.p, c_inout, MN * 4, hipMemcpyHostToDevice));
-        g.pos = (const float*)dpos.p; g.pos_rows = M;
+    std::vector<bf16_t> hi(MN);
+    std::vector<int8_t> lo(MN);
+    if (epi == EPI_RESID) {     // the addend goes in as the pair the engine would hold
+        pair_pack(c_inout, MN, lo_shift, hi.data(), lo.data());
+        HIPCHK(dxh.upload(hi.data(), MN * 2)); HIPCHK(dxl.upload(lo.data(), MN));
+    } else {
+        HIPCHK(dxh.alloc(MN * 2)); HIPCHK(dxl.alloc(MN));
     }
+    if (epi == EPI_F32_POS) {
+        HIPCHK(dpos.upload(c_inout, MN * 4));
+        g.pos = dpos.as<const float>(); g.pos_rows = M;
+    }
+    g.Xh = dxh.as<bf16_t>(); g.Xl = dxl.as<uint8_t>(); g.ldx = N; g.Cb = dcb.as<bf16_t>(); g.ldcb = N;
     if (x_epi) {
         HIPCHK(dcst.alloc((size_t)M * (N / VT_STAT_CHUNK) * 8));
-        g.cstat = (float2*)dcst.p;
+        g.cstat = dcst.as<float2>();
     } else if (rowstat_in) {
         if (!colsum) return set_err(VT_ERR_INVALID_ARG, "gemm: rowstat without colsum");
-        HIPCHK(drs.alloc((size_t)M * 8 + 16)); HIPCHK(dcs.alloc((size_t)N * 4));
-        HIPCHK(hipMemcpy(drs.p, rowstat_in, (size_t)M * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dcs.p, colsum, (size_t)N * 4, hipMemcpyHostToDevice));
-        g.rowstat = (const float2*)drs.p; g.colsum = (const float*)dcs.p;
+        HIPCHK(drs.upload(rowstat_in, (size_t)M * 8, 16)); HIPCHK(dcs.upload(colsum, (size_t)N * 4));
+        g.rowstat = drs.as<const float2>(); g.colsum = dcs.as<const float>();
     }
     // X-epilogues on the 256x256 kernel finalize the row terms themselves (last workgroup of each row panel)
-    DevBuf dcnt;
     bool fused = false;
-    if (cfg >= 0) { g.tile_order = (cfg >> 8) & 3; cfg &= 0xff; }   // bits 8-9 of a given configuration: the XCD tile order (1 rows, 2 columns)
+    const TileCfg tc = split_cfg(cfg);
+    g.tile_order = tc.order; cfg = tc.cfg;
     if (x_epi && rowstat_out) {
-        HIPCHK(dro.alloc((size_t)M * 8));
-        HIPCHK(dcnt.alloc((size_t)((M + 255) / 256 + 1) * 4));
-        HIPCHK(hipMemset(dcnt.p, 0, (size_t)((M + 255) / 256 + 1) * 4));
-        HIPCHK(hipMemset(dro.p, 0xff, (size_t)M * 8));
+        HIPCHK(dro.filled((size_t)M * 8, 0xff));
+        HIPCHK(dcnt.zeros(cnt_bytes));
         const int eff = cfg < 0 ? gemm_effective_config(g, epi) : cfg;
         if (eff >= GEMM_CFG_256_MIN) {
-            g.rowstat_out = (float2*)dro.p; g.panel_cnt = (unsigned*)dcnt.p; g.ln_eps = eps;
+            g.rowstat_out = dro.as<float2>(); g.panel_cnt = dcnt.as<unsigned>(); g.ln_eps = eps;
             fused = true;
         }
     }
@@ -101,31 +92,20 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
     else if (launch_gemm_cfg(g, epi, cfg, nullptr) != hipSuccess)
         return set_err(VT_ERR_INVALID_ARG, "gemm: tile configuration %d does not fit M=%d N=%d K=%d", cfg, M, N, K);
     if (x_epi && rowstat_out && !fused)
-        HIPCHK(launch_rowstat_finalize(g.cstat, (float2*)dro.p, M, N / VT_STAT_CHUNK, eps, nullptr));
+        HIPCHK(launch_rowstat_finalize(g.cstat, dro.as<float2>(), M, N / VT_STAT_CHUNK, eps, nullptr));
     if (fused) {      // launch it twice more: the counters must come back to zero by themselves
         for (int rep = 0; rep < 2 && (epi == EPI_F32 || epi == EPI_F32_POS); ++rep) HIPCHK(launch_gemm_cfg(g, epi, cfg < 0 ? gemm_effective_config(g, epi) : cfg, nullptr));
     }
     HIPCHK(hipDeviceSynchronize());
     if (x_epi) {
-        hi.resize(MN); lo.resize(MN);
-        HIPCHK(hipMemcpy(hi.data(), dxh.p, MN * 2, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(lo.data(), dxl.p, MN, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < MN; ++i) c_inout[i] = host_f32(hi[i]) + (float)lo[i] * g.lq.q;
-        if (rowstat_out) HIPCHK(hipMemcpy(rowstat_out, dro.p, (size_t)M * 8, hipMemcpyDeviceToHost));
+        HIPCHK(dxh.download(hi.data())); HIPCHK(dxl.download(lo.data()));
+        pair_value(hi.data(), lo.data(), MN, g.lq.q, c_inout);
+        if (rowstat_out) HIPCHK(dro.download(rowstat_out));
     } else {
-        std::vector<bf16_t> tmp(MN);
-        HIPCHK(hipMemcpy(tmp.data(), dcb.p, tmp.size() * 2, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < tmp.size(); ++i) c_inout[i] = host_f32(tmp[i]);
+        HIPCHK(download_bf16(dcb.p, MN, c_inout));
     }
     return VT_OK;
 } VT_NOTHROW_INT
-
-int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias, float* c_inout,
-                    int M, int N, int K, int epilogue, int cfg, const float* rowstat_in, const float* colsum,
-                    float* rowstat_out, float eps) {
-    return vt_op_gemm_bf16_lo(device_id, a, w, bias, c_inout, M, N, K, epilogue, cfg, rowstat_in, colsum, rowstat_out, eps,
-                              VT_LO_SHIFT_DEFAULT);
-}
 
 // The residual GEMM of the 256x256 kernel on a pair given as it is stored, with the remapped addend read of the last
 // encoder block (GemmArgs.seg_rows / seg_skip / Xh_in): see include/vittrack_hip_ops.h
@@ -134,7 +114,7 @@ int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* 
                               float* rowstat_out, int M, int N, int K, int seg_rows, int seg_skip, float eps, int lo_shift) try {
     if (!a || !w || !xh_in || !xl_in || !xh_out || !xl_out || M <= 0 || N <= 0 || K <= 0 || rows_in <= 0 || seg_rows < 0 || seg_skip < 0)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "gemm: lo_shift %d out of range", lo_shift);
+    if (!lo_shift_ok(lo_shift)) return set_err(VT_ERR_INVALID_ARG, "gemm: lo_shift %d out of range", lo_shift);
     // every input row the kernel may read exists: the last output row's place in the input layout
     const long long last_in = seg_rows > 0 ? (long long)(M - 1) + ((long long)((M - 1) / seg_rows) + 1) * seg_skip : (long long)M - 1;
     if (last_in >= rows_in) return set_err(VT_ERR_INVALID_ARG, "gemm: the input pair has %d rows, the addend read reaches row %lld", rows_in, last_in);
@@ -142,38 +122,30 @@ int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* 
     DEVICE_SCOPE(device_id);
     HIPCHK(gemm_prepare());
     const size_t MN = (size_t)M * N, IN = (size_t)rows_in * N, nchunk = (size_t)N / VT_STAT_CHUNK;
-    DevBuf da, dw, db, dih, dil, doh, dol, dcst, dro, dcnt;
-    HIPCHK(da.alloc((size_t)M * K * 2)); HIPCHK(dw.alloc((size_t)N * K * 2)); HIPCHK(db.alloc((size_t)N * 4));
-    HIPCHK(dih.alloc(IN * 2)); HIPCHK(dil.alloc(IN)); HIPCHK(doh.alloc(MN * 2)); HIPCHK(dol.alloc(MN));
-    HIPCHK(dcst.alloc((size_t)M * nchunk * 8)); HIPCHK(dro.alloc((size_t)M * 8));
-    HIPCHK(dcnt.alloc((size_t)((M + 255) / 256 + 1) * 4));
-    HIPCHK(hipMemcpy(da.p, a, (size_t)M * K * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    std::vector<float> zb((size_t)N, 0.0f);
-    HIPCHK(hipMemcpy(db.p, bias ? bias : zb.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dih.p, xh_in, IN * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dil.p, xl_in, IN, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dcnt.p, 0, (size_t)((M + 255) / 256 + 1) * 4));
-    HIPCHK(hipMemset(dcst.p, 0xff, (size_t)M * nchunk * 8)); HIPCHK(hipMemset(dro.p, 0xff, (size_t)M * 8));
     GemmArgs g{};
-    g.A = (const bf16_t*)da.p; g.lda = K; g.W = (const bf16_t*)dw.p; g.ldw = K; g.bias = (const float*)db.p;
-    g.M = M; g.N = N; g.K = K; g.Xh = (bf16_t*)doh.p; g.Xl = (uint8_t*)dol.p; g.ldx = N;
-    g.cstat = (float2*)dcst.p; g.rowstat_out = (float2*)dro.p; g.panel_cnt = (unsigned*)dcnt.p; g.ln_eps = eps;
-    g.lq = lo_quant(lo_shift);
+    GemmOperands ops;
+    HIPCHK(ops.upload(g, a, w, bias, M, N, K, K));
+    DevArr dih, dil, doh, dol, dcst, dro, dcnt;
+    HIPCHK(dih.upload(xh_in, IN * 2)); HIPCHK(dil.upload(xl_in, IN));
+    HIPCHK(dcnt.zeros((size_t)((M + 255) / 256 + 1) * 4));
+    HIPCHK(dcst.filled((size_t)M * nchunk * 8, 0xff)); HIPCHK(dro.filled((size_t)M * 8, 0xff));
     if (seg_rows > 0) {     // addend from the input pair through the remap, output compact
-        g.Xh_in = (const bf16_t*)dih.p; g.Xl_in = (const uint8_t*)dil.p; g.seg_rows = seg_rows; g.seg_skip = seg_skip;
-        HIPCHK(hipMemset(doh.p, 0xff, MN * 2)); HIPCHK(hipMemset(dol.p, 0xff, MN));
+        g.Xh_in = dih.as<const bf16_t>(); g.Xl_in = dil.as<const uint8_t>(); g.seg_rows = seg_rows; g.seg_skip = seg_skip;
+        HIPCHK(doh.filled(MN * 2, 0xff)); HIPCHK(dol.filled(MN, 0xff));
     } else {                // the launch as it always was: rows 0 .. M-1 of the pair, read and written in place
-        HIPCHK(hipMemcpy(doh.p, dih.p, MN * 2, hipMemcpyDeviceToDevice));
-        HIPCHK(hipMemcpy(dol.p, dil.p, MN, hipMemcpyDeviceToDevice));
+        HIPCHK(doh.alloc(MN * 2)); HIPCHK(dol.alloc(MN));
+        HIPCHK(hipMemcpy(doh.p, dih.p, doh.bytes, hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(dol.p, dil.p, dol.bytes, hipMemcpyDeviceToDevice));
     }
+    g.Xh = doh.as<bf16_t>(); g.Xl = dol.as<uint8_t>(); g.ldx = N;
+    g.cstat = dcst.as<float2>(); g.rowstat_out = dro.as<float2>(); g.panel_cnt = dcnt.as<unsigned>(); g.ln_eps = eps;
+    g.lq = lo_quant(lo_shift);
     if (launch_gemm_cfg(g, EPI_RESID, GEMM_CFG_256P4, nullptr) != hipSuccess)
         return set_err(VT_ERR_INVALID_ARG, "gemm: the 256x256 kernel does not take M=%d N=%d K=%d seg_rows=%d seg_skip=%d", M, N, K, seg_rows, seg_skip);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(xh_out, doh.p, MN * 2, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(xl_out, dol.p, MN, hipMemcpyDeviceToHost));
-    if (cstat_out) HIPCHK(hipMemcpy(cstat_out, dcst.p, (size_t)M * nchunk * 8, hipMemcpyDeviceToHost));
-    if (rowstat_out) HIPCHK(hipMemcpy(rowstat_out, dro.p, (size_t)M * 8, hipMemcpyDeviceToHost));
+    HIPCHK(doh.download(xh_out)); HIPCHK(dol.download(xl_out));
+    if (cstat_out) HIPCHK(dcst.download(cstat_out));
+    if (rowstat_out) HIPCHK(dro.download(rowstat_out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -186,66 +158,47 @@ int vt_op_gemm_bench(int device_id, int M, int N, int K, int epilogue, int cfg, 
     DEVICE_SCOPE(device_id);
     HIPCHK(gemm_prepare()); HIPCHK(attention_prepare()); HIPCHK(headconv_prepare());
     const int D = N / 3, tokens = 4 * ((M + 3) / 4), npad = (tokens + 63) / 64 * 64;
-    DevBuf da, dw, db, dc, dcb, dvt, dxl, dcst, drs;
-    HIPCHK(da.alloc((size_t)M * K * 2)); HIPCHK(dw.alloc((size_t)N * K * 2)); HIPCHK(db.alloc((size_t)N * 4));
-    HIPCHK(dc.alloc((size_t)M * N * 4)); HIPCHK(dcb.alloc((size_t)M * N * 2)); HIPCHK(dxl.alloc((size_t)M * N * 2));
-    HIPCHK(dcst.alloc((size_t)M * (N / VT_STAT_CHUNK) * 8)); HIPCHK(drs.alloc((size_t)M * 8 + 16));
-    HIPCHK(dvt.alloc((size_t)(N / 64 + 1) * 64 * npad * 2));
     std::vector<bf16_t> ha((size_t)M * K), hw((size_t)N * K);
-    uint32_t seed = 12345u;
-    auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (bf16_t)(0x3c00u + ((seed >> 9) & 0x3ffu) + ((seed >> 3) & 0x8000u)); };
-    for (auto& v : ha) v = rnd();
-    for (auto& v : hw) v = rnd();
-    HIPCHK(hipMemcpy(da.p, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(db.p, 0, (size_t)N * 4));
-    HIPCHK(hipMemset(dc.p, 0, (size_t)M * N * 4));
-    HIPCHK(hipMemset(dcb.p, 0, (size_t)M * N * 2)); HIPCHK(hipMemset(dxl.p, 0, (size_t)M * N * 2));
+    fill_lcg_bf16(hw.data(), hw.size(), fill_lcg_bf16(ha.data(), ha.size(), 12345u));
+    GemmArgs g{};
+    GemmOperands ops;           // the bias: zeros
+    HIPCHK(ops.upload(g, ha.data(), hw.data(), nullptr, M, N, K, K));
+    DevArr dc, dcb, dvt, dxl, dcst, drs;
+    HIPCHK(dc.zeros((size_t)M * N * 4)); HIPCHK(dcb.zeros((size_t)M * N * 2)); HIPCHK(dxl.zeros((size_t)M * N * 2));
+    HIPCHK(dcst.alloc((size_t)M * (N / VT_STAT_CHUNK) * 8));
+    HIPCHK(dvt.alloc((size_t)(N / 64 + 1) * 64 * npad * 2));
     {   // folded-LayerNorm row terms as the engine passes them to the QKV / fc1 GEMMs: (1, 0) per row
         std::vector<float> rs((size_t)M * 2);
         for (int i = 0; i < M; ++i) { rs[2 * (size_t)i] = 1.0f; rs[2 * (size_t)i + 1] = 0.0f; }
-        HIPCHK(hipMemcpy(drs.p, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(drs.upload(rs.data(), rs.size() * 4, 16));
     }
-    GemmArgs g{};
-    g.A = (const bf16_t*)da.p; g.lda = K; g.W = (const bf16_t*)dw.p; g.ldw = K; g.bias = (const float*)db.p;
-    g.M = M; g.N = N; g.K = K; g.Cb = (bf16_t*)dcb.p; g.ldcb = N;
+    g.Cb = dcb.as<bf16_t>(); g.ldcb = N;
     const bool x_epi = epilogue == EPI_F32 || epilogue == EPI_RESID || epilogue == EPI_F32_POS;
-    DevBuf dcnt, dro;
+    DevArr dcnt, dro;
     if (x_epi) {      // as the engine launches it: chunk partials + the row terms finalized by the last workgroup of each panel
-        g.Xh = (bf16_t*)dcb.p; g.Xl = (uint8_t*)dxl.p; g.ldx = N; g.cstat = (float2*)dcst.p;
-        HIPCHK(dcnt.alloc((size_t)((M + 255) / 256 + 1) * 4)); HIPCHK(dro.alloc((size_t)M * 8 + 16));
-        HIPCHK(hipMemset(dcnt.p, 0, (size_t)((M + 255) / 256 + 1) * 4));
-        g.rowstat_out = (float2*)dro.p; g.panel_cnt = (unsigned*)dcnt.p; g.ln_eps = 1e-6f;
+        g.Xh = dcb.as<bf16_t>(); g.Xl = dxl.as<uint8_t>(); g.ldx = N; g.cstat = dcst.as<float2>();
+        HIPCHK(dcnt.zeros((size_t)((M + 255) / 256 + 1) * 4)); HIPCHK(dro.alloc((size_t)M * 8 + 16));
+        g.rowstat_out = dro.as<float2>(); g.panel_cnt = dcnt.as<unsigned>(); g.ln_eps = 1e-6f;
     }
-    else if (epilogue == EPI_QKV || epilogue == EPI_GELU_BF16) { g.rowstat = (const float2*)drs.p; g.colsum = (const float*)db.p; }
-    g.pos = (const float*)dc.p; g.pos_rows = M;
-    g.qk = (bf16_t*)dcb.p; g.vt = (bf16_t*)dvt.p; g.tokens = tokens; g.npad = npad; g.D = D;
+    else if (epilogue == EPI_QKV || epilogue == EPI_GELU_BF16) { g.rowstat = drs.as<const float2>(); g.colsum = ops.bias.as<const float>(); }
+    g.pos = dc.as<const float>(); g.pos_rows = M;
+    g.qk = dcb.as<bf16_t>(); g.vt = dvt.as<bf16_t>(); g.tokens = tokens; g.npad = npad; g.D = D;
     if (epilogue == EPI_QKV && (N % 192 || tokens != M)) return set_err(VT_ERR_INVALID_ARG, "qkv bench: N = 3D, D %% 64 == 0, M %% 4 == 0");
-    if (cfg >= 0) { g.tile_order = (cfg >> 8) & 3; cfg &= 0xff; }   // sweeps: bits 8-9 force the XCD tile order (1 rows, 2 columns)
+    const TileCfg tc = split_cfg(cfg);      // sweeps force the XCD tile order
+    g.tile_order = tc.order; cfg = tc.cfg;
     if (cfg < 0) cfg = gemm_pick_config(M, N, K, epilogue);
-    DevBuf ddbg;
+    DevArr ddbg;
     const size_t dbg_words = (size_t)((M + 63) / 64) * (N / 64) * 8 * 4;
 #ifdef VT_STAMPS   // diagnostic builds only: per-wave cycle sums of the main loop
-    HIPCHK(ddbg.alloc(dbg_words * 8));
-    HIPCHK(hipMemset(ddbg.p, 0, dbg_words * 8));
-    g.dbg = (unsigned long long*)ddbg.p;
+    HIPCHK(ddbg.zeros(dbg_words * 8));
+    g.dbg = ddbg.as<unsigned long long>();
 #else
     (void)dbg_words;
 #endif
-    for (int i = 0; i < 3; ++i) HIPCHK(launch_gemm_cfg(g, epilogue, cfg, nullptr));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) HIPCHK(launch_gemm_cfg(g, epilogue, cfg, nullptr));
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *us_out = ms * 1000.0f / iters;
+    HIPCHK(time_launches(iters, [&] { return launch_gemm_cfg(g, epilogue, cfg, nullptr); }, us_out));
     if (g.dbg) {   // diagnostic build: mean per-wave cycle split of the main loop
         std::vector<unsigned long long> h(dbg_words);
-        HIPCHK(hipMemcpy(h.data(), ddbg.p, dbg_words * 8, hipMemcpyDeviceToHost));
+        HIPCHK(ddbg.download(h.data()));
         double s[4] = {0, 0, 0, 0};
         size_t n = 0;
         for (size_t i = 0; i + 3 < dbg_words; i += 4)
@@ -266,73 +219,29 @@ int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const fl
     DEVICE_SCOPE(device_id);
     HIPCHK(gemm_prepare()); HIPCHK(attention_prepare()); HIPCHK(headconv_prepare());
     const int M = B * tokens, H = D / 64, npad = (tokens + 63) / 64 * 64;
-    DevBuf da, dw, db, dqk, dvt;
-    HIPCHK(da.alloc((size_t)M * D * 2)); HIPCHK(dw.alloc((size_t)3 * D * D * 2)); HIPCHK(db.alloc((size_t)3 * D * 4));
-    HIPCHK(dqk.alloc((size_t)M * 2 * D * 2)); HIPCHK(dvt.alloc((size_t)B * H * 64 * npad * 2));
-    HIPCHK(hipMemcpy(da.p, a, (size_t)M * D * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, w, (size_t)3 * D * D * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, bias, (size_t)3 * D * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dvt.p, 0, (size_t)B * H * 64 * npad * 2));
+    const size_t n_qk = (size_t)M * 2 * D, n_vt = (size_t)B * H * 64 * npad;
     GemmArgs g{};
-    g.A = (const bf16_t*)da.p; g.lda = D; g.W = (const bf16_t*)dw.p; g.ldw = D; g.bias = (const float*)db.p;
-    g.M = M; g.N = 3 * D; g.K = D; g.qk = (bf16_t*)dqk.p; g.vt = (bf16_t*)dvt.p; g.tokens = tokens; g.npad = npad; g.D = D;
+    GemmOperands ops;
+    HIPCHK(ops.upload(g, a, w, bias, M, 3 * D, D, D));
+    DevArr dqk, dvt, drs, dcs;
+    HIPCHK(dqk.alloc(n_qk * 2)); HIPCHK(dvt.zeros(n_vt * 2));
+    g.qk = dqk.as<bf16_t>(); g.vt = dvt.as<bf16_t>(); g.tokens = tokens; g.npad = npad; g.D = D;
     g.vt_perm = vt_perm ? 1 : 0;   // 1: the key order attention mode 3 reads
-    DevBuf drs, dcs;
     if (rowstat_in) {              // folded LayerNorm: [M][2] row terms, [3D] column sums
         if (!colsum) return set_err(VT_ERR_INVALID_ARG, "qkv: rowstat without colsum");
-        HIPCHK(drs.alloc((size_t)M * 8 + 16)); HIPCHK(dcs.alloc((size_t)3 * D * 4));
-        HIPCHK(hipMemcpy(drs.p, rowstat_in, (size_t)M * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dcs.p, colsum, (size_t)3 * D * 4, hipMemcpyHostToDevice));
-        g.rowstat = (const float2*)drs.p; g.colsum = (const float*)dcs.p;
+        HIPCHK(drs.upload(rowstat_in, (size_t)M * 8, 16)); HIPCHK(dcs.upload(colsum, (size_t)3 * D * 4));
+        g.rowstat = drs.as<const float2>(); g.colsum = dcs.as<const float>();
     }
-    if (cfg >= 0) { g.tile_order = (cfg >> 8) & 3; cfg &= 0xff; }   // as in vt_op_gemm_bf16
+    const TileCfg tc = split_cfg(cfg);
+    g.tile_order = tc.order; cfg = tc.cfg;
     if (cfg < 0) HIPCHK(launch_gemm(g, EPI_QKV, nullptr));
     else if (launch_gemm_cfg(g, EPI_QKV, cfg, nullptr) != hipSuccess)
         return set_err(VT_ERR_INVALID_ARG, "qkv: tile configuration %d does not fit this shape", cfg);
     HIPCHK(hipDeviceSynchronize());
-    auto widen = [](const DevBuf& d, size_t count, float* out) -> hipError_t {
-        std::vector<bf16_t> tmp(count);
-        hipError_t e = hipMemcpy(tmp.data(), d.p, count * 2, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-        for (size_t i = 0; i < count; ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
-        return hipSuccess;
-    };
-    HIPCHK(widen(dqk, (size_t)M * 2 * D, qk_out));
-    HIPCHK(widen(dvt, (size_t)B * H * 64 * npad, vt_out));
+    HIPCHK(download_bf16(dqk.p, n_qk, qk_out));
+    HIPCHK(download_bf16(dvt.p, n_vt, vt_out));
     return VT_OK;
 } VT_NOTHROW_INT
-
-// The output buffer of an attention hook between two guard bands: the bands carry a byte pattern, the output 0xff (a
-// bf16 NaN), so a row the kernel never stores arrives as NaN instead of whatever a reused allocation held, and a store
-// just outside the buffer (a slip in a row or block index) is reported instead of landing in a neighbour's memory.
-struct GuardedOut {
-    static constexpr size_t kGuard = 4096;      // bytes on each side; keeps out() 4 KiB aligned
-    static constexpr int kPattern = 0xA5;
-    DevBuf buf;
-    size_t bytes = 0;
-    hipError_t alloc(size_t n) {
-        bytes = n;
-        hipError_t e = buf.alloc(n + 2 * kGuard);
-        if (e != hipSuccess) return e;
-        e = hipMemset(buf.p, kPattern, n + 2 * kGuard);
-        if (e != hipSuccess) return e;
-        return hipMemset(out(), 0xff, n);
-    }
-    void* out() const { return static_cast<char*>(buf.p) + kGuard; }
-    // after the synchronise: *where = 0 when both bands are intact, otherwise the signed distance in bytes of the first
-    // changed byte from the output (negative: in front of it, positive: 1 = the first byte behind it)
-    hipError_t check(long* where) const {
-        std::vector<unsigned char> g(2 * kGuard);
-        hipError_t e = hipMemcpy(g.data(), buf.p, kGuard, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-        e = hipMemcpy(g.data() + kGuard, static_cast<char*>(buf.p) + kGuard + bytes, kGuard, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-        *where = 0;
-        for (size_t i = 0; i < 2 * kGuard && !*where; ++i)
-            if (g[i] != kPattern) *where = i < kGuard ? (long)i - (long)kGuard : (long)(i - kGuard) + 1;
-        return hipSuccess;
-    }
-};
 
 int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, const uint16_t* v, float* out,
                          int B, int N, int H, int mode) try {
@@ -340,31 +249,20 @@ int vt_op_attention_bf16(int device_id, const uint16_t* q, const uint16_t* k, co
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     HIPCHK(attention_prepare());
-    const int D = H * 64, M = B * N, npad = (N + 63) / 64 * 64;
-    // host-side packing into the layouts the QKV epilogue produces
+    const int npad = (N + 63) / 64 * 64;
+    const size_t n_out = (size_t)B * N * H * 64;
     if (mode < 0) mode = attention_pick_mode(N, npad);
-    const bool perm = attention_vt_perm(mode) != 0;
-    std::vector<bf16_t> qk((size_t)M * 2 * D), vt((size_t)B * H * 64 * npad, 0);
-    for (int m = 0; m < M; ++m) {
-        memcpy(&qk[(size_t)m * 2 * D], q + (size_t)m * D, (size_t)D * 2);
-        memcpy(&qk[(size_t)m * 2 * D + D], k + (size_t)m * D, (size_t)D * 2);
-        const int b = m / N, t = m % N, tp = perm ? attn_perm16(t) : t;
-        for (int c = 0; c < D; ++c)
-            vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
-    }
-    DevBuf dqk, dvt;
+    std::vector<bf16_t> qk, vt;
+    pack_qkv(q, k, v, B, N, H, npad, attention_vt_perm(mode) != 0, qk, vt);
+    DevArr dqk, dvt;
     GuardedOut dout;
-    HIPCHK(dqk.alloc(qk.size() * 2)); HIPCHK(dvt.alloc(vt.size() * 2)); HIPCHK(dout.alloc((size_t)M * D * 2));
-    HIPCHK(hipMemcpy(dqk.p, qk.data(), qk.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dvt.p, vt.data(), vt.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(launch_attention_mode((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.out(), B, N, H, npad, mode, nullptr));
+    HIPCHK(dqk.upload(qk.data(), qk.size() * 2)); HIPCHK(dvt.upload(vt.data(), vt.size() * 2)); HIPCHK(dout.alloc(n_out * 2));
+    HIPCHK(launch_attention_mode(dqk.as<const bf16_t>(), dvt.as<const bf16_t>(), dout.as<bf16_t>(), B, N, H, npad, mode, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    long where = 0;
-    HIPCHK(dout.check(&where));
-    if (where) return set_err(VT_ERR_HIP, "attention mode %d wrote outside its output: guard byte %ld changed", mode, where);
-    std::vector<bf16_t> tmp((size_t)M * D);
-    HIPCHK(hipMemcpy(tmp.data(), dout.out(), tmp.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
+    char what[48];
+    snprintf(what, sizeof(what), "attention mode %d", mode);
+    if (int rc = guards_intact(what, {{&dout, "output"}})) return rc;
+    HIPCHK(download_bf16(dout.out(), n_out, out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -376,29 +274,19 @@ int vt_op_attention_queries_bf16(int device_id, const uint16_t* q, const uint16_
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     HIPCHK(attention_prepare());
-    const int D = H * 64, M = B * N, npad = (N + 63) / 64 * 64;
-    std::vector<bf16_t> qk((size_t)M * 2 * D), vt((size_t)B * H * 64 * npad, 0);
-    for (int m = 0; m < M; ++m) {       // the layouts the QKV epilogue produces for mode 3
-        memcpy(&qk[(size_t)m * 2 * D], q + (size_t)m * D, (size_t)D * 2);
-        memcpy(&qk[(size_t)m * 2 * D + D], k + (size_t)m * D, (size_t)D * 2);
-        const int b = m / N, tp = attn_perm16(m % N);
-        for (int c = 0; c < D; ++c)
-            vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
-    }
-    const size_t MO = (size_t)B * nq * D;
-    DevBuf dqk, dvt;
+    const int npad = (N + 63) / 64 * 64;
+    const size_t n_out = (size_t)B * nq * H * 64;
+    std::vector<bf16_t> qk, vt;
+    pack_qkv(q, k, v, B, N, H, npad, true, qk, vt);
+    DevArr dqk, dvt;
     GuardedOut dout;
-    HIPCHK(dqk.alloc(qk.size() * 2)); HIPCHK(dvt.alloc(vt.size() * 2)); HIPCHK(dout.alloc(MO * 2));
-    HIPCHK(hipMemcpy(dqk.p, qk.data(), qk.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dvt.p, vt.data(), vt.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(launch_attention_queries((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.out(), B, N, H, npad, q0, nq, nullptr));
+    HIPCHK(dqk.upload(qk.data(), qk.size() * 2)); HIPCHK(dvt.upload(vt.data(), vt.size() * 2)); HIPCHK(dout.alloc(n_out * 2));
+    HIPCHK(launch_attention_queries(dqk.as<const bf16_t>(), dvt.as<const bf16_t>(), dout.as<bf16_t>(), B, N, H, npad, q0, nq, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    long where = 0;
-    HIPCHK(dout.check(&where));
-    if (where) return set_err(VT_ERR_HIP, "attention on queries %d..%d wrote outside its output: guard byte %ld changed", q0, q0 + nq - 1, where);
-    std::vector<bf16_t> tmp(MO);
-    HIPCHK(hipMemcpy(tmp.data(), dout.out(), tmp.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
+    char what[64];
+    snprintf(what, sizeof(what), "attention on queries %d..%d", q0, q0 + nq - 1);
+    if (int rc = guards_intact(what, {{&dout, "output"}})) return rc;
+    HIPCHK(download_bf16(dout.out(), n_out, out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -411,27 +299,12 @@ int vt_op_attention_bench(int device_id, int B, int N, int H, int mode, int iter
     HIPCHK(attention_prepare());
     const int D = H * 64, M = B * N, npad = (N + 63) / 64 * 64;
     std::vector<bf16_t> qk((size_t)M * 2 * D), vt((size_t)B * H * 64 * npad);
-    uint32_t seed = 777u;
-    auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (bf16_t)(0x3c00u + ((seed >> 9) & 0x3ffu) + ((seed >> 3) & 0x8000u)); };
-    for (auto& v : qk) v = rnd();
-    for (auto& v : vt) v = rnd();
-    DevBuf dqk, dvt, dout;
-    HIPCHK(dqk.alloc(qk.size() * 2)); HIPCHK(dvt.alloc(vt.size() * 2)); HIPCHK(dout.alloc((size_t)M * D * 2));
-    HIPCHK(hipMemcpy(dqk.p, qk.data(), qk.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dvt.p, vt.data(), vt.size() * 2, hipMemcpyHostToDevice));
-    for (int i = 0; i < 3; ++i)
-        HIPCHK(launch_attention_mode((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.p, B, N, H, npad, mode, nullptr));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i)
-        HIPCHK(launch_attention_mode((const bf16_t*)dqk.p, (const bf16_t*)dvt.p, (bf16_t*)dout.p, B, N, H, npad, mode, nullptr));
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *us_out = ms * 1000.0f / iters;
+    fill_lcg_bf16(vt.data(), vt.size(), fill_lcg_bf16(qk.data(), qk.size(), 777u));
+    DevArr dqk, dvt, dout;
+    HIPCHK(dqk.upload(qk.data(), qk.size() * 2)); HIPCHK(dvt.upload(vt.data(), vt.size() * 2)); HIPCHK(dout.alloc((size_t)M * D * 2));
+    HIPCHK(time_launches(iters, [&] {
+        return launch_attention_mode(dqk.as<const bf16_t>(), dvt.as<const bf16_t>(), dout.as<bf16_t>(), B, N, H, npad, mode, nullptr);
+    }, us_out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -439,24 +312,11 @@ int vt_op_nv12_to_rgb8_bench(int device_id, int w, int h, int iters, float* us_o
     if (w < 2 || h < 2 || w > 16384 || h > 16384 || iters < 1 || !us_out) return set_err(VT_ERR_INVALID_ARG, "bad argument");
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
-    const size_t in_bytes = nv12_bytes_read(w, h) + 16, out_bytes = (size_t)w * h * 3;
-    DevBuf din, dout;
-    HIPCHK(din.alloc(in_bytes)); HIPCHK(dout.alloc(out_bytes));
-    std::vector<uint8_t> host(in_bytes);
-    uint32_t seed = 2463534242u;
-    for (auto& v : host) { seed ^= seed << 13; seed ^= seed >> 17; seed ^= seed << 5; v = (uint8_t)seed; }
-    HIPCHK(hipMemcpy(din.p, host.data(), in_bytes, hipMemcpyHostToDevice));
-    for (int i = 0; i < 3; ++i) HIPCHK(launch_nv12_to_rgb8((const uint8_t*)din.p, w, h, (uint8_t*)dout.p, nullptr));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) HIPCHK(launch_nv12_to_rgb8((const uint8_t*)din.p, w, h, (uint8_t*)dout.p, nullptr));
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *us_out = ms * 1000.0f / iters;
+    std::vector<uint8_t> host(nv12_bytes_read(w, h) + 16);
+    fill_xorshift_u8(host.data(), host.size());
+    DevArr din, dout;
+    HIPCHK(din.upload(host.data(), host.size())); HIPCHK(dout.alloc((size_t)w * h * 3));
+    HIPCHK(time_launches(iters, [&] { return launch_nv12_to_rgb8(din.as<const uint8_t>(), w, h, dout.as<uint8_t>(), nullptr); }, us_out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -465,29 +325,18 @@ int vt_op_nv12_to_rgb8_batch_bench(int device_id, int w, int h, int n, int iters
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t in_bytes = (nv12_bytes_read(w, h) + 16 + 255) & ~(size_t)255, out_bytes = ((size_t)w * h * 3 + 255) & ~(size_t)255;
-    DevBuf din, dout;
+    DevArr din, dout;
     HIPCHK(din.alloc(in_bytes * n)); HIPCHK(dout.alloc(out_bytes * n));
     std::vector<uint8_t> host(in_bytes);
-    uint32_t seed = 2463534242u;
-    for (auto& v : host) { seed ^= seed << 13; seed ^= seed >> 17; seed ^= seed << 5; v = (uint8_t)seed; }
+    fill_xorshift_u8(host.data(), host.size());
     std::vector<const uint8_t*> ins((size_t)n);
     std::vector<uint8_t*> outs((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        ins[(size_t)i] = (const uint8_t*)din.p + (size_t)i * in_bytes;
-        outs[(size_t)i] = (uint8_t*)dout.p + (size_t)i * out_bytes;
+    for (int i = 0; i < n; ++i) {       // every frame the same bytes
+        ins[(size_t)i] = din.as<const uint8_t>() + (size_t)i * in_bytes;
+        outs[(size_t)i] = dout.as<uint8_t>() + (size_t)i * out_bytes;
         HIPCHK(hipMemcpy((void*)ins[(size_t)i], host.data(), in_bytes, hipMemcpyHostToDevice));
     }
-    for (int i = 0; i < 3; ++i) HIPCHK(launch_nv12_to_rgb8_batch(ins.data(), outs.data(), n, w, h, nullptr));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) HIPCHK(launch_nv12_to_rgb8_batch(ins.data(), outs.data(), n, w, h, nullptr));
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *us_out = ms * 1000.0f / iters;
+    HIPCHK(time_launches(iters, [&] { return launch_nv12_to_rgb8_batch(ins.data(), outs.data(), n, w, h, nullptr); }, us_out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -495,16 +344,12 @@ int vt_op_layernorm(int device_id, const float* x, const float* gamma, const flo
     if (!x || !gamma || !beta || !y || M <= 0 || D % 128) return set_err(VT_ERR_INVALID_ARG, "bad argument");
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
-    DevBuf dx, dg, db, dy;
-    HIPCHK(dx.alloc((size_t)M * D * 4)); HIPCHK(dg.alloc((size_t)D * 4)); HIPCHK(db.alloc((size_t)D * 4)); HIPCHK(dy.alloc((size_t)M * D * 2));
-    HIPCHK(hipMemcpy(dx.p, x, (size_t)M * D * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dg.p, gamma, (size_t)D * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, beta, (size_t)D * 4, hipMemcpyHostToDevice));
-    HIPCHK(launch_layernorm((const float*)dx.p, (const float*)dg.p, (const float*)db.p, (bf16_t*)dy.p, M, D, M, 0, 0, 1e-6f, nullptr));
+    const size_t MD = (size_t)M * D;
+    DevArr dx, dg, db, dy;
+    HIPCHK(dx.upload(x, MD * 4)); HIPCHK(dg.upload(gamma, (size_t)D * 4)); HIPCHK(db.upload(beta, (size_t)D * 4)); HIPCHK(dy.alloc(MD * 2));
+    HIPCHK(launch_layernorm(dx.as<const float>(), dg.as<const float>(), db.as<const float>(), dy.as<bf16_t>(), M, D, M, 0, 0, 1e-6f, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    std::vector<bf16_t> tmp((size_t)M * D);
-    HIPCHK(hipMemcpy(tmp.data(), dy.p, tmp.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(y + i, &u, 4); }
+    HIPCHK(download_bf16(dy.p, MD, y));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -519,33 +364,27 @@ int vt_op_conv3x3_relu_bf16(int device_id, const uint16_t* t, const uint16_t* w,
     DEVICE_SCOPE(device_id);
     HIPCHK(gemm_prepare());
     const size_t M = (size_t)B * grid * grid;
-    DevBuf dt, dw, db, dout, dz;
-    HIPCHK(dt.alloc(M * C * 2)); HIPCHK(dw.alloc((size_t)N * 9 * C * 2)); HIPCHK(db.alloc((size_t)N * 4));
-    HIPCHK(dout.alloc(M * N * 2)); HIPCHK(dz.alloc(256));
-    HIPCHK(hipMemcpy(dt.p, t, M * C * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw.p, w, (size_t)N * 9 * C * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dz.p, 0, 256));
     GemmArgs g{};
-    g.A = (const bf16_t*)dt.p; g.lda = C; g.W = (const bf16_t*)dw.p; g.ldw = 9 * C; g.bias = (const float*)db.p;
-    g.M = (int)M; g.N = N; g.K = 9 * C; g.Cb = (bf16_t*)dout.p; g.ldcb = N;
-    g.conv_grid = grid; g.conv_C = C; g.zeros = (const bf16_t*)dz.p;
+    GemmOperands ops;
+    HIPCHK(ops.upload(g, t, w, bias, M, N, 9 * C, C));
+    DevArr dout, dz;
+    HIPCHK(dout.alloc(M * N * 2)); HIPCHK(dz.zeros(256));
+    g.Cb = dout.as<bf16_t>(); g.ldcb = N;
+    g.conv_grid = grid; g.conv_C = C; g.zeros = dz.as<const bf16_t>();
     if (cfg < 0) HIPCHK(launch_gemm(g, EPI_RELU_BF16, nullptr));
     else HIPCHK(launch_gemm_cfg(g, EPI_RELU_BF16, cfg, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    std::vector<bf16_t> tmp(M * N);
-    HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
+    HIPCHK(download_bf16(dout.p, M * N, out));
     return VT_OK;
 } VT_NOTHROW_INT
 
 // The head's band kernel (k_head.hip) on its own: out = relu(conv(t) + bias), conv3x3 != 0: t [B*grid*grid][Cin],
 // w [N][9*Cin], N == Cin; else the 1x1 layer: w [N][Cin]. R / ncb <= 0: the launcher's plan. t == NULL: operands
 // filled with a fixed pseudo-random pattern (timing runs). out (nullable): [B*grid*grid][N] bf16 values widened
-// to f32. iters > 0 and us_out: mean microseconds per launch over iters launches.
+// to f32. us_out (nullable): mean microseconds per launch over iters >= 1 launches.
 int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, const float* bias, float* out,
                         int B, int grid, int Cin, int N, int conv3x3, int R, int ncb, int iters, float* us_out) try {
-    if (B < 1 || grid < 1 || Cin % 64 || N % 64 || (t && (!w || !bias)))
+    if (B < 1 || grid < 1 || Cin % 64 || N % 64 || (t && (!w || !bias)) || (us_out && iters < 1))
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
     const int K = conv3x3 ? 9 * Cin : Cin;
     if (!headconv_supported(grid, conv3x3 ? Cin : N, N, K, conv3x3 != 0))
@@ -553,61 +392,35 @@ int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, con
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     HIPCHK(headconv_prepare());
-    const size_t M = (size_t)B * grid * grid;
-    DevBuf dt, dw, db, dout, dz;
-    HIPCHK(dt.alloc(M * Cin * 2)); HIPCHK(dw.alloc((size_t)N * K * 2)); HIPCHK(db.alloc((size_t)N * 4));
-    HIPCHK(dout.alloc(M * N * 2)); HIPCHK(dz.alloc(256));
+    const size_t M = (size_t)B * grid * grid, t_bytes = M * Cin * 2, w_bytes = (size_t)N * K * 2, b_bytes = (size_t)N * 4;
+    DevArr dt, dw, db, dout, dz;
     if (t) {
-        HIPCHK(hipMemcpy(dt.p, t, M * Cin * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+        HIPCHK(dt.upload(t, t_bytes)); HIPCHK(dw.upload(w, w_bytes)); HIPCHK(db.upload(bias, b_bytes));
     } else {
-        std::vector<bf16_t> ht(M * Cin), hw((size_t)N * K);
-        uint32_t seed = 777u;
-        auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (bf16_t)(0x3c00u + ((seed >> 9) & 0x3ffu) + ((seed >> 3) & 0x8000u)); };
-        for (auto& v : ht) v = rnd();
-        for (auto& v : hw) v = rnd();
-        HIPCHK(hipMemcpy(dt.p, ht.data(), ht.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dw.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(db.p, 0, (size_t)N * 4));
+        std::vector<bf16_t> ht(t_bytes / 2), hw(w_bytes / 2);
+        fill_lcg_bf16(hw.data(), hw.size(), fill_lcg_bf16(ht.data(), ht.size(), 777u));
+        HIPCHK(dt.upload(ht.data(), t_bytes)); HIPCHK(dw.upload(hw.data(), w_bytes)); HIPCHK(db.zeros(b_bytes));
     }
-    HIPCHK(hipMemset(dz.p, 0, 256));
+    HIPCHK(dout.alloc(M * N * 2)); HIPCHK(dz.zeros(256));
     HeadConvArgs h{};
-    h.in = (const bf16_t*)dt.p; h.ldin = Cin; h.W = (const bf16_t*)dw.p; h.ldw = K; h.bias = (const float*)db.p;
-    h.out = (bf16_t*)dout.p; h.ldout = N; h.zeros = (const bf16_t*)dz.p;
+    h.in = dt.as<const bf16_t>(); h.ldin = Cin; h.W = dw.as<const bf16_t>(); h.ldw = K; h.bias = db.as<const float>();
+    h.out = dout.as<bf16_t>(); h.ldout = N; h.zeros = dz.as<const bf16_t>();
     h.B = B; h.grid = grid; h.C = conv3x3 ? Cin : N; h.N = N; h.K = K; h.conv3x3 = conv3x3 ? 1 : 0;
     h.R = R; h.ncb = ncb;
     HIPCHK(launch_headconv(h, nullptr, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    if (out) {
-        std::vector<bf16_t> tmp(M * N);
-        HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
-    }
+    if (out) HIPCHK(download_bf16(dout.p, M * N, out));
 #ifdef VT_STAMPS   // diagnostic builds only: per-wave cycle sums of the main loop, medians printed
-    DevBuf ddbg;
+    DevArr ddbg;
     const size_t dbg_words = (size_t)B * grid * 2 * 8 * 4;
-    HIPCHK(ddbg.alloc(dbg_words * 8));
-    HIPCHK(hipMemset(ddbg.p, 0, dbg_words * 8));
-    h.dbg = (unsigned long long*)ddbg.p;
+    HIPCHK(ddbg.zeros(dbg_words * 8));
+    h.dbg = ddbg.as<unsigned long long>();
 #endif
-    if (iters > 0 && us_out) {
-        for (int i = 0; i < 3; ++i) HIPCHK(launch_headconv(h, nullptr, nullptr));
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, nullptr));
-        for (int i = 0; i < iters; ++i) HIPCHK(launch_headconv(h, nullptr, nullptr));
-        HIPCHK(hipEventRecord(e1, nullptr));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *us_out = ms * 1000.0f / iters;
-    }
+    if (us_out) HIPCHK(time_launches(iters, [&] { return launch_headconv(h, nullptr, nullptr); }, us_out));
 #ifdef VT_STAMPS
     {
         std::vector<unsigned long long> hd(dbg_words);
-        HIPCHK(hipMemcpy(hd.data(), ddbg.p, dbg_words * 8, hipMemcpyDeviceToHost));
+        HIPCHK(ddbg.download(hd.data()));
         std::vector<unsigned long long> col[2][4];
         for (size_t wg = 0; wg < dbg_words / 32; ++wg)
             for (int wv = 0; wv < 8; ++wv) {
@@ -631,93 +444,53 @@ int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* x
                               float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
                               int D, int N, int fused, int R, int ncb, int iters, float* us_out, int lo_shift) try {
     const int ns = grid * grid;
-    if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "headconv_ln: lo_shift %d out of range", lo_shift);
+    if (!lo_shift_ok(lo_shift)) return set_err(VT_ERR_INVALID_ARG, "headconv_ln: lo_shift %d out of range", lo_shift);
     const float lo_q = lo_quant(lo_shift).q;
-    if (B < 1 || grid < 1 || off < 0 || ntok < off + ns || (xh && (!xl || !gamma || !beta || !w || !bias)))
+    if (B < 1 || grid < 1 || off < 0 || ntok < off + ns || (xh && (!xl || !gamma || !beta || !w || !bias)) || (us_out && iters < 1))
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
     if (!headconv_ln_supported(grid, N, D))
         return set_err(VT_ERR_INVALID_ARG, "shape not supported by the band kernel with the LayerNorm inside");
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     HIPCHK(headconv_prepare());
-    const size_t Mx = (size_t)B * ntok, M = (size_t)B * ns;
-    DevBuf dh, dl, dg, dbt, dw, db, dfeat, dout;
-    HIPCHK(dh.alloc(Mx * D * 2)); HIPCHK(dl.alloc(Mx * D * 2)); HIPCHK(dg.alloc((size_t)D * 4)); HIPCHK(dbt.alloc((size_t)D * 4));
-    HIPCHK(dw.alloc((size_t)N * D * 2)); HIPCHK(db.alloc((size_t)N * 4)); HIPCHK(dfeat.alloc(M * D * 2)); HIPCHK(dout.alloc(M * N * 2));
+    const size_t MxD = (size_t)B * ntok * D, M = (size_t)B * ns, w_bytes = (size_t)N * D * 2, d_bytes = (size_t)D * 4, b_bytes = (size_t)N * 4;
+    DevArr dh, dl, dg, dbt, dw, db, dfeat, dout;
     if (xh) {
-        HIPCHK(hipMemcpy(dh.p, xh, Mx * D * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dl.p, xl, Mx * D, hipMemcpyHostToDevice));       // lo8 bytes
-        HIPCHK(hipMemcpy(dg.p, gamma, (size_t)D * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dbt.p, beta, (size_t)D * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dw.p, w, (size_t)N * D * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+        HIPCHK(dh.upload(xh, MxD * 2)); HIPCHK(dl.upload(xl, MxD));       // lo8 bytes
+        HIPCHK(dg.upload(gamma, d_bytes)); HIPCHK(dbt.upload(beta, d_bytes));
+        HIPCHK(dw.upload(w, w_bytes)); HIPCHK(db.upload(bias, b_bytes));
     } else {
-        std::vector<bf16_t> hx(Mx * D), hw((size_t)N * D);
+        std::vector<bf16_t> hx(MxD), hw(w_bytes / 2);
         std::vector<float> ones((size_t)D, 1.0f);
-        uint32_t seed = 4242u;
-        auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (bf16_t)(0x3c00u + ((seed >> 9) & 0x3ffu) + ((seed >> 3) & 0x8000u)); };
-        for (auto& v : hx) v = rnd();
-        for (auto& v : hw) v = rnd();
-        HIPCHK(hipMemcpy(dh.p, hx.data(), hx.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(dl.p, 0, Mx * D * 2));
-        HIPCHK(hipMemcpy(dg.p, ones.data(), (size_t)D * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(dbt.p, 0, (size_t)D * 4));
-        HIPCHK(hipMemcpy(dw.p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(db.p, 0, (size_t)N * 4));
+        fill_lcg_bf16(hw.data(), hw.size(), fill_lcg_bf16(hx.data(), hx.size(), 4242u));
+        HIPCHK(dh.upload(hx.data(), MxD * 2)); HIPCHK(dl.zeros(MxD * 2));
+        HIPCHK(dg.upload(ones.data(), d_bytes)); HIPCHK(dbt.zeros(d_bytes));
+        HIPCHK(dw.upload(hw.data(), w_bytes)); HIPCHK(db.zeros(b_bytes));
     }
+    HIPCHK(dfeat.alloc(M * D * 2)); HIPCHK(dout.alloc(M * N * 2));
     HeadConvArgs h{};
-    h.W = (const bf16_t*)dw.p; h.ldw = D; h.bias = (const float*)db.p; h.out = (bf16_t*)dout.p; h.ldout = N;
+    h.W = dw.as<const bf16_t>(); h.ldw = D; h.bias = db.as<const float>(); h.out = dout.as<bf16_t>(); h.ldout = N;
     h.B = B; h.grid = grid; h.C = N; h.N = N; h.K = D; h.conv3x3 = 0; h.R = R; h.ncb = ncb;
     if (fused) {
-        h.xh = (const bf16_t*)dh.p; h.xl = (const uint8_t*)dl.p; h.ln_g = (const float*)dg.p; h.ln_b = (const float*)dbt.p;
+        h.xh = dh.as<const bf16_t>(); h.xl = dl.as<const uint8_t>(); h.ln_g = dg.as<const float>(); h.ln_b = dbt.as<const float>();
         h.ln_eps = eps; h.in_stride = ntok; h.in_off = off; h.lo_q = lo_q;
     } else {
-        h.in = (const bf16_t*)dfeat.p; h.ldin = D;
+        h.in = dfeat.as<const bf16_t>(); h.ldin = D;
     }
     auto run = [&]() -> hipError_t {
         if (!fused) {
-            hipError_t e = launch_layernorm_split((const bf16_t*)dh.p, (const uint8_t*)dl.p, (const float*)dg.p, (const float*)dbt.p,
-                                                  (bf16_t*)dfeat.p, (int)M, D, ns, ntok, off, eps, lo_q, nullptr);
+            hipError_t e = launch_layernorm_split(dh.as<const bf16_t>(), dl.as<const uint8_t>(), dg.as<const float>(), dbt.as<const float>(),
+                                                  dfeat.as<bf16_t>(), (int)M, D, ns, ntok, off, eps, lo_q, nullptr);
             if (e != hipSuccess) return e;
         }
         return launch_headconv(h, nullptr, nullptr);
     };
     HIPCHK(run());
     HIPCHK(hipDeviceSynchronize());
-    if (out) {
-        std::vector<bf16_t> tmp(M * N);
-        HIPCHK(hipMemcpy(tmp.data(), dout.p, tmp.size() * 2, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < tmp.size(); ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(out + i, &u, 4); }
-    }
-    if (iters > 0 && us_out) {
-        for (int i = 0; i < 3; ++i) HIPCHK(run());
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, nullptr));
-        for (int i = 0; i < iters; ++i) HIPCHK(run());
-        HIPCHK(hipEventRecord(e1, nullptr));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *us_out = ms * 1000.0f / iters;
-    }
+    if (out) HIPCHK(download_bf16(dout.p, M * N, out));
+    if (us_out) HIPCHK(time_launches(iters, run, us_out));
     return VT_OK;
 } VT_NOTHROW_INT
-
-int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
-                           float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
-                           int D, int N, int fused, int R, int ncb, int iters, float* us_out) {
-    return vt_op_headconv_ln_bf16_lo(device_id, xh, xl, gamma, beta, eps, ntok, off, w, bias, out, B, grid, D, N, fused, R, ncb,
-                                     iters, us_out, VT_LO_SHIFT_DEFAULT);
-}
-
-// pinned, device-visible host memory (what PassOut points the decode at)
-struct PinnedBuf {
-    void* p = nullptr;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t n) { return hipHostMalloc(&p, n ? n : 4); }
-};
 
 // The decode stage on given operands: see include/vittrack_hip_ops.h. A thin launcher: everything is checked here or by
 // the launchers themselves before a kernel runs.
@@ -747,50 +520,36 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
     DEVICE_SCOPE(device_id);
     HIPCHK(headconv_prepare());
     const int ns = grid * grid;
-    const size_t M = (size_t)B * ns;
-    DevBuf dt, dt3, dw3, db3, dw4, db4, dhann, dho, dst, dres, dpo, dmap, dcnt, dbest, dz;
+    const size_t M = (size_t)B * ns, res_bytes = (size_t)B * sizeof(vt_result), st_bytes = (size_t)n_states * sizeof(StreamState);
+    DevArr dt, dt3, dw3, db3, dw4, db4, dhann, dho, dst, dres, dpo, dmap, dcnt, dbest, dz;
     PinnedBuf hres, hst;
-    HIPCHK(dt.alloc(M * C * 2)); HIPCHK(dw4.alloc((size_t)8 * C * 4)); HIPCHK(db4.alloc(8 * 4)); HIPCHK(dhann.alloc((size_t)ns * 4));
-    HIPCHK(dho.alloc(M * 8 * 4)); HIPCHK(dst.alloc((size_t)n_states * sizeof(StreamState))); HIPCHK(dres.alloc((size_t)B * sizeof(vt_result)));
-    HIPCHK(dpo.alloc(sizeof(PassOut))); HIPCHK(dcnt.alloc((size_t)B * 4)); HIPCHK(dbest.alloc((size_t)B * grid * 2 * 4));
-    HIPCHK(hres.alloc((size_t)B * sizeof(vt_result))); HIPCHK(hst.alloc((size_t)n_states * sizeof(StreamState)));
-    HIPCHK(hipMemcpy(dt.p, t, M * C * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dw4.p, w4, (size_t)8 * C * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db4.p, b4, 8 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dhann.p, hann, (size_t)ns * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst.p, states, (size_t)n_states * sizeof(StreamState), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dho.p, 0xff, M * 8 * 4));
-    HIPCHK(hipMemset(dres.p, 0xff, (size_t)B * sizeof(vt_result)));
-    HIPCHK(hipMemset(dcnt.p, 0, (size_t)B * 4));
-    HIPCHK(hipMemset(dbest.p, 0, (size_t)B * grid * 2 * 4));
-    memcpy(hres.p, host_results, (size_t)B * sizeof(vt_result));
-    memcpy(hst.p, host_states, (size_t)n_states * sizeof(StreamState));
+    HIPCHK(dt.upload(t, M * C * 2)); HIPCHK(dw4.upload(w4, (size_t)8 * C * 4)); HIPCHK(db4.upload(b4, 8 * 4));
+    HIPCHK(dhann.upload(hann, (size_t)ns * 4)); HIPCHK(dst.upload(states, st_bytes));
+    HIPCHK(dho.filled(M * 8 * 4, 0xff)); HIPCHK(dres.filled(res_bytes, 0xff));
+    HIPCHK(dcnt.zeros((size_t)B * 4)); HIPCHK(dbest.zeros((size_t)B * grid * 2 * 4));
+    HIPCHK(hres.alloc(res_bytes)); HIPCHK(hst.alloc(st_bytes));
+    memcpy(hres.p, host_results, res_bytes);
+    memcpy(hst.p, host_states, st_bytes);
     const PassOut po{(flags & 1) ? nullptr : (vt_result*)hres.p, (flags & 2) ? nullptr : (StreamState*)hst.p};
-    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
-    if (slot_stream) {
-        HIPCHK(dmap.alloc((size_t)B * 4));
-        HIPCHK(hipMemcpy(dmap.p, slot_stream, (size_t)B * 4, hipMemcpyHostToDevice));
-    }
+    HIPCHK(dpo.upload(&po, sizeof(po)));
+    HIPCHK(dmap.upload(slot_stream, (size_t)B * 4));
     DecodeArgs dec{};
-    dec.w4 = (const float*)dw4.p; dec.b4 = (const float*)db4.p; dec.hann = (const float*)dhann.p;
-    dec.head_out = (float*)dho.p; dec.states = (StreamState*)dst.p; dec.results = (vt_result*)dres.p;
-    dec.out = (const PassOut*)dpo.p; dec.slot_stream = slot_stream ? (const int32_t*)dmap.p : nullptr;
+    dec.w4 = dw4.as<const float>(); dec.b4 = db4.as<const float>(); dec.hann = dhann.as<const float>();
+    dec.head_out = dho.as<float>(); dec.states = dst.as<StreamState>(); dec.results = dres.as<vt_result>();
+    dec.out = dpo.as<const PassOut>(); dec.slot_stream = dmap.as<const int32_t>();
     dec.B = B; dec.ns = ns; dec.grid = grid; dec.C = C; dec.success_threshold = success_threshold;
     HeadConvArgs h{};
     if (form == 0) {
-        dec.t3 = (const bf16_t*)dt.p;
+        dec.t3 = dt.as<const bf16_t>();
     } else {
-        HIPCHK(dt3.alloc(M * C * 2)); HIPCHK(dw3.alloc((size_t)C * 9 * C * 2)); HIPCHK(db3.alloc((size_t)C * 4)); HIPCHK(dz.alloc(256));
-        HIPCHK(hipMemcpy(dw3.p, w3, (size_t)C * 9 * C * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db3.p, b3, (size_t)C * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(dz.p, 0, 256));
-        HIPCHK(hipMemset(dt3.p, 0xff, M * C * 2));
-        dec.t3 = (const bf16_t*)dt3.p;
-        h.in = (const bf16_t*)dt.p; h.ldin = C; h.W = (const bf16_t*)dw3.p; h.ldw = 9 * C; h.bias = (const float*)db3.p;
-        h.out = (bf16_t*)dt3.p; h.ldout = C; h.zeros = (const bf16_t*)dz.p;
+        HIPCHK(dw3.upload(w3, (size_t)C * 9 * C * 2)); HIPCHK(db3.upload(b3, (size_t)C * 4));
+        HIPCHK(dz.zeros(256)); HIPCHK(dt3.filled(M * C * 2, 0xff));
+        dec.t3 = dt3.as<const bf16_t>();
+        h.in = dt.as<const bf16_t>(); h.ldin = C; h.W = dw3.as<const bf16_t>(); h.ldw = 9 * C; h.bias = db3.as<const float>();
+        h.out = dt3.as<bf16_t>(); h.ldout = C; h.zeros = dz.as<const bf16_t>();
         h.B = B; h.grid = grid; h.C = C; h.N = C; h.K = 9 * C; h.conv3x3 = 1;
         h.R = R > 0 ? R : 0; h.ncb = R > 0 ? C / 64 : 0;      // a given R keeps the tail's one column group; else both planned
-        h.band_cnt = (unsigned*)dcnt.p; h.band_best = (float*)dbest.p;
+        h.band_cnt = dcnt.as<unsigned>(); h.band_best = dbest.as<float>();
     }
     for (int i = 0; i < launches; ++i) {
         const hipError_t e = form == 0 ? launch_decode(dec, nullptr) : launch_headconv(h, &dec, nullptr);
@@ -801,12 +560,9 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
         HIPCHK(e);
     }
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(head_out, dho.p, M * 8 * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(results, dres.p, (size_t)B * sizeof(vt_result), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(states, dst.p, (size_t)n_states * sizeof(StreamState), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(band_cnt, dcnt.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    memcpy(host_results, hres.p, (size_t)B * sizeof(vt_result));
-    memcpy(host_states, hst.p, (size_t)n_states * sizeof(StreamState));
+    HIPCHK(dho.download(head_out)); HIPCHK(dres.download(results)); HIPCHK(dst.download(states)); HIPCHK(dcnt.download(band_cnt));
+    memcpy(host_results, hres.p, res_bytes);
+    memcpy(host_states, hst.p, st_bytes);
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -822,47 +578,31 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
     for (int s = 0; s < n_states; ++s)
         if (pol[s].max_peaks < 0 || pol[s].max_peaks > VT_PEAKS_MAX || pol[s].radius < 1 || pol[s].radius > 4)
             return set_err(VT_ERR_INVALID_ARG, "response_peaks: policy %d: max_peaks %d, radius %d", s, pol[s].max_peaks, pol[s].radius);
-    for (int b = 0; b < B; ++b) {
-        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_states))
-            return set_err(VT_ERR_INVALID_ARG, "response_peaks: slot %d names stream %d of %d", b, (int)slot_stream[b], n_states);
-        if (winner && (winner[b] < 0 || winner[b] >= B))
-            return set_err(VT_ERR_INVALID_ARG, "response_peaks: winner[%d] = %d of %d slots", b, (int)winner[b], B);
-    }
+    SlotMaps maps{slot_stream, winner, B, n_states};
+    for (int b = 0; b < B; ++b)
+        if (int rc = maps.check("response_peaks", b)) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const int ns = grid * grid;
-    const size_t M = (size_t)B * ns;
-    DevBuf dho, dhann, dst, dpol, dmap, dwin, drec, dpo;
+    const size_t rec_bytes = (size_t)B * sizeof(vt_peaks);
+    DevArr dho, dhann, dst, dpol, drec, dpo;
     PinnedBuf hrec;
-    HIPCHK(dho.alloc(M * 8 * 4)); HIPCHK(dhann.alloc((size_t)ns * 4)); HIPCHK(dst.alloc((size_t)n_states * sizeof(StreamState)));
-    HIPCHK(dpol.alloc((size_t)n_states * sizeof(PeaksPolicy))); HIPCHK(drec.alloc((size_t)B * sizeof(vt_peaks)));
-    HIPCHK(dpo.alloc(sizeof(PassOut))); HIPCHK(hrec.alloc((size_t)B * sizeof(vt_peaks)));
-    HIPCHK(hipMemcpy(dho.p, head_out, M * 8 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dhann.p, hann, (size_t)ns * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst.p, states, (size_t)n_states * sizeof(StreamState), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpol.p, policies, (size_t)n_states * sizeof(PeaksPolicy), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(drec.p, records, (size_t)B * sizeof(vt_peaks), hipMemcpyHostToDevice));
-    memcpy(hrec.p, host_records, (size_t)B * sizeof(vt_peaks));
+    HIPCHK(dho.upload(head_out, (size_t)B * ns * 8 * 4)); HIPCHK(dhann.upload(hann, (size_t)ns * 4));
+    HIPCHK(dst.upload(states, (size_t)n_states * sizeof(StreamState))); HIPCHK(dpol.upload(policies, (size_t)n_states * sizeof(PeaksPolicy)));
+    HIPCHK(drec.upload(records, rec_bytes));
+    HIPCHK(hrec.alloc(rec_bytes));
+    memcpy(hrec.p, host_records, rec_bytes);
     const PassOut po{nullptr, nullptr, (vt_peaks*)hrec.p};
-    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
-    if (slot_stream) {
-        HIPCHK(dmap.alloc((size_t)B * 4));
-        HIPCHK(hipMemcpy(dmap.p, slot_stream, (size_t)B * 4, hipMemcpyHostToDevice));
-    }
-    if (winner) {
-        HIPCHK(dwin.alloc((size_t)B * 4));
-        HIPCHK(hipMemcpy(dwin.p, winner, (size_t)B * 4, hipMemcpyHostToDevice));
-    }
-    const PeaksArgs pa{(const float*)dho.p, (const float*)dhann.p, (const StreamState*)dst.p,
-                       slot_stream ? (const int32_t*)dmap.p : nullptr, winner ? (const int32_t*)dwin.p : nullptr,
-                       (const PeaksPolicy*)dpol.p, (vt_peaks*)drec.p, (const PassOut*)dpo.p, B, ns, grid};
+    HIPCHK(dpo.upload(&po, sizeof(po)));
+    HIPCHK(maps.upload());
+    const PeaksArgs pa{dho.as<const float>(), dhann.as<const float>(), dst.as<const StreamState>(), maps.dev_slot_stream(),
+                       maps.dev_winner(), dpol.as<const PeaksPolicy>(), drec.as<vt_peaks>(), dpo.as<const PassOut>(), B, ns, grid};
     const hipError_t e = launch_response_peaks(pa, nullptr);
     if (e == hipErrorInvalidValue) return set_err(VT_ERR_INVALID_ARG, "response_peaks: the launcher refuses grid %d", grid);
     HIPCHK(e);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(records, drec.p, (size_t)B * sizeof(vt_peaks), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(states, dst.p, (size_t)n_states * sizeof(StreamState), hipMemcpyDeviceToHost));
-    memcpy(host_records, hrec.p, (size_t)B * sizeof(vt_peaks));
+    HIPCHK(drec.download(records)); HIPCHK(dst.download(states));
+    memcpy(host_records, hrec.p, rec_bytes);
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -880,40 +620,26 @@ int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result*
         pol.min_score_pct > 100)
         return set_err(VT_ERR_INVALID_ARG, "result_overlay: policy out of range");
     std::vector<FrameDesc> desc((size_t)n);
+    SlotMaps maps{slot_stream, winner, n, n_streams};
     for (int b = 0; b < n; ++b) {
         if (int rc = check_frame(frames[b])) return rc;
         to_desc(frames[b], &desc[(size_t)b]);
-        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_streams))
-            return set_err(VT_ERR_INVALID_ARG, "result_overlay: slot %d names stream %d of %d", b, (int)slot_stream[b], n_streams);
-        if (winner && (winner[b] < 0 || winner[b] >= n))
-            return set_err(VT_ERR_INVALID_ARG, "result_overlay: winner[%d] = %d of %d slots", b, (int)winner[b], n);
+        if (int rc = maps.check("result_overlay", b)) return rc;
     }
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
-    DevBuf dfr, dres, dmap, dwin, dpol, dst, dflag;
-    HIPCHK(dfr.alloc((size_t)n * sizeof(FrameDesc))); HIPCHK(dres.alloc((size_t)n * sizeof(vt_result)));
-    HIPCHK(dpol.alloc(sizeof(OverlayPolicy))); HIPCHK(dst.alloc((size_t)n_streams * sizeof(OverlayStats))); HIPCHK(dflag.alloc(4));
-    HIPCHK(hipMemcpy(dfr.p, desc.data(), (size_t)n * sizeof(FrameDesc), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dres.p, results, (size_t)n * sizeof(vt_result), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst.p, stats, (size_t)n_streams * sizeof(OverlayStats), hipMemcpyHostToDevice));
     const int32_t flag = device_frames != 0;
-    HIPCHK(hipMemcpy(dflag.p, &flag, 4, hipMemcpyHostToDevice));
-    if (slot_stream) {
-        HIPCHK(dmap.alloc((size_t)n * 4));
-        HIPCHK(hipMemcpy(dmap.p, slot_stream, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    if (winner) {
-        HIPCHK(dwin.alloc((size_t)n * 4));
-        HIPCHK(hipMemcpy(dwin.p, winner, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    const ResultOverlayArgs oa{(const FrameDesc*)dfr.p, (const vt_result*)dres.p, slot_stream ? (const int32_t*)dmap.p : nullptr,
-                               winner ? (const int32_t*)dwin.p : nullptr, (const OverlayPolicy*)dpol.p, (OverlayStats*)dst.p,
-                               (const int32_t*)dflag.p, n};
+    DevArr dfr, dres, dpol, dst, dflag;
+    HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
+    HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dst.upload(stats, (size_t)n_streams * sizeof(OverlayStats)));
+    HIPCHK(dflag.upload(&flag, 4));
+    HIPCHK(maps.upload());
+    const ResultOverlayArgs oa{dfr.as<const FrameDesc>(), dres.as<const vt_result>(), maps.dev_slot_stream(), maps.dev_winner(),
+                               dpol.as<const OverlayPolicy>(), dst.as<OverlayStats>(), dflag.as<const int32_t>(), n};
     HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
     HIPCHK(launch_result_overlay(oa, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(stats, dst.p, (size_t)n_streams * sizeof(OverlayStats), hipMemcpyDeviceToHost));
+    HIPCHK(dst.download(stats));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -932,47 +658,32 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
     if (pol.on < 0 || pol.on > 1 || pol.gain_pct < 1 || pol.gain_pct > 100 || pol.coast < 0 || pol.coast > 60 || pol.max_pct < 0 ||
         pol.max_pct > 200)
         return set_err(VT_ERR_INVALID_ARG, "motion_prior: policy out of range");
-    std::vector<int32_t> map;
+    std::vector<int32_t> map;       // the candidate form's map is its slots' streams
     if (cands || slot_stream) map.resize((size_t)n);
+    SlotMaps maps{map.empty() ? nullptr : map.data(), winner, n, n_streams};
     for (int i = 0; i < n; ++i) {
         if (!map.empty()) map[(size_t)i] = cands ? cands[i].stream : slot_stream[i];
-        if (!map.empty() && (map[(size_t)i] < 0 || map[(size_t)i] >= n_streams))
-            return set_err(VT_ERR_INVALID_ARG, "motion_prior: slot %d names stream %d of %d", i, (int)map[(size_t)i], n_streams);
-        if (winner && (winner[i] < 0 || winner[i] >= n))
-            return set_err(VT_ERR_INVALID_ARG, "motion_prior: winner[%d] = %d of %d slots", i, (int)winner[i], n);
+        if (int rc = maps.check("motion_prior", i)) return rc;
     }
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t sb = (size_t)n_streams * sizeof(StreamState), rb = (size_t)n_streams * sizeof(MotionRec);
-    DevBuf dst, drec, dpol, dres, dmap, dwin, dcand, dpo;
+    DevArr dst, drec, dpol, dres, dcand, dpo;
     PinnedBuf hst, hrec;
-    HIPCHK(dst.alloc(sb)); HIPCHK(drec.alloc(rb)); HIPCHK(dpol.alloc(sizeof(pol))); HIPCHK(dres.alloc((size_t)n * sizeof(vt_result)));
-    HIPCHK(dpo.alloc(sizeof(PassOut)));
-    HIPCHK(hipMemcpy(dst.p, states, sb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(drec.p, records, rb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dres.p, results, (size_t)n * sizeof(vt_result), hipMemcpyHostToDevice));
+    HIPCHK(dst.upload(states, sb)); HIPCHK(drec.upload(records, rb)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
+    HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
     if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
     if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
     const PassOut po{nullptr, (StreamState*)hst.p, nullptr, (MotionRec*)hrec.p};
-    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
-    if (!map.empty()) {
-        HIPCHK(dmap.alloc((size_t)n * 4));
-        HIPCHK(hipMemcpy(dmap.p, map.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    if (cands) {
-        HIPCHK(dwin.alloc((size_t)n * 4)); HIPCHK(dcand.alloc((size_t)n * sizeof(vt_candidate)));
-        HIPCHK(hipMemcpy(dwin.p, winner, (size_t)n * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dcand.p, cands, (size_t)n * sizeof(vt_candidate), hipMemcpyHostToDevice));
-    }
-    const MotionArgs ma{(StreamState*)dst.p, (MotionRec*)drec.p, (const MotionPolicy*)dpol.p, (const vt_result*)dres.p,
-                        map.empty() ? nullptr : (const int32_t*)dmap.p, cands ? (const int32_t*)dwin.p : nullptr,
-                        cands ? (const vt_candidate*)dcand.p : nullptr, (const PassOut*)dpo.p, nullptr, n};
+    HIPCHK(dpo.upload(&po, sizeof(po)));
+    HIPCHK(maps.upload());
+    HIPCHK(dcand.upload(cands, (size_t)n * sizeof(vt_candidate)));
+    const MotionArgs ma{dst.as<StreamState>(), drec.as<MotionRec>(), dpol.as<const MotionPolicy>(), dres.as<const vt_result>(),
+                        maps.dev_slot_stream(), maps.dev_winner(), dcand.as<const vt_candidate>(), dpo.as<const PassOut>(), nullptr, n};
     if (stages & 1) HIPCHK(launch_motion_place(ma, nullptr));
     if (stages & 2) HIPCHK(launch_motion_settle(ma, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(states, dst.p, sb, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(records, drec.p, rb, hipMemcpyDeviceToHost));
+    HIPCHK(dst.download(states)); HIPCHK(drec.download(records));
     if (host_states) memcpy(host_states, hst.p, sb);
     if (host_records) memcpy(host_records, hrec.p, rb);
     return VT_OK;
@@ -989,30 +700,22 @@ int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t
     DEVICE_SCOPE(device_id);
     const size_t n = (size_t)n_slots, rows = n * (size_t)nt * (size_t)kpad * sizeof(bf16_t);
     const size_t nch = (size_t)appear_chunks(nt);
-    DevBuf da, dp, dpol, drec, dcnt, dtick, dpart, dsum;
-    HIPCHK(da.alloc(rows)); HIPCHK(dp.alloc(rows)); HIPCHK(dpol.alloc(sizeof(AppearPolicy))); HIPCHK(drec.alloc(n * sizeof(AppearRec)));
-    HIPCHK(dcnt.alloc(n * sizeof(AppearCount))); HIPCHK(dtick.alloc(n * sizeof(unsigned)));
-    HIPCHK(dpart.alloc(n * nch * 5 * sizeof(double))); HIPCHK(dsum.alloc(n * 5 * sizeof(double)));
-    HIPCHK(hipMemcpy(da.p, anchor, rows, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dp.p, probe, rows, hipMemcpyHostToDevice));
     const AppearPolicy pol{1, 1, 0, 0.0f};
-    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
     std::vector<AppearRec> recs(n, AppearRec{1, 0, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}, 0});
-    HIPCHK(hipMemcpy(drec.p, recs.data(), n * sizeof(AppearRec), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dcnt.p, 0, n * sizeof(AppearCount)));
-    HIPCHK(hipMemset(dtick.p, 0, n * sizeof(unsigned)));
-    HIPCHK(hipMemset(dpart.p, 0xff, n * nch * 5 * sizeof(double)));      // NaN: a partial nobody wrote would show
-    HIPCHK(hipMemset(dsum.p, 0xff, n * 5 * sizeof(double)));
+    std::vector<unsigned> ticks(n);
+    DevArr da, dp, dpol, drec, dcnt, dtick, dpart, dsum;
+    HIPCHK(da.upload(anchor, rows)); HIPCHK(dp.upload(probe, rows)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
+    HIPCHK(drec.upload(recs.data(), n * sizeof(AppearRec)));
+    HIPCHK(dcnt.zeros(n * sizeof(AppearCount))); HIPCHK(dtick.zeros(n * sizeof(unsigned)));
+    HIPCHK(dpart.filled(n * nch * 5 * sizeof(double), 0xff));      // NaN: a partial nobody wrote would show
+    HIPCHK(dsum.filled(n * 5 * sizeof(double), 0xff));
     AppearArgs a{};
-    a.policy = (const AppearPolicy*)dpol.p; a.counts = (AppearCount*)dcnt.p; a.recs = (AppearRec*)drec.p;
-    a.tickets = (unsigned*)dtick.p; a.partials = (double*)dpart.p;
-    a.anchor = (const bf16_t*)da.p; a.probe = (bf16_t*)dp.p; a.sums = (double*)dsum.p; a.n = n_slots;
+    a.policy = dpol.as<const AppearPolicy>(); a.counts = dcnt.as<AppearCount>(); a.recs = drec.as<AppearRec>();
+    a.tickets = dtick.as<unsigned>(); a.partials = dpart.as<double>();
+    a.anchor = da.as<const bf16_t>(); a.probe = dp.as<bf16_t>(); a.sums = dsum.as<double>(); a.n = n_slots;
     HIPCHK(launch_appearance_score(a, nt, cols, kpad, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(recs.data(), drec.p, n * sizeof(AppearRec), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sums, dsum.p, n * 5 * sizeof(double), hipMemcpyDeviceToHost));
-    std::vector<unsigned> ticks(n);
-    HIPCHK(hipMemcpy(ticks.data(), dtick.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCHK(drec.download(recs.data())); HIPCHK(dsum.download(sums)); HIPCHK(dtick.download(ticks.data()));
     for (size_t i = 0; i < n; ++i) {
         if (ticks[i] != 0) return set_err(VT_ERR_HIP, "appearance_score: slot %zu left its ticket at %u", i, ticks[i]);
         similarity[i] = recs[i].similarity;
@@ -1041,13 +744,11 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
         return set_err(VT_ERR_INVALID_ARG, "proposals: policy out of range");
     pol.tau = (float)pol.min_sim_pm / 1000.0f;
     std::vector<FrameDesc> desc((size_t)n);
+    SlotMaps maps{slot_stream, winner, n, n_streams};
     for (int b = 0; b < n; ++b) {
         if (int rc = check_frame(frames[b])) return rc;
         to_desc(frames[b], &desc[(size_t)b]);
-        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_streams))
-            return set_err(VT_ERR_INVALID_ARG, "proposals: slot %d names stream %d of %d", b, (int)slot_stream[b], n_streams);
-        if (winner && (winner[b] < 0 || winner[b] >= n))
-            return set_err(VT_ERR_INVALID_ARG, "proposals: winner[%d] = %d of %d slots", b, (int)winner[b], n);
+        if (int rc = maps.check("proposals", b)) return rc;
     }
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
@@ -1055,38 +756,21 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
     d.T = T; d.patch = patch; d.gt = T / patch; d.nt = d.gt * d.gt; d.kpad = kpad;
     for (int c = 0; c < 3; ++c) { d.norm_a[c] = norm[c]; d.norm_b[c] = norm[3 + c]; }
     const size_t ns = (size_t)n, mc = (size_t)pol.max_cells, pm = VT_PROP_M_MAX * VT_PROP_M_MAX;
-    const size_t tpl_b = (size_t)n_streams * tpl_bufs * d.nt * kpad * sizeof(bf16_t);
-    DevBuf dfr, dst, dres, dmap, dwin, dpol, dflag, dtpl, dcnt, dhead, dpo;
+    const int32_t flag = device_frames != 0;
+    const PassOut po{};
+    DevArr dfr, dst, dres, dpol, dflag, dtpl, dcnt, dhead, dpo;
     GuardedOut gpat, gth, gmap, grec;
-    HIPCHK(dfr.alloc(ns * sizeof(FrameDesc))); HIPCHK(dst.alloc((size_t)n_streams * sizeof(StreamState)));
-    HIPCHK(dres.alloc(ns * sizeof(vt_result))); HIPCHK(dpol.alloc(sizeof(pol))); HIPCHK(dflag.alloc(4)); HIPCHK(dtpl.alloc(tpl_b));
-    HIPCHK(dcnt.alloc((size_t)n_streams * 4)); HIPCHK(dhead.alloc(ns * sizeof(PropHead))); HIPCHK(dpo.alloc(sizeof(PassOut)));
+    HIPCHK(dfr.upload(desc.data(), ns * sizeof(FrameDesc))); HIPCHK(dst.upload(states, (size_t)n_streams * sizeof(StreamState)));
+    HIPCHK(dres.upload(results, ns * sizeof(vt_result))); HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4));
+    HIPCHK(dtpl.upload(tpl, (size_t)n_streams * tpl_bufs * d.nt * kpad * sizeof(bf16_t)));
+    HIPCHK(dcnt.upload(evaluated, (size_t)n_streams * 4)); HIPCHK(dhead.zeros(ns * sizeof(PropHead))); HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(gpat.alloc(ns * pm * sizeof(int16_t))); HIPCHK(gth.alloc(ns * mc * sizeof(int16_t))); HIPCHK(gmap.alloc(ns * mc * sizeof(float)));
     HIPCHK(grec.alloc((size_t)n_streams * sizeof(PropRec)));
-    HIPCHK(hipMemcpy(dfr.p, desc.data(), ns * sizeof(FrameDesc), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst.p, states, (size_t)n_streams * sizeof(StreamState), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dres.p, results, ns * sizeof(vt_result), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpol.p, &pol, sizeof(pol), hipMemcpyHostToDevice));
-    const int32_t flag = device_frames != 0;
-    HIPCHK(hipMemcpy(dflag.p, &flag, 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dtpl.p, tpl, tpl_b, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dcnt.p, evaluated, (size_t)n_streams * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dhead.p, 0, ns * sizeof(PropHead)));
-    const PassOut po{};
-    HIPCHK(hipMemcpy(dpo.p, &po, sizeof(po), hipMemcpyHostToDevice));
-    if (slot_stream) {
-        HIPCHK(dmap.alloc(ns * 4));
-        HIPCHK(hipMemcpy(dmap.p, slot_stream, ns * 4, hipMemcpyHostToDevice));
-    }
-    if (winner) {
-        HIPCHK(dwin.alloc(ns * 4));
-        HIPCHK(hipMemcpy(dwin.p, winner, ns * 4, hipMemcpyHostToDevice));
-    }
-    const PropArgs pa{(const FrameDesc*)dfr.p, (const StreamState*)dst.p, (const vt_result*)dres.p,
-                      slot_stream ? (const int32_t*)dmap.p : nullptr, winner ? (const int32_t*)dwin.p : nullptr,
-                      (const PropPolicy*)dpol.p, (const int32_t*)dflag.p, (const bf16_t*)dtpl.p, tpl_bufs, (PropRec*)grec.out(),
-                      (int32_t*)dcnt.p, (PropHead*)dhead.p, (int16_t*)gpat.out(), (int16_t*)gth.out(), (float*)gmap.out(),
-                      (const PassOut*)dpo.p, pol.max_cells, n};
+    HIPCHK(maps.upload());
+    const PropArgs pa{dfr.as<const FrameDesc>(), dst.as<const StreamState>(), dres.as<const vt_result>(), maps.dev_slot_stream(),
+                      maps.dev_winner(), dpol.as<const PropPolicy>(), dflag.as<const int32_t>(), dtpl.as<const bf16_t>(), tpl_bufs,
+                      grec.as<PropRec>(), dcnt.as<int32_t>(), dhead.as<PropHead>(), gpat.as<int16_t>(), gth.as<int16_t>(),
+                      gmap.as<float>(), dpo.as<const PassOut>(), pol.max_cells, n};
     HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
     HIPCHK(launch_proposals_prepare(pa, d, nullptr));
     int level = 0;
@@ -1095,18 +779,9 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
     HIPCHK(launch_proposals_match(pa, nullptr));
     HIPCHK(launch_proposals_list(pa, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    const GuardedOut* outs[] = {&gpat, &gth, &gmap, &grec};
-    const char* const names[] = {"pattern", "thumbnail", "map", "records"};
-    for (int k = 0; k < 4; ++k) {
-        long where = 0;
-        HIPCHK(outs[k]->check(&where));
-        if (where) return set_err(VT_ERR_HIP, "proposals wrote outside its %s: guard byte %ld changed", names[k], where);
-    }
-    HIPCHK(hipMemcpy(pattern, gpat.out(), gpat.bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(thumb, gth.out(), gth.bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(map, gmap.out(), gmap.bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(records, grec.out(), grec.bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(evaluated, dcnt.p, (size_t)n_streams * 4, hipMemcpyDeviceToHost));
+    if (int rc = guards_intact("proposals", {{&gpat, "pattern"}, {&gth, "thumbnail"}, {&gmap, "map"}, {&grec, "records"}})) return rc;
+    HIPCHK(gpat.download(pattern)); HIPCHK(gth.download(thumb)); HIPCHK(gmap.download(map)); HIPCHK(grec.download(records));
+    HIPCHK(dcnt.download(evaluated));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -1135,7 +810,7 @@ int vt_op_ln_chain_bf16(int device_id, const float* x, int B, int tokens, int D,
     if (!fold_only) {
         if (!x || !out || B <= 0 || tokens <= 0 || Mll > (1 << 20) || D % 64 || N % 64 || D > 2048 || !(eps >= 0.0f))
             return set_err(VT_ERR_INVALID_ARG, "bad argument");
-        if (lo_shift < VT_LO_SHIFT_MIN || lo_shift > VT_LO_SHIFT_MAX) return set_err(VT_ERR_INVALID_ARG, "ln chain: lo_shift %d out of range", lo_shift);
+        if (!lo_shift_ok(lo_shift)) return set_err(VT_ERR_INVALID_ARG, "ln chain: lo_shift %d out of range", lo_shift);
         if (route < 0 || route > 2) return set_err(VT_ERR_INVALID_ARG, "ln chain: unknown route %d", route);
         if (epi == EPI_QKV && (N != 3 * D || (tokens & 3) || !vt_out))
             return set_err(VT_ERR_INVALID_ARG, "ln chain: QKV takes N == 3 * D, tokens %% 4 == 0 and vt_out");
@@ -1151,101 +826,80 @@ int vt_op_ln_chain_bf16(int device_id, const float* x, int B, int tokens, int D,
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t WN = (size_t)N * D;
-    DevBuf dw, dg, dbeta, dbias;
+    DevArr dw, dg, dbeta, dbias;
     GuardedOut gwf, gcs, gcv;
-    HIPCHK(dw.alloc(WN * 2)); HIPCHK(dg.alloc((size_t)D * 4)); HIPCHK(dbeta.alloc((size_t)D * 4)); HIPCHK(dbias.alloc((size_t)N * 4));
+    HIPCHK(dw.upload(w, WN * 2)); HIPCHK(dg.upload(gamma, (size_t)D * 4)); HIPCHK(dbeta.upload(beta, (size_t)D * 4));
+    HIPCHK(dbias.upload(bias, (size_t)N * 4));
     HIPCHK(gwf.alloc(WN * 2)); HIPCHK(gcs.alloc((size_t)N * 4)); HIPCHK(gcv.alloc((size_t)N * 4));
-    HIPCHK(hipMemcpy(dw.p, w, WN * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dg.p, gamma, (size_t)D * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dbeta.p, beta, (size_t)D * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
     auto fold = [&] {
-        return launch_fold_layernorm((const bf16_t*)dw.p, (const float*)dg.p, (const float*)dbeta.p, (const float*)dbias.p,
-                                     (bf16_t*)gwf.out(), (float*)gcs.out(), (float*)gcv.out(), N, D, nullptr);
-    };
-    auto guards = [&](std::initializer_list<std::pair<const GuardedOut*, const char*>> outs) -> int {
-        for (const auto& o : outs) {
-            if (!o.first->bytes) continue;
-            long where = 0;
-            HIPCHK(o.first->check(&where));
-            if (where) return set_err(VT_ERR_HIP, "ln chain wrote outside its %s: guard byte %ld changed", o.second, where);
-        }
-        return VT_OK;
+        return launch_fold_layernorm(dw.as<const bf16_t>(), dg.as<const float>(), dbeta.as<const float>(), dbias.as<const float>(),
+                                     gwf.as<bf16_t>(), gcs.as<float>(), gcv.as<float>(), N, D, nullptr);
     };
     auto fold_back = [&]() -> int {
-        if (wf_out) HIPCHK(hipMemcpy(wf_out, gwf.out(), WN * 2, hipMemcpyDeviceToHost));
-        if (colsum_out) HIPCHK(hipMemcpy(colsum_out, gcs.out(), (size_t)N * 4, hipMemcpyDeviceToHost));
-        if (cvec_out) HIPCHK(hipMemcpy(cvec_out, gcv.out(), (size_t)N * 4, hipMemcpyDeviceToHost));
+        if (wf_out) HIPCHK(gwf.download(wf_out));
+        if (colsum_out) HIPCHK(gcs.download(colsum_out));
+        if (cvec_out) HIPCHK(gcv.download(cvec_out));
         return VT_OK;
     };
     if (fold_only) {
         for (int rep = 0; rep < launches; ++rep) HIPCHK(fold());
         HIPCHK(hipDeviceSynchronize());
-        if (int rc = guards({{&gwf, "folded weights"}, {&gcs, "column sums"}, {&gcv, "constant vector"}})) return rc;
+        if (int rc = guards_intact("ln chain", {{&gwf, "folded weights"}, {&gcs, "column sums"}, {&gcv, "constant vector"}})) return rc;
         return fold_back();
     }
     HIPCHK(gemm_prepare());
     const int M = (int)Mll, nchunk = D / VT_STAT_CHUNK, H = D / 64, npad = ca.npad;
     const size_t MD = (size_t)M * D, n_out = epi == EPI_QKV ? (size_t)M * 2 * D : (size_t)M * N,
                  n_vt = epi == EPI_QKV ? (size_t)B * H * 64 * npad : 0, n_cnt = (size_t)(M + 255) / 256 + 1;
-    DevBuf dza, dzw, dzb, dpos, dcnt;
+    DevArr dza, dzw, dzb, dpos, dcnt;
     GuardedOut gxh, gxl, gcst, grs, gout, gvt;
-    HIPCHK(dza.alloc((size_t)M * 128 * 2)); HIPCHK(dzw.alloc((size_t)D * 128 * 2)); HIPCHK(dzb.alloc((size_t)D * 4));
-    HIPCHK(dpos.alloc(MD * 4)); HIPCHK(dcnt.alloc(n_cnt * 4));
+    HIPCHK(dza.zeros((size_t)M * 128 * 2)); HIPCHK(dzw.zeros((size_t)D * 128 * 2)); HIPCHK(dzb.zeros((size_t)D * 4));
+    HIPCHK(dcnt.zeros(n_cnt * 4)); HIPCHK(dpos.upload(x, MD * 4));
     HIPCHK(gxh.alloc(MD * 2)); HIPCHK(gxl.alloc(MD)); HIPCHK(gcst.alloc((size_t)M * nchunk * 8)); HIPCHK(grs.alloc((size_t)M * 8));
     HIPCHK(gout.alloc(n_out * 2));
     if (n_vt) HIPCHK(gvt.alloc(n_vt * 2));
-    HIPCHK(hipMemset(dza.p, 0, (size_t)M * 128 * 2)); HIPCHK(hipMemset(dzw.p, 0, (size_t)D * 128 * 2));
-    HIPCHK(hipMemset(dzb.p, 0, (size_t)D * 4)); HIPCHK(hipMemset(dcnt.p, 0, n_cnt * 4));
-    HIPCHK(hipMemcpy(dpos.p, x, MD * 4, hipMemcpyHostToDevice));
     // producer: (0 + 0) + pos = x exactly, through the X-epilogue's statistics and split
-    pa.A = (const bf16_t*)dza.p; pa.W = (const bf16_t*)dzw.p; pa.bias = (const float*)dzb.p;
-    pa.pos = (const float*)dpos.p; pa.Xh = (bf16_t*)gxh.out(); pa.Xl = (uint8_t*)gxl.out();
-    pa.cstat = (float2*)gcst.out(); pa.ln_eps = eps; pa.lq = lo_quant(lo_shift);
-    if (pcfg >= 0) { pa.tile_order = (pcfg >> 8) & 3; pcfg &= 0xff; }
-    if (route == 1) { pa.rowstat_out = (float2*)grs.out(); pa.panel_cnt = (unsigned*)dcnt.p; }
+    pa.A = dza.as<const bf16_t>(); pa.W = dzw.as<const bf16_t>(); pa.bias = dzb.as<const float>();
+    pa.pos = dpos.as<const float>(); pa.Xh = gxh.as<bf16_t>(); pa.Xl = gxl.as<uint8_t>();
+    pa.cstat = gcst.as<float2>(); pa.ln_eps = eps; pa.lq = lo_quant(lo_shift);
+    pa.tile_order = split_cfg(pcfg).order; pcfg = split_cfg(pcfg).cfg;
+    if (route == 1) { pa.rowstat_out = grs.as<float2>(); pa.panel_cnt = dcnt.as<unsigned>(); }
     if (pcfg < 0) pcfg = gemm_effective_config(pa, EPI_F32_POS);
     if (route == 1 && !(pcfg >= GEMM_CFG_256_MIN && gemm256_fits(pa, EPI_F32_POS)))
         return set_err(VT_ERR_INVALID_ARG, "ln chain: route 1 takes a 256x256 producer (configuration %d chosen)", pcfg);
     // consumer: A = the hi half, W = the folded weights, bias = cvec, row terms by route
-    ca.A = (const bf16_t*)gxh.out(); ca.W = (const bf16_t*)gwf.out(); ca.bias = (const float*)gcv.out();
-    ca.colsum = (const float*)gcs.out(); ca.ln_eps = eps;
-    if (epi == EPI_QKV) { ca.qk = (bf16_t*)gout.out(); ca.vt = (bf16_t*)gvt.out(); }
-    else ca.Cb = (bf16_t*)gout.out();
-    if (ccfg >= 0) { ca.tile_order = (ccfg >> 8) & 3; ccfg &= 0xff; }
-    if (route == 2) ca.cstat_in = (const float2*)gcst.out();
-    else ca.rowstat = (const float2*)grs.out();        // the pair load of the last even row ends in the guard band
+    ca.A = gxh.as<const bf16_t>(); ca.W = gwf.as<const bf16_t>(); ca.bias = gcv.as<const float>();
+    ca.colsum = gcs.as<const float>(); ca.ln_eps = eps;
+    if (epi == EPI_QKV) { ca.qk = gout.as<bf16_t>(); ca.vt = gvt.as<bf16_t>(); }
+    else ca.Cb = gout.as<bf16_t>();
+    ca.tile_order = split_cfg(ccfg).order; ccfg = split_cfg(ccfg).cfg;
+    if (route == 2) ca.cstat_in = gcst.as<const float2>();
+    else ca.rowstat = grs.as<const float2>();        // the pair load of the last even row ends in the guard band
     if (ccfg < 0) ccfg = gemm_effective_config(ca, epi);
     if (route == 2 && ccfg > GEMM_CFG_SMALL_MAX)
         return set_err(VT_ERR_INVALID_ARG, "ln chain: route 2 takes a 4-wave consumer (configuration %d chosen)", ccfg);
     for (int rep = 0; rep < launches; ++rep) {
         if (launch_gemm_cfg(pa, EPI_F32_POS, pcfg, nullptr) != hipSuccess)
             return set_err(VT_ERR_INVALID_ARG, "ln chain: producer configuration %d does not fit M=%d D=%d", pcfg, M, D);
-        if (route == 0) HIPCHK(launch_rowstat_finalize(pa.cstat, (float2*)grs.out(), M, nchunk, eps, nullptr));
+        if (route == 0) HIPCHK(launch_rowstat_finalize(pa.cstat, grs.as<float2>(), M, nchunk, eps, nullptr));
         HIPCHK(fold());
         if (launch_gemm_cfg(ca, epi, ccfg, nullptr) != hipSuccess)
             return set_err(VT_ERR_INVALID_ARG, "ln chain: consumer configuration %d does not fit M=%d N=%d D=%d", ccfg, M, N, D);
     }
     HIPCHK(hipDeviceSynchronize());
-    if (int rc = guards({{&gxh, "hi half"}, {&gxl, "lo8 half"}, {&gcst, "chunk partials"}, {&grs, "row terms"}, {&gout, "output"},
-                         {&gvt, "Vt"}, {&gwf, "folded weights"}, {&gcs, "column sums"}, {&gcv, "constant vector"}})) return rc;
+    if (int rc = guards_intact("ln chain", {{&gxh, "hi half"}, {&gxl, "lo8 half"}, {&gcst, "chunk partials"}, {&grs, "row terms"},
+                                            {&gout, "output"}, {&gvt, "Vt"}, {&gwf, "folded weights"}, {&gcs, "column sums"},
+                                            {&gcv, "constant vector"}})) return rc;
     std::vector<unsigned> cnt(n_cnt);
-    HIPCHK(hipMemcpy(cnt.data(), dcnt.p, n_cnt * 4, hipMemcpyDeviceToHost));
+    HIPCHK(dcnt.download(cnt.data()));
     for (size_t i = 0; i < n_cnt; ++i)
         if (cnt[i]) return set_err(VT_ERR_HIP, "ln chain: panel counter %zu is %u after %d launches", i, cnt[i], launches);
-    auto widen = [](const void* d, size_t count, float* o) -> hipError_t {
-        std::vector<bf16_t> tmp(count);
-        hipError_t e = hipMemcpy(tmp.data(), d, count * 2, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-        for (size_t i = 0; i < count; ++i) { uint32_t u = ((uint32_t)tmp[i]) << 16; memcpy(o + i, &u, 4); }
-        return hipSuccess;
-    };
-    HIPCHK(widen(gout.out(), n_out, out));
-    if (n_vt) HIPCHK(widen(gvt.out(), n_vt, vt_out));
-    if (xh_out) HIPCHK(hipMemcpy(xh_out, gxh.out(), MD * 2, hipMemcpyDeviceToHost));
-    if (xl_out) HIPCHK(hipMemcpy(xl_out, gxl.out(), MD, hipMemcpyDeviceToHost));
-    if (cstat_out) HIPCHK(hipMemcpy(cstat_out, gcst.out(), (size_t)M * nchunk * 8, hipMemcpyDeviceToHost));
-    if (rowstat_out) HIPCHK(hipMemcpy(rowstat_out, grs.out(), (size_t)M * 8, hipMemcpyDeviceToHost));
+    HIPCHK(download_bf16(gout.out(), n_out, out));
+    if (n_vt) HIPCHK(download_bf16(gvt.out(), n_vt, vt_out));
+    if (xh_out) HIPCHK(gxh.download(xh_out));
+    if (xl_out) HIPCHK(gxl.download(xl_out));
+    if (cstat_out) HIPCHK(gcst.download(cstat_out));
+    if (rowstat_out) HIPCHK(grs.download(rowstat_out));
     return fold_back();
 } VT_NOTHROW_INT
 

@@ -21,19 +21,15 @@ extern "C" {
  * K % 64 == 0, N % 64 == 0. cfg: tile configuration as in vt_op_gemm_bench (< 0: the launcher's own
  * choice for the shape). epilogue:
  *   0  x = acc + bias                    the X-epilogues the engine keeps its residual stream with: x is
- *   1  x = (acc + bias) + c_inout        stored as the 3-byte pair (hi = bf16(x), lo8 = clamp(rint((x - hi) * 2^12), +-127))
- *   4  x = (acc + bias) + pos            and comes back as hi + lo8 * 2^-12; pos = c_inout, one row per
+ *   1  x = (acc + bias) + c_inout        stored as the 3-byte pair (hi = bf16(x), lo8 = clamp(rint((x - hi) * 2^lo_shift), +-127))
+ *   4  x = (acc + bias) + pos            and comes back as hi + lo8 * 2^-lo_shift (lo_shift 6..14, the engine's default is
+ *                                        12; epilogue 1 takes c_inout through the same pair); pos = c_inout, one row per
  *                                        output row. rowstat_out (may be NULL) receives per row the terms
  *                                        (rstd, -mean * rstd) of LayerNorm(x) with `eps`, computed from the
  *                                        float32 x before the split (what the consuming GEMM multiplies with).
  *   2  GELU(y) -> bf16, 3  ReLU(y) -> bf16 (returned widened to f32); y = acc + bias, or with a folded
  *      LayerNorm (rowstat_in [M][2] and colsum [N] not NULL): y = rowstat_in[m][0] * acc +
  *      (rowstat_in[m][1] * colsum[n] + bias[n]). */
-int vt_op_gemm_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias,
-                    float* c_inout, int M, int N, int K, int epilogue, int cfg,
-                    const float* rowstat_in, const float* colsum, float* rowstat_out, float eps);
-/* The same with the pair's quantum 2^-lo_shift (6..14; vt_op_gemm_bf16 is lo_shift = 12): lo8 = clamp(rint((x - hi) *
- * 2^lo_shift), +-127), x comes back as hi + lo8 * 2^-lo_shift, and epilogue 1 decodes c_inout's pair with it. */
 int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, const float* bias,
                        float* c_inout, int M, int N, int K, int epilogue, int cfg,
                        const float* rowstat_in, const float* colsum, float* rowstat_out, float eps, int lo_shift);
@@ -54,7 +50,7 @@ int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* 
  * (K-tile depth 64); 4 = 64x64 ring 3, 5 = 64x64 ring 2, 6 = 128x128 ring 2 (K-tile depth 128, K % 128 == 0);
  * 7 = 64x64 ring 3 and 8 = 128x64 ring 3 with four loader waves (K-tile depth 128);
  * 18 / 19 = 256x256 8-wave kernels (one tile per workgroup / persistent); <0 = the launcher's own choice.
- * Bits 8-9 of a cfg >= 0 (here, in vt_op_gemm_bf16 and in vt_op_qkv_bf16) force the order in which an XCD's run of
+ * Bits 8-9 of a cfg >= 0 (here, in vt_op_gemm_bf16_lo and in vt_op_qkv_bf16) force the order in which an XCD's run of
  * workgroups covers the tile grid of configurations 0-8: 0 = the launcher's rule, 1 = row panels x all columns,
  * 2 = column tiles x all rows (placement only: the results are the same bits). */
 int vt_op_gemm_bench(int device_id, int M, int N, int K, int epilogue, int cfg, int iters,
@@ -68,20 +64,18 @@ int vt_op_conv3x3_relu_bf16(int device_id, const uint16_t* t, const uint16_t* w,
 /* The head's band kernel (csrc/k_head.hip) on its own: out = relu(conv(t) + bias). conv3x3 != 0: t [B*grid*grid][Cin],
  * w [N][9*Cin] (column (ky*3+kx)*Cin + c), N == Cin, zero padding; else the 1x1 layer, w [N][Cin]. R (rows of the
  * map per workgroup) / ncb (16-column blocks per wave) <= 0: the launcher's plan. t == NULL: operands filled with a
- * fixed pseudo-random pattern (timing runs). out (nullable): bf16 values widened to f32. iters > 0 and us_out: mean
- * microseconds per launch. */
+ * fixed pseudo-random pattern (timing runs). out (nullable): bf16 values widened to f32. us_out (nullable): mean
+ * microseconds per launch over `iters` launches; asking for it with iters < 1 is VT_ERR_INVALID_ARG, as in the timing
+ * helpers. */
 int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, const float* bias, float* out,
                         int B, int grid, int Cin, int N, int conv3x3, int R, int ncb, int iters, float* us_out);
 /* The head's first (1x1) layer with the final LayerNorm in front of it: out[b*grid*grid + cell][n] =
- * relu(LayerNorm(xh + xl * 2^-12)[b*ntok + off + cell] . w[n] + bias[n]); xh (bf16 bits) / xl (signed bytes) [B*ntok][D] the
- * 3-byte pair of the residual stream, gamma / beta [D], w [N][D], D = 768 or 1024. fused != 0: ONE launch - the band kernel normalises its band's
+ * relu(LayerNorm(xh + xl * 2^-lo_shift)[b*ntok + off + cell] . w[n] + bias[n]); xh (bf16 bits) / xl (signed bytes) [B*ntok][D] the
+ * 3-byte pair of the residual stream with the quantum 2^-lo_shift (6..14, the engine's default is 12), gamma / beta [D],
+ * w [N][D], D = 768 or 1024. fused != 0: ONE launch - the band kernel normalises its band's
  * rows itself (what the engine runs); fused == 0: the LayerNorm kernel, then the band kernel on its output - the fused
- * form reproduces it bit for bit. R / ncb / iters / us_out / out as above; xh == NULL: synthetic operands (timing). */
-int vt_op_headconv_ln_bf16(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
-                           float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
-                           int D, int N, int fused, int R, int ncb, int iters, float* us_out);
-/* The same on a pair whose quantum is 2^-lo_shift (6..14; vt_op_headconv_ln_bf16 is lo_shift = 12). fused == 0 runs the
- * stand-alone LayerNorm kernel's pair reader (csrc/k_misc.hip), fused != 0 the band kernel's. */
+ * form reproduces it bit for bit: fused == 0 runs the stand-alone LayerNorm kernel's pair reader (csrc/k_misc.hip),
+ * fused != 0 the band kernel's. R / ncb / iters / us_out / out as above; xh == NULL: synthetic operands (timing). */
 int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* xl, const float* gamma, const float* beta,
                               float eps, int ntok, int off, const uint16_t* w, const float* bias, float* out, int B, int grid,
                               int D, int N, int fused, int R, int ncb, int iters, float* us_out, int lo_shift);
@@ -165,7 +159,7 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
  * vt_perm = 1: Vt in the key order attention mode 3 reads (attn_perm16 inside every 16 keys).
- * rowstat_in [B*tokens][2] / colsum [3D] (both or neither NULL): a folded LayerNorm as in vt_op_gemm_bf16. */
+ * rowstat_in [B*tokens][2] / colsum [3D] (both or neither NULL): a folded LayerNorm as in vt_op_gemm_bf16_lo. */
 int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const float* bias,
                    float* qk_out, float* vt_out, int B, int tokens, int D, int cfg, int vt_perm,
                    const float* rowstat_in, const float* colsum);
@@ -207,7 +201,7 @@ int vt_op_layernorm(int device_id, const float* x, const float* gamma, const flo
  *             4 QKV (N == 3 * D, tokens % 4 == 0): out = qk [M][2D], vt_out = Vt [B * D / 64][64][npad] in natural key
  *             order, as vt_op_qkv_bf16 returns them (pad columns of Vt stay 0xff);
  *             0 the fold alone (x, B, tokens, route and the configurations are ignored; N >= 1, D even).
- * producer_cfg / consumer_cfg as in vt_op_gemm_bf16 (< 0: the launcher's choice). The chain runs `launches` (1..16)
+ * producer_cfg / consumer_cfg as in vt_op_gemm_bf16_lo (< 0: the launcher's choice). The chain runs `launches` (1..16)
  * times on the same buffers; the panel counters of route 1 must be zero afterwards (VT_ERR_HIP otherwise). Every
  * device output starts as 0xff between guard bands; a changed guard byte is VT_ERR_HIP. VT_ERR_INVALID_ARG, with
  * nothing launched and no output written: route 1 with a producer configuration below 18, D % 256 or D > 1536;

@@ -20,4 +20,4 @@ for r in range(rounds):
         assert rc == 0, rc
         t[p].append(us.value)
 for p in paths:
-    print(f"M {M} N {N} K {K} epi {epi} cfg {cfg} {p.split('/')[-1]:36s} med {np.median(t[p]):7.2f} min {min(t[p]):7.2f} us", flush=True)
+    print(f"M {M} N {N} K {K} epi {epi} cfg {cfg} {p.split('/')[-1]:36s} med {np.median(t[p]):7.2f} min {min(t[p]):7.2f} max {max(t[p]):7.2f} us", flush=True)
