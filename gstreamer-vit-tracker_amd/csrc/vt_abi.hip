@@ -374,10 +374,8 @@ int vt_group_set_tuning(vt_group* g, const char* key, int value) try {
     DEVICE_SCOPE(e->device);
     HIPCHK(hipStreamSynchronize(e->stream));
     const std::string k = key;
-    if (Engine::overlay_key(k)) return e->set_overlay(k, value);    // engine options: the passes are captured again by the first enable only
-    if (Engine::motion_key(k)) return e->set_motion(k, value);
-    if (Engine::appearance_key(k)) return e->set_appearance(k, value);
-    if (Engine::proposals_key(k)) return e->set_proposals(k, value);
+    for (const KeyedFeature& f : keyed_features())     // engine options: the passes are captured again by the first enable only
+        if (k.rfind(f.prefix, 0) == 0) return e->set_keyed(f, k, value);
     if (k == "head_band") e->head_band_kernel = value < 0 ? 2 : value;   // 0 / 1 / 2, see Engine::head_band_kernel
     else if (k == "last_rows") e->last_rows = value != 0;        // 0: the last block runs all rows; else (default) the search rows where eligible
     else if (k == "crop_tier") e->crop_tier_forced = value;      // < 0: chosen per pass from the known boxes (default)
@@ -491,33 +489,16 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         return set_err(VT_ERR_HIP, "read_tensor: sync failed");
     const ModelDims& d = e->d;
     std::string n(name);
-    if (n == "result_overlay") {        // by stream, whatever the last pass was: the overlay's flags and the stream's counters
-        if (!out) return e->overlay_capable ? 6 : e->overlay_stats(stream, nullptr);
-        if (capacity < 6) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
-        if (int rc = e->overlay_stats(stream, out)) return rc;
-        return 6;
-    }
-    if (n == "motion") {                // by stream, whatever the last pass was: the engine flag and the stream's record
-        if (!out) return e->motion_capable ? 8 : e->motion_stats(stream, nullptr);
-        if (capacity < 8) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
-        if (int rc = e->motion_stats(stream, out)) return rc;
-        return 8;
-    }
-    if (n == "appearance") {            // by stream, whatever the last pass was: the engine flag, the stream's record and counters
-        if (!out) return e->appear_capable ? 8 : e->appearance_stats(stream, nullptr);
-        if (capacity < 8) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
-        if (int rc = e->appearance_stats(stream, out)) return rc;
-        return 8;
+    for (const KeyedFeature& f : keyed_features()) {      // by stream, whatever the last pass was: the policy, the stream's record and counters
+        if (n != f.tensor) continue;
+        if (!out) return e->*f.capable ? f.stats_len : (e->*f.stats)(stream, nullptr);
+        if (capacity < f.stats_len) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        const int rc = (e->*f.stats)(stream, out);
+        return rc ? rc : f.stats_len;
     }
     if (n == "anchor" || n == "probe") {    // by stream: the rows the stream is compared with / the rows of its last cut probe
         if (!e->appear_capable) return e->appearance_stats(stream, nullptr);
         return copy_out_bf16(n == "anchor" ? e->d_anchor(stream) : e->d_probe(stream), (int64_t)d.nt * d.kpad, out, capacity);
-    }
-    if (n == "proposals") {             // by stream, whatever the last pass was: the policy, the stream's record and counter
-        if (!out) return e->prop_capable ? VT_PROP_STATS : e->proposals_stats(stream, nullptr);
-        if (capacity < VT_PROP_STATS) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
-        if (int rc = e->proposals_stats(stream, out)) return rc;
-        return VT_PROP_STATS;
     }
     if (n == "proposals_pattern" || n == "proposals_map") {     // of the stream's slot in the last pass, as its header says
         if (!e->prop_capable) return e->proposals_stats(stream, nullptr);

@@ -37,16 +37,18 @@ void Engine::destroy() {
     drop_graphs();
     void* devp[] = {d_blob, d_patches, d_tpl, d_qk, d_vt, d_attn, d_mlp, d_feat, d_ta, d_tb, d_zeros,
                     d_xh, d_xl, d_cstat, d_rstat, d_panel_cnt, d_band_cnt, d_band_best, d_foldw, d_foldv, d_headout, d_taps, d_states, d_frames,
-                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks, d_overlay, d_motion, d_appear, d_prop};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
+                    d_results, d_cand_states, d_cands, d_winner, d_xrange, d_policy, d_tickets, d_chips, d_chip_policy, d_peaks};     // d_chip_infos: part of d_chips, d_peaks_policy: of d_peaks
     for (void* p : devp)
         if (p) (void)hipFree(p);
+    for (const KeyedFeature& f : keyed_features())      // the keyed features' stores: from their list
+        if (this->*f.store) (void)hipFree(this->*f.store);
     if (h_chip_stage) (void)hipHostFree(h_chip_stage);
     if (h_cands) (void)hipHostFree(h_cands);
     if (h_winner) (void)hipHostFree(h_winner);
     if (h_frames) (void)hipHostFree(h_frames);
     if (h_state) (void)hipHostFree(h_state);
     stage.release();
-    PassOut own = own_sinks();
+    PassOut own = pass_sinks(nullptr, true);     // a mirror of a feature the engine is not capable of: null
     sinks_free(&own, SINK_ALL);
     for (HostSlot& sl : hs) {
         sl.arena.release();
@@ -867,11 +869,7 @@ int Engine::build_block(const int32_t* map, const vt_frame* frames, int n, const
         to_desc(frames[i], hf + i);
         ps->any_layout = std::max(ps->any_layout, pix_level(frames[i].format));
     }
-    const PassOut own = own_sinks();
-    const PassOut& to = sinks ? *sinks : own;
-    *(PassOut*)(hf + B) = PassOut{to.host_results, by_stream_states ? to.host_states : nullptr,
-                                  peaks_capable ? to.host_peaks : nullptr, motion_capable ? to.host_motion : nullptr,
-                                  appear_capable ? to.host_appearance : nullptr, prop_capable ? to.host_proposals : nullptr};
+    *(PassOut*)(hf + B) = pass_sinks(sinks, by_stream_states);
     if (map) std::copy(map, map + n, (int32_t*)((char*)hf + map_offset()));
     *(int32_t*)((char*)hf + devflag_offset()) = frames_on_device;
     HIPCHK(hipMemcpyAsync(d_frames, hf, frames_block_bytes(), hipMemcpyHostToDevice, stream));
@@ -938,639 +936,6 @@ int Engine::wait(vt_result* out, int n) {
         for (int b = 0; b < B; ++b) known[b] = h_states_all[b];
         for (int b = 0; b < B && motion_capable; ++b) known_motion[(size_t)b] = h_motion_all[b];
         peaks_n = pass_n;                           // h_peaks holds the records of the pass just waited for
-    }
-    return VT_OK;
-}
-
-// ---- the first enable of an optional feature -------------------------------------------------------------
-
-// The one transaction (vt_engine.hpp: Feature). The captured passes are those of an engine without the feature: they
-// are dropped and captured again, as vt_group_set_tuning does.
-int Engine::enable_feature(const Feature& f) {
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    const double mib = f.extra / 1048576.0;
-    if (max_device_bytes && activation_bytes() + blob_bytes + feature_bytes() + f.extra > max_device_bytes)
-        return set_err(VT_ERR_OOM, "%s: needs %.3f MiB more HBM; vt_config.max_device_mib allows %.1f in all", f.name, mib,
-                       max_device_bytes / 1048576.0);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && f.extra > free_b)
-        return set_err(VT_ERR_OOM, "%s: needs %.3f MiB more HBM; %.1f MiB are free", f.name, mib, free_b / 1048576.0);
-    hipError_t he = f.alloc();
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);    // the fills and copies have landed
-    if (he != hipSuccess) {
-        f.uninstall();
-        return set_err(he == hipErrorOutOfMemory ? VT_ERR_OOM : VT_ERR_HIP, "%s: %s", f.name, hipGetErrorString(he));
-    }
-    f.install();
-    drop_graphs();
-    if (int rc = capture_all_graphs()) {
-        char keep[512];
-        memcpy(keep, vt_err_text(), sizeof(keep));
-        drop_graphs();
-        f.uninstall();
-        (void)capture_all_graphs();     // the passes the engine had; should that fail too, enqueue() captures on demand
-        memcpy(vt_err_text(), keep, sizeof(keep));
-        return rc;
-    }
-    if (f.commit) f.commit();
-    return VT_OK;
-}
-
-template <typename T>
-static hipError_t pinned0(T** p, size_t count) {
-    if (*p) return hipSuccess;
-    hipError_t e = hipHostMalloc((void**)p, count * sizeof(T));
-    if (e == hipSuccess) memset(*p, 0, count * sizeof(T));
-    return e;
-}
-
-hipError_t Engine::sinks_alloc(PassOut* o, unsigned members) const {
-    hipError_t e = hipSuccess;
-    if (members & SINK_BASE) e = pinned0(&o->host_results, (size_t)B);
-    if (e == hipSuccess && (members & SINK_BASE)) e = pinned0(&o->host_states, (size_t)B);
-    if (e == hipSuccess && (members & SINK_PEAKS)) e = pinned0(&o->host_peaks, (size_t)B);
-    if (e == hipSuccess && (members & SINK_MOTION)) e = pinned0(&o->host_motion, (size_t)B);
-    if (e == hipSuccess && (members & SINK_APPEAR)) e = pinned0(&o->host_appearance, (size_t)B);
-    if (e == hipSuccess && (members & SINK_PROP)) e = pinned0(&o->host_proposals, (size_t)B);
-    return e;
-}
-
-void Engine::sinks_free(PassOut* o, unsigned members) const {
-    auto drop = [](auto** p) { if (*p) (void)hipHostFree(*p); *p = nullptr; };
-    if (members & SINK_BASE) { drop(&o->host_results); drop(&o->host_states); }
-    if (members & SINK_PEAKS) drop(&o->host_peaks);
-    if (members & SINK_MOTION) drop(&o->host_motion);
-    if (members & SINK_APPEAR) drop(&o->host_appearance);
-    if (members & SINK_PROP) drop(&o->host_proposals);
-}
-
-// ---- template refresh --------------------------------------------------------------------------------
-
-int Engine::reset_refresh_tickets() {
-    if (d_tickets) HIPCHK(hipMemsetAsync(d_tickets, 0, sizeof(unsigned) * (size_t)B, stream));
-    if (appear_capable) HIPCHK(hipMemsetAsync(d_appear_tickets(), 0, sizeof(unsigned) * (size_t)B, stream));
-    return VT_OK;
-}
-
-// The first enabled policy: the store grows to two buffers per stream (buffer tpl_gen & 1 = the stream's rows), policy
-// array and tickets are allocated. The old store is kept until the new passes exist: a failed capture puts it back.
-int Engine::enable_refresh() {
-    if (refresh_capable) return VT_OK;
-    const size_t rows = (size_t)d.nt * d.kpad;
-    bf16_t *tpl2 = nullptr, *const tpl1 = d_tpl;
-    RefreshPolicy* pol = nullptr;
-    unsigned* tick = nullptr;
-    const bool moved = segments_moved;
-    auto alloc = [&] {
-        std::vector<StreamState> sts((size_t)B);     // before the device allocations: may throw
-        hipError_t he = dalloc0(&tpl2, 2 * rows * (size_t)B, stream);
-        if (he == hipSuccess) he = dalloc0(&pol, (size_t)B, stream);
-        if (he == hipSuccess) he = dalloc0(&tick, (size_t)B, stream);
-        if (he == hipSuccess)
-            he = hipMemcpy2DAsync(tpl2, 2 * rows * sizeof(bf16_t), tpl1, rows * sizeof(bf16_t), rows * sizeof(bf16_t),
-                                  (size_t)B, hipMemcpyDeviceToDevice, stream);
-        // a stream that was imported (vt_snapshot.hip) may carry an odd tpl_gen in this single-buffer engine: its current rows
-        // belong into buffer tpl_gen & 1 of the new store, where every reader will look for them (buffer 0 keeps a copy)
-        if (he == hipSuccess) he = hipMemcpyAsync(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost, stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(stream);
-        for (int b = 0; b < B && he == hipSuccess; ++b)
-            if (sts[(size_t)b].tpl_gen & 1)
-                he = hipMemcpyAsync(tpl2 + ((size_t)b * 2 + 1) * rows, tpl1 + (size_t)b * rows, rows * sizeof(bf16_t),
-                                    hipMemcpyDeviceToDevice, stream);
-        return he;
-    };
-    auto install = [&] {
-        d_tpl = tpl2; d_policy = pol; d_tickets = tick;
-        refresh_capable = true;
-        segments_moved = false;
-    };
-    auto uninstall = [&] {
-        d_tpl = tpl1; d_policy = nullptr; d_tickets = nullptr;
-        refresh_capable = false;
-        segments_moved = moved;
-        (void)hipFree(tpl2); (void)hipFree(pol); (void)hipFree(tick);     // null: no operation
-    };
-    return enable_feature({"template refresh", refresh_bytes(), alloc, install, uninstall, [&] { (void)hipFree(tpl1); }});
-}
-
-int Engine::set_refresh(int s, int period, float min_score) {
-    if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "template refresh: stream %d out of range (-1..%d)", s, B - 1);
-    if (period < 0 || period == 1 || period > VT_REFRESH_MAX_PERIOD)
-        return set_err(VT_ERR_INVALID_ARG, "template refresh: period %d (0 = off, else 2..%d)", period, VT_REFRESH_MAX_PERIOD);
-    if (!std::isfinite(min_score) || min_score < 0.0f || min_score > 1.0f)
-        return set_err(VT_ERR_INVALID_ARG, "template refresh: min_score must be finite and in 0..1");
-    if (period > 0)
-        if (int rc = enable_refresh()) return rc;
-    const int s0 = s < 0 ? 0 : s, s1 = s < 0 ? B : s + 1;
-    if (refresh_capable) {      // period and min_score only: the diagnostic counter behind them is the device's
-        DEVICE_SCOPE(device);
-        HIPCHK(hipStreamSynchronize(stream));
-        for (int b = s0; b < s1; ++b) {
-            const RefreshPolicy p{period, min_score, 0, 0};
-            HIPCHK(hipMemcpy(d_policy + b, &p, 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        if (int rc = reset_refresh_tickets()) return rc;
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    for (int b = s0; b < s1; ++b) { h_policy[(size_t)b].period = period; h_policy[(size_t)b].min_score = min_score; }
-    return VT_OK;
-}
-
-int Engine::refresh_stats(int s, vt_refresh_stats* out) {
-    if (!out) return set_err(VT_ERR_INVALID_ARG, "null argument");
-    if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "template refresh: stream %d out of range (0..%d)", s, B - 1);
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    memset(out, 0, sizeof(*out));
-    out->period = h_policy[(size_t)s].period;
-    out->min_score = h_policy[(size_t)s].min_score;
-    if (refresh_capable) {
-        RefreshPolicy p{};
-        HIPCHK(hipMemcpy(&p, d_policy + s, sizeof(p), hipMemcpyDeviceToHost));
-        out->skipped_geometry = p.skipped_geometry;
-    }
-    StreamState st{};
-    HIPCHK(hipMemcpy(&st, d_states + s, sizeof(st), hipMemcpyDeviceToHost));
-    out->generation = st.tpl_gen;
-    out->last_frame = st.tpl_frame;
-    return VT_OK;
-}
-
-// ---- target chips ------------------------------------------------------------------------------------
-
-// The first enable allocates the store (enable_feature). A second enable with the same parameters is a no-op.
-int Engine::enable_chips(int size, int kind, const float* na, const float* nb) {
-    if (size < 32 || size > 512 || size % 8 != 0)
-        return set_err(VT_ERR_INVALID_ARG, "chips: size %d (a multiple of 8 in 32..512)", size);
-    if (kind != VT_CHIP_NORM_BF16 && kind != VT_CHIP_RGB8) return set_err(VT_ERR_INVALID_ARG, "chips: unknown kind %d", kind);
-    float a3[3] = {1.0f, 1.0f, 1.0f}, b3[3] = {0.0f, 0.0f, 0.0f};
-    if (kind == VT_CHIP_NORM_BF16) {
-        if (!na || !nb) return set_err(VT_ERR_INVALID_ARG, "chips: the bf16 kind needs norm_a and norm_b");
-        for (int c = 0; c < 3; ++c) {
-            if (!std::isfinite(na[c]) || !std::isfinite(nb[c])) return set_err(VT_ERR_INVALID_ARG, "chips: norms must be finite");
-            a3[c] = na[c]; b3[c] = nb[c];
-        }
-    }
-    if (chip_capable) {
-        if (size != chip_size || kind != chip_kind || memcmp(a3, chip_na, sizeof(a3)) != 0 || memcmp(b3, chip_nb, sizeof(b3)) != 0)
-            return set_err(VT_ERR_INVALID_ARG, "chips: the engine's chips are fixed at size %d, kind %d and the norms of the "
-                           "first enable", chip_size, chip_kind);
-        return VT_OK;
-    }
-    const size_t cb = chip_bytes_of(size, kind);
-    uint8_t* chips = nullptr;       // one allocation: [B][cb] chips | [B] infos (cb is a multiple of 192: the infos are aligned)
-    ChipPolicy* pol = nullptr;
-    auto alloc = [&] {
-        hipError_t he = dalloc0(&chips, (cb + sizeof(vt_chip_info)) * (size_t)B, stream);
-        return he == hipSuccess ? dalloc0(&pol, (size_t)B, stream) : he;
-    };
-    auto install = [&] {
-        d_chips = chips; d_chip_infos = reinterpret_cast<vt_chip_info*>(chips + cb * (size_t)B); d_chip_policy = pol;
-        chip_size = size; chip_kind = kind;
-        memcpy(chip_na, a3, sizeof(a3)); memcpy(chip_nb, b3, sizeof(b3));
-        chip_capable = true;
-    };
-    auto uninstall = [&] {
-        (void)hipFree(chips); (void)hipFree(pol);       // null: no operation
-        d_chips = nullptr; d_chip_infos = nullptr; d_chip_policy = nullptr;
-        chip_capable = false;
-        chip_size = chip_kind = 0;
-    };
-    return enable_feature({"chips", chip_store_bytes_of(B, size, kind), alloc, install, uninstall});
-}
-
-int Engine::set_chips(int s, float factor, int period, int phase) {
-    if (!chip_capable) return set_err(VT_ERR_INVALID_ARG, "chips: not enabled on this engine (vt_group_enable_chips)");
-    if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "chips: stream %d out of range (-1..%d)", s, B - 1);
-    if (!(factor == 0.0f || (factor >= 0.5f && factor <= 4.0f)))     // a NaN fails both
-        return set_err(VT_ERR_INVALID_ARG, "chips: factor must be 0 (off) or in 0.5..4");
-    if (period < 1 || period > VT_CHIP_MAX_PERIOD)
-        return set_err(VT_ERR_INVALID_ARG, "chips: period %d (1..%d)", period, VT_CHIP_MAX_PERIOD);
-    if (phase < 0 || phase >= period) return set_err(VT_ERR_INVALID_ARG, "chips: phase %d (0..period-1 = %d)", phase, period - 1);
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    const ChipPolicy p{factor == 0.0f ? 0.0f : factor, period, phase, 0};
-    for (int b = s < 0 ? 0 : s; b < (s < 0 ? B : s + 1); ++b)
-        HIPCHK(hipMemcpy(d_chip_policy + b, &p, sizeof(p), hipMemcpyHostToDevice));
-    return VT_OK;
-}
-
-// behind every queued pass on the group's stream: ONE device-to-host copy of the store's bytes from the first listed
-// stream's chip (infos only: info) to the last listed stream's info (chips only: chip) into the pinned mirror, then handed out
-int Engine::read_chips(const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos) {
-    if (!chip_capable) return set_err(VT_ERR_INVALID_ARG, "chips: not enabled on this engine (vt_group_enable_chips)");
-    const size_t cb = chip_bytes(), ib = sizeof(vt_chip_info), info0 = (size_t)B * cb;
-    if (n < 1 || n > B || (out && out_stride < cb) || (!out && !infos))
-        return set_err(VT_ERR_INVALID_ARG, "read_chips: bad count, stride or no output");
-    int lo = B, hi = -1;
-    for (int i = 0; i < n; ++i) {
-        const int s = streams ? streams[i] : i;
-        if (s < 0 || s >= B) return set_err(VT_ERR_INVALID_ARG, "read_chips: stream %d out of range (0..%d)", s, B - 1);
-        lo = std::min(lo, s); hi = std::max(hi, s);
-    }
-    DEVICE_SCOPE(device);
-    if (!h_chip_stage) HIPCHK(hipHostMalloc((void**)&h_chip_stage, (size_t)B * (cb + ib), hipHostMallocDefault));
-    const size_t from = out ? (size_t)lo * cb : info0 + (size_t)lo * ib;
-    const size_t to = infos ? info0 + (size_t)(hi + 1) * ib : (size_t)(hi + 1) * cb;
-    HIPCHK(hipMemcpyAsync(h_chip_stage + from, d_chips + from, to - from, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    for (int i = 0; i < n; ++i) {
-        const int s = streams ? streams[i] : i;
-        if (out) memcpy((uint8_t*)out + (size_t)i * out_stride, h_chip_stage + (size_t)s * cb, cb);
-        if (infos) memcpy(infos + i, h_chip_stage + info0 + (size_t)s * ib, ib);
-    }
-    return VT_OK;
-}
-
-// ---- response peaks ----------------------------------------------------------------------------------
-
-// The policy of stream s (-1: all). The first policy with max_peaks > 0 allocates the records, the policies and the
-// pinned mirrors (enable_feature).
-int Engine::set_peaks(int s, int max_peaks, int radius, float min_resp) {
-    if (s < -1 || s >= B) return set_err(VT_ERR_INVALID_ARG, "peaks: stream %d out of range (-1..%d)", s, B - 1);
-    if (max_peaks < 0 || max_peaks > VT_PEAKS_MAX)
-        return set_err(VT_ERR_INVALID_ARG, "peaks: max_peaks %d (0: off, else 1..%d)", max_peaks, VT_PEAKS_MAX);
-    if (radius < 1 || radius > 4) return set_err(VT_ERR_INVALID_ARG, "peaks: radius %d (1..4)", radius);
-    if (!(min_resp >= 0.0f && min_resp <= 1.0f))       // a NaN fails both
-        return set_err(VT_ERR_INVALID_ARG, "peaks: min_resp must be finite in 0..1");
-    if (!peaks_capable && max_peaks == 0)
-        return set_err(VT_ERR_INVALID_ARG, "peaks: not enabled on this engine (a policy with max_peaks > 0 enables it)");
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    if (!peaks_capable) {
-        uint8_t* store = nullptr;       // one allocation: [B] records | [B] policies, all zero (every policy off)
-        PassOut own{};                  // the engine's own mirror
-        auto alloc = [&] {
-            peaks_policy.assign((size_t)B, PeaksPolicy{0, 0, 0.0f, 0});     // before the device allocation: may throw
-            hipError_t he = dalloc0(&store, peaks_bytes(), stream);
-            if (he == hipSuccess) he = sinks_alloc(&own, SINK_PEAKS);
-            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
-                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_PEAKS);
-            return he;
-        };
-        auto install = [&] {
-            d_peaks = reinterpret_cast<vt_peaks*>(store);
-            d_peaks_policy = reinterpret_cast<PeaksPolicy*>(store + sizeof(vt_peaks) * (size_t)B);
-            h_peaks = own.host_peaks;
-            peaks_n = 0;
-            peaks_capable = true;
-        };
-        auto uninstall = [&] {
-            (void)hipFree(store);       // null: no operation
-            sinks_free(&own, SINK_PEAKS);
-            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_PEAKS);
-            d_peaks = nullptr; d_peaks_policy = nullptr; h_peaks = nullptr;
-            peaks_policy.clear();
-            peaks_capable = false;
-        };
-        if (int rc = enable_feature({"peaks", peaks_bytes(), alloc, install, uninstall})) return rc;
-    }
-    const PeaksPolicy p{max_peaks, radius, min_resp == 0.0f ? 0.0f : min_resp, 0};
-    for (int b = s < 0 ? 0 : s; b < (s < 0 ? B : s + 1); ++b) {
-        HIPCHK(hipMemcpy(d_peaks_policy + b, &p, sizeof(p), hipMemcpyHostToDevice));
-        peaks_policy[(size_t)b] = p;
-    }
-    return VT_OK;
-}
-
-int Engine::last_peaks(vt_peaks* out, int n) const {
-    if (!peaks_capable) return set_err(VT_ERR_INVALID_ARG, "peaks: not enabled on this engine (vt_group_set_peaks)");
-    if (!out || n < 1) return set_err(VT_ERR_INVALID_ARG, "last_peaks: null output or n < 1");
-    for (int i = 0; i < std::min(n, peaks_n); ++i) out[i] = h_peaks[i];
-    return VT_OK;
-}
-
-// ---- result overlay ----------------------------------------------------------------------------------
-
-// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero flags allocate the policy record and
-// the counters (enable_feature). Every later change is one small copy: the passes read the record.
-int Engine::set_overlay(const std::string& key, int value) {
-    OverlayPolicy p = overlay_policy;
-    const OverlayPolicy def = VT_OVERLAY_DEFAULT_POLICY;
-    if (key == "result_overlay") {
-        p.flags = value < 0 ? def.flags : value;
-        if (p.flags > 7) return set_err(VT_ERR_INVALID_ARG, "result_overlay: flags %d (1 rectangle | 2 crosshair | 4 label, 0: off)", value);
-    } else if (key == "result_overlay_style") {
-        const int th = value & 255, size = (value >> 8) & 255, scale = value >> 16;
-        if (value < 0) { p.thickness = def.thickness; p.size = def.size; p.scale = def.scale; }
-        else if (th < 1 || th > 16 || size < 1 || size > 64 || scale < 1 || scale > 4)
-            return set_err(VT_ERR_INVALID_ARG, "result_overlay_style: thickness %d (1..16), size %d (1..64), scale %d (1..4)", th, size, scale);
-        else { p.thickness = th; p.size = size; p.scale = scale; }
-    } else if (key == "result_overlay_luma") {
-        p.luma = value < 0 ? def.luma : value;
-        if (p.luma > 255) return set_err(VT_ERR_INVALID_ARG, "result_overlay_luma: %d (0..255)", value);
-    } else if (key == "result_overlay_rgb") {
-        p.rgb = value < 0 ? def.rgb : value;
-        if (p.rgb > 0xFFFFFF) return set_err(VT_ERR_INVALID_ARG, "result_overlay_rgb: 0x%x (0..0xFFFFFF)", (unsigned)value);
-    } else if (key == "result_overlay_min_score_pct") {
-        p.min_score_pct = value < 0 ? def.min_score_pct : value;
-        if (p.min_score_pct > 100) return set_err(VT_ERR_INVALID_ARG, "result_overlay_min_score_pct: %d (0..100)", value);
-    } else {
-        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
-    }
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    if (!overlay_capable && p.flags != 0) {
-        uint8_t* store = nullptr;       // the policy | [B] counters, all zero
-        auto alloc = [&] {
-            hipError_t he = dalloc0(&store, overlay_bytes(), stream);
-            return he == hipSuccess ? hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream) : he;
-        };
-        auto install = [&] { d_overlay = store; overlay_capable = true; };
-        auto uninstall = [&] {
-            (void)hipFree(store);       // null: no operation
-            d_overlay = nullptr;
-            overlay_capable = false;
-        };
-        if (int rc = enable_feature({"result overlay", overlay_bytes(), alloc, install, uninstall})) return rc;
-    } else if (overlay_capable) {
-        HIPCHK(hipMemcpy(d_overlay_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
-    }
-    overlay_policy = p;
-    return VT_OK;
-}
-
-// [6]: flags, drawn by the stream's last pass, passes drawn / gated / on a format that is not drawable, N of the last label
-int Engine::overlay_stats(int s, float* out6) {
-    if (!overlay_capable)
-        return set_err(VT_ERR_INVALID_ARG, "result overlay: not enabled on this engine (vt_group_set_tuning \"result_overlay\")");
-    OverlayStats st{};
-    HIPCHK(hipMemcpy(&st, d_overlay_stats() + s, sizeof(st), hipMemcpyDeviceToHost));
-    out6[0] = (float)overlay_policy.flags; out6[1] = (float)st.drawn_last; out6[2] = (float)st.n_drawn;
-    out6[3] = (float)st.n_gated; out6[4] = (float)st.n_unsupported; out6[5] = (float)st.last_n;
-    return VT_OK;
-}
-
-// ---- motion prior ------------------------------------------------------------------------------------
-
-// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "motion_prior" allocates the policy
-// record, the records and their pinned mirrors (enable_feature). Every later change is one small copy: the passes read
-// the record. "motion_prior" 0 zeroes every stream's record.
-int Engine::set_motion(const std::string& key, int value) {
-    MotionPolicy p = motion_policy;
-    const MotionPolicy def = VT_MOTION_DEFAULT_POLICY;
-    if (key == "motion_prior") {
-        p.on = value < 0 ? def.on : value;
-        if (p.on > 1) return set_err(VT_ERR_INVALID_ARG, "motion_prior: %d (0: off, 1: on)", value);
-    } else if (key == "motion_gain_pct") {
-        p.gain_pct = value < 0 ? def.gain_pct : value;
-        if (p.gain_pct < 1 || p.gain_pct > 100) return set_err(VT_ERR_INVALID_ARG, "motion_gain_pct: %d (1..100)", value);
-    } else if (key == "motion_coast") {
-        p.coast = value < 0 ? def.coast : value;
-        if (p.coast > 60) return set_err(VT_ERR_INVALID_ARG, "motion_coast: %d (0..60)", value);
-    } else if (key == "motion_max_pct") {
-        p.max_pct = value < 0 ? def.max_pct : value;
-        if (p.max_pct > 200) return set_err(VT_ERR_INVALID_ARG, "motion_max_pct: %d (0..200)", value);
-    } else {
-        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
-    }
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    if (!motion_capable && p.on != 0) {
-        uint8_t* store = nullptr;       // the policy | [B] records, all zero
-        PassOut own{};                  // the engine's own mirror
-        auto alloc = [&] {
-            hipError_t he = dalloc0(&store, motion_bytes(), stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
-            if (he == hipSuccess) he = sinks_alloc(&own, SINK_MOTION);
-            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
-                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_MOTION);
-            return he;
-        };
-        auto install = [&] {
-            d_motion = store; h_motion_all = own.host_motion;
-            known_motion.assign((size_t)B, MotionRec{});    // B entries since alloc_buffers: no allocation
-            motion_capable = true;
-        };
-        auto uninstall = [&] {
-            (void)hipFree(store);       // null: no operation
-            sinks_free(&own, SINK_MOTION);
-            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_MOTION);
-            d_motion = nullptr; h_motion_all = nullptr;
-            motion_capable = false;
-        };
-        if (int rc = enable_feature({"motion prior", motion_bytes(), alloc, install, uninstall})) return rc;
-    } else if (motion_capable) {
-        HIPCHK(hipMemcpy(d_motion_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
-        if (key == "motion_prior" && p.on == 0) {
-            HIPCHK(hipMemset(d_motion_recs(), 0, sizeof(MotionRec) * (size_t)B));
-            memset(h_motion_all, 0, sizeof(MotionRec) * (size_t)B);
-            known_motion.assign((size_t)B, MotionRec{});
-        }
-    }
-    motion_policy = p;
-    return VT_OK;
-}
-
-int Engine::zero_motion(int b) {
-    if (!motion_capable) return VT_OK;
-    HIPCHK(hipMemsetAsync(d_motion_recs() + b, 0, sizeof(MotionRec), stream));
-    h_motion_all[b] = MotionRec{};
-    known_motion[(size_t)b] = MotionRec{};
-    return VT_OK;
-}
-
-void Engine::predicted_box(int s, float* box4, int steps) const {
-    const StreamState& k = known[(size_t)s];
-    memcpy(box4, k.box, 4 * sizeof(float));
-    for (int i = 0; i < steps && motion_capable; ++i) {
-        float from[4];
-        memcpy(from, box4, sizeof(from));
-        if (!motion_predict(motion_policy.on, from, known_motion[(size_t)s].v, k.frame_w, k.frame_h, box4)) break;
-    }
-}
-
-// [8]: the engine flag, vx, vy, live, the shift of the stream's last pass, passes with a shift, failed updates that advanced
-int Engine::motion_stats(int s, float* out8) {
-    if (!motion_capable)
-        return set_err(VT_ERR_INVALID_ARG, "motion prior: not enabled on this engine (vt_group_set_tuning \"motion_prior\")");
-    MotionRec r{};
-    HIPCHK(hipMemcpy(&r, d_motion_recs() + s, sizeof(r), hipMemcpyDeviceToHost));
-    out8[0] = (float)motion_policy.on; out8[1] = r.v[0]; out8[2] = r.v[1]; out8[3] = (float)r.live;
-    out8[4] = r.shift[0]; out8[5] = r.shift[1]; out8[6] = (float)r.n_shift; out8[7] = (float)r.n_coast;
-    return VT_OK;
-}
-
-// ---- appearance check ---------------------------------------------------------------------------------
-
-hipError_t Engine::anchor_from_template(int b, int gen) {
-    if (!appear_capable) return hipSuccess;
-    const bf16_t* rows = tpl_init_rows(b) + (refresh_capable ? (size_t)(gen & 1) * appear_rows() : 0);
-    hipError_t he = hipMemcpyAsync(d_anchor(b), rows, sizeof(bf16_t) * appear_rows(), hipMemcpyDeviceToDevice, stream);
-    if (he == hipSuccess) he = hipMemsetAsync(d_appear_recs() + b, 0, sizeof(AppearRec), stream);
-    h_appear_all[b] = AppearRec{};      // the stream is in no outstanding pass: nothing else writes its entry
-    return he;
-}
-
-// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "appearance" is the enable
-// (enable_feature): the store, the anchors of the streams that are initialised, the pinned mirrors. Every later change is
-// one small copy: the passes read the record. "appearance_anchor" is an action: the anchor of stream `value` (-1: of every
-// initialised stream) becomes the stream's CURRENT template rows.
-int Engine::set_appearance(const std::string& key, int value) {
-    AppearPolicy p = appear_policy;
-    const AppearPolicy def = VT_APPEAR_DEFAULT_POLICY;
-    if (key == "appearance") {
-        p.on = value < 0 ? def.on : value;
-        if (p.on > 1) return set_err(VT_ERR_INVALID_ARG, "appearance: %d (0: off, 1: on)", value);
-    } else if (key == "appearance_period") {
-        p.period = value < 0 ? def.period : value;
-        if (p.period < 1 || p.period > VT_APPEAR_MAX_PERIOD)
-            return set_err(VT_ERR_INVALID_ARG, "appearance_period: %d (1..%d)", value, VT_APPEAR_MAX_PERIOD);
-    } else if (key == "appearance_gate_pm") {
-        p.gate_pm = value < 0 ? def.gate_pm : value;
-        if (p.gate_pm > 1000) return set_err(VT_ERR_INVALID_ARG, "appearance_gate_pm: %d (0..1000)", value);
-        p.tau = (float)p.gate_pm / 1000.0f;
-    } else if (key == "appearance_anchor") {
-        if (!appear_capable)
-            return set_err(VT_ERR_INVALID_ARG, "appearance_anchor: the check is not enabled on this engine (vt_group_set_tuning \"appearance\")");
-        if (value < -1 || value >= B) return set_err(VT_ERR_INVALID_ARG, "appearance_anchor: stream %d (-1: all, else 0..%d)", value, B - 1);
-        if (value >= 0 && !h_initialized[(size_t)value]) return set_err(VT_ERR_NOT_INITIALIZED, "appearance_anchor: stream %d not initialised", value);
-        DEVICE_SCOPE(device);
-        HIPCHK(hipStreamSynchronize(stream));
-        std::vector<StreamState> sts((size_t)B);
-        HIPCHK(hipMemcpy(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost));
-        for (int b = value < 0 ? 0 : value; b < (value < 0 ? B : value + 1); ++b)
-            if (h_initialized[(size_t)b]) HIPCHK(anchor_from_template(b, sts[(size_t)b].tpl_gen));
-        HIPCHK(hipStreamSynchronize(stream));
-        return VT_OK;
-    } else {
-        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
-    }
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    if (!appear_capable && p.on != 0) {
-        uint8_t* store = nullptr;       // all zero but the policy and the anchors of the initialised streams
-        PassOut own{};                  // the engine's own mirror
-        auto alloc = [&] {
-            std::vector<StreamState> sts((size_t)B);     // before the device allocation: may throw
-            hipError_t he = dalloc0(&store, appear_bytes(), stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost, stream);
-            if (he == hipSuccess) he = hipStreamSynchronize(stream);
-            bf16_t* anchors = reinterpret_cast<bf16_t*>(store + appear_off_anchor());
-            for (int b = 0; b < B && he == hipSuccess; ++b)
-                if (h_initialized[(size_t)b])
-                    he = hipMemcpyAsync(anchors + (size_t)b * appear_rows(),
-                                        tpl_init_rows(b) + (refresh_capable ? (size_t)(sts[(size_t)b].tpl_gen & 1) * appear_rows() : 0),
-                                        sizeof(bf16_t) * appear_rows(), hipMemcpyDeviceToDevice, stream);
-            if (he == hipSuccess) he = sinks_alloc(&own, SINK_APPEAR);
-            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
-                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_APPEAR);
-            return he;
-        };
-        auto install = [&] { d_appear = store; h_appear_all = own.host_appearance; appear_capable = true; };
-        auto uninstall = [&] {
-            (void)hipFree(store);       // null: no operation
-            sinks_free(&own, SINK_APPEAR);
-            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_APPEAR);
-            d_appear = nullptr; h_appear_all = nullptr;
-            appear_capable = false;
-        };
-        if (int rc = enable_feature({"appearance check", appear_bytes(), alloc, install, uninstall})) return rc;
-    } else if (appear_capable) {
-        HIPCHK(hipMemcpy(d_appear_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
-    }
-    appear_policy = p;
-    return VT_OK;
-}
-
-// [8]: the engine flag, the stream's record (status, similarity, frames_done), its counters (evaluated, gated), period, gate_pm
-int Engine::appearance_stats(int s, float* out8) {
-    if (!appear_capable)
-        return set_err(VT_ERR_INVALID_ARG, "appearance check: not enabled on this engine (vt_group_set_tuning \"appearance\")");
-    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected (a pipelined pass still
-    // running has written the device record already, and may yet be redone); the counters: the device's
-    const AppearRec r = h_appear_all[s];
-    AppearCount c{};
-    HIPCHK(hipMemcpy(&c, d_appear_counts() + s, sizeof(c), hipMemcpyDeviceToHost));
-    out8[0] = (float)appear_policy.on; out8[1] = (float)r.status; out8[2] = r.similarity; out8[3] = (float)r.frames_done;
-    out8[4] = (float)c.evaluated; out8[5] = (float)c.gated; out8[6] = (float)appear_policy.period; out8[7] = (float)appear_policy.gate_pm;
-    return VT_OK;
-}
-
-// ---- reacquire proposals ------------------------------------------------------------------------------
-
-// One key of vt_group_set_tuning. A bad value changes nothing. The first non-zero "proposals" is the enable
-// (enable_feature): the store and the pinned mirrors, sized by the max_cells of that moment. Every later change is one
-// small copy: the passes read the record.
-int Engine::set_proposals(const std::string& key, int value) {
-    PropPolicy p = prop_policy;
-    const PropPolicy def = VT_PROP_DEFAULT_POLICY;
-    if (key == "proposals") {
-        p.mode = value < 0 ? def.mode : value;
-        if (p.mode > 2) return set_err(VT_ERR_INVALID_ARG, "proposals: %d (0: off, 1: failed updates, 2: every update)", value);
-    } else if (key == "proposals_period") {
-        p.period = value < 0 ? def.period : value;
-        if (p.period < 1 || p.period > VT_PROP_MAX_PERIOD)
-            return set_err(VT_ERR_INVALID_ARG, "proposals_period: %d (1..%d)", value, VT_PROP_MAX_PERIOD);
-    } else if (key == "proposals_max") {
-        p.max_n = value < 0 ? def.max_n : value;
-        if (p.max_n < 1 || p.max_n > VT_PROP_MAX) return set_err(VT_ERR_INVALID_ARG, "proposals_max: %d (1..%d)", value, VT_PROP_MAX);
-    } else if (key == "proposals_min_sim_pm") {
-        p.min_sim_pm = value < 0 ? def.min_sim_pm : value;
-        if (p.min_sim_pm > 1000) return set_err(VT_ERR_INVALID_ARG, "proposals_min_sim_pm: %d (0..1000)", value);
-        p.tau = (float)p.min_sim_pm / 1000.0f;
-    } else if (key == "proposals_max_cells") {
-        if (prop_capable)
-            return set_err(VT_ERR_INVALID_ARG, "proposals_max_cells: fixed by the first enable of \"proposals\" (%d)", prop_policy.max_cells);
-        p.max_cells = value < 0 ? def.max_cells : value;
-        if (p.max_cells < VT_PROP_MIN_CELLS || p.max_cells > VT_PROP_MAX_CELLS)
-            return set_err(VT_ERR_INVALID_ARG, "proposals_max_cells: %d (%d..%d)", value, VT_PROP_MIN_CELLS, VT_PROP_MAX_CELLS);
-    } else {
-        return set_err(VT_ERR_INVALID_ARG, "unknown tuning key '%s'", key.c_str());
-    }
-    DEVICE_SCOPE(device);
-    HIPCHK(hipStreamSynchronize(stream));
-    if (!prop_capable && p.mode != 0) {
-        if (prop_pattern_side(d.T) == 0)
-            return set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", d.T);
-        uint8_t* store = nullptr;       // all zero but the policy; the thumbnails and maps are written before they are read
-        PassOut own{};                  // the engine's own mirror
-        const PropPolicy before = prop_policy;
-        const size_t bytes = prop_bytes_of(p.max_cells);
-        auto alloc = [&] {
-            hipError_t he = hipMalloc((void**)&store, bytes);
-            if (he == hipSuccess) he = hipMemsetAsync(store, 0, prop_off_thumb(), stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(store, &p, sizeof(p), hipMemcpyHostToDevice, stream);
-            if (he == hipSuccess) he = sinks_alloc(&own, SINK_PROP);
-            for (HostSlot& sl : hs)     // pipelined slots that exist already; later ones: host_slot_prepare
-                if (he == hipSuccess && sl.out.host_results) he = sinks_alloc(&sl.out, SINK_PROP);
-            return he;
-        };
-        auto install = [&] { d_prop = store; h_prop_all = own.host_proposals; prop_policy = p; prop_capable = true; };
-        auto uninstall = [&] {
-            (void)hipFree(store);       // null: no operation
-            sinks_free(&own, SINK_PROP);
-            for (HostSlot& sl : hs) sinks_free(&sl.out, SINK_PROP);
-            d_prop = nullptr; h_prop_all = nullptr; prop_policy = before;
-            prop_capable = false;
-        };
-        if (int rc = enable_feature({"reacquire proposals", bytes, alloc, install, uninstall})) return rc;
-    } else if (prop_capable) {
-        HIPCHK(hipMemcpy(d_prop_policy(), &p, sizeof(p), hipMemcpyHostToDevice));
-    }
-    prop_policy = p;
-    return VT_OK;
-}
-
-// [VT_PROP_STATS]: mode, status, frames_done, n, c, Wg, Hg, evaluated, period, max, min_sim_pm, max_cells, then per
-// proposal sim, box[4], position
-int Engine::proposals_stats(int s, float* out) {
-    if (!prop_capable)
-        return set_err(VT_ERR_INVALID_ARG, "reacquire proposals: not enabled on this engine (vt_group_set_tuning \"proposals\")");
-    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counter: the device's
-    const PropRec r = h_prop_all[s];
-    int32_t ev = 0;
-    HIPCHK(hipMemcpy(&ev, d_prop_counts() + s, sizeof(ev), hipMemcpyDeviceToHost));
-    out[0] = (float)prop_policy.mode; out[1] = (float)r.status; out[2] = (float)r.frames_done; out[3] = (float)r.n;
-    out[4] = r.c; out[5] = (float)r.Wg; out[6] = (float)r.Hg; out[7] = (float)ev;
-    out[8] = (float)prop_policy.period; out[9] = (float)prop_policy.max_n; out[10] = (float)prop_policy.min_sim_pm;
-    out[11] = (float)prop_policy.max_cells;
-    for (int k = 0; k < VT_PROP_MAX; ++k) {
-        float* o = out + 12 + 6 * k;
-        o[0] = r.p[k].sim; o[1] = r.p[k].box[0]; o[2] = r.p[k].box[1]; o[3] = r.p[k].box[2]; o[4] = r.p[k].box[3];
-        o[5] = (float)r.p[k].pos;
     }
     return VT_OK;
 }

@@ -2,8 +2,9 @@
 // scope, the Engine (one GPU's batch of tracked streams) and the handles of the C ABI.
 //   vt_engine.hip   the Engine: weight blob, buffers, the per-frame launch plan (run_pass), graphs, the one way a pass is
 //                   submitted (prepare_pass / enqueue; enqueue_candidates for a candidate pass - both put their block
-//                   together in build_block), wait, and the one transaction behind the first enable of every optional
-//                   in-the-pass feature (enable_feature)
+//                   together in build_block), wait
+//   vt_features.hip the optional in-the-pass features: the one transaction behind every first enable (enable_feature), the
+//                   optional sinks, the keyed features' descriptors and their one setter (set_keyed), policies, statistics
 //   vt_abi.hip      the extern "C" boundary of include/vittrack_hip.h (create / init / update, device-frame passes of a
 //                   group, diagnostics, colour converter, overlays, dma-buf and host-mapping ingest)
 //   vt_ingest.hip   host-frame ingest: the staging arena, window planning and packing, the host-frame passes of a group
@@ -14,12 +15,14 @@
 //                   libvittrack_hip_ops.so (tests, tuning tools) only, NOT into the product library
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <atomic>
 #include <new>
@@ -29,6 +32,7 @@
 #include "vt_common.hpp"
 #include "k_cand.hpp"
 #include "k_result_overlay.hpp"
+#include "vt_feature_keys.hpp"
 
 // ---- error plumbing ------------------------------------------------------------------------------
 
@@ -144,6 +148,7 @@ struct StageArena {
     void release();
 };
 
+struct KeyedFeature;
 struct Engine {
     int device = 0, B = 1;
     bool use_graph = true, taps = false;
@@ -178,7 +183,7 @@ struct Engine {
     // slots' segments of d_patches, and the next full pass puts every segment back from here
     bf16_t* d_tpl = nullptr;
     bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
-    // The first enable of an optional in-the-pass feature, for all five below: on the idle stream,
+    // The first enable of an optional in-the-pass feature, for all seven below: on the idle stream,
     // never inside an update - `extra` bytes checked against max_device_mib (beside activation_bytes() and
     // feature_bytes()) and against free memory (VT_ERR_OOM), alloc(), install() (pointers, *_capable = true), every
     // graph dropped and captured again with the feature's launches in it, commit() if there is one. Should alloc() or
@@ -192,6 +197,14 @@ struct Engine {
         std::function<void()> install, uninstall, commit;
     };
     int enable_feature(const Feature& f);
+    // enable_feature for "one store of `bytes` with its first `zeroed` bytes zero-filled, `policy` (or null) uploaded to
+    // its start and fill(store) run on it + the sinks `sink` on the engine's own mirror and on every HostSlot that already
+    // has sinks (later ones: host_slot_prepare)". wire(store) at install, wire(null) at uninstall: the feature's own members.
+    int enable_store(const char* name, size_t bytes, size_t zeroed, const void* policy, size_t policy_bytes, unsigned sink,
+                     hipError_t (*fill)(Engine*, uint8_t* store), const std::function<void(uint8_t*)>& wire);
+    // One key of vt_group_set_tuning that belongs to f. A bad value changes nothing. Before the enable a value is kept in
+    // the host's copy; the first non-zero "on" word is the enable; every later change is one small copy to the record.
+    int set_keyed(const KeyedFeature& f, const std::string& key, int value);
     // template refresh (k_refresh.hip). The first policy that is enabled makes the engine refresh-capable: d_tpl becomes
     // [B][2][nt][kpad] (a stream's rows: buffer tpl_gen & 1 of its state), every pass - full ones too - gathers its
     // template rows from there and runs the refresh launch behind its decode. restore_segments / segments_moved are
@@ -222,11 +235,7 @@ struct Engine {
         return (size_t)B * (chip_bytes_of(size, kind) + sizeof(vt_chip_info) + sizeof(ChipPolicy));
     }
     // HBM of the optional features this engine has enabled, beside activation_bytes() under max_device_mib
-    size_t feature_bytes() const {
-        return (refresh_capable ? refresh_bytes() : 0) + (chip_capable ? chip_store_bytes_of(B, chip_size, chip_kind) : 0) +
-               (peaks_capable ? peaks_bytes() : 0) + (overlay_capable ? overlay_bytes() : 0) +
-               (motion_capable ? motion_bytes() : 0) + (appear_capable ? appear_bytes() : 0) + (prop_capable ? prop_bytes() : 0);
-    }
+    size_t feature_bytes() const;
     int enable_chips(int size, int kind, const float* na, const float* nb);   // enable_feature: the store
     int set_chips(int stream, float factor, int period, int phase);           // stream -1: all
     int read_chips(const int* streams, int n, void* out, size_t out_stride, vt_chip_info* infos);
@@ -244,7 +253,6 @@ struct Engine {
     int last_peaks(vt_peaks* out, int n) const;
     // result overlay (k_result_overlay.hip). ONE policy per engine. The first non-zero flags allocate the policy record +
     // the [B] counters by stream: every pass ends with the overlay launch, behind the refresh, chip and peaks launches.
-    // A style, colour or gate value set before that is kept in overlay_policy and goes up with the enable.
     bool overlay_capable = false;
     OverlayPolicy overlay_policy = VT_OVERLAY_DEFAULT_POLICY;     // the host's copy
     uint8_t* d_overlay = nullptr;                 // ONE allocation: the policy record, then the [B] OverlayStats
@@ -255,13 +263,10 @@ struct Engine {
     // pass's block, where the overlay launch reads it. Host-pointer passes hand the kernels staging or mapped host
     // memory: they never draw.
     int frames_on_device = 0;
-    static bool overlay_key(const std::string& key) { return key.rfind("result_overlay", 0) == 0; }
-    int set_overlay(const std::string& key, int value);     // the keys of vt_group_set_tuning; the first enable is in here
     int overlay_stats(int stream, float* out6);
     // motion prior (k_motion.hip). ONE policy per engine, one record per stream. The first non-zero "motion_prior"
     // allocates the policy record + the [B] records and their pinned mirrors: every pass starts with the place launch and
-    // runs the settle launch directly behind its decode (its commit). A gain, coast or limit set before that is kept in
-    // motion_policy and goes up with the enable.
+    // runs the settle launch directly behind its decode (its commit).
     bool motion_capable = false;
     MotionPolicy motion_policy = VT_MOTION_DEFAULT_POLICY;       // the host's copy
     uint8_t* d_motion = nullptr;                  // ONE allocation: the policy record, then the [B] MotionRec by stream
@@ -270,8 +275,6 @@ struct Engine {
     size_t motion_bytes() const { return sizeof(MotionPolicy) + (size_t)B * sizeof(MotionRec); }
     MotionRec* h_motion_all = nullptr;            // pinned [B] by stream: beside h_states_all, written by the settle launch
     std::vector<MotionRec> known_motion;          // beside `known`: the records after the last pass the HOST has collected
-    static bool motion_key(const std::string& key) { return key.rfind("motion_", 0) == 0; }
-    int set_motion(const std::string& key, int value);      // the keys of vt_group_set_tuning; the first enable is in here
     int motion_stats(int stream, float* out8);
     // stream b's record zeroed on the device (behind the stream's work) and in the host's copies: every call that gives
     // the stream a new state from outside (init, set_state_box, import)
@@ -284,7 +287,7 @@ struct Engine {
     // record and two counters. The first non-zero "appearance" allocates all of it, fills the anchors of the streams that
     // are initialised from their current template rows and makes the engine appearance-capable for good: every pass runs
     // the probe and the score launch behind its decode (its commit, motion_settle), ahead of the refresh launch, whose rule
-    // 8 reads the records. A period or gate set before that is kept in appear_policy and goes up with the enable.
+    // 8 reads the records.
     bool appear_capable = false;
     AppearPolicy appear_policy = VT_APPEAR_DEFAULT_POLICY;      // the host's copy
     // ONE allocation: the policy | [B] counters | [B] records | [B] tickets | [B][chunks][5] partials (binary64) |
@@ -307,8 +310,7 @@ struct Engine {
     // pinned [B] by stream: the records of the last passes the host collected - what "appearance" of vt_group_read_tensor
     // reports (the kernels store to the pass's sink; adopt_slot copies a collected pipelined pass's entries here)
     AppearRec* h_appear_all = nullptr;
-    static bool appearance_key(const std::string& key) { return key.rfind("appearance", 0) == 0; }
-    int set_appearance(const std::string& key, int value);  // the keys of vt_group_set_tuning; the first enable is in here
+    int appearance_anchor(int stream);      // the "appearance_anchor" action: stream's (-1: every initialised stream's) anchor <- its CURRENT template rows
     int appearance_stats(int stream, float* out8);
     // stream b's anchor <- its current template rows (buffer gen & 1 of a refresh-capable engine's store), its record
     // zeroed; behind the stream's work. init, queued init, import, copy, the "appearance_anchor" action
@@ -316,8 +318,7 @@ struct Engine {
     // reacquire proposals (k_proposals.hip). ONE policy per engine; per stream a record and a counter, per slot the working
     // set of the four launches. The first non-zero "proposals" allocates all of it with the max_cells of that moment and
     // makes the engine proposals-capable for good: every pass runs the four launches behind its decode (its commit,
-    // motion_settle, the appearance launches), ahead of the refresh launch. Keys set before that are kept in prop_policy
-    // and go up with the enable.
+    // motion_settle, the appearance launches), ahead of the refresh launch.
     bool prop_capable = false;
     PropPolicy prop_policy = VT_PROP_DEFAULT_POLICY;            // the host's copy
     // ONE allocation: the policy | [B] counters | [B] records | [B] headers | [B] patterns | [B][max_cells] thumbnails
@@ -329,8 +330,7 @@ struct Engine {
     size_t prop_off_pattern() const { return (prop_off_heads() + sizeof(PropHead) * (size_t)B + 63) & ~(size_t)63; }
     size_t prop_off_thumb() const { return prop_off_pattern() + sizeof(int16_t) * VT_PROP_M_MAX * VT_PROP_M_MAX * (size_t)B; }
     size_t prop_off_map(int max_cells) const { return prop_off_thumb() + sizeof(int16_t) * (size_t)max_cells * (size_t)B; }
-    size_t prop_bytes_of(int max_cells) const { return prop_off_map(max_cells) + sizeof(float) * (size_t)max_cells * (size_t)B; }
-    size_t prop_bytes() const { return prop_bytes_of(prop_policy.max_cells); }
+    size_t prop_bytes() const { return prop_off_map(prop_policy.max_cells) + sizeof(float) * (size_t)prop_policy.max_cells * (size_t)B; }
     PropPolicy* d_prop_policy() const { return reinterpret_cast<PropPolicy*>(d_prop); }
     int32_t* d_prop_counts() const { return reinterpret_cast<int32_t*>(d_prop + prop_off_counts()); }
     PropRec* d_prop_recs() const { return reinterpret_cast<PropRec*>(d_prop + prop_off_recs()); }
@@ -341,8 +341,6 @@ struct Engine {
     // pinned [B] by stream: the records of the last passes the host collected - what "proposals" of vt_group_read_tensor
     // reports (the list launch stores to the pass's sink; adopt_slot copies a collected pipelined pass's entries here)
     PropRec* h_prop_all = nullptr;
-    static bool proposals_key(const std::string& key) { return key.rfind("proposals", 0) == 0; }
-    int set_proposals(const std::string& key, int value);   // the keys of vt_group_set_tuning; the first enable is in here
 #define VT_PROP_STATS 60    // floats of "proposals": 12 + VT_PROP_MAX * 6
     int proposals_stats(int stream, float* out60);
     vt_result* d_results = nullptr;
@@ -395,13 +393,13 @@ struct Engine {
     // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
     // slot, states, motion, appearance and proposal records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
     // h_motion_all, h_appear_all and h_prop_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
-    // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them.
+    // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them. The
+    // optional ones are the rows of ONE list (vt_features.hip: kSinks), which everything below walks.
     enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_ALL = 31 };
-    unsigned sink_members() const {
-        return SINK_BASE | (peaks_capable ? SINK_PEAKS : 0u) | (motion_capable ? SINK_MOTION : 0u) | (appear_capable ? SINK_APPEAR : 0u) |
-               (prop_capable ? SINK_PROP : 0u);
-    }
-    PassOut own_sinks() const { return {h_results, h_states_all, h_peaks, h_motion_all, h_appear_all, h_prop_all}; }
+    unsigned sink_members() const;      // SINK_BASE and the sinks of the features the engine is capable of
+    // what a pass's block carries of `to` (null: of the engine's own): host_states only with by_stream_states, an optional member only on a capable engine
+    PassOut pass_sinks(const PassOut* to, bool by_stream_states) const;
+    void adopt_stream_sinks(PassOut from, int stream);      // a collected pass's optional by-stream records of `stream` into the engine's own
     hipError_t sinks_alloc(PassOut* o, unsigned members) const;
     void sinks_free(PassOut* o, unsigned members) const;
     // graph
@@ -527,6 +525,25 @@ struct Engine {
     double flops_encoder() const;
     double flops_head() const;
 };
+
+// A keyed feature: ONE engine-wide policy of int32_t words set through keys of vt_group_set_tuning (vt_feature_keys.hpp),
+// a device store with that policy at its start, at most one by-stream sink, one statistics tensor of vt_group_read_tensor.
+// keyed_features() (vt_features.hip) is the ONE place a new one registers: everything else walks that list.
+struct KeyedFeature {
+    const char *name, *prefix;                  // for the messages; a key is the feature's iff it starts with prefix
+    vtkeys::Apply apply;                        // the key table and its specials
+    int32_t Engine::*policy; int words, on_word;        // the host's copy as words (a new Engine's: the defaults); the first non-zero value of word on_word enables
+    bool Engine::*capable; uint8_t* Engine::*store;
+    size_t (Engine::*store_bytes)() const;      // of an engine with the host's copy as it is
+    size_t (Engine::*zeroed_bytes)() const;     // leading bytes the enable zero-fills; null: all
+    unsigned sink; const char* tensor; int stats_len;   // SINK_* or 0: none; the name of vt_group_read_tensor that answers stats_len floats from stats
+    int (Engine::*stats)(int stream, float* out);       // on an engine that is not capable: the not-enabled error. The rest: null if not needed
+    int (*changed)(Engine*, const char* key, const int32_t* words) = nullptr;   // behind the small policy copy of a capable engine
+    hipError_t (*fill)(Engine*, uint8_t* store) = nullptr;      // more than zeros and the policy in the new store
+    const char* action_key = nullptr; int (Engine::*action)(int value) = nullptr;       // a key that is an action, not a field, and what it does
+    int (*refuse_enable)(Engine*) = nullptr;    // a reason this engine cannot enable at all
+};
+const std::array<KeyedFeature, 4>& keyed_features();
 
 // zero-filled device buffer. The fill is ordered on the ENGINE's stream: that stream is non-blocking, so a
 // hipMemset on the null stream (asynchronous for device memory) is not ordered against the kernels the

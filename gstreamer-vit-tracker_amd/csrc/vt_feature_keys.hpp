@@ -1,0 +1,93 @@
+// vt_feature_keys.hpp — the vt_group_set_tuning keys of the keyed optional features as tables: the word of the policy a key
+// writes, what it accepts, what it says when it refuses. Pure C++17 - no HIP, nothing of vt_engine.hpp - so
+// tests/feature_keys_main.cpp runs all of it on the CPU. vt_features.hip asserts the word indices against the structs.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+namespace vtkeys {
+// a value < 0 stands for the default's word, anything else must lie in lo..hi; refusal: a printf format for the caller's value
+struct Key { const char* key; int word; int32_t lo, hi; const char* refusal; };
+enum Answer { ACCEPTED, REFUSED, UNKNOWN };     // REFUSED: words untouched, text written; UNKNOWN: not a key of the table
+constexpr int kMaxWords = 8;                    // of the longest policy
+template <int N>
+inline Answer apply(const Key (&rows)[N], const char* key, int value, const int32_t* def, int32_t* words, char* text, size_t cap) {
+    for (const Key& k : rows) {
+        if (strcmp(key, k.key) != 0) continue;
+        const int32_t v = value < 0 ? def[k.word] : value;
+        if (v < k.lo || v > k.hi) { snprintf(text, cap, k.refusal, value); return REFUSED; }
+        words[k.word] = v;
+        return ACCEPTED;
+    }
+    return UNKNOWN;
+}
+inline float tau_of(int32_t pm) { return (float)pm / 1000.0f; }
+inline void put_tau(int32_t* word, int32_t pm) { const float tau = tau_of(pm); memcpy(word, &tau, sizeof(tau)); }    // one binary32 divide
+// a feature's keys from outside, table and specials: one (key, value) applied to `words`; capable: the engine has enabled it
+typedef Answer (*Apply)(const char* key, int value, const int32_t* def, int32_t* words, bool capable, char* text, size_t cap);
+
+enum { OV_FLAGS, OV_THICKNESS, OV_SIZE, OV_SCALE, OV_LUMA, OV_RGB, OV_MIN_SCORE_PCT, OV_WORDS = 8 };      // OverlayPolicy
+static constexpr Key kOverlayKeys[] = {
+    {"result_overlay", OV_FLAGS, 0, 7, "result_overlay: flags %d (1 rectangle | 2 crosshair | 4 label, 0: off)"},
+    {"result_overlay_luma", OV_LUMA, 0, 255, "result_overlay_luma: %d (0..255)"},
+    {"result_overlay_rgb", OV_RGB, 0, 0xFFFFFF, "result_overlay_rgb: 0x%x (0..0xFFFFFF)"},
+    {"result_overlay_min_score_pct", OV_MIN_SCORE_PCT, 0, 100, "result_overlay_min_score_pct: %d (0..100)"},
+};
+// "result_overlay_style": thickness | size << 8 | scale << 16; a negative value restores all three
+inline Answer apply_overlay(const char* key, int value, const int32_t* def, int32_t* words, bool, char* text, size_t cap) {
+    if (strcmp(key, "result_overlay_style") != 0) return apply(kOverlayKeys, key, value, def, words, text, cap);
+    const int th = value & 255, size = (value >> 8) & 255, scale = value >> 16;
+    if (value >= 0 && (th < 1 || th > 16 || size < 1 || size > 64 || scale < 1 || scale > 4)) {
+        snprintf(text, cap, "result_overlay_style: thickness %d (1..16), size %d (1..64), scale %d (1..4)", th, size, scale);
+        return REFUSED;
+    }
+    words[OV_THICKNESS] = value < 0 ? def[OV_THICKNESS] : th;
+    words[OV_SIZE] = value < 0 ? def[OV_SIZE] : size;
+    words[OV_SCALE] = value < 0 ? def[OV_SCALE] : scale;
+    return ACCEPTED;
+}
+
+enum { MO_ON, MO_GAIN_PCT, MO_COAST, MO_MAX_PCT, MO_WORDS };      // MotionPolicy
+static constexpr Key kMotionKeys[] = {
+    {"motion_prior", MO_ON, 0, 1, "motion_prior: %d (0: off, 1: on)"},
+    {"motion_gain_pct", MO_GAIN_PCT, 1, 100, "motion_gain_pct: %d (1..100)"},
+    {"motion_coast", MO_COAST, 0, 60, "motion_coast: %d (0..60)"},
+    {"motion_max_pct", MO_MAX_PCT, 0, 200, "motion_max_pct: %d (0..200)"},
+};
+inline Answer apply_motion(const char* key, int value, const int32_t* def, int32_t* words, bool, char* text, size_t cap) {
+    return apply(kMotionKeys, key, value, def, words, text, cap);
+}
+
+enum { AP_ON, AP_PERIOD, AP_GATE_PM, AP_TAU, AP_WORDS };          // AppearPolicy
+static constexpr Key kAppearKeys[] = {
+    {"appearance", AP_ON, 0, 1, "appearance: %d (0: off, 1: on)"},
+    {"appearance_period", AP_PERIOD, 1, 1000000, "appearance_period: %d (1..1000000)"},
+    {"appearance_gate_pm", AP_GATE_PM, 0, 1000, "appearance_gate_pm: %d (0..1000)"},
+};
+inline Answer apply_appearance(const char* key, int value, const int32_t* def, int32_t* words, bool, char* text, size_t cap) {
+    const Answer a = apply(kAppearKeys, key, value, def, words, text, cap);
+    if (a == ACCEPTED && strcmp(key, "appearance_gate_pm") == 0) put_tau(words + AP_TAU, words[AP_GATE_PM]);
+    return a;
+}
+
+enum { PR_MODE, PR_PERIOD, PR_MAX_N, PR_MIN_SIM_PM, PR_TAU, PR_MAX_CELLS, PR_WORDS = 8 };     // PropPolicy
+static constexpr Key kPropKeys[] = {
+    {"proposals", PR_MODE, 0, 2, "proposals: %d (0: off, 1: failed updates, 2: every update)"},
+    {"proposals_period", PR_PERIOD, 1, 1000000, "proposals_period: %d (1..1000000)"},
+    {"proposals_max", PR_MAX_N, 1, 8, "proposals_max: %d (1..8)"},
+    {"proposals_min_sim_pm", PR_MIN_SIM_PM, 0, 1000, "proposals_min_sim_pm: %d (0..1000)"},
+    {"proposals_max_cells", PR_MAX_CELLS, 16384, 4194304, "proposals_max_cells: %d (16384..4194304)"},
+};
+// "proposals_max_cells" sizes the store: frozen once the engine is capable, whatever the value
+inline Answer apply_proposals(const char* key, int value, const int32_t* def, int32_t* words, bool capable, char* text, size_t cap) {
+    if (capable && strcmp(key, "proposals_max_cells") == 0) {
+        snprintf(text, cap, "proposals_max_cells: fixed by the first enable of \"proposals\" (%d)", (int)words[PR_MAX_CELLS]);
+        return REFUSED;
+    }
+    const Answer a = apply(kPropKeys, key, value, def, words, text, cap);
+    if (a == ACCEPTED && strcmp(key, "proposals_min_sim_pm") == 0) put_tau(words + PR_TAU, words[PR_MIN_SIM_PM]);
+    return a;
+}
+}   // namespace vtkeys

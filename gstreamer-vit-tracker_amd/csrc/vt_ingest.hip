@@ -230,8 +230,8 @@ int stage_host_frames(Engine* e, const vt_frame* host, int n, const float (*boxe
 
 static int host_slot_prepare(Engine* e, Engine::HostSlot& sl) {
     DEVICE_SCOPE(e->device);
-    // whatever of the slot's sinks is missing: all of them at its first use, the peak, motion or appearance records at its first use
-    // after that feature's enable (the enable itself covers the slots that exist)
+    // whatever of the slot's sinks is missing: all of them at its first use, an optional feature's records at its first use
+    // after that feature's enable (the enable itself covers the slots that exist, so no pass allocates for them)
     HIPCHK(e->sinks_alloc(&sl.out, e->sink_members()));
     if (sl.done_ev) return VT_OK;
     // HIP multiplexes a process's streams onto a few hardware queues (four by default): with more
@@ -285,9 +285,8 @@ static void adopt_slot(Engine* e, const Engine::HostSlot& sl) {
         const int s = sl.list[i];
         e->known[s] = sl.out.host_states[s];
         e->h_states_all[s] = sl.out.host_states[s];        // the engine's own mirrors follow
-        if (e->motion_capable && sl.out.host_motion) e->known_motion[(size_t)s] = e->h_motion_all[s] = sl.out.host_motion[s];
-        if (e->appear_capable && sl.out.host_appearance) e->h_appear_all[s] = sl.out.host_appearance[s];
-        if (e->prop_capable && sl.out.host_proposals) e->h_prop_all[s] = sl.out.host_proposals[s];
+        e->adopt_stream_sinks(sl.out, s);                  // ... and those of the optional by-stream records
+        if (e->motion_capable && sl.out.host_motion) e->known_motion[(size_t)s] = sl.out.host_motion[s];
         e->h_results[i] = sl.out.host_results[i];
     }
     adopt_peaks(e, sl);                         // the peak records are by slot, like the results

@@ -1,10 +1,11 @@
-"""The first enable of the five optional in-the-pass features - template refresh, target chips, response peaks, result
-overlay, motion prior - as ONE behaviour, on the MI355X.
+"""The first enable of the seven optional in-the-pass features - template refresh, target chips, response peaks, result
+overlay, motion prior, appearance check, reacquire proposals - as ONE behaviour, on the MI355X.
 
 Tiny model, 3 streams on 640 x 480 MovingSquare NV12 clips. Three properties that hold whatever the host code behind the
 enables looks like:
-  * the order of the enables does not matter: two engines that enable the five in opposite orders give the same bits on
+  * the order of the enables does not matter: two engines that enable the seven in opposite orders give the same bits on
     every kind of pass (full, subset, candidate, synchronous host, pipelined host);
+  * nor does it matter whether the pipelined slots owned their sinks before an enable or got them afterwards;
   * a first enable captures every wanted graph set exactly once; a repeated enable, a later key and a pass capture nothing;
   * a call refused for its arguments leaves nothing behind: no capture, the feature still "not enabled", the next pass
     that of an untouched engine."""
@@ -43,12 +44,14 @@ ENABLES = {
     "peaks": lambda g, gpu: g.set_peaks(3),
     "overlay": lambda g, gpu: g.set_tuning("result_overlay", 7),
     "motion": lambda g, gpu: g.set_tuning("motion_prior", 1),
+    "appearance": lambda g, gpu: g.set_tuning("appearance", 1),
+    "proposals": lambda g, gpu: g.set_tuning("proposals", 2),       # mode 2: every update evaluates
 }
-ORDER = ["refresh", "chips", "peaks", "overlay", "motion"]
+ORDER = ["refresh", "chips", "peaks", "overlay", "motion", "appearance", "proposals"]
 
 
 def _observe(g):
-    """everything the five features and the tracker itself let the host see, as exact values"""
+    """everything the seven features and the tracker itself let the host see, as exact values"""
     chips, infos = g.read_chips()
     return dict(
         states=[g.read_tensor("state", s).tobytes() for s in range(B)],
@@ -56,6 +59,8 @@ def _observe(g):
         chips=chips.tobytes(), chip_infos=infos,
         motion=[g.motion(s) for s in range(B)],
         overlay=[g.result_overlay_stats(s) for s in range(B)],
+        appearance=[g.appearance(s) for s in range(B)], anchors=[g.anchor(s).tobytes() for s in range(B)],
+        proposals=[g.proposals(s) for s in range(B)],
         refresh=[g.template_refresh_stats(s) for s in range(B)])
 
 
@@ -68,7 +73,7 @@ def _same(a, b, results, what):
 
 
 def test_enable_order_does_not_matter_bit_for_bit(gpu, weights_tiny, capsys):
-    """engine a enables refresh, chips, peaks, overlay, motion; engine b the same in reverse; then two full device passes, a
+    """engine a enables refresh, chips, peaks, overlay, motion, appearance, proposals; engine b the same in reverse; then two full device passes, a
     subset pass (slot != stream), a candidate pass, a synchronous host pass and two pipelined host passes two deep. Each
     engine has its own copies of the device frames: the overlay draws into them."""
     scs = _scs(gpu)
@@ -116,7 +121,9 @@ def test_enable_order_does_not_matter_bit_for_bit(gpu, weights_tiny, capsys):
     did = dict(refreshes=sum(a.template_refresh_stats(s)["generation"] for s in range(B)),
                shifts=sum(a.motion(s)["n_shift"] for s in range(B)),
                drawn=sum(a.result_overlay_stats(s)["n_drawn"] for s in range(B)),
-               peaks=int(a.last_peaks()["n"].sum()), chips=sum(i["status"] == 1 for i in a.read_chips()[1]))
+               peaks=int(a.last_peaks()["n"].sum()), chips=sum(i["status"] == 1 for i in a.read_chips()[1]),
+               appearance=sum(a.appearance(s)["evaluated"] for s in range(B)),
+               proposals=sum(a.proposals(s)["evaluated"] for s in range(B)))
     with capsys.disabled():
         print(f"\n[enable order] {did}")
     assert min(did.values()) >= 1, f"the run exercises little: a feature did nothing: {did}"
@@ -141,6 +148,10 @@ def test_a_first_enable_captures_once_and_nothing_else_captures(gpu, weights_tin
                     lambda: g.set_tuning("result_overlay", 0), lambda: g.set_tuning("result_overlay", 7)],
         "motion": [lambda: g.set_tuning("motion_gain_pct", 70), lambda: g.set_tuning("motion_coast", 3),
                    lambda: g.set_tuning("motion_prior", 0), lambda: g.set_tuning("motion_prior", 1)],
+        "appearance": [lambda: g.set_tuning("appearance_period", 2), lambda: g.set_tuning("appearance_gate_pm", 900),
+                       lambda: g.set_tuning("appearance_anchor", 1)],
+        "proposals": [lambda: g.set_tuning("proposals_period", 2), lambda: g.set_tuning("proposals_max", 3),
+                      lambda: g.set_tuning("proposals_min_sim_pm", 250)],
     }
     caps = c0
     for name in ORDER:
@@ -172,6 +183,8 @@ REFUSED = {
     "peaks": lambda g, gpu: g.set_peaks(3, 9),
     "overlay": lambda g, gpu: g.set_tuning("result_overlay", 8),
     "motion": lambda g, gpu: g.set_tuning("motion_gain_pct", 0),
+    "appearance": lambda g, gpu: g.set_tuning("appearance_period", 0),
+    "proposals": lambda g, gpu: g.set_tuning("proposals_max", 0),
 }
 
 
@@ -195,7 +208,8 @@ def test_a_refused_enable_leaves_nothing_behind(gpu, weights_tiny, feature):
         REFUSED[feature](g, gpu)
     assert ei.value.code == INVALID
     assert g.graph_captures() == caps
-    for not_enabled in (g.last_peaks, g.read_chips, lambda: g.read_tensor("motion", 0), lambda: g.read_tensor("result_overlay", 0)):
+    for not_enabled in (g.last_peaks, g.read_chips, lambda: g.read_tensor("motion", 0), lambda: g.read_tensor("result_overlay", 0),
+                        lambda: g.read_tensor("appearance", 0), lambda: g.read_tensor("anchor", 0), lambda: g.read_tensor("proposals", 0)):
         with pytest.raises(gpu.VtError) as ei:
             not_enabled()
         assert ei.value.code == INVALID
@@ -204,3 +218,48 @@ def test_a_refused_enable_leaves_nothing_behind(gpu, weights_tiny, feature):
     assert [g.read_tensor("state", s).tobytes() for s in range(B)] == states
     assert g.graph_captures() == caps
     g.close()
+
+
+def test_slots_that_owned_sinks_before_the_enable_get_the_new_ones(gpu, weights_tiny):
+    """engine a enables peaks, motion, appearance and proposals before any pass, so its pipelined slots get all their
+    sinks at their first use. Engine b first runs and collects two pipelined host passes - both slots own their base
+    sinks - and enables afterwards: the enable itself must give those slots the new members. a runs the same two passes
+    before it is compared - capable, but with the three keyed policies switched off for them, or its motion record and
+    its counters would be two passes ahead of b's by design; then two more pipelined passes two deep on both: the same
+    bits everywhere."""
+    a, b = _group(gpu, weights_tiny), _group(gpu, weights_tiny)
+    sinks = ["peaks", "motion", "appearance", "proposals"]
+    for name in sinks:
+        ENABLES[name](a, gpu)
+    for key in ("motion_prior", "appearance", "proposals"):
+        a.set_tuning(key, 0)
+    caps = a.graph_captures()
+    before = []
+    for g in (b, a):
+        g.enqueue_host(_host_frames(gpu, 1))
+        g.enqueue_host(_host_frames(gpu, 2))
+        before.append([[_res(r) for r in g.wait_next()], [_res(r) for r in g.wait_next()]])
+    assert before[0] == before[1], "the features changed the results of the two passes ahead of b's enables"
+    for name in sinks:
+        ENABLES[name](a, gpu)       # a is capable: the policies go on again, nothing is captured
+        ENABLES[name](b, gpu)
+    assert a.graph_captures() == caps
+    for g in (a, b):
+        g.enqueue_host(_host_frames(gpu, 3))
+        g.enqueue_host(_host_frames(gpu, 4))
+
+    def seen(g):
+        return dict(states=[g.read_tensor("state", s).tobytes() for s in range(B)], peaks=g.last_peaks().tobytes(),
+                    motion=[g.motion(s) for s in range(B)], appearance=[g.appearance(s) for s in range(B)],
+                    proposals=[g.proposals(s) for s in range(B)])
+
+    for k in (1, 2):
+        ra, rb = a.wait_next(), b.wait_next()
+        assert [_res(r) for r in ra] == [_res(r) for r in rb], f"pipelined pass {k} after the enables: results differ"
+        assert a.last_peaks().tobytes() == b.last_peaks().tobytes(), f"pipelined pass {k} after the enables: peaks differ"
+    sa, sb = seen(a), seen(b)
+    for key in sa:
+        assert sa[key] == sb[key], f"{key} differs between slots that had sinks before the enable and slots that had none"
+    assert int(a.last_peaks()["n"].sum()) >= 1 and all(sb["appearance"][s]["status"] == 1 for s in range(B))
+    a.close()
+    b.close()
