@@ -90,4 +90,27 @@ inline Answer apply_proposals(const char* key, int value, const int32_t* def, in
     if (a == ACCEPTED && strcmp(key, "proposals_min_sim_pm") == 0) put_tau(words + PR_TAU, words[PR_MIN_SIM_PM]);
     return a;
 }
+
+// camera motion (k_camera_motion.hip): the policy words of vt_op_camera_motion, which validates them with this table; no
+// engine key reaches it yet
+enum { CM_MODE, CM_CELL, CM_RANGE, CM_CONF_PM, CM_MAX_CELLS, CM_WORDS = 8 };      // CamPolicy
+static constexpr Key kCameraKeys[] = {
+    {"camera_motion", CM_MODE, 0, 2, "camera_motion: %d (0: off, 1: measure, 2: measure and move the box)"},
+    {"camera_motion_cell", CM_CELL, 0, 32, "camera_motion_cell: %d (0: automatic, 4, 8, 16 or 32)"},
+    {"camera_motion_range", CM_RANGE, 2, 16, "camera_motion_range: %d (2..16)"},
+    {"camera_motion_conf_pm", CM_CONF_PM, 0, 1000, "camera_motion_conf_pm: %d (0..1000)"},
+    {"camera_motion_max_cells", CM_MAX_CELLS, 4096, 1048576, "camera_motion_max_cells: %d (4096..1048576)"},
+};
+// "camera_motion_cell": 0 or a power of two in 4..32; "camera_motion_max_cells" sizes the store: frozen once the engine is capable
+inline Answer apply_camera_motion(const char* key, int value, const int32_t* def, int32_t* words, bool capable, char* text, size_t cap) {
+    if (capable && strcmp(key, "camera_motion_max_cells") == 0) {
+        snprintf(text, cap, "camera_motion_max_cells: fixed by the first enable of \"camera_motion\" (%d)", (int)words[CM_MAX_CELLS]);
+        return REFUSED;
+    }
+    if (strcmp(key, "camera_motion_cell") == 0 && value > 0 && (value < 4 || (value & (value - 1)) != 0)) {
+        snprintf(text, cap, kCameraKeys[CM_CELL].refusal, value);
+        return REFUSED;
+    }
+    return apply(kCameraKeys, key, value, def, words, text, cap);
+}
 }   // namespace vtkeys

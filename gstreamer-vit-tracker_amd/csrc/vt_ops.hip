@@ -785,6 +785,69 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The four launches of the camera motion on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_camera_prepare, _thumb, _search and _decide, in that order. Thumbnails, records and tables each sit between guard
+// bands; the tables start as 0xff bytes, the thumbnails and records as the caller's.
+int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
+                        const int32_t* policy, int device_frames, uint16_t* thumbs, void* records, int64_t* sad,
+                        void* host_states, void* host_records) try {
+    if (!frames || !states || !policy || !thumbs || !records || !sad || n < 1 || n > VT_MAX_STREAMS || n_streams < 1 ||
+        n_streams > VT_MAX_STREAMS)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "camera_motion: %d streams for %d slots", n_streams, n);
+    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here, in its words
+    static_assert(sizeof(CamPolicy) == 4 * vtkeys::CM_WORDS && vtkeys::kCameraKeys[2].hi == VT_CAM_R_MAX &&
+                  vtkeys::kCameraKeys[4].lo == VT_CAM_MIN_CELLS && vtkeys::kCameraKeys[4].hi == VT_CAM_MAX_CELLS, "CamPolicy");
+    const CamPolicy def = VT_CAM_DEFAULT_POLICY;
+    int32_t words[vtkeys::kMaxWords] = {};
+    for (const vtkeys::Key& k : vtkeys::kCameraKeys) {
+        char text[256];
+        if (policy[k.word] < 0 || vtkeys::apply_camera_motion(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false,
+                                                             text, sizeof(text)) != vtkeys::ACCEPTED)
+            return set_err(VT_ERR_INVALID_ARG, "camera_motion: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
+    }
+    CamPolicy pol;
+    memcpy(&pol, words, sizeof(pol));
+    std::vector<FrameDesc> desc((size_t)n);
+    SlotMaps maps{slot_stream, nullptr, n, n_streams};
+    for (int b = 0; b < n; ++b) {
+        if (int rc = check_frame(frames[b])) return rc;
+        to_desc(frames[b], &desc[(size_t)b]);
+        if (int rc = maps.check("camera_motion", b)) return rc;
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t ns = (size_t)n_streams, sb = ns * sizeof(StreamState), rb = ns * sizeof(CamRec);
+    const size_t tb = ns * 2 * (size_t)pol.max_cells * sizeof(uint16_t), ab = ns * VT_CAM_TABLE * sizeof(long long);
+    const int32_t flag = device_frames != 0;
+    DevArr dfr, dst, dpol, dflag, dhead;
+    GuardedOut gth, grec, gsad;
+    PinnedBuf hst, hrec;
+    HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dst.upload(states, sb));
+    HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4)); HIPCHK(dhead.zeros((size_t)n * sizeof(CamHead)));
+    HIPCHK(gth.alloc(tb)); HIPCHK(grec.alloc(rb)); HIPCHK(gsad.alloc(ab));
+    HIPCHK(hipMemcpy(gth.out(), thumbs, tb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(grec.out(), records, rb, hipMemcpyHostToDevice));
+    if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
+    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    HIPCHK(maps.upload());
+    const CamArgs ca{dfr.as<const FrameDesc>(), dst.as<StreamState>(), maps.dev_slot_stream(), dpol.as<const CamPolicy>(),
+                     dflag.as<const int32_t>(), grec.as<CamRec>(), dhead.as<CamHead>(), gsad.as<unsigned long long>(),
+                     gth.as<uint16_t>(), (StreamState*)hst.p, (CamRec*)hrec.p, pol.max_cells, n};
+    int level = 0;
+    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
+    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(launch_camera_prepare(ca, nullptr));
+    HIPCHK(launch_camera_thumb(ca, level, nullptr));
+    HIPCHK(launch_camera_search(ca, nullptr));
+    HIPCHK(launch_camera_decide(ca, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("camera_motion", {{&gth, "thumbnails"}, {&grec, "records"}, {&gsad, "tables"}})) return rc;
+    HIPCHK(gth.download(thumbs)); HIPCHK(grec.download(records)); HIPCHK(gsad.download(sad)); HIPCHK(dst.download(states));
+    if (host_states) memcpy(host_states, hst.p, sb);
+    if (host_records) memcpy(host_records, hrec.p, rb);
+    return VT_OK;
+} VT_NOTHROW_INT
+
 // The folded LayerNorm as the engine runs it, end to end (see include/vittrack_hip_ops.h): X-epilogue producer -> row
 // terms by one of the three routes of the xgemm lambda (vt_engine.hip) -> launch_fold_layernorm -> the consuming GEMM
 // on the hi half of the pair. Every device output lies between guard bands and starts as 0xff.

@@ -23,7 +23,7 @@ OPS_EXPORTS = [
     "vt_op_attention_bench", "vt_op_layernorm", "vt_op_nv12_to_rgb8_bench", "vt_op_nv12_to_rgb8_batch_bench", "vt_op_conv3x3_relu_bf16", "vt_op_headconv_bf16",
     "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
-    "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_ln_chain_bf16",
+    "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_camera_motion", "vt_op_ln_chain_bf16",
 ]
 
 _ops = None
@@ -65,6 +65,8 @@ def ops_lib():
     L.vt_op_proposals.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, c_void_p, i32p, i32p, c_int,
                                   c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]
+    L.vt_op_camera_motion.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, i32p, i32p, c_int, c_void_p, c_void_p,
                                        c_int, c_int]
     _ops = L
@@ -456,6 +458,43 @@ def op_proposals(frames, states, results, tpl, T, patch, norm, mode=2, period=1,
         device, arr, _vp(st), ns, _vp(res), _opt(smap, _i32), _opt(win, _i32), n, _vp(t), tpl_bufs, T, patch, kpad, _vp(nrm),
         _vp(pol), 1 if device_frames else 0, _vp(pattern), _vp(thumb), _vp(smap_out), _vp(recs), _vp(ev)))
     return dict(pattern=pattern, thumb=thumb, map=smap_out, records=recs, evaluated=ev)
+
+
+# the 104-byte record of the camera motion (csrc/vt_common.hpp: CamRec) and the entries of a stream's SAD table
+CAMERA_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"), ("R", "<i4"),
+                             ("dx", "<i4"), ("dy", "<i4"), ("shift", "<f4", 2), ("applied", "<i4"), ("n", "<i4"), ("S_best", "<i8"),
+                             ("S0", "<i8"), ("S2", "<i8"), ("evaluated", "<i4"), ("moved", "<i4"), ("has_prev", "<i4"), ("cur", "<i4"),
+                             ("pW", "<i4"), ("pH", "<i4"), ("pc", "<i4"), ("reserved", "<i4")])
+CAMERA_TABLE = 33 * 33
+
+
+def op_camera_motion(frames, states, mode=2, cell=0, rng=8, conf_pm=800, max_cells=65536, slot_stream=None, thumbs=None, records=None,
+                     device_frames=True, host_states=None, host_records=None, device=0):
+    """vt_op_camera_motion: the four launches of k_camera_motion.hip on given operands, nothing else. frames: CFrame per slot
+    with DEVICE planes; states: snapshot.STATE records by stream; slot_stream [n]: slot -> stream (None: the identity);
+    thumbs [n_streams, 2, max_cells] uint16 and records [n_streams] CAMERA_REC_DTYPE to start from (None: zeros - no
+    previous thumbnail); host_states / host_records: what the pinned mirrors hold before (None: that mirror is null).
+    -> dict(states, thumbs, records, sad [n_streams, 1089] int64 - what no launch stored is 0xff bytes -, host_states,
+    host_records) as they came back; feed thumbs and records to the next call to go on"""
+    n = len(frames)
+    arr = (CFrame * n)(*frames)
+    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    ns = len(st)
+    smap = _arr(slot_stream, np.int32)
+    assert smap is None or smap.shape == (n,)
+    th = np.zeros((ns, 2, max_cells), np.uint16) if thumbs is None else np.ascontiguousarray(thumbs, np.uint16).copy()
+    assert th.shape == (ns, 2, max_cells)
+    rec = np.zeros(ns, CAMERA_REC_DTYPE) if records is None else np.ascontiguousarray(records, CAMERA_REC_DTYPE).reshape(-1).copy()
+    assert len(rec) == ns and CAMERA_REC_DTYPE.itemsize == 104
+    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
+    hrec = None if host_records is None else np.ascontiguousarray(host_records, CAMERA_REC_DTYPE).reshape(-1).copy()
+    assert (hst is None or len(hst) == ns) and (hrec is None or len(hrec) == ns)
+    pol = np.array([mode, cell, rng, conf_pm, max_cells, 0, 0, 0], np.int32)
+    sad = np.empty((ns, CAMERA_TABLE), np.int64)
+    _check_op(ops_lib().vt_op_camera_motion(
+        device, arr, _vp(st), ns, _opt(smap, _i32), n, _i32(pol), 1 if device_frames else 0, _vp(th), _vp(rec), _vp(sad),
+        _opt(hst, _vp), _opt(hrec, _vp)))
+    return dict(states=st, thumbs=th, records=rec, sad=sad, host_states=hst, host_records=hrec)
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)

@@ -155,6 +155,56 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
                     const int32_t* slot_stream, const int32_t* winner, int n, const uint16_t* tpl, int tpl_bufs, int T, int patch,
                     int kpad, const float* norm, const int32_t* policy, int device_frames, int16_t* pattern, int16_t* thumb,
                     float* map, void* records, int32_t* evaluated);
+/* The four launches of the camera motion (csrc/k_camera_motion.hip; DESIGN.md section 3 "Camera motion") on caller-supplied
+ * operands, and nothing else: per stream the translation of the whole picture since the stream's last call, measured from
+ * two uint16 thumbnails by an exact integer SAD search, and with mode 2 the stream's box moved by it. No engine pass
+ * carries the launches yet: this hook is their only caller. THE RULE, to the bit:
+ *   POLICY: 8 int32 = mode (0 off, 1 measure and report, 2 measure, report and move the box), cell (0 = automatic, or 4, 8,
+ * 16, 32: cell side in source pixels), range (R = 2..16 cells searched each way), conf_pm (0..1000 per mille), max_cells
+ * (4,096..1,048,576 thumbnail cells per stream), 0, 0, 0 - the bounds of the table kCameraKeys of csrc/vt_feature_keys.hpp,
+ * which names the words "camera_motion", "camera_motion_cell", "camera_motion_range", "camera_motion_conf_pm" and
+ * "camera_motion_max_cells" (defaults 0, 0, 8, 800, 65,536).
+ *   DUE: slot i with stream s is due iff (a) the mode is not 0; (b) it is the first slot naming s; (c) s is initialised;
+ * (d) device_frames != 0; (e) the planes hold the whole frame (windowed != 1). Not due by (a) or (c): status 0. Failing (d)
+ * or (e): status 4. A listed stream that is not evaluated (status 0, 2 or 4) loses its previous thumbnail (has_prev = 0).
+ *   GEOMETRY: W, H the frame's size; c the key's cell, or with 0 the smallest of 4, 8, 16, 32, 64 with (W / c) * (H / c) <=
+ * max_cells (integer divisions). Wg = W / c, Hg = H / c: whole cells only, a partial column or row at the right or bottom
+ * edge is not used. Status 2, nothing evaluated: no such c, Wg * Hg > max_cells, Wg - 2R < 8 or Hg - 2R < 8.
+ *   THUMBNAIL cell (i, j): sixteen taps (u, v), u, v in 0..3, at px = i * c + u * (c / 4) + c / 8 and py likewise (integer
+ * expressions; every tap lies inside the frame). A tap is one pixel as the crop reads it - any vt_pixfmt / vt_pixfmt2,
+ * integers R, G, B in 0..255 -, its value Y = (77 * R + 150 * G + 29 * B + 128) >> 8; the cell is the sum of the sixteen
+ * (0..4080), a uint16.
+ *   PREVIOUS: if the stream has no previous thumbnail, or one of another W, H or c: status 5, shift 0, the current thumbnail
+ * is kept as the previous one of the next pass.
+ *   SEARCH: for dx, dy in -R..R: S(dx, dy) = sum over j in [R, Hg - R), i in [R, Wg - R) of |cur(i, j) - prev(i - dx, j - dy)|,
+ * exact in int64; every displacement sums the same n = (Wg - 2R) * (Hg - 2R) cells. Content that moved by +d cells gives
+ * S(d) = 0. No floating-point operation, no floating-point atomic: the sums do not depend on the order of additions.
+ *   DECISION: the best (dx, dy) is the least (S, dx * dx + dy * dy, (dy + R) * (2R + 1) + (dx + R)) in lexicographic order:
+ * ties prefer the smaller displacement, a still picture gives (0, 0). S0 = S(0, 0); S2 = the least S among displacements at
+ * Chebyshev distance > 1 from the best. Status, in this order of tests: 3 (flat) S2 == 0; 6 (at the border: the motion may
+ * exceed the range) |dx| == R or |dy| == R; 7 (ambiguous) S_best * 1000 > conf_pm * S2 (int64); else 1 (good). The shift is
+ * 0 for every status other than 1.
+ *   SUB-CELL SHIFT (status 1), per axis with the two neighbours Sm, Sp of the best along that axis: den = Sm - 2 * S_best + Sp
+ * (int64); off = (den > 0 && S_best > 0) ? (0.5f * (float)(Sm - Sp)) / (float)den : 0.0f - an exact match (S_best == 0) is a
+ * whole-cell shift, whatever its neighbours are -; shift = ((float)d + off) * (float)c. Binary32, one IEEE operation per
+ * source operation; the int64 -> binary32 conversions round to nearest even.
+ *   APPLY (mode 2, status 1, shift != (0, 0)): px = x + shift_x, py = y + shift_y; if the moved centre (px + 0.5f * w, py +
+ * 0.5f * h) satisfies 0 <= cx < (float)frame_w and 0 <= cy < (float)frame_h (the place rule of the motion prior) the state
+ * box becomes (px, py, w, h) and applied = 1, else the box stays and applied = 0. The box moves whether or not the update
+ * then succeeds: a lost target's last position stays fixed in the scene, not in the picture.
+ *   RECORD, per stream: status, frames_done, c, Wg, Hg, R, dx, dy, shift[2], applied, n, S_best, S0, S2 (int64) and the
+ * counters evaluated (status 1, 3, 6, 7) and moved (applied); behind them the thumbnails' bookkeeping: has_prev, cur (the
+ * buffer of the last thumbnail), pW, pH, pc (the geometry it was taken with).
+ *   OPERANDS: frames: [n] by slot with DEVICE planes (read only); states: [n_streams] raw 88-byte stream states, in and out
+ * (box[0], box[1] move in mode 2; frame_w, frame_h, initialized, frames_done are read); slot_stream: [n] slot -> stream or
+ * null (the identity). In and out: thumbs [n_streams][2][max_cells] uint16 (Hg x Wg at the front of each buffer) and
+ * records [n_streams] of 104 bytes. Out: sad [n_streams][1089] int64, (2R + 1)^2 sums at the front of a stream's table,
+ * row dy + R, column dx + R; every byte of it no launch stored is 0xff. host_states / host_records (nullable, in and out):
+ * [n_streams] pinned mirrors the decide launch stores the moved x, y and the record to. The three device buffers sit
+ * between guard bands; a changed guard byte is VT_ERR_HIP. A policy or map out of range, n > 1024: VT_ERR_INVALID_ARG. */
+int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
+                        const int32_t* policy, int device_frames, uint16_t* thumbs, void* records, int64_t* sad,
+                        void* host_states, void* host_records);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
