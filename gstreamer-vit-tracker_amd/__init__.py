@@ -808,6 +808,16 @@ class VitTrack:
     def proposals(self) -> dict:
         return self.as_group().proposals(0)
 
+    def set_conflicts(self, on: bool = True, iou: float | None = None, gate: bool | None = None) -> None:
+        """the stream conflicts of this tracker's engine: see Group.set_conflicts (a group of one has nobody to compare with)"""
+        self.as_group().set_conflicts(on, iou, gate)
+
+    def set_scene(self, scene: int) -> None:
+        self.as_group().set_scene(0, scene)
+
+    def conflicts(self) -> dict:
+        return self.as_group().conflicts(0)
+
     def export_state(self) -> bytes:
         """vt_export_state: this tracker's stream as a snapshot (state, refresh policy, current template rows) - what a
         later VitTrack of the same input geometry, in any process and on any checkpoint, resumes from with import_state"""
@@ -1422,6 +1432,39 @@ class Group:
         v = self.read_tensor("proposals_map", stream)
         m = self.proposals_pattern(stream).shape[0]
         return v.reshape(hg - m + 1, wg - m + 1)
+
+    def set_conflicts(self, on: bool = True, iou: float | None = None, gate: bool | None = None) -> None:
+        """the "conflicts*" keys of vt_group_set_tuning: behind the decode of every pass the engine records, per stream, which
+        other streams of the same pass and the same scene (set_scene) overlap its new box - IoU at or over `iou` (0.001..1,
+        stored per mille) - and lists the up to four largest. gate True: a stream with such a partner does not refresh its
+        template in that pass (refresh rule 9). None keeps a value. The first enable makes the engine conflicts-capable
+        (graphs recaptured, one more launch per pass from then on). Refused while a pipelined pass is outstanding."""
+        if iou is not None:
+            if not 0.001 <= float(iou) <= 1.0:
+                raise ValueError(f"conflicts iou: {iou}")
+            self.set_tuning("conflicts_iou_pm", int(round(float(iou) * 1000.0)))
+        if gate is not None:
+            self.set_tuning("conflicts_gate", 1 if gate else 0)
+        self.set_tuning("conflicts", 1 if on else 0)
+
+    def set_scene(self, stream: int | None, scene: int) -> None:
+        """the "conflicts_scene" action: `stream` (None: every stream) shows picture `scene` (0..32767; 0, the default:
+        compared with nobody). The records of the streams it names are zeroed. Needs a conflicts-capable engine."""
+        st = 0xFFFF if stream is None else int(stream)
+        if not (0 <= st <= 0xFFFF and 0 <= int(scene) <= 0x7FFF):
+            raise ValueError(f"set_scene: stream {stream}, scene {scene}")
+        self.set_tuning("conflicts_scene", st | int(scene) << 16)
+
+    def conflicts(self, stream: int = 0) -> dict:
+        """vt_group_read_tensor "conflicts": the engine flag, the stream's record of its last collected pass - status (0 no
+        pass wrote it, 1 evaluated and alone, 2 evaluated with partners over the threshold, 3 not eligible), frames_done,
+        n_over and the listed partners, largest IoU first: (stream, iou) -, its counters (evaluated, conflicting; gated:
+        refreshes rule 9 refused) and its scene"""
+        v = self.read_tensor("conflicts", stream)
+        partners = [(int(v[4 + k]), float(v[8 + k])) for k in range(4) if int(v[4 + k]) >= 0]
+        return dict(on=int(v[0]), status=int(v[1]), frames_done=int(v[2]), n_over=int(v[3]), partners=partners,
+                    partner=[int(x) for x in v[4:8]], iou=np.asarray(v[8:12], np.float32).copy(), evaluated=int(v[12]),
+                    conflicting=int(v[13]), gated=int(v[14]), scene=int(v[15]))
 
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats

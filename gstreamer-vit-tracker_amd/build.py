@@ -30,7 +30,7 @@ LIB_OPS = os.path.join(PKG, "libvittrack_hip_ops.so")
 LIB_HOST = os.path.join(HOST, "libvittrack_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_proposals.hip", "k_camera_motion.hip", "k_overlay.hip", "k_result_overlay.hip",
+HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_overlay.hip", "k_result_overlay.hip",
                "k_snapshot.hip", "vt_engine.hip", "vt_features.hip", "vt_abi.hip", "vt_ingest.hip", "vt_snapshot.hip", "vt_rccl.hip"]
 OPS_SOURCES = ["vt_ops.hip"]          # libvittrack_hip_ops.so only
 HEADER = os.path.join(PKG, "..", "include", "vittrack_hip.h")
@@ -50,7 +50,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
              "-Wno-unused-function"]
 # fused multiply-add allowed where no bit-exact float spec applies (MFMA kernels' epilogues and
 # softmax); the pixel stage and the box decode keep one IEEE operation per source operation
-FAST_CONTRACT = {"k_gemm.hip", "k_gemm256.hip", "k_attn.hip"}     # not k_head.hip, k_peaks.hip, k_result_overlay.hip, k_motion.hip, k_appearance.hip, k_proposals.hip, k_camera_motion.hip: the decode, the motion rule, the appearance crop and sums, the proposals' thumbnail and the camera shift keep one IEEE operation per source operation
+FAST_CONTRACT = {"k_gemm.hip", "k_gemm256.hip", "k_attn.hip"}     # not k_head.hip, k_peaks.hip, k_result_overlay.hip, k_motion.hip, k_appearance.hip, k_proposals.hip, k_camera_motion.hip, k_conflicts.hip: the decode, the motion rule, the appearance crop and sums, the proposals' thumbnail, the camera shift and the conflicts' IoU keep one IEEE operation per source operation
 # k_gemm256.hip: hipcc's SLP vectoriser packs the last FMA of the GELU epilogue into v_pk_fma_f32,
 # which has no |x| modifier, so it also emits one v_or per element to build -|x| (and a packed f32
 # op issues at the rate of two scalar ones on CDNA4): 8 % more epilogue VALU for nothing

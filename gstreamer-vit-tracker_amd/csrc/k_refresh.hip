@@ -21,16 +21,18 @@
 
 // What the kernels take of RefreshArgs: the members every engine sets, in their order, and - LAST in the argument block, so
 // that the kernels of engines without the appearance check read the arguments they always read where they always lay -
-// rule 8's three pointers, or nothing.
+// rule 8's three pointers, rule 8's and rule 9's (a null rule-8 policy: an engine without the appearance check), or nothing.
 struct RefreshCore {
     const FrameDesc* frames; StreamState* states; const vt_result* results; const int32_t* slot_stream; const int32_t* winner;
     RefreshPolicy* policy; unsigned* tickets; bf16_t* tpl; const PassOut* out; StreamState* host_states; int n;
 };
 template <int GATE> struct RefreshGate {};
 template <> struct RefreshGate<1> { const AppearPolicy* policy; AppearCount* counts; const AppearRec* recs; };
+template <> struct RefreshGate<2> : RefreshGate<1> { const ConflictPolicy* cf_policy; ConflictCount* cf_counts; const ConflictRec* cf_recs; };
 
-// MODE: which crop body (k_refresh_dev.hpp, VT_TEMPLATE_CROP_LAUNCH). GATE: 1 on appearance-capable engines - rule 8 -,
-// 0 everywhere else: the kernels without the rule
+// MODE: which crop body (k_refresh_dev.hpp, VT_TEMPLATE_CROP_LAUNCH). GATE: 2 on conflicts-capable engines - rule 9, and
+// rule 8 where the engine is appearance-capable too -, 1 on engines that are appearance-capable only - rule 8 -, 0 everywhere
+// else: the kernels without the rules
 template <int MODE, int ANY, int GATE>
 __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshCore a, int size, int ssize, int patch, int kpad,
                                                                int tpl_elems, float na0, float na1, float na2, float nb0,
@@ -48,6 +50,18 @@ __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshCore a, in
     StreamState st = a.states[stream];                              // a copy: the crop below never sees the bump
     if (!refresh_rule4(pol, st)) return;
     if (st.window_miss == st.frames_done) return;                   // this pass's search crop missed its window: the redo refreshes
+    // ---- rule 9: no other stream of the stream's scene sits on the same pixels (k_conflicts.hip) ----
+    // ahead of the geometry: a gated refresh counts no geometry skip and sets no window-miss mark
+    if constexpr (GATE == 2) {
+        const ConflictPolicy cp = *gate.cf_policy;
+        if (cp.on != 0 && cp.gate != 0) {                             // "conflicts" 0 switches the gate off with the check
+            const ConflictRec rec = gate.cf_recs[stream];
+            if (rec.status == 2 && rec.frames_done == st.frames_done) {     // this pass's record
+                if (blockIdx.x == 0 && threadIdx.x == 0) gate.cf_counts[stream].gated += 1;
+                return;
+            }
+        }
+    }
     // ---- rules 6 and 7: the geometry (k_refresh_dev.hpp) ----
     {
         const int rule = template_taps_rule(st, a.frames[slot], size, ssize);
@@ -63,7 +77,7 @@ __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshCore a, in
     }
     // ---- rule 8: what the box holds still looks like what the stream was started from (k_appearance.hip) ----
     if constexpr (GATE != 0) {
-        const AppearPolicy ap = *gate.policy;
+        const AppearPolicy ap = GATE == 1 || gate.policy ? *gate.policy : AppearPolicy{0, 1, 0, 0.0f};    // GATE 2 without the check: off
         const float tau = ap.tau;
         if (ap.on != 0 && tau > 0.0f) {                               // "appearance" 0 switches the gate off with the check
             const AppearRec rec = gate.recs[stream];
@@ -96,7 +110,8 @@ static void launch_refresh_t(const RefreshArgs& ra, const ModelDims& d, int tier
     const RefreshCore a{ra.frames, ra.states, ra.results, ra.slot_stream, ra.winner, ra.policy, ra.tickets, ra.tpl, ra.out,
                         ra.host_states, ra.n};
     RefreshGate<GATE> gate;
-    if constexpr (GATE != 0) gate = RefreshGate<1>{ra.ap_policy, ra.ap_counts, ra.ap_recs};
+    if constexpr (GATE != 0) { gate.policy = ra.ap_policy; gate.counts = ra.ap_counts; gate.recs = ra.ap_recs; }
+    if constexpr (GATE == 2) { gate.cf_policy = ra.cf_policy; gate.cf_counts = ra.cf_counts; gate.cf_recs = ra.cf_recs; }
 #define RF_KERNEL(MODE) template_refresh_kernel<MODE, ANY, GATE>
     VT_TEMPLATE_CROP_LAUNCH(RF_KERNEL, d, tier, a.n, st, a, size, d.S, d.patch, d.kpad, tpl_elems, d.norm_a[0], d.norm_a[1],
                             d.norm_a[2], d.norm_b[0], d.norm_b[1], d.norm_b[2], gate);
@@ -115,7 +130,9 @@ hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int
         return hipErrorInvalidValue;
     const bool gate = a.ap_policy != nullptr;
     if (gate && (!a.ap_counts || !a.ap_recs)) return hipErrorInvalidValue;
-    if (gate) launch_refresh_g<1>(a, d, tier, any_layout, st);
+    if (a.cf_policy && (!a.cf_counts || !a.cf_recs)) return hipErrorInvalidValue;
+    if (a.cf_policy) launch_refresh_g<2>(a, d, tier, any_layout, st);
+    else if (gate) launch_refresh_g<1>(a, d, tier, any_layout, st);
     else launch_refresh_g<0>(a, d, tier, any_layout, st);
     return hipGetLastError();
 }

@@ -398,6 +398,7 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4) try {
     memcpy(e->h_states_all[stream].box, box4, 4 * sizeof(float));
     memcpy(e->known[stream].box, box4, 4 * sizeof(float));
     if (int rc = e->zero_motion(stream)) return rc;     // the caller placed the box: the jump is no motion
+    if (int rc = e->zero_conflicts(stream)) return rc;  // nor does the last pass's record speak of the new box
     HIPCHK(hipStreamSynchronize(e->stream));
     return VT_OK;
 } VT_NOTHROW_INT

@@ -349,6 +349,7 @@ hipError_t launch_overlay_rgb(uint8_t* rgb, int width, int height, int stride, c
 struct MotionRec;
 struct AppearRec;
 struct PropRec;
+struct ConflictRec;
 struct PassOut {
     vt_result* host_results;    // [slots of the pass] or null
     StreamState* host_states;   // [B] (by stream) or null
@@ -356,6 +357,7 @@ struct PassOut {
     MotionRec* host_motion;      // [B] (by stream) or null: the motion records as the settle launch left them (k_motion.hip)
     AppearRec* host_appearance;  // [B] (by stream) or null: the appearance records of the pass's streams (k_appearance.hip)
     PropRec* host_proposals;     // [B] (by stream) or null: the proposal records of the pass's streams (k_proposals.hip)
+    ConflictRec* host_conflicts; // [B] (by stream) or null: the conflict records of the pass's streams (k_conflicts.hip)
 };
 
 struct DecodeArgs {
@@ -386,6 +388,8 @@ struct RefreshPolicy {
 #define VT_REFRESH_MAX_PERIOD 1000000
 struct AppearPolicy;
 struct AppearCount;
+struct ConflictPolicy;
+struct ConflictCount;
 struct RefreshArgs {
     const FrameDesc* frames;    // [n] by slot: the frames of this pass
     StreamState* states;        // [B] by stream, as decode / cand_commit left them
@@ -404,6 +408,12 @@ struct RefreshArgs {
     const AppearPolicy* ap_policy;
     AppearCount* ap_counts;     // [B] by stream
     const AppearRec* ap_recs;   // [B] by stream
+    // rule 9 (conflicts-capable engines; all three null elsewhere). With the policy's flag and gate on, a stream whose record
+    // of THIS pass (the conflicts launch runs ahead of this one) has status 2 is not refreshed and counts[stream].gated += 1;
+    // checked behind rules 1-5 and ahead of rules 6-8: no geometry skip is counted and no window-miss mark is set
+    const ConflictPolicy* cf_policy;
+    ConflictCount* cf_counts;   // [B] by stream
+    const ConflictRec* cf_recs; // [B] by stream
 };
 // behind the decode (candidate pass: behind the commit): per slot the gate of DESIGN.md section 3 and, where it fires, the
 // template crop of this pass's frame at the committed box into the stream's other buffer + the state's two words
@@ -723,6 +733,54 @@ hipError_t launch_camera_prepare(const CamArgs& a, hipStream_t st);
 hipError_t launch_camera_thumb(const CamArgs& a, int any_layout, hipStream_t st);
 hipError_t launch_camera_search(const CamArgs& a, hipStream_t st);
 hipError_t launch_camera_decide(const CamArgs& a, hipStream_t st);
+
+// ---- stream conflicts (k_conflicts.hip) ---------------------------------------------------------------------------------
+// DESIGN.md section 3 "Stream conflicts": per stream of a pass, which other streams of the same pass and the same scene
+// overlap its new box, and by how much (IoU). Per stream, device memory, mirrored to pinned host memory beside the states;
+// every pass writes the records of its streams whole (a redone pass writes them again); no part of StreamState or of a
+// snapshot.
+#define VT_CONFLICT_MAX 4       // partners a record lists
+struct ConflictRec {
+    int32_t status;             // 0: no pass wrote it; 1: evaluated, nobody over tau; 2: evaluated, n_over > 0; 3: not eligible
+    int32_t frames_done;        // the stream's frames_done in the pass that wrote the record
+    int32_t n_over;             // partners with iou >= tau (may exceed VT_CONFLICT_MAX)
+    int32_t reserved;
+    int32_t partner[VT_CONFLICT_MAX];   // the over-tau partners' stream indices by (iou descending, stream ascending); unused: -1
+    float iou[VT_CONFLICT_MAX];         // theirs; unused: 0
+};
+static_assert(sizeof(ConflictRec) == 48, "ConflictRec layout");
+// ONE record per engine, device memory, written by the host only (vt_group_set_tuning "conflicts*")
+struct ConflictPolicy {
+    int32_t on;                 // "conflicts": 0 / 1
+    int32_t iou_pm;             // 1..1000 per mille
+    int32_t gate;               // "conflicts_gate": 0 / 1 - refresh rule 9
+    float tau;                  // (float)iou_pm / 1000.0f, one binary32 divide (the host's)
+    int32_t reserved[4];
+};
+#define VT_CONFLICT_DEFAULT_POLICY ConflictPolicy{0, 300, 0, 0.3f, {0, 0, 0, 0}}
+#define VT_CONFLICT_MAX_SCENE 65535
+// per stream, beside the policy: diagnostics, never rewound - a redone pass may count twice (like skipped_geometry)
+struct ConflictCount {
+    int32_t evaluated;          // records written with status 1 or 2
+    int32_t conflicting;        // of which status 2
+    int32_t gated;              // refreshes that rules 1-5 allowed and rule 9 refused
+    int32_t reserved;
+};
+struct ConflictArgs {
+    const StreamState* states;  // [B] by stream, as decode / cand_commit / motion_settle left them
+    const vt_result* results;   // [n] by slot
+    const int32_t* slot_stream; // [n] slot -> stream, null: the identity
+    const int32_t* winner;      // candidate pass: [n] the winning slot of slot i's stream (only winners work); else null
+    const ConflictPolicy* policy;   // the engine's record
+    const int32_t* scenes;      // [B] by stream; 0: compared with nobody
+    ConflictRec* recs;          // [B] by stream
+    ConflictCount* counts;      // [B] by stream
+    const PassOut* out;         // device copy of the pass's PassOut: host_conflicts; may be null
+    int n;
+};
+// behind the decode (candidate pass: the commit) and motion_settle, ahead of the appearance, proposals, refresh, chip, peaks
+// and overlay launches: one workgroup, one lane per slot (n <= VT_MAX_STREAMS), the records and counters of the pass's streams
+hipError_t launch_conflicts_check(const ConflictArgs& a, hipStream_t st);
 
 // The head's convolutions on the band kernel of k_head.hip: out[B*grid*grid][N] bf16 = relu(conv(in) + bias).
 // conv3x3: in [B*grid*grid][C] (ldin >= C), W [N][9*C] with column (ky*3+kx)*C + c, zero padding (zeros: >= 256 B

@@ -586,6 +586,12 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     if (motion_capable)     // ahead of everything that reads the new box: the velocity, the coast or the restore
         L("motion_settle", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + 3.0 * sizeof(MotionRec)),
           [&] { return launch_motion_settle(ma, stream); });
+    if (conflict_capable) { // directly behind the final boxes, ahead of the refresh launch, whose rule 9 reads the records: k_conflicts.hip
+        const ConflictArgs ca{d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_conflict_policy(),
+                              d_conflict_scenes(), d_conflict_recs(), d_conflict_counts(), (const PassOut*)(d_frames + B), n};
+        L("conflicts_check", 10.0 * n * n, (double)n * (sizeof(StreamState) + sizeof(vt_result) + 2.0 * sizeof(ConflictRec)),
+          [&] { return launch_conflicts_check(ca, stream); });
+    }
     if (appear_capable) {   // ahead of everything that cuts or draws: the probe at the new box and its similarity to the anchor
         const AppearArgs aa{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_appear_policy(),
                             d_appear_counts(), d_appear_recs(), refresh_capable ? d_policy : nullptr, d_appear_tickets(),
@@ -611,6 +617,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         RefreshArgs ra{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_policy,
                        d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
         if (appear_capable) { ra.ap_policy = d_appear_policy(); ra.ap_counts = d_appear_counts(); ra.ap_recs = d_appear_recs(); }
+        if (conflict_capable) { ra.cf_policy = d_conflict_policy(); ra.cf_counts = d_conflict_counts(); ra.cf_recs = d_conflict_recs(); }
         L("refresh_template", 0, 2.0 * n * (sizeof(StreamState) + sizeof(vt_result)),
           [&] { return launch_template_refresh(ra, d, ps.tier, ps.any_layout, stream); });
     }
@@ -790,6 +797,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     h_st->initialized = 1;
     HIPCHK(hipMemcpyAsync(d_states + b, h_st, sizeof(StreamState), hipMemcpyHostToDevice, stream));
     if (int rc = zero_motion(b)) return rc;
+    if (int rc = zero_conflicts(b)) return rc;
     to_desc(*f, h_desc);
     // entry b of the per-pass block: every pass uploads its own block ahead of its kernels, in stream order
     HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));

@@ -183,7 +183,7 @@ struct Engine {
     // slots' segments of d_patches, and the next full pass puts every segment back from here
     bf16_t* d_tpl = nullptr;
     bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
-    // The first enable of an optional in-the-pass feature, for all seven below: on the idle stream,
+    // The first enable of an optional in-the-pass feature, for all eight below: on the idle stream,
     // never inside an update - `extra` bytes checked against max_device_mib (beside activation_bytes() and
     // feature_bytes()) and against free memory (VT_ERR_OOM), alloc(), install() (pointers, *_capable = true), every
     // graph dropped and captured again with the feature's launches in it, commit() if there is one. Should alloc() or
@@ -343,6 +343,31 @@ struct Engine {
     PropRec* h_prop_all = nullptr;
 #define VT_PROP_STATS 60    // floats of "proposals": 12 + VT_PROP_MAX * 6
     int proposals_stats(int stream, float* out60);
+    // stream conflicts (k_conflicts.hip). ONE policy per engine; per stream a scene, a record and three counters. The first
+    // non-zero "conflicts" allocates all of it and makes the engine conflicts-capable for good: every pass runs the check
+    // launch behind its decode (its commit, motion_settle), ahead of the appearance, proposals and refresh launches; refresh
+    // rule 9 reads the records.
+    bool conflict_capable = false;
+    ConflictPolicy conflict_policy = VT_CONFLICT_DEFAULT_POLICY;     // the host's copy
+    std::vector<int32_t> conflict_scenes;         // beside it: the host's copy of the scenes, [B] on a capable engine
+    // ONE allocation: the policy | [B] scenes | [B] records | [B] counters, all zero but the policy
+    uint8_t* d_conflict = nullptr;
+    size_t conflict_off_scenes() const { return 64; }
+    size_t conflict_off_recs() const { return (conflict_off_scenes() + sizeof(int32_t) * (size_t)B + 63) & ~(size_t)63; }
+    size_t conflict_off_counts() const { return conflict_off_recs() + sizeof(ConflictRec) * (size_t)B; }
+    size_t conflict_bytes() const { return conflict_off_counts() + sizeof(ConflictCount) * (size_t)B; }
+    ConflictPolicy* d_conflict_policy() const { return reinterpret_cast<ConflictPolicy*>(d_conflict); }
+    int32_t* d_conflict_scenes() const { return reinterpret_cast<int32_t*>(d_conflict + conflict_off_scenes()); }
+    ConflictRec* d_conflict_recs() const { return reinterpret_cast<ConflictRec*>(d_conflict + conflict_off_recs()); }
+    ConflictCount* d_conflict_counts() const { return reinterpret_cast<ConflictCount*>(d_conflict + conflict_off_counts()); }
+    // pinned [B] by stream: the records of the last passes the host collected - what "conflicts" of vt_group_read_tensor reports
+    ConflictRec* h_conflict_all = nullptr;
+    // the "conflicts_scene" action: value >= 0: stream value & 0xFFFF (0xFFFF: every stream) goes to scene value >> 16; -1:
+    // every stream back to scene 0. The records of the streams it names are zeroed.
+    int conflicts_scene(int value);
+    int conflicts_stats(int stream, float* out16);
+    // stream b's record zeroed on the device (behind the stream's work) and in the engine's mirror: wherever zero_motion is called
+    int zero_conflicts(int b);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -391,11 +416,11 @@ struct Engine {
     vt_result* h_results = nullptr;
     StreamState* h_state = nullptr;
     // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
-    // slot, states, motion, appearance and proposal records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
-    // h_motion_all, h_appear_all and h_prop_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
+    // slot, states, motion, appearance, proposal and conflict records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
+    // h_motion_all, h_appear_all, h_prop_all and h_conflict_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
     // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them. The
     // optional ones are the rows of ONE list (vt_features.hip: kSinks), which everything below walks.
-    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_ALL = 31 };
+    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_CONFLICT = 32, SINK_ALL = 63 };
     unsigned sink_members() const;      // SINK_BASE and the sinks of the features the engine is capable of
     // what a pass's block carries of `to` (null: of the engine's own): host_states only with by_stream_states, an optional member only on a capable engine
     PassOut pass_sinks(const PassOut* to, bool by_stream_states) const;
@@ -543,7 +568,7 @@ struct KeyedFeature {
     const char* action_key = nullptr; int (Engine::*action)(int value) = nullptr;       // a key that is an action, not a field, and what it does
     int (*refuse_enable)(Engine*) = nullptr;    // a reason this engine cannot enable at all
 };
-const std::array<KeyedFeature, 4>& keyed_features();
+const std::array<KeyedFeature, 5>& keyed_features();
 
 // zero-filled device buffer. The fill is ordered on the ENGINE's stream: that stream is non-blocking, so a
 // hipMemset on the null stream (asynchronous for device memory) is not ordered against the kernels the

@@ -91,6 +91,33 @@ inline Answer apply_proposals(const char* key, int value, const int32_t* def, in
     return a;
 }
 
+enum { CF_ON, CF_IOU_PM, CF_GATE, CF_TAU, CF_WORDS = 8 };         // ConflictPolicy
+static constexpr Key kConflictKeys[] = {
+    {"conflicts", CF_ON, 0, 1, "conflicts: %d (0: off, 1: on)"},
+    {"conflicts_iou_pm", CF_IOU_PM, 1, 1000, "conflicts_iou_pm: %d (1..1000)"},
+    {"conflicts_gate", CF_GATE, 0, 1, "conflicts_gate: %d (0: report only, 1: refresh rule 9)"},
+};
+inline Answer apply_conflicts(const char* key, int value, const int32_t* def, int32_t* words, bool, char* text, size_t cap) {
+    const Answer a = apply(kConflictKeys, key, value, def, words, text, cap);
+    if (a == ACCEPTED && strcmp(key, "conflicts_iou_pm") == 0) put_tau(words + CF_TAU, words[CF_IOU_PM]);
+    return a;
+}
+// The value of the "conflicts_scene" action on an engine of B streams: stream | scene << 16. Stream 0xFFFF: every stream;
+// -1: every stream back to scene 0. ACCEPTED: streams [*first, *last) go to *scene; REFUSED: text written, nothing else.
+constexpr int kSceneAllStreams = 0xFFFF;
+inline Answer decode_scene(int value, int B, int* first, int* last, int32_t* scene, char* text, size_t cap) {
+    const int stream = value & 0xFFFF, sc = value >> 16;
+    if (value < -1 || (value >= 0 && stream != kSceneAllStreams && stream >= B)) {
+        if (value < -1) snprintf(text, cap, "conflicts_scene: %d (stream | scene << 16, stream 0xFFFF: all; -1: every stream to scene 0)", value);
+        else snprintf(text, cap, "conflicts_scene: stream %d (0..%d, 0xFFFF: all) of scene %d", stream, B - 1, sc);
+        return REFUSED;
+    }
+    const bool all = value < 0 || stream == kSceneAllStreams;
+    *first = all ? 0 : stream; *last = all ? B : stream + 1;
+    *scene = value < 0 ? 0 : sc;
+    return ACCEPTED;
+}
+
 // camera motion (k_camera_motion.hip): the policy words of vt_op_camera_motion, which validates them with this table; no
 // engine key reaches it yet
 enum { CM_MODE, CM_CELL, CM_RANGE, CM_CONF_PM, CM_MAX_CELLS, CM_WORDS = 8 };      // CamPolicy

@@ -1,4 +1,4 @@
-// vt_features.hip — host side of the seven optional in-the-pass features of an Engine
+// vt_features.hip — host side of the eight optional in-the-pass features of an Engine
 #include "vt_engine.hpp"
 
 // ---- the first enable of an optional feature -------------------------------------------------------------
@@ -45,6 +45,7 @@ static const Sink kSinks[] = {      // the casts: every member is a pointer to r
     {Engine::SINK_MOTION, sizeof(MotionRec), true, (void* PassOut::*)&PassOut::host_motion, (void* Engine::*)&Engine::h_motion_all, &Engine::motion_capable},
     {Engine::SINK_APPEAR, sizeof(AppearRec), true, (void* PassOut::*)&PassOut::host_appearance, (void* Engine::*)&Engine::h_appear_all, &Engine::appear_capable},
     {Engine::SINK_PROP, sizeof(PropRec), true, (void* PassOut::*)&PassOut::host_proposals, (void* Engine::*)&Engine::h_prop_all, &Engine::prop_capable},
+    {Engine::SINK_CONFLICT, sizeof(ConflictRec), true, (void* PassOut::*)&PassOut::host_conflicts, (void* Engine::*)&Engine::h_conflict_all, &Engine::conflict_capable},
 };
 
 static hipError_t pinned0(void** p, size_t bytes) {
@@ -77,7 +78,7 @@ unsigned Engine::sink_members() const {
 }
 
 PassOut Engine::pass_sinks(const PassOut* to, bool by_stream_states) const {
-    PassOut o{to ? to->host_results : h_results, !by_stream_states ? nullptr : to ? to->host_states : h_states_all, nullptr, nullptr, nullptr, nullptr};
+    PassOut o{to ? to->host_results : h_results, !by_stream_states ? nullptr : to ? to->host_states : h_states_all, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (const Sink& s : kSinks)
         if (this->*s.capable) o.*s.in = to ? to->*s.in : this->*s.own;
     return o;
@@ -458,6 +459,51 @@ int Engine::proposals_stats(int s, float* out) {
     return VT_OK;
 }
 
+// ---- stream conflicts ----------------------------------------------------------------------------------
+
+int Engine::zero_conflicts(int b) {
+    if (!conflict_capable) return VT_OK;
+    HIPCHK(hipMemsetAsync(d_conflict_recs() + b, 0, sizeof(ConflictRec), stream));
+    h_conflict_all[b] = ConflictRec{};      // the stream is in no outstanding pass: nothing else writes its entry
+    return VT_OK;
+}
+
+int Engine::conflicts_scene(int value) {
+    if (!conflict_capable)
+        return set_err(VT_ERR_INVALID_ARG, "conflicts_scene: stream conflicts are not enabled on this engine (vt_group_set_tuning \"conflicts\")");
+    int first = 0, last = 0;
+    int32_t scene = 0;
+    char text[256];
+    if (vtkeys::decode_scene(value, B, &first, &last, &scene, text, sizeof(text)) != vtkeys::ACCEPTED)
+        return set_err(VT_ERR_INVALID_ARG, "%s", text);
+    std::vector<int32_t> now = conflict_scenes;     // may throw: before anything changes
+    now.resize((size_t)B, 0);
+    std::fill(now.begin() + first, now.begin() + last, scene);
+    DEVICE_SCOPE(device);
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(d_conflict_scenes() + first, now.data() + first, sizeof(int32_t) * (size_t)(last - first), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_conflict_recs() + first, 0, sizeof(ConflictRec) * (size_t)(last - first)));
+    std::fill(h_conflict_all + first, h_conflict_all + last, ConflictRec{});
+    conflict_scenes.swap(now);
+    return VT_OK;
+}
+
+// [16]: the engine flag, the stream's record (status, frames_done, n_over, partner[4], iou[4]), its counters (evaluated,
+// conflicting, gated), its scene
+int Engine::conflicts_stats(int s, float* out16) {
+    if (!conflict_capable)
+        return set_err(VT_ERR_INVALID_ARG, "stream conflicts: not enabled on this engine (vt_group_set_tuning \"conflicts\")");
+    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counters: the device's
+    const ConflictRec r = h_conflict_all[s];
+    ConflictCount c{};
+    HIPCHK(hipMemcpy(&c, d_conflict_counts() + s, sizeof(c), hipMemcpyDeviceToHost));
+    out16[0] = (float)conflict_policy.on; out16[1] = (float)r.status; out16[2] = (float)r.frames_done; out16[3] = (float)r.n_over;
+    for (int k = 0; k < VT_CONFLICT_MAX; ++k) { out16[4 + k] = (float)r.partner[k]; out16[8 + k] = r.iou[k]; }
+    out16[12] = (float)c.evaluated; out16[13] = (float)c.conflicting; out16[14] = (float)c.gated;
+    out16[15] = (float)(conflict_scenes.empty() ? 0 : conflict_scenes[(size_t)s]);
+    return VT_OK;
+}
+
 // ---- the keyed features: ONE list, ONE setter -----------------------------------------------------------
 using namespace vtkeys;
 
@@ -474,6 +520,8 @@ static_assert(sizeof(PropPolicy) == 4 * PR_WORDS && at(offsetof(PropPolicy, mode
               at(offsetof(PropPolicy, max_n), PR_MAX_N) && at(offsetof(PropPolicy, min_sim_pm), PR_MIN_SIM_PM) && at(offsetof(PropPolicy, tau), PR_TAU) &&
               at(offsetof(PropPolicy, max_cells), PR_MAX_CELLS) && kPropKeys[1].hi == VT_PROP_MAX_PERIOD && kPropKeys[2].hi == VT_PROP_MAX &&
               kPropKeys[4].lo == VT_PROP_MIN_CELLS && kPropKeys[4].hi == VT_PROP_MAX_CELLS && OV_WORDS <= kMaxWords && PR_WORDS <= kMaxWords, "PropPolicy");
+static_assert(sizeof(ConflictPolicy) == 4 * CF_WORDS && at(offsetof(ConflictPolicy, on), CF_ON) && at(offsetof(ConflictPolicy, iou_pm), CF_IOU_PM) &&
+              at(offsetof(ConflictPolicy, gate), CF_GATE) && at(offsetof(ConflictPolicy, tau), CF_TAU) && CF_WORDS <= kMaxWords, "ConflictPolicy");
 
 // "motion_prior" 0 on a capable engine zeroes every stream's record, on the device and in both host copies
 static int motion_changed(Engine* e, const char* key, const int32_t* words) {
@@ -489,9 +537,9 @@ static int proposals_refuse(Engine* e) {
 
 // The stores: overlay the policy | [B] counters, motion the policy | [B] records (zero like known_motion, which nothing writes
 // before the engine is capable), appearance all zero but the policy and the anchors of the initialised streams, proposals
-// sized by the max_cells of the enable and zero up to the thumbnails. The casts: a policy is words from its first member on.
-const std::array<KeyedFeature, 4>& keyed_features() {
-    static const std::array<KeyedFeature, 4> list = {{
+// sized by the max_cells of the enable and zero up to the thumbnails, conflicts all zero but the policy (every stream in scene 0). The casts: a policy is words from its first member on.
+const std::array<KeyedFeature, 5>& keyed_features() {
+    static const std::array<KeyedFeature, 5> list = {{
         {"result overlay", "result_overlay", apply_overlay, (int32_t Engine::*)&Engine::overlay_policy, OV_WORDS, OV_FLAGS, &Engine::overlay_capable,
          &Engine::d_overlay, &Engine::overlay_bytes, nullptr, 0, "result_overlay", 6, &Engine::overlay_stats},
         {"motion prior", "motion_", apply_motion, (int32_t Engine::*)&Engine::motion_policy, MO_WORDS, MO_ON, &Engine::motion_capable,
@@ -502,6 +550,9 @@ const std::array<KeyedFeature, 4>& keyed_features() {
         {"reacquire proposals", "proposals", apply_proposals, (int32_t Engine::*)&Engine::prop_policy, PR_WORDS, PR_MODE, &Engine::prop_capable,
          &Engine::d_prop, &Engine::prop_bytes, &Engine::prop_off_thumb, Engine::SINK_PROP, "proposals", VT_PROP_STATS, &Engine::proposals_stats,
          nullptr, nullptr, nullptr, nullptr, proposals_refuse},
+        {"stream conflicts", "conflicts", apply_conflicts, (int32_t Engine::*)&Engine::conflict_policy, CF_WORDS, CF_ON, &Engine::conflict_capable,
+         &Engine::d_conflict, &Engine::conflict_bytes, nullptr, Engine::SINK_CONFLICT, "conflicts", 16, &Engine::conflicts_stats,
+         nullptr, nullptr, "conflicts_scene", &Engine::conflicts_scene},
     }};
     return list;
 }

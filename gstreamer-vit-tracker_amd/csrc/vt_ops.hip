@@ -848,6 +848,59 @@ int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The one launch of the stream conflicts on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_conflicts_check. Records and counters sit between guard bands and start as the caller's bytes.
+int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, const vt_result* results, const int32_t* slot_stream,
+                           const int32_t* winner, int n, const int32_t* scenes, const int32_t* policy, void* records, void* counts,
+                           void* host_records) try {
+    if (!states || !results || !scenes || !policy || !records || !counts || n < 1 || n > VT_MAX_STREAMS || n_streams < 1 ||
+        n_streams > VT_MAX_STREAMS)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "stream_conflicts: %d streams for %d slots", n_streams, n);
+    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here; tau is the table's
+    const ConflictPolicy def = VT_CONFLICT_DEFAULT_POLICY;
+    int32_t words[vtkeys::kMaxWords] = {};
+    for (const vtkeys::Key& k : vtkeys::kConflictKeys) {
+        char text[256];
+        if (policy[k.word] < 0 || vtkeys::apply_conflicts(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false, text,
+                                                         sizeof(text)) != vtkeys::ACCEPTED)
+            return set_err(VT_ERR_INVALID_ARG, "stream_conflicts: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
+    }
+    ConflictPolicy pol;
+    static_assert(sizeof(pol) == sizeof(words), "ConflictPolicy is kMaxWords words");
+    memcpy(&pol, words, sizeof(pol));
+    SlotMaps maps{slot_stream, winner, n, n_streams};
+    for (int b = 0; b < n; ++b)
+        if (int rc = maps.check("stream_conflicts", b)) return rc;
+    for (int s = 0; s < n_streams; ++s)
+        if (scenes[s] < 0 || scenes[s] > VT_CONFLICT_MAX_SCENE)
+            return set_err(VT_ERR_INVALID_ARG, "stream_conflicts: scene %d of stream %d (0..%d)", (int)scenes[s], s, VT_CONFLICT_MAX_SCENE);
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t ns = (size_t)n_streams, rb = ns * sizeof(ConflictRec), cb = ns * sizeof(ConflictCount);
+    DevArr dst, dres, dsc, dpol, dpo;
+    GuardedOut grec, gcnt;
+    PinnedBuf hrec;
+    HIPCHK(dst.upload(states, ns * sizeof(StreamState))); HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
+    HIPCHK(dsc.upload(scenes, ns * 4)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
+    HIPCHK(grec.alloc(rb)); HIPCHK(gcnt.alloc(cb));
+    HIPCHK(hipMemcpy(grec.out(), records, rb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(gcnt.out(), counts, cb, hipMemcpyHostToDevice));
+    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    PassOut po{};
+    po.host_conflicts = (ConflictRec*)hrec.p;
+    HIPCHK(dpo.upload(&po, sizeof(po)));
+    HIPCHK(maps.upload());
+    const ConflictArgs ca{dst.as<const StreamState>(), dres.as<const vt_result>(), maps.dev_slot_stream(), maps.dev_winner(),
+                          dpol.as<const ConflictPolicy>(), dsc.as<const int32_t>(), grec.as<ConflictRec>(), gcnt.as<ConflictCount>(),
+                          dpo.as<const PassOut>(), n};
+    HIPCHK(launch_conflicts_check(ca, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("stream_conflicts", {{&grec, "records"}, {&gcnt, "counters"}})) return rc;
+    HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
+    if (host_records) memcpy(host_records, hrec.p, rb);
+    return VT_OK;
+} VT_NOTHROW_INT
+
 // The folded LayerNorm as the engine runs it, end to end (see include/vittrack_hip_ops.h): X-epilogue producer -> row
 // terms by one of the three routes of the xgemm lambda (vt_engine.hip) -> launch_fold_layernorm -> the consuming GEMM
 // on the hi half of the pair. Every device output lies between guard bands and starts as 0xff.

@@ -24,6 +24,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
     "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_camera_motion", "vt_op_ln_chain_bf16",
+    "vt_op_stream_conflicts",
 ]
 
 _ops = None
@@ -67,6 +68,8 @@ def ops_lib():
                                   c_void_p, c_void_p]
     L.vt_op_camera_motion.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]
+    L.vt_op_stream_conflicts.argtypes = [c_int, c_void_p, c_int, c_void_p, i32p, i32p, c_int, i32p, i32p, c_void_p, c_void_p,
+                                         c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, i32p, i32p, c_int, c_void_p, c_void_p,
                                        c_int, c_int]
     _ops = L
@@ -498,6 +501,42 @@ def op_camera_motion(frames, states, mode=2, cell=0, rng=8, conf_pm=800, max_cel
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)
+# the stream conflicts' records (csrc/vt_common.hpp: ConflictRec 48 bytes and ConflictCount 16 bytes, both by stream)
+CONFLICT_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n_over", "<i4"), ("reserved", "<i4"),
+                               ("partner", "<i4", 4), ("iou", "<f4", 4)])
+CONFLICT_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("conflicting", "<i4"), ("gated", "<i4"), ("reserved", "<i4")])
+
+
+def op_stream_conflicts(states, results, scenes, on=1, iou_pm=300, gate=0, slot_stream=None, winner=None, records=None, counts=None,
+                        host_records=None, fill=0xA5, device=0):
+    """vt_op_stream_conflicts: the one launch of k_conflicts.hip on given operands, nothing else. states: snapshot.STATE
+    records by stream; results [n] RESULT_DTYPE by slot; scenes [n_streams] int32; slot_stream [n]: slot -> stream (None: the
+    identity); winner [n]: the winning slot of slot i's stream (None: the first slot naming a stream works for it). records
+    [n_streams] CONFLICT_REC_DTYPE and counts [n_streams] CONFLICT_COUNT_DTYPE to start from (None: every byte `fill`);
+    host_records: what the pinned mirror holds before (None: the mirror is null). -> dict(records, counts, host_records) as
+    they came back"""
+    st = np.ascontiguousarray(states, STATE).reshape(-1)
+    ns = len(st)
+    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+    n = len(res)
+    sc = np.ascontiguousarray(scenes, np.int32).reshape(-1)
+    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
+    assert sc.shape == (ns,) and (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
+
+    def start(a, dtype):
+        if a is None:
+            return np.frombuffer(bytes([fill]) * (ns * dtype.itemsize), dtype).copy()
+        return np.ascontiguousarray(a, dtype).reshape(-1).copy()
+    rec, cnt = start(records, CONFLICT_REC_DTYPE), start(counts, CONFLICT_COUNT_DTYPE)
+    hrec = None if host_records is None else np.ascontiguousarray(host_records, CONFLICT_REC_DTYPE).reshape(-1).copy()
+    assert len(rec) == ns and len(cnt) == ns and (hrec is None or len(hrec) == ns) and CONFLICT_REC_DTYPE.itemsize == 48
+    pol = np.array([on, iou_pm, gate, 0, 0, 0, 0, 0], np.int32)
+    _check_op(ops_lib().vt_op_stream_conflicts(
+        device, _vp(st), ns, _vp(res), _opt(smap, _i32), _opt(win, _i32), n, _i32(sc), _i32(pol), _vp(rec), _vp(cnt),
+        _opt(hrec, _vp)))
+    return dict(records=rec, counts=cnt, host_records=hrec)
+
+
 OVERLAY_POLICY_DTYPE = np.dtype([("flags", "<i4"), ("thickness", "<i4"), ("size", "<i4"), ("scale", "<i4"), ("luma", "<i4"),
                                  ("rgb", "<i4"), ("min_score_pct", "<i4"), ("reserved", "<i4")])
 OVERLAY_STATS_DTYPE = np.dtype([("drawn", "<i4"), ("n_drawn", "<i4"), ("n_gated", "<i4"), ("n_unsupported", "<i4"),

@@ -996,6 +996,58 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * window miss and adds no redo.
  *   Read-out: vt_group_read_tensor(g, stream, "proposals" / "proposals_pattern" / "proposals_map", ...).
  *
+ * ENGINE OPTIONS - stream conflicts (DESIGN.md section 3 "Stream conflicts"). Every other option looks at one stream in
+ * isolation. Streams of one picture that slide onto the same target, or whose targets cross, each keep success = 1, and a
+ * template refresh then cuts the other target into the template. With these keys every pass records, per stream, which
+ * other streams of the same SCENE overlap its new box and by how much, and - with the gate - keeps a conflicting stream
+ * from refreshing its template. Keys, per engine; a negative value selects the default; a value outside its range returns
+ * VT_ERR_INVALID_ARG and changes nothing:
+ *   key                  value                                                                   default
+ *   "conflicts"          0 = off, 1 = on                                                         0
+ *   "conflicts_iou_pm"   1..1000 per mille; tau = (float)pm / 1000.0f                            300
+ *   "conflicts_gate"     0 = report only, 1 = refresh rule 9                                     0
+ *   "conflicts_scene"    ACTION: value >= 0: stream (value & 0xFFFF) goes to scene (value >> 16), stream 0xFFFF = every
+ *                        stream; -1: every stream back to scene 0. Any other stream or value: VT_ERR_INVALID_ARG
+ * SCENES. The device cannot tell which slots show the same picture (a host-pointer pass hands it staged windows only), so
+ * the host says so: every stream has a scene number, an int32 in 0..65535 (the packed value of the key reaches 0..32767).
+ * Scene 0, the default, means "compared with nobody". Scenes are policy, not stream state: they live in the option's store,
+ * survive vt_group_init_*, import and copy, and are no part of a snapshot (format 0001, vt_snapshot_bytes unchanged). The
+ * action needs a capable engine (else VT_ERR_INVALID_ARG); it waits for the group's stream, writes the scene words and
+ * zeroes the records of the streams it names. Values of the other keys set before the first enable are remembered.
+ * The first non-zero "conflicts" makes the engine conflicts-capable for good: one store - the policy, per stream a scene, a
+ * 48-byte record and four counters - and the records' pinned mirror, within max_device_mib, else VT_ERR_OOM and nothing
+ * changes; the captured passes are captured again, here. From then on every pass - full, subset, candidate, synchronous and
+ * pipelined host, vt_group_profile_device - carries ONE more launch; engines that never enable launch exactly what they
+ * always did. Later changes of any key are one small copy and capture nothing.
+ *   THE RULE, to the bit. One launch directly behind the decode (candidate pass: behind the commit) and the motion prior's
+ * settle launch, ahead of the appearance, proposals, refresh, chip, peaks and overlay launches; it reads device memory only.
+ * With "conflicts" 0 it leaves at once and writes nothing. Otherwise, per stream s of the pass (a candidate pass: at its
+ * winning slot; losing slots leave no trace), st its state as the pass left it and r its final result: s is ELIGIBLE iff ALL
+ * of: (a) scene[s] != 0; (b) st.initialized != 0; (c) r.success != 0; (d) st.window_miss != st.frames_done. A stream that is
+ * not eligible gets the record {status 3, st.frames_done, n_over 0, partner -1, iou 0} and is nobody's partner. An eligible
+ * s with (x, y, w, h) = st.box is compared with every other eligible stream t OF THE SAME PASS with scene[t] == scene[s]:
+ * streams that are not in the pass are never read, so a record is a function of one pass alone and a redone pipelined pass
+ * recomputes it whole. Every operation a binary32 operation rounded on its own:
+ *   ix = fminf(x_s + w_s, x_t + w_t) - fmaxf(x_s, x_t), iy likewise; if !(ix > 0 && iy > 0) the pair has IoU 0 and is not
+ *   listed; else inter = ix * iy, uni = (w_s * h_s + w_t * h_t) - inter, iou = inter / uni (correctly rounded);
+ * iou(s, t) and iou(t, s) are the same bits. t is OVER iff iou >= tau; n_over counts them; partner[] / iou[] hold the up
+ * to 4 largest by (iou descending, stream index ascending) - the stream index, not the slot, breaks ties, so the order of
+ * a subset pass's list changes no record -, unused entries partner = -1, iou = 0. status = n_over > 0 ? 2 : 1.
+ *   THE RECORD, per stream, on the device and mirrored to pinned host memory like the appearance records: status (0 = no pass
+ * wrote it, 1, 2, 3), frames_done, n_over, a reserved word, partner[4], iou[4]. It is zeroed by vt_group_init_*,
+ * vt_group_enqueue_init_host, vt_group_set_state_box, vt_group_import_stream, vt_import_state, on the destination of
+ * vt_group_copy_stream and by the scene action; a stream that was not in a pass keeps its record. Three diagnostic counters
+ * per stream: `evaluated` (records with status 1 or 2), `conflicting` (status 2) and `gated`; like skipped_geometry they
+ * are never rewound and may count a redone pass twice.
+ *   REFRESH RULE 9. With "conflicts" 1 and "conflicts_gate" 1, a refresh that rules 1-5 of vt_group_set_template_refresh
+ * allow is suppressed, and gated += 1, where THIS pass's record of the stream (frames_done == st.frames_done) has status 2.
+ * The rule is checked ahead of rules 6, 7 and 8: a gated refresh counts no geometry skip and sets no window-miss mark, and
+ * it is tried again at the stream's next update. Switching the flag or the gate off switches the rule off; the appearance
+ * probe's own due rule is unchanged. THE TWIN IDENTITY: with gate 0 the option only reads - an enabled engine equals a plain
+ * engine in results, state words, templates, chips, peaks, records of the other options and overlays, bit for bit, in every
+ * kind of pass.
+ *   Read-out: vt_group_read_tensor(g, stream, "conflicts", ...).
+ *
  * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
@@ -1060,6 +1112,10 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * listed. "proposals_pattern" [M,M] and "proposals_map" [Hg-M+1,Wg-M+1]: the pattern (integers) and the similarity map of
  * the stream's slot in the LAST pass; VT_ERR_INVALID_ARG where that slot was not evaluated (the map: status 1; the pattern:
  * 1 or 3). Each of the three returns VT_ERR_INVALID_ARG on an engine that never enabled the proposals.
+ * "conflicts" [16] (by STREAM, whatever the last pass was; see vt_group_set_tuning "conflicts"): the engine flag, then the
+ * stream's record as the pinned mirror holds it (that of its last COLLECTED pass) - status, frames_done, n_over,
+ * partner[0..3], iou[0..3] -, its counters evaluated, conflicting and gated (the device's), and the stream's scene.
+ * VT_ERR_INVALID_ARG on an engine that never enabled the stream conflicts.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

@@ -205,6 +205,19 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
 int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
                         const int32_t* policy, int device_frames, uint16_t* thumbs, void* records, int64_t* sad,
                         void* host_states, void* host_records);
+/* The one launch of the stream conflicts (csrc/k_conflicts.hip; the rule: include/vittrack_hip.h above the "conflicts*" keys,
+ * DESIGN.md section 3 "Stream conflicts") on caller-supplied operands, and nothing else. states: [n_streams] raw 88-byte
+ * stream states (box, initialized, frames_done, window_miss are read); results: [n] by slot; slot_stream: [n] slot -> stream
+ * or null (the identity); winner: [n] the winning slot of slot i's stream, or null - then the FIRST slot that names a stream
+ * works for it; scenes: [n_streams] in 0..65535; policy: 8 int32 = flag, iou_pm, gate, then words the hook ignores (tau is
+ * computed from iou_pm as the key does) - validated with the table kConflictKeys of csrc/vt_feature_keys.hpp. In and out:
+ * records [n_streams] of 48 bytes and counts [n_streams] of 16 bytes (evaluated, conflicting, gated, reserved), which the
+ * caller pre-fills with a pattern: every byte of a stream no lane worked for, and with flag 0 every byte, comes back as it
+ * went in. host_records (nullable, in and out): the [n_streams] pinned mirror. Records and counters sit between guard
+ * bands; a changed guard byte is VT_ERR_HIP. A policy, scene or map out of range, n > 1024: VT_ERR_INVALID_ARG. */
+int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, const vt_result* results, const int32_t* slot_stream,
+                           const int32_t* winner, int n, const int32_t* scenes, const int32_t* policy, void* records, void* counts,
+                           void* host_records);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
