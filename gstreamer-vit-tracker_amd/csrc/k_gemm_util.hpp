@@ -13,7 +13,8 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 // log2(0.5 erfc(a / sqrt 2)) on [0, 9] (weighted so that the error of a * Phi(-a) is minimax): the
 // absolute error of GELU is <= 6.4e-7 for every finite x (float32 evaluation, checked on 2e6
 // points in [-30, 30]; beyond 9 the polynomial keeps falling, so the term underflows to 0 as the
-// true tail does). Cost: 5 fma + v_exp + v_max + fma. The previous form (Abramowitz-Stegun erf:
+// true tail does; tests/test_gpu_epilogue_edges.py holds the device to it value by value, through the interval
+// of bf16 results a GELU within that error can round to). Cost: 5 fma + v_exp + v_max + fma. The previous form (Abramowitz-Stegun erf:
 // v_rcp + v_exp + 13 more VALU) took 8 us of a 256x256 fc1 tile round of 33 us, because a tile's
 // epilogue is not overlapped with anything when a workgroup owns the whole CU.
 __device__ __forceinline__ float gelu_erf(float x) {

@@ -837,7 +837,11 @@ __device__ __forceinline__ float bf16_to_f32(bf16_t b) {
 }
 // f32 -> bf16, round to nearest even, NaN kept a NaN: one v_cvt_pk_bf16_f32 (gfx950). Same
 // result as the integer rounding (u + 0x7fff + ((u >> 16) & 1)) >> 16 of the oracle for every
-// finite input.
+// finite input. Observed on the MI355X through the ReLU, GELU and QKV epilogues of configurations 2, 3, 18
+// and 19 (tests/test_gpu_epilogue_edges.py): every normal bf16 pattern, both tie directions at every
+// exponent, the band that rounds to infinity and 4 * 10^5 ordinary values come back as the oracle's bits;
+// so do the subnormal inputs (bf16 subnormal patterns, their ties, a subnormal q = y * QK_SCALE) - none is
+// flushed to zero, in the scalar or in the packed form (profiles/epilogue_edges.txt).
 typedef __bf16 bf16v2_t __attribute__((ext_vector_type(2)));
 typedef float f32v2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bf16_t f32_to_bf16(float f) {

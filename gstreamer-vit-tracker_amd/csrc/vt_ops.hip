@@ -1,6 +1,8 @@
 // vt_ops.hip — operator-level entry points (include/vittrack_hip_ops.h): numerics tests and tuning tools call the
 // same kernel launchers the pass uses. Linked into libvittrack_hip_ops.so only; the product library does not carry them.
 // What the hooks share lives in vt_ops_host.hpp (host arithmetic) and vt_ops_util.hpp (device buffers, guard bands, timing).
+// Every buffer a kernel writes and a hook downloads is a GuardedOut, checked with guards_intact() after the synchronise;
+// the timing entry points and loops are not.
 #include "vt_ops_util.hpp"
 #include "../../include/vittrack_hip_ops.h"
 
@@ -41,7 +43,8 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
     GemmArgs g{};
     GemmOperands ops;
     HIPCHK(ops.upload(g, a, w, bias, M, N, K, K));
-    DevArr dxh, dxl, dpos, dcb, dcs, drs, dcst, dro, dcnt;
+    DevArr dpos, dcs, drs, dcnt;
+    GuardedOut dxh, dxl, dcb, dcst, dro;
     HIPCHK(dcb.alloc(MN * 2));
     g.lq = lo_quant(lo_shift);
     int epi;
@@ -56,7 +59,7 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
     const bool x_epi = epi == EPI_F32 || epi == EPI_RESID || epi == EPI_F32_POS;
     std::vector<bf16_t> hi(MN);
     std::vector<int8_t> lo(MN);
-    if (epi == EPI_RESID) {     // the addend goes in as the pair the engine would hold
+    if (epi == EPI_RESID) {     // the addend goes in as the pair the engine would hold, and stays between the bands
         pair_pack(c_inout, MN, lo_shift, hi.data(), lo.data());
         HIPCHK(dxh.upload(hi.data(), MN * 2)); HIPCHK(dxl.upload(lo.data(), MN));
     } else {
@@ -80,7 +83,7 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
     const TileCfg tc = split_cfg(cfg);
     g.tile_order = tc.order; cfg = tc.cfg;
     if (x_epi && rowstat_out) {
-        HIPCHK(dro.filled((size_t)M * 8, 0xff));
+        HIPCHK(dro.alloc((size_t)M * 8));
         HIPCHK(dcnt.zeros(cnt_bytes));
         const int eff = cfg < 0 ? gemm_effective_config(g, epi) : cfg;
         if (eff >= GEMM_CFG_256_MIN) {
@@ -97,12 +100,16 @@ int vt_op_gemm_bf16_lo(int device_id, const uint16_t* a, const uint16_t* w, cons
         for (int rep = 0; rep < 2 && (epi == EPI_F32 || epi == EPI_F32_POS); ++rep) HIPCHK(launch_gemm_cfg(g, epi, cfg < 0 ? gemm_effective_config(g, epi) : cfg, nullptr));
     }
     HIPCHK(hipDeviceSynchronize());
+    char what[48];
+    snprintf(what, sizeof(what), "gemm epilogue %d", epilogue);
+    if (int rc = guards_intact(what, {{&dcb, "bf16 output"}, {&dxh, "hi half"}, {&dxl, "lo8 half"}, {&dcst, "chunk partials"},
+                                      {&dro, "row terms"}})) return rc;
     if (x_epi) {
         HIPCHK(dxh.download(hi.data())); HIPCHK(dxl.download(lo.data()));
         pair_value(hi.data(), lo.data(), MN, g.lq.q, c_inout);
         if (rowstat_out) HIPCHK(dro.download(rowstat_out));
     } else {
-        HIPCHK(download_bf16(dcb.p, MN, c_inout));
+        HIPCHK(download_bf16(dcb.out(), MN, c_inout));
     }
     return VT_OK;
 } VT_NOTHROW_INT
@@ -125,17 +132,16 @@ int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* 
     GemmArgs g{};
     GemmOperands ops;
     HIPCHK(ops.upload(g, a, w, bias, M, N, K, K));
-    DevArr dih, dil, doh, dol, dcst, dro, dcnt;
+    DevArr dih, dil, dcnt;
+    GuardedOut doh, dol, dcst, dro;
     HIPCHK(dih.upload(xh_in, IN * 2)); HIPCHK(dil.upload(xl_in, IN));
     HIPCHK(dcnt.zeros((size_t)((M + 255) / 256 + 1) * 4));
-    HIPCHK(dcst.filled((size_t)M * nchunk * 8, 0xff)); HIPCHK(dro.filled((size_t)M * 8, 0xff));
+    HIPCHK(dcst.alloc((size_t)M * nchunk * 8)); HIPCHK(dro.alloc((size_t)M * 8));
     if (seg_rows > 0) {     // addend from the input pair through the remap, output compact
         g.Xh_in = dih.as<const bf16_t>(); g.Xl_in = dil.as<const uint8_t>(); g.seg_rows = seg_rows; g.seg_skip = seg_skip;
-        HIPCHK(doh.filled(MN * 2, 0xff)); HIPCHK(dol.filled(MN, 0xff));
-    } else {                // the launch as it always was: rows 0 .. M-1 of the pair, read and written in place
         HIPCHK(doh.alloc(MN * 2)); HIPCHK(dol.alloc(MN));
-        HIPCHK(hipMemcpy(doh.p, dih.p, doh.bytes, hipMemcpyDeviceToDevice));
-        HIPCHK(hipMemcpy(dol.p, dil.p, dol.bytes, hipMemcpyDeviceToDevice));
+    } else {                // the launch as it always was: rows 0 .. M-1 of the pair, read and written in place
+        HIPCHK(doh.upload(xh_in, MN * 2)); HIPCHK(dol.upload(xl_in, MN));
     }
     g.Xh = doh.as<bf16_t>(); g.Xl = dol.as<uint8_t>(); g.ldx = N;
     g.cstat = dcst.as<float2>(); g.rowstat_out = dro.as<float2>(); g.panel_cnt = dcnt.as<unsigned>(); g.ln_eps = eps;
@@ -143,6 +149,8 @@ int vt_op_gemm_resid_seg_bf16(int device_id, const uint16_t* a, const uint16_t* 
     if (launch_gemm_cfg(g, EPI_RESID, GEMM_CFG_256P4, nullptr) != hipSuccess)
         return set_err(VT_ERR_INVALID_ARG, "gemm: the 256x256 kernel does not take M=%d N=%d K=%d seg_rows=%d seg_skip=%d", M, N, K, seg_rows, seg_skip);
     HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("gemm resid_seg", {{&doh, "hi half"}, {&dol, "lo8 half"}, {&dcst, "chunk partials"}, {&dro, "row terms"}}))
+        return rc;
     HIPCHK(doh.download(xh_out)); HIPCHK(dol.download(xl_out));
     if (cstat_out) HIPCHK(dcst.download(cstat_out));
     if (rowstat_out) HIPCHK(dro.download(rowstat_out));
@@ -223,8 +231,9 @@ int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const fl
     GemmArgs g{};
     GemmOperands ops;
     HIPCHK(ops.upload(g, a, w, bias, M, 3 * D, D, D));
-    DevArr dqk, dvt, drs, dcs;
-    HIPCHK(dqk.alloc(n_qk * 2)); HIPCHK(dvt.zeros(n_vt * 2));
+    DevArr drs, dcs;
+    GuardedOut dqk, dvt;    // Vt starts as zeros: the kernels leave its padding positions alone, the engine zeroes it once
+    HIPCHK(dqk.alloc(n_qk * 2)); HIPCHK(dvt.alloc(n_vt * 2, 0));
     g.qk = dqk.as<bf16_t>(); g.vt = dvt.as<bf16_t>(); g.tokens = tokens; g.npad = npad; g.D = D;
     g.vt_perm = vt_perm ? 1 : 0;   // 1: the key order attention mode 3 reads
     if (rowstat_in) {              // folded LayerNorm: [M][2] row terms, [3D] column sums
@@ -238,8 +247,9 @@ int vt_op_qkv_bf16(int device_id, const uint16_t* a, const uint16_t* w, const fl
     else if (launch_gemm_cfg(g, EPI_QKV, cfg, nullptr) != hipSuccess)
         return set_err(VT_ERR_INVALID_ARG, "qkv: tile configuration %d does not fit this shape", cfg);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(download_bf16(dqk.p, n_qk, qk_out));
-    HIPCHK(download_bf16(dvt.p, n_vt, vt_out));
+    if (int rc = guards_intact("qkv", {{&dqk, "qk"}, {&dvt, "Vt"}})) return rc;
+    HIPCHK(download_bf16(dqk.out(), n_qk, qk_out));
+    HIPCHK(download_bf16(dvt.out(), n_vt, vt_out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -345,11 +355,13 @@ int vt_op_layernorm(int device_id, const float* x, const float* gamma, const flo
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t MD = (size_t)M * D;
-    DevArr dx, dg, db, dy;
+    DevArr dx, dg, db;
+    GuardedOut dy;
     HIPCHK(dx.upload(x, MD * 4)); HIPCHK(dg.upload(gamma, (size_t)D * 4)); HIPCHK(db.upload(beta, (size_t)D * 4)); HIPCHK(dy.alloc(MD * 2));
     HIPCHK(launch_layernorm(dx.as<const float>(), dg.as<const float>(), db.as<const float>(), dy.as<bf16_t>(), M, D, M, 0, 0, 1e-6f, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(download_bf16(dy.p, MD, y));
+    if (int rc = guards_intact("layernorm", {{&dy, "output"}})) return rc;
+    HIPCHK(download_bf16(dy.out(), MD, y));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -367,14 +379,16 @@ int vt_op_conv3x3_relu_bf16(int device_id, const uint16_t* t, const uint16_t* w,
     GemmArgs g{};
     GemmOperands ops;
     HIPCHK(ops.upload(g, t, w, bias, M, N, 9 * C, C));
-    DevArr dout, dz;
+    DevArr dz;
+    GuardedOut dout;
     HIPCHK(dout.alloc(M * N * 2)); HIPCHK(dz.zeros(256));
     g.Cb = dout.as<bf16_t>(); g.ldcb = N;
     g.conv_grid = grid; g.conv_C = C; g.zeros = dz.as<const bf16_t>();
     if (cfg < 0) HIPCHK(launch_gemm(g, EPI_RELU_BF16, nullptr));
     else HIPCHK(launch_gemm_cfg(g, EPI_RELU_BF16, cfg, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(download_bf16(dout.p, M * N, out));
+    if (int rc = guards_intact("conv3x3", {{&dout, "output"}})) return rc;
+    HIPCHK(download_bf16(dout.out(), M * N, out));
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -393,7 +407,8 @@ int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, con
     DEVICE_SCOPE(device_id);
     HIPCHK(headconv_prepare());
     const size_t M = (size_t)B * grid * grid, t_bytes = M * Cin * 2, w_bytes = (size_t)N * K * 2, b_bytes = (size_t)N * 4;
-    DevArr dt, dw, db, dout, dz;
+    DevArr dt, dw, db, dz;
+    GuardedOut dout;        // checked after the first launch; the timing loop behind it runs unchecked
     if (t) {
         HIPCHK(dt.upload(t, t_bytes)); HIPCHK(dw.upload(w, w_bytes)); HIPCHK(db.upload(bias, b_bytes));
     } else {
@@ -409,7 +424,8 @@ int vt_op_headconv_bf16(int device_id, const uint16_t* t, const uint16_t* w, con
     h.R = R; h.ncb = ncb;
     HIPCHK(launch_headconv(h, nullptr, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    if (out) HIPCHK(download_bf16(dout.p, M * N, out));
+    if (int rc = guards_intact("headconv", {{&dout, "output"}})) return rc;
+    if (out) HIPCHK(download_bf16(dout.out(), M * N, out));
 #ifdef VT_STAMPS   // diagnostic builds only: per-wave cycle sums of the main loop, medians printed
     DevArr ddbg;
     const size_t dbg_words = (size_t)B * grid * 2 * 8 * 4;
@@ -454,7 +470,8 @@ int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* x
     DEVICE_SCOPE(device_id);
     HIPCHK(headconv_prepare());
     const size_t MxD = (size_t)B * ntok * D, M = (size_t)B * ns, w_bytes = (size_t)N * D * 2, d_bytes = (size_t)D * 4, b_bytes = (size_t)N * 4;
-    DevArr dh, dl, dg, dbt, dw, db, dfeat, dout;
+    DevArr dh, dl, dg, dbt, dw, db;
+    GuardedOut dfeat, dout; // checked after the first run; the timing loop behind it runs unchecked
     if (xh) {
         HIPCHK(dh.upload(xh, MxD * 2)); HIPCHK(dl.upload(xl, MxD));       // lo8 bytes
         HIPCHK(dg.upload(gamma, d_bytes)); HIPCHK(dbt.upload(beta, d_bytes));
@@ -487,7 +504,8 @@ int vt_op_headconv_ln_bf16_lo(int device_id, const uint16_t* xh, const int8_t* x
     };
     HIPCHK(run());
     HIPCHK(hipDeviceSynchronize());
-    if (out) HIPCHK(download_bf16(dout.p, M * N, out));
+    if (int rc = guards_intact("headconv_ln", {{&dfeat, "normalised rows"}, {&dout, "output"}})) return rc;
+    if (out) HIPCHK(download_bf16(dout.out(), M * N, out));
     if (us_out) HIPCHK(time_launches(iters, run, us_out));
     return VT_OK;
 } VT_NOTHROW_INT
@@ -521,12 +539,13 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
     HIPCHK(headconv_prepare());
     const int ns = grid * grid;
     const size_t M = (size_t)B * ns, res_bytes = (size_t)B * sizeof(vt_result), st_bytes = (size_t)n_states * sizeof(StreamState);
-    DevArr dt, dt3, dw3, db3, dw4, db4, dhann, dho, dst, dres, dpo, dmap, dcnt, dbest, dz;
+    DevArr dt, dw3, db3, dw4, db4, dhann, dpo, dmap, dbest, dz;
+    GuardedOut dt3, dho, dst, dres, dcnt;   // states: the caller's; band counters: zeros; the rest 0xff
     PinnedBuf hres, hst;
     HIPCHK(dt.upload(t, M * C * 2)); HIPCHK(dw4.upload(w4, (size_t)8 * C * 4)); HIPCHK(db4.upload(b4, 8 * 4));
     HIPCHK(dhann.upload(hann, (size_t)ns * 4)); HIPCHK(dst.upload(states, st_bytes));
-    HIPCHK(dho.filled(M * 8 * 4, 0xff)); HIPCHK(dres.filled(res_bytes, 0xff));
-    HIPCHK(dcnt.zeros((size_t)B * 4)); HIPCHK(dbest.zeros((size_t)B * grid * 2 * 4));
+    HIPCHK(dho.alloc(M * 8 * 4)); HIPCHK(dres.alloc(res_bytes));
+    HIPCHK(dcnt.alloc((size_t)B * 4, 0)); HIPCHK(dbest.zeros((size_t)B * grid * 2 * 4));
     HIPCHK(hres.alloc(res_bytes)); HIPCHK(hst.alloc(st_bytes));
     memcpy(hres.p, host_results, res_bytes);
     memcpy(hst.p, host_states, st_bytes);
@@ -543,7 +562,7 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
         dec.t3 = dt.as<const bf16_t>();
     } else {
         HIPCHK(dw3.upload(w3, (size_t)C * 9 * C * 2)); HIPCHK(db3.upload(b3, (size_t)C * 4));
-        HIPCHK(dz.zeros(256)); HIPCHK(dt3.filled(M * C * 2, 0xff));
+        HIPCHK(dz.zeros(256)); HIPCHK(dt3.alloc(M * C * 2));
         dec.t3 = dt3.as<const bf16_t>();
         h.in = dt.as<const bf16_t>(); h.ldin = C; h.W = dw3.as<const bf16_t>(); h.ldw = 9 * C; h.bias = db3.as<const float>();
         h.out = dt3.as<bf16_t>(); h.ldout = C; h.zeros = dz.as<const bf16_t>();
@@ -560,6 +579,8 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
         HIPCHK(e);
     }
     HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("head_decode", {{&dt3, "conv output"}, {&dho, "head output"}, {&dst, "states"}, {&dres, "results"},
+                                               {&dcnt, "band counters"}})) return rc;
     HIPCHK(dho.download(head_out)); HIPCHK(dres.download(results)); HIPCHK(dst.download(states)); HIPCHK(dcnt.download(band_cnt));
     memcpy(host_results, hres.p, res_bytes);
     memcpy(host_states, hst.p, st_bytes);
@@ -585,7 +606,8 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
     DEVICE_SCOPE(device_id);
     const int ns = grid * grid;
     const size_t rec_bytes = (size_t)B * sizeof(vt_peaks);
-    DevArr dho, dhann, dst, dpol, drec, dpo;
+    DevArr dho, dhann, dpol, dpo;
+    GuardedOut dst, drec;   // both start as the caller's bytes
     PinnedBuf hrec;
     HIPCHK(dho.upload(head_out, (size_t)B * ns * 8 * 4)); HIPCHK(dhann.upload(hann, (size_t)ns * 4));
     HIPCHK(dst.upload(states, (size_t)n_states * sizeof(StreamState))); HIPCHK(dpol.upload(policies, (size_t)n_states * sizeof(PeaksPolicy)));
@@ -601,6 +623,7 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
     if (e == hipErrorInvalidValue) return set_err(VT_ERR_INVALID_ARG, "response_peaks: the launcher refuses grid %d", grid);
     HIPCHK(e);
     HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("response_peaks", {{&drec, "records"}, {&dst, "states"}})) return rc;
     HIPCHK(drec.download(records)); HIPCHK(dst.download(states));
     memcpy(host_records, hrec.p, rec_bytes);
     return VT_OK;
@@ -629,7 +652,8 @@ int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result*
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const int32_t flag = device_frames != 0;
-    DevArr dfr, dres, dpol, dst, dflag;
+    DevArr dfr, dres, dpol, dflag;
+    GuardedOut dst;         // the counters start as the caller's; the frames are the caller's own memory
     HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
     HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dst.upload(stats, (size_t)n_streams * sizeof(OverlayStats)));
     HIPCHK(dflag.upload(&flag, 4));
@@ -639,6 +663,7 @@ int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result*
     HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
     HIPCHK(launch_result_overlay(oa, nullptr));
     HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("result_overlay", {{&dst, "counters"}})) return rc;
     HIPCHK(dst.download(stats));
     return VT_OK;
 } VT_NOTHROW_INT
@@ -668,7 +693,8 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t sb = (size_t)n_streams * sizeof(StreamState), rb = (size_t)n_streams * sizeof(MotionRec);
-    DevArr dst, drec, dpol, dres, dcand, dpo;
+    DevArr dpol, dres, dcand, dpo;
+    GuardedOut dst, drec;   // both start as the caller's bytes
     PinnedBuf hst, hrec;
     HIPCHK(dst.upload(states, sb)); HIPCHK(drec.upload(records, rb)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
@@ -683,6 +709,7 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
     if (stages & 1) HIPCHK(launch_motion_place(ma, nullptr));
     if (stages & 2) HIPCHK(launch_motion_settle(ma, nullptr));
     HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("motion_prior", {{&dst, "states"}, {&drec, "records"}})) return rc;
     HIPCHK(dst.download(states)); HIPCHK(drec.download(records));
     if (host_states) memcpy(host_states, hst.p, sb);
     if (host_records) memcpy(host_records, hrec.p, rb);
@@ -703,18 +730,21 @@ int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t
     const AppearPolicy pol{1, 1, 0, 0.0f};
     std::vector<AppearRec> recs(n, AppearRec{1, 0, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}, 0});
     std::vector<unsigned> ticks(n);
-    DevArr da, dp, dpol, drec, dcnt, dtick, dpart, dsum;
+    DevArr da, dp, dpol, dcnt;
+    GuardedOut drec, dtick, dpart, dsum;
     HIPCHK(da.upload(anchor, rows)); HIPCHK(dp.upload(probe, rows)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(drec.upload(recs.data(), n * sizeof(AppearRec)));
-    HIPCHK(dcnt.zeros(n * sizeof(AppearCount))); HIPCHK(dtick.zeros(n * sizeof(unsigned)));
-    HIPCHK(dpart.filled(n * nch * 5 * sizeof(double), 0xff));      // NaN: a partial nobody wrote would show
-    HIPCHK(dsum.filled(n * 5 * sizeof(double), 0xff));
+    HIPCHK(dcnt.zeros(n * sizeof(AppearCount))); HIPCHK(dtick.alloc(n * sizeof(unsigned), 0));
+    HIPCHK(dpart.alloc(n * nch * 5 * sizeof(double)));      // NaN: a partial nobody wrote would show
+    HIPCHK(dsum.alloc(n * 5 * sizeof(double)));
     AppearArgs a{};
     a.policy = dpol.as<const AppearPolicy>(); a.counts = dcnt.as<AppearCount>(); a.recs = drec.as<AppearRec>();
     a.tickets = dtick.as<unsigned>(); a.partials = dpart.as<double>();
     a.anchor = da.as<const bf16_t>(); a.probe = dp.as<bf16_t>(); a.sums = dsum.as<double>(); a.n = n_slots;
     HIPCHK(launch_appearance_score(a, nt, cols, kpad, nullptr));
     HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("appearance_score", {{&drec, "records"}, {&dtick, "tickets"}, {&dpart, "partials"}, {&dsum, "sums"}}))
+        return rc;
     HIPCHK(drec.download(recs.data())); HIPCHK(dsum.download(sums)); HIPCHK(dtick.download(ticks.data()));
     for (size_t i = 0; i < n; ++i) {
         if (ticks[i] != 0) return set_err(VT_ERR_HIP, "appearance_score: slot %zu left its ticket at %u", i, ticks[i]);
@@ -825,8 +855,7 @@ int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int
     PinnedBuf hst, hrec;
     HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dst.upload(states, sb));
     HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4)); HIPCHK(dhead.zeros((size_t)n * sizeof(CamHead)));
-    HIPCHK(gth.alloc(tb)); HIPCHK(grec.alloc(rb)); HIPCHK(gsad.alloc(ab));
-    HIPCHK(hipMemcpy(gth.out(), thumbs, tb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(grec.out(), records, rb, hipMemcpyHostToDevice));
+    HIPCHK(gth.upload(thumbs, tb)); HIPCHK(grec.upload(records, rb)); HIPCHK(gsad.alloc(ab));
     if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
     if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
     HIPCHK(maps.upload());
@@ -883,8 +912,7 @@ int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, con
     PinnedBuf hrec;
     HIPCHK(dst.upload(states, ns * sizeof(StreamState))); HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
     HIPCHK(dsc.upload(scenes, ns * 4)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
-    HIPCHK(grec.alloc(rb)); HIPCHK(gcnt.alloc(cb));
-    HIPCHK(hipMemcpy(grec.out(), records, rb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(gcnt.out(), counts, cb, hipMemcpyHostToDevice));
+    HIPCHK(grec.upload(records, rb)); HIPCHK(gcnt.upload(counts, cb));
     if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
     PassOut po{};
     po.host_conflicts = (ConflictRec*)hrec.p;

@@ -40,18 +40,24 @@ struct PinnedBuf {
 // The output buffer of a hook between two guard bands: the bands carry a byte pattern, the output 0xff (a
 // bf16 NaN), so a row the kernel never stores arrives as NaN instead of whatever a reused allocation held, and a store
 // just outside the buffer (a slip in a row or block index) is reported instead of landing in a neighbour's memory.
+// A buffer whose start value is part of the kernel's contract takes that value instead: another byte (zeros for V^T and
+// the counters) or the caller's bytes (upload: an addend updated in place, states, records).
 struct GuardedOut {
     static constexpr size_t kGuard = 4096;      // bytes on each side; keeps out() 4 KiB aligned
     static constexpr int kPattern = 0xA5;
     DevBuf buf;
     size_t bytes = 0;
-    hipError_t alloc(size_t n) {
+    hipError_t alloc(size_t n, int start = 0xff) {
         bytes = n;
         hipError_t e = buf.alloc(n + 2 * kGuard);
         if (e != hipSuccess) return e;
         e = hipMemset(buf.p, kPattern, n + 2 * kGuard);
         if (e != hipSuccess) return e;
-        return hipMemset(out(), 0xff, n);
+        return hipMemset(out(), start, n);
+    }
+    hipError_t upload(const void* host, size_t n) {
+        const hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemcpy(out(), host, n, hipMemcpyHostToDevice);
     }
     void* out() const { return static_cast<char*>(buf.p) + kGuard; }
     template <class T> T* as() const { return static_cast<T*>(out()); }

@@ -15,7 +15,12 @@
 extern "C" {
 #endif
 
-/* ---- operator-level entry points (numerics tests call the same kernels the pass uses) ---- */
+/* ---- operator-level entry points (numerics tests call the same kernels the pass uses) ----
+ * Every hook that hands results back puts each device buffer a kernel writes between two 4 KiB guard bands: a store into
+ * a band is VT_ERR_HIP with a message naming the buffer. A pure output is filled with 0xff before the launch, so an
+ * element the kernel never stores comes back as NaN (bf16, float32, the pair) or as 0xff bytes; a buffer whose start
+ * value belongs to the contract keeps it (Vt and counters: zeros; an addend updated in place, states, records: the
+ * caller's bytes). The timing entry points (*_bench, a hook's iters / us_out loop) are not checked. */
 
 /* acc[M,N] = A[M,K] (bf16 bits) x W[N,K]^T (bf16 bits), float32 accumulation. Host pointers.
  * K % 64 == 0, N % 64 == 0. cfg: tile configuration as in vt_op_gemm_bench (< 0: the launcher's own
