@@ -1466,6 +1466,37 @@ class Group:
                     partner=[int(x) for x in v[4:8]], iou=np.asarray(v[8:12], np.float32).copy(), evaluated=int(v[12]),
                     conflicting=int(v[13]), gated=int(v[14]), scene=int(v[15]))
 
+    def set_health(self, on: bool = True, gate: bool | None = None, **keys) -> None:
+        """the "health*" keys of vt_group_set_tuning: behind the decode of every pass the engine takes a thumbnail of each due
+        stream's whole frame, measures it and its change since the stream's previous thumbnail, and flags a FROZEN (1), FLAT
+        (2) or CUT (4) picture. gate True: a flagged picture is not cut into the template in that pass (refresh rule 10).
+        keys: period, cell, still_run, flat_q, cut_pm, max_cells (max_cells before the first enable only). None keeps a
+        value. The first enable makes the engine health-capable (graphs recaptured, four more launches per pass from then
+        on). Refused while a pipelined pass is outstanding."""
+        for k, v in keys.items():
+            if k not in ("period", "cell", "still_run", "flat_q", "cut_pm", "max_cells"):
+                raise ValueError(f"set_health: {k}")
+            self.set_tuning("health_" + k, int(v))
+        if gate is not None:
+            self.set_tuning("health_gate", 1 if gate else 0)
+        self.set_tuning("health", 1 if on else 0)
+
+    def frame_health(self, stream: int = 0) -> dict:
+        """the stream's frame-health record of its last collected pass as exact integers (vt_group_read_tensor
+        "health_words": the record's 32-bit words in 16-bit halves) - status (0 no pass wrote it, 1 measured and compared, 2
+        no geometry, 4 no whole device frame, 5 measured without a comparable previous thumbnail), frames_done, flags, c, Wg,
+        Hg, still, S1, S2, G, D, HD, G_ref, has_prev - plus the engine flag and the stream's counters (evaluated, flagged;
+        gated: refreshes rule 10 refused) of the tensor "health".
+        The thumbnail's bookkeeping follows in the words and is not returned but for has_prev"""
+        h = self.read_tensor("health_words", stream).astype(np.uint32)
+        w = (h[0::2] | (h[1::2] << 16)).astype(np.uint32)
+        i32 = w.view(np.int32)
+        i64 = w[8:20].view(np.int64)
+        v = self.read_tensor("health", stream)
+        return dict(on=int(v[0]), status=int(i32[0]), frames_done=int(i32[1]), flags=int(i32[2]), c=int(i32[3]), Wg=int(i32[4]),
+                    Hg=int(i32[5]), still=int(i32[6]), S1=int(i64[0]), S2=int(i64[1]), G=int(i64[2]), D=int(i64[3]), HD=int(i64[4]),
+                    G_ref=int(i64[5]), has_prev=int(i32[20]), evaluated=int(v[13]), flagged=int(v[14]), gated=int(v[15]))
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""

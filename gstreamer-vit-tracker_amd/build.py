@@ -30,7 +30,7 @@ LIB_OPS = os.path.join(PKG, "libvittrack_hip_ops.so")
 LIB_HOST = os.path.join(HOST, "libvittrack_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_overlay.hip", "k_result_overlay.hip",
+HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_health.hip", "k_overlay.hip", "k_result_overlay.hip",
                "k_snapshot.hip", "vt_engine.hip", "vt_features.hip", "vt_abi.hip", "vt_ingest.hip", "vt_snapshot.hip", "vt_rccl.hip"]
 OPS_SOURCES = ["vt_ops.hip"]          # libvittrack_hip_ops.so only
 HEADER = os.path.join(PKG, "..", "include", "vittrack_hip.h")
@@ -100,7 +100,7 @@ def build_hip(force: bool = False, save_temps: bool = False, stamps: bool = Fals
         lib_hip, lib_ops = None, os.path.join(PKG, f"libvittrack_hip_{variant}.so")
     os.makedirs(obj_dir, exist_ok=True)
     headers = [os.path.join(CSRC, "vt_common.hpp"), os.path.join(CSRC, "k_gemm_util.hpp"), os.path.join(CSRC, "vt_engine.hpp"), os.path.join(CSRC, "k_cand.hpp"), os.path.join(CSRC, "k_snapshot.hpp"),
-               os.path.join(CSRC, "k_preproc_dev.hpp"), os.path.join(CSRC, "k_overlay_dev.hpp"), os.path.join(CSRC, "k_result_overlay.hpp"), os.path.join(CSRC, "k_preproc_body.inc"),
+               os.path.join(CSRC, "k_preproc_dev.hpp"), os.path.join(CSRC, "k_thumb_dev.hpp"), os.path.join(CSRC, "k_overlay_dev.hpp"), os.path.join(CSRC, "k_result_overlay.hpp"), os.path.join(CSRC, "k_preproc_body.inc"),
                os.path.join(CSRC, "k_refresh_dev.hpp"), os.path.join(CSRC, "k_refresh_crop.inc"),
                os.path.join(CSRC, "vt_ops_host.hpp"), os.path.join(CSRC, "vt_ops_util.hpp"), os.path.join(CSRC, "vt_feature_keys.hpp"),
                os.path.join(PKG, "..", "include", "vittrack_hip.h"), os.path.join(PKG, "..", "include", "vittrack_hip_ops.h")]

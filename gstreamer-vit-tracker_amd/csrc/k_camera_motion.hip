@@ -26,7 +26,7 @@
 // Only the option's own buffers and (mode 2) box[0], box[1] of the stream's state are written. Compiled like k_motion.hip
 // (-ffp-contract=off, correctly rounded division): one IEEE operation per source operation.
 #include "vt_common.hpp"
-#include "k_preproc_dev.hpp"
+#include "k_thumb_dev.hpp"
 
 #pragma clang fp contract(off)
 
@@ -93,20 +93,7 @@ __global__ __launch_bounds__(256) void camera_thumb_kernel(CamArgs a) {
     const int cell = blockIdx.x * 256 + threadIdx.x;
     if (cell >= cells) return;
     const int j = cell / Wg, i = cell - j * Wg;
-    const int c = h.c, step = c >> 2, half = c >> 3;
-    const FrameDesc& f = a.frames[slot];
-    int sum = 0, miss = 0;
-#pragma unroll 1
-    for (int v = 0; v < 4; ++v) {
-        const int py = j * c + v * step + half;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int px = i * c + u * step + half;
-            float rgb[3];
-            fetch_rgb<ANY>(f, px, py, rgb, miss);       // integers 0..255
-            sum += (77 * (int)rgb[0] + 150 * (int)rgb[1] + 29 * (int)rgb[2] + 128) >> 8;
-        }
-    }
+    const int sum = thumb_cell<ANY>(a.frames[slot], i, j, h.c);     // k_thumb_dev.hpp
     a.thumbs[((size_t)h.stream * 2 + h.cur) * (size_t)a.max_cells + cell] = (uint16_t)sum;
 }
 

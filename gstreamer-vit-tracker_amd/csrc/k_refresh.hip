@@ -21,7 +21,8 @@
 
 // What the kernels take of RefreshArgs: the members every engine sets, in their order, and - LAST in the argument block, so
 // that the kernels of engines without the appearance check read the arguments they always read where they always lay -
-// rule 8's three pointers, rule 8's and rule 9's (a null rule-8 policy: an engine without the appearance check), or nothing.
+// rule 8's three pointers, rule 8's and rule 9's (a null rule-8 policy: an engine without the appearance check), those and
+// rule 10's, or nothing.
 struct RefreshCore {
     const FrameDesc* frames; StreamState* states; const vt_result* results; const int32_t* slot_stream; const int32_t* winner;
     RefreshPolicy* policy; unsigned* tickets; bf16_t* tpl; const PassOut* out; StreamState* host_states; int n;
@@ -29,8 +30,10 @@ struct RefreshCore {
 template <int GATE> struct RefreshGate {};
 template <> struct RefreshGate<1> { const AppearPolicy* policy; AppearCount* counts; const AppearRec* recs; };
 template <> struct RefreshGate<2> : RefreshGate<1> { const ConflictPolicy* cf_policy; ConflictCount* cf_counts; const ConflictRec* cf_recs; };
+template <> struct RefreshGate<3> : RefreshGate<2> { const HealthPolicy* hl_policy; HealthCount* hl_counts; const HealthRec* hl_recs; };
 
-// MODE: which crop body (k_refresh_dev.hpp, VT_TEMPLATE_CROP_LAUNCH). GATE: 2 on conflicts-capable engines - rule 9, and
+// MODE: which crop body (k_refresh_dev.hpp, VT_TEMPLATE_CROP_LAUNCH). GATE: 3 on health-capable engines - rule 10, and rules 9
+// and 8 where the engine has those features too (a null policy: off) -, 2 on conflicts-capable engines - rule 9, and
 // rule 8 where the engine is appearance-capable too -, 1 on engines that are appearance-capable only - rule 8 -, 0 everywhere
 // else: the kernels without the rules
 template <int MODE, int ANY, int GATE>
@@ -52,12 +55,24 @@ __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshCore a, in
     if (st.window_miss == st.frames_done) return;                   // this pass's search crop missed its window: the redo refreshes
     // ---- rule 9: no other stream of the stream's scene sits on the same pixels (k_conflicts.hip) ----
     // ahead of the geometry: a gated refresh counts no geometry skip and sets no window-miss mark
-    if constexpr (GATE == 2) {
-        const ConflictPolicy cp = *gate.cf_policy;
+    if constexpr (GATE >= 2) {
+        const ConflictPolicy cp = GATE == 2 || gate.cf_policy ? *gate.cf_policy : ConflictPolicy{};    // GATE 3 without the check: off
         if (cp.on != 0 && cp.gate != 0) {                             // "conflicts" 0 switches the gate off with the check
             const ConflictRec rec = gate.cf_recs[stream];
             if (rec.status == 2 && rec.frames_done == st.frames_done) {     // this pass's record
                 if (blockIdx.x == 0 && threadIdx.x == 0) gate.cf_counts[stream].gated += 1;
+                return;
+            }
+        }
+    }
+    // ---- rule 10: the picture itself is no good - frozen, flat or cut (k_health.hip). Behind rule 9: a refresh rule 9 refused
+    // is not counted here; ahead of the geometry, like rule 9 ----
+    if constexpr (GATE == 3) {
+        const HealthPolicy hp = *gate.hl_policy;
+        if (hp.on != 0 && hp.gate != 0) {                             // "health" 0 switches the gate off with the measures
+            const HealthRec rec = gate.hl_recs[stream];
+            if (rec.flags != 0 && rec.frames_done == st.frames_done) {      // this pass's record
+                if (blockIdx.x == 0 && threadIdx.x == 0) gate.hl_counts[stream].gated += 1;
                 return;
             }
         }
@@ -77,7 +92,7 @@ __global__ __launch_bounds__(256) void template_refresh_kernel(RefreshCore a, in
     }
     // ---- rule 8: what the box holds still looks like what the stream was started from (k_appearance.hip) ----
     if constexpr (GATE != 0) {
-        const AppearPolicy ap = GATE == 1 || gate.policy ? *gate.policy : AppearPolicy{0, 1, 0, 0.0f};    // GATE 2 without the check: off
+        const AppearPolicy ap = GATE == 1 || gate.policy ? *gate.policy : AppearPolicy{0, 1, 0, 0.0f};    // GATE 2, 3 without the check: off
         const float tau = ap.tau;
         if (ap.on != 0 && tau > 0.0f) {                               // "appearance" 0 switches the gate off with the check
             const AppearRec rec = gate.recs[stream];
@@ -111,7 +126,8 @@ static void launch_refresh_t(const RefreshArgs& ra, const ModelDims& d, int tier
                         ra.host_states, ra.n};
     RefreshGate<GATE> gate;
     if constexpr (GATE != 0) { gate.policy = ra.ap_policy; gate.counts = ra.ap_counts; gate.recs = ra.ap_recs; }
-    if constexpr (GATE == 2) { gate.cf_policy = ra.cf_policy; gate.cf_counts = ra.cf_counts; gate.cf_recs = ra.cf_recs; }
+    if constexpr (GATE >= 2) { gate.cf_policy = ra.cf_policy; gate.cf_counts = ra.cf_counts; gate.cf_recs = ra.cf_recs; }
+    if constexpr (GATE == 3) { gate.hl_policy = ra.hl_policy; gate.hl_counts = ra.hl_counts; gate.hl_recs = ra.hl_recs; }
 #define RF_KERNEL(MODE) template_refresh_kernel<MODE, ANY, GATE>
     VT_TEMPLATE_CROP_LAUNCH(RF_KERNEL, d, tier, a.n, st, a, size, d.S, d.patch, d.kpad, tpl_elems, d.norm_a[0], d.norm_a[1],
                             d.norm_a[2], d.norm_b[0], d.norm_b[1], d.norm_b[2], gate);
@@ -131,7 +147,9 @@ hipError_t launch_template_refresh(const RefreshArgs& a, const ModelDims& d, int
     const bool gate = a.ap_policy != nullptr;
     if (gate && (!a.ap_counts || !a.ap_recs)) return hipErrorInvalidValue;
     if (a.cf_policy && (!a.cf_counts || !a.cf_recs)) return hipErrorInvalidValue;
-    if (a.cf_policy) launch_refresh_g<2>(a, d, tier, any_layout, st);
+    if (a.hl_policy && (!a.hl_counts || !a.hl_recs)) return hipErrorInvalidValue;
+    if (a.hl_policy) launch_refresh_g<3>(a, d, tier, any_layout, st);
+    else if (a.cf_policy) launch_refresh_g<2>(a, d, tier, any_layout, st);
     else if (gate) launch_refresh_g<1>(a, d, tier, any_layout, st);
     else launch_refresh_g<0>(a, d, tier, any_layout, st);
     return hipGetLastError();

@@ -497,6 +497,12 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         const int rc = (e->*f.stats)(stream, out);
         return rc ? rc : f.stats_len;
     }
+    if (n == "health_words") {              // by stream: the record of "health" as exact integers, two 16-bit halves per 32-bit word
+        if (!out) return e->health_capable ? VT_HEALTH_WORDS : e->health_stats(stream, nullptr);
+        if (capacity < VT_HEALTH_WORDS) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
+        const int rc = e->health_words(stream, out);
+        return rc ? rc : VT_HEALTH_WORDS;
+    }
     if (n == "anchor" || n == "probe") {    // by stream: the rows the stream is compared with / the rows of its last cut probe
         if (!e->appear_capable) return e->appearance_stats(stream, nullptr);
         return copy_out_bf16(n == "anchor" ? e->d_anchor(stream) : e->d_probe(stream), (int64_t)d.nt * d.kpad, out, capacity);

@@ -592,6 +592,15 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
         L("conflicts_check", 10.0 * n * n, (double)n * (sizeof(StreamState) + sizeof(vt_result) + 2.0 * sizeof(ConflictRec)),
           [&] { return launch_conflicts_check(ca, stream); });
     }
+    if (health_capable) {   // directly behind conflicts_check, ahead of the refresh launch, whose rule 10 reads the records; undrawn pixels: k_health.hip
+        const HealthArgs ha{d_frames, d_states, slot_stream, d_health_policy(), d_devflag(), d_health_recs(), d_health_counts(),
+                            d_health_heads(), d_health_accs(), d_health_hist(), d_health_thumbs(), (const PassOut*)(d_frames + B),
+                            health_policy.max_cells, n};
+        L("health_prepare", 0, (double)n * (sizeof(StreamState) + sizeof(HealthHead)), [&] { return launch_health_prepare(ha, stream); });
+        L("health_thumb", 0, 0, [&] { return launch_health_thumb(ha, ps.any_layout, stream); });
+        L("health_measure", 0, 0, [&] { return launch_health_measure(ha, stream); });
+        L("health_decide", 0, (double)n * 2.0 * sizeof(HealthRec), [&] { return launch_health_decide(ha, stream); });
+    }
     if (appear_capable) {   // ahead of everything that cuts or draws: the probe at the new box and its similarity to the anchor
         const AppearArgs aa{d_frames, d_states, d_results, slot_stream, ps.cand ? ps.cand->winner : nullptr, d_appear_policy(),
                             d_appear_counts(), d_appear_recs(), refresh_capable ? d_policy : nullptr, d_appear_tickets(),
@@ -618,6 +627,7 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
                        d_tickets, d_tpl, (const PassOut*)(d_frames + B), ps.cand ? ps.cand->host_states : nullptr, n};
         if (appear_capable) { ra.ap_policy = d_appear_policy(); ra.ap_counts = d_appear_counts(); ra.ap_recs = d_appear_recs(); }
         if (conflict_capable) { ra.cf_policy = d_conflict_policy(); ra.cf_counts = d_conflict_counts(); ra.cf_recs = d_conflict_recs(); }
+        if (health_capable) { ra.hl_policy = d_health_policy(); ra.hl_counts = d_health_counts(); ra.hl_recs = d_health_recs(); }
         L("refresh_template", 0, 2.0 * n * (sizeof(StreamState) + sizeof(vt_result)),
           [&] { return launch_template_refresh(ra, d, ps.tier, ps.any_layout, stream); });
     }
@@ -798,6 +808,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     HIPCHK(hipMemcpyAsync(d_states + b, h_st, sizeof(StreamState), hipMemcpyHostToDevice, stream));
     if (int rc = zero_motion(b)) return rc;
     if (int rc = zero_conflicts(b)) return rc;
+    if (int rc = zero_health(b)) return rc;
     to_desc(*f, h_desc);
     // entry b of the per-pass block: every pass uploads its own block ahead of its kernels, in stream order
     HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));

@@ -368,6 +368,38 @@ struct Engine {
     int conflicts_stats(int stream, float* out16);
     // stream b's record zeroed on the device (behind the stream's work) and in the engine's mirror: wherever zero_motion is called
     int zero_conflicts(int b);
+    // frame health (k_health.hip). ONE policy per engine; per stream a record, three counters, four accumulators, two
+    // histograms and two thumbnails of max_cells, per slot a header. The first non-zero "health" allocates all of it with the
+    // max_cells of that moment and makes the engine health-capable for good: every pass runs the four launches directly behind
+    // conflicts_check, ahead of the appearance, proposals and refresh launches; refresh rule 10 reads the records.
+    bool health_capable = false;
+    HealthPolicy health_policy = VT_HEALTH_DEFAULT_POLICY;      // the host's copy
+    // ONE allocation: the policy | [B] records | [B] counters | [B] headers | [B] accumulators | [B][2][32] histograms |
+    // [B][2][max_cells] thumbnails, zero up to the thumbnails
+    uint8_t* d_health = nullptr;
+    static size_t health_off_recs() { return 64; }
+    size_t health_off_counts() const { return health_off_recs() + sizeof(HealthRec) * (size_t)B; }
+    size_t health_off_heads() const { return (health_off_counts() + sizeof(HealthCount) * (size_t)B + 63) & ~(size_t)63; }
+    size_t health_off_accs() const { return health_off_heads() + sizeof(HealthHead) * (size_t)B; }
+    size_t health_off_hist() const { return health_off_accs() + sizeof(long long) * HEALTH_ACCS * (size_t)B; }
+    size_t health_off_thumbs() const { return (health_off_hist() + sizeof(int32_t) * 2 * VT_HEALTH_BINS * (size_t)B + 63) & ~(size_t)63; }
+    size_t health_bytes() const { return health_off_thumbs() + sizeof(uint16_t) * 2 * (size_t)health_policy.max_cells * (size_t)B; }
+    HealthPolicy* d_health_policy() const { return reinterpret_cast<HealthPolicy*>(d_health); }
+    HealthRec* d_health_recs() const { return reinterpret_cast<HealthRec*>(d_health + health_off_recs()); }
+    HealthCount* d_health_counts() const { return reinterpret_cast<HealthCount*>(d_health + health_off_counts()); }
+    HealthHead* d_health_heads() const { return reinterpret_cast<HealthHead*>(d_health + health_off_heads()); }
+    unsigned long long* d_health_accs() const { return reinterpret_cast<unsigned long long*>(d_health + health_off_accs()); }
+    int32_t* d_health_hist() const { return reinterpret_cast<int32_t*>(d_health + health_off_hist()); }
+    uint16_t* d_health_thumbs() const { return reinterpret_cast<uint16_t*>(d_health + health_off_thumbs()); }
+    // pinned [B] by stream: the records of the last passes the host collected - what "health" and "health_words" report
+    HealthRec* h_health_all = nullptr;
+#define VT_HEALTH_STATS 24
+#define VT_HEALTH_WORDS (2 * (int)(sizeof(HealthRec) / 4))
+    int health_stats(int stream, float* out24);
+    int health_words(int stream, float* out);       // the record's 32-bit words, low half then high half: every float exact
+    // stream b without a previous thumbnail, still 0, a zero record, on the device (behind the stream's work) and in the
+    // engine's mirror: wherever zero_conflicts is called for a stream that starts anew
+    int zero_health(int b);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -417,10 +449,10 @@ struct Engine {
     StreamState* h_state = nullptr;
     // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
     // slot, states, motion, appearance, proposal and conflict records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
-    // h_motion_all, h_appear_all, h_prop_all and h_conflict_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
+    // h_motion_all, h_appear_all, h_prop_all, h_conflict_all and h_health_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
     // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them. The
     // optional ones are the rows of ONE list (vt_features.hip: kSinks), which everything below walks.
-    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_CONFLICT = 32, SINK_ALL = 63 };
+    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_CONFLICT = 32, SINK_HEALTH = 64, SINK_ALL = 127 };
     unsigned sink_members() const;      // SINK_BASE and the sinks of the features the engine is capable of
     // what a pass's block carries of `to` (null: of the engine's own): host_states only with by_stream_states, an optional member only on a capable engine
     PassOut pass_sinks(const PassOut* to, bool by_stream_states) const;
@@ -568,7 +600,7 @@ struct KeyedFeature {
     const char* action_key = nullptr; int (Engine::*action)(int value) = nullptr;       // a key that is an action, not a field, and what it does
     int (*refuse_enable)(Engine*) = nullptr;    // a reason this engine cannot enable at all
 };
-const std::array<KeyedFeature, 5>& keyed_features();
+const std::array<KeyedFeature, 6>& keyed_features();
 
 // zero-filled device buffer. The fill is ordered on the ENGINE's stream: that stream is non-blocking, so a
 // hipMemset on the null stream (asynchronous for device memory) is not ordered against the kernels the

@@ -140,4 +140,29 @@ inline Answer apply_camera_motion(const char* key, int value, const int32_t* def
     }
     return apply(kCameraKeys, key, value, def, words, text, cap);
 }
+
+// frame health (k_health.hip): the "health*" keys; vt_op_frame_health validates its policy words with the same table
+enum { HL_ON, HL_PERIOD, HL_CELL, HL_STILL_RUN, HL_FLAT_Q, HL_CUT_PM, HL_GATE, HL_MAX_CELLS, HL_WORDS = 8 };     // HealthPolicy
+static constexpr Key kHealthKeys[] = {
+    {"health", HL_ON, 0, 1, "health: %d (0: off, 1: on)"},
+    {"health_period", HL_PERIOD, 1, 1000000, "health_period: %d (1..1000000)"},
+    {"health_cell", HL_CELL, 0, 32, "health_cell: %d (0: automatic, 4, 8, 16 or 32)"},
+    {"health_still_run", HL_STILL_RUN, 1, 1000, "health_still_run: %d (1..1000)"},
+    {"health_flat_q", HL_FLAT_Q, 0, 4080, "health_flat_q: %d (0..4080)"},
+    {"health_cut_pm", HL_CUT_PM, 0, 1000, "health_cut_pm: %d (0..1000, 0: never)"},
+    {"health_gate", HL_GATE, 0, 1, "health_gate: %d (0: report only, 1: refresh rule 10)"},
+    {"health_max_cells", HL_MAX_CELLS, 4096, 262144, "health_max_cells: %d (4096..262144)"},
+};
+// "health_cell": 0 or a power of two in 4..32; "health_max_cells" sizes the store: frozen once the engine is capable
+inline Answer apply_health(const char* key, int value, const int32_t* def, int32_t* words, bool capable, char* text, size_t cap) {
+    if (capable && strcmp(key, "health_max_cells") == 0) {
+        snprintf(text, cap, "health_max_cells: fixed by the first enable of \"health\" (%d)", (int)words[HL_MAX_CELLS]);
+        return REFUSED;
+    }
+    if (strcmp(key, "health_cell") == 0 && value > 0 && (value < 4 || (value & (value - 1)) != 0)) {
+        snprintf(text, cap, kHealthKeys[HL_CELL].refusal, value);
+        return REFUSED;
+    }
+    return apply(kHealthKeys, key, value, def, words, text, cap);
+}
 }   // namespace vtkeys

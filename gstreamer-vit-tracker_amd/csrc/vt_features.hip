@@ -1,4 +1,4 @@
-// vt_features.hip — host side of the eight optional in-the-pass features of an Engine
+// vt_features.hip — host side of the nine optional in-the-pass features of an Engine
 #include "vt_engine.hpp"
 
 // ---- the first enable of an optional feature -------------------------------------------------------------
@@ -46,6 +46,7 @@ static const Sink kSinks[] = {      // the casts: every member is a pointer to r
     {Engine::SINK_APPEAR, sizeof(AppearRec), true, (void* PassOut::*)&PassOut::host_appearance, (void* Engine::*)&Engine::h_appear_all, &Engine::appear_capable},
     {Engine::SINK_PROP, sizeof(PropRec), true, (void* PassOut::*)&PassOut::host_proposals, (void* Engine::*)&Engine::h_prop_all, &Engine::prop_capable},
     {Engine::SINK_CONFLICT, sizeof(ConflictRec), true, (void* PassOut::*)&PassOut::host_conflicts, (void* Engine::*)&Engine::h_conflict_all, &Engine::conflict_capable},
+    {Engine::SINK_HEALTH, sizeof(HealthRec), true, (void* PassOut::*)&PassOut::host_health, (void* Engine::*)&Engine::h_health_all, &Engine::health_capable},
 };
 
 static hipError_t pinned0(void** p, size_t bytes) {
@@ -78,7 +79,7 @@ unsigned Engine::sink_members() const {
 }
 
 PassOut Engine::pass_sinks(const PassOut* to, bool by_stream_states) const {
-    PassOut o{to ? to->host_results : h_results, !by_stream_states ? nullptr : to ? to->host_states : h_states_all, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PassOut o{to ? to->host_results : h_results, !by_stream_states ? nullptr : to ? to->host_states : h_states_all, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (const Sink& s : kSinks)
         if (this->*s.capable) o.*s.in = to ? to->*s.in : this->*s.own;
     return o;
@@ -504,6 +505,44 @@ int Engine::conflicts_stats(int s, float* out16) {
     return VT_OK;
 }
 
+// ---- frame health ------------------------------------------------------------------------------------
+
+int Engine::zero_health(int b) {
+    if (!health_capable) return VT_OK;
+    HIPCHK(hipMemsetAsync(d_health_recs() + b, 0, sizeof(HealthRec), stream));     // has_prev, still and the record
+    h_health_all[b] = HealthRec{};          // the stream is in no outstanding pass: nothing else writes its entry
+    return VT_OK;
+}
+
+// [24], for people: mode, status, frames_done, flags, c, Wg, Hg, still, S1 / n, the standard deviation, D / n,
+// HD * 1000 / (2 n), G * 1000 / G_ref, evaluated, flagged, gated, then period, cell, still_run, flat_q, cut_pm, gate, and two
+// zeros. The exact integers: "health_words"
+int Engine::health_stats(int s, float* out) {
+    if (!health_capable)
+        return set_err(VT_ERR_INVALID_ARG, "frame health: not enabled on this engine (vt_group_set_tuning \"health\")");
+    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counters: the device's
+    const HealthRec r = h_health_all[s];
+    HealthCount c{};
+    HIPCHK(hipMemcpy(&c, d_health_counts() + s, sizeof(c), hipMemcpyDeviceToHost));
+    const double n = (double)r.Wg * r.Hg, mean = n > 0 ? r.S1 / n : 0.0, var = n > 0 ? r.S2 / n - mean * mean : 0.0;
+    const float v[VT_HEALTH_STATS] = {(float)health_policy.on, (float)r.status, (float)r.frames_done, (float)r.flags, (float)r.c, (float)r.Wg,
+                                      (float)r.Hg, (float)r.still, (float)mean, (float)sqrt(var > 0 ? var : 0.0), n > 0 ? (float)(r.D / n) : 0.0f,
+                                      n > 0 ? (float)(r.HD * 1000.0 / (2.0 * n)) : 0.0f, r.G_ref > 0 ? (float)(r.G * 1000.0 / (double)r.G_ref) : 0.0f,
+                                      (float)c.evaluated, (float)c.flagged, (float)c.gated, (float)health_policy.period, (float)health_policy.cell,
+                                      (float)health_policy.still_run, (float)health_policy.flat_q, (float)health_policy.cut_pm, (float)health_policy.gate,
+                                      0.0f, 0.0f};
+    memcpy(out, v, sizeof(v));
+    return VT_OK;
+}
+
+int Engine::health_words(int s, float* out) {
+    if (!health_capable) return health_stats(s, nullptr);
+    uint32_t w[sizeof(HealthRec) / 4];
+    memcpy(w, h_health_all + s, sizeof(w));
+    for (size_t k = 0; k < sizeof(HealthRec) / 4; ++k) { out[2 * k] = (float)(w[k] & 0xFFFFu); out[2 * k + 1] = (float)(w[k] >> 16); }
+    return VT_OK;
+}
+
 // ---- the keyed features: ONE list, ONE setter -----------------------------------------------------------
 using namespace vtkeys;
 
@@ -522,6 +561,11 @@ static_assert(sizeof(PropPolicy) == 4 * PR_WORDS && at(offsetof(PropPolicy, mode
               kPropKeys[4].lo == VT_PROP_MIN_CELLS && kPropKeys[4].hi == VT_PROP_MAX_CELLS && OV_WORDS <= kMaxWords && PR_WORDS <= kMaxWords, "PropPolicy");
 static_assert(sizeof(ConflictPolicy) == 4 * CF_WORDS && at(offsetof(ConflictPolicy, on), CF_ON) && at(offsetof(ConflictPolicy, iou_pm), CF_IOU_PM) &&
               at(offsetof(ConflictPolicy, gate), CF_GATE) && at(offsetof(ConflictPolicy, tau), CF_TAU) && CF_WORDS <= kMaxWords, "ConflictPolicy");
+static_assert(sizeof(HealthPolicy) == 4 * HL_WORDS && at(offsetof(HealthPolicy, on), HL_ON) && at(offsetof(HealthPolicy, period), HL_PERIOD) &&
+              at(offsetof(HealthPolicy, cell), HL_CELL) && at(offsetof(HealthPolicy, still_run), HL_STILL_RUN) && at(offsetof(HealthPolicy, flat_q), HL_FLAT_Q) &&
+              at(offsetof(HealthPolicy, cut_pm), HL_CUT_PM) && at(offsetof(HealthPolicy, gate), HL_GATE) && at(offsetof(HealthPolicy, max_cells), HL_MAX_CELLS) &&
+              kHealthKeys[HL_PERIOD].hi == VT_HEALTH_MAX_PERIOD && kHealthKeys[HL_MAX_CELLS].lo == VT_HEALTH_MIN_CELLS &&
+              kHealthKeys[HL_MAX_CELLS].hi == VT_HEALTH_MAX_CELLS && HL_WORDS <= kMaxWords, "HealthPolicy");
 
 // "motion_prior" 0 on a capable engine zeroes every stream's record, on the device and in both host copies
 static int motion_changed(Engine* e, const char* key, const int32_t* words) {
@@ -531,15 +575,22 @@ static int motion_changed(Engine* e, const char* key, const int32_t* words) {
     e->known_motion.assign((size_t)e->B, MotionRec{});
     return VT_OK;
 }
+// "health" 0 on a capable engine zeroes every stream's record and bookkeeping, on the device and in the host's copies
+static int health_changed(Engine* e, const char* key, const int32_t* words) {
+    if (strcmp(key, "health") != 0 || words[HL_ON] != 0) return VT_OK;
+    HIPCHK(hipMemset(e->d_health_recs(), 0, sizeof(HealthRec) * (size_t)e->B));
+    memset(e->h_health_all, 0, sizeof(HealthRec) * (size_t)e->B);
+    return VT_OK;
+}
 static int proposals_refuse(Engine* e) {
     return prop_pattern_side(e->d.T) ? VT_OK : set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", e->d.T);
 }
 
 // The stores: overlay the policy | [B] counters, motion the policy | [B] records (zero like known_motion, which nothing writes
 // before the engine is capable), appearance all zero but the policy and the anchors of the initialised streams, proposals
-// sized by the max_cells of the enable and zero up to the thumbnails, conflicts all zero but the policy (every stream in scene 0). The casts: a policy is words from its first member on.
-const std::array<KeyedFeature, 5>& keyed_features() {
-    static const std::array<KeyedFeature, 5> list = {{
+// sized by the max_cells of the enable and zero up to the thumbnails, conflicts all zero but the policy (every stream in scene 0), health sized by the max_cells of the enable and zero up to the thumbnails. The casts: a policy is words from its first member on.
+const std::array<KeyedFeature, 6>& keyed_features() {
+    static const std::array<KeyedFeature, 6> list = {{
         {"result overlay", "result_overlay", apply_overlay, (int32_t Engine::*)&Engine::overlay_policy, OV_WORDS, OV_FLAGS, &Engine::overlay_capable,
          &Engine::d_overlay, &Engine::overlay_bytes, nullptr, 0, "result_overlay", 6, &Engine::overlay_stats},
         {"motion prior", "motion_", apply_motion, (int32_t Engine::*)&Engine::motion_policy, MO_WORDS, MO_ON, &Engine::motion_capable,
@@ -553,6 +604,9 @@ const std::array<KeyedFeature, 5>& keyed_features() {
         {"stream conflicts", "conflicts", apply_conflicts, (int32_t Engine::*)&Engine::conflict_policy, CF_WORDS, CF_ON, &Engine::conflict_capable,
          &Engine::d_conflict, &Engine::conflict_bytes, nullptr, Engine::SINK_CONFLICT, "conflicts", 16, &Engine::conflicts_stats,
          nullptr, nullptr, "conflicts_scene", &Engine::conflicts_scene},
+        {"frame health", "health", apply_health, (int32_t Engine::*)&Engine::health_policy, HL_WORDS, HL_ON, &Engine::health_capable,
+         &Engine::d_health, &Engine::health_bytes, &Engine::health_off_thumbs, Engine::SINK_HEALTH, "health", VT_HEALTH_STATS, &Engine::health_stats,
+         health_changed},
     }};
     return list;
 }

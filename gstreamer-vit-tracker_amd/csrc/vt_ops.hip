@@ -877,6 +877,72 @@ int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The four launches of the frame health on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_health_prepare, _thumb, _measure and _decide, in that order. Every array the launches may write sits between guard
+// bands; headers and accumulators start as 0xff bytes, the others as the caller's.
+int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
+                       const int32_t* policy, int device_frames, uint16_t* thumbs, int64_t* accs, int32_t* hist, void* heads,
+                       void* records, void* counts, void* host_records) try {
+    if (!frames || !states || !policy || !thumbs || !accs || !hist || !heads || !records || !counts || n < 1 || n > VT_MAX_STREAMS ||
+        n_streams < 1 || n_streams > VT_MAX_STREAMS)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "frame_health: %d streams for %d slots", n_streams, n);
+    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here, in its words
+    const HealthPolicy def = VT_HEALTH_DEFAULT_POLICY;
+    int32_t words[vtkeys::kMaxWords] = {};
+    for (const vtkeys::Key& k : vtkeys::kHealthKeys) {
+        char text[256];
+        if (policy[k.word] < 0 || vtkeys::apply_health(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false, text,
+                                                      sizeof(text)) != vtkeys::ACCEPTED)
+            return set_err(VT_ERR_INVALID_ARG, "frame_health: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
+    }
+    HealthPolicy pol;
+    static_assert(sizeof(pol) == sizeof(words), "HealthPolicy is kMaxWords words");
+    memcpy(&pol, words, sizeof(pol));
+    std::vector<FrameDesc> desc((size_t)n);
+    SlotMaps maps{slot_stream, nullptr, n, n_streams};
+    for (int b = 0; b < n; ++b) {
+        if (int rc = check_frame(frames[b])) return rc;
+        to_desc(frames[b], &desc[(size_t)b]);
+        if (int rc = maps.check("frame_health", b)) return rc;
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t ns = (size_t)n_streams, sb = ns * sizeof(StreamState), rb = ns * sizeof(HealthRec), cb = ns * sizeof(HealthCount);
+    const size_t tb = ns * 2 * (size_t)pol.max_cells * sizeof(uint16_t), ab = ns * HEALTH_ACCS * sizeof(long long);
+    const size_t hb = ns * 2 * VT_HEALTH_BINS * sizeof(int32_t), hdb = (size_t)n * sizeof(HealthHead);
+    const int32_t flag = device_frames != 0;
+    DevArr dfr, dpol, dflag;
+    DevArr dpo;
+    GuardedOut gst, gth, gacc, ghist, ghead, grec, gcnt;
+    PinnedBuf hrec;
+    HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4));
+    HIPCHK(gst.upload(states, sb)); HIPCHK(gth.upload(thumbs, tb)); HIPCHK(ghist.upload(hist, hb)); HIPCHK(grec.upload(records, rb));
+    HIPCHK(gcnt.upload(counts, cb)); HIPCHK(gacc.alloc(ab)); HIPCHK(ghead.alloc(hdb));
+    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    PassOut po{};
+    po.host_health = (HealthRec*)hrec.p;
+    HIPCHK(dpo.upload(&po, sizeof(po)));
+    HIPCHK(maps.upload());
+    const HealthArgs ha{dfr.as<const FrameDesc>(), gst.as<const StreamState>(), maps.dev_slot_stream(), dpol.as<const HealthPolicy>(),
+                        dflag.as<const int32_t>(), grec.as<HealthRec>(), gcnt.as<HealthCount>(), ghead.as<HealthHead>(),
+                        gacc.as<unsigned long long>(), ghist.as<int32_t>(), gth.as<uint16_t>(), dpo.as<const PassOut>(), pol.max_cells, n};
+    int level = 0;
+    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
+    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(launch_health_prepare(ha, nullptr));
+    HIPCHK(launch_health_thumb(ha, level, nullptr));
+    HIPCHK(launch_health_measure(ha, nullptr));
+    HIPCHK(launch_health_decide(ha, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("frame_health", {{&gst, "states"}, {&gth, "thumbnails"}, {&gacc, "accumulators"}, {&ghist, "histograms"},
+                                                {&ghead, "headers"}, {&grec, "records"}, {&gcnt, "counters"}})) return rc;
+    HIPCHK(gst.download(states)); HIPCHK(gth.download(thumbs)); HIPCHK(gacc.download(accs)); HIPCHK(ghist.download(hist));
+    HIPCHK(ghead.download(heads)); HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
+    if (host_records) memcpy(host_records, hrec.p, rb);
+    return VT_OK;
+} VT_NOTHROW_INT
+
 // The one launch of the stream conflicts on given operands: see include/vittrack_hip_ops.h. Nothing runs but
 // launch_conflicts_check. Records and counters sit between guard bands and start as the caller's bytes.
 int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, const vt_result* results, const int32_t* slot_stream,

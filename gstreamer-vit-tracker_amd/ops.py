@@ -24,7 +24,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
     "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_camera_motion", "vt_op_ln_chain_bf16",
-    "vt_op_stream_conflicts",
+    "vt_op_stream_conflicts", "vt_op_frame_health",
 ]
 
 _ops = None
@@ -68,6 +68,8 @@ def ops_lib():
                                   c_void_p, c_void_p]
     L.vt_op_camera_motion.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]
+    L.vt_op_frame_health.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]
     L.vt_op_stream_conflicts.argtypes = [c_int, c_void_p, c_int, c_void_p, i32p, i32p, c_int, i32p, i32p, c_void_p, c_void_p,
                                          c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, i32p, i32p, c_int, c_void_p, c_void_p,
@@ -498,6 +500,50 @@ def op_camera_motion(frames, states, mode=2, cell=0, rng=8, conf_pm=800, max_cel
         device, arr, _vp(st), ns, _opt(smap, _i32), n, _i32(pol), 1 if device_frames else 0, _vp(th), _vp(rec), _vp(sad),
         _opt(hst, _vp), _opt(hrec, _vp)))
     return dict(states=st, thumbs=th, records=rec, sad=sad, host_states=hst, host_records=hrec)
+
+
+# the frame health's arrays (csrc/vt_common.hpp: HealthRec 104 bytes and HealthCount 16 bytes by stream, HealthHead 32 bytes by slot)
+HEALTH_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("flags", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"),
+                             ("still", "<i4"), ("reserved0", "<i4"), ("S1", "<i8"), ("S2", "<i8"), ("G", "<i8"), ("D", "<i8"),
+                             ("HD", "<i8"), ("G_ref", "<i8"), ("has_prev", "<i4"), ("cur", "<i4"), ("pW", "<i4"), ("pH", "<i4"),
+                             ("pc", "<i4"), ("reserved1", "<i4")])
+HEALTH_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("flagged", "<i4"), ("gated", "<i4"), ("reserved", "<i4")])
+HEALTH_HEAD_DTYPE = np.dtype([("status", "<i4"), ("stream", "<i4"), ("frames_done", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"),
+                              ("cur", "<i4"), ("reserved", "<i4")])
+_HEALTH_BINS = 32      # a record's flags: 1 FROZEN, 2 FLAT, 4 CUT
+
+
+def op_frame_health(frames, states, on=1, period=1, cell=0, still_run=3, flat_q=32, cut_pm=500, gate=0, max_cells=65536,
+                    slot_stream=None, thumbs=None, hist=None, records=None, counts=None, device_frames=True, host_records=None,
+                    device=0):
+    """vt_op_frame_health: the four launches of k_health.hip on given operands, nothing else. frames: CFrame per slot with
+    DEVICE planes; states: snapshot.STATE records by stream; slot_stream [n]: slot -> stream (None: the identity). The
+    store to start from: thumbs [n_streams, 2, max_cells] uint16 and hist [n_streams, 2, 32] int32 (None: 0xff bytes - what
+    no launch stores shows), records [n_streams] HEALTH_REC_DTYPE and counts [n_streams] HEALTH_COUNT_DTYPE (None: zeros - no
+    previous thumbnail); host_records: what the pinned mirror holds before (None: the mirror is null). -> dict(states,
+    thumbs, hist, records, counts, accs [n_streams, 4] int64 = S1, S2, G, D - 0xff bytes where no launch stored -, heads [n]
+    HEALTH_HEAD_DTYPE, host_records) as they came back; feed thumbs, hist, records and counts to the next call to go on"""
+    n = len(frames)
+    arr = (CFrame * n)(*frames)
+    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    ns = len(st)
+    smap = _arr(slot_stream, np.int32)
+    assert smap is None or smap.shape == (n,)
+    th = np.full((ns, 2, max_cells), 0xFFFF, np.uint16) if thumbs is None else np.ascontiguousarray(thumbs, np.uint16).copy()
+    hi = np.full((ns, 2, _HEALTH_BINS), -1, np.int32) if hist is None else np.ascontiguousarray(hist, np.int32).copy()
+    assert th.shape == (ns, 2, max_cells) and hi.shape == (ns, 2, _HEALTH_BINS)
+    rec = np.zeros(ns, HEALTH_REC_DTYPE) if records is None else np.ascontiguousarray(records, HEALTH_REC_DTYPE).reshape(-1).copy()
+    cnt = np.zeros(ns, HEALTH_COUNT_DTYPE) if counts is None else np.ascontiguousarray(counts, HEALTH_COUNT_DTYPE).reshape(-1).copy()
+    assert len(rec) == ns and len(cnt) == ns and HEALTH_REC_DTYPE.itemsize == 104 and HEALTH_HEAD_DTYPE.itemsize == 32
+    hrec = None if host_records is None else np.ascontiguousarray(host_records, HEALTH_REC_DTYPE).reshape(-1).copy()
+    assert hrec is None or len(hrec) == ns
+    pol = np.array([on, period, cell, still_run, flat_q, cut_pm, gate, max_cells], np.int32)
+    accs = np.empty((ns, 4), np.int64)
+    heads = np.empty(n, HEALTH_HEAD_DTYPE)
+    _check_op(ops_lib().vt_op_frame_health(
+        device, arr, _vp(st), ns, _opt(smap, _i32), n, _i32(pol), 1 if device_frames else 0, _vp(th), _vp(accs), _vp(hi),
+        _vp(heads), _vp(rec), _vp(cnt), _opt(hrec, _vp)))
+    return dict(states=st, thumbs=th, hist=hi, records=rec, counts=cnt, accs=accs, heads=heads, host_records=hrec)
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)

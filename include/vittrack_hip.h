@@ -1048,6 +1048,37 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * kind of pass.
  *   Read-out: vt_group_read_tensor(g, stream, "conflicts", ...).
  *
+ * FRAME HEALTH (csrc/k_health.hip; the rule to the bit: include/vittrack_hip_ops.h, vt_op_frame_health):
+ * every option above judges the target, this one the picture - a frozen feed, a covered or blacked-out lens and a cut to
+ * another scene all look like ordinary updates. Keys (a negative value selects the default):
+ *   "health"             0 = off, 1 = on                                                         0
+ *   "health_period"      1..1,000,000: a stream is due when frames_done % period == 0            1
+ *   "health_cell"        0 = automatic, or 4, 8, 16, 32: the thumbnail cell in source pixels     0
+ *   "health_still_run"   1..1000: FROZEN at this many identical comparisons in a row             3
+ *   "health_flat_q"      0..4080: FLAT at a standard deviation of the thumbnail <= this          32
+ *   "health_cut_pm"      0..1000 per mille of the cells in another histogram bin: CUT; 0 never   500
+ *   "health_gate"        0 = report only, 1 = refresh rule 10                                    0
+ *   "health_max_cells"   4,096..262,144 thumbnail cells per stream; fixed by the first enable    65,536
+ * The first non-zero "health" makes the engine health-capable for good: one store - the policy, per stream a record, three
+ * counters, four accumulators, two histograms and two uint16 thumbnails of max_cells -, a pinned mirror of the records, the
+ * graphs captured again with four launches directly behind the decode (the commit, conflicts_check) and ahead of the
+ * appearance, proposals, refresh, chip, peak and overlay launches (the thumbnail is taken from undrawn pixels) in EVERY
+ * kind of pass. Per due stream of a pass whose frame is a whole frame in device memory: a thumbnail t (camera motion's
+ * cell: sixteen integer luma taps), S1 = sum t, S2 = sum t * t, G = the absolute differences of horizontal and vertical
+ * neighbours, a 32-bin histogram of t >> 7, and against the stream's previous thumbnail of the same geometry D = sum |t - p|
+ * and HD = sum |hist - hist_p|. Status: 0 not due (the record, the previous thumbnail and the counters stay), 4 no whole
+ * device frame (every host-pointer pass), 2 no geometry, 5 measured without a comparable previous thumbnail, 1 measured and
+ * compared. Flags: 1 FROZEN (status 1, D == 0 in still_run comparisons in a row), 2 FLAT (n * S2 - S1 * S1 <= flat_q^2 * n^2),
+ * 4 CUT (status 1, HD * 1000 >= cut_pm * 2 * n). Integers only: a pipelined run equals a synchronous one. vt_group_init_*,
+ * an import and the destination of a copy clear the stream's previous thumbnail and record; "health" 0 clears every
+ * stream's; no part of a snapshot.
+ *   REFRESH RULE 10. With "health" 1 and "health_gate" 1, a refresh that rules 1-5 and rule 9 allow is not made when the
+ * stream's record of THIS pass has flags != 0: nothing is cut, the stream's gated counter grows, no geometry skip is counted
+ * and no window miss is marked; it is tried again at the next update. THE TWIN IDENTITY: with gate 0 the option only
+ * reads - an enabled engine equals a plain engine in results, state words, templates, chips, peaks and overlays, bit for
+ * bit, in every kind of pass.
+ *   Read-out: vt_group_read_tensor(g, stream, "health" / "health_words", ...).
+ *
  * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
@@ -1116,6 +1147,13 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * stream's record as the pinned mirror holds it (that of its last COLLECTED pass) - status, frames_done, n_over,
  * partner[0..3], iou[0..3] -, its counters evaluated, conflicting and gated (the device's), and the stream's scene.
  * VT_ERR_INVALID_ARG on an engine that never enabled the stream conflicts.
+ * "health" [24] (by STREAM; see vt_group_set_tuning "health"), for people: the engine flag, then the stream's record as the
+ * pinned mirror holds it (that of its last COLLECTED pass) - status, frames_done, flags, c, Wg, Hg, still, S1 / n, the
+ * standard deviation sqrt(S2 / n - (S1 / n)^2), D / n, HD * 1000 / (2 n), G * 1000 / G_ref (0 where G_ref is 0) -, its
+ * counters evaluated, flagged and gated (the device's), then period, cell, still_run, flat_q, cut_pm, gate, 0, 0.
+ * "health_words" [52] (by STREAM): the same record as exact integers - its 26 32-bit words (status, frames_done, flags, c,
+ * Wg, Hg, still, 0, then S1, S2, G, D, HD, G_ref as int64 low word first, then has_prev, cur, pW, pH, pc, 0), each as two
+ * floats: the low and the high 16 bits. Both: VT_ERR_INVALID_ARG on an engine that never enabled the frame health.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

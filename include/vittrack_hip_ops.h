@@ -210,6 +210,47 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
 int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
                         const int32_t* policy, int device_frames, uint16_t* thumbs, void* records, int64_t* sad,
                         void* host_states, void* host_records);
+/* The four launches of the frame health (csrc/k_health.hip; DESIGN.md section 3 "Frame health") on caller-supplied operands,
+ * and nothing else: per stream a thumbnail of the whole frame, five exact integer measures of it and of its change since the
+ * stream's previous thumbnail, and three flags: the picture is FROZEN, FLAT (covered, blacked out) or CUT to another scene.
+ * The engine runs them in every pass of a health-enabled engine (include/vittrack_hip.h, "health*" keys), where refresh rule
+ * 10 reads the record and counts `gated`. THE RULE, to the bit:
+ *   POLICY: 8 int32 = on (0 / 1), period (1..1,000,000), cell (0 = automatic, or 4, 8, 16, 32), still_run (1..1000), flat_q
+ * (0..4080), cut_pm (0..1000 per mille, 0: never), gate (0 / 1: refresh rule 10; read by no launch of this hook), max_cells (4,096..262,144
+ * thumbnail cells per stream) - the bounds of the table kHealthKeys of csrc/vt_feature_keys.hpp, which names the words
+ * "health", "health_period", "health_cell", "health_still_run", "health_flat_q", "health_cut_pm", "health_gate" and
+ * "health_max_cells" (defaults 0, 1, 0, 3, 32, 500, 0, 65,536).
+ *   SLOTS: the first slot that names a stream works for it; a later slot of that stream gets header status -1 and does nothing.
+ *   STATUS of the working slot, in this order of tests. 0 (not due): on == 0, the stream is not initialised, or frames_done %
+ * period != 0 - record, bookkeeping, counters and the previous thumbnail stay as they are. 4: device_frames == 0 or the
+ * planes do not hold the whole frame (windowed: x0, y0 != 0 or ww, wh != w, h). 2 (no geometry): with c the key's cell, or
+ * with 0 the smallest of 4, 8, 16, 32, 64 with (W / c) * (H / c) <= max_cells (integer divisions), Wg = W / c, Hg = H / c,
+ * n = Wg * Hg: no such c, n > max_cells, Wg < 8 or Hg < 8. 5: measured, but the stream has no previous thumbnail, or one of
+ * another W, H or c. 1: measured and compared. Statuses 4 and 2 write the record with zero measures and flags (c, Wg, Hg as
+ * far as they exist), G_ref = 0, and clear has_prev and still. frames_done is the state's value as the hook receives it.
+ *   THUMBNAIL t[j][i], uint16 <= 4080: the cell of vt_op_camera_motion above (sixteen taps, (77 R + 150 G + 29 B + 128) >> 8
+ * each, summed). Statuses 1 and 5 store it to the stream's other buffer (cur ^ 1 of the last one; buffer 0 with has_prev 0)
+ * and set has_prev = 1, cur, pW, pH, pc.
+ *   MEASURES, int64: S1 = sum t; S2 = sum t * t; G = sum over j, i < Wg - 1 of |t[j][i + 1] - t[j][i]| + sum over j < Hg - 1, i
+ * of |t[j + 1][i] - t[j][i]|; hist[b] = #{cells: t >> 7 == b}, b = 0..31, int32. Status 1, with p the previous thumbnail and
+ * hist_p its histogram: D = sum |t - p|, HD = sum over b of |hist[b] - hist_p[b]|; status 5: D = HD = 0.
+ *   STILL: status 1: still = (D == 0) ? min(still + 1, 1 << 30) : 0; status 5: still = 0.
+ *   FLAGS: FROZEN (1): status 1 and still >= still_run. FLAT (2): status 1 or 5 and n * S2 - S1 * S1 <= flat_q * flat_q * n * n
+ * (the thumbnail's standard deviation is at most flat_q; all products below 2^61). CUT (4): status 1, cut_pm > 0 and HD * 1000
+ * >= cut_pm * 2 * n (HD counts every moved cell twice). G_ref := G at status 5 and at a CUT; it stays otherwise.
+ *   COUNTERS per stream: evaluated (status 1 or 5), flagged (of which flags != 0), gated (no launch of this hook counts it).
+ *   RECORD, per stream, 104 bytes: status, frames_done, flags, c, Wg, Hg, still, a reserved word; S1, S2, G, D, HD, G_ref
+ * (int64); has_prev, cur, pW, pH, pc, a reserved word.
+ *   OPERANDS: frames: [n] by slot with DEVICE planes (read only); states: [n_streams] raw 88-byte stream states (initialized
+ * and frames_done are read; they come back as they went in); slot_stream: [n] slot -> stream or null (the identity). In and
+ * out: thumbs [n_streams][2][max_cells] uint16 (Hg x Wg at the front of each buffer), hist [n_streams][2][32] int32, records
+ * [n_streams] of 104 bytes, counts [n_streams] of 16 bytes. Out: accs [n_streams][4] int64 = S1, S2, G, D as the launches
+ * summed them, heads [n] of 32 bytes (status, stream, frames_done, c, Wg, Hg, cur, 0); every byte of accs no launch stored is
+ * 0xff. host_records (nullable, in and out): the [n_streams] pinned mirror of the records. All seven device arrays sit between
+ * guard bands; a changed guard byte is VT_ERR_HIP. A policy or map out of range, n > 1024: VT_ERR_INVALID_ARG. */
+int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
+                       const int32_t* policy, int device_frames, uint16_t* thumbs, int64_t* accs, int32_t* hist, void* heads,
+                       void* records, void* counts, void* host_records);
 /* The one launch of the stream conflicts (csrc/k_conflicts.hip; the rule: include/vittrack_hip.h above the "conflicts*" keys,
  * DESIGN.md section 3 "Stream conflicts") on caller-supplied operands, and nothing else. states: [n_streams] raw 88-byte
  * stream states (box, initialized, frames_done, window_miss are read); results: [n] by slot; slot_stream: [n] slot -> stream
