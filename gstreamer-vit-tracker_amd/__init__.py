@@ -1497,6 +1497,30 @@ class Group:
                     Hg=int(i32[5]), still=int(i32[6]), S1=int(i64[0]), S2=int(i64[1]), G=int(i64[2]), D=int(i64[3]), HD=int(i64[4]),
                     G_ref=int(i64[5]), has_prev=int(i32[20]), evaluated=int(v[13]), flagged=int(v[14]), gated=int(v[15]))
 
+    def set_arbitration(self, on: bool = True, **keys) -> None:
+        """the "arbitrate*" keys of vt_group_set_tuning: behind the decode of every pass, where the committed box no longer
+        looks like the stream's anchor (similarity below low_pm) and a runner-up peak of the response map does (at least
+        high_pm), the runner-up is committed instead. keys: max, radius, min_resp_pm, low_pm, high_pm; None keeps a value. The
+        first enable needs an appearance-capable engine (set_appearance first) and makes the engine arbitration-capable (graphs
+        recaptured, four more launches per pass from then on). Refused while a pipelined pass is outstanding."""
+        for k, v in keys.items():
+            if k not in ("max", "radius", "min_resp_pm", "low_pm", "high_pm"):
+                raise ValueError(f"set_arbitration: {k}")
+            if v is not None:
+                self.set_tuning("arbitrate_" + k, int(v))
+        self.set_tuning("arbitrate", 1 if on else 0)
+
+    def arbitration(self, stream: int = 0) -> dict:
+        """the stream's arbitration record of its last collected pass (vt_group_read_tensor "arbitrate"): status (0 not due, 1
+        kept, 2 switched, 3 candidate pass, 4 rule 6 failed at peak 0, 5 window miss), frames_done, n, chosen, the counters
+        evaluated and switched, and peaks: n dicts of cell, status, score, resp, similarity (np.float32) and box"""
+        v = self.read_tensor("arbitrate", stream)
+        n = int(v[3])
+        peaks = [dict(cell=int(p[0]), status=int(p[1]), score=np.float32(p[2]), resp=np.float32(p[3]), similarity=np.float32(p[4]),
+                      box=np.asarray(p[5:9], np.float32).copy()) for p in (v[8 + 10 * k:18 + 10 * k] for k in range(n))]
+        return dict(on=int(v[0]), status=int(v[1]), frames_done=int(v[2]), n=n, chosen=int(v[4]), evaluated=int(v[5]),
+                    switched=int(v[6]), peaks=peaks)
+
     def graph_captures(self) -> int:
         """hipGraph captures since creation: all crop tiers are captured when the engine is created (those for formats
         other than RGB8 / NV12 / YUY2 in the first init on such a format), none inside a pass"""

@@ -30,7 +30,7 @@ LIB_OPS = os.path.join(PKG, "libvittrack_hip_ops.so")
 LIB_HOST = os.path.join(HOST, "libvittrack_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_health.hip", "k_overlay.hip", "k_result_overlay.hip",
+HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_arbitrate.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_health.hip", "k_overlay.hip", "k_result_overlay.hip",
                "k_snapshot.hip", "vt_engine.hip", "vt_features.hip", "vt_abi.hip", "vt_ingest.hip", "vt_snapshot.hip", "vt_rccl.hip"]
 OPS_SOURCES = ["vt_ops.hip"]          # libvittrack_hip_ops.so only
 HEADER = os.path.join(PKG, "..", "include", "vittrack_hip.h")
@@ -50,7 +50,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
              "-Wno-unused-function"]
 # fused multiply-add allowed where no bit-exact float spec applies (MFMA kernels' epilogues and
 # softmax); the pixel stage and the box decode keep one IEEE operation per source operation
-FAST_CONTRACT = {"k_gemm.hip", "k_gemm256.hip", "k_attn.hip"}     # not k_head.hip, k_peaks.hip, k_result_overlay.hip, k_motion.hip, k_appearance.hip, k_proposals.hip, k_camera_motion.hip, k_conflicts.hip: the decode, the motion rule, the appearance crop and sums, the proposals' thumbnail, the camera shift and the conflicts' IoU keep one IEEE operation per source operation
+FAST_CONTRACT = {"k_gemm.hip", "k_gemm256.hip", "k_attn.hip"}     # not k_head.hip, k_peaks.hip, k_result_overlay.hip, k_motion.hip, k_appearance.hip, k_proposals.hip, k_camera_motion.hip, k_conflicts.hip, k_arbitrate.hip: the decode, the motion rule, the appearance crop and sums, the proposals' thumbnail, the camera shift, the conflicts' IoU and the arbitration's lists, crops and sums keep one IEEE operation per source operation
 # k_gemm256.hip: hipcc's SLP vectoriser packs the last FMA of the GELU epilogue into v_pk_fma_f32,
 # which has no |x| modifier, so it also emits one v_or per element to build -|x| (and a packed f32
 # op issues at the rate of two scalar ones on CDNA4): 8 % more epilogue VALU for nothing
@@ -102,6 +102,7 @@ def build_hip(force: bool = False, save_temps: bool = False, stamps: bool = Fals
     headers = [os.path.join(CSRC, "vt_common.hpp"), os.path.join(CSRC, "k_gemm_util.hpp"), os.path.join(CSRC, "vt_engine.hpp"), os.path.join(CSRC, "k_cand.hpp"), os.path.join(CSRC, "k_snapshot.hpp"),
                os.path.join(CSRC, "k_preproc_dev.hpp"), os.path.join(CSRC, "k_thumb_dev.hpp"), os.path.join(CSRC, "k_overlay_dev.hpp"), os.path.join(CSRC, "k_result_overlay.hpp"), os.path.join(CSRC, "k_preproc_body.inc"),
                os.path.join(CSRC, "k_refresh_dev.hpp"), os.path.join(CSRC, "k_refresh_crop.inc"),
+               os.path.join(CSRC, "k_peaks_dev.hpp"), os.path.join(CSRC, "k_appearance_dev.hpp"),
                os.path.join(CSRC, "vt_ops_host.hpp"), os.path.join(CSRC, "vt_ops_util.hpp"), os.path.join(CSRC, "vt_feature_keys.hpp"),
                os.path.join(PKG, "..", "include", "vittrack_hip.h"), os.path.join(PKG, "..", "include", "vittrack_hip_ops.h")]
     objs, jobs = [], []

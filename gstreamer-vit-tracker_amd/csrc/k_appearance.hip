@@ -19,11 +19,13 @@
 // butterfly 32, 16, 8, 4, 2, 1; the 4 waves in index order; the chunk partials go to global memory and the slot's
 // last-arriving workgroup (the ticket pattern of k_refresh.hip) adds them in chunk order. No floating-point atomics: the
 // record is a function of the inputs alone, whichever workgroup arrives last - pipelined == synchronous, bit for bit.
-// Pad columns (cols..kpad) are never read.
+// Pad columns (cols..kpad) are never read. The summation's text is k_appearance_dev.hpp's, which the score launch of the peak
+// arbitration (k_arbitrate.hip) shares.
 //
 // Compiled like k_refresh.hip (-ffp-contract=off): one IEEE operation per source operation.
 #include "vt_common.hpp"
 #include "k_refresh_dev.hpp"
+#include "k_appearance_dev.hpp"
 
 // the stream's record, on the device and - final records only - in the pinned mirror of the pass
 __device__ __forceinline__ void appear_store(const AppearArgs& a, int stream, const AppearRec& rec, bool mirror) {
@@ -93,12 +95,6 @@ hipError_t launch_appearance_probe(const AppearArgs& a, const ModelDims& d, int 
     return hipGetLastError();
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void appearance_score_kernel(AppearArgs a, int nt, int cols, int kpad) {
     __shared__ double wsum[4][5];
     const int slot = blockIdx.y, chunk = blockIdx.x, nch = gridDim.x;
@@ -108,50 +104,21 @@ __global__ __launch_bounds__(256) void appearance_score_kernel(AppearArgs a, int
     // reads the status in front of its own: all of them decide alike.
     if (a.recs[stream].status != 1) return;
     const int r0 = chunk * VT_APPEAR_CHUNK_ROWS, r1 = min(nt, r0 + VT_APPEAR_CHUNK_ROWS);
-    const int cnt = (r1 - r0) * cols;
     const bf16_t* __restrict__ A = a.anchor + (size_t)stream * nt * kpad + (size_t)r0 * kpad;
     const bf16_t* __restrict__ P = a.probe + (size_t)stream * nt * kpad + (size_t)r0 * kpad;
-    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < cnt; i += 256) {
-        const int rr = i / cols, c = i - rr * cols;
-        const size_t o = (size_t)rr * kpad + c;
-        const double x = (double)bf16_to_f32(A[o]), y = (double)bf16_to_f32(P[o]);
-        s[0] = s[0] + x;
-        s[1] = s[1] + y;
-        s[2] = s[2] + x * x;
-        s[3] = s[3] + y * y;
-        s[4] = s[4] + x * y;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) s[k] = wave_sum_f64(s[k]);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) wsum[wave][k] = s[k];
-    __syncthreads();
+    double part_sums[5];
+    appear_chunk_sums(A, P, r1 - r0, cols, kpad, wsum, part_sums);      // k_appearance_dev.hpp: the fixed order
     if (threadIdx.x != 0) return;
     double* part = a.partials + ((size_t)slot * nch + chunk) * 5;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) part[k] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+    for (int k = 0; k < 5; ++k) part[k] = part_sums[k];
     const unsigned arrived = __hip_atomic_fetch_add(a.tickets + slot, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (arrived != (unsigned)nch - 1) return;
     // ---- the slot's last workgroup: the chunks in index order, the similarity, the record ----
-    double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    const double* all = a.partials + (size_t)slot * nch * 5;
-    for (int c = 0; c < nch; ++c)
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            t[k] = t[k] + __hip_atomic_load(all + (size_t)c * 5 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double n = (double)nt * (double)cols;
-    const double cov = t[4] - t[0] * t[1] / n;
-    const double va = t[2] - t[0] * t[0] / n;
-    const double vp = t[3] - t[1] * t[1] / n;
-    const bool ok = va > 0.0 && vp > 0.0;
-    double sim = ok ? cov / sqrt(va * vp) : 0.0;
-    sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
+    double t[5];
+    appear_add_chunks(a.partials + (size_t)slot * nch * 5, nch, t);
     AppearRec rec = a.recs[stream];
-    rec.status = ok ? 1 : 3;
-    rec.similarity = (float)sim;
+    rec.status = appear_similarity(t, nt, cols, &rec.similarity) ? 1 : 3;
     if (a.counts) a.counts[stream].evaluated += 1;
     if (a.sums)
 #pragma unroll

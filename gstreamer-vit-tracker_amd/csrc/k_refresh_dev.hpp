@@ -1,5 +1,6 @@
-// k_refresh_dev.hpp — what the launches that cut a template-sized crop at the committed box share: the template refresh
-// (k_refresh.hip) and the appearance probe (k_appearance.hip). The ONE text of refresh rules 1, 3, 4 (the policy's part of
+// k_refresh_dev.hpp — what the launches that cut a template-sized crop at a box of the pass share: the template refresh
+// (k_refresh.hip), the appearance probe (k_appearance.hip) and the peak arbitration (k_arbitrate.hip: rules 6 and 7 in its list
+// launch, the launch table in its probe launch). The ONE text of refresh rules 1, 3, 4 (the policy's part of
 // the gate), of rules 6 and 7 (the geometry: DESIGN.md section 3, "Template refresh"), of the window-miss mark a rule-7
 // failure leaves, and of the launch table that picks a crop body as launch_preproc picks it for the template. The crop
 // itself is the text of k_refresh_crop.inc around the crop kernels' bodies (k_preproc_body.inc).

@@ -583,6 +583,20 @@ int Engine::run_pass(Profiler* prof, const PassShape& ps) {
     }
     if (ps.cand)
         L("cand_commit", 0, 2.0 * n * sizeof(StreamState), [&] { return launch_cand_commit(*ps.cand, stream); });
+    if (arb_capable) {      // directly behind the decode / the commit: everything below reads the box the arbitration left (k_arbitrate.hip)
+        ArbArgs aa{};
+        aa.head_out = d_headout; aa.hann = dec.hann; aa.frames = d_frames; aa.states = d_states; aa.results = d_results;
+        aa.slot_stream = slot_stream; aa.winner = ps.cand ? ps.cand->winner : nullptr; aa.policy = d_arb_policy();
+        aa.recs = d_arb_recs(); aa.counts = d_arb_counts(); aa.tickets = d_arb_tickets(); aa.partials = d_arb_partials();
+        aa.anchor = d_anchor(); aa.probe = d_arb_probe(); aa.out = (const PassOut*)(d_frames + B);
+        aa.host_states = ps.cand ? ps.cand->host_states : nullptr;
+        aa.n = n; aa.ns = d.ns; aa.grid = d.gs; aa.success_threshold = success_threshold;
+        const int cols = 3 * d.patch * d.patch;
+        L("arbitrate_list", 0, (double)n * (d.ns * 8.0 * 4 + sizeof(StreamState) + sizeof(ArbRec)), [&] { return launch_arbitrate_list(aa, d, stream); });
+        L("arbitrate_probe", 0, 0, [&] { return launch_arbitrate_probe(aa, d, ps.tier, ps.any_layout, stream); });
+        L("arbitrate_score", 0, 0, [&] { return launch_arbitrate_score(aa, d.nt, cols, d.kpad, stream); });
+        L("arbitrate_commit", 0, (double)n * 2.0 * sizeof(ArbRec), [&] { return launch_arbitrate_commit(aa, stream); });
+    }
     if (motion_capable)     // ahead of everything that reads the new box: the velocity, the coast or the restore
         L("motion_settle", 0, (double)n * (sizeof(StreamState) + sizeof(vt_result) + 3.0 * sizeof(MotionRec)),
           [&] { return launch_motion_settle(ma, stream); });
@@ -809,6 +823,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     if (int rc = zero_motion(b)) return rc;
     if (int rc = zero_conflicts(b)) return rc;
     if (int rc = zero_health(b)) return rc;
+    if (int rc = zero_arbitrate(b)) return rc;
     to_desc(*f, h_desc);
     // entry b of the per-pass block: every pass uploads its own block ahead of its kernels, in stream order
     HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));

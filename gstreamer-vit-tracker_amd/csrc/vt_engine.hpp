@@ -400,6 +400,34 @@ struct Engine {
     // stream b without a previous thumbnail, still 0, a zero record, on the device (behind the stream's work) and in the
     // engine's mirror: wherever zero_conflicts is called for a stream that starts anew
     int zero_health(int b);
+    // peak arbitration (k_arbitrate.hip). ONE policy per engine; per stream a record, two counters and four probes of template
+    // rows, per (slot, peak) a ticket and the score launch's chunk partials. The first non-zero "arbitrate" - refused unless the
+    // engine is appearance-capable: the anchors are the appearance store's - allocates all of it and makes the engine
+    // arbitration-capable for good: every pass runs the four launches directly behind decode / cand_commit, ahead of
+    // motion_settle, so that everything that reads the new box reads the final one.
+    bool arb_capable = false;
+    ArbPolicy arb_policy = VT_ARB_DEFAULT_POLICY;       // the host's copy
+    // ONE allocation: the policy | [B] records | [B] counters | [4B] tickets | [4B][chunks][5] partials | [B][4][nt][kpad] probes,
+    // zero up to the probes
+    uint8_t* d_arb = nullptr;
+    static size_t arb_off_recs() { return 64; }
+    size_t arb_off_counts() const { return arb_off_recs() + sizeof(ArbRec) * (size_t)B; }
+    size_t arb_off_tickets() const { return arb_off_counts() + sizeof(ArbCount) * (size_t)B; }
+    size_t arb_off_partials() const { return (arb_off_tickets() + sizeof(unsigned) * VT_ARB_MAX * (size_t)B + 63) & ~(size_t)63; }
+    size_t arb_off_probe() const { return (arb_off_partials() + sizeof(double) * 5 * VT_ARB_MAX * (size_t)B * appear_chunks(d.nt) + 63) & ~(size_t)63; }
+    size_t arb_bytes() const { return arb_off_probe() + sizeof(bf16_t) * VT_ARB_MAX * appear_rows() * (size_t)B; }
+    ArbPolicy* d_arb_policy() const { return reinterpret_cast<ArbPolicy*>(d_arb); }
+    ArbRec* d_arb_recs() const { return reinterpret_cast<ArbRec*>(d_arb + arb_off_recs()); }
+    ArbCount* d_arb_counts() const { return reinterpret_cast<ArbCount*>(d_arb + arb_off_counts()); }
+    unsigned* d_arb_tickets() const { return reinterpret_cast<unsigned*>(d_arb + arb_off_tickets()); }
+    double* d_arb_partials() const { return reinterpret_cast<double*>(d_arb + arb_off_partials()); }
+    bf16_t* d_arb_probe() const { return reinterpret_cast<bf16_t*>(d_arb + arb_off_probe()); }
+    // pinned [B] by stream: the records of the last passes the host collected - what "arbitrate" of vt_group_read_tensor reports
+    ArbRec* h_arb_all = nullptr;
+#define VT_ARB_STATS 48
+    int arbitrate_stats(int stream, float* out48);
+    // stream b's record zeroed on the device (behind the stream's work) and in the engine's mirror: wherever zero_health is called
+    int zero_arbitrate(int b);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -452,7 +480,7 @@ struct Engine {
     // h_motion_all, h_appear_all, h_prop_all, h_conflict_all and h_health_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
     // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them. The
     // optional ones are the rows of ONE list (vt_features.hip: kSinks), which everything below walks.
-    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_CONFLICT = 32, SINK_HEALTH = 64, SINK_ALL = 127 };
+    enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_CONFLICT = 32, SINK_HEALTH = 64, SINK_ARB = 128, SINK_ALL = 255 };
     unsigned sink_members() const;      // SINK_BASE and the sinks of the features the engine is capable of
     // what a pass's block carries of `to` (null: of the engine's own): host_states only with by_stream_states, an optional member only on a capable engine
     PassOut pass_sinks(const PassOut* to, bool by_stream_states) const;
@@ -600,7 +628,7 @@ struct KeyedFeature {
     const char* action_key = nullptr; int (Engine::*action)(int value) = nullptr;       // a key that is an action, not a field, and what it does
     int (*refuse_enable)(Engine*) = nullptr;    // a reason this engine cannot enable at all
 };
-const std::array<KeyedFeature, 6>& keyed_features();
+const std::array<KeyedFeature, 7>& keyed_features();
 
 // zero-filled device buffer. The fill is ordered on the ENGINE's stream: that stream is non-blocking, so a
 // hipMemset on the null stream (asynchronous for device memory) is not ordered against the kernels the

@@ -165,4 +165,20 @@ inline Answer apply_health(const char* key, int value, const int32_t* def, int32
     }
     return apply(kHealthKeys, key, value, def, words, text, cap);
 }
+
+// peak arbitration (k_arbitrate.hip): the "arbitrate*" keys; vt_op_arbitrate validates its policy words with the same table.
+// Six keys and two reserved words; the kernels form each threshold as (float)pm / 1000.0f - the text of tau_of -
+// so no derived word is stored
+enum { AR_ON, AR_MAX, AR_RADIUS, AR_MIN_RESP_PM, AR_LOW_PM, AR_HIGH_PM, AR_WORDS = 8 };      // ArbPolicy
+static constexpr Key kArbKeys[] = {
+    {"arbitrate", AR_ON, 0, 1, "arbitrate: %d (0: off, 1: on)"},
+    {"arbitrate_max", AR_MAX, 2, 4, "arbitrate_max: %d (2..4)"},
+    {"arbitrate_radius", AR_RADIUS, 1, 4, "arbitrate_radius: %d (1..4)"},
+    {"arbitrate_min_resp_pm", AR_MIN_RESP_PM, 0, 1000, "arbitrate_min_resp_pm: %d (0..1000)"},
+    {"arbitrate_low_pm", AR_LOW_PM, 0, 1000, "arbitrate_low_pm: %d (0..1000)"},
+    {"arbitrate_high_pm", AR_HIGH_PM, 0, 1000, "arbitrate_high_pm: %d (0..1000)"},
+};
+inline Answer apply_arbitrate(const char* key, int value, const int32_t* def, int32_t* words, bool, char* text, size_t cap) {
+    return apply(kArbKeys, key, value, def, words, text, cap);
+}
 }   // namespace vtkeys

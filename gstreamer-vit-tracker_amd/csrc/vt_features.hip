@@ -1,4 +1,4 @@
-// vt_features.hip — host side of the nine optional in-the-pass features of an Engine
+// vt_features.hip — host side of the ten optional in-the-pass features of an Engine
 #include "vt_engine.hpp"
 
 // ---- the first enable of an optional feature -------------------------------------------------------------
@@ -47,6 +47,7 @@ static const Sink kSinks[] = {      // the casts: every member is a pointer to r
     {Engine::SINK_PROP, sizeof(PropRec), true, (void* PassOut::*)&PassOut::host_proposals, (void* Engine::*)&Engine::h_prop_all, &Engine::prop_capable},
     {Engine::SINK_CONFLICT, sizeof(ConflictRec), true, (void* PassOut::*)&PassOut::host_conflicts, (void* Engine::*)&Engine::h_conflict_all, &Engine::conflict_capable},
     {Engine::SINK_HEALTH, sizeof(HealthRec), true, (void* PassOut::*)&PassOut::host_health, (void* Engine::*)&Engine::h_health_all, &Engine::health_capable},
+    {Engine::SINK_ARB, sizeof(ArbRec), true, (void* PassOut::*)&PassOut::host_arbitrate, (void* Engine::*)&Engine::h_arb_all, &Engine::arb_capable},
 };
 
 static hipError_t pinned0(void** p, size_t bytes) {
@@ -79,7 +80,7 @@ unsigned Engine::sink_members() const {
 }
 
 PassOut Engine::pass_sinks(const PassOut* to, bool by_stream_states) const {
-    PassOut o{to ? to->host_results : h_results, !by_stream_states ? nullptr : to ? to->host_states : h_states_all, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PassOut o{to ? to->host_results : h_results, !by_stream_states ? nullptr : to ? to->host_states : h_states_all, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (const Sink& s : kSinks)
         if (this->*s.capable) o.*s.in = to ? to->*s.in : this->*s.own;
     return o;
@@ -124,6 +125,7 @@ int Engine::enable_store(const char* name, size_t bytes, size_t zeroed, const vo
 int Engine::reset_refresh_tickets() {
     if (d_tickets) HIPCHK(hipMemsetAsync(d_tickets, 0, sizeof(unsigned) * (size_t)B, stream));
     if (appear_capable) HIPCHK(hipMemsetAsync(d_appear_tickets(), 0, sizeof(unsigned) * (size_t)B, stream));
+    if (arb_capable) HIPCHK(hipMemsetAsync(d_arb_tickets(), 0, sizeof(unsigned) * VT_ARB_MAX * (size_t)B, stream));
     return VT_OK;
 }
 
@@ -543,6 +545,35 @@ int Engine::health_words(int s, float* out) {
     return VT_OK;
 }
 
+// ---- peak arbitration -----------------------------------------------------------------------------------
+
+int Engine::zero_arbitrate(int b) {
+    if (!arb_capable) return VT_OK;
+    HIPCHK(hipMemsetAsync(d_arb_recs() + b, 0, sizeof(ArbRec), stream));
+    h_arb_all[b] = ArbRec{};            // the stream is in no outstanding pass: nothing else writes its entry
+    return VT_OK;
+}
+
+// [48]: the flag, status, frames_done, n, chosen, evaluated, switched, 0; then four peaks of cell, status, score, response,
+// similarity, the float box x, y, w, h, 0. Every value is exact in binary32 (cells, counts and statuses are small integers)
+int Engine::arbitrate_stats(int s, float* out) {
+    if (!arb_capable)
+        return set_err(VT_ERR_INVALID_ARG, "peak arbitration: not enabled on this engine (vt_group_set_tuning \"arbitrate\")");
+    // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counters: the device's
+    const ArbRec r = h_arb_all[s];
+    ArbCount c{};
+    HIPCHK(hipMemcpy(&c, d_arb_counts() + s, sizeof(c), hipMemcpyDeviceToHost));
+    float v[VT_ARB_STATS] = {(float)arb_policy.on, (float)r.status, (float)r.frames_done, (float)r.n, (float)r.chosen, (float)c.evaluated,
+                             (float)c.switched, 0.0f};
+    for (int k = 0; k < VT_ARB_MAX; ++k) {
+        const ArbPeak& p = r.peak[k];
+        const float w[10] = {(float)p.cell, (float)p.status, p.score, p.resp, p.similarity, p.box[0], p.box[1], p.box[2], p.box[3], 0.0f};
+        memcpy(v + 8 + 10 * k, w, sizeof(w));
+    }
+    memcpy(out, v, sizeof(v));
+    return VT_OK;
+}
+
 // ---- the keyed features: ONE list, ONE setter -----------------------------------------------------------
 using namespace vtkeys;
 
@@ -582,15 +613,30 @@ static int health_changed(Engine* e, const char* key, const int32_t* words) {
     memset(e->h_health_all, 0, sizeof(HealthRec) * (size_t)e->B);
     return VT_OK;
 }
+static_assert(sizeof(ArbPolicy) == 4 * AR_WORDS && at(offsetof(ArbPolicy, on), AR_ON) && at(offsetof(ArbPolicy, max_peaks), AR_MAX) &&
+              at(offsetof(ArbPolicy, radius), AR_RADIUS) && at(offsetof(ArbPolicy, min_resp_pm), AR_MIN_RESP_PM) && at(offsetof(ArbPolicy, low_pm), AR_LOW_PM) &&
+              at(offsetof(ArbPolicy, high_pm), AR_HIGH_PM) && kArbKeys[AR_MAX].hi == VT_ARB_MAX && AR_WORDS <= kMaxWords, "ArbPolicy");
+// "arbitrate" 0 on a capable engine zeroes every stream's record, on the device and in the host's copy
+static int arb_changed(Engine* e, const char* key, const int32_t* words) {
+    if (strcmp(key, "arbitrate") != 0 || words[AR_ON] != 0) return VT_OK;
+    HIPCHK(hipMemset(e->d_arb_recs(), 0, sizeof(ArbRec) * (size_t)e->B));
+    memset(e->h_arb_all, 0, sizeof(ArbRec) * (size_t)e->B);
+    return VT_OK;
+}
+// the anchors are the appearance store's
+static int arb_refuse(Engine* e) {
+    return e->appear_capable ? VT_OK
+                             : set_err(VT_ERR_INVALID_ARG, "arbitrate: the engine is not appearance-capable (vt_group_set_tuning \"appearance\" first: the anchors are the appearance store's)");
+}
 static int proposals_refuse(Engine* e) {
     return prop_pattern_side(e->d.T) ? VT_OK : set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", e->d.T);
 }
 
 // The stores: overlay the policy | [B] counters, motion the policy | [B] records (zero like known_motion, which nothing writes
 // before the engine is capable), appearance all zero but the policy and the anchors of the initialised streams, proposals
-// sized by the max_cells of the enable and zero up to the thumbnails, conflicts all zero but the policy (every stream in scene 0), health sized by the max_cells of the enable and zero up to the thumbnails. The casts: a policy is words from its first member on.
-const std::array<KeyedFeature, 6>& keyed_features() {
-    static const std::array<KeyedFeature, 6> list = {{
+// sized by the max_cells of the enable and zero up to the thumbnails, conflicts all zero but the policy (every stream in scene 0), health sized by the max_cells of the enable and zero up to the thumbnails, arbitration all zero but the policy up to the probes. The casts: a policy is words from its first member on.
+const std::array<KeyedFeature, 7>& keyed_features() {
+    static const std::array<KeyedFeature, 7> list = {{
         {"result overlay", "result_overlay", apply_overlay, (int32_t Engine::*)&Engine::overlay_policy, OV_WORDS, OV_FLAGS, &Engine::overlay_capable,
          &Engine::d_overlay, &Engine::overlay_bytes, nullptr, 0, "result_overlay", 6, &Engine::overlay_stats},
         {"motion prior", "motion_", apply_motion, (int32_t Engine::*)&Engine::motion_policy, MO_WORDS, MO_ON, &Engine::motion_capable,
@@ -607,6 +653,9 @@ const std::array<KeyedFeature, 6>& keyed_features() {
         {"frame health", "health", apply_health, (int32_t Engine::*)&Engine::health_policy, HL_WORDS, HL_ON, &Engine::health_capable,
          &Engine::d_health, &Engine::health_bytes, &Engine::health_off_thumbs, Engine::SINK_HEALTH, "health", VT_HEALTH_STATS, &Engine::health_stats,
          health_changed},
+        {"peak arbitration", "arbitrate", apply_arbitrate, (int32_t Engine::*)&Engine::arb_policy, AR_WORDS, AR_ON, &Engine::arb_capable,
+         &Engine::d_arb, &Engine::arb_bytes, &Engine::arb_off_probe, Engine::SINK_ARB, "arbitrate", VT_ARB_STATS, &Engine::arbitrate_stats,
+         arb_changed, nullptr, nullptr, nullptr, arb_refuse},
     }};
     return list;
 }

@@ -877,6 +877,101 @@ int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int
     return VT_OK;
 } VT_NOTHROW_INT
 
+// The four launches of the peak arbitration on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_arbitrate_list, _probe, _score and _commit, in that order. Every array a launch may write sits between guard bands;
+// records, probe rows and partials start as 0xff bytes, the tickets as zeros, the others as the caller's.
+int vt_op_arbitrate(int device_id, const float* head_out, const float* hann, const vt_frame* frames, void* states, int n_streams,
+                    vt_result* results, const int32_t* slot_stream, const int32_t* winner, int n, int grid, const uint16_t* anchor,
+                    int T, int S, int patch, int kpad, const float* norm, float success_threshold, const int32_t* policy, int tier,
+                    void* records, int32_t* counts, uint16_t* probe, vt_result* host_results, void* host_states,
+                    void* host_records) try {
+    if (!head_out || !hann || !frames || !states || !results || !anchor || !norm || !policy || !records || !counts || !probe || n < 1 ||
+        n > VT_MAX_STREAMS || n_streams < 1 || n_streams > VT_MAX_STREAMS || grid < 1 || grid > 110 || patch < 1 || T < patch ||
+        T % patch != 0 || S < T || kpad < 3 * patch * patch || kpad > 65536 || tier < 0 || tier > 2)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "arbitrate: %d streams for %d slots", n_streams, n);
+    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here, in its words
+    static_assert(sizeof(ArbPolicy) == 4 * vtkeys::AR_WORDS && vtkeys::kArbKeys[1].hi == VT_ARB_MAX, "ArbPolicy");
+    const ArbPolicy def = VT_ARB_DEFAULT_POLICY;
+    int32_t words[vtkeys::kMaxWords] = {};
+    for (const vtkeys::Key& k : vtkeys::kArbKeys) {
+        char text[256];
+        if (policy[k.word] < 0 || vtkeys::apply_arbitrate(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false, text,
+                                                         sizeof(text)) != vtkeys::ACCEPTED)
+            return set_err(VT_ERR_INVALID_ARG, "arbitrate: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
+    }
+    ArbPolicy pol;
+    memcpy(&pol, words, sizeof(pol));
+    std::vector<FrameDesc> desc((size_t)n);
+    SlotMaps maps{slot_stream, winner, n, n_streams};
+    for (int b = 0; b < n; ++b) {
+        if (int rc = check_frame(frames[b])) return rc;
+        to_desc(frames[b], &desc[(size_t)b]);
+        if (int rc = maps.check("arbitrate", b)) return rc;
+    }
+    // outside a candidate pass a stream has ONE slot (every pass of the engine is built so): two slots of one stream would
+    // write the same record, state and counters from two workgroups
+    if (!winner && slot_stream) {
+        std::vector<char> named((size_t)n_streams, 0);
+        for (int b = 0; b < n; ++b) {
+            if (named[(size_t)slot_stream[b]]) return set_err(VT_ERR_INVALID_ARG, "arbitrate: stream %d is named by two slots", (int)slot_stream[b]);
+            named[(size_t)slot_stream[b]] = 1;
+        }
+    }
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    ModelDims d{};
+    d.T = T; d.S = S; d.patch = patch; d.gt = T / patch; d.nt = d.gt * d.gt; d.kpad = kpad;
+    for (int c = 0; c < 3; ++c) { d.norm_a[c] = norm[c]; d.norm_b[c] = norm[3 + c]; }
+    const int ns = grid * grid, cols = 3 * patch * patch;
+    const size_t nn = (size_t)n, nst = (size_t)n_streams, rows = (size_t)d.nt * kpad * sizeof(bf16_t);
+    const size_t sb = nst * sizeof(StreamState), rb = nst * sizeof(ArbRec), resb = nn * sizeof(vt_result);
+    const size_t pairs = nn * VT_ARB_MAX, nch = (size_t)appear_chunks(d.nt);
+    std::vector<unsigned> ticks(pairs);
+    DevArr dho, dhann, dfr, dpol, danchor, dpo;
+    GuardedOut gst, gres, grec, gcnt, gprobe, gtick, gpart;
+    PinnedBuf hres, hst, hrec;
+    HIPCHK(dho.upload(head_out, nn * ns * 8 * 4)); HIPCHK(dhann.upload(hann, (size_t)ns * 4));
+    HIPCHK(dfr.upload(desc.data(), nn * sizeof(FrameDesc))); HIPCHK(dpol.upload(&pol, sizeof(pol)));
+    HIPCHK(danchor.upload(anchor, nst * rows));
+    HIPCHK(gst.upload(states, sb)); HIPCHK(gres.upload(results, resb)); HIPCHK(grec.alloc(rb));
+    HIPCHK(gcnt.upload(counts, nst * sizeof(ArbCount))); HIPCHK(gprobe.alloc(nst * VT_ARB_MAX * rows));
+    HIPCHK(gtick.alloc(pairs * sizeof(unsigned), 0));
+    HIPCHK(gpart.alloc(pairs * nch * 5 * sizeof(double)));      // NaN: a partial nobody wrote would show
+    if (host_results) { HIPCHK(hres.alloc(resb)); memcpy(hres.p, host_results, resb); }
+    if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
+    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    const PassOut po{(vt_result*)hres.p, (StreamState*)hst.p};
+    HIPCHK(dpo.upload(&po, sizeof(po)));
+    HIPCHK(maps.upload());
+    ArbArgs a{};
+    a.head_out = dho.as<const float>(); a.hann = dhann.as<const float>(); a.frames = dfr.as<const FrameDesc>();
+    a.states = gst.as<StreamState>(); a.results = gres.as<vt_result>(); a.slot_stream = maps.dev_slot_stream();
+    a.winner = maps.dev_winner(); a.policy = dpol.as<const ArbPolicy>(); a.recs = grec.as<ArbRec>(); a.counts = gcnt.as<ArbCount>();
+    a.tickets = gtick.as<unsigned>(); a.partials = gpart.as<double>(); a.anchor = danchor.as<const bf16_t>();
+    a.probe = gprobe.as<bf16_t>(); a.out = dpo.as<const PassOut>(); a.host_recs = (ArbRec*)hrec.p;
+    a.n = n; a.ns = ns; a.grid = grid; a.success_threshold = success_threshold;
+    int level = 0;
+    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
+    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(launch_arbitrate_list(a, d, nullptr));
+    HIPCHK(launch_arbitrate_probe(a, d, tier, level, nullptr));
+    HIPCHK(launch_arbitrate_score(a, d.nt, cols, kpad, nullptr));
+    HIPCHK(launch_arbitrate_commit(a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("arbitrate", {{&gst, "states"}, {&gres, "results"}, {&grec, "records"}, {&gcnt, "counters"},
+                                             {&gprobe, "probe rows"}, {&gtick, "tickets"}, {&gpart, "partials"}})) return rc;
+    HIPCHK(gtick.download(ticks.data()));
+    for (size_t i = 0; i < pairs; ++i)
+        if (ticks[i] != 0) return set_err(VT_ERR_HIP, "arbitrate: slot %zu, peak %zu left its ticket at %u", i / VT_ARB_MAX, i % VT_ARB_MAX, ticks[i]);
+    HIPCHK(gst.download(states)); HIPCHK(gres.download(results)); HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
+    HIPCHK(gprobe.download(probe));
+    if (host_results) memcpy(host_results, hres.p, resb);
+    if (host_states) memcpy(host_states, hst.p, sb);
+    if (host_records) memcpy(host_records, hrec.p, rb);
+    return VT_OK;
+} VT_NOTHROW_INT
+
 // The four launches of the frame health on given operands: see include/vittrack_hip_ops.h. Nothing runs but
 // launch_health_prepare, _thumb, _measure and _decide, in that order. Every array the launches may write sits between guard
 // bands; headers and accumulators start as 0xff bytes, the others as the caller's.

@@ -279,6 +279,7 @@ static int snap_import(Engine* e, int t, const StreamState& st, const RefreshPol
     if (he != hipSuccess) return set_err(VT_ERR_HIP, "snapshot unpack: %s", hipGetErrorString(he));
     if (int rc = e->zero_motion(t)) return rc;          // no part of a snapshot: the imported stream starts without a velocity
     if (int rc = e->zero_conflicts(t)) return rc;       // nor is the conflict record (the stream's scene stays: policy, not state)
+    if (int rc = e->zero_arbitrate(t)) return rc;       // nor the arbitration record
     if (int rc = e->zero_health(t)) return rc;          // nor a thumbnail: the imported stream starts without a previous one
     HIPCHK(e->anchor_from_template(t, st.tpl_gen));     // nor is the appearance anchor: the imported rows become it
     if (!pipelined) HIPCHK(hipStreamSynchronize(e->stream));    // synchronous, like vt_group_init_device

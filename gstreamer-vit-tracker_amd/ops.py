@@ -24,7 +24,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
     "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_camera_motion", "vt_op_ln_chain_bf16",
-    "vt_op_stream_conflicts", "vt_op_frame_health",
+    "vt_op_stream_conflicts", "vt_op_frame_health", "vt_op_arbitrate",
 ]
 
 _ops = None
@@ -70,6 +70,9 @@ def ops_lib():
                                       c_void_p, c_void_p, c_void_p]
     L.vt_op_frame_health.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]
+    L.vt_op_arbitrate.argtypes = [c_int, fp, fp, POINTER(CFrame), c_void_p, c_int, c_void_p, i32p, i32p, c_int, c_int, c_void_p,
+                                  c_int, c_int, c_int, c_int, fp, c_float, i32p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]
     L.vt_op_stream_conflicts.argtypes = [c_int, c_void_p, c_int, c_void_p, i32p, i32p, c_int, i32p, i32p, c_void_p, c_void_p,
                                          c_void_p]
     L.vt_op_result_overlay.argtypes = [c_int, POINTER(CFrame), c_void_p, i32p, i32p, c_int, c_void_p, c_void_p,
@@ -544,6 +547,58 @@ def op_frame_health(frames, states, on=1, period=1, cell=0, still_run=3, flat_q=
         device, arr, _vp(st), ns, _opt(smap, _i32), n, _i32(pol), 1 if device_frames else 0, _vp(th), _vp(accs), _vp(hi),
         _vp(heads), _vp(rec), _vp(cnt), _opt(hrec, _vp)))
     return dict(states=st, thumbs=th, hist=hi, records=rec, counts=cnt, accs=accs, heads=heads, host_records=hrec)
+
+
+# the peak arbitration's records (csrc/vt_common.hpp: ArbRec 176 bytes and ArbCount 8 bytes, both by stream)
+ARBITRATE_PEAK_DTYPE = np.dtype([("cell", "<i4"), ("status", "<i4"), ("score", "<f4"), ("resp", "<f4"), ("similarity", "<f4"),
+                                 ("reserved", "<i4"), ("box", "<f4", 4)])
+ARBITRATE_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n", "<i4"), ("chosen", "<i4"),
+                                ("peak", ARBITRATE_PEAK_DTYPE, 4)])
+ARBITRATE_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("switched", "<i4")])
+
+
+def op_arbitrate(head_out, hann, frames, states, results, anchor, grid, T, S, patch, norm, success_threshold, on=1, max_peaks=3,
+                 radius=2, min_resp_pm=50, low_pm=300, high_pm=500, slot_stream=None, winner=None, counts=None, tier=0,
+                 host_results=None, host_states=None, host_records=None, device=0):
+    """vt_op_arbitrate: the four launches of k_arbitrate.hip on given operands, nothing else. head_out [n * grid^2][8] float32
+    logits by slot, hann [grid^2], frames: CFrame per slot with DEVICE planes; states: snapshot.STATE records by stream;
+    results [n] RESULT_DTYPE by slot; anchor [n_streams, nt, kpad] uint16 bf16 bit patterns; norm: (a0, a1, a2, b0, b1, b2);
+    slot_stream [n]: slot -> stream (None: the identity); winner [n]: not None marks a candidate pass; counts [n_streams]
+    ARBITRATE_COUNT_DTYPE to start from (None: zeros); host_*: what the pinned mirrors hold before (None: that mirror is null).
+    -> dict(states, results, records [n_streams] ARBITRATE_REC_DTYPE, probe [n_streams, 4, nt, kpad] uint16 - both 0xff bytes
+    where no launch stored -, counts, host_results, host_states, host_records) as they came back"""
+    n = len(frames)
+    arr = (CFrame * n)(*frames)
+    ns = grid * grid
+    ho = np.ascontiguousarray(head_out, np.float32)
+    assert ho.shape == (n * ns, 8)
+    hn = np.ascontiguousarray(hann, np.float32).reshape(-1)
+    assert hn.shape == (ns,)
+    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    nst = len(st)
+    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1).copy()
+    assert res.shape == (n,)
+    an = np.ascontiguousarray(anchor, np.uint16)
+    nt = (T // patch) ** 2
+    assert an.ndim == 3 and an.shape[:2] == (nst, nt)
+    kpad = an.shape[2]
+    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
+    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
+    nrm = np.ascontiguousarray(norm, np.float32).reshape(6)
+    pol = np.array([on, max_peaks, radius, min_resp_pm, low_pm, high_pm, 0, 0], np.int32)
+    rec = np.empty(nst, ARBITRATE_REC_DTYPE)
+    cnt = np.zeros(nst, ARBITRATE_COUNT_DTYPE) if counts is None else np.ascontiguousarray(counts, ARBITRATE_COUNT_DTYPE).reshape(-1).copy()
+    probe = np.empty((nst, 4, nt, kpad), np.uint16)
+    hres = None if host_results is None else np.ascontiguousarray(host_results, RESULT_DTYPE).reshape(-1).copy()
+    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
+    hrec = None if host_records is None else np.ascontiguousarray(host_records, ARBITRATE_REC_DTYPE).reshape(-1).copy()
+    assert len(cnt) == nst and (hres is None or len(hres) == n) and (hst is None or len(hst) == nst) and (hrec is None or len(hrec) == nst)
+    assert ARBITRATE_REC_DTYPE.itemsize == 176
+    _check_op(ops_lib().vt_op_arbitrate(
+        device, _f32(ho), _f32(hn), arr, _vp(st), nst, _vp(res), _opt(smap, _i32), _opt(win, _i32), n, grid, _vp(an), T, S, patch,
+        kpad, _f32(nrm), c_float(success_threshold), _i32(pol), tier, _vp(rec), _vp(cnt), _vp(probe), _opt(hres, _vp),
+        _opt(hst, _vp), _opt(hrec, _vp)))
+    return dict(states=st, results=res, records=rec, probe=probe, counts=cnt, host_results=hres, host_states=hst, host_records=hrec)
 
 
 # the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)

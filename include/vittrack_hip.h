@@ -1079,6 +1079,40 @@ int vt_group_enable_taps(vt_group* g, int enable);
  * bit, in every kind of pass.
  *   Read-out: vt_group_read_tensor(g, stream, "health" / "health_words", ...).
  *
+ * PEAK ARBITRATION (csrc/k_arbitrate.hip; the rule to the bit: include/vittrack_hip_ops.h, vt_op_arbitrate; DESIGN.md section
+ * 3): the options above report or gate; this one changes which box a pass commits. Where the box the decode committed (peak 0
+ * of the response map) no longer looks like the stream's anchor and a runner-up peak does, the runner-up is committed instead.
+ * Keys (a negative value selects the default):
+ *   "arbitrate"             0 = off, 1 = on                                                      0
+ *   "arbitrate_max"         2..4 peaks examined, peak 0 included                                 3
+ *   "arbitrate_radius"      1..4: suppression radius of the iteration (as vt_group_set_peaks)    2
+ *   "arbitrate_min_resp_pm" 0..1000: a runner-up needs response > 0 and >= pm / 1000             50
+ *   "arbitrate_low_pm"      0..1000: peak 0 is challenged only while its similarity is below     300
+ *                           pm / 1000; 0: never challenged (1 challenges every similarity below
+ *                           0.001, the negative ones included: the step lies between 0 and 1)
+ *   "arbitrate_high_pm"     0..1000: a runner-up must reach this similarity                      500
+ * Each threshold is (float)pm / 1000.0f, one binary32 divide. The first non-zero "arbitrate" is refused
+ * (VT_ERR_INVALID_ARG) unless the engine is appearance-capable: the anchors are the appearance store's. It makes the engine
+ * arbitration-capable for good: one store - the policy, per stream a record, two counters and four probes of template rows -,
+ * a pinned mirror of the records, the graphs captured again with four launches directly behind the decode (a candidate
+ * pass: the commit) and ahead of motion_settle in EVERY kind of pass, so that everything that reads the new box - the
+ * settle's velocity, conflicts, health, the appearance record, refresh rule 8, chips, peaks, the overlay - reads the final
+ * one. It neither needs nor touches the response-peaks option. A slot is due when the flag is on, the pass is no candidate
+ * pass, result.success is set, window_miss != frames_done, and at least one runner-up k >= 1 is eligible: its score >= the
+ * model's success threshold and its integer box (floorf(v + 0.5f) of the four floats, as the decode rounds) passes refresh
+ * rule 6. Per listed, eligible peak - peak 0 included - the template-sized crop at its integer box is scored against the
+ * stream's anchor with the appearance check's sums. With sim[k] the similarity of peak k: a switch requires sim[0] < low and
+ * some eligible k >= 1 with sim[k] >= high. The chosen peak is the one with the largest similarity; on a tie, the lowest k.
+ * On a switch the result becomes success 1, the peak's score and integer box, and the state's last_fbox, last_score, last_idx
+ * and box become the peak's, on the device and in the host's copies: exactly what the decode would have written had that peak
+ * been the argmax. frames_done and success_count stay as the decode left them. Record status: 0 not due, 1 kept, 2 switched,
+ * 3 candidate pass (nothing is arbitrated there), 4 refresh rule 6 failed at peak 0, 5 refresh rule 7 failed at an examined
+ * peak - the pass is marked a window miss and nothing else happens: the host's redo with an exact window decides, so a
+ * pipelined run equals a synchronous one. vt_group_init_*, an import and the destination of a copy zero the stream's record;
+ * "arbitrate" 0 zeroes every stream's; no part of a snapshot. "arbitrate_low_pm" 0 challenges nobody, a negative similarity
+ * included: the engine equals one without the option, bit for bit.
+ *   Read-out: vt_group_read_tensor(g, stream, "arbitrate", ...).
+ *
  * DIAGNOSTICS (A/B measurements and parity tests of alternative kernels; results are the same quantity either
  * way): key "head_band": 2 (default; any negative value selects it) = the head's convolutions on the band kernel, the
  * final LayerNorm inside the first layer's launch and the logits and the decode behind the last layer's, 1 = the same
@@ -1154,6 +1188,15 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4);
  * "health_words" [52] (by STREAM): the same record as exact integers - its 26 32-bit words (status, frames_done, flags, c,
  * Wg, Hg, still, 0, then S1, S2, G, D, HD, G_ref as int64 low word first, then has_prev, cur, pW, pH, pc, 0), each as two
  * floats: the low and the high 16 bits. Both: VT_ERR_INVALID_ARG on an engine that never enabled the frame health.
+ * "arbitrate" [48] (by STREAM; see vt_group_set_tuning "arbitrate"): the engine flag, then the stream's record as the pinned
+ * mirror holds it (that of its last COLLECTED pass) - status, frames_done, n, chosen -, its counters evaluated (status 1 or 2)
+ * and switched (the device's), 0; then four peaks of ten values: cell, status (0 not cut, 1 cut and scored, 2 rule 6 failed, 3
+ * a variance is not positive), score, response, similarity, the float box x, y, w, h, 0. Every value is exact.
+ * In a PIPELINED host run, read between two vt_group_wait_next calls, a by-stream mirror - this one like "appearance",
+ * "conflicts", "health" - may already hold the record of the successor of a pass that was redone: compare a stream's record
+ * with a synchronous run's where both have collected the same pass. The counters evaluated and switched are the device's and
+ * may count a redone pass twice.
+ * VT_ERR_INVALID_ARG on an engine that never enabled the peak arbitration.
  * Returns the element count, or a negative vt_status. With out == NULL only the count. */
 int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* out,
                              int64_t capacity);

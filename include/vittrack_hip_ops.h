@@ -264,6 +264,54 @@ int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int 
 int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, const vt_result* results, const int32_t* slot_stream,
                            const int32_t* winner, int n, const int32_t* scenes, const int32_t* policy, void* records, void* counts,
                            void* host_records);
+/* The four launches of the peak arbitration (csrc/k_arbitrate.hip; DESIGN.md section 3 "Peak arbitration") on caller-supplied
+ * operands, and nothing else: arbitrate_list, arbitrate_probe, arbitrate_score, arbitrate_commit, in that order. Where the box
+ * the decode committed (peak 0 of the response map) no longer looks like the stream's anchor and a runner-up peak does, the
+ * runner-up is committed instead. The engine runs them in every pass of an arbitration-enabled engine (include/vittrack_hip.h,
+ * "arbitrate*" keys), directly behind the decode and ahead of motion_settle. THE RULE, to the bit:
+ *   POLICY: 8 int32 = on (0 / 1), max (2..4 peaks examined, peak 0 included), radius (1..4), min_resp_pm, low_pm, high_pm
+ * (0..1000 per mille each), two reserved words - the bounds of the table kArbKeys of csrc/vt_feature_keys.hpp, which names the
+ * words "arbitrate", "arbitrate_max", "arbitrate_radius", "arbitrate_min_resp_pm", "arbitrate_low_pm" and
+ * "arbitrate_high_pm" (defaults 0, 3, 2, 50, 300, 500). Each threshold is (float)pm / 1000.0f, one binary32 divide.
+ *   LIST: the iteration of vt_op_response_peaks above with max_peaks = max, radius and min_resp = min_resp_pm's threshold:
+ * the same cells, scores, responses and float boxes, bit for bit. The integer box of a peak is floorf(v + 0.5f) of its four
+ * floats, as the decode rounds.
+ *   DUE: on != 0, the pass is no candidate pass (winner == NULL), result.success != 0, window_miss != frames_done, and at
+ * least one runner-up k >= 1 is eligible. A runner-up is eligible when its score >= success_threshold (a NaN fails) and its
+ * integer box passes refresh rule 6 (the template crop's taps at that box lie inside the taps of the search crop the pass
+ * sampled: state.geo). Peaks are examined in listing order, peak 0 first, and the first of these ends the examination:
+ * peak 0 fails rule 6 - record status 4; peak 0 or a runner-up with a passing score and rule 6 fails refresh rule 7 (the
+ * in-frame part of the template's taps leaves the window stored of the slot's frame) - record status 5, window_miss =
+ * frames_done in the state and its mirror, nothing else. Not due: status 0; a candidate pass with on != 0: status 3 for the
+ * winning slots' streams, nothing else written.
+ *   PROBE: for peak 0 and every eligible runner-up of a due slot the template-sized crop (factor 2, side T) of the slot's
+ * frame at the peak's integer box into probe[stream][k]: the rows vt_group_init_* would write at that box, bit for bit.
+ *   SCORE: per cut peak the five binary64 sums of vt_op_appearance_score below on anchor[stream] and probe[stream][k], in the
+ * same order of additions: the same similarity bits. Peak status 1: scored; 3: a variance is not positive (similarity 0).
+ *   COMMIT: with sim[k] the similarity of a peak of status 1, low and high the thresholds: a switch requires sim[0] < low and
+ * some eligible k >= 1 with sim[k] >= high. The chosen peak is the one with the largest similarity; on a tie, the lowest k.
+ * low_pm 0 challenges nobody (a negative similarity included): the option is inert there.
+ * On a switch (record status 2, chosen = k) the result (device and mirror) becomes success 1, the peak's score, its integer
+ * box; the state's last_fbox becomes the peak's float box, last_score its score, last_idx its cell, box its integer box, in
+ * the state and its mirror. frames_done and success_count stay as the decode left them. Otherwise status 1, chosen = 0 and
+ * nothing but the record is written. Counters per stream: evaluated (status 1 or 2), switched (status 2).
+ *   RECORD, per stream, 176 bytes: status, frames_done, n (peaks listed; 0 where the slot left before the list), chosen; then
+ * four peaks of 40 bytes: cell, status (0: not cut; 1: cut and scored; 2: rule 6 failed; 3: a variance is not positive),
+ * score, resp, similarity, a reserved word, the float box. Peaks are marked 1 only in records of status 1 and 2.
+ *   OPERANDS: head_out [n * grid^2][8] and hann [grid^2] as for vt_op_response_peaks; frames: [n] by slot with DEVICE planes
+ * (read only); states: [n_streams] raw 88-byte stream states, in and out; results: [n] by slot, in and out; slot_stream: [n]
+ * slot -> stream or null (the identity); winner: non-null marks a candidate pass; anchor: [n_streams][nt][kpad] bf16 bits, nt
+ * = (T / patch)^2; norm: a0, a1, a2, b0, b1, b2 of the crop's normalisation; tier 0..2: the crop body's LDS tier. Out: records
+ * [n_streams] of 176 bytes and probe [n_streams][4][nt][kpad], both 0xff where no launch stored; counts [n_streams][2] int32,
+ * in and out. host_results [n], host_states [n_streams], host_records [n_streams] (nullable, in and out): pinned mirrors.
+ * States, results, records, probe rows, counters, tickets and partials sit between guard bands; a changed guard byte or a
+ * ticket left non-zero is VT_ERR_HIP. A policy word the table refuses, a map out of range, n > 1024, and - with winner == NULL -
+ * a stream named by two slots: VT_ERR_INVALID_ARG. */
+int vt_op_arbitrate(int device_id, const float* head_out, const float* hann, const vt_frame* frames, void* states, int n_streams,
+                    vt_result* results, const int32_t* slot_stream, const int32_t* winner, int n, int grid, const uint16_t* anchor,
+                    int T, int S, int patch, int kpad, const float* norm, float success_threshold, const int32_t* policy, int tier,
+                    void* records, int32_t* counts, uint16_t* probe, vt_result* host_results, void* host_states,
+                    void* host_records);
 /* The QKV projection with its attention-layout epilogue: a [B*tokens, D], w [3D, D], bias [3D] ->
  * qk_out [B*tokens, 2D] (q scaled by 1/8, then k) and vt_out [B*H, 64, npad] (v transposed per head,
  * npad = tokens rounded up to 64, padding zero); bf16 results widened to f32. cfg as above;
