@@ -183,7 +183,7 @@ struct Engine {
     // slots' segments of d_patches, and the next full pass puts every segment back from here
     bf16_t* d_tpl = nullptr;
     bool segments_moved = false;        // d_patches' template rows are not in stream order (a subset pass ran since)
-    // The first enable of an optional in-the-pass feature, for all eight below: on the idle stream,
+    // The first enable of an optional in-the-pass feature, for every one below: on the idle stream,
     // never inside an update - `extra` bytes checked against max_device_mib (beside activation_bytes() and
     // feature_bytes()) and against free memory (VT_ERR_OOM), alloc(), install() (pointers, *_capable = true), every
     // graph dropped and captured again with the feature's launches in it, commit() if there is one. Should alloc() or
@@ -476,9 +476,9 @@ struct Engine {
     vt_result* h_results = nullptr;
     StreamState* h_state = nullptr;
     // A pass's sinks: the PassOut (vt_common.hpp) of pinned buffers its outputs land in - results and peak records by
-    // slot, states, motion, appearance, proposal and conflict records [B] by stream. The engine's own are h_results, h_states_all, h_peaks,
-    // h_motion_all, h_appear_all, h_prop_all, h_conflict_all and h_health_all; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for that it
-    // lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them. The
+    // slot, states and every optional feature's records [B] by stream. The engine's own are h_results, h_states_all, h_peaks
+    // and the h_*_all above; every pipelined slot has a record of its own. sinks_alloc gives a record the members asked for
+    // that it lacks, [B] each and zero-filled (a member that exists stays: idempotent); sinks_free frees and nulls them. The
     // optional ones are the rows of ONE list (vt_features.hip: kSinks), which everything below walks.
     enum : unsigned { SINK_BASE = 1 /* results, states */, SINK_PEAKS = 2, SINK_MOTION = 4, SINK_APPEAR = 8, SINK_PROP = 16, SINK_CONFLICT = 32, SINK_HEALTH = 64, SINK_ARB = 128, SINK_ALL = 255 };
     unsigned sink_members() const;      // SINK_BASE and the sinks of the features the engine is capable of

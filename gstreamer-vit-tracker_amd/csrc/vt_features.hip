@@ -632,9 +632,11 @@ static int proposals_refuse(Engine* e) {
     return prop_pattern_side(e->d.T) ? VT_OK : set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", e->d.T);
 }
 
-// The stores: overlay the policy | [B] counters, motion the policy | [B] records (zero like known_motion, which nothing writes
-// before the engine is capable), appearance all zero but the policy and the anchors of the initialised streams, proposals
-// sized by the max_cells of the enable and zero up to the thumbnails, conflicts all zero but the policy (every stream in scene 0), health sized by the max_cells of the enable and zero up to the thumbnails, arbitration all zero but the policy up to the probes. The casts: a policy is words from its first member on.
+// The stores: overlay the policy | [B] counters; motion the policy | [B] records (zero like known_motion, which nothing
+// writes before the engine is capable); appearance all zero but the policy and the anchors of the initialised streams;
+// proposals sized by the max_cells of the enable and zero up to the thumbnails; conflicts all zero but the policy (every
+// stream in scene 0); health sized by the max_cells of the enable and zero up to the thumbnails; arbitration all zero but
+// the policy up to the probes. The casts: a policy is words from its first member on.
 const std::array<KeyedFeature, 7>& keyed_features() {
     static const std::array<KeyedFeature, 7> list = {{
         {"result overlay", "result_overlay", apply_overlay, (int32_t Engine::*)&Engine::overlay_policy, OV_WORDS, OV_FLAGS, &Engine::overlay_capable,
