@@ -27,6 +27,17 @@ inline float tau_of(int32_t pm) { return (float)pm / 1000.0f; }
 inline void put_tau(int32_t* word, int32_t pm) { const float tau = tau_of(pm); memcpy(word, &tau, sizeof(tau)); }    // one binary32 divide
 // a feature's keys from outside, table and specials: one (key, value) applied to `words`; capable: the engine has enabled it
 typedef Answer (*Apply)(const char* key, int value, const int32_t* def, int32_t* words, bool capable, char* text, size_t cap);
+// An operator hook's policy words through a feature's table, row by row: -1 and `words` filled, or the index of the first row
+// refused. A hook takes no "default" value: a negative word is refused here
+template <int N>
+inline int check_words(const Key (&rows)[N], Apply apply, const int32_t* def, const int32_t* policy, int32_t* words) {
+    char text[256];
+    for (int i = 0; i < N; ++i) {
+        const int32_t v = policy[rows[i].word];
+        if (v < 0 || apply(rows[i].key, v, def, words, false, text, sizeof(text)) != ACCEPTED) return i;
+    }
+    return -1;
+}
 
 enum { OV_FLAGS, OV_THICKNESS, OV_SIZE, OV_SCALE, OV_LUMA, OV_RGB, OV_MIN_SCORE_PCT, OV_WORDS = 8 };      // OverlayPolicy
 static constexpr Key kOverlayKeys[] = {

@@ -1,6 +1,7 @@
 // vt_ops.hip — operator-level entry points (include/vittrack_hip_ops.h): numerics tests and tuning tools call the
 // same kernel launchers the pass uses. Linked into libvittrack_hip_ops.so only; the product library does not carry them.
-// What the hooks share lives in vt_ops_host.hpp (host arithmetic) and vt_ops_util.hpp (device buffers, guard bands, timing).
+// What the hooks share lives in vt_ops_host.hpp (host arithmetic) and vt_ops_util.hpp (device buffers, guard bands, timing,
+// and for the in-the-pass launches the slot maps, the frame list, the pinned mirrors and the policy words through a key table).
 // Every buffer a kernel writes and a hook downloads is a GuardedOut, checked with guards_intact() after the synchronise;
 // the timing entry points and loops are not.
 #include "vt_ops_util.hpp"
@@ -21,6 +22,8 @@ static void pack_qkv(const uint16_t* q, const uint16_t* k, const uint16_t* v, in
             vt[((size_t)(b * H + c / 64) * 64 + c % 64) * npad + tp] = v[(size_t)m * D + c];
     }
 }
+
+using namespace vtkeys;     // the key tables (vt_feature_keys.hpp) under their own names, as in vt_features.hip
 
 extern "C" {
 
@@ -521,17 +524,9 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
         launches < 1 || launches > 64 || (form == 1 && (!w3 || !b3)))
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
     if (C % 2) return set_err(VT_ERR_INVALID_ARG, "head_decode: C must be even");
-    if (!slot_stream && n_states < B)
-        return set_err(VT_ERR_INVALID_ARG, "head_decode: %d states for %d slots", n_states, B);
-    if (slot_stream) {      // every slot's stream exists, and no two slots write one state
-        std::vector<char> seen((size_t)n_states, 0);
-        for (int b = 0; b < B; ++b) {
-            const int32_t s = slot_stream[b];
-            if (s < 0 || s >= n_states) return set_err(VT_ERR_INVALID_ARG, "head_decode: slot %d names stream %d of %d", b, (int)s, n_states);
-            if (seen[(size_t)s]) return set_err(VT_ERR_INVALID_ARG, "head_decode: stream %d listed twice", (int)s);
-            seen[(size_t)s] = 1;
-        }
-    }
+    SlotMaps maps{slot_stream, nullptr, B, n_states};       // every slot's stream exists, and no two slots write one state
+    if (int rc = maps.check_all("head_decode", "states")) return rc;
+    if (int rc = maps.check_unique("head_decode", "listed twice")) return rc;
     if (form == 1 && !headconv_plannable(grid, C, C, 9 * C, true, true))
         return set_err(VT_ERR_INVALID_ARG, "head_decode: grid %d, C %d is no shape of the band kernel's fused tail", grid, C);
     if (int rc = check_device(device_id)) return rc;
@@ -539,23 +534,21 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
     HIPCHK(headconv_prepare());
     const int ns = grid * grid;
     const size_t M = (size_t)B * ns, res_bytes = (size_t)B * sizeof(vt_result), st_bytes = (size_t)n_states * sizeof(StreamState);
-    DevArr dt, dw3, db3, dw4, db4, dhann, dpo, dmap, dbest, dz;
+    DevArr dt, dw3, db3, dw4, db4, dhann, dpo, dbest, dz;
     GuardedOut dt3, dho, dst, dres, dcnt;   // states: the caller's; band counters: zeros; the rest 0xff
-    PinnedBuf hres, hst;
+    Mirror hres, hst;
     HIPCHK(dt.upload(t, M * C * 2)); HIPCHK(dw4.upload(w4, (size_t)8 * C * 4)); HIPCHK(db4.upload(b4, 8 * 4));
     HIPCHK(dhann.upload(hann, (size_t)ns * 4)); HIPCHK(dst.upload(states, st_bytes));
     HIPCHK(dho.alloc(M * 8 * 4)); HIPCHK(dres.alloc(res_bytes));
     HIPCHK(dcnt.alloc((size_t)B * 4, 0)); HIPCHK(dbest.zeros((size_t)B * grid * 2 * 4));
-    HIPCHK(hres.alloc(res_bytes)); HIPCHK(hst.alloc(st_bytes));
-    memcpy(hres.p, host_results, res_bytes);
-    memcpy(hst.p, host_states, st_bytes);
-    const PassOut po{(flags & 1) ? nullptr : (vt_result*)hres.p, (flags & 2) ? nullptr : (StreamState*)hst.p};
+    HIPCHK(hres.from(host_results, res_bytes)); HIPCHK(hst.from(host_states, st_bytes));
+    const PassOut po{(flags & 1) ? nullptr : hres.as<vt_result>(), (flags & 2) ? nullptr : hst.as<StreamState>()};
     HIPCHK(dpo.upload(&po, sizeof(po)));
-    HIPCHK(dmap.upload(slot_stream, (size_t)B * 4));
+    HIPCHK(maps.upload());
     DecodeArgs dec{};
     dec.w4 = dw4.as<const float>(); dec.b4 = db4.as<const float>(); dec.hann = dhann.as<const float>();
     dec.head_out = dho.as<float>(); dec.states = dst.as<StreamState>(); dec.results = dres.as<vt_result>();
-    dec.out = dpo.as<const PassOut>(); dec.slot_stream = dmap.as<const int32_t>();
+    dec.out = dpo.as<const PassOut>(); dec.slot_stream = maps.dev_slot_stream();
     dec.B = B; dec.ns = ns; dec.grid = grid; dec.C = C; dec.success_threshold = success_threshold;
     HeadConvArgs h{};
     if (form == 0) {
@@ -582,8 +575,7 @@ int vt_op_head_decode(int device_id, int form, const uint16_t* t, const uint16_t
     if (int rc = guards_intact("head_decode", {{&dt3, "conv output"}, {&dho, "head output"}, {&dst, "states"}, {&dres, "results"},
                                                {&dcnt, "band counters"}})) return rc;
     HIPCHK(dho.download(head_out)); HIPCHK(dres.download(results)); HIPCHK(dst.download(states)); HIPCHK(dcnt.download(band_cnt));
-    memcpy(host_results, hres.p, res_bytes);
-    memcpy(host_states, hst.p, st_bytes);
+    hres.back(); hst.back();
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -594,27 +586,25 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
     if (!head_out || !hann || !states || !policies || !records || !host_records || B < 1 || B > 4096 || grid < 1 || grid > 110 ||
         n_states < 1)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && n_states < B) return set_err(VT_ERR_INVALID_ARG, "response_peaks: %d states for %d slots", n_states, B);
+    // a per-stream record with a float and no key table: the ranges are checked here
     const PeaksPolicy* pol = (const PeaksPolicy*)policies;
     for (int s = 0; s < n_states; ++s)
         if (pol[s].max_peaks < 0 || pol[s].max_peaks > VT_PEAKS_MAX || pol[s].radius < 1 || pol[s].radius > 4)
             return set_err(VT_ERR_INVALID_ARG, "response_peaks: policy %d: max_peaks %d, radius %d", s, pol[s].max_peaks, pol[s].radius);
     SlotMaps maps{slot_stream, winner, B, n_states};
-    for (int b = 0; b < B; ++b)
-        if (int rc = maps.check("response_peaks", b)) return rc;
+    if (int rc = maps.check_all("response_peaks", "states")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const int ns = grid * grid;
     const size_t rec_bytes = (size_t)B * sizeof(vt_peaks);
     DevArr dho, dhann, dpol, dpo;
     GuardedOut dst, drec;   // both start as the caller's bytes
-    PinnedBuf hrec;
+    Mirror hrec;
     HIPCHK(dho.upload(head_out, (size_t)B * ns * 8 * 4)); HIPCHK(dhann.upload(hann, (size_t)ns * 4));
     HIPCHK(dst.upload(states, (size_t)n_states * sizeof(StreamState))); HIPCHK(dpol.upload(policies, (size_t)n_states * sizeof(PeaksPolicy)));
     HIPCHK(drec.upload(records, rec_bytes));
-    HIPCHK(hrec.alloc(rec_bytes));
-    memcpy(hrec.p, host_records, rec_bytes);
-    const PassOut po{nullptr, nullptr, (vt_peaks*)hrec.p};
+    HIPCHK(hrec.from(host_records, rec_bytes));
+    const PassOut po{nullptr, nullptr, hrec.as<vt_peaks>()};
     HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(maps.upload());
     const PeaksArgs pa{dho.as<const float>(), dhann.as<const float>(), dst.as<const StreamState>(), maps.dev_slot_stream(),
@@ -625,7 +615,7 @@ int vt_op_response_peaks(int device_id, const float* head_out, const float* hann
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("response_peaks", {{&drec, "records"}, {&dst, "states"}})) return rc;
     HIPCHK(drec.download(records)); HIPCHK(dst.download(states));
-    memcpy(host_records, hrec.p, rec_bytes);
+    hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -635,32 +625,27 @@ int vt_op_result_overlay(int device_id, const vt_frame* frames, const vt_result*
                          int device_frames) try {
     if (!frames || !results || !policy || !stats || n < 1 || n > VT_RESULT_OVERLAY_MAX_SLOTS || n_streams < 1)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "result_overlay: %d streams for %d slots", n_streams, n);
+    // thickness, size and scale are one packed key of the table and three words here: the ranges are checked by hand
     OverlayPolicy pol;
     memcpy(&pol, policy, sizeof(pol));
     if (pol.flags < 0 || pol.flags > 7 || pol.thickness < 1 || pol.thickness > 16 || pol.size < 1 || pol.size > 64 || pol.scale < 1 ||
         pol.scale > 4 || pol.luma < 0 || pol.luma > 255 || pol.rgb < 0 || pol.rgb > 0xFFFFFF || pol.min_score_pct < 0 ||
         pol.min_score_pct > 100)
         return set_err(VT_ERR_INVALID_ARG, "result_overlay: policy out of range");
-    std::vector<FrameDesc> desc((size_t)n);
+    HookFrames fr;
     SlotMaps maps{slot_stream, winner, n, n_streams};
-    for (int b = 0; b < n; ++b) {
-        if (int rc = check_frame(frames[b])) return rc;
-        to_desc(frames[b], &desc[(size_t)b]);
-        if (int rc = maps.check("result_overlay", b)) return rc;
-    }
+    if (int rc = fr.check(frames, n)) return rc;
+    if (int rc = maps.check_all("result_overlay")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
-    const int32_t flag = device_frames != 0;
-    DevArr dfr, dres, dpol, dflag;
+    DevArr dres, dpol;
     GuardedOut dst;         // the counters start as the caller's; the frames are the caller's own memory
-    HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
+    HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
     HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dst.upload(stats, (size_t)n_streams * sizeof(OverlayStats)));
-    HIPCHK(dflag.upload(&flag, 4));
     HIPCHK(maps.upload());
-    const ResultOverlayArgs oa{dfr.as<const FrameDesc>(), dres.as<const vt_result>(), maps.dev_slot_stream(), maps.dev_winner(),
-                               dpol.as<const OverlayPolicy>(), dst.as<OverlayStats>(), dflag.as<const int32_t>(), n};
-    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(fr.upload(device_frames));
+    const ResultOverlayArgs oa{fr.dev(), dres.as<const vt_result>(), maps.dev_slot_stream(), maps.dev_winner(),
+                               dpol.as<const OverlayPolicy>(), dst.as<OverlayStats>(), fr.dev_flag(), n};
     HIPCHK(launch_result_overlay(oa, nullptr));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("result_overlay", {{&dst, "counters"}})) return rc;
@@ -675,32 +660,25 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
                        void* host_states, void* host_records) try {
     if (!states || !records || !policy || !results || n < 1 || n > VT_MAX_STREAMS || n_streams < 1 || stages < 1 || stages > 3)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && !cands && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "motion_prior: %d streams for %d slots", n_streams, n);
     if ((cands != nullptr) != (winner != nullptr))
         return set_err(VT_ERR_INVALID_ARG, "motion_prior: the candidate form needs both the slots and the winner list");
+    static_assert(sizeof(MotionPolicy) == 4 * MO_WORDS, "MotionPolicy");
     MotionPolicy pol;
-    memcpy(&pol, policy, sizeof(pol));
-    if (pol.on < 0 || pol.on > 1 || pol.gain_pct < 1 || pol.gain_pct > 100 || pol.coast < 0 || pol.coast > 60 || pol.max_pct < 0 ||
-        pol.max_pct > 200)
-        return set_err(VT_ERR_INVALID_ARG, "motion_prior: policy out of range");
+    if (int rc = policy_from_words("motion_prior", kMotionKeys, apply_motion, VT_MOTION_DEFAULT_POLICY, policy, &pol)) return rc;
     std::vector<int32_t> map;       // the candidate form's map is its slots' streams
-    if (cands || slot_stream) map.resize((size_t)n);
-    SlotMaps maps{map.empty() ? nullptr : map.data(), winner, n, n_streams};
-    for (int i = 0; i < n; ++i) {
-        if (!map.empty()) map[(size_t)i] = cands ? cands[i].stream : slot_stream[i];
-        if (int rc = maps.check("motion_prior", i)) return rc;
-    }
+    for (int i = 0; i < n && cands; ++i) map.push_back(cands[i].stream);
+    SlotMaps maps{cands ? map.data() : slot_stream, winner, n, n_streams};
+    if (int rc = maps.check_all("motion_prior")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t sb = (size_t)n_streams * sizeof(StreamState), rb = (size_t)n_streams * sizeof(MotionRec);
     DevArr dpol, dres, dcand, dpo;
     GuardedOut dst, drec;   // both start as the caller's bytes
-    PinnedBuf hst, hrec;
+    Mirror hst, hrec;
     HIPCHK(dst.upload(states, sb)); HIPCHK(drec.upload(records, rb)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
-    if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
-    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
-    const PassOut po{nullptr, (StreamState*)hst.p, nullptr, (MotionRec*)hrec.p};
+    HIPCHK(hst.from(host_states, sb)); HIPCHK(hrec.from(host_records, rb));
+    const PassOut po{nullptr, hst.as<StreamState>(), nullptr, hrec.as<MotionRec>()};
     HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(maps.upload());
     HIPCHK(dcand.upload(cands, (size_t)n * sizeof(vt_candidate)));
@@ -711,8 +689,7 @@ int vt_op_motion_prior(int device_id, void* states, void* records, int n_streams
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("motion_prior", {{&dst, "states"}, {&drec, "records"}})) return rc;
     HIPCHK(dst.download(states)); HIPCHK(drec.download(records));
-    if (host_states) memcpy(host_states, hst.p, sb);
-    if (host_records) memcpy(host_records, hrec.p, rb);
+    hst.back(); hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -729,7 +706,6 @@ int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t
     const size_t nch = (size_t)appear_chunks(nt);
     const AppearPolicy pol{1, 1, 0, 0.0f};
     std::vector<AppearRec> recs(n, AppearRec{1, 0, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}, 0});
-    std::vector<unsigned> ticks(n);
     DevArr da, dp, dpol, dcnt;
     GuardedOut drec, dtick, dpart, dsum;
     HIPCHK(da.upload(anchor, rows)); HIPCHK(dp.upload(probe, rows)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
@@ -745,9 +721,9 @@ int vt_op_appearance_score(int device_id, const uint16_t* anchor, const uint16_t
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("appearance_score", {{&drec, "records"}, {&dtick, "tickets"}, {&dpart, "partials"}, {&dsum, "sums"}}))
         return rc;
-    HIPCHK(drec.download(recs.data())); HIPCHK(dsum.download(sums)); HIPCHK(dtick.download(ticks.data()));
+    HIPCHK(drec.download(recs.data())); HIPCHK(dsum.download(sums));
+    if (int rc = tickets_returned("appearance_score", dtick, 1)) return rc;
     for (size_t i = 0; i < n; ++i) {
-        if (ticks[i] != 0) return set_err(VT_ERR_HIP, "appearance_score: slot %zu left its ticket at %u", i, ticks[i]);
         similarity[i] = recs[i].similarity;
         status[i] = recs[i].status;
     }
@@ -766,46 +742,38 @@ int vt_op_proposals(int device_id, const vt_frame* frames, const void* states, i
         kpad < 3 * patch * patch || kpad > 65536 || (tpl_bufs != 1 && tpl_bufs != 2))
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
     if (prop_pattern_side(T) == 0) return set_err(VT_ERR_INVALID_ARG, "proposals: template size %d is a multiple of neither 16 nor 14", T);
-    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "proposals: %d streams for %d slots", n_streams, n);
+    // max_cells from VT_PROP_M_MAX^2 here, from 16384 as the engine's key: the op tests use small stores, so no table
     PropPolicy pol;
     memcpy(&pol, policy, sizeof(pol));
     if (pol.mode < 0 || pol.mode > 2 || pol.period < 1 || pol.period > VT_PROP_MAX_PERIOD || pol.max_n < 1 || pol.max_n > VT_PROP_MAX ||
         pol.min_sim_pm < 0 || pol.min_sim_pm > 1000 || pol.max_cells < VT_PROP_M_MAX * VT_PROP_M_MAX || pol.max_cells > VT_PROP_MAX_CELLS)
         return set_err(VT_ERR_INVALID_ARG, "proposals: policy out of range");
     pol.tau = (float)pol.min_sim_pm / 1000.0f;
-    std::vector<FrameDesc> desc((size_t)n);
+    HookFrames fr;
     SlotMaps maps{slot_stream, winner, n, n_streams};
-    for (int b = 0; b < n; ++b) {
-        if (int rc = check_frame(frames[b])) return rc;
-        to_desc(frames[b], &desc[(size_t)b]);
-        if (int rc = maps.check("proposals", b)) return rc;
-    }
+    if (int rc = fr.check(frames, n)) return rc;
+    if (int rc = maps.check_all("proposals")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
-    ModelDims d{};
-    d.T = T; d.patch = patch; d.gt = T / patch; d.nt = d.gt * d.gt; d.kpad = kpad;
-    for (int c = 0; c < 3; ++c) { d.norm_a[c] = norm[c]; d.norm_b[c] = norm[3 + c]; }
+    const ModelDims d = model_dims(T, 0, patch, kpad, norm);
     const size_t ns = (size_t)n, mc = (size_t)pol.max_cells, pm = VT_PROP_M_MAX * VT_PROP_M_MAX;
-    const int32_t flag = device_frames != 0;
     const PassOut po{};
-    DevArr dfr, dst, dres, dpol, dflag, dtpl, dcnt, dhead, dpo;
+    DevArr dst, dres, dpol, dtpl, dcnt, dhead, dpo;
     GuardedOut gpat, gth, gmap, grec;
-    HIPCHK(dfr.upload(desc.data(), ns * sizeof(FrameDesc))); HIPCHK(dst.upload(states, (size_t)n_streams * sizeof(StreamState)));
-    HIPCHK(dres.upload(results, ns * sizeof(vt_result))); HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4));
+    HIPCHK(dst.upload(states, (size_t)n_streams * sizeof(StreamState)));
+    HIPCHK(dres.upload(results, ns * sizeof(vt_result))); HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(dtpl.upload(tpl, (size_t)n_streams * tpl_bufs * d.nt * kpad * sizeof(bf16_t)));
     HIPCHK(dcnt.upload(evaluated, (size_t)n_streams * 4)); HIPCHK(dhead.zeros(ns * sizeof(PropHead))); HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(gpat.alloc(ns * pm * sizeof(int16_t))); HIPCHK(gth.alloc(ns * mc * sizeof(int16_t))); HIPCHK(gmap.alloc(ns * mc * sizeof(float)));
     HIPCHK(grec.alloc((size_t)n_streams * sizeof(PropRec)));
     HIPCHK(maps.upload());
-    const PropArgs pa{dfr.as<const FrameDesc>(), dst.as<const StreamState>(), dres.as<const vt_result>(), maps.dev_slot_stream(),
-                      maps.dev_winner(), dpol.as<const PropPolicy>(), dflag.as<const int32_t>(), dtpl.as<const bf16_t>(), tpl_bufs,
+    HIPCHK(fr.upload(device_frames));
+    const PropArgs pa{fr.dev(), dst.as<const StreamState>(), dres.as<const vt_result>(), maps.dev_slot_stream(),
+                      maps.dev_winner(), dpol.as<const PropPolicy>(), fr.dev_flag(), dtpl.as<const bf16_t>(), tpl_bufs,
                       grec.as<PropRec>(), dcnt.as<int32_t>(), dhead.as<PropHead>(), gpat.as<int16_t>(), gth.as<int16_t>(),
                       gmap.as<float>(), dpo.as<const PassOut>(), pol.max_cells, n};
-    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
     HIPCHK(launch_proposals_prepare(pa, d, nullptr));
-    int level = 0;
-    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
-    HIPCHK(launch_proposals_thumb(pa, d, level, nullptr));
+    HIPCHK(launch_proposals_thumb(pa, d, fr.level, nullptr));
     HIPCHK(launch_proposals_match(pa, nullptr));
     HIPCHK(launch_proposals_list(pa, nullptr));
     HIPCHK(hipDeviceSynchronize());
@@ -824,56 +792,38 @@ int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int
     if (!frames || !states || !policy || !thumbs || !records || !sad || n < 1 || n > VT_MAX_STREAMS || n_streams < 1 ||
         n_streams > VT_MAX_STREAMS)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "camera_motion: %d streams for %d slots", n_streams, n);
-    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here, in its words
-    static_assert(sizeof(CamPolicy) == 4 * vtkeys::CM_WORDS && vtkeys::kCameraKeys[2].hi == VT_CAM_R_MAX &&
-                  vtkeys::kCameraKeys[4].lo == VT_CAM_MIN_CELLS && vtkeys::kCameraKeys[4].hi == VT_CAM_MAX_CELLS, "CamPolicy");
-    const CamPolicy def = VT_CAM_DEFAULT_POLICY;
-    int32_t words[vtkeys::kMaxWords] = {};
-    for (const vtkeys::Key& k : vtkeys::kCameraKeys) {
-        char text[256];
-        if (policy[k.word] < 0 || vtkeys::apply_camera_motion(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false,
-                                                             text, sizeof(text)) != vtkeys::ACCEPTED)
-            return set_err(VT_ERR_INVALID_ARG, "camera_motion: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
-    }
+    static_assert(sizeof(CamPolicy) == 4 * CM_WORDS && kCameraKeys[2].hi == VT_CAM_R_MAX && kCameraKeys[4].lo == VT_CAM_MIN_CELLS &&
+                  kCameraKeys[4].hi == VT_CAM_MAX_CELLS, "CamPolicy");
     CamPolicy pol;
-    memcpy(&pol, words, sizeof(pol));
-    std::vector<FrameDesc> desc((size_t)n);
+    if (int rc = policy_from_words("camera_motion", kCameraKeys, apply_camera_motion, VT_CAM_DEFAULT_POLICY, policy, &pol)) return rc;
+    HookFrames fr;
     SlotMaps maps{slot_stream, nullptr, n, n_streams};
-    for (int b = 0; b < n; ++b) {
-        if (int rc = check_frame(frames[b])) return rc;
-        to_desc(frames[b], &desc[(size_t)b]);
-        if (int rc = maps.check("camera_motion", b)) return rc;
-    }
+    if (int rc = fr.check(frames, n)) return rc;
+    if (int rc = maps.check_all("camera_motion")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t ns = (size_t)n_streams, sb = ns * sizeof(StreamState), rb = ns * sizeof(CamRec);
     const size_t tb = ns * 2 * (size_t)pol.max_cells * sizeof(uint16_t), ab = ns * VT_CAM_TABLE * sizeof(long long);
-    const int32_t flag = device_frames != 0;
-    DevArr dfr, dst, dpol, dflag, dhead;
+    DevArr dst, dpol, dhead;
     GuardedOut gth, grec, gsad;
-    PinnedBuf hst, hrec;
-    HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dst.upload(states, sb));
-    HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4)); HIPCHK(dhead.zeros((size_t)n * sizeof(CamHead)));
+    Mirror hst, hrec;
+    HIPCHK(dst.upload(states, sb));
+    HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dhead.zeros((size_t)n * sizeof(CamHead)));
     HIPCHK(gth.upload(thumbs, tb)); HIPCHK(grec.upload(records, rb)); HIPCHK(gsad.alloc(ab));
-    if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
-    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    HIPCHK(hst.from(host_states, sb)); HIPCHK(hrec.from(host_records, rb));
     HIPCHK(maps.upload());
-    const CamArgs ca{dfr.as<const FrameDesc>(), dst.as<StreamState>(), maps.dev_slot_stream(), dpol.as<const CamPolicy>(),
-                     dflag.as<const int32_t>(), grec.as<CamRec>(), dhead.as<CamHead>(), gsad.as<unsigned long long>(),
-                     gth.as<uint16_t>(), (StreamState*)hst.p, (CamRec*)hrec.p, pol.max_cells, n};
-    int level = 0;
-    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
-    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
+    HIPCHK(fr.upload(device_frames));
+    const CamArgs ca{fr.dev(), dst.as<StreamState>(), maps.dev_slot_stream(), dpol.as<const CamPolicy>(),
+                     fr.dev_flag(), grec.as<CamRec>(), dhead.as<CamHead>(), gsad.as<unsigned long long>(),
+                     gth.as<uint16_t>(), hst.as<StreamState>(), hrec.as<CamRec>(), pol.max_cells, n};
     HIPCHK(launch_camera_prepare(ca, nullptr));
-    HIPCHK(launch_camera_thumb(ca, level, nullptr));
+    HIPCHK(launch_camera_thumb(ca, fr.level, nullptr));
     HIPCHK(launch_camera_search(ca, nullptr));
     HIPCHK(launch_camera_decide(ca, nullptr));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("camera_motion", {{&gth, "thumbnails"}, {&grec, "records"}, {&gsad, "tables"}})) return rc;
     HIPCHK(gth.download(thumbs)); HIPCHK(grec.download(records)); HIPCHK(gsad.download(sad)); HIPCHK(dst.download(states));
-    if (host_states) memcpy(host_states, hst.p, sb);
-    if (host_records) memcpy(host_records, hrec.p, rb);
+    hst.back(); hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -889,86 +839,55 @@ int vt_op_arbitrate(int device_id, const float* head_out, const float* hann, con
         n > VT_MAX_STREAMS || n_streams < 1 || n_streams > VT_MAX_STREAMS || grid < 1 || grid > 110 || patch < 1 || T < patch ||
         T % patch != 0 || S < T || kpad < 3 * patch * patch || kpad > 65536 || tier < 0 || tier > 2)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "arbitrate: %d streams for %d slots", n_streams, n);
-    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here, in its words
-    static_assert(sizeof(ArbPolicy) == 4 * vtkeys::AR_WORDS && vtkeys::kArbKeys[1].hi == VT_ARB_MAX, "ArbPolicy");
-    const ArbPolicy def = VT_ARB_DEFAULT_POLICY;
-    int32_t words[vtkeys::kMaxWords] = {};
-    for (const vtkeys::Key& k : vtkeys::kArbKeys) {
-        char text[256];
-        if (policy[k.word] < 0 || vtkeys::apply_arbitrate(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false, text,
-                                                         sizeof(text)) != vtkeys::ACCEPTED)
-            return set_err(VT_ERR_INVALID_ARG, "arbitrate: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
-    }
+    static_assert(sizeof(ArbPolicy) == 4 * AR_WORDS && kArbKeys[1].hi == VT_ARB_MAX, "ArbPolicy");
     ArbPolicy pol;
-    memcpy(&pol, words, sizeof(pol));
-    std::vector<FrameDesc> desc((size_t)n);
+    if (int rc = policy_from_words("arbitrate", kArbKeys, apply_arbitrate, VT_ARB_DEFAULT_POLICY, policy, &pol)) return rc;
+    HookFrames fr;
     SlotMaps maps{slot_stream, winner, n, n_streams};
-    for (int b = 0; b < n; ++b) {
-        if (int rc = check_frame(frames[b])) return rc;
-        to_desc(frames[b], &desc[(size_t)b]);
-        if (int rc = maps.check("arbitrate", b)) return rc;
-    }
-    // outside a candidate pass a stream has ONE slot (every pass of the engine is built so): two slots of one stream would
-    // write the same record, state and counters from two workgroups
-    if (!winner && slot_stream) {
-        std::vector<char> named((size_t)n_streams, 0);
-        for (int b = 0; b < n; ++b) {
-            if (named[(size_t)slot_stream[b]]) return set_err(VT_ERR_INVALID_ARG, "arbitrate: stream %d is named by two slots", (int)slot_stream[b]);
-            named[(size_t)slot_stream[b]] = 1;
-        }
-    }
+    if (int rc = fr.check(frames, n)) return rc;
+    if (int rc = maps.check_all("arbitrate")) return rc;
+    // outside a candidate pass a stream has ONE slot (every pass of the engine is built so)
+    if (int rc = maps.check_unique("arbitrate", "is named by two slots")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
-    ModelDims d{};
-    d.T = T; d.S = S; d.patch = patch; d.gt = T / patch; d.nt = d.gt * d.gt; d.kpad = kpad;
-    for (int c = 0; c < 3; ++c) { d.norm_a[c] = norm[c]; d.norm_b[c] = norm[3 + c]; }
+    const ModelDims d = model_dims(T, S, patch, kpad, norm);
     const int ns = grid * grid, cols = 3 * patch * patch;
     const size_t nn = (size_t)n, nst = (size_t)n_streams, rows = (size_t)d.nt * kpad * sizeof(bf16_t);
     const size_t sb = nst * sizeof(StreamState), rb = nst * sizeof(ArbRec), resb = nn * sizeof(vt_result);
     const size_t pairs = nn * VT_ARB_MAX, nch = (size_t)appear_chunks(d.nt);
-    std::vector<unsigned> ticks(pairs);
-    DevArr dho, dhann, dfr, dpol, danchor, dpo;
+    DevArr dho, dhann, dpol, danchor, dpo;
     GuardedOut gst, gres, grec, gcnt, gprobe, gtick, gpart;
-    PinnedBuf hres, hst, hrec;
+    Mirror hres, hst, hrec;
     HIPCHK(dho.upload(head_out, nn * ns * 8 * 4)); HIPCHK(dhann.upload(hann, (size_t)ns * 4));
-    HIPCHK(dfr.upload(desc.data(), nn * sizeof(FrameDesc))); HIPCHK(dpol.upload(&pol, sizeof(pol)));
+    HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(danchor.upload(anchor, nst * rows));
     HIPCHK(gst.upload(states, sb)); HIPCHK(gres.upload(results, resb)); HIPCHK(grec.alloc(rb));
     HIPCHK(gcnt.upload(counts, nst * sizeof(ArbCount))); HIPCHK(gprobe.alloc(nst * VT_ARB_MAX * rows));
     HIPCHK(gtick.alloc(pairs * sizeof(unsigned), 0));
     HIPCHK(gpart.alloc(pairs * nch * 5 * sizeof(double)));      // NaN: a partial nobody wrote would show
-    if (host_results) { HIPCHK(hres.alloc(resb)); memcpy(hres.p, host_results, resb); }
-    if (host_states) { HIPCHK(hst.alloc(sb)); memcpy(hst.p, host_states, sb); }
-    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
-    const PassOut po{(vt_result*)hres.p, (StreamState*)hst.p};
+    HIPCHK(hres.from(host_results, resb)); HIPCHK(hst.from(host_states, sb)); HIPCHK(hrec.from(host_records, rb));
+    const PassOut po{hres.as<vt_result>(), hst.as<StreamState>()};
     HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(maps.upload());
+    HIPCHK(fr.upload());
     ArbArgs a{};
-    a.head_out = dho.as<const float>(); a.hann = dhann.as<const float>(); a.frames = dfr.as<const FrameDesc>();
+    a.head_out = dho.as<const float>(); a.hann = dhann.as<const float>(); a.frames = fr.dev();
     a.states = gst.as<StreamState>(); a.results = gres.as<vt_result>(); a.slot_stream = maps.dev_slot_stream();
     a.winner = maps.dev_winner(); a.policy = dpol.as<const ArbPolicy>(); a.recs = grec.as<ArbRec>(); a.counts = gcnt.as<ArbCount>();
     a.tickets = gtick.as<unsigned>(); a.partials = gpart.as<double>(); a.anchor = danchor.as<const bf16_t>();
-    a.probe = gprobe.as<bf16_t>(); a.out = dpo.as<const PassOut>(); a.host_recs = (ArbRec*)hrec.p;
+    a.probe = gprobe.as<bf16_t>(); a.out = dpo.as<const PassOut>(); a.host_recs = hrec.as<ArbRec>();
     a.n = n; a.ns = ns; a.grid = grid; a.success_threshold = success_threshold;
-    int level = 0;
-    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
-    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
     HIPCHK(launch_arbitrate_list(a, d, nullptr));
-    HIPCHK(launch_arbitrate_probe(a, d, tier, level, nullptr));
+    HIPCHK(launch_arbitrate_probe(a, d, tier, fr.level, nullptr));
     HIPCHK(launch_arbitrate_score(a, d.nt, cols, kpad, nullptr));
     HIPCHK(launch_arbitrate_commit(a, nullptr));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("arbitrate", {{&gst, "states"}, {&gres, "results"}, {&grec, "records"}, {&gcnt, "counters"},
                                              {&gprobe, "probe rows"}, {&gtick, "tickets"}, {&gpart, "partials"}})) return rc;
-    HIPCHK(gtick.download(ticks.data()));
-    for (size_t i = 0; i < pairs; ++i)
-        if (ticks[i] != 0) return set_err(VT_ERR_HIP, "arbitrate: slot %zu, peak %zu left its ticket at %u", i / VT_ARB_MAX, i % VT_ARB_MAX, ticks[i]);
+    if (int rc = tickets_returned("arbitrate", gtick, VT_ARB_MAX)) return rc;
     HIPCHK(gst.download(states)); HIPCHK(gres.download(results)); HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
     HIPCHK(gprobe.download(probe));
-    if (host_results) memcpy(host_results, hres.p, resb);
-    if (host_states) memcpy(host_states, hst.p, sb);
-    if (host_records) memcpy(host_records, hrec.p, rb);
+    hres.back(); hst.back(); hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -981,52 +900,35 @@ int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int 
     if (!frames || !states || !policy || !thumbs || !accs || !hist || !heads || !records || !counts || n < 1 || n > VT_MAX_STREAMS ||
         n_streams < 1 || n_streams > VT_MAX_STREAMS)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "frame_health: %d streams for %d slots", n_streams, n);
-    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here, in its words
-    const HealthPolicy def = VT_HEALTH_DEFAULT_POLICY;
-    int32_t words[vtkeys::kMaxWords] = {};
-    for (const vtkeys::Key& k : vtkeys::kHealthKeys) {
-        char text[256];
-        if (policy[k.word] < 0 || vtkeys::apply_health(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false, text,
-                                                      sizeof(text)) != vtkeys::ACCEPTED)
-            return set_err(VT_ERR_INVALID_ARG, "frame_health: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
-    }
+    static_assert(sizeof(HealthPolicy) == 4 * HL_WORDS, "HealthPolicy");
     HealthPolicy pol;
-    static_assert(sizeof(pol) == sizeof(words), "HealthPolicy is kMaxWords words");
-    memcpy(&pol, words, sizeof(pol));
-    std::vector<FrameDesc> desc((size_t)n);
+    if (int rc = policy_from_words("frame_health", kHealthKeys, apply_health, VT_HEALTH_DEFAULT_POLICY, policy, &pol)) return rc;
+    HookFrames fr;
     SlotMaps maps{slot_stream, nullptr, n, n_streams};
-    for (int b = 0; b < n; ++b) {
-        if (int rc = check_frame(frames[b])) return rc;
-        to_desc(frames[b], &desc[(size_t)b]);
-        if (int rc = maps.check("frame_health", b)) return rc;
-    }
+    if (int rc = fr.check(frames, n)) return rc;
+    if (int rc = maps.check_all("frame_health")) return rc;
     if (int rc = check_device(device_id)) return rc;
     DEVICE_SCOPE(device_id);
     const size_t ns = (size_t)n_streams, sb = ns * sizeof(StreamState), rb = ns * sizeof(HealthRec), cb = ns * sizeof(HealthCount);
     const size_t tb = ns * 2 * (size_t)pol.max_cells * sizeof(uint16_t), ab = ns * HEALTH_ACCS * sizeof(long long);
     const size_t hb = ns * 2 * VT_HEALTH_BINS * sizeof(int32_t), hdb = (size_t)n * sizeof(HealthHead);
-    const int32_t flag = device_frames != 0;
-    DevArr dfr, dpol, dflag;
-    DevArr dpo;
+    DevArr dpol, dpo;
     GuardedOut gst, gth, gacc, ghist, ghead, grec, gcnt;
-    PinnedBuf hrec;
-    HIPCHK(dfr.upload(desc.data(), (size_t)n * sizeof(FrameDesc))); HIPCHK(dpol.upload(&pol, sizeof(pol))); HIPCHK(dflag.upload(&flag, 4));
+    Mirror hrec;
+    HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(gst.upload(states, sb)); HIPCHK(gth.upload(thumbs, tb)); HIPCHK(ghist.upload(hist, hb)); HIPCHK(grec.upload(records, rb));
     HIPCHK(gcnt.upload(counts, cb)); HIPCHK(gacc.alloc(ab)); HIPCHK(ghead.alloc(hdb));
-    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    HIPCHK(hrec.from(host_records, rb));
     PassOut po{};
-    po.host_health = (HealthRec*)hrec.p;
+    po.host_health = hrec.as<HealthRec>();
     HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(maps.upload());
-    const HealthArgs ha{dfr.as<const FrameDesc>(), gst.as<const StreamState>(), maps.dev_slot_stream(), dpol.as<const HealthPolicy>(),
-                        dflag.as<const int32_t>(), grec.as<HealthRec>(), gcnt.as<HealthCount>(), ghead.as<HealthHead>(),
+    HIPCHK(fr.upload(device_frames));
+    const HealthArgs ha{fr.dev(), gst.as<const StreamState>(), maps.dev_slot_stream(), dpol.as<const HealthPolicy>(),
+                        fr.dev_flag(), grec.as<HealthRec>(), gcnt.as<HealthCount>(), ghead.as<HealthHead>(),
                         gacc.as<unsigned long long>(), ghist.as<int32_t>(), gth.as<uint16_t>(), dpo.as<const PassOut>(), pol.max_cells, n};
-    int level = 0;
-    for (int b = 0; b < n; ++b) level = std::max(level, pix_level(frames[b].format));
-    HIPCHK(hipDeviceSynchronize());     // the caller's frames may have been filled on another stream
     HIPCHK(launch_health_prepare(ha, nullptr));
-    HIPCHK(launch_health_thumb(ha, level, nullptr));
+    HIPCHK(launch_health_thumb(ha, fr.level, nullptr));
     HIPCHK(launch_health_measure(ha, nullptr));
     HIPCHK(launch_health_decide(ha, nullptr));
     HIPCHK(hipDeviceSynchronize());
@@ -1034,7 +936,7 @@ int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int 
                                                 {&ghead, "headers"}, {&grec, "records"}, {&gcnt, "counters"}})) return rc;
     HIPCHK(gst.download(states)); HIPCHK(gth.download(thumbs)); HIPCHK(gacc.download(accs)); HIPCHK(ghist.download(hist));
     HIPCHK(ghead.download(heads)); HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
-    if (host_records) memcpy(host_records, hrec.p, rb);
+    hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT
 
@@ -1046,22 +948,11 @@ int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, con
     if (!states || !results || !scenes || !policy || !records || !counts || n < 1 || n > VT_MAX_STREAMS || n_streams < 1 ||
         n_streams > VT_MAX_STREAMS)
         return set_err(VT_ERR_INVALID_ARG, "bad argument");
-    if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "stream_conflicts: %d streams for %d slots", n_streams, n);
-    // the policy through the key table (vt_feature_keys.hpp): a word the table refuses is refused here; tau is the table's
-    const ConflictPolicy def = VT_CONFLICT_DEFAULT_POLICY;
-    int32_t words[vtkeys::kMaxWords] = {};
-    for (const vtkeys::Key& k : vtkeys::kConflictKeys) {
-        char text[256];
-        if (policy[k.word] < 0 || vtkeys::apply_conflicts(k.key, policy[k.word], reinterpret_cast<const int32_t*>(&def), words, false, text,
-                                                         sizeof(text)) != vtkeys::ACCEPTED)
-            return set_err(VT_ERR_INVALID_ARG, "stream_conflicts: policy word %d (%s) = %d refused", k.word, k.key, (int)policy[k.word]);
-    }
-    ConflictPolicy pol;
-    static_assert(sizeof(pol) == sizeof(words), "ConflictPolicy is kMaxWords words");
-    memcpy(&pol, words, sizeof(pol));
+    static_assert(sizeof(ConflictPolicy) == 4 * CF_WORDS, "ConflictPolicy");
+    ConflictPolicy pol;         // tau is the table's
+    if (int rc = policy_from_words("stream_conflicts", kConflictKeys, apply_conflicts, VT_CONFLICT_DEFAULT_POLICY, policy, &pol)) return rc;
     SlotMaps maps{slot_stream, winner, n, n_streams};
-    for (int b = 0; b < n; ++b)
-        if (int rc = maps.check("stream_conflicts", b)) return rc;
+    if (int rc = maps.check_all("stream_conflicts")) return rc;
     for (int s = 0; s < n_streams; ++s)
         if (scenes[s] < 0 || scenes[s] > VT_CONFLICT_MAX_SCENE)
             return set_err(VT_ERR_INVALID_ARG, "stream_conflicts: scene %d of stream %d (0..%d)", (int)scenes[s], s, VT_CONFLICT_MAX_SCENE);
@@ -1070,13 +961,13 @@ int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, con
     const size_t ns = (size_t)n_streams, rb = ns * sizeof(ConflictRec), cb = ns * sizeof(ConflictCount);
     DevArr dst, dres, dsc, dpol, dpo;
     GuardedOut grec, gcnt;
-    PinnedBuf hrec;
+    Mirror hrec;
     HIPCHK(dst.upload(states, ns * sizeof(StreamState))); HIPCHK(dres.upload(results, (size_t)n * sizeof(vt_result)));
     HIPCHK(dsc.upload(scenes, ns * 4)); HIPCHK(dpol.upload(&pol, sizeof(pol)));
     HIPCHK(grec.upload(records, rb)); HIPCHK(gcnt.upload(counts, cb));
-    if (host_records) { HIPCHK(hrec.alloc(rb)); memcpy(hrec.p, host_records, rb); }
+    HIPCHK(hrec.from(host_records, rb));
     PassOut po{};
-    po.host_conflicts = (ConflictRec*)hrec.p;
+    po.host_conflicts = hrec.as<ConflictRec>();
     HIPCHK(dpo.upload(&po, sizeof(po)));
     HIPCHK(maps.upload());
     const ConflictArgs ca{dst.as<const StreamState>(), dres.as<const vt_result>(), maps.dev_slot_stream(), maps.dev_winner(),
@@ -1086,7 +977,7 @@ int vt_op_stream_conflicts(int device_id, const void* states, int n_streams, con
     HIPCHK(hipDeviceSynchronize());
     if (int rc = guards_intact("stream_conflicts", {{&grec, "records"}, {&gcnt, "counters"}})) return rc;
     HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
-    if (host_records) memcpy(host_records, hrec.p, rb);
+    hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT
 

@@ -1,5 +1,6 @@
 // vt_ops_util.hpp — what the operator entry points (vt_ops.hip) share on the device side: buffers that know their size,
-// guard bands, the timing loop, the operand set of a GEMM launch and the slot maps of the in-the-pass launches.
+// guard bands, the timing loop, the operand set of a GEMM launch and, for the in-the-pass launches, the slot maps, the frame
+// list, the pinned mirrors and the policy words through a key table.
 #pragma once
 #include <initializer_list>
 #include <utility>
@@ -30,11 +31,21 @@ struct DevArr : DevBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
-// pinned, device-visible host memory (what PassOut points the decode at)
-struct PinnedBuf {
-    void* p = nullptr;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t n) { return hipHostMalloc(&p, n ? n : 4); }
+// An optional pinned, device-visible mirror of a caller's host array (what PassOut points a launch at): from() copies the
+// caller's bytes in, back() - after the guards are checked - copies them out. A null host pointer: as<T>() is null, no copy.
+struct Mirror {
+    void *p = nullptr, *host = nullptr;
+    size_t bytes = 0;
+    ~Mirror() { if (p) (void)hipHostFree(p); }
+    hipError_t from(void* h, size_t n) {
+        if (!h) return hipSuccess;
+        host = h; bytes = n;
+        const hipError_t e = hipHostMalloc(&p, n ? n : 4);
+        if (e == hipSuccess) memcpy(p, h, n);
+        return e;
+    }
+    void back() const { if (host) memcpy(host, p, bytes); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
 // The output buffer of a hook between two guard bands: the bands carry a byte pattern, the output 0xff (a
@@ -131,17 +142,93 @@ struct GemmOperands {
     }
 };
 
+// after the guards: every ticket of `per` per slot came back to zero by itself
+static inline int tickets_returned(const char* hook, const GuardedOut& tickets, size_t per) {
+    std::vector<unsigned> t(tickets.bytes / sizeof(unsigned));
+    HIPCHK(tickets.download(t.data()));
+    for (size_t i = 0; i < t.size(); ++i) {
+        if (!t[i]) continue;
+        char peak[32] = "";
+        if (per > 1) snprintf(peak, sizeof(peak), ", peak %zu", i % per);
+        return set_err(VT_ERR_HIP, "%s: slot %zu%s left its ticket at %u", hook, i / per, peak, t[i]);
+    }
+    return VT_OK;
+}
+
+// the dimensions the in-the-pass crops read: template T (search S), patch, padded patch columns, norm (a0, a1, a2, b0, b1, b2)
+static inline ModelDims model_dims(int T, int S, int patch, int kpad, const float* norm) {
+    ModelDims d{};
+    d.T = T; d.S = S; d.patch = patch; d.gt = T / patch; d.nt = d.gt * d.gt; d.kpad = kpad;
+    for (int c = 0; c < 3; ++c) { d.norm_a[c] = norm[c]; d.norm_b[c] = norm[3 + c]; }
+    return d;
+}
+
+// A hook's policy words through its feature's key table (vt_feature_keys.hpp): VT_OK and *pol filled, or the refusal of the
+// first word the table refuses, in the words every hook uses
+template <class Pol, int N>
+static inline int policy_from_words(const char* hook, const vtkeys::Key (&rows)[N], vtkeys::Apply apply, const Pol& def,
+                                    const int32_t* policy, Pol* pol) {
+    static_assert(sizeof(Pol) <= sizeof(int32_t) * vtkeys::kMaxWords, "a policy is at most kMaxWords words");
+    int32_t words[vtkeys::kMaxWords] = {};
+    const int bad = vtkeys::check_words(rows, apply, reinterpret_cast<const int32_t*>(&def), policy, words);
+    if (bad >= 0)
+        return set_err(VT_ERR_INVALID_ARG, "%s: policy word %d (%s) = %d refused", hook, rows[bad].word, rows[bad].key,
+                       (int)policy[rows[bad].word]);
+    memcpy(pol, words, sizeof(Pol));
+    return VT_OK;
+}
+
+// The frames of an in-the-pass launch, one per slot: check() refuses what check_frame refuses and keeps the descriptors and
+// the highest pixel level among the formats; upload() is the last step before the launches.
+struct HookFrames {
+    std::vector<FrameDesc> desc;
+    int level = 0;
+    DevArr dfr, dflag;
+    int check(const vt_frame* frames, int n) {
+        desc.resize((size_t)n);
+        for (int b = 0; b < n; ++b) {
+            if (int rc = check_frame(frames[b])) return rc;
+            to_desc(frames[b], &desc[(size_t)b]);
+            level = std::max(level, pix_level(frames[b].format));
+        }
+        return VT_OK;
+    }
+    hipError_t upload(int device_frames = 1) {
+        const int32_t flag = device_frames != 0;
+        hipError_t e = dfr.upload(desc.data(), desc.size() * sizeof(FrameDesc));
+        if (e == hipSuccess) e = dflag.upload(&flag, 4);
+        return e != hipSuccess ? e : hipDeviceSynchronize();    // the caller's frames may have been filled on another stream
+    }
+    const FrameDesc* dev() const { return dfr.as<const FrameDesc>(); }
+    const int32_t* dev_flag() const { return dflag.as<const int32_t>(); }
+};
+
 // The two optional maps of an in-the-pass launch over n slots: slot_stream (slot -> stream < n_streams) and winner (a
-// candidate pass's winner table, entries < n). check(hook, b) is VT_OK or the refusal of slot b, under the hook's name.
+// candidate pass's winner table, entries < n). check_all(hook) is VT_OK or the first refusal, under the hook's name.
 struct SlotMaps {
     const int32_t *slot_stream, *winner;
     int n, n_streams;
     DevArr dmap, dwin;
-    int check(const char* hook, int b) const {
-        if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_streams))
-            return set_err(VT_ERR_INVALID_ARG, "%s: slot %d names stream %d of %d", hook, b, (int)slot_stream[b], n_streams);
-        if (winner && (winner[b] < 0 || winner[b] >= n))
-            return set_err(VT_ERR_INVALID_ARG, "%s: winner[%d] = %d of %d slots", hook, b, (int)winner[b], n);
+    // noun: what the hook calls the records a stream indexes; without a map, slot b is stream b
+    int check_all(const char* hook, const char* noun = "streams") const {
+        if (!slot_stream && n_streams < n) return set_err(VT_ERR_INVALID_ARG, "%s: %d %s for %d slots", hook, n_streams, noun, n);
+        for (int b = 0; b < n; ++b) {
+            if (slot_stream && (slot_stream[b] < 0 || slot_stream[b] >= n_streams))
+                return set_err(VT_ERR_INVALID_ARG, "%s: slot %d names stream %d of %d", hook, b, (int)slot_stream[b], n_streams);
+            if (winner && (winner[b] < 0 || winner[b] >= n))
+                return set_err(VT_ERR_INVALID_ARG, "%s: winner[%d] = %d of %d slots", hook, b, (int)winner[b], n);
+        }
+        return VT_OK;
+    }
+    // after check_all: outside a candidate pass (no winner table) no stream has two writers - two slots of one stream would
+    // write the same record, state and counters from two workgroups. twice: the hook's words for it
+    int check_unique(const char* hook, const char* twice) const {
+        if (!slot_stream || winner) return VT_OK;
+        std::vector<char> named((size_t)n_streams, 0);
+        for (int b = 0; b < n; ++b) {
+            if (named[(size_t)slot_stream[b]]) return set_err(VT_ERR_INVALID_ARG, "%s: stream %d %s", hook, (int)slot_stream[b], twice);
+            named[(size_t)slot_stream[b]] = 1;
+        }
         return VT_OK;
     }
     hipError_t upload() {

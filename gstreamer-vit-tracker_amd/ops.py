@@ -109,6 +109,36 @@ def _arr(a, dtype):
     return None if a is None else np.ascontiguousarray(a, dtype)
 
 
+def _frames(frames):
+    """the frames of the slots as one C array -> (n, array)"""
+    n = len(frames)
+    return n, (CFrame * n)(*frames)
+
+
+def _maps(n, slot_stream, winner=None):
+    """the two optional maps of n slots: slot -> stream, and a candidate pass's winner table"""
+    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
+    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
+    return smap, win
+
+
+def _start(a, dtype, shape=None, fill=0):
+    """an array a hook starts from and writes into, as a copy of the caller's a or (None) every byte `fill`. shape (n,): n
+    records, flattened from whatever shape they come in; shape None: records, however many"""
+    if a is None:
+        return np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, fill, np.uint8).view(dtype).reshape(shape)
+    r = np.ascontiguousarray(a, dtype).copy()
+    if shape is None or len(shape) == 1:
+        r = r.reshape(-1)
+    assert shape is None or r.shape == tuple(shape)
+    return r
+
+
+def _mirror(host, dtype, n):
+    """what a pinned mirror of n records holds before the call; None: that mirror is null"""
+    return None if host is None else _start(host, dtype, (n,))
+
+
 def _timed(fn, *args) -> float:
     """a timing hook's value: its trailing us_out"""
     us = c_float()
@@ -328,17 +358,15 @@ def op_head_decode(t_bf16_bits, w4, b4, hann, states, B, grid, form=0, w3_bf16_b
     b4 = np.ascontiguousarray(b4, np.float32)
     hann = np.ascontiguousarray(hann, np.float32).reshape(-1)
     assert w4.shape == (8, C) and b4.shape == (8,) and hann.shape == (ns,)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    st = _start(states, STATE)
     w3 = b3a = None
     if form == 1:
         w3 = np.ascontiguousarray(w3_bf16_bits, np.uint16)
         b3a = np.ascontiguousarray(b3, np.float32)
         assert w3.shape == (C, 9 * C) and b3a.shape == (C,)
-    smap = _arr(slot_stream, np.int32)
-    assert smap is None or smap.shape == (B,)
+    smap, _ = _maps(B, slot_stream)
     out = dict(head_out=np.empty((B * ns, 8), np.float32), results=np.zeros(B, RESULT_DTYPE),
-               host_results=np.frombuffer(bytes([mirror_fill]) * (B * RESULT_DTYPE.itemsize), RESULT_DTYPE).copy(),
-               host_states=np.frombuffer(bytes([mirror_fill]) * (len(st) * STATE.itemsize), STATE).copy(),
+               host_results=_start(None, RESULT_DTYPE, (B,), mirror_fill), host_states=_start(None, STATE, (len(st),), mirror_fill),
                band_cnt=np.full(B, 0xFFFFFFFF, np.uint32))
     flags = (0 if host_results else 1) | (0 if host_states else 2)
     _check_op(ops_lib().vt_op_head_decode(
@@ -368,17 +396,15 @@ def op_response_peaks(head_out, hann, states, policies, B, grid, slot_stream=Non
     assert ho.shape == (B * ns, 8)
     hann = np.ascontiguousarray(hann, np.float32).reshape(-1)
     assert hann.shape == (ns,)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    st = _start(states, STATE)
     if isinstance(policies, tuple):
         pol = np.zeros(len(st), PEAKS_POLICY_DTYPE)
         pol["max_peaks"], pol["radius"], pol["min_resp"] = policies
     else:
         pol = np.ascontiguousarray(policies, PEAKS_POLICY_DTYPE).reshape(-1)
     assert len(pol) == len(st)
-    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
-    assert (smap is None or smap.shape == (B,)) and (win is None or win.shape == (B,))
-    fill = lambda: np.frombuffer(bytes([mirror_fill]) * (B * PEAKS_DTYPE.itemsize), PEAKS_DTYPE).copy()
-    out = dict(records=fill(), host_records=fill())
+    smap, win = _maps(B, slot_stream, winner)
+    out = dict(records=_start(None, PEAKS_DTYPE, (B,), mirror_fill), host_records=_start(None, PEAKS_DTYPE, (B,), mirror_fill))
     _check_op(ops_lib().vt_op_response_peaks(
         device, _f32(ho), _f32(hann), _vp(st), len(st), _vp(pol), _opt(smap, _i32), _opt(win, _i32),
         B, grid, _vp(out["records"]), _vp(out["host_records"])))
@@ -399,17 +425,14 @@ def op_motion_prior(states, records, results, on=1, gain_pct=50, coast=5, max_pc
     slot, slot_stream [n]: slot -> stream (None: the identity); the candidate form: cands [n] CANDIDATE_DTYPE + winner [n].
     host_states / host_records: what the pinned mirrors hold before (None: that mirror is null). -> dict(states, records,
     host_states, host_records) as they came back"""
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
-    rec = np.ascontiguousarray(records, MOTION_REC_DTYPE).reshape(-1).copy()
-    assert len(rec) == len(st)
+    st = _start(states, STATE)
+    rec = _start(records, MOTION_REC_DTYPE, (len(st),))
     res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
     n = len(res)
-    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
+    smap, win = _maps(n, slot_stream, winner)
     cd = None if cands is None else np.ascontiguousarray(cands, CANDIDATE_DTYPE).reshape(-1)
-    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,)) and (cd is None or cd.shape == (n,))
-    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
-    hrec = None if host_records is None else np.ascontiguousarray(host_records, MOTION_REC_DTYPE).reshape(-1).copy()
-    assert (hst is None or len(hst) == len(st)) and (hrec is None or len(hrec) == len(st))
+    assert cd is None or cd.shape == (n,)
+    hst, hrec = _mirror(host_states, STATE, len(st)), _mirror(host_records, MOTION_REC_DTYPE, len(st))
     pol = np.array([on, gain_pct, coast, max_pct], np.int32)
     _check_op(ops_lib().vt_op_motion_prior(
         device, _vp(st), _vp(rec), len(st), _i32(pol), _vp(res), _opt(smap, _i32), _opt(win, _i32), _opt(cd, _vp), n, stages,
@@ -445,23 +468,22 @@ def op_proposals(frames, states, results, tpl, T, patch, norm, mode=2, period=1,
     nt, kpad] uint16 bf16 bit patterns; norm: (a0, a1, a2, b0, b1, b2). -> dict(pattern [n, 256] int16, thumb [n, max_cells]
     int16, map [n, max_cells] float32, records [n_streams] PROPOSALS_REC_DTYPE, evaluated [n_streams] int32); what no
     launch stored is 0xff bytes"""
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
-    st = np.ascontiguousarray(states, STATE).reshape(-1)
+    n, arr = _frames(frames)
+    st = _start(states, STATE)
     ns = len(st)
     res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
     assert res.shape == (n,)
     t = np.ascontiguousarray(tpl, np.uint16)
     kpad = t.shape[-1]
     assert t.size == ns * tpl_bufs * (T // patch) ** 2 * kpad
-    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
+    smap, win = _maps(n, slot_stream, winner)
     nrm = np.ascontiguousarray(norm, np.float32).reshape(6)
     pol = np.array([mode, period, max_n, min_sim_pm, 0, max_cells, 0, 0], np.int32)
     pattern = np.empty((n, 256), np.int16)
     thumb = np.empty((n, max_cells), np.int16)
     smap_out = np.empty((n, max_cells), np.float32)
     recs = np.empty(ns, PROPOSALS_REC_DTYPE)
-    ev = np.zeros(ns, np.int32) if evaluated is None else np.ascontiguousarray(evaluated, np.int32).copy()
+    ev = _start(evaluated, np.int32, (ns,))
     _check_op(ops_lib().vt_op_proposals(
         device, arr, _vp(st), ns, _vp(res), _opt(smap, _i32), _opt(win, _i32), n, _vp(t), tpl_bufs, T, patch, kpad, _vp(nrm),
         _vp(pol), 1 if device_frames else 0, _vp(pattern), _vp(thumb), _vp(smap_out), _vp(recs), _vp(ev)))
@@ -474,6 +496,7 @@ CAMERA_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("c", "<
                              ("S0", "<i8"), ("S2", "<i8"), ("evaluated", "<i4"), ("moved", "<i4"), ("has_prev", "<i4"), ("cur", "<i4"),
                              ("pW", "<i4"), ("pH", "<i4"), ("pc", "<i4"), ("reserved", "<i4")])
 CAMERA_TABLE = 33 * 33
+assert CAMERA_REC_DTYPE.itemsize == 104
 
 
 def op_camera_motion(frames, states, mode=2, cell=0, rng=8, conf_pm=800, max_cells=65536, slot_stream=None, thumbs=None, records=None,
@@ -484,19 +507,13 @@ def op_camera_motion(frames, states, mode=2, cell=0, rng=8, conf_pm=800, max_cel
     previous thumbnail); host_states / host_records: what the pinned mirrors hold before (None: that mirror is null).
     -> dict(states, thumbs, records, sad [n_streams, 1089] int64 - what no launch stored is 0xff bytes -, host_states,
     host_records) as they came back; feed thumbs and records to the next call to go on"""
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    n, arr = _frames(frames)
+    st = _start(states, STATE)
     ns = len(st)
-    smap = _arr(slot_stream, np.int32)
-    assert smap is None or smap.shape == (n,)
-    th = np.zeros((ns, 2, max_cells), np.uint16) if thumbs is None else np.ascontiguousarray(thumbs, np.uint16).copy()
-    assert th.shape == (ns, 2, max_cells)
-    rec = np.zeros(ns, CAMERA_REC_DTYPE) if records is None else np.ascontiguousarray(records, CAMERA_REC_DTYPE).reshape(-1).copy()
-    assert len(rec) == ns and CAMERA_REC_DTYPE.itemsize == 104
-    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
-    hrec = None if host_records is None else np.ascontiguousarray(host_records, CAMERA_REC_DTYPE).reshape(-1).copy()
-    assert (hst is None or len(hst) == ns) and (hrec is None or len(hrec) == ns)
+    smap, _ = _maps(n, slot_stream)
+    th = _start(thumbs, np.uint16, (ns, 2, max_cells))
+    rec = _start(records, CAMERA_REC_DTYPE, (ns,))
+    hst, hrec = _mirror(host_states, STATE, ns), _mirror(host_records, CAMERA_REC_DTYPE, ns)
     pol = np.array([mode, cell, rng, conf_pm, max_cells, 0, 0, 0], np.int32)
     sad = np.empty((ns, CAMERA_TABLE), np.int64)
     _check_op(ops_lib().vt_op_camera_motion(
@@ -514,6 +531,7 @@ HEALTH_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("flagged", "<i4"), ("gated
 HEALTH_HEAD_DTYPE = np.dtype([("status", "<i4"), ("stream", "<i4"), ("frames_done", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"),
                               ("cur", "<i4"), ("reserved", "<i4")])
 _HEALTH_BINS = 32      # a record's flags: 1 FROZEN, 2 FLAT, 4 CUT
+assert HEALTH_REC_DTYPE.itemsize == 104 and HEALTH_HEAD_DTYPE.itemsize == 32
 
 
 def op_frame_health(frames, states, on=1, period=1, cell=0, still_run=3, flat_q=32, cut_pm=500, gate=0, max_cells=65536,
@@ -526,20 +544,13 @@ def op_frame_health(frames, states, on=1, period=1, cell=0, still_run=3, flat_q=
     previous thumbnail); host_records: what the pinned mirror holds before (None: the mirror is null). -> dict(states,
     thumbs, hist, records, counts, accs [n_streams, 4] int64 = S1, S2, G, D - 0xff bytes where no launch stored -, heads [n]
     HEALTH_HEAD_DTYPE, host_records) as they came back; feed thumbs, hist, records and counts to the next call to go on"""
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    n, arr = _frames(frames)
+    st = _start(states, STATE)
     ns = len(st)
-    smap = _arr(slot_stream, np.int32)
-    assert smap is None or smap.shape == (n,)
-    th = np.full((ns, 2, max_cells), 0xFFFF, np.uint16) if thumbs is None else np.ascontiguousarray(thumbs, np.uint16).copy()
-    hi = np.full((ns, 2, _HEALTH_BINS), -1, np.int32) if hist is None else np.ascontiguousarray(hist, np.int32).copy()
-    assert th.shape == (ns, 2, max_cells) and hi.shape == (ns, 2, _HEALTH_BINS)
-    rec = np.zeros(ns, HEALTH_REC_DTYPE) if records is None else np.ascontiguousarray(records, HEALTH_REC_DTYPE).reshape(-1).copy()
-    cnt = np.zeros(ns, HEALTH_COUNT_DTYPE) if counts is None else np.ascontiguousarray(counts, HEALTH_COUNT_DTYPE).reshape(-1).copy()
-    assert len(rec) == ns and len(cnt) == ns and HEALTH_REC_DTYPE.itemsize == 104 and HEALTH_HEAD_DTYPE.itemsize == 32
-    hrec = None if host_records is None else np.ascontiguousarray(host_records, HEALTH_REC_DTYPE).reshape(-1).copy()
-    assert hrec is None or len(hrec) == ns
+    smap, _ = _maps(n, slot_stream)
+    th, hi = _start(thumbs, np.uint16, (ns, 2, max_cells), 0xff), _start(hist, np.int32, (ns, 2, _HEALTH_BINS), 0xff)
+    rec, cnt = _start(records, HEALTH_REC_DTYPE, (ns,)), _start(counts, HEALTH_COUNT_DTYPE, (ns,))
+    hrec = _mirror(host_records, HEALTH_REC_DTYPE, ns)
     pol = np.array([on, period, cell, still_run, flat_q, cut_pm, gate, max_cells], np.int32)
     accs = np.empty((ns, 4), np.int64)
     heads = np.empty(n, HEALTH_HEAD_DTYPE)
@@ -555,6 +566,7 @@ ARBITRATE_PEAK_DTYPE = np.dtype([("cell", "<i4"), ("status", "<i4"), ("score", "
 ARBITRATE_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n", "<i4"), ("chosen", "<i4"),
                                 ("peak", ARBITRATE_PEAK_DTYPE, 4)])
 ARBITRATE_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("switched", "<i4")])
+assert ARBITRATE_REC_DTYPE.itemsize == 176
 
 
 def op_arbitrate(head_out, hann, frames, states, results, anchor, grid, T, S, patch, norm, success_threshold, on=1, max_peaks=3,
@@ -567,33 +579,27 @@ def op_arbitrate(head_out, hann, frames, states, results, anchor, grid, T, S, pa
     ARBITRATE_COUNT_DTYPE to start from (None: zeros); host_*: what the pinned mirrors hold before (None: that mirror is null).
     -> dict(states, results, records [n_streams] ARBITRATE_REC_DTYPE, probe [n_streams, 4, nt, kpad] uint16 - both 0xff bytes
     where no launch stored -, counts, host_results, host_states, host_records) as they came back"""
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
+    n, arr = _frames(frames)
     ns = grid * grid
     ho = np.ascontiguousarray(head_out, np.float32)
     assert ho.shape == (n * ns, 8)
     hn = np.ascontiguousarray(hann, np.float32).reshape(-1)
     assert hn.shape == (ns,)
-    st = np.ascontiguousarray(states, STATE).reshape(-1).copy()
+    st = _start(states, STATE)
     nst = len(st)
-    res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1).copy()
-    assert res.shape == (n,)
+    res = _start(results, RESULT_DTYPE, (n,))
     an = np.ascontiguousarray(anchor, np.uint16)
     nt = (T // patch) ** 2
     assert an.ndim == 3 and an.shape[:2] == (nst, nt)
     kpad = an.shape[2]
-    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
-    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
+    smap, win = _maps(n, slot_stream, winner)
     nrm = np.ascontiguousarray(norm, np.float32).reshape(6)
     pol = np.array([on, max_peaks, radius, min_resp_pm, low_pm, high_pm, 0, 0], np.int32)
     rec = np.empty(nst, ARBITRATE_REC_DTYPE)
-    cnt = np.zeros(nst, ARBITRATE_COUNT_DTYPE) if counts is None else np.ascontiguousarray(counts, ARBITRATE_COUNT_DTYPE).reshape(-1).copy()
+    cnt = _start(counts, ARBITRATE_COUNT_DTYPE, (nst,))
     probe = np.empty((nst, 4, nt, kpad), np.uint16)
-    hres = None if host_results is None else np.ascontiguousarray(host_results, RESULT_DTYPE).reshape(-1).copy()
-    hst = None if host_states is None else np.ascontiguousarray(host_states, STATE).reshape(-1).copy()
-    hrec = None if host_records is None else np.ascontiguousarray(host_records, ARBITRATE_REC_DTYPE).reshape(-1).copy()
-    assert len(cnt) == nst and (hres is None or len(hres) == n) and (hst is None or len(hst) == nst) and (hrec is None or len(hrec) == nst)
-    assert ARBITRATE_REC_DTYPE.itemsize == 176
+    hres, hst = _mirror(host_results, RESULT_DTYPE, n), _mirror(host_states, STATE, nst)
+    hrec = _mirror(host_records, ARBITRATE_REC_DTYPE, nst)
     _check_op(ops_lib().vt_op_arbitrate(
         device, _f32(ho), _f32(hn), arr, _vp(st), nst, _vp(res), _opt(smap, _i32), _opt(win, _i32), n, grid, _vp(an), T, S, patch,
         kpad, _f32(nrm), c_float(success_threshold), _i32(pol), tier, _vp(rec), _vp(cnt), _vp(probe), _opt(hres, _vp),
@@ -601,11 +607,11 @@ def op_arbitrate(head_out, hann, frames, states, results, anchor, grid, T, S, pa
     return dict(states=st, results=res, records=rec, probe=probe, counts=cnt, host_results=hres, host_states=hst, host_records=hrec)
 
 
-# the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)
 # the stream conflicts' records (csrc/vt_common.hpp: ConflictRec 48 bytes and ConflictCount 16 bytes, both by stream)
 CONFLICT_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n_over", "<i4"), ("reserved", "<i4"),
                                ("partner", "<i4", 4), ("iou", "<f4", 4)])
 CONFLICT_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("conflicting", "<i4"), ("gated", "<i4"), ("reserved", "<i4")])
+assert CONFLICT_REC_DTYPE.itemsize == 48
 
 
 def op_stream_conflicts(states, results, scenes, on=1, iou_pm=300, gate=0, slot_stream=None, winner=None, records=None, counts=None,
@@ -616,21 +622,15 @@ def op_stream_conflicts(states, results, scenes, on=1, iou_pm=300, gate=0, slot_
     [n_streams] CONFLICT_REC_DTYPE and counts [n_streams] CONFLICT_COUNT_DTYPE to start from (None: every byte `fill`);
     host_records: what the pinned mirror holds before (None: the mirror is null). -> dict(records, counts, host_records) as
     they came back"""
-    st = np.ascontiguousarray(states, STATE).reshape(-1)
+    st = _start(states, STATE)
     ns = len(st)
     res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
     n = len(res)
     sc = np.ascontiguousarray(scenes, np.int32).reshape(-1)
-    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
-    assert sc.shape == (ns,) and (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
-
-    def start(a, dtype):
-        if a is None:
-            return np.frombuffer(bytes([fill]) * (ns * dtype.itemsize), dtype).copy()
-        return np.ascontiguousarray(a, dtype).reshape(-1).copy()
-    rec, cnt = start(records, CONFLICT_REC_DTYPE), start(counts, CONFLICT_COUNT_DTYPE)
-    hrec = None if host_records is None else np.ascontiguousarray(host_records, CONFLICT_REC_DTYPE).reshape(-1).copy()
-    assert len(rec) == ns and len(cnt) == ns and (hrec is None or len(hrec) == ns) and CONFLICT_REC_DTYPE.itemsize == 48
+    smap, win = _maps(n, slot_stream, winner)
+    assert sc.shape == (ns,)
+    rec, cnt = _start(records, CONFLICT_REC_DTYPE, (ns,), fill), _start(counts, CONFLICT_COUNT_DTYPE, (ns,), fill)
+    hrec = _mirror(host_records, CONFLICT_REC_DTYPE, ns)
     pol = np.array([on, iou_pm, gate, 0, 0, 0, 0, 0], np.int32)
     _check_op(ops_lib().vt_op_stream_conflicts(
         device, _vp(st), ns, _vp(res), _opt(smap, _i32), _opt(win, _i32), n, _i32(sc), _i32(pol), _vp(rec), _vp(cnt),
@@ -638,6 +638,7 @@ def op_stream_conflicts(states, results, scenes, on=1, iou_pm=300, gate=0, slot_
     return dict(records=rec, counts=cnt, host_records=hrec)
 
 
+# the 32-byte records of the result overlay (csrc/k_result_overlay.hpp)
 OVERLAY_POLICY_DTYPE = np.dtype([("flags", "<i4"), ("thickness", "<i4"), ("size", "<i4"), ("scale", "<i4"), ("luma", "<i4"),
                                  ("rgb", "<i4"), ("min_score_pct", "<i4"), ("reserved", "<i4")])
 OVERLAY_STATS_DTYPE = np.dtype([("drawn", "<i4"), ("n_drawn", "<i4"), ("n_gated", "<i4"), ("n_unsupported", "<i4"),
@@ -651,16 +652,13 @@ def op_result_overlay(frames, results, flags=7, thickness=3, size=15, scale=2, l
     (None: the identity), winner [n]: a candidate pass's winner table (None: every slot may draw), stats: OVERLAY_STATS_DTYPE
     records by stream to start from (None: zeros), device_frames False: the launch of a host pass. -> the stats as they
     came back"""
-    n = len(frames)
-    arr = (CFrame * n)(*frames)
+    n, arr = _frames(frames)
     res = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
     assert res.shape == (n,)
-    smap, win = _arr(slot_stream, np.int32), _arr(winner, np.int32)
-    assert (smap is None or smap.shape == (n,)) and (win is None or win.shape == (n,))
+    smap, win = _maps(n, slot_stream, winner)
     if n_streams is None:
         n_streams = n if stats is None else len(stats)
-    st = np.zeros(n_streams, OVERLAY_STATS_DTYPE) if stats is None else np.ascontiguousarray(stats, OVERLAY_STATS_DTYPE).reshape(-1).copy()
-    assert len(st) == n_streams
+    st = _start(stats, OVERLAY_STATS_DTYPE, (n_streams,))
     pol = np.zeros(1, OVERLAY_POLICY_DTYPE)
     pol[0] = (flags, thickness, size, scale, luma, rgb, min_score_pct, 0)
     _check_op(ops_lib().vt_op_result_overlay(

@@ -21,6 +21,10 @@ static const int32_t kOverlayDef[8] = {0, 3, 15, 2, 255, 0x00FF00, 25, 0};
 static const int32_t kMotionDef[8] = {0, 50, 5, 100, 0, 0, 0, 0};
 static const int32_t kAppearDef[8] = {0, 1, 0, 0 /* 0.0f */, 0, 0, 0, 0};
 static const int32_t kPropDef[8] = {0, 1, 4, 500, 0x3F000000 /* 0.5f */, 262144, 0, 0};
+static const int32_t kConflictDef[8] = {0, 300, 0, 0x3E99999A /* 0.3f */, 0, 0, 0, 0};
+static const int32_t kCameraDef[8] = {0, 0, 8, 800, 65536, 0, 0, 0};
+static const int32_t kHealthDef[8] = {0, 1, 0, 3, 32, 500, 0, 65536};
+static const int32_t kArbDef[8] = {0, 3, 2, 50, 300, 500, 0, 0};
 
 // one key as the engine's callers know it: bounds, and the texts one past each bound (null: a value below is the default)
 struct Want { const char* key; int32_t lo, hi; const char* below; const char* above; };
@@ -87,6 +91,42 @@ static void table(const char* name, const Key (&rows)[N], const Want (&want)[M],
     scramble(w); scramble(before);
     CHECK(apply(unknown, 1, def, w, false, text, sizeof(text)) == UNKNOWN && same(w, before), "%s: '%s' is not unknown", name, unknown);
     CHECK(apply("", 1, def, w, true, text, sizeof(text)) == UNKNOWN && same(w, before), "%s: the empty key is not unknown", name);
+}
+
+// check_words: the policy words of an operator hook through a table. Every row's lo and hi are legal values of these five
+// tables (the cell keys: 0 and 32). pm, tau: the word of a per-mille key and the word its threshold lands in, or -1
+template <int N>
+static void hook_words(const char* name, const Key (&rows)[N], Apply apply, const int32_t* def, int pm, int tau) {
+    int32_t pol[kMaxWords], w[kMaxWords], want[kMaxWords];
+    for (const bool high : {false, true}) {
+        memset(pol, 0, sizeof(pol));
+        for (const Key& k : rows) pol[k.word] = high ? k.hi : k.lo;
+        memcpy(want, pol, sizeof(want));
+        if (pm >= 0) want[tau] = bits_of((float)pol[pm] / 1000.0f);
+        memset(w, 0, sizeof(w));
+        CHECK(check_words(rows, apply, def, pol, w) == -1 && same(w, want), "%s: the %s bounds are not taken as they are", name, high ? "upper" : "lower");
+    }
+    for (int i = 0; i < N; ++i) {
+        for (const int32_t v : {rows[i].lo - 1, rows[i].hi + 1, -1, -7}) {      // a hook takes no "default": a negative word is refused
+            for (const Key& k : rows) pol[k.word] = k.lo;
+            pol[rows[i].word] = v;
+            CHECK(check_words(rows, apply, def, pol, w) == i, "%s: %s = %d is not refused at row %d", name, rows[i].key, (int)v, i);
+            pol[rows[N - 1].word] = rows[N - 1].hi + 1;     // a second bad word behind it: the lower row is named
+            CHECK(check_words(rows, apply, def, pol, w) == i, "%s: %s = %d and a bad last word: not row %d", name, rows[i].key, (int)v, i);
+        }
+    }
+}
+
+static void hook_cells() {      // neither 0 nor a power of two in 4..32
+    int32_t pol[kMaxWords], w[kMaxWords];
+    for (const int32_t cell : {1, 2, 3, 5, 12, 31}) {
+        memcpy(pol, kCameraDef, sizeof(pol)); pol[CM_CELL] = cell;
+        CHECK(check_words(kCameraKeys, apply_camera_motion, kCameraDef, pol, w) == CM_CELL, "camera_motion_cell %d", (int)cell);
+        memcpy(pol, kHealthDef, sizeof(pol)); pol[HL_CELL] = cell;
+        CHECK(check_words(kHealthKeys, apply_health, kHealthDef, pol, w) == HL_CELL, "health_cell %d", (int)cell);
+    }
+    memcpy(pol, kHealthDef, sizeof(pol));       // the defaults themselves pass, as the words they are
+    CHECK(check_words(kHealthKeys, apply_health, kHealthDef, pol, w) == -1 && same(w, kHealthDef), "the health defaults");
 }
 
 static void derived() {
@@ -166,6 +206,12 @@ int main() {
     derived();
     style();
     frozen_max_cells();
+    hook_words("motion prior", kMotionKeys, apply_motion, kMotionDef, -1, -1);
+    hook_words("stream conflicts", kConflictKeys, apply_conflicts, kConflictDef, CF_IOU_PM, CF_TAU);
+    hook_words("camera motion", kCameraKeys, apply_camera_motion, kCameraDef, -1, -1);
+    hook_words("frame health", kHealthKeys, apply_health, kHealthDef, -1, -1);
+    hook_words("peak arbitration", kArbKeys, apply_arbitrate, kArbDef, -1, -1);
+    hook_cells();
     int32_t w[kMaxWords];
     char text[256];
     CHECK(apply_appearance("appearance_anchor", 0, kAppearDef, w, true, text, sizeof(text)) == UNKNOWN, "the anchor action is no field of the table");

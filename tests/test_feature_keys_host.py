@@ -1,5 +1,5 @@
 """The key tables of the keyed optional features (csrc/vt_feature_keys.hpp: bounds, defaults, refusal texts, the derived
-thresholds, the packed overlay style, the frozen thumbnail size) in a stand-alone program of its own,
+thresholds, the packed overlay style, the frozen thumbnail size, the operator hooks' check_words) in a stand-alone program of its own,
 tests/feature_keys_main.cpp, compiled with AddressSanitizer and UndefinedBehaviorSanitizer and run as a child process.
 No GPU, nothing loaded into Python."""
 import os
