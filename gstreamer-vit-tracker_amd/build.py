@@ -58,7 +58,17 @@ EXTRA_FLAGS = {"k_gemm256.hip": ["-fno-slp-vectorize"]}
 HOST_SOURCES = ["host_capi.cpp"]
 # translation units whose build identity the library reports (vt_build_info): committed PMC summaries name it, and
 # bench.py prints their traffic only for the kernel build they were collected on
-STAMPED = {"k_gemm256.hip": ["k_gemm256.hip", "k_gemm_util.hpp", "vt_common.hpp"]}
+# Each list is exactly the include closure of its translation unit - the file and every csrc header reachable from it
+# (tests/test_header_layout.py follows the include lines) - so the identity moves when the kernel's own text moves, and only then.
+STAMPED = {"k_gemm256.hip": ["k_gemm256.hip", "k_gemm.hpp", "k_attn.hpp", "k_gemm_util.hpp", "k_ln_dev.hpp", "vt_common.hpp"]}
+# every header and .inc of csrc/: a change to ANY of them rebuilds every translation unit (a stale object is a silent
+# wrong-library failure; per-unit dependencies are not tracked)
+HEADERS = ["vt_common.hpp", "vt_frame.hpp", "vt_engine.hpp", "vt_ops_host.hpp", "vt_ops_util.hpp", "vt_feature_keys.hpp",
+           "k_gemm.hpp", "k_gemm_util.hpp", "k_ln_dev.hpp", "k_misc.hpp", "k_attn.hpp", "k_head.hpp",
+           "k_preproc.hpp", "k_preproc_dev.hpp", "k_preproc_body.inc", "k_thumb_dev.hpp", "k_overlay.hpp", "k_overlay_dev.hpp",
+           "k_refresh.hpp", "k_refresh_dev.hpp", "k_refresh_crop.inc", "k_chip.hpp", "k_peaks.hpp", "k_peaks_dev.hpp",
+           "k_motion.hpp", "k_appearance.hpp", "k_appearance_dev.hpp", "k_arbitrate.hpp", "k_proposals.hpp",
+           "k_camera_motion.hpp", "k_conflicts.hpp", "k_health.hpp", "k_cand.hpp", "k_result_overlay.hpp", "k_snapshot.hpp"]
 
 
 def tu_sha256(source: str, flags: "list[str]") -> str:
@@ -99,12 +109,8 @@ def build_hip(force: bool = False, save_temps: bool = False, stamps: bool = Fals
         obj_dir = os.path.join(PKG, "build_" + variant)
         lib_hip, lib_ops = None, os.path.join(PKG, f"libvittrack_hip_{variant}.so")
     os.makedirs(obj_dir, exist_ok=True)
-    headers = [os.path.join(CSRC, "vt_common.hpp"), os.path.join(CSRC, "k_gemm_util.hpp"), os.path.join(CSRC, "vt_engine.hpp"), os.path.join(CSRC, "k_cand.hpp"), os.path.join(CSRC, "k_snapshot.hpp"),
-               os.path.join(CSRC, "k_preproc_dev.hpp"), os.path.join(CSRC, "k_thumb_dev.hpp"), os.path.join(CSRC, "k_overlay_dev.hpp"), os.path.join(CSRC, "k_result_overlay.hpp"), os.path.join(CSRC, "k_preproc_body.inc"),
-               os.path.join(CSRC, "k_refresh_dev.hpp"), os.path.join(CSRC, "k_refresh_crop.inc"),
-               os.path.join(CSRC, "k_peaks_dev.hpp"), os.path.join(CSRC, "k_appearance_dev.hpp"),
-               os.path.join(CSRC, "vt_ops_host.hpp"), os.path.join(CSRC, "vt_ops_util.hpp"), os.path.join(CSRC, "vt_feature_keys.hpp"),
-               os.path.join(PKG, "..", "include", "vittrack_hip.h"), os.path.join(PKG, "..", "include", "vittrack_hip_ops.h")]
+    headers = [os.path.join(CSRC, h) for h in HEADERS] + [
+        os.path.join(PKG, "..", "include", "vittrack_hip.h"), os.path.join(PKG, "..", "include", "vittrack_hip_ops.h")]
     objs, jobs = [], []
     for s in HIP_SOURCES + OPS_SOURCES:
         src = os.path.join(CSRC, s)

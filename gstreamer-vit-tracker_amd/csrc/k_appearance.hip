@@ -23,7 +23,7 @@
 // arbitration (k_arbitrate.hip) shares.
 //
 // Compiled like k_refresh.hip (-ffp-contract=off): one IEEE operation per source operation.
-#include "vt_common.hpp"
+#include "k_appearance.hpp"
 #include "k_refresh_dev.hpp"
 #include "k_appearance_dev.hpp"
 

@@ -21,7 +21,7 @@
 // words decode_box (k_head.hip) would have written had the chosen peak been the argmax.
 //
 // Compiled like k_refresh.hip (-ffp-contract=off, correctly rounded divide and sqrt): one IEEE operation per source operation.
-#include "vt_common.hpp"
+#include "k_arbitrate.hpp"
 #include "k_refresh_dev.hpp"
 #include "k_peaks_dev.hpp"
 #include "k_appearance_dev.hpp"

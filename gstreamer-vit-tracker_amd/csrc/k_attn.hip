@@ -26,7 +26,7 @@
 // Keys >= tokens (padding of the last tile) are masked to -inf; Vt padding is zero.
 #include <cstdlib>
 
-#include "vt_common.hpp"
+#include "k_attn.hpp"
 #include "k_gemm_util.hpp"
 
 __device__ __forceinline__ bf16x8_t ld16(const bf16_t* p) {

@@ -25,7 +25,7 @@
 //
 // Only the option's own buffers and (mode 2) box[0], box[1] of the stream's state are written. Compiled like k_motion.hip
 // (-ffp-contract=off, correctly rounded division): one IEEE operation per source operation.
-#include "vt_common.hpp"
+#include "k_camera_motion.hpp"
 #include "k_thumb_dev.hpp"
 
 #pragma clang fp contract(off)

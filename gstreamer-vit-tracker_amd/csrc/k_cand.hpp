@@ -1,6 +1,7 @@
 // k_cand.hpp — launchers of the candidate-pass kernels (k_cand.hip), shared with the engine.
 #pragma once
 #include "vt_common.hpp"
+#include "vt_frame.hpp"
 
 // A candidate pass: slot i works for stream cands[i].stream, on a candidate state of its own. Crop and decode run on
 // cand_states with the identity slot map; the template gather keeps the slot -> stream map.

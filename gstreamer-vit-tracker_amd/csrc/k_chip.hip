@@ -11,7 +11,7 @@
 // is_template = 1: the body's own store then writes the planar [3][C][C] bf16 chip, and vto_preproc with the same
 // arguments is its oracle. The u8 kind keeps the bilinear value v of the same text (PRE_OUT) and stores packed RGB bytes
 // (PRE_STORE_RGB8). This file is compiled like k_preproc.hip (-ffp-contract=off).
-#include "vt_common.hpp"
+#include "k_chip.hpp"
 #include "k_preproc_dev.hpp"
 
 // a lane's run of 8 pixels as packed RGB: 24 bytes at a 24-byte stride (8-byte aligned: C is a multiple of 8), stored as

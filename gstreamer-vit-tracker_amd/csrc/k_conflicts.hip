@@ -13,7 +13,7 @@
 // Binary32 throughout, one IEEE operation per source operation: this file is built like k_motion.hip, with
 // -ffp-contract=off and correctly rounded division (build.py), and says so itself with the pragma below.
 // Plain vector stores, no atomics: exactly one lane works for a stream. Streams that are not in the pass are never read.
-#include "vt_common.hpp"
+#include "k_conflicts.hpp"
 
 #pragma clang fp contract(off)
 

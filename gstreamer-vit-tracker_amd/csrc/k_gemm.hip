@@ -21,7 +21,8 @@
 //     that the store side is wide: f32 outputs keep the column on the lane (128 B contiguous per
 //     row per store), bf16 row-major outputs put the ROW on the lane so each lane owns 4
 //     consecutive columns per accumulator quad (one 8-B store).
-#include "vt_common.hpp"
+#include "k_gemm.hpp"
+#include "k_attn.hpp"           // attn_perm16: the Vt key order of the QKV epilogue
 #include "k_gemm_util.hpp"
 
 #define GEMM_BK 64
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(WVM * WVN * 64 * (LW ? 2 : 1), 2) void gemm_bf16_ke
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
     if constexpr (EPI == EPI_F32_POS || EPI == EPI_RESID || EPI == EPI_F32) {
-        // ---- X-epilogues: the residual stream as the 3-byte pair (bf16 + lo8, vt_common.hpp) + chunk statistics ----
+        // ---- X-epilogues: the residual stream as the 3-byte pair (bf16 + lo8, k_gemm.hpp) + chunk statistics ----
         // The accumulators (row on the lane, 4 consecutive columns per register quad) are staged as a
         // float32 tile [BM][BN] in the dead operand ring (16-B chunk c of row r at c ^ (r & 7)) and written
         // out row-wise, 8 consecutive columns per lane: addend, bias, statistics of the 32-column chunk a

@@ -31,7 +31,8 @@
 // f32 outputs in four double-buffered quarters of 64 rows x 1 KiB (staging of one under the stores of the
 // one before; order and RAW / WAR argument at the X-epilogues below), bf16 outputs in one pass of 256 rows x 512 B.
 #include <type_traits>
-#include "vt_common.hpp"
+#include "k_gemm.hpp"
+#include "k_attn.hpp"           // attn_perm16: the Vt key order of the QKV epilogue
 #include "k_gemm_util.hpp"
 
 #define G256_BUF 65536
@@ -227,7 +228,7 @@ __device__ __forceinline__ void g256_mainloop2(const GemmArgs& p, char* smem, in
 }
 
 // REMAP (EPI_RESID only): the addend pair is p.Xh_in / p.Xl_in and, with p.seg_rows > 0, its rows are those of a
-// layout with p.seg_skip unread rows in front of every segment of p.seg_rows rows (GemmArgs, vt_common.hpp). A template
+// layout with p.seg_skip unread rows in front of every segment of p.seg_rows rows (GemmArgs, k_gemm.hpp). A template
 // parameter, so that every other X-epilogue launch runs the very code it ran before the remap existed.
 template <int EPI, bool REMAP = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         const unsigned long long xs_t1 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_sched_barrier(0);
 #endif
-        // ---- X-epilogues: the residual stream as the 3-byte pair (bf16 + lo8) + chunk statistics (vt_common.hpp) ----
+        // ---- X-epilogues: the residual stream as the 3-byte pair (bf16 + lo8) + chunk statistics (k_gemm.hpp) ----
         // Four QUARTERS q = 2i + h of 64 rows x 256 f32 (64 KiB), quarter (i, h) = accumulator blocks mf = 2h, 2h+1 of
         // rows i, staged alternately in the two 64-KiB halves of the dead ring (half q & 1): row qr = wr*32 + (mf&1)*16
         // + l15 of the quarter, 16-B chunk ch of the row stored at ch ^ (qr & 7) (qr & 7 = l15 & 7 as before the split:
@@ -528,7 +529,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p) {
         if (!v_tile) {
             g256_mainloop2<true>(p, smem, m0, n0, acc);
             // whole tile as [256 rows][512 B]; 8-B chunk c8 of row r stored at c8 ^ ((r & 7) << 1)
-            // folded LayerNorm (vt_common.hpp): y = a_r * acc + (b_r * colsum[n] + bias[n]); without one
+            // folded LayerNorm (k_gemm.hpp): y = a_r * acc + (b_r * colsum[n] + bias[n]); without one
             // a_r = 1, b_r = 0 and fma(1, acc, bias) = acc + bias exactly
             const bool ln = p.rowstat != nullptr;
             f32x4_t bias4[2][2], cs4[2][2];
@@ -922,7 +923,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmArgs p, int tiles, in
             int te = tid;
             asm volatile("" : "+v"(te));
             const int el = te & 63, e15 = el & 15, eq = el >> 4;
-            // folded LayerNorm (vt_common.hpp): y = a_r * acc + (b_r * colsum[n] + bias[n]); the row terms of
+            // folded LayerNorm (k_gemm.hpp): y = a_r * acc + (b_r * colsum[n] + bias[n]); the row terms of
             // the lane's eight rows (one per 16-row block), the bias and the column sums come from the
             // wave's staging area, where the DMA of the tile's top left them (inline-asm LDS reads, one
             // wait naming every destination: compiler-visible reads would be sunk into the pipelined

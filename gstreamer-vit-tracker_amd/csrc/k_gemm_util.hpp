@@ -1,6 +1,8 @@
 // k_gemm_util.hpp — device helpers shared by the GEMM kernels (k_gemm.hip, k_gemm256.hip).
 #pragma once
 #include "vt_common.hpp"
+#include "k_gemm.hpp"
+#include "k_ln_dev.hpp"
 
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
     __builtin_amdgcn_global_load_lds(
@@ -94,7 +96,7 @@ __device__ __forceinline__ u32x2_t gload_b64_asm(const void* p) {
 
 // sum over the four lanes of a quad (lanes 4k .. 4k+3), every lane gets the same bits: two DPP
 // quad_perm moves, no LDS traffic
-// (full EXEC required: see half_wave_sum in vt_common.hpp)
+// (full EXEC required: see half_wave_sum in k_ln_dev.hpp)
 __device__ __forceinline__ float quad_sum(float v) {
     const float a = v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
     return a + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0x4E, 0xF, 0xF, true));
@@ -114,7 +116,7 @@ __device__ __forceinline__ void x_chunk_stats(const float (&x)[8], float& sum, f
     sum = s;
     m2 = quad_sum(q);
 }
-// x_split8 / x_join8: the 3-byte residual pair, vt_common.hpp (shared with the LayerNorm readers)
+// x_split8 / x_join8: the 3-byte residual pair, k_ln_dev.hpp (shared with the LayerNorm readers)
 
 // value of the same lane of the other wave half (lane ^ 32): v_permlane32_swap, no LDS round trip
 __device__ __forceinline__ float other_half_f32(float v) {

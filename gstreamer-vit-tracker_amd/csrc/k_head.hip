@@ -28,7 +28,8 @@
 // Numerics: every output element is one MFMA accumulation chain over k = tap * C + c in ascending order,
 // bias added in f32, ReLU, round-to-nearest-even to bf16 - bit-identical to the implicit-GEMM kernel
 // (tests/test_gpu_ops.py). The decode is the float-op order of vto_decode (oracle/vt_oracle.c).
-#include "vt_common.hpp"
+#include "k_head.hpp"
+#include "k_ln_dev.hpp"
 #include "k_gemm_util.hpp"
 #include <algorithm>
 
@@ -236,7 +237,7 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t st) {
 // band's last cell and stores nothing for them. TAIL: + logits + decode (needs BN = N = C).
 // sum over the 16 lanes of a DPP row (lanes 16k .. 16k+15), every lane gets the same bits: two quad_perm moves,
 // row_half_mirror, row_mirror - no LDS round trip (a ds_bpermute butterfly was 20 dependent LDS trips per cell group)
-// (full EXEC required for row16_sum / row8_sum: see half_wave_sum in vt_common.hpp)
+// (full EXEC required for row16_sum / row8_sum: see half_wave_sum in k_ln_dev.hpp)
 __device__ __forceinline__ float row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
@@ -356,7 +357,7 @@ __global__ __launch_bounds__(512) void head_conv_kernel(HeadConvArgs p, DecodeAr
             const int D = p.K;
             const size_t tok0 = (size_t)b * p.in_stride + p.in_off + y0 * grid;
             u32x4_t rh[3][LNC];
-            u32x2_t rl[3][LNC];            // the row's lo8 bytes (3-byte residual pair, vt_common.hpp)
+            u32x2_t rl[3][LNC];            // the row's lo8 bytes (3-byte residual pair, k_gemm.hpp)
             auto fetch = [&](int it, int slot) {
                 int r = it * 16 + hwv;
                 r = r < cells ? r : cells - 1;

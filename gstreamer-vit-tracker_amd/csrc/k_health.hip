@@ -28,7 +28,8 @@
 // first use on: k_thumb_dev.hpp.) Launch dimensions depend on max_cells and
 // the slot count alone; workgroups of slots that are not measured, and those beyond Wg * Hg, leave at once from wave-uniform
 // loads of the header. Only the feature's own buffers are written.
-#include "vt_common.hpp"
+#include "k_health.hpp"
+#include "k_camera_motion.hpp"  // cam_auto_cell: the automatic cell is the camera motion's
 #include "k_thumb_dev.hpp"
 
 static constexpr int kHealthRecWords = sizeof(HealthRec) / 4;

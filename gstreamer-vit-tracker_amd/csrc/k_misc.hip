@@ -1,11 +1,12 @@
 // k_misc.hip — LayerNorm, row statistics and the LayerNorm fold for gfx950 (the head lives in k_head.hip).
-#include "vt_common.hpp"
+#include "k_misc.hpp"
+#include "k_ln_dev.hpp"
 #include <algorithm>
 
 // ---- LayerNorm: one wave per row, row kept in registers, two-pass variance -----------------------
-// Residual stream in (float32, or SPLIT: the 3-byte pair of the engine, x = xh + xl * lo_q: vt_common.hpp), bf16 GEMM
+// Residual stream in (float32, or SPLIT: the 3-byte pair of the engine, x = xh + xl * lo_q: k_gemm.hpp), bf16 GEMM
 // operand out. In the engine only the FINAL LayerNorm (search tokens, before the head) runs as a kernel:
-// the two LayerNorms of every block are folded into the GEMMs that consume them (vt_common.hpp).
+// the two LayerNorms of every block are folded into the GEMMs that consume them (k_gemm.hpp).
 // NCH = D / 128 float2 chunks per lane.
 template <int NCH, bool SPLIT>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x,

@@ -12,7 +12,7 @@
 // this file is built like the decode, with -ffp-contract=off and correctly rounded division and square root (build.py),
 // and says so itself with the pragma below.
 // Plain vector stores, no atomics: exactly one lane works for a stream.
-#include "vt_common.hpp"
+#include "k_motion.hpp"
 
 #pragma clang fp contract(off)
 

@@ -10,6 +10,7 @@
 // the closed forms of the reference's loops, including its usize wrap-around quirks (a rectangle
 // whose right edge x + w is negative extends to the last column). Bit-exact with
 // oracle/vt_oracle.c's line-by-line restatements.
+#include "k_overlay.hpp"
 #include "k_overlay_dev.hpp"     // covers, covers_rgb, glyph_bit and the glyph table
 
 __global__ __launch_bounds__(256) void overlay_kernel(uint8_t* __restrict__ yplane, int width,

@@ -4,6 +4,7 @@
 // wrap-around quirks; bit-exact with oracle/vt_oracle.c's line-by-line restatements.
 #pragma once
 #include "vt_common.hpp"
+#include "../../include/vittrack_hip.h"
 
 typedef unsigned long long u64;
 

@@ -12,7 +12,7 @@
 //
 // This file is compiled with k_head.hip's flags (one IEEE operation per source operation).
 // tests/test_gpu_response_peaks.py holds peak 0 to the decode's bits.
-#include "vt_common.hpp"
+#include "k_peaks.hpp"
 #include "k_peaks_dev.hpp"
 
 static_assert(sizeof(vt_peak) == 32 && sizeof(vt_peaks) == 272, "vt_peaks layout");

@@ -15,7 +15,7 @@
 // sqrt/div) and identical to oracle/vt_oracle.c, so the outputs agree bit for bit.
 #include <algorithm>
 
-#include "vt_common.hpp"
+#include "k_preproc.hpp"
 #include "k_preproc_dev.hpp"
 
 // One lane converts 4 horizontally adjacent pixels (two UV pairs). Packed NV12, stride == width

@@ -3,6 +3,7 @@
 // rectangle of a crop.
 #pragma once
 #include "vt_common.hpp"
+#include "vt_frame.hpp"
 
 // /root/reference/src/nv12_convert.rs:24-29 (table entries) and :124-131 (per pixel)
 __device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, int& r, int& g, int& b) {
@@ -21,7 +22,7 @@ __device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, int& r, int& g, 
 
 // frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding).
 // ANY = 0: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
-// constants); ANY = 1: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_common.hpp); ANY = 2:
+// constants); ANY = 1: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_frame.hpp); ANY = 2:
 // every vt_pixfmt2 as well, through the whole layout word. The engine launches the kernels of the lowest level that reads
 // every format of the pass (pix_level): reading the offsets at run time costs the crop kernels 3-19 SGPRs, the planar,
 // 16-bit and grey layouts another 6 and 23 spilled (kernel-resource-usage; profiles/planar_formats_cfg3.txt), and the

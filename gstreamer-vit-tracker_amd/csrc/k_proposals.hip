@@ -26,7 +26,7 @@
 //
 // Nothing but the option's own buffers is written: no word of StreamState, no result, no template row, no pixel. No
 // atomics, no tickets. Compiled like k_refresh.hip (-ffp-contract=off): one IEEE operation per source operation.
-#include "vt_common.hpp"
+#include "k_proposals.hpp"
 #include "k_preproc_dev.hpp"
 
 static constexpr int kPropRecWords = sizeof(PropRec) / 4;

@@ -16,7 +16,10 @@
 // workgroup can see the bumped state and decide otherwise than its neighbours. The rows themselves are read by later
 // launches only. The last arrival puts the ticket back to zero; the engine also zeroes the tickets wherever a pass may
 // have been abandoned (Engine::reset_refresh_tickets).
-#include "vt_common.hpp"
+#include "k_refresh.hpp"
+#include "k_appearance.hpp"     // rules 8, 9 and 10 read the three features' policies, counters and records
+#include "k_conflicts.hpp"
+#include "k_health.hpp"
 #include "k_refresh_dev.hpp"
 
 // What the kernels take of RefreshArgs: the members every engine sets, in their order, and - LAST in the argument block, so

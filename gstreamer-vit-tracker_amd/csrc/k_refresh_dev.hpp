@@ -5,7 +5,7 @@
 // failure leaves, and of the launch table that picks a crop body as launch_preproc picks it for the template. The crop
 // itself is the text of k_refresh_crop.inc around the crop kernels' bodies (k_preproc_body.inc).
 #pragma once
-#include "vt_common.hpp"
+#include "k_refresh.hpp"
 #include "k_preproc_dev.hpp"
 
 // rule 1: the stream has a policy; rule 3: the update succeeded with at least the policy's score (a NaN score fails);

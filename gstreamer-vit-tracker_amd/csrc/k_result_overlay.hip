@@ -25,8 +25,8 @@
 // vector registers; the counters are bumped with ordinary atomics by one thread per slot. Nothing is read back.
 //
 // Compiled with k_head.hip's flags (one IEEE operation per source operation: the gate's divide, the label's multiply).
-#include "k_overlay_dev.hpp"
 #include "k_result_overlay.hpp"
+#include "k_overlay_dev.hpp"
 
 static_assert(sizeof(OverlayPolicy) == 32 && sizeof(OverlayStats) == 32, "overlay record layout");
 static_assert(sizeof(vt_draw_cmd) == 64, "vt_draw_cmd layout");

@@ -1,6 +1,7 @@
 // k_result_overlay.hpp — the result overlay's records and launcher (k_result_overlay.hip; DESIGN.md section 3 "Result overlay").
 #pragma once
 #include "vt_common.hpp"
+#include "vt_frame.hpp"
 
 // ONE per engine, device memory, written by the host only (never rewound, not part of a snapshot)
 struct OverlayPolicy {

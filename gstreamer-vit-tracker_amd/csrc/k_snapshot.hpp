@@ -1,6 +1,8 @@
 // k_snapshot.hpp — stream snapshots on the device (k_snapshot.hip; byte layout: include/vittrack_hip.h).
 #pragma once
 #include "vt_common.hpp"
+#include "vt_frame.hpp"
+#include "k_refresh.hpp"        // RefreshPolicy: part of the payload
 
 // The payload of a snapshot record as it lies in device staging: state words, policy words, template rows, at the
 // offsets of the byte string (whose header the host writes). rec is 16-byte aligned, so rec + VT_SNAP_ROWS_OFF is too.

@@ -140,7 +140,7 @@ int Engine::index_blob(const uint8_t* hc, size_t bytes) {
     for (int i = 0; i < 3; ++i) { d.norm_a[i] = fl[i]; d.norm_b[i] = fl[3 + i]; }
     d.success_threshold = fl[6];
     d.ln_eps = fl[7];
-    // header int 12: the shift of the residual pair's quantum (vt_common.hpp, specification v3). 0: the default
+    // header int 12: the shift of the residual pair's quantum (k_gemm.hpp, specification v3). 0: the default
     if (ints[12] != 0 && (ints[12] < VT_LO_SHIFT_MIN || ints[12] > VT_LO_SHIFT_MAX))
         return set_err(VT_ERR_FORMAT, "weight blob: lo_shift %d out of range (0 = %d, or %d..%d)", ints[12],
                        VT_LO_SHIFT_DEFAULT, VT_LO_SHIFT_MIN, VT_LO_SHIFT_MAX);
@@ -742,7 +742,7 @@ int Engine::capture_graphs_for(int format) {
     return VT_OK;
 }
 
-// every format is checked by its family (vt_common.hpp: PixFamily): a luma plane with chroma planes by the rules of NV12
+// every format is checked by its family (vt_frame.hpp: PixFamily): a luma plane with chroma planes by the rules of NV12
 // (NV16: the window rules of YUY2) on the bytes of its samples and planes, packed 4:2:2 by those of YUY2, packed RGB and
 // grey by the bytes per pixel
 int check_frame(const vt_frame& f) {

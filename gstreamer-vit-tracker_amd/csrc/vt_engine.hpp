@@ -13,6 +13,15 @@
 //   vt_rccl.hip     the start-up weight broadcast over a lazily loaded librccl
 //   vt_ops.hip      operator-level entry points of include/vittrack_hip_ops.h - linked into
 //                   libvittrack_hip_ops.so (tests, tuning tools) only, NOT into the product library
+// The headers. A kernel file's host-visible ABI lives in the header of the same name; vt_common.hpp holds only what the
+// math kernels also need.
+//   vt_common.hpp   the core: vector types, vt_launch, bf16 helpers
+//   vt_frame.hpp    pixel formats, FrameDesc, StreamState, ModelDims, PassOut
+//   k_gemm.hpp      k_gemm.hip and k_gemm256.hip: the residual pair's specification, GemmArgs, the launch API
+//   k_misc.hpp  k_attn.hpp  k_head.hpp  k_preproc.hpp  k_overlay.hpp  k_cand.hpp  k_snapshot.hpp   the launch APIs of those files
+//   k_refresh.hpp  k_chip.hpp  k_peaks.hpp  k_motion.hpp  k_appearance.hpp  k_arbitrate.hpp  k_proposals.hpp
+//   k_camera_motion.hpp  k_conflicts.hpp  k_health.hpp  k_result_overlay.hpp   one optional feature each: records, policy, launchers
+//   k_ln_dev.hpp and the other *_dev.hpp, k_gemm_util.hpp   device code shared between kernel files; not included here
 #pragma once
 #include <algorithm>
 #include <array>
@@ -30,6 +39,23 @@
 #include <vector>
 
 #include "vt_common.hpp"
+#include "vt_frame.hpp"
+#include "k_gemm.hpp"
+#include "k_misc.hpp"
+#include "k_attn.hpp"
+#include "k_head.hpp"
+#include "k_preproc.hpp"
+#include "k_overlay.hpp"
+#include "k_refresh.hpp"
+#include "k_chip.hpp"
+#include "k_peaks.hpp"
+#include "k_motion.hpp"
+#include "k_appearance.hpp"
+#include "k_arbitrate.hpp"
+#include "k_proposals.hpp"
+#include "k_camera_motion.hpp"
+#include "k_conflicts.hpp"
+#include "k_health.hpp"
 #include "k_cand.hpp"
 #include "k_result_overlay.hpp"
 #include "vt_feature_keys.hpp"

@@ -56,7 +56,7 @@ static int plan_window(const Engine* e, const vt_frame& hf, const float* box, fl
     if (!p0 || w < 16 || h < 16) return set_err(VT_ERR_INVALID_ARG, "null frame or size < 16");
     if (w > e->max_w || h > e->max_h)
         return set_err(VT_ERR_INVALID_ARG, "frame %dx%d exceeds configured max %dx%d", w, h, e->max_w, e->max_h);
-    // by family (vt_common.hpp: PixFamily); the messages name the format
+    // by family (vt_frame.hpp: PixFamily); the messages name the format
     const int fam = pix_family(fmt), bpp = pix_row_bpp(fmt);
     if (fam == PIXF_RGB) {
         if (s0 < bpp * w) return set_err(VT_ERR_INVALID_ARG, "%s stride < %d*width", pix_name(fmt), bpp);

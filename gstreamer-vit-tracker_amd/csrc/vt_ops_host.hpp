@@ -22,7 +22,7 @@ static inline void widen_bf16(const uint16_t* in, size_t n, float* out) {     //
     for (size_t i = 0; i < n; ++i) { const uint32_t u = ((uint32_t)in[i]) << 16; memcpy(out + i, &u, 4); }
 }
 
-// the 3-byte pair of the residual stream (specification v3, vt_common.hpp): hi = bf16(x),
+// the 3-byte pair of the residual stream (specification v3, k_gemm.hpp): hi = bf16(x),
 // lo8 = clamp(rint((x - hi) * 2^s), -127, 127); its value is hi + lo8 * q with the quantum q = 2^-s
 static inline void pair_pack(const float* x, size_t n, int s, uint16_t* hi, int8_t* lo) {
     for (size_t i = 0; i < n; ++i) {

@@ -412,7 +412,7 @@ def op_response_peaks(head_out, hann, states, policies, B, grid, slot_stream=Non
     return out
 
 
-# the motion prior's records (csrc/vt_common.hpp: MotionRec 48 bytes by stream, MotionPolicy 16 bytes per engine)
+# the motion prior's records (csrc/k_motion.hpp: MotionRec 48 bytes by stream, MotionPolicy 16 bytes per engine)
 MOTION_REC_DTYPE = np.dtype([("v", "<f4", 2), ("prior", "<f4", 4), ("shift", "<f4", 2), ("live", "<i4"), ("n_shift", "<i4"),
                              ("n_coast", "<i4"), ("reserved", "<i4")])
 CANDIDATE_DTYPE = np.dtype([("stream", "<i4"), ("has_box", "<i4"), ("box", "<f4", 4)])
@@ -455,7 +455,7 @@ def op_appearance_score(anchor, probe, cols, device=0):
     return dict(sums=sums, similarity=sim, status=status)
 
 
-# the 224-byte record of the reacquire proposals (csrc/vt_common.hpp: PropRec)
+# the 224-byte record of the reacquire proposals (csrc/k_proposals.hpp: PropRec)
 PROPOSAL_DTYPE = np.dtype([("sim", "<f4"), ("box", "<f4", 4), ("pos", "<i4")])
 PROPOSALS_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n", "<i4"), ("c", "<f4"), ("Wg", "<i4"), ("Hg", "<i4"),
                                 ("reserved", "<i4", 2), ("p", PROPOSAL_DTYPE, 8)])
@@ -490,7 +490,7 @@ def op_proposals(frames, states, results, tpl, T, patch, norm, mode=2, period=1,
     return dict(pattern=pattern, thumb=thumb, map=smap_out, records=recs, evaluated=ev)
 
 
-# the 104-byte record of the camera motion (csrc/vt_common.hpp: CamRec) and the entries of a stream's SAD table
+# the 104-byte record of the camera motion (csrc/k_camera_motion.hpp: CamRec) and the entries of a stream's SAD table
 CAMERA_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"), ("R", "<i4"),
                              ("dx", "<i4"), ("dy", "<i4"), ("shift", "<f4", 2), ("applied", "<i4"), ("n", "<i4"), ("S_best", "<i8"),
                              ("S0", "<i8"), ("S2", "<i8"), ("evaluated", "<i4"), ("moved", "<i4"), ("has_prev", "<i4"), ("cur", "<i4"),
@@ -522,7 +522,7 @@ def op_camera_motion(frames, states, mode=2, cell=0, rng=8, conf_pm=800, max_cel
     return dict(states=st, thumbs=th, records=rec, sad=sad, host_states=hst, host_records=hrec)
 
 
-# the frame health's arrays (csrc/vt_common.hpp: HealthRec 104 bytes and HealthCount 16 bytes by stream, HealthHead 32 bytes by slot)
+# the frame health's arrays (csrc/k_health.hpp: HealthRec 104 bytes and HealthCount 16 bytes by stream, HealthHead 32 bytes by slot)
 HEALTH_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("flags", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"),
                              ("still", "<i4"), ("reserved0", "<i4"), ("S1", "<i8"), ("S2", "<i8"), ("G", "<i8"), ("D", "<i8"),
                              ("HD", "<i8"), ("G_ref", "<i8"), ("has_prev", "<i4"), ("cur", "<i4"), ("pW", "<i4"), ("pH", "<i4"),
@@ -560,7 +560,7 @@ def op_frame_health(frames, states, on=1, period=1, cell=0, still_run=3, flat_q=
     return dict(states=st, thumbs=th, hist=hi, records=rec, counts=cnt, accs=accs, heads=heads, host_records=hrec)
 
 
-# the peak arbitration's records (csrc/vt_common.hpp: ArbRec 176 bytes and ArbCount 8 bytes, both by stream)
+# the peak arbitration's records (csrc/k_arbitrate.hpp: ArbRec 176 bytes and ArbCount 8 bytes, both by stream)
 ARBITRATE_PEAK_DTYPE = np.dtype([("cell", "<i4"), ("status", "<i4"), ("score", "<f4"), ("resp", "<f4"), ("similarity", "<f4"),
                                  ("reserved", "<i4"), ("box", "<f4", 4)])
 ARBITRATE_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n", "<i4"), ("chosen", "<i4"),
@@ -607,7 +607,7 @@ def op_arbitrate(head_out, hann, frames, states, results, anchor, grid, T, S, pa
     return dict(states=st, results=res, records=rec, probe=probe, counts=cnt, host_results=hres, host_states=hst, host_records=hrec)
 
 
-# the stream conflicts' records (csrc/vt_common.hpp: ConflictRec 48 bytes and ConflictCount 16 bytes, both by stream)
+# the stream conflicts' records (csrc/k_conflicts.hpp: ConflictRec 48 bytes and ConflictCount 16 bytes, both by stream)
 CONFLICT_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("n_over", "<i4"), ("reserved", "<i4"),
                                ("partner", "<i4", 4), ("iou", "<f4", 4)])
 CONFLICT_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("conflicting", "<i4"), ("gated", "<i4"), ("reserved", "<i4")])

@@ -25,7 +25,7 @@ HEADER = np.dtype([("magic", "S4"), ("version", "S4"), ("total_bytes", "<u4"), (
                    ("patch", "<i4"), ("template_size", "<i4"), ("search_size", "<i4"), ("kpad", "<i4"),
                    ("tokens_template", "<i4"), ("norm_a", "<f4", 3), ("norm_b", "<f4", 3), ("reserved0", "<u4"),
                    ("checksum", "<u8"), ("reserved", "<u4", 16)])
-# the device's StreamState record (csrc/vt_common.hpp), 22 words
+# the device's StreamState record (csrc/vt_frame.hpp), 22 words
 STATE = np.dtype([("box", "<f4", 4), ("geo", "<f4", 4), ("frame_w", "<i4"), ("frame_h", "<i4"), ("initialized", "<i4"),
                   ("frames_done", "<i4"), ("success_count", "<i4"), ("last_idx", "<i4"), ("last_fbox", "<f4", 4),
                   ("last_score", "<f4"), ("window_miss", "<i4"), ("tpl_gen", "<i4"), ("tpl_frame", "<i4")])

@@ -45,7 +45,7 @@ def test_python_binding_and_record_layout(vt):
     assert callable(vt.op_arbitrate)
     assert vt.ARBITRATE_PEAK_DTYPE.itemsize == 40 and vt.ARBITRATE_REC_DTYPE.itemsize == 176 and vt.ARBITRATE_COUNT_DTYPE.itemsize == 8
     assert vt.ARBITRATE_REC_DTYPE.fields["peak"][1] == 16 and vt.ARBITRATE_PEAK_DTYPE.fields["box"][1] == 24
-    common = open(os.path.join(CSRC, "vt_common.hpp")).read()
+    common = open(os.path.join(CSRC, "k_arbitrate.hpp")).read()
     assert "sizeof(ArbPeak) == 40 && sizeof(ArbRec) == 176" in common and "#define VT_ARB_MAX 4" in common
 
 

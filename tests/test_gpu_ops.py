@@ -504,7 +504,7 @@ def test_head_band_kernel_conv1x1(gpu, B, grid, K, N, R, ncb):
 def test_head_band_kernel_with_the_final_layernorm_inside(gpu, B, grid, D, N, ntok, off, R, ncb):
     """k_head.hip, LNC: the 1x1 layer's workgroup normalises its band's rows of the split residual stream itself (resident
     A image, weights through the ring). Bit-identical to the LayerNorm kernel followed by the band kernel - the same
-    row arithmetic by construction (ln_row, vt_common.hpp) - on every plan incl. a short last band (grid 15) and an A
+    row arithmetic by construction (ln_row, k_ln_dev.hpp) - on every plan incl. a short last band (grid 15) and an A
     image that is not a whole number of KiB; and within bf16 rounding of a float64 LayerNorm + product."""
     rng = np.random.default_rng(B * 7 + grid + D + N + R + ncb)
     x = (rng.standard_normal((B * ntok, D)) * rng.uniform(0.2, 3.0, size=(B * ntok, 1)) +
@@ -716,7 +716,7 @@ def test_attention_second_pass_only_where_needed(gpu):
 
 
 def test_register_only_half_wave_sum_has_the_butterflys_bits(gpu, tmp_path):
-    """half_wave_sum (vt_common.hpp: v_permlane16_swap + DPP, the two row sums of the final LayerNorm) against the
+    """half_wave_sum (k_ln_dev.hpp: v_permlane16_swap + DPP, the two row sums of the final LayerNorm) against the
     __shfl_xor butterfly it replaced, lane by lane on 4,096 waves of pseudo-random values: the same partners in the same
     order, so the same bits. Built from tools/dpp_xor_check.hip on the box (the check that caught hipcc adding the swap's
     first result to itself when the builtin gets bit-cast floats)."""

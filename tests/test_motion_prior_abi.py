@@ -62,7 +62,7 @@ def test_the_kernels_keep_one_operation_per_operation_and_the_state_stays_88_byt
     assert "vt_ingest.hip" not in b.FAST_CONTRACT, "the host's window planning repeats the place rule: same flags"
     assert "-ffp-contract=off" in b.HIP_FLAGS
     csrc = os.path.join(ROOT, "gstreamer-vit-tracker_amd", "csrc")
-    common = open(os.path.join(csrc, "vt_common.hpp")).read()
+    common = open(os.path.join(csrc, "vt_frame.hpp")).read() + open(os.path.join(csrc, "k_motion.hpp")).read()   # the state; the feature
     assert "static_assert(sizeof(StreamState) == 88" in common and "static_assert(sizeof(MotionRec) == 48" in common
     for decl in ("hipError_t launch_motion_place(", "hipError_t launch_motion_settle(", "bool motion_predict("):
         assert decl in common, decl

@@ -93,7 +93,7 @@ def test_the_records_are_32_and_272_bytes_on_every_side(vt, tmp_path):
 
 
 def test_the_stream_state_is_untouched_and_the_kernel_is_built_like_the_decode():
-    src = open(os.path.join(ROOT, "gstreamer-vit-tracker_amd", "csrc", "vt_common.hpp")).read()
+    src = open(os.path.join(ROOT, "gstreamer-vit-tracker_amd", "csrc", "vt_frame.hpp")).read()
     assert "static_assert(sizeof(StreamState) == 88" in src
     b = _build_py()
     assert "k_peaks.hip" in b.HIP_SOURCES and "k_peaks.hip" not in b.FAST_CONTRACT and "k_head.hip" not in b.FAST_CONTRACT

@@ -71,7 +71,7 @@ def test_vt_chip_info_is_48_bytes_in_c_ctypes_and_rust(vt):
 
 
 def test_the_stream_state_is_untouched_and_the_kernel_is_built_like_the_crop_kernels():
-    src = open(os.path.join(ROOT, "gstreamer-vit-tracker_amd", "csrc", "vt_common.hpp")).read()
+    src = open(os.path.join(ROOT, "gstreamer-vit-tracker_amd", "csrc", "vt_frame.hpp")).read()
     assert "static_assert(sizeof(StreamState) == 88" in src
     spec = importlib.util.spec_from_file_location("_vt_build", os.path.join(ROOT, "gstreamer-vit-tracker_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)

@@ -1,4 +1,4 @@
-// dpp_xor_check.hip - the register-only 32-lane xor butterfly of ln_row (vt_common.hpp: v_permlane16_swap + DPP) against the
+// dpp_xor_check.hip - the register-only 32-lane xor butterfly of ln_row (k_ln_dev.hpp: v_permlane16_swap + DPP) against the
 // __shfl_xor (ds_bpermute) butterfly it replaced: same partners in the same order (16, 8, 4, 2, 1), so the same bits.
 // Build: hipcc --offload-arch=gfx950 -O3 tools/dpp_xor_check.hip -o /tmp/dpp_xor_check && /tmp/dpp_xor_check (on the GPU box).
 #include <hip/hip_runtime.h>
@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "../gstreamer-vit-tracker_amd/csrc/vt_common.hpp"
+#include "../gstreamer-vit-tracker_amd/csrc/k_ln_dev.hpp"
 
 __global__ void k(const float* x, float* y, float* z) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
