@@ -20,6 +20,9 @@ use ndarray::ArrayView3;
 use std::ffi::{c_int, c_void, CStr, CString};
 
 pub use sys::BBox;
+/// The colour meaning of a YUV frame (BT.601 / BT.709 / BT.2020, limited / full range) and the `const fn` that forms
+/// `VtFrame::format` from a pixel format and the two: a plain pixel format value stays BT.601 limited range.
+pub use sys::{vt_frame_format as frame_format, VT_COLOR_BT2020, VT_COLOR_BT601, VT_COLOR_BT709, VT_RANGE_FULL, VT_RANGE_LIMITED};
 
 impl BBox {
     /// src/selection_state.rs:44

@@ -38,6 +38,19 @@ pub const VT_PIX2_GRAY8: i32 = 20;
 pub const VT_PIX2_XRGB: i32 = 21;
 pub const VT_PIX2_XBGR: i32 = 22;
 
+/// ≙ vt_color_matrix / vt_color_range: the colour meaning of a YUV frame, in bits 8..11 / 12..15 of `VtFrame::format`
+pub const VT_COLOR_BT601: i32 = 0;
+pub const VT_COLOR_BT709: i32 = 1;
+pub const VT_COLOR_BT2020: i32 = 2;
+pub const VT_RANGE_LIMITED: i32 = 0;
+pub const VT_RANGE_FULL: i32 = 1;
+
+/// ≙ VT_FRAME_FORMAT(pix, matrix, range): the format word of a frame; (pix, VT_COLOR_BT601, VT_RANGE_LIMITED) is `pix`.
+/// Constant shift amounts and a bitwise or: nothing here can panic. The library checks the word (include/vittrack_hip.h).
+pub const fn vt_frame_format(pix: i32, matrix: i32, range: i32) -> i32 {
+    pix | (matrix << 8) | (range << 12)
+}
+
 /// ≙ vt_bbox ≙ vit_tracker::BBox (src/selection_state.rs:44, src/tracker_context.rs:85)
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]

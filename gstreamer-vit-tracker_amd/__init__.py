@@ -27,6 +27,33 @@ PIX_RGB8, PIX_NV12, PIX_YUY2 = 0, 1, 2
 PIX_BGR8, PIX_RGBX, PIX_BGRX, PIX_NV21, PIX_UYVY = 3, 4, 5, 6, 7
 # vt_pixfmt2: further values of vt_frame.format (three-plane 4:2:0, 16-bit NV12, 4:2:2 semi-planar, grey, pad-first RGB)
 PIX_I420, PIX_YV12, PIX_P010, PIX_NV16, PIX_GRAY8, PIX_XRGB, PIX_XBGR = 16, 17, 18, 19, 20, 21, 22
+# colour meaning of a YUV frame (vt_color_matrix, vt_color_range): vt_frame.format = pixel format | matrix << 8 | range << 12
+COLOR_BT601, COLOR_BT709, COLOR_BT2020 = 0, 1, 2
+RANGE_LIMITED, RANGE_FULL = 0, 1
+
+
+def frame_format(pix: int, matrix: int = COLOR_BT601, full_range: bool = False) -> int:
+    """VT_FRAME_FORMAT: the format word of a frame. The defaults give `pix` itself (BT.601, limited range). The library
+    refuses colour bits on a format without chroma, a matrix above 2 and anything above bit 15."""
+    return int(pix) | int(matrix) << 8 | (RANGE_FULL if full_range else RANGE_LIMITED) << 12
+
+
+def colorimetry_from_gst(text: str):
+    """(matrix, full_range) of the `colorimetry` field of GStreamer video/x-raw caps: the named forms bt601, bt709, bt2020
+    and bt2020-10 (all limited range) or range:matrix:transfer:primaries in numbers (GstVideoColorRange: 1 full (0-255),
+    2 limited (16-235); GstVideoColorMatrix: 3 BT.709, 4 BT.601, 6 BT.2020). ValueError for everything else: an unknown
+    range or matrix, RGB, FCC, SMPTE240M, sRGB - there is no format word for them."""
+    t = str(text).strip().lower()
+    named = {"bt601": COLOR_BT601, "bt709": COLOR_BT709, "bt2020": COLOR_BT2020, "bt2020-10": COLOR_BT2020}
+    if t in named:
+        return named[t], False
+    parts = t.split(":")
+    if len(parts) == 4 and all(q.isdigit() for q in parts):
+        rng, mat = int(parts[0]), int(parts[1])
+        matrices = {3: COLOR_BT709, 4: COLOR_BT601, 6: COLOR_BT2020}
+        if rng in (1, 2) and mat in matrices:
+            return matrices[mat], rng == 1
+    raise ValueError(f"colorimetry {text!r}: no BT.601 / BT.709 / BT.2020 YUV frame format")
 
 
 class VtError(RuntimeError):
@@ -513,27 +540,29 @@ class NV12Frame:
     """packed NV12 host buffer: Y plane then interleaved UV, stride == width
     (the layout /root/reference/src/nv12_convert.rs:47-54 assumes)"""
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(PIX_NV12, matrix, full_range)
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= width * height + ((width + 1) & ~1) * ((height + 1) // 2)
 
     def cframe(self) -> "CFrame":
         uv = self.buf[self.w * self.h:]
-        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, self.w, (self.w + 1) & ~1, PIX_NV12,
+        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, self.w, (self.w + 1) & ~1, self.format,
                       0, 0, 0, 0, 0)
 
 
 class YUY2Frame:
     """packed 4:2:2 host frame (Y0 U Y1 V), rows of 2*width bytes (src/pipeline_ir.rs:27-41)"""
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(PIX_YUY2, matrix, full_range)
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= 2 * width * height and width % 2 == 0
 
     def cframe(self) -> "CFrame":
-        return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, PIX_YUY2, 0, 0, 0, 0, 0)
+        return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, self.format, 0, 0, 0, 0, 0)
 
 
 class _PackedFrame:
@@ -583,27 +612,29 @@ class BGRXFrame(_PackedFrame):
 class NV21Frame:
     """packed NV21 host buffer: Y plane then interleaved V,U, stride == width (Android / V4L2 sensors)"""
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(PIX_NV21, matrix, full_range)
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= width * height + ((width + 1) & ~1) * ((height + 1) // 2)
 
     def cframe(self) -> "CFrame":
         vu = self.buf[self.w * self.h:]
-        return CFrame(self.buf.ctypes.data, vu.ctypes.data, self.w, self.h, self.w, (self.w + 1) & ~1, PIX_NV21,
+        return CFrame(self.buf.ctypes.data, vu.ctypes.data, self.w, self.h, self.w, (self.w + 1) & ~1, self.format,
                       0, 0, 0, 0, 0)
 
 
 class UYVYFrame:
     """packed 4:2:2 host frame (U Y0 V Y1), rows of 2*width bytes (V4L2 / SDI capture)"""
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(PIX_UYVY, matrix, full_range)
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= 2 * width * height and width % 2 == 0
 
     def cframe(self) -> "CFrame":
-        return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
+        return CFrame(self.buf.ctypes.data, None, self.w, self.h, 2 * self.w, 0, self.format, 0, 0, 0, 0, 0)
 
 
 class I420Frame:
@@ -611,14 +642,15 @@ class I420Frame:
     ceil(h/2) bytes with stride ceil(w/2) (libav / GStreamer software decoders, raw .yuv files)"""
     FMT = PIX_I420
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(self.FMT, matrix, full_range)
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= width * height + 2 * ((width + 1) // 2) * ((height + 1) // 2)
 
     def cframe(self) -> "CFrame":
         c = self.buf[self.w * self.h:]
-        return CFrame(self.buf.ctypes.data, c.ctypes.data, self.w, self.h, self.w, (self.w + 1) // 2, self.FMT,
+        return CFrame(self.buf.ctypes.data, c.ctypes.data, self.w, self.h, self.w, (self.w + 1) // 2, self.format,
                       0, 0, 0, 0, 0)
 
 
@@ -631,7 +663,8 @@ class P010Frame:
     """packed P010 (P012, P016) host buffer: NV12's layout with 16-bit little-endian samples, rows of 2*width bytes; only
     the high byte of a sample is read. `buf`: uint8 bytes or uint16 samples"""
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(PIX_P010, matrix, full_range)
         buf = np.ascontiguousarray(buf)
         if buf.dtype == np.uint16:
             buf = buf.astype("<u2", copy=False).view(np.uint8)
@@ -641,21 +674,22 @@ class P010Frame:
 
     def cframe(self) -> "CFrame":
         uv = self.buf[2 * self.w * self.h:]
-        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, 2 * self.w, 2 * ((self.w + 1) & ~1), PIX_P010,
+        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, 2 * self.w, 2 * ((self.w + 1) & ~1), self.format,
                       0, 0, 0, 0, 0)
 
 
 class NV16Frame:
     """packed NV16 host buffer: Y plane then interleaved U,V with one chroma row per luma row, stride == width (even)"""
 
-    def __init__(self, buf: np.ndarray, width: int, height: int):
+    def __init__(self, buf: np.ndarray, width: int, height: int, matrix: int = COLOR_BT601, full_range: bool = False):
+        self.format = frame_format(PIX_NV16, matrix, full_range)
         self.buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
         self.w, self.h = width, height
         assert self.buf.size >= 2 * width * height and width % 2 == 0
 
     def cframe(self) -> "CFrame":
         uv = self.buf[self.w * self.h:]
-        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, self.w, self.w, PIX_NV16, 0, 0, 0, 0, 0)
+        return CFrame(self.buf.ctypes.data, uv.ctypes.data, self.w, self.h, self.w, self.w, self.format, 0, 0, 0, 0, 0)
 
 
 class Gray8Frame(_PackedFrame):
@@ -909,8 +943,12 @@ def _refresh_stats_dict(st: "CRefreshStats") -> dict:
                 last_frame=int(st.last_frame), skipped_geometry=int(st.skipped_geometry))
 
 
-def frame_nv12(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
-    return CFrame(d_y, d_uv, w, h, y_stride or w, uv_stride or ((w + 1) & ~1), PIX_NV12, 0, 0, 0, 0, 0)
+def frame_nv12(d_y, d_uv, w, h, y_stride=None, uv_stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
+    return CFrame(d_y, d_uv, w, h, y_stride or w, uv_stride or ((w + 1) & ~1), frame_format(PIX_NV12, matrix, full_range), 0, 0, 0, 0, 0)
+
+
+def frame_yuy2(d_yuy2, w, h, stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
+    return CFrame(d_yuy2, None, w, h, stride or 2 * w, 0, frame_format(PIX_YUY2, matrix, full_range), 0, 0, 0, 0, 0)
 
 
 def frame_rgb8(d_rgb, w, h, stride=None) -> CFrame:
@@ -929,31 +967,31 @@ def frame_bgrx(d_bgrx, w, h, stride=None) -> CFrame:
     return CFrame(d_bgrx, None, w, h, stride or 4 * w, 0, PIX_BGRX, 0, 0, 0, 0, 0)
 
 
-def frame_nv21(d_y, d_vu, w, h, y_stride=None, vu_stride=None) -> CFrame:
-    return CFrame(d_y, d_vu, w, h, y_stride or w, vu_stride or ((w + 1) & ~1), PIX_NV21, 0, 0, 0, 0, 0)
+def frame_nv21(d_y, d_vu, w, h, y_stride=None, vu_stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
+    return CFrame(d_y, d_vu, w, h, y_stride or w, vu_stride or ((w + 1) & ~1), frame_format(PIX_NV21, matrix, full_range), 0, 0, 0, 0, 0)
 
 
-def frame_uyvy(d_uyvy, w, h, stride=None) -> CFrame:
-    return CFrame(d_uyvy, None, w, h, stride or 2 * w, 0, PIX_UYVY, 0, 0, 0, 0, 0)
+def frame_uyvy(d_uyvy, w, h, stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
+    return CFrame(d_uyvy, None, w, h, stride or 2 * w, 0, frame_format(PIX_UYVY, matrix, full_range), 0, 0, 0, 0, 0)
 
 
-def frame_i420(d_y, d_u, w, h, y_stride=None, c_stride=None) -> CFrame:
+def frame_i420(d_y, d_u, w, h, y_stride=None, c_stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
     """d_u: the U plane; the V plane lies c_stride * ceil(h / 2) bytes behind it"""
-    return CFrame(d_y, d_u, w, h, y_stride or w, c_stride or (w + 1) // 2, PIX_I420, 0, 0, 0, 0, 0)
+    return CFrame(d_y, d_u, w, h, y_stride or w, c_stride or (w + 1) // 2, frame_format(PIX_I420, matrix, full_range), 0, 0, 0, 0, 0)
 
 
-def frame_yv12(d_y, d_v, w, h, y_stride=None, c_stride=None) -> CFrame:
+def frame_yv12(d_y, d_v, w, h, y_stride=None, c_stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
     """d_v: the V plane; the U plane lies c_stride * ceil(h / 2) bytes behind it"""
-    return CFrame(d_y, d_v, w, h, y_stride or w, c_stride or (w + 1) // 2, PIX_YV12, 0, 0, 0, 0, 0)
+    return CFrame(d_y, d_v, w, h, y_stride or w, c_stride or (w + 1) // 2, frame_format(PIX_YV12, matrix, full_range), 0, 0, 0, 0, 0)
 
 
-def frame_p010(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
+def frame_p010(d_y, d_uv, w, h, y_stride=None, uv_stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
     """strides in bytes"""
-    return CFrame(d_y, d_uv, w, h, y_stride or 2 * w, uv_stride or 2 * ((w + 1) & ~1), PIX_P010, 0, 0, 0, 0, 0)
+    return CFrame(d_y, d_uv, w, h, y_stride or 2 * w, uv_stride or 2 * ((w + 1) & ~1), frame_format(PIX_P010, matrix, full_range), 0, 0, 0, 0, 0)
 
 
-def frame_nv16(d_y, d_uv, w, h, y_stride=None, uv_stride=None) -> CFrame:
-    return CFrame(d_y, d_uv, w, h, y_stride or w, uv_stride or w, PIX_NV16, 0, 0, 0, 0, 0)
+def frame_nv16(d_y, d_uv, w, h, y_stride=None, uv_stride=None, matrix=COLOR_BT601, full_range=False) -> CFrame:
+    return CFrame(d_y, d_uv, w, h, y_stride or w, uv_stride or w, frame_format(PIX_NV16, matrix, full_range), 0, 0, 0, 0, 0)
 
 
 def frame_gray8(d_y, w, h, stride=None) -> CFrame:

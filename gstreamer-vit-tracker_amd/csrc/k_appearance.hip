@@ -89,7 +89,8 @@ static void launch_probe_t(const AppearArgs& a, const ModelDims& d, int tier, hi
 
 hipError_t launch_appearance_probe(const AppearArgs& a, const ModelDims& d, int tier, int any_layout, hipStream_t st) {
     if (a.n < 1 || !a.frames || !a.states || !a.results || !a.policy || !a.recs || !a.probe) return hipErrorInvalidValue;
-    if (any_layout >= 2) launch_probe_t<2>(a, d, tier, st);
+    if (any_layout >= 3) launch_probe_t<3>(a, d, tier, st);
+    else if (any_layout == 2) launch_probe_t<2>(a, d, tier, st);
     else if (any_layout == 1) launch_probe_t<1>(a, d, tier, st);
     else launch_probe_t<0>(a, d, tier, st);
     return hipGetLastError();

@@ -155,7 +155,8 @@ static void launch_arb_probe_t(const ArbArgs& a, const ModelDims& d, int tier, h
 
 hipError_t launch_arbitrate_probe(const ArbArgs& a, const ModelDims& d, int tier, int any_layout, hipStream_t st) {
     if (a.n < 1 || a.n * VT_ARB_MAX > 65535 || !a.frames || !a.states || !a.recs || !a.probe) return hipErrorInvalidValue;
-    if (any_layout >= 2) launch_arb_probe_t<2>(a, d, tier, st);
+    if (any_layout >= 3) launch_arb_probe_t<3>(a, d, tier, st);
+    else if (any_layout == 2) launch_arb_probe_t<2>(a, d, tier, st);
     else if (any_layout == 1) launch_arb_probe_t<1>(a, d, tier, st);
     else launch_arb_probe_t<0>(a, d, tier, st);
     return hipGetLastError();

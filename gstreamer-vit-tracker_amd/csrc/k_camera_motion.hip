@@ -275,7 +275,8 @@ hipError_t launch_camera_prepare(const CamArgs& a, hipStream_t st) {
 hipError_t launch_camera_thumb(const CamArgs& a, int any_layout, hipStream_t st) {
     if (!cam_args_ok(a)) return hipErrorInvalidValue;
     const dim3 grid((a.max_cells + 255) / 256, a.n);
-    if (any_layout >= 2) vt_launch(camera_thumb_kernel<2>, grid, dim3(256), 0, st, a);
+    if (any_layout >= 3) vt_launch(camera_thumb_kernel<3>, grid, dim3(256), 0, st, a);
+    else if (any_layout == 2) vt_launch(camera_thumb_kernel<2>, grid, dim3(256), 0, st, a);
     else if (any_layout == 1) vt_launch(camera_thumb_kernel<1>, grid, dim3(256), 0, st, a);
     else vt_launch(camera_thumb_kernel<0>, grid, dim3(256), 0, st, a);
     return hipGetLastError();

@@ -162,11 +162,13 @@ hipError_t launch_target_chips(const ChipArgs& a, int C, int kind, const float* 
         return hipErrorInvalidValue;
     const int chip_bytes = C * C * (kind == VT_CHIP_NORM_BF16 ? 6 : 3);
     if (kind == VT_CHIP_NORM_BF16) {
-        if (any_layout >= 2) launch_chips_t<2, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        if (any_layout >= 3) launch_chips_t<3, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        else if (any_layout == 2) launch_chips_t<2, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
         else if (any_layout == 1) launch_chips_t<1, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
         else launch_chips_t<0, VT_CHIP_NORM_BF16>(a, C, chip_bytes, na, nb, search_size, tier, st);
     } else {
-        if (any_layout >= 2) launch_chips_t<2, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        if (any_layout >= 3) launch_chips_t<3, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
+        else if (any_layout == 2) launch_chips_t<2, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
         else if (any_layout == 1) launch_chips_t<1, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
         else launch_chips_t<0, VT_CHIP_RGB8>(a, C, chip_bytes, na, nb, search_size, tier, st);
     }

@@ -374,7 +374,8 @@ static void launch_preproc_t(const FrameDesc* frames, StreamState* states, bf16_
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
                           const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier,
                           const int32_t* slot_stream, int any_layout) {
-    if (any_layout >= 2) launch_preproc_t<2>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
+    if (any_layout >= 3) launch_preproc_t<3>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
+    else if (any_layout == 2) launch_preproc_t<2>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
     else if (any_layout == 1) launch_preproc_t<1>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
     else launch_preproc_t<0>(frames, states, patches, d, b0, nb, is_template, st, tier, slot_stream);
     return hipGetLastError();

@@ -7,7 +7,7 @@
 // tier: the tile kernel's LDS buffer (0: 16 KiB, 1: 32 KiB, 2 or more: 64 KiB), a choice of speed only
 // slot_stream (device, [nb + b0] or null = identity): the stream a slot works for. Frame descriptor and patch rows are
 // the slot's; the StreamState read (and its geo / frame_w / frame_h / window_miss written) is the stream's.
-// any_layout: the highest pix_level of the slots' formats (above 0 the layout is read from FrameDesc.lay: k_preproc.hip, fetch_rgb)
+// any_layout: the highest pix_level of the slots' formats (above 0 the layout is read from FrameDesc.lay, at 3 the colour code as well: k_preproc_dev.hpp, fetch_rgb)
 hipError_t launch_preproc(const FrameDesc* frames, StreamState* states, bf16_t* patches,
                           const ModelDims& d, int b0, int nb, bool is_template, hipStream_t st, int tier = 0,
                           const int32_t* slot_stream = nullptr, int any_layout = 0);

@@ -170,6 +170,7 @@
         // window: black + miss), so every entry of the LDS image is what the per-pixel loop writes.
         // NV21 takes the same path (ANY kernels): the descriptor says which byte of a pair is U
         // and so does NV16, with one chroma row per luma row; the planar and 16-bit layouts have groups of their own below
+        // ANY = 3: every group converts with the frame's colour code (yuv_to_rgb_lay), as its per-pixel fallback does in fetch_rgb
         const bool fast = f.fmt == PIXF_420SP && (ANY < 2 || (f.lay & (PIXL_PLANAR | PIXL_S16)) == 0) && (((uintptr_t)f.p0 | (uintptr_t)f.p1 | (uintptr_t)f.s0 | (uintptr_t)f.s1) & 7) == 0;
         // ANY kernels, 4-byte RGB formats (RGBX, BGRX, XRGB, XBGR) whose rows start on 16-byte boundaries (the library's packed
         // windows; whole frames with such strides): ONE 16-byte load per 4 pixels, where the per-pixel path issues 12
@@ -208,7 +209,7 @@
                         if (col < 0 || col >= w_) continue;
                         const uint32_t pair = uw[k >> 2] >> (((k >> 1) & 1) * 16);   // U, V of the pixel pair
                         int r, g, b;
-                        yuv_to_rgb((int)((yw[k >> 2] >> ((k & 3) * 8)) & 255u), (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
+                        yuv_to_rgb_lay<ANY>(f.lay, (int)((yw[k >> 2] >> ((k & 3) * 8)) & 255u), (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
                         dst[k] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
                     }
                 } else {
@@ -266,7 +267,7 @@
                         } else {
                             const uint32_t pair = uw[k >> 2] >> (((k >> 1) & 1) * 16);   // U, V of the pixel pair
                             int r, g, b;
-                            yuv_to_rgb((int)yk, (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
+                            yuv_to_rgb_lay<ANY>(f.lay, (int)yk, (int)((pair >> us) & 255u), (int)((pair >> vs) & 255u), r, g, b);
                             dst[k] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
                         }
                     }

@@ -20,13 +20,46 @@ __device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, int& r, int& g, 
     b = min(max(b, 0), 0xffff) >> 8;
 }
 
+// The coefficient table of the colour codes (vt_frame.hpp: pix_color_code; vittrack_hip.h: vt_color_matrix), the ONE copy
+// the kernels have: row c = matrix * 2 + range holds YO, CY, CRV, CGU, CGV, CBU, each rint(256 * exact) (DESIGN.md section 3
+// "Colorimetry"). Row 0 is yuv_to_rgb's; rows 6 and 7 repeat it so that any three bits index inside the table.
+struct YuvCoef { int yo, cy, crv, cgu, cgv, cbu; };
+// the row of a layout word's code (bits 28..30 of FrameDesc.lay, set by to_desc). The word is uniform per slot - a pass's
+// slots may carry different codes - so the row is read with scalar loads, not per pixel.
+__device__ __forceinline__ YuvCoef yuv_coef(int lay) {
+    static constexpr YuvCoef table[8] = {
+        {16, 298, 409, -100, -208, 516}, {0, 256, 359, -88, -183, 454},
+        {16, 298, 459, -55, -136, 541},  {0, 256, 403, -48, -120, 475},
+        {16, 298, 430, -48, -167, 548},  {0, 256, 377, -42, -146, 482},
+        {16, 298, 409, -100, -208, 516}, {16, 298, 409, -100, -208, 516}};
+    return table[(lay >> PIXL_CODE_SHIFT) & PIXL_CODE_MASK];
+}
+// yuv_to_rgb with the coefficients of a code: the same form - clamp first, shift second (see above); the sums reach 140946
+__device__ __forceinline__ void yuv_to_rgb_code(const YuvCoef& k, int y, int u, int v, int& r, int& g, int& b) {
+    const int yv = k.cy * (y - k.yo);
+    r = yv + k.crv * (v - 128) + 128;
+    g = yv + k.cgu * (u - 128) + k.cgv * (v - 128) + 128;
+    b = yv + k.cbu * (u - 128) + 128;
+    r = min(max(r, 0), 0xffff) >> 8;
+    g = min(max(g, 0), 0xffff) >> 8;
+    b = min(max(b, 0), 0xffff) >> 8;
+}
+// the conversion of a kernel of level ANY: levels 0..2 never see a frame with a code and keep yuv_to_rgb's constants and
+// instructions; level 3 converts with the frame's row
+template <int ANY>
+__device__ __forceinline__ void yuv_to_rgb_lay(int lay, int y, int u, int v, int& r, int& g, int& b) {
+    if constexpr (ANY >= 3) yuv_to_rgb_code(yuv_coef(lay), y, u, v, r, g, b);
+    else yuv_to_rgb(y, u, v, r, g, b);
+}
+
 // frame pixel (px,py) as float RGB; outside the frame -> 0 (zero padding).
 // ANY = 0: the kernels of RGB8, NV12 and YUY2 (the layouts that define the families, with their byte offsets as
 // constants); ANY = 1: every vt_pixfmt, each its family read through the byte offsets of f.lay (vt_frame.hpp); ANY = 2:
 // every vt_pixfmt2 as well, through the whole layout word. The engine launches the kernels of the lowest level that reads
 // every format of the pass (pix_level): reading the offsets at run time costs the crop kernels 3-19 SGPRs, the planar,
 // 16-bit and grey layouts another 6 and 23 spilled (kernel-resource-usage; profiles/planar_formats_cfg3.txt), and the
-// kernels of the formats that were there before keep their budgets and their instructions.
+// kernels of the formats that were there before keep their budgets and their instructions. ANY = 3: every layout of level
+// 2, converted with the frame's colour code (bits 28..30 of f.lay) instead of the BT.601 limited-range constants.
 template <int ANY>
 __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, float* rgb, int& miss) {
     if (px < 0 || py < 0 || px >= f.w || py >= f.h) {
@@ -42,7 +75,7 @@ __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, fl
         miss = 1;
         return;
     }
-    if constexpr (ANY == 2) {    // the masks keep every offset inside its pixel / pair / sample: no other byte is read
+    if constexpr (ANY >= 2) {    // the masks keep every offset inside its pixel / pair / sample: no other byte is read
         const int lay = f.lay;
         if (f.fmt == PIXF_RGB) {            // RGB8 .. BGRX, XRGB, XBGR, GRAY8: the colour bytes at their offsets in the pixel
             const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)sx * (unsigned)(lay >> 24);
@@ -61,10 +94,10 @@ __device__ __forceinline__ void fetch_rgb(const FrameDesc& f, int px, int py, fl
                 u = uv[(lay & 1) << ss];
                 v = uv[((lay >> 8) & 1) << ss];
             }
-            yuv_to_rgb(y, u, v, r, g, b);
+            yuv_to_rgb_lay<ANY>(lay, y, u, v, r, g, b);
         } else {                            // YUY2 (Y0 U Y1 V), UYVY (U Y0 V Y1) per pixel pair
             const uint8_t* p = f.p0 + (size_t)sy * f.s0 + (size_t)(sx & ~1) * 2;
-            yuv_to_rgb(p[(sx & 1) ? (lay >> 16) & 3 : lay & 3], p[(lay >> 8) & 3], p[(lay >> 24) & 3], r, g, b);
+            yuv_to_rgb_lay<ANY>(lay, p[(sx & 1) ? (lay >> 16) & 3 : lay & 3], p[(lay >> 8) & 3], p[(lay >> 24) & 3], r, g, b);
         }
     } else if constexpr (ANY == 1) {    // the masks keep every offset inside its pixel / pair
         const int lay = f.lay;

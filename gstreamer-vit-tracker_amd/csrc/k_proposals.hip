@@ -291,7 +291,8 @@ hipError_t launch_proposals_thumb(const PropArgs& a, const ModelDims& d, int any
     const dim3 grid((a.max_cells + 255) / 256, a.n);
 #define PROP_THUMB(ANY) vt_launch(proposals_thumb_kernel<ANY>, grid, dim3(256), 0, st, a, d.norm_a[0], d.norm_a[1], d.norm_a[2], \
                                   d.norm_b[0], d.norm_b[1], d.norm_b[2])
-    if (any_layout >= 2) PROP_THUMB(2);
+    if (any_layout >= 3) PROP_THUMB(3);
+    else if (any_layout == 2) PROP_THUMB(2);
     else if (any_layout == 1) PROP_THUMB(1);
     else PROP_THUMB(0);
 #undef PROP_THUMB

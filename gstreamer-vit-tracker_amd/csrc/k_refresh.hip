@@ -139,7 +139,8 @@ static void launch_refresh_t(const RefreshArgs& ra, const ModelDims& d, int tier
 
 template <int GATE>
 static void launch_refresh_g(const RefreshArgs& a, const ModelDims& d, int tier, int any_layout, hipStream_t st) {
-    if (any_layout >= 2) launch_refresh_t<2, GATE>(a, d, tier, st);
+    if (any_layout >= 3) launch_refresh_t<3, GATE>(a, d, tier, st);
+    else if (any_layout == 2) launch_refresh_t<2, GATE>(a, d, tier, st);
     else if (any_layout == 1) launch_refresh_t<1, GATE>(a, d, tier, st);
     else launch_refresh_t<0, GATE>(a, d, tier, st);
 }

@@ -749,8 +749,11 @@ int check_frame(const vt_frame& f) {
     if (!f.plane0 || f.width < 16 || f.height < 16 || f.width > 16384 || f.height > 16384)
         return set_err(VT_ERR_INVALID_ARG, "frame: null plane or size out of range");
     const int fam = pix_family(f.format);
-    if (fam < 0)
+    if (fam < 0) {
+        if (const char* why = pix_refusal(f.format))    // a known format with colour bits the boundary refuses
+            return set_err(VT_ERR_INVALID_ARG, "%s frame format 0x%x: %s", pix_name(f.format), (unsigned)f.format, why);
         return set_err(VT_ERR_INVALID_ARG, "unknown pixel format %d", f.format);
+    }
     const bool window = f.origin_x != 0 || f.origin_y != 0 || f.windowed == 1;
     const bool rows422 = pix_rows422(f.format);     // NV16: pairs along x only
     if (f.origin_x < 0 || f.origin_y < 0 || f.origin_x >= f.width || f.origin_y >= f.height ||
@@ -803,6 +806,9 @@ void to_desc(const vt_frame& f, FrameDesc* o) {
     // two chroma planes: the second one lies behind the rows of the first, those of the whole frame unless the planes hold a
     // packed window (vittrack_hip.h: vt_pixfmt2)
     if (pix_planar(f.format) && f.windowed != 1) o->lay |= PIXL_FULLH;
+    // the colour code of a YUV frame (0 for every plain format value: the word is then what it was): read by the kernels
+    // of level 3 alone, the only ones that see a frame with it set (pix_level)
+    o->lay |= pix_color_code(f.format) << PIXL_CODE_SHIFT;
 }
 
 int Engine::check_init_box(vt_bbox box) const {
@@ -944,6 +950,9 @@ int Engine::enqueue(const int32_t* streams, const vt_frame* frames, int n, const
     if (int rc = prepare_pass(streams, frames, n, sinks, &ps)) return rc;
     if (!ps.slot_stream && use_graph && !taps) {
         // the captured set of the lowest level that reads every format of the pass
+        // (a pass of level 1 or 2 on an engine whose only further set came from a coloured init replays the level-3 set:
+        // code 0 is row 0 of the table, the same values from the kernels that load their coefficients. A snapshot of an
+        // engine with any further set says "any graphs": its import captures the level-1 set, as it always did)
         int level = ps.any_layout;
         while (level > 0 && level + 1 < PIX_LEVELS && !graphs[level][ps.tier].exec) ++level;
         const PassGraph& g = graphs[level][ps.tier];

@@ -516,8 +516,9 @@ struct Engine {
     // graph
     // one captured pass per crop-buffer tier (k_preproc.hip: 16 / 32 / 64 KiB of LDS per tile), all captured at creation
     static constexpr int TIERS = 3;
-    // graphs[1], graphs[2]: the same passes with the crop kernels that read any vt_pixfmt / any vt_pixfmt2 as well
-    // (k_preproc.hip: fetch_rgb<level>, vt_common.hpp: pix_level), for passes that carry a format other than RGB8 / NV12 /
+    // graphs[1], graphs[2], graphs[3]: the same passes with the crop kernels that read any vt_pixfmt / any vt_pixfmt2 as
+    // well / any of those with a colour code other than BT.601 limited range
+    // (k_preproc.hip: fetch_rgb<level>, vt_frame.hpp: pix_level), for passes that carry a format other than RGB8 / NV12 /
     // YUY2: all tiers of a level captured together (capture_all_graphs) when the first stream is initialised on a format
     // of that level - never inside an update
     struct PassGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };

@@ -25,8 +25,19 @@ enum PixFamily {
 #define PIXL_ROWS422 (1 << 24)    // one chroma row per luma row (no row shift)
 #define PIXL_FULLH (1 << 25)      // set by to_desc: the planes belong to a whole frame (vt_frame.windowed != 1)
 
-// family of a format (-1: unknown) and its layout word
-inline int pix_family(int fmt) {
+// vt_frame.format = pixel format | matrix << 8 | range << 12 (vittrack_hip.h: VT_FRAME_FORMAT). The word is split and checked
+// HERE and nowhere else: pix_family refuses (-1) what the boundary refuses, every other helper works on the base format,
+// so that the frame checks, the window packing and the drawable rule need no case for colour.
+inline int pix_base(int fmt) { return fmt & 0xff; }
+// colour code of a word = matrix * 2 + range: the row of the coefficient table (k_preproc_dev.hpp: yuv_to_rgb_code), 0 =
+// BT.601 limited, the conversion every format had before the bits existed. Meaningful for a word pix_family accepts.
+inline int pix_color_code(int fmt) { return ((fmt >> 8) & 15) * 2 + ((fmt >> 12) & 15); }
+// where the code travels to the kernels: bits 28..30 of FrameDesc.lay (to_desc), free in the PIXF_420SP and PIXF_422 layout
+// words - every read of those words by a kernel of levels 0..2 is masked below bit 26 - and never set for PIXF_RGB
+#define PIXL_CODE_SHIFT 28
+#define PIXL_CODE_MASK 7
+
+inline int pix_family_base(int fmt) {
     switch (fmt) {
     case VT_PIX_RGB8: case VT_PIX_BGR8: case VT_PIX_RGBX: case VT_PIX_BGRX:
     case VT_PIX2_GRAY8: case VT_PIX2_XRGB: case VT_PIX2_XBGR: return PIXF_RGB;
@@ -36,8 +47,18 @@ inline int pix_family(int fmt) {
     default: return -1;
     }
 }
+// family of a format word (-1: refused) and its layout word. Refused: an unknown base format, a bit above 15, a matrix
+// above VT_COLOR_BT2020, a range above VT_RANGE_FULL, colour bits on a format without chroma (PIXF_RGB)
+inline int pix_family(int fmt) {
+    if (fmt < 0 || fmt > 0xffff) return -1;
+    const int fam = pix_family_base(pix_base(fmt));
+    const int matrix = (fmt >> 8) & 15, range = (fmt >> 12) & 15;
+    if (fam < 0 || matrix > VT_COLOR_BT2020 || range > VT_RANGE_FULL) return -1;
+    if (fam == PIXF_RGB && (matrix | range) != 0) return -1;
+    return fam;
+}
 inline int32_t pix_layout(int fmt) {
-    switch (fmt) {
+    switch (pix_base(fmt)) {
     case VT_PIX_RGB8: return 0 | 1 << 8 | 2 << 16 | 3 << 24;
     case VT_PIX_BGR8: return 2 | 1 << 8 | 0 << 16 | 3 << 24;
     case VT_PIX_RGBX: return 0 | 1 << 8 | 2 << 16 | 4 << 24;
@@ -56,17 +77,31 @@ inline int32_t pix_layout(int fmt) {
     default: return 0;
     }
 }
-// name of a format for error texts
+// name of a format (of its base format) for error texts
 inline const char* pix_name(int fmt) {
     static const char* const names[] = {"rgb8", "nv12", "yuy2", "bgr8", "rgbx", "bgrx", "nv21", "uyvy"};
     static const char* const names2[] = {"i420", "yv12", "p010", "nv16", "gray8", "xrgb", "xbgr"};
+    fmt = fmt < 0 ? -1 : pix_base(fmt);
     return fmt >= 0 && fmt < 8 ? names[fmt] : fmt >= VT_PIX2_I420 && fmt <= VT_PIX2_XBGR ? names2[fmt - VT_PIX2_I420] : "?";
 }
+// why pix_family refuses a word, for error texts that name the format: null for a word it accepts or whose base format is
+// unknown (the caller's "unknown pixel format" text)
+inline const char* pix_refusal(int fmt) {
+    if (pix_family(fmt) >= 0 || fmt < 0 || pix_family_base(pix_base(fmt)) < 0) return nullptr;
+    if (fmt > 0xffff) return "format bits above 15 must be zero";
+    if (((fmt >> 8) & 15) > VT_COLOR_BT2020) return "unknown colour matrix";
+    if (((fmt >> 12) & 15) > VT_RANGE_FULL) return "unknown colour range";
+    return "colour matrix / range bits on a format without chroma";
+}
 // which crop kernels (k_preproc.hip, fetch_rgb<level>) read this format: 0 those of RGB8, NV12 and YUY2, 1 those that read
-// the byte offsets of f.lay (every vt_pixfmt), 2 those that read the whole layout word (every vt_pixfmt2 as well). A
-// kernel of a level reads every format of the levels below it.
-#define PIX_LEVELS 3
-inline int pix_level(int fmt) { return fmt >= VT_PIX2_I420 ? 2 : fmt != VT_PIX_RGB8 && fmt != VT_PIX_NV12 && fmt != VT_PIX_YUY2 ? 1 : 0; }
+// the byte offsets of f.lay (every vt_pixfmt), 2 those that read the whole layout word (every vt_pixfmt2 as well), 3 those
+// that also convert with the frame's colour code (every word whose code is not 0). A kernel of a level reads every format
+// of the levels below it.
+#define PIX_LEVELS 4
+inline int pix_level(int fmt) {
+    if (pix_family(fmt) >= 0 && pix_color_code(fmt) != 0) return 3;
+    return fmt >= VT_PIX2_I420 ? 2 : fmt != VT_PIX_RGB8 && fmt != VT_PIX_NV12 && fmt != VT_PIX_YUY2 ? 1 : 0;
+}
 // bytes per pixel of plane 0's rows (PIXF_420SP: the luma plane)
 inline int pix_row_bpp(int fmt) {
     const int fam = pix_family(fmt);

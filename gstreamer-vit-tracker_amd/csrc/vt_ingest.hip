@@ -67,6 +67,8 @@ static int plan_window(const Engine* e, const vt_frame& hf, const float* box, fl
             return set_err(VT_ERR_INVALID_ARG, "%s: bad plane or stride", pix_name(fmt));
         if (pix_rows422(fmt) && (w & 1)) return set_err(VT_ERR_INVALID_ARG, "%s: odd width", pix_name(fmt));
     } else {
+        if (const char* why = pix_refusal(fmt))     // as check_frame
+            return set_err(VT_ERR_INVALID_ARG, "%s frame format 0x%x: %s", pix_name(fmt), (unsigned)fmt, why);
         return set_err(VT_ERR_INVALID_ARG, "unknown pixel format %d", fmt);
     }
     // window = search crop (factor 4; it contains the factor-2 template crop) + bilinear margin

@@ -69,15 +69,25 @@ class MovingSquare:
         return nv12_planes_to_rgb8(yy, uv[:, : self.w], self.w, self.h)
 
 
-def nv12_planes_to_rgb8(yy: np.ndarray, uv: np.ndarray, w: int, h: int) -> np.ndarray:
-    """Vectorised integer BT.601 limited-range conversion, same arithmetic as
-    /root/reference/src/nv12_convert.rs:24-29,124-131 (used to synthesise RGB test frames)."""
-    yv = 298 * (yy.astype(np.int32) - 16)
+# integer YUV -> RGB coefficients by colour code = matrix * 2 + range (include/vittrack_hip.h, vt_color_matrix / vt_color_range):
+# YO, CY, CRV, CGU, CGV, CBU. Row 0 is the reference's BT.601 limited-range formula.
+YUV_COEF = ((16, 298, 409, -100, -208, 516), (0, 256, 359, -88, -183, 454),
+            (16, 298, 459, -55, -136, 541), (0, 256, 403, -48, -120, 475),
+            (16, 298, 430, -48, -167, 548), (0, 256, 377, -42, -146, 482))
+
+
+def nv12_planes_to_rgb8(yy: np.ndarray, uv: np.ndarray, w: int, h: int, matrix: int = 0, full_range: bool = False) -> np.ndarray:
+    """Vectorised integer conversion, same arithmetic as /root/reference/src/nv12_convert.rs:24-29,124-131 (used to
+    synthesise RGB test frames). The defaults are that file's BT.601 limited-range constants; matrix (0 BT.601, 1 BT.709,
+    2 BT.2020) and full_range choose another row of YUV_COEF, as the frame format's colour bits do in the library."""
+    yo, cy, crv, cgu, cgv, cbu = YUV_COEF[int(matrix) * 2 + (1 if full_range else 0)]
+    yv = cy * (yy.astype(np.int32) - yo)
     cols = (np.arange(w) // 2) * 2
     rows = np.arange(h) // 2
     u = uv[rows][:, cols].astype(np.int32) - 128
     v = uv[rows][:, np.minimum(cols + 1, uv.shape[1] - 1)].astype(np.int32) - 128
-    r = (yv + 409 * v + 128) >> 8
-    g = (yv - 100 * u - 208 * v + 128) >> 8
-    b = (yv + 516 * u + 128) >> 8
-    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+    out = np.empty((h, w, 3), np.uint8)      # C-contiguous whatever the layout of the indexed chroma: callers hand it to the GPU as it lies
+    out[..., 0] = np.clip((yv + crv * v + 128) >> 8, 0, 255)
+    out[..., 1] = np.clip((yv + cgu * u + cgv * v + 128) >> 8, 0, 255)
+    out[..., 2] = np.clip((yv + cbu * u + 128) >> 8, 0, 255)
+    return out

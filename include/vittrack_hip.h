@@ -205,7 +205,7 @@ typedef enum vt_pixfmt {
 
 /* Further values of vt_frame.format (vt_pixfmt itself is closed at the eight formats above). Each is DEFINED as a byte
  * re-arrangement of RGB8, NV12 or YUY2 - its sibling - and samples exactly as the sibling does. Values 8..15 and
- * everything above 22 are invalid.
+ * everything above 22 are invalid (in bits 0..7; bits 8..15: vt_color_matrix below).
  * I420 / YV12: the chroma planes are ceil(w/2) x ceil(h/2) bytes and share stride1 (>= ceil(w/2)). plane1 is the FIRST
  * chroma plane (U for I420, V for YV12); the second begins stride1 * ceil(R/2) bytes behind plane1, R = window_h when
  * windowed == 1, else height: the contiguous layout of GStreamer's default GstVideoInfo, of av_image_fill_arrays and of
@@ -225,13 +225,44 @@ typedef enum vt_pixfmt2 {
     VT_PIX2_XBGR  = 22  /* packed x,B,G,R (ABGR: alpha ignored), stride >= 4*w                          -> RGB8 */
 } vt_pixfmt2;
 
+/* The colour MEANING of a YUV frame, chosen per frame: vt_frame.format = pixel format | matrix << 8 | range << 12.
+ * Bits 0..7 hold a vt_pixfmt / vt_pixfmt2 value, bits 8..11 the matrix (0..2), bits 12..15 the range (0..1), bits 16..31
+ * are zero. VT_FRAME_FORMAT(p, VT_COLOR_BT601, VT_RANGE_LIMITED) == p: a plain format value means what it always meant,
+ * the reference's BT.601 limited-range conversion. Refused with VT_ERR_INVALID_ARG, wherever a frame is checked and with
+ * nothing changed: a matrix above 2, a range above 1, any bit above 15, and colour bits that are not zero on a format
+ * without chroma (RGB8, BGR8, RGBX, BGRX, XRGB, XBGR, GRAY8: limited-range RGB and grey are not described); the error
+ * text names the format. Chroma siting (the nearest stored sample, replicated), P010's high byte and the layouts are what
+ * they are without the bits; transfer functions (PQ, HLG) are not applied.
+ * The rule, to the bit, for code c = matrix * 2 + range, Y, U, V the stored samples, int32 arithmetic:
+ *     yv = CY * (Y - YO)
+ *     R = yv + CRV * (V - 128) + 128
+ *     G = yv + CGU * (U - 128) + CGV * (V - 128) + 128
+ *     B = yv + CBU * (U - 128) + 128
+ *     each: min(max(x, 0), 0xffff) >> 8           (arithmetic shift)
+ *     c  matrix, range      YO   CY  CRV   CGU   CGV  CBU
+ *     0  BT.601 limited     16  298  409  -100  -208  516    (the reference's constants)
+ *     1  BT.601 full         0  256  359   -88  -183  454
+ *     2  BT.709 limited     16  298  459   -55  -136  541
+ *     3  BT.709 full         0  256  403   -48  -120  475
+ *     4  BT.2020 limited    16  298  430   -48  -167  548
+ *     5  BT.2020 full        0  256  377   -42  -146  482
+ * Each entry is rint(256 * exact) with Kr / Kb = 0.299 / 0.114, 0.2126 / 0.0722, 0.2627 / 0.0593, luma scale 255/219
+ * (limited) or 1 (full), chroma scale 255/224 or 1; every channel of every row lies within 1 of the clipped, rounded
+ * float64 conversion over all 2^24 triples (DESIGN.md section 3 "Colorimetry").
+ * The entry points WITHOUT a format argument stay BT.601 limited range: the NV12 and YUY2 convenience calls of the single
+ * tracker (init / update, host and device) and the whole-frame NV12 to RGB8 converters. A frame of another colour goes
+ * through the calls that take a vt_frame: the single tracker's frame calls and every group call. */
+typedef enum vt_color_matrix { VT_COLOR_BT601 = 0, VT_COLOR_BT709 = 1, VT_COLOR_BT2020 = 2 } vt_color_matrix;   /* BT.2020: non-constant luminance */
+typedef enum vt_color_range  { VT_RANGE_LIMITED = 0, VT_RANGE_FULL = 1 } vt_color_range;
+#define VT_FRAME_FORMAT(pix, matrix, range) ((int32_t)(pix) | ((int32_t)(matrix) << 8) | ((int32_t)(range) << 12))
+
 typedef struct vt_frame {        /* one device-resident frame (or a window of it) */
     const void* plane0;          /* packed formats and GRAY8: the pixels; NV12 / NV21 / I420 / YV12 / P010 / NV16: Y plane */
     const void* plane1;          /* NV12 / NV21 / P010 / NV16: interleaved chroma plane; I420 / YV12: the first chroma
                                   * plane (the second follows it, see vt_pixfmt2); packed formats and GRAY8: NULL */
     int32_t width, height;       /* size of the FULL frame in pixels */
     int32_t stride0, stride1;    /* bytes */
-    int32_t format;              /* vt_pixfmt or vt_pixfmt2 */
+    int32_t format;              /* vt_pixfmt or vt_pixfmt2, or with colour bits: VT_FRAME_FORMAT (vt_color_matrix) */
     /* The planes may hold only a window of the frame: plane0 points at frame pixel
      * (origin_x, origin_y) (NV12 / NV21 / I420 / YV12 / P010: both even, plane1 at the matching chroma
      * sample; YUY2 / UYVY / NV16: origin_x even). Pixels of the frame
