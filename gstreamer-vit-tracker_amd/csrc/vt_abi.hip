@@ -397,8 +397,8 @@ int vt_group_set_state_box(vt_group* g, int stream, const float* box4) try {
     HIPCHK(hipMemcpy(e->d_states[stream].box, box4, 4 * sizeof(float), hipMemcpyHostToDevice));
     memcpy(e->h_states_all[stream].box, box4, 4 * sizeof(float));
     memcpy(e->known[stream].box, box4, 4 * sizeof(float));
-    if (int rc = e->zero_motion(stream)) return rc;     // the caller placed the box: the jump is no motion
-    if (int rc = e->zero_conflicts(stream)) return rc;  // nor does the last pass's record speak of the new box
+    // the caller placed the box: the jump is no motion, nor does the last pass's conflict record speak of the new box
+    if (int rc = e->reset_records(Engine::RESET_BOX, stream, stream + 1)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return VT_OK;
 } VT_NOTHROW_INT
@@ -490,25 +490,28 @@ int64_t vt_group_read_tensor(vt_group* g, int stream, const char* name, float* o
         return set_err(VT_ERR_HIP, "read_tensor: sync failed");
     const ModelDims& d = e->d;
     std::string n(name);
-    for (const KeyedFeature& f : keyed_features()) {      // by stream, whatever the last pass was: the policy, the stream's record and counters
-        if (n != f.tensor) continue;
-        if (!out) return e->*f.capable ? f.stats_len : (e->*f.stats)(stream, nullptr);
+    // a keyed feature's tensors: its statistics, and the few more that read its store (named by the statistics tensor)
+    const std::string of = n == "health_words" ? "health" : n == "anchor" || n == "probe" ? "appearance" :
+                           n == "proposals_pattern" || n == "proposals_map" ? "proposals" : n;
+    for (const KeyedFeature& f : keyed_features()) {
+        if (of != f.tensor) continue;
+        if (!(e->*f.capable)) return not_enabled(f);    // whatever is asked, the length (out == null) too
+        if (of != n) break;
+        // by stream, whatever the last pass was: the policy, the stream's record and counters
+        if (!out) return f.stats_len;
         if (capacity < f.stats_len) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
         const int rc = (e->*f.stats)(stream, out);
         return rc ? rc : f.stats_len;
     }
     if (n == "health_words") {              // by stream: the record of "health" as exact integers, two 16-bit halves per 32-bit word
-        if (!out) return e->health_capable ? VT_HEALTH_WORDS : e->health_stats(stream, nullptr);
+        if (!out) return VT_HEALTH_WORDS;
         if (capacity < VT_HEALTH_WORDS) return set_err(VT_ERR_INVALID_ARG, "read_tensor: capacity too small");
         const int rc = e->health_words(stream, out);
         return rc ? rc : VT_HEALTH_WORDS;
     }
-    if (n == "anchor" || n == "probe") {    // by stream: the rows the stream is compared with / the rows of its last cut probe
-        if (!e->appear_capable) return e->appearance_stats(stream, nullptr);
+    if (n == "anchor" || n == "probe")      // by stream: the rows the stream is compared with / the rows of its last cut probe
         return copy_out_bf16(n == "anchor" ? e->d_anchor(stream) : e->d_probe(stream), (int64_t)d.nt * d.kpad, out, capacity);
-    }
     if (n == "proposals_pattern" || n == "proposals_map") {     // of the stream's slot in the last pass, as its header says
-        if (!e->prop_capable) return e->proposals_stats(stream, nullptr);
         const int slot = e->slot_of(stream);
         if (slot < 0) return set_err(VT_ERR_INVALID_ARG, "read_tensor: stream %d was not in the last pass", stream);
         PropHead h{};

@@ -826,10 +826,7 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     h_st->frame_w = f->width; h_st->frame_h = f->height;
     h_st->initialized = 1;
     HIPCHK(hipMemcpyAsync(d_states + b, h_st, sizeof(StreamState), hipMemcpyHostToDevice, stream));
-    if (int rc = zero_motion(b)) return rc;
-    if (int rc = zero_conflicts(b)) return rc;
-    if (int rc = zero_health(b)) return rc;
-    if (int rc = zero_arbitrate(b)) return rc;
+    if (int rc = reset_records(RESET_INIT, b, b + 1)) return rc;    // every record spoke of the target the stream had
     to_desc(*f, h_desc);
     // entry b of the per-pass block: every pass uploads its own block ahead of its kernels, in stream order
     HIPCHK(hipMemcpyAsync(d_frames + b, h_desc, sizeof(FrameDesc), hipMemcpyHostToDevice, stream));
@@ -841,10 +838,6 @@ int Engine::launch_init(int b, const vt_frame* f, vt_bbox box, StreamState* h_st
     HIPCHK(hipMemcpyAsync(tpl_init_rows(b), d_patches + (size_t)b * d.ntok * d.kpad,
                           sizeof(bf16_t) * d.nt * d.kpad, hipMemcpyDeviceToDevice, stream));
     HIPCHK(anchor_from_template(b, 0));     // the appearance anchor: the init's rows (buffer 0)
-    if (prop_capable) {     // the proposals a record lists belong to the target the stream had
-        HIPCHK(hipMemsetAsync(d_prop_recs() + b, 0, sizeof(PropRec), stream));
-        h_prop_all[b] = PropRec{};          // the stream is in no outstanding pass: nothing else writes its entry
-    }
     return VT_OK;
 }
 

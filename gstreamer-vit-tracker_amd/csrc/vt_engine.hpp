@@ -297,14 +297,12 @@ struct Engine {
     MotionPolicy motion_policy = VT_MOTION_DEFAULT_POLICY;       // the host's copy
     uint8_t* d_motion = nullptr;                  // ONE allocation: the policy record, then the [B] MotionRec by stream
     MotionPolicy* d_motion_policy() const { return reinterpret_cast<MotionPolicy*>(d_motion); }
-    MotionRec* d_motion_recs() const { return reinterpret_cast<MotionRec*>(d_motion + sizeof(MotionPolicy)); }
-    size_t motion_bytes() const { return sizeof(MotionPolicy) + (size_t)B * sizeof(MotionRec); }
+    size_t motion_off_recs() const { return sizeof(MotionPolicy); }
+    MotionRec* d_motion_recs() const { return reinterpret_cast<MotionRec*>(d_motion + motion_off_recs()); }
+    size_t motion_bytes() const { return motion_off_recs() + (size_t)B * sizeof(MotionRec); }
     MotionRec* h_motion_all = nullptr;            // pinned [B] by stream: beside h_states_all, written by the settle launch
     std::vector<MotionRec> known_motion;          // beside `known`: the records after the last pass the HOST has collected
     int motion_stats(int stream, float* out8);
-    // stream b's record zeroed on the device (behind the stream's work) and in the host's copies: every call that gives
-    // the stream a new state from outside (init, set_state_box, import)
-    int zero_motion(int b);
     // the box the next pass of `stream` is cut around, from what the host knows: the place rule on known / known_motion.
     // steps == 2: the stream is in the pass still running, whose outcome nobody knows - the rule applied twice, once for
     // that pass's own move and once for the next one's (a target at constant velocity lands there)
@@ -338,8 +336,8 @@ struct Engine {
     AppearRec* h_appear_all = nullptr;
     int appearance_anchor(int stream);      // the "appearance_anchor" action: stream's (-1: every initialised stream's) anchor <- its CURRENT template rows
     int appearance_stats(int stream, float* out8);
-    // stream b's anchor <- its current template rows (buffer gen & 1 of a refresh-capable engine's store), its record
-    // zeroed; behind the stream's work. init, queued init, import, copy, the "appearance_anchor" action
+    // stream b's anchor <- its current template rows (buffer gen & 1 of a refresh-capable engine's store); behind the
+    // stream's work. init, queued init, import, copy, the "appearance_anchor" action
     hipError_t anchor_from_template(int b, int gen);
     // reacquire proposals (k_proposals.hip). ONE policy per engine; per stream a record and a counter, per slot the working
     // set of the four launches. The first non-zero "proposals" allocates all of it with the max_cells of that moment and
@@ -392,8 +390,6 @@ struct Engine {
     // every stream back to scene 0. The records of the streams it names are zeroed.
     int conflicts_scene(int value);
     int conflicts_stats(int stream, float* out16);
-    // stream b's record zeroed on the device (behind the stream's work) and in the engine's mirror: wherever zero_motion is called
-    int zero_conflicts(int b);
     // frame health (k_health.hip). ONE policy per engine; per stream a record, three counters, four accumulators, two
     // histograms and two thumbnails of max_cells, per slot a header. The first non-zero "health" allocates all of it with the
     // max_cells of that moment and makes the engine health-capable for good: every pass runs the four launches directly behind
@@ -403,7 +399,7 @@ struct Engine {
     // ONE allocation: the policy | [B] records | [B] counters | [B] headers | [B] accumulators | [B][2][32] histograms |
     // [B][2][max_cells] thumbnails, zero up to the thumbnails
     uint8_t* d_health = nullptr;
-    static size_t health_off_recs() { return 64; }
+    size_t health_off_recs() const { return 64; }
     size_t health_off_counts() const { return health_off_recs() + sizeof(HealthRec) * (size_t)B; }
     size_t health_off_heads() const { return (health_off_counts() + sizeof(HealthCount) * (size_t)B + 63) & ~(size_t)63; }
     size_t health_off_accs() const { return health_off_heads() + sizeof(HealthHead) * (size_t)B; }
@@ -423,9 +419,6 @@ struct Engine {
 #define VT_HEALTH_WORDS (2 * (int)(sizeof(HealthRec) / 4))
     int health_stats(int stream, float* out24);
     int health_words(int stream, float* out);       // the record's 32-bit words, low half then high half: every float exact
-    // stream b without a previous thumbnail, still 0, a zero record, on the device (behind the stream's work) and in the
-    // engine's mirror: wherever zero_conflicts is called for a stream that starts anew
-    int zero_health(int b);
     // peak arbitration (k_arbitrate.hip). ONE policy per engine; per stream a record, two counters and four probes of template
     // rows, per (slot, peak) a ticket and the score launch's chunk partials. The first non-zero "arbitrate" - refused unless the
     // engine is appearance-capable: the anchors are the appearance store's - allocates all of it and makes the engine
@@ -436,7 +429,7 @@ struct Engine {
     // ONE allocation: the policy | [B] records | [B] counters | [4B] tickets | [4B][chunks][5] partials | [B][4][nt][kpad] probes,
     // zero up to the probes
     uint8_t* d_arb = nullptr;
-    static size_t arb_off_recs() { return 64; }
+    size_t arb_off_recs() const { return 64; }
     size_t arb_off_counts() const { return arb_off_recs() + sizeof(ArbRec) * (size_t)B; }
     size_t arb_off_tickets() const { return arb_off_counts() + sizeof(ArbCount) * (size_t)B; }
     size_t arb_off_partials() const { return (arb_off_tickets() + sizeof(unsigned) * VT_ARB_MAX * (size_t)B + 63) & ~(size_t)63; }
@@ -452,8 +445,6 @@ struct Engine {
     ArbRec* h_arb_all = nullptr;
 #define VT_ARB_STATS 48
     int arbitrate_stats(int stream, float* out48);
-    // stream b's record zeroed on the device (behind the stream's work) and in the engine's mirror: wherever zero_health is called
-    int zero_arbitrate(int b);
     vt_result* d_results = nullptr;
     // candidate passes (allocated by the first one): per slot a candidate state, the slot's vt_candidate and the winner
     // table; the pinned ring of candidate lists runs beside h_frames (same ring position, same event)
@@ -513,6 +504,14 @@ struct Engine {
     void adopt_stream_sinks(PassOut from, int stream);      // a collected pass's optional by-stream records of `stream` into the engine's own
     hipError_t sinks_alloc(PassOut* o, unsigned members) const;
     void sinks_free(PassOut* o, unsigned members) const;
+    // What zeroes a by-stream record (the table's columns): an init, synchronous or queued; an import or
+    // being the destination of a copy; vt_group_set_state_box; the feature's on-key set to 0; the feature's action key. Which
+    // of them zeroes which record is the mask of its row of kSinks, and nowhere else.
+    enum : unsigned { RESET_INIT = 1, RESET_IMPORT = 2, RESET_BOX = 4, RESET_OFF = 8, RESET_ACTION = 16 };
+    // The records of streams [first, last) that `event` zeroes, among the sinks `of` (the last two events are one feature's),
+    // on a capable engine: on the device behind the work on the engine's stream, and in the host's copies - the streams are
+    // in no outstanding pass, nothing else writes their entries. The caller synchronises where it has to.
+    int reset_records(unsigned event, int first, int last, unsigned of = SINK_ALL);
     // graph
     // one captured pass per crop-buffer tier (k_preproc.hip: 16 / 32 / 64 KiB of LDS per tile), all captured at creation
     static constexpr int TIERS = 3;
@@ -645,17 +644,18 @@ struct KeyedFeature {
     const char *name, *prefix;                  // for the messages; a key is the feature's iff it starts with prefix
     vtkeys::Apply apply;                        // the key table and its specials
     int32_t Engine::*policy; int words, on_word;        // the host's copy as words (a new Engine's: the defaults); the first non-zero value of word on_word enables
+    const char* on_key;                         // that word's key: set to 0 on a capable engine it is the RESET_OFF of the feature's records
     bool Engine::*capable; uint8_t* Engine::*store;
     size_t (Engine::*store_bytes)() const;      // of an engine with the host's copy as it is
     size_t (Engine::*zeroed_bytes)() const;     // leading bytes the enable zero-fills; null: all
     unsigned sink; const char* tensor; int stats_len;   // SINK_* or 0: none; the name of vt_group_read_tensor that answers stats_len floats from stats
-    int (Engine::*stats)(int stream, float* out);       // on an engine that is not capable: the not-enabled error. The rest: null if not needed
-    int (*changed)(Engine*, const char* key, const int32_t* words) = nullptr;   // behind the small policy copy of a capable engine
+    int (Engine::*stats)(int stream, float* out);       // of a capable engine. The rest: null if not needed
     hipError_t (*fill)(Engine*, uint8_t* store) = nullptr;      // more than zeros and the policy in the new store
     const char* action_key = nullptr; int (Engine::*action)(int value) = nullptr;       // a key that is an action, not a field, and what it does
     int (*refuse_enable)(Engine*) = nullptr;    // a reason this engine cannot enable at all
 };
 const std::array<KeyedFeature, 7>& keyed_features();
+int not_enabled(const KeyedFeature& f);         // the ONE error of a tensor of f's on an engine that is not capable of f
 
 // zero-filled device buffer. The fill is ordered on the ENGINE's stream: that stream is non-blocking, so a
 // hipMemset on the null stream (asynchronous for device memory) is not ordered against the kernels the

@@ -38,17 +38,39 @@ int Engine::enable_feature(const Feature& f) {
 
 // ---- the optional sinks: ONE list --------------------------------------------------------------------
 // A row per optional member of PassOut: bit, element size, by stream (peak records: by slot - adopt_peaks, peaks_n), where
-// it is in a record and in the engine (its own mirror), the feature's capable flag.
-struct Sink { unsigned bit; size_t elem; bool by_stream; void* PassOut::*in; void* Engine::*own; bool Engine::*capable; };
+// it is in a record and in the engine (its own mirror), the feature's capable flag. By stream, behind the brace: the device
+// records [B] (the feature's store, their offset in it), the events that zero them (the table of DESIGN.md section 3, cell by
+// cell - proposals are not reset by an import) and, for motion, the host's second copy beside `known`.
+struct Sink {
+    unsigned bit; size_t elem; bool by_stream; void* PassOut::*in; void* Engine::*own; bool Engine::*capable;
+    struct Recs { uint8_t* Engine::*store; size_t (Engine::*off)() const; unsigned resets; std::vector<MotionRec> Engine::*known; } recs;
+};
 static const Sink kSinks[] = {      // the casts: every member is a pointer to records of elem bytes
     {Engine::SINK_PEAKS, sizeof(vt_peaks), false, (void* PassOut::*)&PassOut::host_peaks, (void* Engine::*)&Engine::h_peaks, &Engine::peaks_capable},
-    {Engine::SINK_MOTION, sizeof(MotionRec), true, (void* PassOut::*)&PassOut::host_motion, (void* Engine::*)&Engine::h_motion_all, &Engine::motion_capable},
-    {Engine::SINK_APPEAR, sizeof(AppearRec), true, (void* PassOut::*)&PassOut::host_appearance, (void* Engine::*)&Engine::h_appear_all, &Engine::appear_capable},
-    {Engine::SINK_PROP, sizeof(PropRec), true, (void* PassOut::*)&PassOut::host_proposals, (void* Engine::*)&Engine::h_prop_all, &Engine::prop_capable},
-    {Engine::SINK_CONFLICT, sizeof(ConflictRec), true, (void* PassOut::*)&PassOut::host_conflicts, (void* Engine::*)&Engine::h_conflict_all, &Engine::conflict_capable},
-    {Engine::SINK_HEALTH, sizeof(HealthRec), true, (void* PassOut::*)&PassOut::host_health, (void* Engine::*)&Engine::h_health_all, &Engine::health_capable},
-    {Engine::SINK_ARB, sizeof(ArbRec), true, (void* PassOut::*)&PassOut::host_arbitrate, (void* Engine::*)&Engine::h_arb_all, &Engine::arb_capable},
+    {Engine::SINK_MOTION, sizeof(MotionRec), true, (void* PassOut::*)&PassOut::host_motion, (void* Engine::*)&Engine::h_motion_all, &Engine::motion_capable,
+     {&Engine::d_motion, &Engine::motion_off_recs, Engine::RESET_INIT | Engine::RESET_IMPORT | Engine::RESET_BOX | Engine::RESET_OFF, &Engine::known_motion}},
+    {Engine::SINK_APPEAR, sizeof(AppearRec), true, (void* PassOut::*)&PassOut::host_appearance, (void* Engine::*)&Engine::h_appear_all, &Engine::appear_capable,
+     {&Engine::d_appear, &Engine::appear_off_recs, Engine::RESET_INIT | Engine::RESET_IMPORT | Engine::RESET_ACTION}},
+    {Engine::SINK_PROP, sizeof(PropRec), true, (void* PassOut::*)&PassOut::host_proposals, (void* Engine::*)&Engine::h_prop_all, &Engine::prop_capable,
+     {&Engine::d_prop, &Engine::prop_off_recs, Engine::RESET_INIT}},
+    {Engine::SINK_CONFLICT, sizeof(ConflictRec), true, (void* PassOut::*)&PassOut::host_conflicts, (void* Engine::*)&Engine::h_conflict_all, &Engine::conflict_capable,
+     {&Engine::d_conflict, &Engine::conflict_off_recs, Engine::RESET_INIT | Engine::RESET_IMPORT | Engine::RESET_BOX | Engine::RESET_ACTION}},
+    {Engine::SINK_HEALTH, sizeof(HealthRec), true, (void* PassOut::*)&PassOut::host_health, (void* Engine::*)&Engine::h_health_all, &Engine::health_capable,
+     {&Engine::d_health, &Engine::health_off_recs, Engine::RESET_INIT | Engine::RESET_IMPORT | Engine::RESET_OFF}},       // the record holds has_prev and still: no previous thumbnail
+    {Engine::SINK_ARB, sizeof(ArbRec), true, (void* PassOut::*)&PassOut::host_arbitrate, (void* Engine::*)&Engine::h_arb_all, &Engine::arb_capable,
+     {&Engine::d_arb, &Engine::arb_off_recs, Engine::RESET_INIT | Engine::RESET_IMPORT | Engine::RESET_OFF}},
 };
+
+int Engine::reset_records(unsigned event, int first, int last, unsigned of) {
+    const size_t n = (size_t)(last - first);
+    for (const Sink& s : kSinks) {
+        if (!(s.bit & of) || !(s.recs.resets & event) || !(this->*s.capable)) continue;
+        HIPCHK(hipMemsetAsync(this->*s.recs.store + (this->*s.recs.off)() + s.elem * (size_t)first, 0, s.elem * n, stream));
+        memset((char*)(this->*s.own) + s.elem * (size_t)first, 0, s.elem * n);
+        if (s.recs.known) std::fill_n((this->*s.recs.known).begin() + first, n, MotionRec{});
+    }
+    return VT_OK;
+}
 
 static hipError_t pinned0(void** p, size_t bytes) {
     if (*p) return hipSuccess;
@@ -344,8 +366,6 @@ int Engine::last_peaks(vt_peaks* out, int n) const {
 
 // [6]: flags, drawn by the stream's last pass, passes drawn / gated / on a format that is not drawable, N of the last label
 int Engine::overlay_stats(int s, float* out6) {
-    if (!overlay_capable)
-        return set_err(VT_ERR_INVALID_ARG, "result overlay: not enabled on this engine (vt_group_set_tuning \"result_overlay\")");
     OverlayStats st{};
     HIPCHK(hipMemcpy(&st, d_overlay_stats() + s, sizeof(st), hipMemcpyDeviceToHost));
     out6[0] = (float)overlay_policy.flags; out6[1] = (float)st.drawn_last; out6[2] = (float)st.n_drawn;
@@ -354,14 +374,6 @@ int Engine::overlay_stats(int s, float* out6) {
 }
 
 // ---- motion prior ------------------------------------------------------------------------------------
-
-int Engine::zero_motion(int b) {
-    if (!motion_capable) return VT_OK;
-    HIPCHK(hipMemsetAsync(d_motion_recs() + b, 0, sizeof(MotionRec), stream));
-    h_motion_all[b] = MotionRec{};
-    known_motion[(size_t)b] = MotionRec{};
-    return VT_OK;
-}
 
 void Engine::predicted_box(int s, float* box4, int steps) const {
     const StreamState& k = known[(size_t)s];
@@ -375,8 +387,6 @@ void Engine::predicted_box(int s, float* box4, int steps) const {
 
 // [8]: the engine flag, vx, vy, live, the shift of the stream's last pass, passes with a shift, failed updates that advanced
 int Engine::motion_stats(int s, float* out8) {
-    if (!motion_capable)
-        return set_err(VT_ERR_INVALID_ARG, "motion prior: not enabled on this engine (vt_group_set_tuning \"motion_prior\")");
     MotionRec r{};
     HIPCHK(hipMemcpy(&r, d_motion_recs() + s, sizeof(r), hipMemcpyDeviceToHost));
     out8[0] = (float)motion_policy.on; out8[1] = r.v[0]; out8[2] = r.v[1]; out8[3] = (float)r.live;
@@ -389,10 +399,7 @@ int Engine::motion_stats(int s, float* out8) {
 hipError_t Engine::anchor_from_template(int b, int gen) {
     if (!appear_capable) return hipSuccess;
     const bf16_t* rows = tpl_init_rows(b) + (refresh_capable ? (size_t)(gen & 1) * appear_rows() : 0);
-    hipError_t he = hipMemcpyAsync(d_anchor(b), rows, sizeof(bf16_t) * appear_rows(), hipMemcpyDeviceToDevice, stream);
-    if (he == hipSuccess) he = hipMemsetAsync(d_appear_recs() + b, 0, sizeof(AppearRec), stream);
-    h_appear_all[b] = AppearRec{};      // the stream is in no outstanding pass: nothing else writes its entry
-    return he;
+    return hipMemcpyAsync(d_anchor(b), rows, sizeof(bf16_t) * appear_rows(), hipMemcpyDeviceToDevice, stream);
 }
 
 int Engine::appearance_anchor(int value) {
@@ -405,7 +412,10 @@ int Engine::appearance_anchor(int value) {
     std::vector<StreamState> sts((size_t)B);
     HIPCHK(hipMemcpy(sts.data(), d_states, sizeof(StreamState) * (size_t)B, hipMemcpyDeviceToHost));
     for (int b = value < 0 ? 0 : value; b < (value < 0 ? B : value + 1); ++b)
-        if (h_initialized[(size_t)b]) HIPCHK(anchor_from_template(b, sts[(size_t)b].tpl_gen));
+        if (h_initialized[(size_t)b]) {
+            HIPCHK(anchor_from_template(b, sts[(size_t)b].tpl_gen));
+            if (int rc = reset_records(RESET_ACTION, b, b + 1, SINK_APPEAR)) return rc;
+        }
     HIPCHK(hipStreamSynchronize(stream));
     return VT_OK;
 }
@@ -427,8 +437,6 @@ static hipError_t fill_anchors(Engine* e, uint8_t* store) {
 
 // [8]: the engine flag, the stream's record (status, similarity, frames_done), its counters (evaluated, gated), period, gate_pm
 int Engine::appearance_stats(int s, float* out8) {
-    if (!appear_capable)
-        return set_err(VT_ERR_INVALID_ARG, "appearance check: not enabled on this engine (vt_group_set_tuning \"appearance\")");
     // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected (a pipelined pass still
     // running has written the device record already, and may yet be redone); the counters: the device's
     const AppearRec r = h_appear_all[s];
@@ -444,8 +452,6 @@ int Engine::appearance_stats(int s, float* out8) {
 // [VT_PROP_STATS]: mode, status, frames_done, n, c, Wg, Hg, evaluated, period, max, min_sim_pm, max_cells, then per
 // proposal sim, box[4], position
 int Engine::proposals_stats(int s, float* out) {
-    if (!prop_capable)
-        return set_err(VT_ERR_INVALID_ARG, "reacquire proposals: not enabled on this engine (vt_group_set_tuning \"proposals\")");
     // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counter: the device's
     const PropRec r = h_prop_all[s];
     int32_t ev = 0;
@@ -464,13 +470,6 @@ int Engine::proposals_stats(int s, float* out) {
 
 // ---- stream conflicts ----------------------------------------------------------------------------------
 
-int Engine::zero_conflicts(int b) {
-    if (!conflict_capable) return VT_OK;
-    HIPCHK(hipMemsetAsync(d_conflict_recs() + b, 0, sizeof(ConflictRec), stream));
-    h_conflict_all[b] = ConflictRec{};      // the stream is in no outstanding pass: nothing else writes its entry
-    return VT_OK;
-}
-
 int Engine::conflicts_scene(int value) {
     if (!conflict_capable)
         return set_err(VT_ERR_INVALID_ARG, "conflicts_scene: stream conflicts are not enabled on this engine (vt_group_set_tuning \"conflicts\")");
@@ -485,8 +484,7 @@ int Engine::conflicts_scene(int value) {
     DEVICE_SCOPE(device);
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipMemcpy(d_conflict_scenes() + first, now.data() + first, sizeof(int32_t) * (size_t)(last - first), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_conflict_recs() + first, 0, sizeof(ConflictRec) * (size_t)(last - first)));
-    std::fill(h_conflict_all + first, h_conflict_all + last, ConflictRec{});
+    if (int rc = reset_records(RESET_ACTION, first, last, SINK_CONFLICT)) return rc;
     conflict_scenes.swap(now);
     return VT_OK;
 }
@@ -494,8 +492,6 @@ int Engine::conflicts_scene(int value) {
 // [16]: the engine flag, the stream's record (status, frames_done, n_over, partner[4], iou[4]), its counters (evaluated,
 // conflicting, gated), its scene
 int Engine::conflicts_stats(int s, float* out16) {
-    if (!conflict_capable)
-        return set_err(VT_ERR_INVALID_ARG, "stream conflicts: not enabled on this engine (vt_group_set_tuning \"conflicts\")");
     // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counters: the device's
     const ConflictRec r = h_conflict_all[s];
     ConflictCount c{};
@@ -509,19 +505,10 @@ int Engine::conflicts_stats(int s, float* out16) {
 
 // ---- frame health ------------------------------------------------------------------------------------
 
-int Engine::zero_health(int b) {
-    if (!health_capable) return VT_OK;
-    HIPCHK(hipMemsetAsync(d_health_recs() + b, 0, sizeof(HealthRec), stream));     // has_prev, still and the record
-    h_health_all[b] = HealthRec{};          // the stream is in no outstanding pass: nothing else writes its entry
-    return VT_OK;
-}
-
 // [24], for people: mode, status, frames_done, flags, c, Wg, Hg, still, S1 / n, the standard deviation, D / n,
 // HD * 1000 / (2 n), G * 1000 / G_ref, evaluated, flagged, gated, then period, cell, still_run, flat_q, cut_pm, gate, and two
 // zeros. The exact integers: "health_words"
 int Engine::health_stats(int s, float* out) {
-    if (!health_capable)
-        return set_err(VT_ERR_INVALID_ARG, "frame health: not enabled on this engine (vt_group_set_tuning \"health\")");
     // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counters: the device's
     const HealthRec r = h_health_all[s];
     HealthCount c{};
@@ -538,7 +525,6 @@ int Engine::health_stats(int s, float* out) {
 }
 
 int Engine::health_words(int s, float* out) {
-    if (!health_capable) return health_stats(s, nullptr);
     uint32_t w[sizeof(HealthRec) / 4];
     memcpy(w, h_health_all + s, sizeof(w));
     for (size_t k = 0; k < sizeof(HealthRec) / 4; ++k) { out[2 * k] = (float)(w[k] & 0xFFFFu); out[2 * k + 1] = (float)(w[k] >> 16); }
@@ -547,18 +533,9 @@ int Engine::health_words(int s, float* out) {
 
 // ---- peak arbitration -----------------------------------------------------------------------------------
 
-int Engine::zero_arbitrate(int b) {
-    if (!arb_capable) return VT_OK;
-    HIPCHK(hipMemsetAsync(d_arb_recs() + b, 0, sizeof(ArbRec), stream));
-    h_arb_all[b] = ArbRec{};            // the stream is in no outstanding pass: nothing else writes its entry
-    return VT_OK;
-}
-
 // [48]: the flag, status, frames_done, n, chosen, evaluated, switched, 0; then four peaks of cell, status, score, response,
 // similarity, the float box x, y, w, h, 0. Every value is exact in binary32 (cells, counts and statuses are small integers)
 int Engine::arbitrate_stats(int s, float* out) {
-    if (!arb_capable)
-        return set_err(VT_ERR_INVALID_ARG, "peak arbitration: not enabled on this engine (vt_group_set_tuning \"arbitrate\")");
     // the record: the pinned mirror, i.e. that of the stream's last pass the HOST has collected; the counters: the device's
     const ArbRec r = h_arb_all[s];
     ArbCount c{};
@@ -598,31 +575,9 @@ static_assert(sizeof(HealthPolicy) == 4 * HL_WORDS && at(offsetof(HealthPolicy, 
               kHealthKeys[HL_PERIOD].hi == VT_HEALTH_MAX_PERIOD && kHealthKeys[HL_MAX_CELLS].lo == VT_HEALTH_MIN_CELLS &&
               kHealthKeys[HL_MAX_CELLS].hi == VT_HEALTH_MAX_CELLS && HL_WORDS <= kMaxWords, "HealthPolicy");
 
-// "motion_prior" 0 on a capable engine zeroes every stream's record, on the device and in both host copies
-static int motion_changed(Engine* e, const char* key, const int32_t* words) {
-    if (strcmp(key, "motion_prior") != 0 || words[MO_ON] != 0) return VT_OK;
-    HIPCHK(hipMemset(e->d_motion_recs(), 0, sizeof(MotionRec) * (size_t)e->B));
-    memset(e->h_motion_all, 0, sizeof(MotionRec) * (size_t)e->B);
-    e->known_motion.assign((size_t)e->B, MotionRec{});
-    return VT_OK;
-}
-// "health" 0 on a capable engine zeroes every stream's record and bookkeeping, on the device and in the host's copies
-static int health_changed(Engine* e, const char* key, const int32_t* words) {
-    if (strcmp(key, "health") != 0 || words[HL_ON] != 0) return VT_OK;
-    HIPCHK(hipMemset(e->d_health_recs(), 0, sizeof(HealthRec) * (size_t)e->B));
-    memset(e->h_health_all, 0, sizeof(HealthRec) * (size_t)e->B);
-    return VT_OK;
-}
 static_assert(sizeof(ArbPolicy) == 4 * AR_WORDS && at(offsetof(ArbPolicy, on), AR_ON) && at(offsetof(ArbPolicy, max_peaks), AR_MAX) &&
               at(offsetof(ArbPolicy, radius), AR_RADIUS) && at(offsetof(ArbPolicy, min_resp_pm), AR_MIN_RESP_PM) && at(offsetof(ArbPolicy, low_pm), AR_LOW_PM) &&
               at(offsetof(ArbPolicy, high_pm), AR_HIGH_PM) && kArbKeys[AR_MAX].hi == VT_ARB_MAX && AR_WORDS <= kMaxWords, "ArbPolicy");
-// "arbitrate" 0 on a capable engine zeroes every stream's record, on the device and in the host's copy
-static int arb_changed(Engine* e, const char* key, const int32_t* words) {
-    if (strcmp(key, "arbitrate") != 0 || words[AR_ON] != 0) return VT_OK;
-    HIPCHK(hipMemset(e->d_arb_recs(), 0, sizeof(ArbRec) * (size_t)e->B));
-    memset(e->h_arb_all, 0, sizeof(ArbRec) * (size_t)e->B);
-    return VT_OK;
-}
 // the anchors are the appearance store's
 static int arb_refuse(Engine* e) {
     return e->appear_capable ? VT_OK
@@ -639,27 +594,30 @@ static int proposals_refuse(Engine* e) {
 // the policy up to the probes. The casts: a policy is words from its first member on.
 const std::array<KeyedFeature, 7>& keyed_features() {
     static const std::array<KeyedFeature, 7> list = {{
-        {"result overlay", "result_overlay", apply_overlay, (int32_t Engine::*)&Engine::overlay_policy, OV_WORDS, OV_FLAGS, &Engine::overlay_capable,
+        {"result overlay", "result_overlay", apply_overlay, (int32_t Engine::*)&Engine::overlay_policy, OV_WORDS, OV_FLAGS, "result_overlay", &Engine::overlay_capable,
          &Engine::d_overlay, &Engine::overlay_bytes, nullptr, 0, "result_overlay", 6, &Engine::overlay_stats},
-        {"motion prior", "motion_", apply_motion, (int32_t Engine::*)&Engine::motion_policy, MO_WORDS, MO_ON, &Engine::motion_capable,
-         &Engine::d_motion, &Engine::motion_bytes, nullptr, Engine::SINK_MOTION, "motion", 8, &Engine::motion_stats, motion_changed},
-        {"appearance check", "appearance", apply_appearance, (int32_t Engine::*)&Engine::appear_policy, AP_WORDS, AP_ON, &Engine::appear_capable,
+        {"motion prior", "motion_", apply_motion, (int32_t Engine::*)&Engine::motion_policy, MO_WORDS, MO_ON, "motion_prior", &Engine::motion_capable,
+         &Engine::d_motion, &Engine::motion_bytes, nullptr, Engine::SINK_MOTION, "motion", 8, &Engine::motion_stats},
+        {"appearance check", "appearance", apply_appearance, (int32_t Engine::*)&Engine::appear_policy, AP_WORDS, AP_ON, "appearance", &Engine::appear_capable,
          &Engine::d_appear, &Engine::appear_bytes, nullptr, Engine::SINK_APPEAR, "appearance", 8, &Engine::appearance_stats,
-         nullptr, fill_anchors, "appearance_anchor", &Engine::appearance_anchor},
-        {"reacquire proposals", "proposals", apply_proposals, (int32_t Engine::*)&Engine::prop_policy, PR_WORDS, PR_MODE, &Engine::prop_capable,
+         fill_anchors, "appearance_anchor", &Engine::appearance_anchor},
+        {"reacquire proposals", "proposals", apply_proposals, (int32_t Engine::*)&Engine::prop_policy, PR_WORDS, PR_MODE, "proposals", &Engine::prop_capable,
          &Engine::d_prop, &Engine::prop_bytes, &Engine::prop_off_thumb, Engine::SINK_PROP, "proposals", VT_PROP_STATS, &Engine::proposals_stats,
-         nullptr, nullptr, nullptr, nullptr, proposals_refuse},
-        {"stream conflicts", "conflicts", apply_conflicts, (int32_t Engine::*)&Engine::conflict_policy, CF_WORDS, CF_ON, &Engine::conflict_capable,
+         nullptr, nullptr, nullptr, proposals_refuse},
+        {"stream conflicts", "conflicts", apply_conflicts, (int32_t Engine::*)&Engine::conflict_policy, CF_WORDS, CF_ON, "conflicts", &Engine::conflict_capable,
          &Engine::d_conflict, &Engine::conflict_bytes, nullptr, Engine::SINK_CONFLICT, "conflicts", 16, &Engine::conflicts_stats,
-         nullptr, nullptr, "conflicts_scene", &Engine::conflicts_scene},
-        {"frame health", "health", apply_health, (int32_t Engine::*)&Engine::health_policy, HL_WORDS, HL_ON, &Engine::health_capable,
-         &Engine::d_health, &Engine::health_bytes, &Engine::health_off_thumbs, Engine::SINK_HEALTH, "health", VT_HEALTH_STATS, &Engine::health_stats,
-         health_changed},
-        {"peak arbitration", "arbitrate", apply_arbitrate, (int32_t Engine::*)&Engine::arb_policy, AR_WORDS, AR_ON, &Engine::arb_capable,
+         nullptr, "conflicts_scene", &Engine::conflicts_scene},
+        {"frame health", "health", apply_health, (int32_t Engine::*)&Engine::health_policy, HL_WORDS, HL_ON, "health", &Engine::health_capable,
+         &Engine::d_health, &Engine::health_bytes, &Engine::health_off_thumbs, Engine::SINK_HEALTH, "health", VT_HEALTH_STATS, &Engine::health_stats},
+        {"peak arbitration", "arbitrate", apply_arbitrate, (int32_t Engine::*)&Engine::arb_policy, AR_WORDS, AR_ON, "arbitrate", &Engine::arb_capable,
          &Engine::d_arb, &Engine::arb_bytes, &Engine::arb_off_probe, Engine::SINK_ARB, "arbitrate", VT_ARB_STATS, &Engine::arbitrate_stats,
-         arb_changed, nullptr, nullptr, nullptr, arb_refuse},
+         nullptr, nullptr, nullptr, arb_refuse},
     }};
     return list;
+}
+
+int not_enabled(const KeyedFeature& f) {
+    return set_err(VT_ERR_INVALID_ARG, "%s: not enabled on this engine (vt_group_set_tuning \"%s\")", f.name, f.on_key);
 }
 
 int Engine::set_keyed(const KeyedFeature& f, const std::string& key, int value) {
@@ -683,7 +641,8 @@ int Engine::set_keyed(const KeyedFeature& f, const std::string& key, int value) 
         if (int rc = enable_store(f.name, size, zeroed, p, bytes, f.sink, f.fill, wire)) { memcpy(host, before, bytes); return rc; }
     } else if (this->*f.capable) {
         HIPCHK(hipMemcpy(this->*f.store, p, bytes, hipMemcpyHostToDevice));
-        if (int rc = f.changed ? f.changed(this, key.c_str(), p) : VT_OK) return rc;
+        if (key == f.on_key && p[f.on_word] == 0)       // that key, value 0: every stream's records (kSinks: RESET_OFF)
+            if (int rc = reset_records(RESET_OFF, 0, B, f.sink)) return rc;
     }
     memcpy(host, p, bytes);
     return VT_OK;

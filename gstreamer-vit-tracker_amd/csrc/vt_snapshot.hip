@@ -277,11 +277,10 @@ static int snap_import(Engine* e, int t, const StreamState& st, const RefreshPol
     const hipError_t he = launch_snapshot_unpack(snap_args(e, t, sg->d), e->stream);
     (void)hipEventRecord(sg->done_ev, e->stream);       // also after a failed launch: the staging is busy until then
     if (he != hipSuccess) return set_err(VT_ERR_HIP, "snapshot unpack: %s", hipGetErrorString(he));
-    if (int rc = e->zero_motion(t)) return rc;          // no part of a snapshot: the imported stream starts without a velocity
-    if (int rc = e->zero_conflicts(t)) return rc;       // nor is the conflict record (the stream's scene stays: policy, not state)
-    if (int rc = e->zero_arbitrate(t)) return rc;       // nor the arbitration record
-    if (int rc = e->zero_health(t)) return rc;          // nor a thumbnail: the imported stream starts without a previous one
-    HIPCHK(e->anchor_from_template(t, st.tpl_gen));     // nor is the appearance anchor: the imported rows become it
+    // no part of a snapshot: the imported stream starts without a velocity, a previous thumbnail or a record of the target
+    // it had (its scene stays: policy, not state), and the imported rows become its appearance anchor
+    if (int rc = e->reset_records(Engine::RESET_IMPORT, t, t + 1)) return rc;
+    HIPCHK(e->anchor_from_template(t, st.tpl_gen));
     if (!pipelined) HIPCHK(hipStreamSynchronize(e->stream));    // synchronous, like vt_group_init_device
     // what the host knows of this stream is the imported state from now on: the next window is cut around its box,
     // exact, and a rewind behind a queued import restores it (the template store is not rewound)

@@ -78,11 +78,13 @@ def test_the_product_header_carries_the_keys_the_tensor_and_the_rule():
 def test_one_keyed_feature_one_sink_and_the_python_methods(vt):
     feats = open(os.path.join(CSRC, "vt_features.hip")).read()
     assert "std::array<KeyedFeature, 7>" in feats
-    # ONE row of keyed_features() carries the table, the store, the sink and the two specials; ONE row of kSinks the mirror
-    assert re.search(r'\{"peak arbitration", "arbitrate", apply_arbitrate,[^}]*&Engine::arb_capable,[^}]*Engine::SINK_ARB, "arbitrate", VT_ARB_STATS,'
-                     r'[^}]*arb_changed,[^}]*arb_refuse\}', feats)
-    assert re.search(r"\{Engine::SINK_ARB, sizeof\(ArbRec\), true,[^}]*PassOut::host_arbitrate,[^}]*Engine::h_arb_all, &Engine::arb_capable\}", feats)
-    assert "arb_refuse" in feats and "arb_changed" in feats
+    # ONE row of keyed_features() carries the table, the on-key, the store, the sink and the refusal; ONE row of kSinks the
+    # mirror, where the records lie and the events that zero them: an init, an import, "arbitrate" 0
+    assert re.search(r'\{"peak arbitration", "arbitrate", apply_arbitrate,[^}]*AR_ON, "arbitrate", &Engine::arb_capable,[^}]*Engine::SINK_ARB, "arbitrate", VT_ARB_STATS,'
+                     r'[^}]*arb_refuse\}', feats)
+    assert re.search(r"\{Engine::SINK_ARB, sizeof\(ArbRec\), true,[^}]*PassOut::host_arbitrate,[^}]*Engine::h_arb_all, &Engine::arb_capable,\s*"
+                     r"\{&Engine::d_arb, &Engine::arb_off_recs, Engine::RESET_INIT \| Engine::RESET_IMPORT \| Engine::RESET_OFF\}\}", feats)
+    assert "arb_refuse" in feats and "_changed" not in feats and "zero_arbitrate" not in feats
     engine = open(os.path.join(CSRC, "vt_engine.hip")).read()
     i = [engine.index(f'L("{n}"') for n in ("cand_commit", "arbitrate_list", "arbitrate_probe", "arbitrate_score", "arbitrate_commit", "motion_settle")]
     assert i == sorted(i)

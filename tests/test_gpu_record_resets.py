@@ -203,6 +203,37 @@ def test_set_scene_zeroes_the_conflict_records_of_the_streams_it_names(rig):
     assert not np.any(after[0]["conflicts"][RECORD["conflicts"]])
 
 
+@pytest.fixture(scope="module")
+def twins(gpu, weights_tiny, clip):
+    """two rigs that only ever make the same calls (their overlays have drawn the same boxes into their frames)"""
+    pair = [Rig(gpu, weights_tiny, clip) for _ in range(2)]
+    yield pair
+    for r in pair:
+        r.close()
+
+
+@pytest.mark.parametrize("feature", ["motion", "health", "arbitrate", "conflicts"])
+def test_a_pass_directly_behind_a_reset_runs_behind_it(twins, feature):
+    """The resets that fill on the engine's stream without waiting for it - an on-key set to 0, vt_group_set_scene - and then,
+    with no read in between, one pass: stream 1's tensor equals, word for word, that of the twin, which made the same calls
+    with a read (it synchronises the stream) between the reset and the pass. A consistency check of the order, no race
+    detector."""
+    got = []
+    for r, read_between in zip(twins, (False, True)):
+        r.refill({feature})
+        if feature == "conflicts":
+            r.g.set_scene(None, 1)
+        else:
+            r.g.set_tuning(ON_KEY[feature], 0)
+        if read_between:
+            r.g.read_tensor(feature, 1)
+        r.g.update_device([r.frames[3]] * 2)
+        got.append(r.tensors(1))
+    for n in RECORD:
+        if FEATURE_OF.get(n, n) == feature:
+            assert np.array_equal(got[0][n], got[1][n]), f"'{n}': {got[0][n]} without a read, {got[1][n]} with one"
+
+
 NOT_ENABLED = {
     "result_overlay": 'result overlay: not enabled on this engine (vt_group_set_tuning "result_overlay")',
     "motion": 'motion prior: not enabled on this engine (vt_group_set_tuning "motion_prior")',
