@@ -30,7 +30,7 @@ LIB_OPS = os.path.join(PKG, "libvittrack_hip_ops.so")
 LIB_HOST = os.path.join(HOST, "libvittrack_host.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_arbitrate.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_health.hip", "k_overlay.hip", "k_result_overlay.hip",
+HIP_SOURCES = ["k_preproc.hip", "k_refresh.hip", "k_chip.hip", "k_gemm.hip", "k_gemm256.hip", "k_attn.hip", "k_misc.hip", "k_head.hip", "k_peaks.hip", "k_cand.hip", "k_motion.hip", "k_appearance.hip", "k_arbitrate.hip", "k_proposals.hip", "k_camera_motion.hip", "k_conflicts.hip", "k_health.hip", "k_movers.hip", "k_overlay.hip", "k_result_overlay.hip",
                "k_snapshot.hip", "vt_engine.hip", "vt_features.hip", "vt_abi.hip", "vt_ingest.hip", "vt_snapshot.hip", "vt_rccl.hip"]
 OPS_SOURCES = ["vt_ops.hip"]          # libvittrack_hip_ops.so only
 HEADER = os.path.join(PKG, "..", "include", "vittrack_hip.h")
@@ -68,7 +68,7 @@ HEADERS = ["vt_common.hpp", "vt_frame.hpp", "vt_engine.hpp", "vt_ops_host.hpp", 
            "k_preproc.hpp", "k_preproc_dev.hpp", "k_preproc_body.inc", "k_thumb_dev.hpp", "k_overlay.hpp", "k_overlay_dev.hpp",
            "k_refresh.hpp", "k_refresh_dev.hpp", "k_refresh_crop.inc", "k_chip.hpp", "k_peaks.hpp", "k_peaks_dev.hpp",
            "k_motion.hpp", "k_appearance.hpp", "k_appearance_dev.hpp", "k_arbitrate.hpp", "k_proposals.hpp",
-           "k_camera_motion.hpp", "k_conflicts.hpp", "k_health.hpp", "k_cand.hpp", "k_result_overlay.hpp", "k_snapshot.hpp"]
+           "k_camera_motion.hpp", "k_conflicts.hpp", "k_health.hpp", "k_movers.hpp", "k_cand.hpp", "k_result_overlay.hpp", "k_snapshot.hpp"]
 
 
 def tu_sha256(source: str, flags: "list[str]") -> str:

@@ -9,16 +9,23 @@
 
 namespace vtkeys {
 // a value < 0 stands for the default's word, anything else must lie in lo..hi; refusal: a printf format for the caller's value
-struct Key { const char* key; int word; int32_t lo, hi; const char* refusal; };
+// bits > 0: the key is the field of `bits` bits at bit `shift` of its word (several small keys share a word); 0: the whole word
+struct Key {
+    const char* key; int word; int32_t lo, hi; const char* refusal; int shift = 0, bits = 0;
+    constexpr int32_t get(int32_t w) const { return bits ? (int32_t)(((uint32_t)w >> shift) & ((1u << bits) - 1u)) : w; }
+    constexpr int32_t put(int32_t w, int32_t v) const {
+        return bits ? (int32_t)(((uint32_t)w & ~(((1u << bits) - 1u) << shift)) | ((uint32_t)v << shift)) : v;
+    }
+};
 enum Answer { ACCEPTED, REFUSED, UNKNOWN };     // REFUSED: words untouched, text written; UNKNOWN: not a key of the table
 constexpr int kMaxWords = 8;                    // of the longest policy
 template <int N>
 inline Answer apply(const Key (&rows)[N], const char* key, int value, const int32_t* def, int32_t* words, char* text, size_t cap) {
     for (const Key& k : rows) {
         if (strcmp(key, k.key) != 0) continue;
-        const int32_t v = value < 0 ? def[k.word] : value;
+        const int32_t v = value < 0 ? k.get(def[k.word]) : value;
         if (v < k.lo || v > k.hi) { snprintf(text, cap, k.refusal, value); return REFUSED; }
-        words[k.word] = v;
+        words[k.word] = k.put(words[k.word], v);
         return ACCEPTED;
     }
     return UNKNOWN;
@@ -33,9 +40,15 @@ template <int N>
 inline int check_words(const Key (&rows)[N], Apply apply, const int32_t* def, const int32_t* policy, int32_t* words) {
     char text[256];
     for (int i = 0; i < N; ++i) {
-        const int32_t v = policy[rows[i].word];
+        const int32_t v = policy[rows[i].word] < 0 ? -1 : rows[i].get(policy[rows[i].word]);
         if (v < 0 || apply(rows[i].key, v, def, words, false, text, sizeof(text)) != ACCEPTED) return i;
     }
+    // a word shared by bit-field keys holds nothing but their fields: a bit beside them is refused at the word's first row
+    for (int i = 0; i < N; ++i)
+        if (rows[i].bits && words[rows[i].word] != policy[rows[i].word]) {
+            for (int j = 0; j < N; ++j)
+                if (rows[j].word == rows[i].word) return j;
+        }
     return -1;
 }
 
@@ -191,5 +204,35 @@ static constexpr Key kArbKeys[] = {
 };
 inline Answer apply_arbitrate(const char* key, int value, const int32_t* def, int32_t* words, bool, char* text, size_t cap) {
     return apply(kArbKeys, key, value, def, words, text, cap);
+}
+
+// moving regions (k_movers.hip): the policy words of vt_op_movers, which validates them with this table; no engine key
+// reaches it yet. Ten keys in
+// eight words - kMaxWords stays 8 -: "movers_learn", "movers_min_nb" and "movers_max" are four-bit fields of word MV_SHAPE
+enum { MV_ON, MV_PERIOD, MV_CELL, MV_THR, MV_MIN_AREA, MV_GLOBAL_PM, MV_SHAPE, MV_MAX_CELLS, MV_WORDS = 8 };     // MoverPolicy
+static constexpr Key kMoverKeys[] = {
+    {"movers", MV_ON, 0, 1, "movers: %d (0: off, 1: on)"},
+    {"movers_period", MV_PERIOD, 1, 1000000, "movers_period: %d (1..1000000)"},
+    {"movers_cell", MV_CELL, 0, 32, "movers_cell: %d (0: automatic, 4, 8, 16 or 32)"},
+    {"movers_thr", MV_THR, 0, 4080, "movers_thr: %d (0..4080)"},
+    {"movers_min_area", MV_MIN_AREA, 1, 262144, "movers_min_area: %d (1..262144)"},
+    {"movers_global_pm", MV_GLOBAL_PM, 0, 1000, "movers_global_pm: %d (0..1000, 1000: never)"},
+    {"movers_learn", MV_SHAPE, 0, 8, "movers_learn: %d (0..8)", 0, 4},
+    {"movers_min_nb", MV_SHAPE, 1, 9, "movers_min_nb: %d (1..9)", 4, 4},
+    {"movers_max", MV_SHAPE, 1, 8, "movers_max: %d (1..8)", 8, 4},
+    {"movers_max_cells", MV_MAX_CELLS, 4096, 262144, "movers_max_cells: %d (4096..262144)"},
+};
+// "movers_cell": 0 or a power of two in 4..32; "movers_max_cells" sizes the store: frozen once the engine is capable
+inline Answer apply_movers(const char* key, int value, const int32_t* def, int32_t* words, bool capable, char* text, size_t cap) {
+    if (capable && strcmp(key, "movers_max_cells") == 0) {
+        snprintf(text, cap, "movers_max_cells: fixed by the first enable of \"movers\" (%d)", (int)words[MV_MAX_CELLS]);
+        return REFUSED;
+    }
+    if (strcmp(key, "movers_cell") == 0 && value > 0 && (value < 4 || (value & (value - 1)) != 0)) {
+        for (const Key& k : kMoverKeys)         // the row of that key, wherever it stands in the table
+            if (strcmp(k.key, key) == 0) snprintf(text, cap, k.refusal, value);
+        return REFUSED;
+    }
+    return apply(kMoverKeys, key, value, def, words, text, cap);
 }
 }   // namespace vtkeys

@@ -5,6 +5,7 @@
 // Every buffer a kernel writes and a hook downloads is a GuardedOut, checked with guards_intact() after the synchronise;
 // the timing entry points and loops are not.
 #include "vt_ops_util.hpp"
+#include "k_movers.hpp"
 #include "../../include/vittrack_hip_ops.h"
 
 // q, k, v [B*N][D] packed into the layouts the QKV epilogue produces: qk [B*N][2D], vt [B*H][64][npad] (perm: in the key
@@ -936,6 +937,55 @@ int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int 
                                                 {&ghead, "headers"}, {&grec, "records"}, {&gcnt, "counters"}})) return rc;
     HIPCHK(gst.download(states)); HIPCHK(gth.download(thumbs)); HIPCHK(gacc.download(accs)); HIPCHK(ghist.download(hist));
     HIPCHK(ghead.download(heads)); HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
+    hrec.back();
+    return VT_OK;
+} VT_NOTHROW_INT
+
+// The launches of the moving regions on given operands: see include/vittrack_hip_ops.h. Nothing runs but
+// launch_movers_prepare, _thumb, _label and _list, in that order. Every array the launches may write sits between guard
+// bands; headers, accumulators, labels, extents and thumbnails start as 0xff bytes, the others as the caller's.
+int vt_op_movers(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
+                 const int32_t* policy, int device_frames, uint16_t* bg, uint16_t* thumbs, uint8_t* mask, int32_t* labels, int32_t* exts,
+                 int32_t* accs, void* heads, void* records, void* counts, void* host_records) try {
+    if (!frames || !states || !policy || !bg || !thumbs || !mask || !labels || !exts || !accs || !heads || !records || !counts || n < 1 ||
+        n > VT_MAX_STREAMS || n_streams < 1 || n_streams > VT_MAX_STREAMS)
+        return set_err(VT_ERR_INVALID_ARG, "bad argument");
+    static_assert(sizeof(MoverPolicy) == 4 * MV_WORDS, "MoverPolicy");
+    MoverPolicy pol;
+    if (int rc = policy_from_words("movers", kMoverKeys, apply_movers, VT_MOVER_DEFAULT_POLICY, policy, &pol)) return rc;
+    HookFrames fr;
+    SlotMaps maps{slot_stream, nullptr, n, n_streams};
+    if (int rc = fr.check(frames, n)) return rc;
+    if (int rc = maps.check_all("movers")) return rc;
+    if (int rc = check_device(device_id)) return rc;
+    DEVICE_SCOPE(device_id);
+    const size_t ns = (size_t)n_streams, sb = ns * sizeof(StreamState), rb = ns * sizeof(MoverRec), cb = ns * sizeof(MoverCount);
+    const size_t cells = ns * (size_t)pol.max_cells, ab = ns * MOVER_ACCS * sizeof(int32_t), hdb = (size_t)n * sizeof(MoverHead);
+    DevArr dpol;
+    GuardedOut gst, gbg, gth, gmask, glab, gext, gacc, ghead, grec, gcnt;
+    Mirror hrec;
+    HIPCHK(dpol.upload(&pol, sizeof(pol)));
+    HIPCHK(gst.upload(states, sb)); HIPCHK(gbg.upload(bg, cells * 2)); HIPCHK(gmask.upload(mask, cells)); HIPCHK(grec.upload(records, rb));
+    HIPCHK(gcnt.upload(counts, cb)); HIPCHK(gth.alloc(cells * 2)); HIPCHK(glab.alloc(cells * 4)); HIPCHK(gext.alloc(cells * 4 * MOVER_EXTS));
+    HIPCHK(gacc.alloc(ab)); HIPCHK(ghead.alloc(hdb));
+    HIPCHK(hrec.from(host_records, rb));
+    HIPCHK(maps.upload());
+    HIPCHK(fr.upload(device_frames));
+    const MoverArgs va{fr.dev(), gst.as<const StreamState>(), maps.dev_slot_stream(), dpol.as<const MoverPolicy>(), fr.dev_flag(),
+                       grec.as<MoverRec>(), gcnt.as<MoverCount>(), ghead.as<MoverHead>(), gacc.as<int32_t>(), glab.as<int32_t>(),
+                       gext.as<int32_t>(), gbg.as<uint16_t>(), gth.as<uint16_t>(), gmask.as<uint8_t>(), hrec.as<MoverRec>(),
+                       pol.max_cells, n};
+    HIPCHK(launch_movers_prepare(va, nullptr));
+    HIPCHK(launch_movers_thumb(va, fr.level, nullptr));
+    HIPCHK(launch_movers_label(va, nullptr));
+    HIPCHK(launch_movers_list(va, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = guards_intact("movers", {{&gst, "states"}, {&gbg, "backgrounds"}, {&gth, "thumbnails"}, {&gmask, "mask"}, {&glab, "labels"},
+                                          {&gext, "extents"}, {&gacc, "accumulators"}, {&ghead, "headers"}, {&grec, "records"},
+                                          {&gcnt, "counters"}})) return rc;
+    HIPCHK(gst.download(states)); HIPCHK(gbg.download(bg)); HIPCHK(gth.download(thumbs)); HIPCHK(gmask.download(mask));
+    HIPCHK(glab.download(labels)); HIPCHK(gext.download(exts)); HIPCHK(gacc.download(accs)); HIPCHK(ghead.download(heads));
+    HIPCHK(grec.download(records)); HIPCHK(gcnt.download(counts));
     hrec.back();
     return VT_OK;
 } VT_NOTHROW_INT

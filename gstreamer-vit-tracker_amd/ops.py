@@ -24,7 +24,7 @@ OPS_EXPORTS = [
     "vt_op_gemm_bf16_lo", "vt_op_headconv_ln_bf16_lo",
     "vt_op_gemm_resid_seg_bf16", "vt_op_attention_queries_bf16", "vt_op_head_decode", "vt_op_response_peaks", "vt_op_result_overlay",
     "vt_op_motion_prior", "vt_op_appearance_score", "vt_op_proposals", "vt_op_camera_motion", "vt_op_ln_chain_bf16",
-    "vt_op_stream_conflicts", "vt_op_frame_health", "vt_op_arbitrate",
+    "vt_op_stream_conflicts", "vt_op_frame_health", "vt_op_arbitrate", "vt_op_movers",
 ]
 
 _ops = None
@@ -70,6 +70,8 @@ def ops_lib():
                                       c_void_p, c_void_p, c_void_p]
     L.vt_op_frame_health.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]
+    L.vt_op_movers.argtypes = [c_int, POINTER(CFrame), c_void_p, c_int, i32p, c_int, i32p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.vt_op_arbitrate.argtypes = [c_int, fp, fp, POINTER(CFrame), c_void_p, c_int, c_void_p, i32p, i32p, c_int, c_int, c_void_p,
                                   c_int, c_int, c_int, c_int, fp, c_float, i32p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]
@@ -560,6 +562,54 @@ def op_frame_health(frames, states, on=1, period=1, cell=0, still_run=3, flat_q=
     return dict(states=st, thumbs=th, hist=hi, records=rec, counts=cnt, accs=accs, heads=heads, host_records=hrec)
 
 
+# the moving regions' arrays (csrc/k_movers.hpp: MoverRec 256 bytes and MoverCount 16 bytes by stream, MoverHead 32 bytes by slot)
+MOVERS_BOX_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("area", "<i4"), ("label", "<i4")])
+MOVERS_REC_DTYPE = np.dtype([("status", "<i4"), ("frames_done", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"), ("n", "<i4"),
+                             ("moving", "<i4"), ("kept", "<i4"), ("components", "<i4"), ("own_cells", "<i4"), ("own_kept", "<i4"),
+                             ("still", "<i4"), ("has_bg", "<i4"), ("pW", "<i4"), ("pH", "<i4"), ("pc", "<i4"),
+                             ("box", MOVERS_BOX_DTYPE, 8)])
+MOVERS_COUNT_DTYPE = np.dtype([("evaluated", "<i4"), ("listed", "<i4"), ("reserved", "<i4", 2)])
+MOVERS_HEAD_DTYPE = np.dtype([("status", "<i4"), ("stream", "<i4"), ("frames_done", "<i4"), ("c", "<i4"), ("Wg", "<i4"), ("Hg", "<i4"),
+                              ("reserved", "<i4", 2)])
+assert MOVERS_REC_DTYPE.itemsize == 256 and MOVERS_HEAD_DTYPE.itemsize == 32 and MOVERS_COUNT_DTYPE.itemsize == 16
+
+
+def movers_shape(learn, min_nb, max_n):
+    """the policy word that carries "movers_learn", "movers_min_nb" and "movers_max" (csrc/vt_feature_keys.hpp: MV_SHAPE)"""
+    return int(learn) | int(min_nb) << 4 | int(max_n) << 8
+
+
+def op_movers(frames, states, on=1, period=1, cell=0, thr=96, min_area=4, global_pm=400, learn=4, min_nb=3, max_n=4, max_cells=65536,
+              slot_stream=None, bg=None, mask=None, records=None, counts=None, device_frames=True, host_records=None, shape=None,
+              device=0):
+    """vt_op_movers: the launches of k_movers.hip on given operands, nothing else. frames: CFrame per slot with DEVICE planes;
+    states: snapshot.STATE records by stream; slot_stream [n]: slot -> stream (None: the identity). The store to start from: bg
+    [n_streams, max_cells] uint16 and mask [n_streams, max_cells] uint8 (None: 0xff bytes - what no launch stores shows),
+    records [n_streams] MOVERS_REC_DTYPE and counts [n_streams] MOVERS_COUNT_DTYPE (None: zeros - no background);
+    host_records: what the pinned mirror holds before (None: the mirror is null); shape: the raw policy word instead of learn,
+    min_nb and max_n. -> dict(states, bg, thumbs, mask, labels [n_streams, max_cells] int32, exts [n_streams, 4, max_cells]
+    int32 = i0, i1, j1, area, accs [n_streams, 4] int32 = moving, kept - 0xff bytes where no launch stored -, heads [n]
+    MOVERS_HEAD_DTYPE, records, counts, host_records) as they came back; feed bg, mask, records and counts to the next call"""
+    n, arr = _frames(frames)
+    st = _start(states, STATE)
+    ns = len(st)
+    smap, _ = _maps(n, slot_stream)
+    b, m = _start(bg, np.uint16, (ns, max_cells), 0xff), _start(mask, np.uint8, (ns, max_cells), 0xff)
+    rec, cnt = _start(records, MOVERS_REC_DTYPE, (ns,)), _start(counts, MOVERS_COUNT_DTYPE, (ns,))
+    hrec = _mirror(host_records, MOVERS_REC_DTYPE, ns)
+    pol = np.array([on, period, cell, thr, min_area, global_pm, movers_shape(learn, min_nb, max_n) if shape is None else shape,
+                    max_cells], np.int32)
+    thumbs = np.empty((ns, max_cells), np.uint16)
+    labels, exts = np.empty((ns, max_cells), np.int32), np.empty((ns, 4, max_cells), np.int32)
+    accs = np.empty((ns, 4), np.int32)
+    heads = np.empty(n, MOVERS_HEAD_DTYPE)
+    _check_op(ops_lib().vt_op_movers(
+        device, arr, _vp(st), ns, _opt(smap, _i32), n, _i32(pol), 1 if device_frames else 0, _vp(b), _vp(thumbs), _vp(m), _vp(labels),
+        _vp(exts), _vp(accs), _vp(heads), _vp(rec), _vp(cnt), _opt(hrec, _vp)))
+    return dict(states=st, bg=b, thumbs=thumbs, mask=m, labels=labels, exts=exts, accs=accs, heads=heads, records=rec, counts=cnt,
+                host_records=hrec)
+
+
 # the peak arbitration's records (csrc/k_arbitrate.hpp: ArbRec 176 bytes and ArbCount 8 bytes, both by stream)
 ARBITRATE_PEAK_DTYPE = np.dtype([("cell", "<i4"), ("status", "<i4"), ("score", "<f4"), ("resp", "<f4"), ("similarity", "<f4"),
                                  ("reserved", "<i4"), ("box", "<f4", 4)])
@@ -666,4 +716,4 @@ def op_result_overlay(frames, results, flags=7, thickness=3, size=15, scale=2, l
     return st
 
 
-__all__ = [n for n in dir() if n.startswith("op_") or n.endswith("_DTYPE")] + ["OPS_LIB_PATH", "OPS_EXPORTS", "ops_lib", "_check_op"]
+__all__ = [n for n in dir() if n.startswith("op_") or n.endswith("_DTYPE")] + ["OPS_LIB_PATH", "OPS_EXPORTS", "ops_lib", "_check_op", "movers_shape"]

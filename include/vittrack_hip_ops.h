@@ -251,6 +251,56 @@ int vt_op_camera_motion(int device_id, const vt_frame* frames, void* states, int
 int vt_op_frame_health(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
                        const int32_t* policy, int device_frames, uint16_t* thumbs, int64_t* accs, int32_t* hist, void* heads,
                        void* records, void* counts, void* host_records);
+/* The launches of the moving regions (csrc/k_movers.hip; DESIGN.md section 3 "Moving regions") on caller-supplied operands,
+ * and nothing else: per stream a background model of the frame thumbnail's cells, the cells that left it, and the largest
+ * 8-connected groups of them as boxes in source pixels. No engine pass carries the launches yet: no "movers*" key of
+ * vt_group_set_tuning exists, the names below are those of the key table the hook validates with. THE RULE, to the bit:
+ *   POLICY: 8 int32 = on (0 / 1), period (1..1,000,000), cell (0 = automatic, or 4, 8, 16, 32), thr (0..4080), min_area
+ * (1..262,144), global_pm (0..1000 per mille; 1000: never), shape = learn (0..8) | min_nb (1..9) << 4 | max_n (1..8) << 8,
+ * max_cells (4,096..262,144 cells per stream) - the bounds of the table kMoverKeys of csrc/vt_feature_keys.hpp, which names
+ * them "movers", "movers_period", "movers_cell", "movers_thr", "movers_min_area", "movers_global_pm", "movers_learn",
+ * "movers_min_nb", "movers_max" (three four-bit fields of one word) and "movers_max_cells" (defaults 0, 1, 0, 96, 4, 400,
+ * 4, 3, 4, 65,536). A shape word with a bit set beside its three fields is refused.
+ *   SLOTS, STATUS 0, 4, 2: those of vt_op_frame_health above, unchanged - the first slot that names a stream works for it (a
+ * later one: header status -1); not due, no whole device frame, no geometry (Wg = W / c, Hg = H / c, Wg, Hg >= 8, Wg * Hg <=
+ * max_cells). 5: the stream has no background, or one of another W, H or c. 1: evaluated. Statuses 4 and 2 write the record
+ * with zeros (c, Wg, Hg as far as they exist) and clear has_bg and still. frames_done is the state's value as the hook receives it.
+ *   THUMBNAIL t[j][i], uint16 <= 4080: the cell of vt_op_camera_motion above. Statuses 1 and 5 store it.
+ *   BACKGROUND bg[j][i], uint16 in sixteenths of t (16 * 4080 = 65,280 fits). Status 5: bg = 16 t, every mask byte 0, nothing
+ * else is evaluated: the record carries c, Wg, Hg and zeros, still = 0. Status 1: d = 16 t - bg (int32, signed), then bg += d
+ * >> learn, where >> is the ARITHMETIC shift of the signed value, floor(d / 2^learn) - a negative d of small size moves bg by
+ * -1, never by 0; learn = 0 is plain frame differencing.
+ *   MASK: a cell is moving iff |d| > 16 thr, with the d of the background from BEFORE the update.
+ *   CLEAN-UP: a cell is kept iff it is moving and at least min_nb of the nine cells of its 3x3 neighbourhood, itself
+ * included, are moving; cells outside the grid count as not moving. mask byte: 0, 1 moving, 2 kept.
+ *   GLOBAL CHANGE: moving * 1000 > global_pm * Wg * Hg (int64): the record's status is 6, n = 0, components = 0; moving, kept,
+ * own_cells and own_kept are written; still = 0.
+ *   COMPONENTS (status 1): 8-connectivity over the kept cells. A component's label is the least row-major index j * Wg + i
+ * of its cells. Per component its area in cells and the inclusive cell bounding box i0..i1, j0..j1. components = their number,
+ * before the two filters below.
+ *   LIST: components with area < min_area are dropped; of the rest up to max_n, by area descending, then label ascending.
+ * Entry k: x = i0 c, y = j0 c, w = (i1 - i0 + 1) c, h = (j1 - j0 + 1) c (source pixels, int32; an evaluated frame is whole,
+ * so the origin of a windowed descriptor is never added: such a frame is status 4), area, label. Entries from n on are zero.
+ *   OWN BOX, statuses 1 and 6, from the state's committed box x, y, w, h (binary32 - the one place of the rule that is not
+ * integer: each product below is by the power of two 1 / c, exact): x0 = floor(x / c), y0 = floor(y / c), x1 = ceil((x + w) /
+ * c), y1 = ceil((y + h) / c), with x + w and y + h binary32 sums, each clipped to 0..Wg or 0..Hg; x1 >= x0 and y1 >= y0
+ * forced. own_cells = (x1 - x0)(y1 - y0); own_kept = the kept cells with x0 <= i < x1, y0 <= j < y1.
+ *   STILL: status 1: still = (own_kept == 0 and kept > 0) ? min(still + 1, 1 << 30) : 0; statuses 5 and 6: 0.
+ *   COUNTERS per stream, never rewound: evaluated (status 1 or 6), listed (the sum of their n).
+ *   RECORD, per stream, 256 bytes of int32: status, frames_done, c, Wg, Hg, n, moving, kept, components, own_cells, own_kept,
+ * still; has_bg, pW, pH, pc (the background's bookkeeping); eight entries of x, y, w, h, area, label.
+ *   OPERANDS: frames: [n] by slot with DEVICE planes (read only); states: [n_streams] raw 88-byte stream states
+ * (initialized, frames_done and box are read; they come back as they went in); slot_stream: [n] slot -> stream or null (the
+ * identity). In and out: bg [n_streams][max_cells] uint16, mask [n_streams][max_cells] bytes, records [n_streams] of 256
+ * bytes, counts [n_streams] of 16 bytes (evaluated, listed, two reserved words). Out: thumbs [n_streams][max_cells] uint16,
+ * labels [n_streams][max_cells] int32 (status 1 without a global change: -1, or the cell's component), exts
+ * [n_streams][4][max_cells] int32 (at a component's label: i0, i1, j1, area), accs [n_streams][4] int32 (moving, kept), heads
+ * [n] of 32 bytes (status, stream, frames_done, c, Wg, Hg, 0, 0); every byte of the five no launch stored is 0xff.
+ * host_records (nullable, in and out): the [n_streams] pinned mirror of the records. All ten device arrays sit between guard
+ * bands; a changed guard byte is VT_ERR_HIP. A policy or map out of range, n > 1024: VT_ERR_INVALID_ARG. */
+int vt_op_movers(int device_id, const vt_frame* frames, void* states, int n_streams, const int32_t* slot_stream, int n,
+                 const int32_t* policy, int device_frames, uint16_t* bg, uint16_t* thumbs, uint8_t* mask, int32_t* labels, int32_t* exts,
+                 int32_t* accs, void* heads, void* records, void* counts, void* host_records);
 /* The one launch of the stream conflicts (csrc/k_conflicts.hip; the rule: include/vittrack_hip.h above the "conflicts*" keys,
  * DESIGN.md section 3 "Stream conflicts") on caller-supplied operands, and nothing else. states: [n_streams] raw 88-byte
  * stream states (box, initialized, frames_done, window_miss are read); results: [n] by slot; slot_stream: [n] slot -> stream
